@@ -15,11 +15,17 @@ Launched without a rendezvous environment (`python bench.py --gpus N`, N > 1) th
 starts its own N ranks as a `torch.distributed.run` child BEFORE anything touches the GPU
 and exits with the child's code.
 
-Timing: after `--prime` untimed steps (clocks, caches, allocator) and the W warm-up steps, the
-block of EXACTLY K steps is timed `--repeats` times, each bracketed by barrier + synchronize on
-both sides; `value` / `ms_per_step` are the MEDIAN block (all blocks are listed in
-`block_ms_per_step`).  A single 20-step block is 1 ms of device work: its time is mostly the
-fences and the launch ramp, which is why the median of many blocks is reported.
+Timing: after `--prime` untimed steps (clocks, caches, allocator) and the W warm-up steps, ONE
+block of exactly K steps is timed, bracketed by barrier + synchronize on both sides; `value` /
+`ms_per_step` come from that block.  `--repeats R` times R such blocks and reports the MEDIAN one
+(all blocks are listed in `block_ms_per_step`; `--repeats 0` picks about 3000 steps in all): a
+single 20-step block is 1 ms of device work, so its time is mostly the fences and the launch ramp.
+
+A plain run does only what the headline needs.  `--full` adds the rest: the fp32 parity-mode leg,
+the torch-CPU baseline and the per-kernel roofline leg (`--cfg3` adds the cfg3 key and implies
+`--full`).  `--dump-outputs DIR` writes what the timed path left after its last timed step (head
+weight, its AdamW moments, that step's scalars) as DIR/<name>.npy; inputs are seeded, so two builds
+run with the same arguments can be compared array by array.
 """
 import argparse
 import contextlib
@@ -48,20 +54,29 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
-    ap.add_argument("--repeats", type=int, default=0, help="timed K-step blocks (0 = auto: about 3000 steps in all, 3..50 blocks)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed K-step blocks, the median one reported (default 1: exactly K timed steps; 0 = auto: about 3000 steps "
+                         "in all, 3..50 blocks; the --full fp32 leg defaults to auto)")
     ap.add_argument("--prime", type=int, default=300, help="untimed steps before the warm-up (clock ramp, caches)")
     ap.add_argument("--precision", default=os.environ.get("UMLH_PRECISION", "bf16"), choices=["fp32", "bf16"],
                     help="bf16 = BASELINE config 2 (headline); fp32 = exact-parity mode")
     ap.add_argument("--force-dp-path", action="store_true", help="N=1 only: run the data-parallel split path (grad -> [all-reduce] -> update) to price it")
     ap.add_argument("--dp-host-loop", action="store_true", help="N>1: per-step Python stepping (torch.distributed all_reduce) instead of the C-level RCCL loop")
-    ap.add_argument("--no-fp32-leg", action="store_true", help="skip the additional fp32 parity-mode measurement")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the fp32 parity-mode leg, the torch-CPU baseline and the "
+                         "per-kernel roofline leg (off by default)")
+    ap.add_argument("--no-fp32-leg", action="store_true", help="--full: skip the additional fp32 parity-mode measurement")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the torch-CPU baseline")
     ap.add_argument("--cfg3", action="store_true", help="N=1: also time BASELINE configs[2] (2-layer head 1024 -> 3200, C=1000, 4096+4096 rows) "
-                                                       "in both precision modes and report it under the extra key 'cfg3' (off by default)")
+                                                       "in both precision modes and report it under the extra key 'cfg3' (implies --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32)")
     ap.add_argument("--order-rng", default="device", choices=["device", "torch-cpu"],
                     help="epoch permutations drawn on the GPU (default) or by the reference-identical CPU sampler")
     ap.add_argument("--block", type=int, default=25, help="steps per umlh_train_steps call (host prepares the next block meanwhile)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    args.full = args.full or args.cfg3
+    return args
 
 
 def self_launch(args):
@@ -97,6 +112,18 @@ def latest_pmc():
         return json.load(open(files[-1]))["kernels"], os.path.relpath(files[-1], ROOT)
     except Exception:
         return None, None
+
+
+def dump_outputs(out_dir, model, optimizer, last_scalars):
+    """What a caller of the timed path holds after its last step: the head weight and its AdamW moments (the fused step
+    updates them in place) and that step's scalar row (losses, accuracies, gradient scales), as float32 .npy files."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    st = optimizer.state_for(model.head.weight)
+    arrays = {"head_weight": model.head.weight.data, "head_exp_avg": st["exp_avg"], "head_exp_avg_sq": st["exp_avg_sq"],
+              "step_scalars": last_scalars}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 def main():
@@ -139,7 +166,11 @@ def main():
     from engine.tools.utils import set_random_seed
     from finetune import _RowSource, _draw_block
 
-    repeats = args.repeats if args.repeats > 0 else max(3, min(50, -(-3000 // max(1, args.steps))))
+    def n_blocks(steps, default):
+        r = default if args.repeats is None else args.repeats
+        return r if r > 0 else max(3, min(50, -(-3000 // max(1, steps))))
+
+    repeats = n_blocks(args.steps, 1)
 
     # ---- synthetic, HBM-resident workload (image rows sharded over ranks, text replicated) ----
     set_random_seed(0)
@@ -167,9 +198,10 @@ def main():
             dist.barrier()
             torch.cuda.synchronize(dev)
 
-    def measure(precision, steps, warmup, prime):
+    def measure(precision, steps, warmup, prime, repeats, roofline=False, dump_dir=None):
         """`prime` + `warmup` untimed steps, then `repeats` timed blocks of `steps` steps, each bracketed by
-        barrier + synchronize; returns the median block."""
+        barrier + synchronize; returns the median block.  `dump_dir`: write the timed path's outputs there;
+        `roofline`: then time 50 instrumented steps per kernel (--full)."""
         engine = model.fused_engine(optimizer, BATCH, BATCH, precision=precision)
         stepper = umlh.DataParallelStepper(engine)
         stepper.broadcast_parameters([model.head.weight.data])
@@ -302,6 +334,14 @@ def main():
             raise SystemExit(f"[rank {rank}] bench: {len(slow)} of {repeats} timed blocks took more than 20x the median block "
                              f"({max(slow) / steps * 1e3:.3f} vs {dt / steps * 1e3:.4f} ms/step): stalled waits or a starved device; "
                              "the run is invalid, no result line is printed")
+        if dump_dir and rank == 0:
+            dump_outputs(dump_dir, model, optimizer, scal[cursor["k"] - 1])
+        result = {"value": rows / dt, "dt": dt, "rows": rows, "ms_per_step": dt / steps * 1e3,
+                  "block_ms_per_step": [round(b[0] / steps * 1e3, 4) for b in blocks],
+                  "host_enqueue_ms_per_step": statistics.median(enq) / steps * 1e3, "final": final, "roofline": None,
+                  "c_level_dp": bool(c_level_dp)}
+        if not roofline:
+            return result
         # roofline leg: per-kernel device time from HIP events recorded on the step's stream (RAW intervals: each
         # carries the cost of its two marker packets, so they read a few hundred ns above rocprofv3's kernel trace)
         engine.profile(True)
@@ -356,16 +396,15 @@ def main():
             # second roof of the forward's present decomposition: every CU streams all of W from L2 for its 32 rows
             l2_bytes = (8192 / 32) * 1024 * 512 * 2
             roof["l2_stream_bound_ms"] = round(l2_bytes / L2_BW * 1e3, 5)
-        return {"value": rows / dt, "dt": dt, "rows": rows, "ms_per_step": dt / steps * 1e3,
-                "block_ms_per_step": [round(b[0] / steps * 1e3, 4) for b in blocks],
-                "host_enqueue_ms_per_step": statistics.median(enq) / steps * 1e3, "final": final, "roofline": roof,
-                "c_level_dp": bool(c_level_dp)}
+        result["roofline"] = roof
+        return result
 
-    head = measure(args.precision, args.steps, args.warmup, args.prime)
+    head = measure(args.precision, args.steps, args.warmup, args.prime, repeats, roofline=args.full, dump_dir=args.dump_outputs)
     other = None
-    if args.precision == "bf16" and not args.no_fp32_leg:
+    if args.full and args.precision == "bf16" and not args.no_fp32_leg:
         # the exact-parity fp32 mode on the same workload (fewer steps: it is ~5x slower)
-        other = measure("fp32", max(10, args.steps // 4), max(3, args.warmup // 4), max(10, args.prime // 4))
+        fp32_steps = max(10, args.steps // 4)
+        other = measure("fp32", fp32_steps, max(3, args.warmup // 4), max(10, args.prime // 4), n_blocks(fp32_steps, 0), roofline=True)
     value, roofline, final = head["value"], head["roofline"], head["final"]
     if other is not None:   # the parity mode's figures as scalars next to the headline's (1e-4 logits/loss parity lives here)
         roofline.update({"fp32_value": round(other["value"], 1), "fp32_ms_per_step": round(other["ms_per_step"], 4),
@@ -376,7 +415,7 @@ def main():
                          "fp32_step_issued_frac_of_bf16_roof": other["roofline"].get("step_issued_frac_of_bf16_roof")})
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import torch_cpu_loop as cpu_loop
         n_sub = 32768
         xi, yi = x_img[:n_sub].cpu(), y_img[:n_sub].cpu()
@@ -408,7 +447,8 @@ def main():
                           "parallelism": f"dp{world}" + (" (REHEARSAL: ranks share GPUs, gloo all-reduce -- not a measurement)" if rehearsal else ""),
                           "dp_stepping": (("c-level peer-to-peer (umlh_p2p)" if os.environ.get("UMLH_DP_P2P", "0") == "1" else "c-level rccl") if head["c_level_dp"] else "python per step") if dp_path else "single gpu",
                           "precision_mode": args.precision, "order_rng": args.order_rng, "steps_per_call": args.block,
-                          "timing": f"median of {repeats} blocks of {args.steps} steps after {args.prime}+{args.warmup} untimed steps; "
+                          "timing": (f"one block of {args.steps} steps" if repeats == 1 else f"median of {repeats} blocks of {args.steps} steps")
+                                    + f" after {args.prime}+{args.warmup} untimed steps; "
                                     "each block draws and marshals the next block's index vectors after enqueuing its own steps"},
                "block_ms_per_step": head["block_ms_per_step"],
                "final_loss": {"img": round(final[0], 4), "txt": round(final[1], 4)},

@@ -5,18 +5,18 @@ tag=$1
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $root
 o=gpurun_out
-python bench.py > $o/${tag}_bench.log 2>&1 || { tail -5 $o/${tag}_bench.log; exit 1; }
+python bench.py --full > $o/${tag}_bench.log 2>&1 || { tail -5 $o/${tag}_bench.log; exit 1; }
 tail -1 $o/${tag}_bench.log > $o/${tag}_bench.json
 python bench.py --gpus 1 --steps 20 --warmup 5 > $o/${tag}_bench_driver_args.log 2>&1; tail -1 $o/${tag}_bench_driver_args.log > $o/${tag}_bench_driver_args.json
-python bench.py --force-dp-path --no-cpu-baseline --no-fp32-leg > $o/${tag}_force_dp.log 2>&1; tail -1 $o/${tag}_force_dp.log > $o/${tag}_bench_force_dp_c_loop.json
-python bench.py --force-dp-path --dp-host-loop --no-cpu-baseline --no-fp32-leg > $o/${tag}_force_dp_host.log 2>&1; tail -1 $o/${tag}_force_dp_host.log > $o/${tag}_bench_force_dp_host_loop.json
+python bench.py --full --force-dp-path --no-cpu-baseline --no-fp32-leg > $o/${tag}_force_dp.log 2>&1; tail -1 $o/${tag}_force_dp.log > $o/${tag}_bench_force_dp_c_loop.json
+python bench.py --full --force-dp-path --dp-host-loop --no-cpu-baseline --no-fp32-leg > $o/${tag}_force_dp_host.log 2>&1; tail -1 $o/${tag}_force_dp_host.log > $o/${tag}_bench_force_dp_host_loop.json
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $root/$o/${tag}_kt -o kt -- python3 $root/bench.py --steps 200 --warmup 20 --no-cpu-baseline > $root/$o/${tag}_kt.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $root/$o/${tag}_kt -o kt -- python3 $root/bench.py --full --steps 200 --warmup 20 --no-cpu-baseline > $root/$o/${tag}_kt.log 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $root/$o/${tag}_pmc_f -o pmc -- python3 $root/bench.py --steps 20 --warmup 3 --repeats 3 --prime 20 --no-cpu-baseline --no-fp32-leg > $root/$o/${tag}_pmc_f.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $root/$o/${tag}_pmc_w -o pmc -- python3 $root/bench.py --steps 20 --warmup 3 --repeats 3 --prime 20 --no-cpu-baseline --no-fp32-leg > $root/$o/${tag}_pmc_w.log 2>&1
 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE GRBM_GUI_ACTIVE --output-format csv -d $root/$o/${tag}_pmc_sq -o pmc -- python3 $root/bench.py --steps 20 --warmup 3 --repeats 3 --prime 20 --no-cpu-baseline --no-fp32-leg > $root/$o/${tag}_pmc_sq.log 2>&1
 cd $root
-python scripts/summarize_rocprof.py $(dirname $(find $o/${tag}_kt -name "kt_kernel_stats.csv" | head -1)) kt $o/${tag}_kernel_stats.md "Command: rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline (bf16 headline + fp32 parity leg; cfg2; MI355X; scripts/profile_round2.sh)" > /dev/null
+python scripts/summarize_rocprof.py $(dirname $(find $o/${tag}_kt -name "kt_kernel_stats.csv" | head -1)) kt $o/${tag}_kernel_stats.md "Command: rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 200 --warmup 20 --no-cpu-baseline (bf16 headline + fp32 parity leg; cfg2; MI355X; scripts/profile_round2.sh)" > /dev/null
 python scripts/make_sq_json.py $(find $o/${tag}_pmc_sq -name "*counter_collection.csv" | head -1) $o/${tag}_bf16_sq.json > /dev/null
 python scripts/make_pmc_json.py $(find $o/${tag}_pmc_f -name "*counter_collection.csv" | head -1) $(find $o/${tag}_pmc_w -name "*counter_collection.csv" | head -1) $o/${tag}_bf16_pmc.json > /dev/null
 # micro step: per-phase stamps, step time, sweeps
@@ -48,9 +48,9 @@ echo "== UMLH_BF16_FWD2D=1 (fwd_ce_bf16_q)" > $o/${tag}_fwd2d_stamps.txt
 UMLH_BF16_FWD2D=1 python scripts/fwd_stamps.py >> $o/${tag}_fwd2d_stamps.txt 2>&1
 echo "== default (fwd_ce_bf16)" >> $o/${tag}_fwd2d_stamps.txt
 UMLH_BF16_FWD2D=0 python scripts/fwd_stamps.py >> $o/${tag}_fwd2d_stamps.txt 2>&1
-UMLH_BF16_FWD2D=1 python bench.py --no-cpu-baseline --no-fp32-leg 2>/dev/null | tail -1 > $o/${tag}_bench_fwd2d_on.json
-UMLH_WT=0 python bench.py --no-cpu-baseline 2>/dev/null | tail -1 > $o/${tag}_bench_plain_stores.json
-UMLH_BF16_FUSE=0 python bench.py --no-cpu-baseline --no-fp32-leg 2>/dev/null | tail -1 > $o/${tag}_bench_two_launches.json
-UMLH_BF16_FUSE=1 python bench.py --no-cpu-baseline --no-fp32-leg 2>/dev/null | tail -1 > $o/${tag}_bench_fwd_dw_one_launch.json
+UMLH_BF16_FWD2D=1 python bench.py --full --no-cpu-baseline --no-fp32-leg 2>/dev/null | tail -1 > $o/${tag}_bench_fwd2d_on.json
+UMLH_WT=0 python bench.py --full --no-cpu-baseline 2>/dev/null | tail -1 > $o/${tag}_bench_plain_stores.json
+UMLH_BF16_FUSE=0 python bench.py --full --no-cpu-baseline --no-fp32-leg 2>/dev/null | tail -1 > $o/${tag}_bench_two_launches.json
+UMLH_BF16_FUSE=1 python bench.py --full --no-cpu-baseline --no-fp32-leg 2>/dev/null | tail -1 > $o/${tag}_bench_fwd_dw_one_launch.json
 python scripts/step_timeline.py 2>/dev/null > $o/${tag}_step_timeline.txt
 tail -2 $o/${tag}_bench.json | cut -c1-600

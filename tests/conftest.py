@@ -21,6 +21,26 @@ def golden_dir():
     return GOLDEN
 
 
+class Golden(dict):
+    """The arrays of one fixture by name; ``files`` lists the names, as numpy's NpzFile does."""
+
+    @property
+    def files(self):
+        return list(self)
+
+
 def load_golden(name):
+    """tests/golden/<name>.npz, merged with <name>.part1.npz, <name>.part2.npz, ... when a fixture is stored in parts
+    (every committed file stays under 1 MiB)."""
     import numpy as np
-    return np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
+    g = Golden()
+    paths, k = [os.path.join(GOLDEN, name + ".npz")], 1
+    while os.path.exists(os.path.join(GOLDEN, f"{name}.part{k}.npz")):
+        paths.append(os.path.join(GOLDEN, f"{name}.part{k}.npz"))
+        k += 1
+    for p in paths:
+        with np.load(p, allow_pickle=False) as z:
+            for key in z.files:
+                assert key not in g, f"{p}: array {key!r} also stored in another part of fixture {name!r}"
+                g[key] = z[key]
+    return g
