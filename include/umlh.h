@@ -59,7 +59,12 @@ extern "C" {
 #define UMLH_PREC_FP32 0   /* fp32 operands, fp32 results: the parity mode (logits / loss 1e-4).  The fused step forms its products
                             * from three-way bf16 splits of both operands on the bf16 MFMA (six exact piece products per product, fp32
                             * accumulation; what is dropped is 2^-24 of a product rms, 2^-20 worst case: as accurate against float64 as the fp32 MFMA chain) -- or, with UMLH_F32_X3=0 in the environment, on
-                            * the f32-input MFMA as in ABI <= 3.  umlh_logits / umlh_gemm_f32 always use the f32-input MFMA. */
+                            * the f32-input MFMA as in ABI <= 3.  umlh_logits, umlh_project and umlh_gemm_f32 use the same x3 form on the
+                            * 128x128 gemm_f32 tile (chosen once its grid reaches 768 workgroups, split-K slabs counted) and in dw_f32x3;
+                            * smaller grids and the dense encoder GEMMs use the f32-input MFMA.  Both forms meet the same accuracy
+                            * criterion against float64 (tests/_gemm_ref.py).  So a row's logits can differ in the last bits with the
+                            * batch size.  An infinite operand on an x3 path gives NaN, not +-inf (its mid piece is inf - inf): a
+                            * non-finite input still never gives a finite output, and NaN stays NaN. */
 #define UMLH_PREC_BF16 1   /* bf16 operands, fp32 accumulate: the throughput mode         */
 
 typedef struct umlh_handle_s* umlh_handle_t;
@@ -356,7 +361,11 @@ int  umlh_infonce_backward(const float* pred_hat, const float* target_hat, const
 
 /* out[m][n] = alpha * sum_k A(m,k) B(n,k).  ta = 0: A[m*lda + k], rows optionally gathered by a_rows[m];
  * ta = 1: A[k*lda + m].  tb = 0: B[n*ldb + k];  tb = 1: B[k*ldb + n], rows optionally gathered by k_rows[k].
- * (ta,tb) in {(0,0),(0,1),(1,1)}: y = x W^T, dx = dy W, dW = dy^T x.  fp32 MFMA (exact fp32 products).
+ * (ta,tb) in {(0,0),(0,1),(1,1)}: y = x W^T, dx = dy W, dW = dy^T x; other pairs and strides shorter than a row
+ * (lda < (ta ? M : K), ldb < (tb ? N : K), ldo < N) are UMLH_E_INVALID.  Only the [M, N] window of out (row stride ldo)
+ * is written.  Products: the fp32 MFMA, or the x3 form of UMLH_PREC_FP32 (three bf16 pieces per operand) on large grids
+ * (the 128x128 tile at >= 768 workgroups, and the dW tile); both meet the same criterion against float64, and an
+ * infinite operand on an x3 path yields NaN rather than +-inf.
  * splits > 1: split-K over `splits` slabs of M*ldo floats in `slabs` (caller scratch), summed into out in slab
  * order -- the encoder's GEMMs have few output tiles and a long K, so one tile per CU is latency-bound. */
 int  umlh_gemm_f32(const float* A, const float* B, float* out, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldb,

@@ -57,6 +57,20 @@ def test_encoder_ops_validate_arguments_before_touching_the_gpu(lib):
     assert lib.umlh_gemm_f32(None, None, None, 4, 4, 4, 4, 4, 4, 0, 0, None, None, C.c_float(1.0), 1, None, None) != 0
     assert b"umlh_gemm_f32" in lib.umlh_last_error()
     assert lib.umlh_gemm_f32(fake, fake, fake, 4, 4, 4, 4, 4, 4, 0, 0, None, None, C.c_float(1.0), 3, None, None) != 0   # splits without slabs
+    # (ta, tb) = (1, 0) has no kernel, and a stride shorter than the row it spans would read or write across rows: rejected up
+    # front as UMLH_E_INVALID (not a HIP error from the launcher)
+    E_INVALID = -1
+    gemm = lambda M, N, K, lda, ldb, ldo, ta, tb: lib.umlh_gemm_f32(fake, fake, fake, M, N, K, lda, ldb, ldo, ta, tb, None, None,
+                                                                     C.c_float(1.0), 1, None, None)
+    for args, what in (((8, 6, 5, 8, 6, 6, 1, 0), b"(ta, tb) = (1, 0)"),
+                       ((8, 6, 5, 5, 5, 5, 0, 0), b"ldo=5"),          # ldo < N
+                       ((8, 6, 5, 4, 5, 6, 0, 0), b"lda=4"),          # ta = 0: lda < K
+                       ((8, 6, 5, 7, 5, 6, 1, 1), b"lda=7"),          # ta = 1: lda < M
+                       ((8, 6, 5, 5, 4, 6, 0, 0), b"ldb=4"),          # tb = 0: ldb < K
+                       ((8, 6, 5, 5, 5, 6, 0, 1), b"ldb=5")):         # tb = 1: ldb < N
+        assert gemm(*args) == E_INVALID, args
+        msg = lib.umlh_last_error()
+        assert b"umlh_gemm_f32" in msg and what in msg, (args, msg)
     rc = lib.umlh_attention_forward(fake, None, 200, 2, 20, 5, C.c_float(0.0), C.c_uint64(0), fake, fake, None)
     assert rc != 0 and b"envelope" in lib.umlh_last_error()
     rc = lib.umlh_attention_backward(fake, None, fake, fake, 16, 2, 330, 5, C.c_float(0.0), C.c_uint64(0), fake, None)   # head dim 66

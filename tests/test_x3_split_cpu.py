@@ -63,3 +63,32 @@ def test_six_piece_products_track_the_exact_product_at_the_fp32_rounding_level()
     fp32 = (X @ W.T).astype(np.float64)
     assert np.abs(dot - ref).max() <= max(np.abs(fp32 - ref).max(), 2e-8) * 1.5
     assert 100.0 * np.abs(dot - ref).max() < 1e-5                        # logits at scale 100: far inside the 1e-4 the mode carries
+
+
+def test_nonfinite_values_split_into_a_nonfinite_hi_and_a_nan_residual():
+    """Documented behaviour of the x3 form on non-finite operands (include/umlh.h, UMLH_PREC_FP32): the split of +-inf is hi = +-inf
+    and a NaN mid (inf - inf), so a product with an infinite operand comes out NaN where float64 and the fp32 MFMA give +-inf; the
+    kernels are not changed to special-case it.  What must hold: a non-finite input never splits into finite pieces only, and a
+    NaN -- including the low-payload 0x7f800001, whose truncated hi piece is +inf -- always leaves a NaN piece."""
+    x = np.asarray([np.inf, -np.inf], dtype=np.float32)
+    with np.errstate(invalid="ignore"):
+        hi, mid, lo = split3(x)
+    assert (hi == x).all()
+    assert np.isnan(mid).all() and np.isnan(lo).all()
+    nans = np.asarray([0x7FC00000, 0xFFC00000, 0x7F800001, 0xFF800001, 0x7FFFFFFF, 0x7F810000], dtype=np.uint32).view(np.float32)
+    with np.errstate(invalid="ignore"):
+        pieces = split3(nans)
+    assert np.isinf(pieces[0][2]) and pieces[0][2] > 0          # 0x7f800001: hi is +inf ...
+    assert np.isinf(pieces[0][3]) and pieces[0][3] < 0
+    for i in range(len(nans)):                                   # ... and every NaN leaves a NaN among its pieces
+        assert any(np.isnan(p[i]) for p in pieces), hex(int(nans.view(np.uint32)[i]))
+    # hence a six-piece product with a non-finite operand is never finite, and with a NaN operand it is NaN
+    with np.errstate(invalid="ignore"):
+        ws = split3(np.asarray([1.5, 0.0, -3.25], dtype=np.float32))
+        for v in np.concatenate([x, nans]):
+            xs = split3(np.asarray([v], dtype=np.float32))
+            for j in range(3):
+                prod = sum(np.float64(xs[a][0]) * np.float64(ws[b][j]) for a, b in ((2, 0), (0, 2), (1, 1), (1, 0), (0, 1), (0, 0)))
+                assert not np.isfinite(prod)
+                if np.isnan(v):
+                    assert np.isnan(prod)

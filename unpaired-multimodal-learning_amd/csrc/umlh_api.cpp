@@ -746,13 +746,18 @@ int umlh_gemm_f32(const float* A, const float* B, float* out, int32_t M, int32_t
                   int32_t splits, float* slabs, void* stream) {
     if (!A || !B || !out || M < 0 || N < 0 || K < 1 || (ta && a_rows) || (!tb && k_rows) || splits < 1 || (splits > 1 && !slabs))
         return fail(UMLH_E_INVALID, "umlh_gemm_f32: bad arguments");
+    if ((ta == 1 && tb == 0) || ta < 0 || ta > 1 || tb < 0 || tb > 1)
+        return fail(UMLH_E_INVALID, "umlh_gemm_f32: (ta, tb) = (%d, %d) unsupported (supported: (0,0), (0,1), (1,1))", ta, tb);
+    if (lda < (ta ? M : K) || ldb < (tb ? N : K) || ldo < N)
+        return fail(UMLH_E_INVALID, "umlh_gemm_f32: strides shorter than a row (lda=%d ldb=%d ldo=%d for M=%d N=%d K=%d ta=%d tb=%d)",
+                    lda, ldb, ldo, M, N, K, ta, tb);
     GemmArgs g;
     memset(&g, 0, sizeof(g));
     g.A = A; g.B = B; g.a_rows = a_rows; g.k_rows = k_rows;
     g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldo = ldo;
     g.alpha = alpha; g.k_switch = K; g.k_valid1 = K;
     // dense operands and a short K range per workgroup: the latency-oriented kernel (see gemm_enc)
-    const bool dense = !a_rows && !k_rows && !(ta == 1 && tb == 0) && (K + splits - 1) / splits <= 512;
+    const bool dense = !a_rows && !k_rows && (K + splits - 1) / splits <= 512;
     auto launch = dense ? umlh_f32_launch_gemm_enc : umlh_f32_launch_gemm;
     if (splits == 1) {
         g.out = out; g.k_chunk = K; g.slab_stride = 0;
@@ -763,10 +768,7 @@ int umlh_gemm_f32(const float* A, const float* B, float* out, int32_t M, int32_t
     const int ns = (K + chunk - 1) / chunk;
     g.out = slabs; g.k_chunk = chunk; g.slab_stride = (long long)M * ldo;
     HIPCHK(launch(&g, ta, tb, ns, (hipStream_t)stream), "gemm_f32 (split-K)");
-    const long long n = (long long)M * ldo;
-    Epilogue none;
-    memset(&none, 0, sizeof(none));
-    HIPCHK(umlh_enc_launch_reduce_epilogue(slabs, ns, n, n, N, &none, out, (hipStream_t)stream), "split-K reduce");
+    HIPCHK(umlh_enc_launch_reduce_window(slabs, ns, g.slab_stride, M, N, ldo, out, (hipStream_t)stream), "split-K reduce");
     return UMLH_OK;
 }
 

@@ -6,6 +6,8 @@
 extern "C" {
 int umlh_enc_launch_reduce_epilogue(const float* slabs, int ns, long long stride, long long total, int N, const Epilogue* e, float* out,
                                     hipStream_t st);
+// out[m*ldo + n] (m < M, n < N) = sum of ns slabs (slab s at slabs + s*stride, same row stride ldo); columns [N, ldo) untouched
+int umlh_enc_launch_reduce_window(const float* slabs, int ns, long long stride, int M, int N, int ldo, float* out, hipStream_t st);
 int umlh_enc_launch_add_layernorm_fused(const float* x, int ns, long long stride, const Epilogue* e, const float* gamma,
                                         const float* beta, int M, int N, float eps, float* s_out, float* y, float* mean, float* rstd,
                                         hipStream_t st);

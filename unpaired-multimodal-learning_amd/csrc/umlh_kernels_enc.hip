@@ -394,6 +394,16 @@ __global__ __launch_bounds__(256) void reduce_epilogue_kernel(const float* __res
     out[i] = e.on ? epilogue_apply(e, v, i, (int)(i % N)) : v;
 }
 
+// out[m*ldo + n] = sum_s slabs[s*stride + m*ldo + n] over the [M, N] window only: the split-K reduce of umlh_gemm_f32, whose
+// output (and slabs) may be a window of wider rows -- columns [N, ldo) belong to the caller
+__global__ __launch_bounds__(256) void reduce_window_kernel(const float* __restrict__ slabs, int ns, long long stride, int M, int N,
+                                                            int ldo, float* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)M * N) return;
+    const long long o = (i / N) * ldo + i % N;
+    out[o] = slab_sum(slabs + o, stride, ns);
+}
+
 // s = epilogue(sum of ns slabs of x) (bias, dropout, + residual through e.add); y = LayerNorm(s) * gamma + beta; a wave per row
 __global__ __launch_bounds__(256) void add_layernorm_fused_kernel(const float* __restrict__ x, int ns, long long stride, Epilogue e,
                                                                   const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -577,6 +587,12 @@ int umlh_enc_launch_reduce_epilogue(const float* slabs, int ns, long long stride
                                     hipStream_t st) {
     if (total <= 0) return 0;
     hipLaunchKernelGGL(reduce_epilogue_kernel, dim3(blocks_for(total)), dim3(256), 0, st, slabs, ns, stride, total, N, *e, out);
+    return (int)hipGetLastError();
+}
+
+int umlh_enc_launch_reduce_window(const float* slabs, int ns, long long stride, int M, int N, int ldo, float* out, hipStream_t st) {
+    if (M <= 0 || N <= 0) return 0;
+    hipLaunchKernelGGL(reduce_window_kernel, dim3(blocks_for((long long)M * N)), dim3(256), 0, st, slabs, ns, stride, M, N, ldo, out);
     return (int)hipGetLastError();
 }
 

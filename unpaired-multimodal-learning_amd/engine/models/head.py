@@ -257,7 +257,8 @@ class _HeadBase(nn.Module):
         bind["m_scales"], bind["v_scales"] = pk
 
     def _infer_engine(self, rows):
-        for eng in self._engines.values():     # logits / eval always run the exact fp32 kernels
+        for eng in self._engines.values():     # logits / eval run the fp32-mode kernels (fp32 MFMA or, on large grids, the x3
+                                               # form: equally accurate, so logits can differ in the last bits with batch size)
             if eng.precision == "fp32" and min(eng.cfg.max_rows_img, eng.cfg.max_rows_txt) >= rows:
                 return eng
         cap = 256

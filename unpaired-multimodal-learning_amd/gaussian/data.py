@@ -32,6 +32,17 @@ def sample_latent(num_samples, dim, dist_type="gaussian", **kwargs):
     raise ValueError(f"Unsupported distribution type: {dist_type}")
 
 
+def _mm_t(a, b):
+    """a @ b.T in fp32 as one fma chain per output over k = 0, 1, ... (each product exact in float64, one rounding to fp32 per
+    step): the order the reference's tensors were formed in.  torch's CPU matmul picks its summation order by BLAS kernel
+    and SIMD width, so its last bits differ between machines; these matrices are tiny (k <= dim_c)."""
+    a64, b64 = a.to(torch.float64), b.to(torch.float64)
+    acc = torch.zeros(a.shape[0], b.shape[0], dtype=torch.float32)
+    for k in range(a.shape[1]):
+        acc = (acc.to(torch.float64) + a64[:, k:k + 1] * b64[:, k][None, :]).to(torch.float32)
+    return acc
+
+
 def generate_data(cfg):
     """x = A_c (w * theta_c) + A_x theta_x + eps;  y = B_c theta_c + B_y theta_y + eps  (data.py:29-61; draw order kept)."""
     make_reproducible(cfg["seed"])
@@ -48,7 +59,7 @@ def generate_data(cfg):
         theta_c_x = theta_c * att
     else:
         theta_c_x = theta_c
-    return {"x": theta_c_x @ a_c.T + theta_x @ a_x.T + noise_x, "y": theta_c @ b_c.T + theta_y @ b_y.T + noise_y}
+    return {"x": _mm_t(theta_c_x, a_c) + _mm_t(theta_x, a_x) + noise_x, "y": _mm_t(theta_c, b_c) + _mm_t(theta_y, b_y) + noise_y}
 
 
 class UnpairedDataset(Dataset):
