@@ -150,7 +150,7 @@ typedef struct {
 #define UMLH_N_SCALARS    12
 
 const char* umlh_last_error(void);
-int  umlh_version(void);        /* ABI revision: 3 = round 2 (grouped / micro / data-parallel / encoder-plan / InfoNCE entry points); 4 = round 3 (umlh_step_status / umlh_step_launches, umlh_p2p_*) */
+int  umlh_version(void);        /* ABI revision: 3 = round 2 (grouped / micro / data-parallel / encoder-plan / InfoNCE entry points); 4 = round 3 (umlh_step_status / umlh_step_launches, umlh_p2p_*); 5 = umlh_align_* (CKA, k-NN, mutual k-NN) */
 
 /* Bytes of workspace a handle with this config needs (0 on invalid config). */
 uint64_t umlh_workspace_bytes(const umlh_config_t* cfg);
@@ -474,6 +474,33 @@ int  umlh_optimizer_step(int32_t optimizer, float* param, const float* grad, flo
 int  umlh_optimizer_step_multi(int32_t optimizer, int32_t n_tensors, float* const* params, const float* const* grads,
                                float* const* m, float* const* v, const int64_t* n, double lr, int64_t step, double beta1,
                                double beta2, double eps, double momentum, double weight_decay, void* stream);
+
+/* ---- representation-alignment metrics (vision_language/metrics.py; the same in MultiBench/metrics.py and
+ * Gaussian_experiment/metrics.py).  Features are row-major fp32 [n, d] with row stride ld >= d.  No N x N array is
+ * formed; results are bitwise reproducible for a given `splits` (0 = auto) and no reduction uses float atomics.
+ * Every argument check happens before any HIP call.  `scratch` is caller device memory of at least
+ * umlh_align_scratch_bytes(...) bytes with the same arguments; results are device memory written on `stream`. */
+
+/* Scratch bytes for umlh_align_knn (topk >= 1; topk = 0: none), umlh_align_mutual_knn and umlh_align_cka with these
+ * arguments: O(n*topk*splits + tiles + d^2), no n^2 term.  0 on invalid arguments (n < 1, d_a or d_b < 1, topk outside
+ * 0..32, topk >= n, splits < 0). */
+uint64_t umlh_align_scratch_bytes(int64_t n, int32_t d_a, int32_t d_b, int32_t topk, int32_t splits);
+/* compute_nearest_neighbors(feats, topk) (metrics.py:272-285): per row i the topk columns j != i with the largest raw
+ * inner product x_i . x_j (not cosine), ordered by (score desc, index asc) -- exact ties go to the smaller index; the
+ * reference excludes self by writing -1e8 on the diagonal, here self is skipped.  knn int32 [n, topk]; scores fp32
+ * [n, topk] or NULL.  Products on the f32 MFMA (a k-ordered fp32 fma chain); the result is bitwise independent of
+ * `splits` (column chunks of the fused Gram + top-k pass).  1 <= topk <= 32, topk < n. */
+int  umlh_align_knn(const float* x, int64_t n, int32_t d, int32_t ldx, int32_t topk, int32_t splits, int32_t* knn,
+                    float* scores, void* scratch, uint64_t scratch_bytes, void* stream);
+/* AlignmentMetrics.mutual_knn given both neighbour lists (metrics.py:55-84): mean over rows of
+ * |knn_a(i) n knn_b(i)| / topk; the counts are summed as integers, the mean is formed once in double -> out[0]. */
+int  umlh_align_mutual_knn(const int32_t* knn_a, const int32_t* knn_b, int64_t n, int32_t topk, double* out, void* scratch,
+                           uint64_t scratch_bytes, void* stream);
+/* AlignmentMetrics.cka(a, b, kernel_metric='ip', unbiased=False) (metrics.py:96-119 with hsic_biased :252-255) in
+ * feature space: trace(K H L H) = ||Ac^T Bc||_F^2 with Ac, Bc the column-centred features (centred on load).
+ * out4 = {hsic_kl / (sqrt(hsic_kk * hsic_ll) + 1e-6), hsic_kl, hsic_kk, hsic_ll} in double; no 1/(n-1)^2 factor. */
+int  umlh_align_cka(const float* a, int32_t lda, int32_t d_a, const float* b, int32_t ldb, int32_t d_b, int64_t n,
+                    int32_t splits, double* out4, void* scratch, uint64_t scratch_bytes, void* stream);
 
 #ifdef __cplusplus
 }

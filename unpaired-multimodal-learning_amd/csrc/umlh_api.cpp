@@ -286,7 +286,7 @@ static inline void mark(umlh_handle_t h, int i, hipStream_t st) {
 }
 
 const char* umlh_last_error(void) { return g_err; }
-int umlh_version(void) { return 4; }   // 3: round 2 (grouped / micro / data-parallel / encoder-plan / InfoNCE entry points, umlh_enc_layer_t.seed_device, umlh_seq_mse_backward scratch); 4: round 3 (umlh_step_status / _launches, umlh_p2p_*)
+int umlh_version(void) { return 5; }   // 3: round 2 (grouped / micro / data-parallel / encoder-plan / InfoNCE entry points, umlh_enc_layer_t.seed_device, umlh_seq_mse_backward scratch); 4: round 3 (umlh_step_status / _launches, umlh_p2p_*); 5: umlh_align_*
 
 int umlh_freeze_proj_row(umlh_handle_t h, int32_t row) {
     if (!h) return fail(UMLH_E_INVALID, "umlh_freeze_proj_row: null handle");
@@ -731,6 +731,79 @@ extern "C" int umlh_launch_feistel_perm(long long n, unsigned long long seed, lo
 int umlh_random_permutation(int64_t n, uint64_t seed, int64_t* out, void* stream) {
     if (n < 0 || (n > 0 && !out)) return fail(UMLH_E_INVALID, "umlh_random_permutation: bad arguments");
     HIPCHK(umlh_launch_feistel_perm(n, seed, reinterpret_cast<long long*>(out), (hipStream_t)stream), "feistel perm");
+    return UMLH_OK;
+}
+
+// ---- alignment metrics (kernels: umlh_kernels_align.hip); every check precedes the first HIP call ----
+extern "C" {
+int umlh_align_knn_splits(long long n, int splits);
+unsigned long long umlh_align_knn_bytes(long long n, int topk, int splits);
+unsigned long long umlh_align_mutual_bytes(long long n);
+unsigned long long umlh_align_cka_bytes(long long n, int da, int db, int splits);
+int umlh_align_launch_knn(const float* x, long long n, int d, int ldx, int topk, int splits, int* knn, float* scores, void* scratch,
+                          hipStream_t st);
+int umlh_align_launch_mutual(const int* ka, const int* kb, long long n, int topk, double* out, void* scratch, hipStream_t st);
+int umlh_align_launch_cka(const float* a, int lda, int da, const float* b, int ldb, int db, long long n, int splits, double* out4,
+                          void* scratch, hipStream_t st);
+}
+
+static const int64_t ALIGN_MAX_ROWS = (int64_t)1 << 30;   // int32 indices with room for the tile and sentinel arithmetic
+
+uint64_t umlh_align_scratch_bytes(int64_t n, int32_t d_a, int32_t d_b, int32_t topk, int32_t splits) {
+    if (n < 1 || n > ALIGN_MAX_ROWS || d_a < 1 || d_b < 1 || topk < 0 || topk > 32 || (topk > 0 && topk >= n) || splits < 0) return 0;
+    uint64_t b = umlh_align_cka_bytes(n, d_a, d_b, splits);
+    const uint64_t m = umlh_align_mutual_bytes(n);
+    if (m > b) b = m;
+    if (topk > 0) {
+        const uint64_t k = umlh_align_knn_bytes(n, topk, splits);
+        if (k > b) b = k;
+    }
+    return b;
+}
+
+int umlh_align_knn(const float* x, int64_t n, int32_t d, int32_t ldx, int32_t topk, int32_t splits, int32_t* knn,
+                   float* scores, void* scratch, uint64_t scratch_bytes, void* stream) {
+    if (!x || !knn || !scratch) return fail(UMLH_E_INVALID, "umlh_align_knn: null pointer (x, knn and scratch are required)");
+    if (topk < 1 || topk > 32) return fail(UMLH_E_INVALID, "umlh_align_knn: topk=%d outside 1..32", topk);
+    if (n <= topk || n > ALIGN_MAX_ROWS)
+        return fail(UMLH_E_INVALID, "umlh_align_knn: n=%lld rows for topk=%d (need topk < n <= 2^30)", (long long)n, topk);
+    if (d < 1 || ldx < d) return fail(UMLH_E_INVALID, "umlh_align_knn: d=%d ldx=%d (need 1 <= d <= ldx)", d, ldx);
+    if (splits < 0) return fail(UMLH_E_INVALID, "umlh_align_knn: splits=%d < 0", splits);
+    const uint64_t need = umlh_align_knn_bytes(n, topk, splits);
+    if (scratch_bytes < need)
+        return fail(UMLH_E_INVALID, "umlh_align_knn: scratch of %llu bytes, %llu needed", (unsigned long long)scratch_bytes,
+                    (unsigned long long)need);
+    HIPCHK(umlh_align_launch_knn(x, n, d, ldx, topk, splits, knn, scores, scratch, (hipStream_t)stream), "umlh_align_knn");
+    return UMLH_OK;
+}
+
+int umlh_align_mutual_knn(const int32_t* knn_a, const int32_t* knn_b, int64_t n, int32_t topk, double* out, void* scratch,
+                          uint64_t scratch_bytes, void* stream) {
+    if (!knn_a || !knn_b || !out || !scratch)
+        return fail(UMLH_E_INVALID, "umlh_align_mutual_knn: null pointer (knn_a, knn_b, out and scratch are required)");
+    if (topk < 1 || topk > 32) return fail(UMLH_E_INVALID, "umlh_align_mutual_knn: topk=%d outside 1..32", topk);
+    if (n <= topk || n > ALIGN_MAX_ROWS)
+        return fail(UMLH_E_INVALID, "umlh_align_mutual_knn: n=%lld rows for topk=%d (need topk < n <= 2^30)", (long long)n, topk);
+    const uint64_t need = umlh_align_mutual_bytes(n);
+    if (scratch_bytes < need)
+        return fail(UMLH_E_INVALID, "umlh_align_mutual_knn: scratch of %llu bytes, %llu needed", (unsigned long long)scratch_bytes,
+                    (unsigned long long)need);
+    HIPCHK(umlh_align_launch_mutual(knn_a, knn_b, n, topk, out, scratch, (hipStream_t)stream), "umlh_align_mutual_knn");
+    return UMLH_OK;
+}
+
+int umlh_align_cka(const float* a, int32_t lda, int32_t d_a, const float* b, int32_t ldb, int32_t d_b, int64_t n,
+                   int32_t splits, double* out4, void* scratch, uint64_t scratch_bytes, void* stream) {
+    if (!a || !b || !out4 || !scratch) return fail(UMLH_E_INVALID, "umlh_align_cka: null pointer (a, b, out4 and scratch are required)");
+    if (d_a < 1 || d_b < 1 || lda < d_a || ldb < d_b)
+        return fail(UMLH_E_INVALID, "umlh_align_cka: d_a=%d lda=%d d_b=%d ldb=%d (need 1 <= d <= ld)", d_a, lda, d_b, ldb);
+    if (n < 1 || n > ALIGN_MAX_ROWS) return fail(UMLH_E_INVALID, "umlh_align_cka: n=%lld rows (need 1 <= n <= 2^30)", (long long)n);
+    if (splits < 0) return fail(UMLH_E_INVALID, "umlh_align_cka: splits=%d < 0", splits);
+    const uint64_t need = umlh_align_cka_bytes(n, d_a, d_b, splits);
+    if (scratch_bytes < need)
+        return fail(UMLH_E_INVALID, "umlh_align_cka: scratch of %llu bytes, %llu needed", (unsigned long long)scratch_bytes,
+                    (unsigned long long)need);
+    HIPCHK(umlh_align_launch_cka(a, lda, d_a, b, ldb, d_b, n, splits, out4, scratch, (hipStream_t)stream), "umlh_align_cka");
     return UMLH_OK;
 }
 

@@ -1,0 +1,474 @@
+// Representation-alignment metrics of the reference (vision_language/metrics.py:55-84,96-119,252-255,272-285) for gfx950.
+//
+//   knn_tiles      fused Gram tile x_i . x_j on v_mfma_f32_32x32x2_f32 (a k-ordered fp32 fma chain) + a streaming
+//                  per-row top-k under the strict order (score desc, index asc); one partial list per column chunk
+//   knn_merge      merges the chunks' lists of a row -> knn int32 [N, k] (+ scores fp32 [N, k])
+//   mutual_count   |knn_a(i) n knn_b(i)| per row, integer block sums
+//   mutual_final   fixed-order sum of the block counts -> mean as double
+//   cka_colsum     column sums of A | B in double, per row chunk
+//   cka_cross      the centred cross products Ac^T Bc, Ac^T Ac, Bc^T Bc as 32x32 tiles on the f32 MFMA, per row chunk
+//                  (centred on load: never X^T Y - N mu mu^T)
+//   cka_tile_sq    each finished tile (its row chunks summed in double, fixed order), squared and summed
+//   cka_final      fixed-order Frobenius sums -> {cka, hsic_kl, hsic_kk, hsic_ll}
+//
+// Nothing here forms an N x N array, and no reduction uses a float atomic: every result is bitwise reproducible for a
+// given `splits`.  knn is bitwise independent of `splits` as well: column chunks start on 256-column tile boundaries,
+// every score is the same fma chain wherever it is computed, and the kept lists are exact top-k under a strict order.
+#include "umlh_common.h"
+#include <climits>
+
+namespace {
+
+constexpr int KN_ROWS = 32;              // rows of a workgroup's strip
+constexpr int KN_COLS = 256;             // columns of a tile: 4 waves x 64
+constexpr int KN_LD = KN_COLS + 1;       // score tile row stride (floats): the filter's reads are conflict-free
+constexpr int KN_KMAX = 32;
+constexpr int KN_KLD = KN_KMAX + 1;      // list row stride
+constexpr int KN_TARGET_WG = 512;        // auto splits: about two workgroups per CU of the 256
+constexpr int KN_MAX_SPLITS = 1024;       // (grid y)
+
+constexpr int CK_TARGET_WG = 512;
+constexpr int CK_SUM_CHUNKS = 64;        // row chunks of the column sums
+constexpr int CK_MAX_RCHUNKS = 4096;     // (grid y)
+
+__device__ __forceinline__ bool kn_better(float s, int j, float ts, int tj) { return s > ts || (s == ts && j < tj); }
+
+// x[row][k .. k+3], zero outside [0, n) x [0, d)
+template <bool VEC>
+__device__ __forceinline__ f32x4v kn_load4(const float* __restrict__ x, long long row, long long n, int k, int d, int ldx) {
+    f32x4v v = {0.f, 0.f, 0.f, 0.f};
+    if (row < n) {
+        const float* p = x + row * (long long)ldx + k;
+        if (VEC) {
+            if (k < d) v = *reinterpret_cast<const f32x4v*>(p);
+        } else {
+            if (k < d) v[0] = p[0];
+            if (k + 1 < d) v[1] = p[1];
+            if (k + 2 < d) v[2] = p[2];
+            if (k + 3 < d) v[3] = p[3];
+        }
+    }
+    return v;
+}
+
+// One workgroup: rows [r0, r0 + 32) x the column tiles [t0, t1) of chunk blockIdx.y.  Wave w computes the 32 x 64 score
+// block of columns w*64.. of a tile with two 32x32 accumulators.  The k loop runs in blocks of 8: lane half h supplies
+// k = 8kb + 4h + s to MFMA step s, for A (the strip rows) and B (the tile rows) alike, so every score is the same fixed
+// permutation of its fma chain.  Epilogue per tile: scores -> LDS; each (row, 32-column part) thread keeps the candidates
+// that beat the row's current k-th entry (on a chunk's first tile also not worse than the k-th best of the 32 group-of-8
+// maxima of the tile, a valid lower bound); then the list is rebuilt from the old list plus the survivors by rank
+// counting, which is exact and independent of the order the survivors were appended in.
+template <bool VEC>
+__global__ __launch_bounds__(256) void knn_tiles(const float* __restrict__ x, int n, int d, int ldx, int topk, int ntiles,
+                                                 int splits, float* __restrict__ part_s, int* __restrict__ part_i) {
+    __shared__ float tile[KN_ROWS * KN_LD];
+    __shared__ float ls[2][KN_ROWS * KN_KLD];
+    __shared__ int li[2][KN_ROWS * KN_KLD];
+    __shared__ unsigned char surv[KN_ROWS * KN_COLS];
+    __shared__ int cnt[KN_ROWS];
+    __shared__ float gms[KN_ROWS * KN_KLD];          // first tile: group maxima, then the tile bound in column 0
+    __shared__ int gmi[KN_ROWS * KN_KLD];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, c32 = lane & 31;
+    const int r0 = blockIdx.x * KN_ROWS, split = blockIdx.y;
+    const int t0 = (int)((long long)split * ntiles / splits), t1 = (int)((long long)(split + 1) * ntiles / splits);
+    for (int e = tid; e < KN_ROWS * KN_KLD; e += 256) {
+        ls[0][e] = -INFINITY;
+        li[0][e] = INT_MAX - (e % KN_KLD);           // distinct sentinels: ranks stay unique
+    }
+    if (tid < KN_ROWS) cnt[tid] = 0;
+    int cur = 0;
+    const int nk = (d + 7) / 8;
+    for (int t = t0; t < t1; ++t) {
+        const int cb = t * KN_COLS;
+        const long long ra = r0 + c32, rb0 = cb + wave * 64 + c32, rb1 = rb0 + 32;
+        f32x16 acc0 = {}, acc1 = {};
+        f32x4v a = kn_load4<VEC>(x, ra, n, 4 * h, d, ldx), b0 = kn_load4<VEC>(x, rb0, n, 4 * h, d, ldx),
+               b1 = kn_load4<VEC>(x, rb1, n, 4 * h, d, ldx);
+        for (int kb = 0; kb < nk; ++kb) {
+            const int kn = (kb + 1) * 8 + 4 * h;     // next block (zero past d: no access)
+            const f32x4v an = kn_load4<VEC>(x, ra, n, kn, d, ldx), b0n = kn_load4<VEC>(x, rb0, n, kn, d, ldx),
+                         b1n = kn_load4<VEC>(x, rb1, n, kn, d, ldx);
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], b0[s], acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], b1[s], acc1, 0, 0, 0);
+            }
+            a = an; b0 = b0n; b1 = b1n;
+        }
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {               // acc[q]: row 8(q/4) + 4h + q%4, column c32 (the last rebuild ended on a barrier)
+            const int i = 8 * (q >> 2) + 4 * h + (q & 3);
+            tile[i * KN_LD + wave * 64 + c32] = acc0[q];
+            tile[i * KN_LD + wave * 64 + 32 + c32] = acc1[q];
+        }
+        __syncthreads();
+        const int fr = tid & 31, part = tid >> 5, gi = r0 + fr;      // filter mapping: row fr, columns part*32 ..
+        const float* cls = ls[cur];
+        const int* cli = li[cur];
+        float bs = -INFINITY;                        // tile bound (first tile of the chunk only)
+        int bj = INT_MAX;
+        if (t == t0) {
+            for (int g = 0; g < 4; ++g) {
+                float ms = -INFINITY;
+                int mj = INT_MAX - KN_KMAX - (part * 4 + g);
+                for (int m = 0; m < 8; ++m) {
+                    const int c = part * 32 + g * 8 + m, j = cb + c;
+                    const float s = tile[fr * KN_LD + c];
+                    if (j < n && j != gi && kn_better(s, j, ms, mj)) { ms = s; mj = j; }
+                }
+                gms[fr * KN_KLD + part * 4 + g] = ms;
+                gmi[fr * KN_KLD + part * 4 + g] = mj;
+            }
+            __syncthreads();
+            const int rr = tid >> 3, sub = tid & 7;
+            float ws = 0.f;
+            int wj = 0, hit = 0;
+            for (int m = sub; m < 32; m += 8) {      // rank of each group maximum among the 32
+                const float s = gms[rr * KN_KLD + m];
+                const int j = gmi[rr * KN_KLD + m];
+                int rank = 0;
+                for (int q = 0; q < 32; ++q) rank += kn_better(gms[rr * KN_KLD + q], gmi[rr * KN_KLD + q], s, j);
+                if (rank == topk - 1) { ws = s; wj = j; hit = 1; }
+            }
+            __syncthreads();
+            if (hit) { gms[rr * KN_KLD] = ws; gmi[rr * KN_KLD] = wj; }
+            __syncthreads();
+            bs = gms[fr * KN_KLD];
+            bj = gmi[fr * KN_KLD];
+        }
+        if (gi < n) {
+            const float ts = cls[fr * KN_KLD + topk - 1];
+            const int tj = cli[fr * KN_KLD + topk - 1];
+            for (int m = 0; m < 32; ++m) {
+                const int c = part * 32 + m, j = cb + c;
+                if (j >= n) break;
+                const float s = tile[fr * KN_LD + c];
+                if (j != gi && kn_better(s, j, ts, tj) && !kn_better(bs, bj, s, j)) {
+                    const int p = atomicAdd(&cnt[fr], 1);
+                    surv[fr * KN_COLS + p] = (unsigned char)c;
+                }
+            }
+        }
+        __syncthreads();
+        {   // rebuild: row rr's candidates are its k list entries and its survivors; rank < k goes to position rank
+            const int rr = tid >> 3, sub = tid & 7, m_all = topk + cnt[rr];
+            float* nls = ls[cur ^ 1];
+            int* nli = li[cur ^ 1];
+            auto cand = [&](int m, float& s, int& j) {
+                if (m < topk) { s = cls[rr * KN_KLD + m]; j = cli[rr * KN_KLD + m]; }
+                else { const int c = surv[rr * KN_COLS + m - topk]; s = tile[rr * KN_LD + c]; j = cb + c; }
+            };
+            for (int m = sub; m < m_all; m += 8) {
+                float s;
+                int j;
+                cand(m, s, j);
+                int rank = 0;
+                for (int q = 0; q < m_all; ++q) {
+                    float s2;
+                    int j2;
+                    cand(q, s2, j2);
+                    rank += kn_better(s2, j2, s, j);
+                }
+                if (rank < topk) { nls[rr * KN_KLD + rank] = s; nli[rr * KN_KLD + rank] = j; }
+            }
+            __syncthreads();
+            if (tid < KN_ROWS) cnt[tid] = 0;
+            cur ^= 1;
+        }
+    }
+    for (int e = tid; e < KN_ROWS * topk; e += 256) {
+        const int r = e / topk, q = e - r * topk;
+        if (r0 + r < n) {
+            const long long o = ((long long)split * n + r0 + r) * topk + q;
+            part_s[o] = ls[cur][r * KN_KLD + q];
+            part_i[o] = li[cur][r * KN_KLD + q];
+        }
+    }
+}
+
+// Thread per row: the chunks' sorted lists merged pairwise in chunk order (exact under the strict order).
+__global__ __launch_bounds__(64) void knn_merge(const float* __restrict__ part_s, const int* __restrict__ part_i, int n, int topk,
+                                                int splits, int* __restrict__ knn, float* __restrict__ scores) {
+    __shared__ float bs[2][64 * KN_KLD];
+    __shared__ int bi[2][64 * KN_KLD];
+    const int tid = threadIdx.x;
+    const long long row = (long long)blockIdx.x * 64 + tid;
+    if (row >= n) return;
+    float* cs = &bs[0][tid * KN_KLD];
+    int* ci = &bi[0][tid * KN_KLD];
+    float* ns = &bs[1][tid * KN_KLD];
+    int* ni = &bi[1][tid * KN_KLD];
+    for (int q = 0; q < topk; ++q) { cs[q] = part_s[row * topk + q]; ci[q] = part_i[row * topk + q]; }
+    for (int s = 1; s < splits; ++s) {
+        const float* ps = part_s + ((long long)s * n + row) * topk;
+        const int* pi = part_i + ((long long)s * n + row) * topk;
+        int ia = 0, ib = 0;
+        for (int q = 0; q < topk; ++q) {             // ia + ib = q < topk: both stay in range
+            const float sa = cs[ia], sb = ps[ib];
+            const int ja = ci[ia], jb = pi[ib];
+            if (kn_better(sa, ja, sb, jb)) { ns[q] = sa; ni[q] = ja; ++ia; }
+            else { ns[q] = sb; ni[q] = jb; ++ib; }
+        }
+        float* ts = cs; cs = ns; ns = ts;
+        int* ti = ci; ci = ni; ni = ti;
+    }
+    for (int q = 0; q < topk; ++q) {
+        knn[row * topk + q] = ci[q];
+        if (scores) scores[row * topk + q] = cs[q];
+    }
+}
+
+__global__ __launch_bounds__(256) void mutual_count(const int* __restrict__ ka, const int* __restrict__ kb, int n, int topk,
+                                                    long long* __restrict__ partial) {
+    __shared__ int red[256];
+    const int tid = threadIdx.x;
+    const long long row = (long long)blockIdx.x * 256 + tid;
+    int c = 0;
+    if (row < n) {
+        const int* a = ka + row * topk;
+        const int* b = kb + row * topk;
+        for (int p = 0; p < topk; ++p) {
+            const int ja = a[p];
+            int hit = 0;
+            for (int q = 0; q < topk; ++q) hit |= (b[q] == ja);
+            c += hit;
+        }
+    }
+    red[tid] = c;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) red[tid] += red[tid + w];
+        __syncthreads();
+    }
+    if (tid == 0) partial[blockIdx.x] = red[0];
+}
+
+__global__ __launch_bounds__(256) void mutual_final(const long long* __restrict__ partial, int nblocks, int n, int topk,
+                                                    double* __restrict__ out) {
+    __shared__ long long red[256];
+    const int tid = threadIdx.x;
+    long long c = 0;
+    for (int b = tid; b < nblocks; b += 256) c += partial[b];
+    red[tid] = c;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) red[tid] += red[tid + w];
+        __syncthreads();
+    }
+    if (tid == 0) out[0] = (double)red[0] / ((double)n * (double)topk);
+}
+
+// Column c of A | B (c < da: A), rows of chunk blockIdx.y; 64 columns x 4 row lanes, in double.
+__global__ __launch_bounds__(256) void cka_colsum(const float* __restrict__ a, int lda, int da, const float* __restrict__ b, int ldb,
+                                                  int db, int n, int chunks, double* __restrict__ partial) {
+    __shared__ double red[256];
+    const int tid = threadIdx.x, cl = tid & 63, rl = tid >> 6, c = blockIdx.x * 64 + cl, dt = da + db;
+    const long long rs = (long long)blockIdx.y * n / chunks, re = (long long)(blockIdx.y + 1) * n / chunks;
+    double s = 0.0;
+    if (c < dt) {
+        const float* p = c < da ? a + c : b + (c - da);
+        const long long ld = c < da ? lda : ldb;
+        for (long long r = rs + rl; r < re; r += 4) s += (double)p[r * ld];
+    }
+    red[tid] = s;
+    __syncthreads();
+    if (rl == 0 && c < dt) partial[(long long)blockIdx.y * dt + c] = ((red[cl] + red[64 + cl]) + red[128 + cl]) + red[192 + cl];
+}
+
+struct CkaArgs {
+    const float* a;
+    const float* b;
+    int lda, ldb, da, db, ta, tb;            // ta, tb: 32-column tiles of A and B
+    int n, sum_chunks, rchunks;
+    const double* colsum;                    // [sum_chunks][da + db]
+    double* cross;                           // [tiles][rchunks][1024]
+    double* tile_sq;                         // [tiles]
+};
+
+// Tile blockIdx.x of the three products (A^T B: ta*tb tiles, A^T A: ta*ta, B^T B: tb*tb), rows of chunk blockIdx.y (whole
+// 32-row blocks).  Wave w takes the 8-row groups w, w+4, ... of the chunk; lane half h supplies rows 4h + s to MFMA step s.
+__global__ __launch_bounds__(256) void cka_cross(CkaArgs g) {
+    __shared__ float red[4][1024];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, c32 = lane & 31;
+    int t = blockIdx.x, ti, tj;
+    const float *X, *Y;
+    int ldx, ldy, dx, dy, ox, oy;            // ox, oy: offsets of X's / Y's columns in the column sums
+    if (t < g.ta * g.tb) {
+        X = g.a; ldx = g.lda; dx = g.da; ox = 0; Y = g.b; ldy = g.ldb; dy = g.db; oy = g.da; ti = t / g.tb; tj = t % g.tb;
+    } else if ((t -= g.ta * g.tb) < g.ta * g.ta) {
+        X = g.a; ldx = g.lda; dx = g.da; ox = 0; Y = g.a; ldy = g.lda; dy = g.da; oy = 0; ti = t / g.ta; tj = t % g.ta;
+    } else {
+        t -= g.ta * g.ta;
+        X = g.b; ldx = g.ldb; dx = g.db; ox = g.da; Y = g.b; ldy = g.ldb; dy = g.db; oy = g.da; ti = t / g.tb; tj = t % g.tb;
+    }
+    const int cx = ti * 32 + c32, cy = tj * 32 + c32, dt = g.da + g.db;
+    // column means (fixed-order double sums of the chunk partials): lanes 0-31 for X's column, 32-63 for Y's
+    float mean;
+    {
+        const int col = h ? cy : cx, lim = h ? dy : dx, off = h ? oy : ox;
+        double s = 0.0;
+        if (col < lim)
+            for (int q = 0; q < g.sum_chunks; ++q) s += g.colsum[(long long)q * dt + off + col];
+        mean = (float)(s / (double)g.n);
+    }
+    const float mx = __shfl(mean, c32), my = __shfl(mean, 32 + c32);
+    const bool vx = cx < dx, vy = cy < dy;
+    const int nb = (g.n + 31) / 32;
+    const long long rs = (long long)((long long)blockIdx.y * nb / g.rchunks) * 32;
+    const long long re = min((long long)g.n, (long long)((long long)(blockIdx.y + 1) * nb / g.rchunks) * 32);
+    auto load = [&](long long base, float* xv, float* yv) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const long long r = base + 4 * h + s;
+            const bool vr = r < re;
+            xv[s] = (vr && vx) ? X[r * ldx + cx] - mx : 0.f;
+            yv[s] = (vr && vy) ? Y[r * ldy + cy] - my : 0.f;
+        }
+    };
+    f32x16 acc = {};
+    long long base = rs + wave * 8;
+    float xv[4], yv[4];
+    load(base, xv, yv);
+    for (; base < re; base += 32) {
+        float xn[4], yn[4];
+        load(base + 32, xn, yn);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xv[s], yv[s], acc, 0, 0, 0);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) { xv[s] = xn[s]; yv[s] = yn[s]; }
+    }
+#pragma unroll
+    for (int q = 0; q < 16; ++q) red[wave][(8 * (q >> 2) + 4 * h + (q & 3)) * 32 + c32] = acc[q];
+    __syncthreads();
+    double* out = g.cross + ((long long)blockIdx.x * g.rchunks + blockIdx.y) * 1024;
+    for (int e = tid; e < 1024; e += 256)
+        out[e] = (((double)red[0][e] + (double)red[1][e]) + (double)red[2][e]) + (double)red[3][e];
+}
+
+__global__ __launch_bounds__(256) void cka_tile_sq(const double* __restrict__ cross, int rchunks, double* __restrict__ tile_sq) {
+    __shared__ double red[256];
+    const int tid = threadIdx.x;
+    const double* p = cross + (long long)blockIdx.x * rchunks * 1024;
+    double sq = 0.0;
+    for (int e = tid; e < 1024; e += 256) {
+        double v = 0.0;
+        for (int r = 0; r < rchunks; ++r) v += p[(long long)r * 1024 + e];
+        sq += v * v;
+    }
+    red[tid] = sq;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) red[tid] += red[tid + w];
+        __syncthreads();
+    }
+    if (tid == 0) tile_sq[blockIdx.x] = red[0];
+}
+
+__global__ __launch_bounds__(256) void cka_final(const double* __restrict__ tile_sq, int ta, int tb, double* __restrict__ out4) {
+    __shared__ double red[256];
+    __shared__ double hs[3];
+    const int tid = threadIdx.x;
+    const int lo[3] = {0, ta * tb, ta * tb + ta * ta}, hi[3] = {ta * tb, ta * tb + ta * ta, ta * tb + ta * ta + tb * tb};
+    for (int p = 0; p < 3; ++p) {
+        double s = 0.0;
+        for (int t = lo[p] + tid; t < hi[p]; t += 256) s += tile_sq[t];
+        red[tid] = s;
+        __syncthreads();
+        for (int w = 128; w > 0; w >>= 1) {
+            if (tid < w) red[tid] += red[tid + w];
+            __syncthreads();
+        }
+        if (tid == 0) hs[p] = red[0];
+        __syncthreads();
+    }
+    if (tid == 0) {   // metrics.py:116: hsic_kl / (sqrt(hsic_kk * hsic_ll) + 1e-6)
+        out4[0] = hs[0] / (sqrt(hs[1] * hs[2]) + 1e-6);
+        out4[1] = hs[0];
+        out4[2] = hs[1];
+        out4[3] = hs[2];
+    }
+}
+
+inline long long align_up(long long x) { return (x + 255) / 256 * 256; }
+
+}  // namespace
+
+// ---- plans and launchers (validation is the caller's: umlh_api.cpp) ----
+extern "C" {
+
+int umlh_align_knn_splits(long long n, int splits) {
+    const long long ntiles = (n + KN_COLS - 1) / KN_COLS, strips = (n + KN_ROWS - 1) / KN_ROWS;
+    long long s = splits > 0 ? splits : (KN_TARGET_WG + strips - 1) / strips;
+    if (s > KN_MAX_SPLITS) s = KN_MAX_SPLITS;
+    return (int)(s < 1 ? 1 : (s > ntiles ? ntiles : s));
+}
+
+unsigned long long umlh_align_knn_bytes(long long n, int topk, int splits) {
+    return (unsigned long long)(2 * align_up((long long)umlh_align_knn_splits(n, splits) * n * topk * 4));
+}
+
+unsigned long long umlh_align_mutual_bytes(long long n) { return (unsigned long long)align_up((n + 255) / 256 * 8); }
+
+struct CkaPlan { int ta, tb, tiles, rchunks, sum_chunks; long long colsum, cross, tile_sq, total; };
+
+static CkaPlan cka_plan(long long n, int da, int db, int splits) {
+    CkaPlan p;
+    p.ta = (da + 31) / 32;
+    p.tb = (db + 31) / 32;
+    p.tiles = p.ta * p.tb + p.ta * p.ta + p.tb * p.tb;
+    const long long nb = (n + 31) / 32;
+    long long r = splits > 0 ? splits : (p.tiles >= CK_TARGET_WG ? 1 : (CK_TARGET_WG + p.tiles - 1) / p.tiles);
+    if (splits <= 0 && r > nb / 4) r = nb / 4;   // auto: at least 128 rows per chunk
+    if (r > CK_MAX_RCHUNKS) r = CK_MAX_RCHUNKS;
+    p.rchunks = (int)(r < 1 ? 1 : (r > nb ? nb : r));
+    p.sum_chunks = (int)(n < CK_SUM_CHUNKS * 64 ? (n + 63) / 64 : CK_SUM_CHUNKS);
+    p.colsum = 0;
+    p.cross = align_up((long long)p.sum_chunks * (da + db) * 8);
+    p.tile_sq = p.cross + align_up((long long)p.tiles * p.rchunks * 1024 * 8);
+    p.total = p.tile_sq + align_up((long long)p.tiles * 8);
+    return p;
+}
+
+unsigned long long umlh_align_cka_bytes(long long n, int da, int db, int splits) {
+    return (unsigned long long)cka_plan(n, da, db, splits).total;
+}
+
+int umlh_align_launch_knn(const float* x, long long n, int d, int ldx, int topk, int splits, int* knn, float* scores, void* scratch,
+                          hipStream_t st) {
+    const int s = umlh_align_knn_splits(n, splits), ntiles = (int)((n + KN_COLS - 1) / KN_COLS);
+    float* ps = (float*)scratch;
+    int* pi = (int*)((char*)scratch + align_up((long long)s * n * topk * 4));
+    const dim3 grid((unsigned)((n + KN_ROWS - 1) / KN_ROWS), (unsigned)s);
+    const bool vec = (d % 4 == 0) && (ldx % 4 == 0) && (((uintptr_t)x & 15) == 0);
+    if (vec) hipLaunchKernelGGL(knn_tiles<true>, grid, dim3(256), 0, st, x, (int)n, d, ldx, topk, ntiles, s, ps, pi);
+    else hipLaunchKernelGGL(knn_tiles<false>, grid, dim3(256), 0, st, x, (int)n, d, ldx, topk, ntiles, s, ps, pi);
+    hipLaunchKernelGGL(knn_merge, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, ps, pi, (int)n, topk, s, knn, scores);
+    return (int)hipGetLastError();
+}
+
+int umlh_align_launch_mutual(const int* ka, const int* kb, long long n, int topk, double* out, void* scratch, hipStream_t st) {
+    const int nblocks = (int)((n + 255) / 256);
+    long long* partial = (long long*)scratch;
+    hipLaunchKernelGGL(mutual_count, dim3((unsigned)nblocks), dim3(256), 0, st, ka, kb, (int)n, topk, partial);
+    hipLaunchKernelGGL(mutual_final, dim3(1), dim3(256), 0, st, partial, nblocks, (int)n, topk, out);
+    return (int)hipGetLastError();
+}
+
+int umlh_align_launch_cka(const float* a, int lda, int da, const float* b, int ldb, int db, long long n, int splits, double* out4,
+                          void* scratch, hipStream_t st) {
+    const CkaPlan p = cka_plan(n, da, db, splits);
+    CkaArgs g;
+    g.a = a; g.b = b; g.lda = lda; g.ldb = ldb; g.da = da; g.db = db; g.ta = p.ta; g.tb = p.tb;
+    g.n = (int)n; g.sum_chunks = p.sum_chunks; g.rchunks = p.rchunks;
+    g.colsum = (const double*)((char*)scratch + p.colsum);
+    g.cross = (double*)((char*)scratch + p.cross);
+    g.tile_sq = (double*)((char*)scratch + p.tile_sq);
+    hipLaunchKernelGGL(cka_colsum, dim3((unsigned)((da + db + 63) / 64), (unsigned)p.sum_chunks), dim3(256), 0, st, a, lda, da, b, ldb,
+                       db, (int)n, p.sum_chunks, (double*)g.colsum);
+    hipLaunchKernelGGL(cka_cross, dim3((unsigned)p.tiles, (unsigned)p.rchunks), dim3(256), 0, st, g);
+    hipLaunchKernelGGL(cka_tile_sq, dim3((unsigned)p.tiles), dim3(256), 0, st, g.cross, p.rchunks, g.tile_sq);
+    hipLaunchKernelGGL(cka_final, dim3(1), dim3(256), 0, st, g.tile_sq, p.ta, p.tb, out4);
+    return (int)hipGetLastError();
+}
+
+}  // extern "C"

@@ -27,6 +27,7 @@ from engine.models.head import UML, UMLClip  # noqa: F401
 from engine.optimizer.default import HYPER_DICT  # noqa: F401
 from engine.optimizer.optim import build_optimizer  # noqa: F401
 from engine.optimizer.scheduler import build_lr_scheduler  # noqa: F401
+from metrics import AlignmentMetrics, cka, mknn  # noqa: F401  finetune.py:111-118 (CKA and mKNN metrics)
 
 EVAL_FREQ = 100   # evaluate on the val set every 100 iterations (early stopping)
 

@@ -1,7 +1,8 @@
 """Training loop of the Gaussian experiment (reference Gaussian_experiment/main.py:33-91,132-151): infinite cycling
 over one shuffled unpaired loader, ``loss = alpha_x*loss_x + alpha_y*loss_y`` ('xy') or ``loss_x`` ('x'), Adam through the
-HIP optimizer kernel, validation reconstruction losses every ``eval_every`` steps.  wandb and the CKA / mutual-kNN
-alignment metrics are outside the path."""
+HIP optimizer kernel, validation reconstruction losses every ``eval_every`` steps.  With ``alignment=True`` every eval
+also logs ``val_cka`` and ``val_mknn`` (topk 10) of the validation embeddings (main.py:78-84) through the HIP metric
+kernels; they stay device scalars until the log is read back at the end.  wandb is outside the path."""
 import torch
 from torch.utils.data import DataLoader
 
@@ -10,10 +11,13 @@ from .model import SharedAutoencoder
 
 
 def train_model_steps(model, data_loader, optimizer, num_steps, val_data_x, val_data_y, device, mode="xy", alpha_x=1.0,
-                      alpha_y=1.0, eval_every=1, on_step=None):
+                      alpha_y=1.0, eval_every=1, on_step=None, alignment=False):
     model.train()
     data_iter = iter(data_loader)
     log = {"loss_x": [], "loss_y": [], "loss": [], "val_loss_x": [], "val_loss_y": []}
+    if alignment:
+        from umlh import align
+        log.update(val_cka=[], val_mknn=[])
     for step in range(num_steps):
         try:
             batch = next(data_iter)
@@ -32,6 +36,9 @@ def train_model_steps(model, data_loader, optimizer, num_steps, val_data_x, val_
             with torch.no_grad():
                 vx, vy, _, _ = model(x=val_data_x, y=val_data_y)      # MSELoss(recon, data) of each view
                 log["val_loss_x"].append(vx.detach()); log["val_loss_y"].append(vy.detach())
+                if alignment:                                             # main.py:78-84
+                    ex, ey = model.get_embeddings(val_data_x, val_data_y)
+                    log["val_cka"].append(align.cka(ex, ey)); log["val_mknn"].append(align.mutual_knn(ex, ey, 10))
             model.train()
         if on_step is not None:
             on_step(step, loss_x, loss_y, loss)

@@ -12,6 +12,7 @@ from .head_engine import (HeadEngine, RowBatch, column_sums, gather_rows, grad_d
                           optimizer_step_multi,
                           random_permutation, to_bf16, train_steps_grouped)
 from .dp import DataParallelStepper  # noqa: F401,E402
+from . import align  # noqa: F401,E402
 
 
 def host_cpu_budget() -> int:

@@ -20,7 +20,7 @@ PREC_IDS = {"fp32": 0, "bf16": 1}
 N_CORE_SCALARS = 8
 N_SCALARS = 12
 
-SOURCES = ["umlh_p2p.hip", "umlh_kernels_f32.hip", "umlh_kernels_bf16.hip", "umlh_kernels_micro.hip", "umlh_kernels_seq.hip", "umlh_kernels_enc.hip", "umlh_api.cpp", "umlh_encoder.cpp"]
+SOURCES = ["umlh_p2p.hip", "umlh_kernels_f32.hip", "umlh_kernels_bf16.hip", "umlh_kernels_micro.hip", "umlh_kernels_seq.hip", "umlh_kernels_enc.hip", "umlh_kernels_align.hip", "umlh_api.cpp", "umlh_encoder.cpp"]
 EXPORTS = ["umlh_last_error", "umlh_version", "umlh_enable_diagnostics", "umlh_set_diagnostic_columns", "umlh_freeze_proj_row", "umlh_workspace_bytes", "umlh_create", "umlh_destroy", "umlh_bind",
            "umlh_zero_shot_init", "umlh_logits", "umlh_train_step", "umlh_grad_step", "umlh_grad_buffer",
            "umlh_apply_update", "umlh_eval_batch", "umlh_eval_rows", "umlh_project", "umlh_optimizer_step",
@@ -34,7 +34,8 @@ EXPORTS = ["umlh_last_error", "umlh_version", "umlh_enable_diagnostics", "umlh_s
            "umlh_encoder_layer_saved_floats", "umlh_encoder_layer_scratch_floats", "umlh_encoder_layer_forward",
            "umlh_encoder_layer_backward", "umlh_encoder_stack_forward", "umlh_encoder_stack_backward",
            "umlh_encoder_plan_floats", "umlh_encoder_plan_create", "umlh_encoder_plan_offsets", "umlh_encoder_plan_forward",
-           "umlh_encoder_plan_backward", "umlh_encoder_plan_destroy"]
+           "umlh_encoder_plan_backward", "umlh_encoder_plan_destroy",
+           "umlh_align_scratch_bytes", "umlh_align_knn", "umlh_align_mutual_knn", "umlh_align_cka"]
 
 
 class UmlhError(RuntimeError):
@@ -93,7 +94,7 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
     """Cross-compile the HIP sources for gfx950 into umlh/libumlh.so (in-tree, so the
     binary travels with the repo snapshot to the GPU box)."""
     srcs = [os.path.join(_CSRC, s) for s in SOURCES]
-    deps = srcs + [os.path.join(_CSRC, "umlh_common.h"), os.path.join(_CSRC, "umlh_micro.h"), os.path.join(_INCLUDE, "umlh.h")]
+    deps = srcs + [os.path.join(_CSRC, h) for h in ("umlh_common.h", "umlh_micro.h", "umlh_enc.h")] + [os.path.join(_INCLUDE, "umlh.h")]
     if not force and os.path.exists(_SO) and all(os.path.getmtime(_SO) >= os.path.getmtime(d) for d in deps):
         return _SO
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -207,11 +208,17 @@ def load_library():
     lib.umlh_seq_mse_backward_scratch_floats.argtypes = [i32, i32, i32, i32]
     lib.umlh_random_permutation.argtypes = [i64, u64, vp, vp]
     lib.umlh_debug_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
+    lib.umlh_align_scratch_bytes.restype = u64
+    lib.umlh_align_scratch_bytes.argtypes = [i64, i32, i32, i32, i32]
+    lib.umlh_align_knn.argtypes = [vp, i64, i32, i32, i32, i32, vp, vp, vp, u64, vp]
+    lib.umlh_align_mutual_knn.argtypes = [vp, vp, i64, i32, vp, vp, u64, vp]
+    lib.umlh_align_cka.argtypes = [vp, i32, i32, vp, i32, i32, i64, i32, vp, vp, u64, vp]
     lib.umlh_profile_enable.argtypes = [vp, C.c_int]
     lib.umlh_profile_read.argtypes = [vp, C.POINTER(C.c_float)]
     for name in EXPORTS:
         fn = getattr(lib, name)
-        if name not in ("umlh_last_error", "umlh_workspace_bytes", "umlh_encoder_layer_saved_floats", "umlh_encoder_layer_scratch_floats"):
+        if name not in ("umlh_last_error", "umlh_workspace_bytes", "umlh_encoder_layer_saved_floats", "umlh_encoder_layer_scratch_floats",
+                        "umlh_align_scratch_bytes"):
             fn.restype = C.c_int
     _LIB = lib
     return lib
