@@ -150,7 +150,7 @@ typedef struct {
 #define UMLH_N_SCALARS    12
 
 const char* umlh_last_error(void);
-int  umlh_version(void);        /* ABI revision: 3 = round 2 (grouped / micro / data-parallel / encoder-plan / InfoNCE entry points); 4 = round 3 (umlh_step_status / umlh_step_launches, umlh_p2p_*); 5 = umlh_align_* (CKA, k-NN, mutual k-NN) */
+int  umlh_version(void);        /* ABI revision: 3 = round 2 (grouped / micro / data-parallel / encoder-plan / InfoNCE entry points); 4 = round 3 (umlh_step_status / umlh_step_launches, umlh_p2p_*); 5 = umlh_align_* (CKA, k-NN, mutual k-NN); 6 = umlh_masked_mean, umlh_probe_* (linear probes of MultiBench evaluate) */
 
 /* Bytes of workspace a handle with this config needs (0 on invalid config). */
 uint64_t umlh_workspace_bytes(const umlh_config_t* cfg);
@@ -501,6 +501,56 @@ int  umlh_align_mutual_knn(const int32_t* knn_a, const int32_t* knn_b, int64_t n
  * out4 = {hsic_kl / (sqrt(hsic_kk * hsic_ll) + 1e-6), hsic_kl, hsic_kk, hsic_ll} in double; no 1/(n-1)^2 factor. */
 int  umlh_align_cka(const float* a, int32_t lda, int32_t d_a, const float* b, int32_t ldb, int32_t d_b, int64_t n,
                     int32_t splits, double* out4, void* scratch, uint64_t scratch_bytes, void* stream);
+
+/* ---- linear probes of the MultiBench evaluate() (MultiBench/train.py:31-91,93-240): masked mean pooling, StandardScaler
+ * statistics, an L2-regularised BINARY logistic regression fitted on the device, and its score.  Features are row-major fp32
+ * [n, d] with row stride ld >= d, labels int32 0/1.  Every argument check happens before any HIP call; everything runs on
+ * `stream`; outputs are device memory; results are bitwise reproducible (fixed-order double reductions, no float atomics). */
+
+#define UMLH_PROBE_LBFGS      0   /* LogisticRegression(max_iter=200): sum_i log(1 + exp(-t_i (w.x_i + b))) + |w|^2 / (2C) */
+#define UMLH_PROBE_LIBLINEAR  1   /* ... solver='liblinear': the intercept is penalised too, (|w|^2 + b^2) / (2C)          */
+
+/* What a fit leaves behind (device memory, 24 bytes). */
+typedef struct {
+    int32_t iterations;   /* accepted Newton steps                                                                       */
+    int32_t converged;    /* 0: iteration budget spent, or the inputs made the gradient NaN; 1: max|gradient| <= gtol;
+                           * 2: the precision floor of the objective: the last accepted step gained less than 1e-11 |f|
+                           *    (Newton's next gain is the square of that), or the predicted gain fell below 8 ulp of f,
+                           *    or no step length gave a representable decrease with less than 1e-10 |f| predicted      */
+    double  max_grad;     /* max |gradient| of the objective at the returned coefficients                                */
+    double  objective;    /* the objective there                                                                         */
+} umlh_probe_record_t;
+
+/* out[b, :] = sum_{t < L_b} z[b, t, :] / L_b with L_b = min(max(lengths[b], 0), t_len) (train.py:120-125); lengths = NULL:
+ * the plain mean over t_len (evaluate_raw_data's x.mean(axis=1)).  z[b, t, c] is read at z[b*ldb + t*ldt + c] (floats; any
+ * strides >= zdim, so a [T, B, Z] block is pooled in place), out[b, c] written at out[b*ldo + c].  L_b = 0 gives NaN like
+ * the reference's 0/0.  One fp32 chain per element, t ascending. */
+int  umlh_masked_mean(const float* z, int32_t b, int32_t t_len, int32_t zdim, int64_t ldb, int64_t ldt, const int64_t* lengths,
+                      float* out, int32_t ldo, void* stream);
+/* Scratch bytes for umlh_probe_fit (max_iter >= 1) or umlh_probe_column_stats (max_iter = 0) at these sizes: 20 n bytes of
+ * O(n) vectors + O(d^2) tiles, no n x d term.  0 on invalid arguments (n < 2 or >= 2^31, d outside 1..1024, max_iter
+ * outside 0..1000). */
+uint64_t umlh_probe_scratch_bytes(int64_t n, int32_t d, int32_t max_iter);
+/* StandardScaler().fit(x): stats[0..d) = column means, stats[d..2d) = population standard deviations (ddof = 0), a value
+ * below 10 * DBL_EPSILON replaced by 1 as sklearn does.  Two passes in double, fixed order. */
+int  umlh_probe_column_stats(const float* x, int64_t n, int32_t d, int32_t ldx, double* stats, void* scratch,
+                             uint64_t scratch_bytes, void* stream);
+/* Fits the optimum of the `kind` objective with x~ = [x, 1], t = 2y - 1 and inverse regularisation c by a damped Newton
+ * iteration from w = 0: the gradient X~^T (p - y) + R w and the objective are summed in double in a fixed order, the
+ * Hessian X~^T diag(p (1 - p)) X~ + R comes off the fp32 MFMA and only shapes the step, and a step is accepted only with
+ * sufficient decrease of the objective (step lengths 1, 1/2, ..., 2^-11).  stats (NULL or the 2d doubles of
+ * umlh_probe_column_stats) standardises x on load; the coefficients then live in the standardised space, as sklearn's
+ * pipeline keeps them.  coef[0..d) = w, coef[d] = intercept (device doubles, also the iterate while the fit runs).
+ * The call enqueues a fixed train of launches for max_iter iterations and returns; once the device-side test fires the
+ * remaining launches return at once.  objectives: NULL or max_iter + 1 doubles, objective after k accepted steps (NaN
+ * beyond the last).  Each fit in flight needs its own scratch, coef and record.  1 <= d <= 1024, 2 <= n < 2^31. */
+int  umlh_probe_fit(const float* x, int64_t n, int32_t d, int32_t ldx, const int32_t* y, const double* stats, int32_t kind,
+                    double c, int32_t max_iter, double gtol, double* coef, umlh_probe_record_t* record, double* objectives,
+                    void* scratch, uint64_t scratch_bytes, void* stream);
+/* decision_i = coef . x~_i (fp32 products on the MFMA, standardised on load when stats is given); prediction 1 iff
+ * decision > 0.  decision: NULL or n floats.  correct: NULL or one int64 = #{i : prediction_i == y_i} (y required then). */
+int  umlh_probe_score(const float* x, int64_t n, int32_t d, int32_t ldx, const double* stats, const double* coef,
+                      const int32_t* y, int64_t* correct, float* decision, void* stream);
 
 #ifdef __cplusplus
 }

@@ -286,7 +286,7 @@ static inline void mark(umlh_handle_t h, int i, hipStream_t st) {
 }
 
 const char* umlh_last_error(void) { return g_err; }
-int umlh_version(void) { return 5; }   // 3: round 2 (grouped / micro / data-parallel / encoder-plan / InfoNCE entry points, umlh_enc_layer_t.seed_device, umlh_seq_mse_backward scratch); 4: round 3 (umlh_step_status / _launches, umlh_p2p_*); 5: umlh_align_*
+int umlh_version(void) { return 6; }   // 3: round 2 (grouped / micro / data-parallel / encoder-plan / InfoNCE entry points, umlh_enc_layer_t.seed_device, umlh_seq_mse_backward scratch); 4: round 3 (umlh_step_status / _launches, umlh_p2p_*); 5: umlh_align_*; 6: umlh_masked_mean, umlh_probe_*
 
 int umlh_freeze_proj_row(umlh_handle_t h, int32_t row) {
     if (!h) return fail(UMLH_E_INVALID, "umlh_freeze_proj_row: null handle");
@@ -1990,4 +1990,79 @@ int umlh_eval_rows(umlh_handle_t h, const umlh_batch_t* b, float* row_stats, voi
     rc = forward_backward(h, b, nullptr, &hy, false, (hipStream_t)stream, &sh, &sp);
     h->row_stats = nullptr;
     return rc;
+}
+
+// ---- linear probes (kernels: umlh_kernels_probe.hip); every check precedes the first HIP call ----
+extern "C" {
+unsigned long long umlh_probe_fit_bytes(long long n, int d, int max_iter);
+unsigned long long umlh_probe_stats_bytes(int d);
+int umlh_probe_launch_masked_mean(const float* z, int B, int T, int Z, long long ldb, long long ldt, const long long* lengths,
+                                  float* out, int ldo, hipStream_t st);
+int umlh_probe_launch_stats(const float* x, long long n, int d, int ldx, double* stats, void* scratch, hipStream_t st);
+int umlh_probe_launch_fit(const float* x, long long n, int d, int ldx, const int* y, const double* stats, int kind, double c,
+                          int max_iter, double gtol, double* coef, umlh_probe_record_t* rec, double* objectives, void* scratch,
+                          hipStream_t st);
+int umlh_probe_launch_score(const float* x, long long n, int d, int ldx, const double* stats, const double* coef, const int* y,
+                            long long* correct, float* decision, hipStream_t st);
+}
+
+static const int PROBE_MAX_D = 1024, PROBE_MAX_ITER = 1000;
+static bool probe_shape_ok(int64_t n, int32_t d, int32_t ldx) { return n >= 2 && n < ((int64_t)1 << 31) && d >= 1 && d <= PROBE_MAX_D && ldx >= d; }
+
+int umlh_masked_mean(const float* z, int32_t b, int32_t t_len, int32_t zdim, int64_t ldb, int64_t ldt, const int64_t* lengths,
+                     float* out, int32_t ldo, void* stream) {
+    if (!z || !out) return fail(UMLH_E_INVALID, "umlh_masked_mean: null pointer (z and out are required)");
+    if (b < 1 || t_len < 1 || zdim < 1) return fail(UMLH_E_INVALID, "umlh_masked_mean: b=%d t_len=%d zdim=%d (need all >= 1)", b, t_len, zdim);
+    if (ldb < zdim || ldt < zdim || ldo < zdim)
+        return fail(UMLH_E_INVALID, "umlh_masked_mean: ldb=%lld ldt=%lld ldo=%d (need every stride >= zdim=%d)", (long long)ldb, (long long)ldt, ldo, zdim);
+    HIPCHK(umlh_probe_launch_masked_mean(z, b, t_len, zdim, ldb, ldt, (const long long*)lengths, out, ldo, (hipStream_t)stream), "umlh_masked_mean");
+    return UMLH_OK;
+}
+
+uint64_t umlh_probe_scratch_bytes(int64_t n, int32_t d, int32_t max_iter) {
+    if (!probe_shape_ok(n, d, d) || max_iter < 0 || max_iter > PROBE_MAX_ITER) return 0;
+    return max_iter == 0 ? umlh_probe_stats_bytes(d) : umlh_probe_fit_bytes(n, d, max_iter);
+}
+
+int umlh_probe_column_stats(const float* x, int64_t n, int32_t d, int32_t ldx, double* stats, void* scratch, uint64_t scratch_bytes,
+                            void* stream) {
+    if (!x || !stats || !scratch) return fail(UMLH_E_INVALID, "umlh_probe_column_stats: null pointer (x, stats and scratch are required)");
+    if (!probe_shape_ok(n, d, ldx))
+        return fail(UMLH_E_INVALID, "umlh_probe_column_stats: n=%lld d=%d ldx=%d (need 2 <= n < 2^31, 1 <= d <= 1024, ldx >= d)", (long long)n, d, ldx);
+    const uint64_t need = umlh_probe_stats_bytes(d);
+    if (scratch_bytes < need)
+        return fail(UMLH_E_INVALID, "umlh_probe_column_stats: scratch of %llu bytes, %llu needed", (unsigned long long)scratch_bytes, (unsigned long long)need);
+    HIPCHK(umlh_probe_launch_stats(x, n, d, ldx, stats, scratch, (hipStream_t)stream), "umlh_probe_column_stats");
+    return UMLH_OK;
+}
+
+int umlh_probe_fit(const float* x, int64_t n, int32_t d, int32_t ldx, const int32_t* y, const double* stats, int32_t kind, double c,
+                   int32_t max_iter, double gtol, double* coef, umlh_probe_record_t* record, double* objectives, void* scratch,
+                   uint64_t scratch_bytes, void* stream) {
+    if (!x || !y || !coef || !record || !scratch)
+        return fail(UMLH_E_INVALID, "umlh_probe_fit: null pointer (x, y, coef, record and scratch are required)");
+    if (!probe_shape_ok(n, d, ldx))
+        return fail(UMLH_E_INVALID, "umlh_probe_fit: n=%lld d=%d ldx=%d (need 2 <= n < 2^31, 1 <= d <= 1024, ldx >= d)", (long long)n, d, ldx);
+    if (kind != UMLH_PROBE_LBFGS && kind != UMLH_PROBE_LIBLINEAR) return fail(UMLH_E_INVALID, "umlh_probe_fit: kind=%d (0 = lbfgs, 1 = liblinear objective)", kind);
+    if (!(c > 0.0) || !(c < 1e300)) return fail(UMLH_E_INVALID, "umlh_probe_fit: c=%g (need a finite c > 0)", c);
+    if (max_iter < 1 || max_iter > PROBE_MAX_ITER) return fail(UMLH_E_INVALID, "umlh_probe_fit: max_iter=%d outside 1..%d", max_iter, PROBE_MAX_ITER);
+    if (!(gtol >= 0.0)) return fail(UMLH_E_INVALID, "umlh_probe_fit: gtol=%g (need gtol >= 0)", gtol);
+    const uint64_t need = umlh_probe_fit_bytes(n, d, max_iter);
+    if (scratch_bytes < need)
+        return fail(UMLH_E_INVALID, "umlh_probe_fit: scratch of %llu bytes, %llu needed", (unsigned long long)scratch_bytes, (unsigned long long)need);
+    if ((reinterpret_cast<uintptr_t>(scratch) & 7) != 0) return fail(UMLH_E_INVALID, "umlh_probe_fit: scratch must be 8-byte aligned");
+    HIPCHK(umlh_probe_launch_fit(x, n, d, ldx, y, stats, kind, c, max_iter, gtol, coef, record, objectives, scratch, (hipStream_t)stream),
+           "umlh_probe_fit");
+    return UMLH_OK;
+}
+
+int umlh_probe_score(const float* x, int64_t n, int32_t d, int32_t ldx, const double* stats, const double* coef, const int32_t* y,
+                     int64_t* correct, float* decision, void* stream) {
+    if (!x || !coef) return fail(UMLH_E_INVALID, "umlh_probe_score: null pointer (x and coef are required)");
+    if (!correct && !decision) return fail(UMLH_E_INVALID, "umlh_probe_score: nothing to compute (correct and decision are both NULL)");
+    if (correct && !y) return fail(UMLH_E_INVALID, "umlh_probe_score: correct needs the labels y");
+    if (!(n >= 1 && n < ((int64_t)1 << 31) && d >= 1 && d <= PROBE_MAX_D && ldx >= d))
+        return fail(UMLH_E_INVALID, "umlh_probe_score: n=%lld d=%d ldx=%d (need 1 <= n < 2^31, 1 <= d <= 1024, ldx >= d)", (long long)n, d, ldx);
+    HIPCHK(umlh_probe_launch_score(x, n, d, ldx, stats, coef, y, (long long*)correct, decision, (hipStream_t)stream), "umlh_probe_score");
+    return UMLH_OK;
 }

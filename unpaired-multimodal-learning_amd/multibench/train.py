@@ -1,11 +1,177 @@
 """The MultiBench unpaired alternation loop (reference: MultiBench/train.py:354-399): two
 INDEPENDENTLY shuffled loaders zipped, x loss switched off while epoch <= step_k in 'xy' mode,
-loss = alpha_x*loss_x + alpha_y*loss_y, one optimizer step per batch pair.  The per-batch
-diagnostics of the reference (covariance / svdvals effective rank, wandb, sklearn probes:
-train.py:386-389,428-443) are outside the hot path."""
+loss = alpha_x*loss_x + alpha_y*loss_y, one optimizer step per batch pair, and the reference's
+``evaluate`` / ``evaluate_raw_data`` (train.py:31-240): every train / val / test batch through the model
+in eval mode, masked-mean pooling and binary logistic probes, all on the HIP kernels of ``umlh.probe``.
+The other per-batch diagnostics of the reference (covariance / svdvals effective rank, wandb, the
+embedding capture: train.py:386-389,428-443,452-515) are outside this port."""
 from __future__ import annotations
 
+import copy
+
+import numpy as np
 import torch
+
+
+# ---- labels (train.py:18-29) ----
+def mosi_label(y_batch):
+    """MOSI / MOSEI sentiment -> 0/1: >= 0 (which -0.0 is) becomes 1, < 0 becomes 0; NaN stays."""
+    res = copy.deepcopy(y_batch)
+    res[y_batch >= 0] = 1
+    res[y_batch < 0] = 0
+    return res
+
+
+def sarcasm_label(y_batch):
+    """Sarcasm / humor -1/+1 -> 0/1: only -1 is rewritten."""
+    res = copy.deepcopy(y_batch)
+    res[y_batch == -1] = 0
+    return res
+
+
+_LABELS = {"mosi": mosi_label, "mosei": mosi_label, "sarcasm": sarcasm_label, "humor": sarcasm_label}
+_NAN_KEYS = [f"{t}/score_{k}" for k in ("x_private", "y_private", "x_complete", "y_complete", "xy_complete") for t in ("test", "val")]
+_TYPES = ("train", "val", "test")
+
+
+def _label_fn(ds_name):
+    if ds_name not in _LABELS:                       # the reference accepts no other name here ('mimic' included)
+        raise NotImplementedError("Dataset not implemented yet")
+    return _LABELS[ds_name]
+
+
+def _labels01(batches, ds_name):
+    """0/1 int64 labels of one split on the host (train.py:41-47)."""
+    fn = _label_fn(ds_name)
+    lab = np.concatenate([np.asarray(b[3].detach().cpu().numpy() if isinstance(b[3], torch.Tensor) else b[3]) for b in batches])
+    return np.asarray(fn(lab)).reshape(-1).astype(int)
+
+
+def _two_classes(y, what):
+    """The check sklearn makes before a fit; here on the host labels, so that the fits need no read-back."""
+    if len(np.unique(y)) < 2:
+        raise ValueError(f"This solver needs samples of at least 2 classes in the data, but the data contains only one class: {y[0]!r} ({what})")
+    if y.min() < 0 or y.max() > 1:
+        raise ValueError(f"{what}: the probes are binary, got labels {np.unique(y)[:5]}")
+
+
+def _kind(ds_name):
+    return "liblinear" if ds_name == "mosi" else "lbfgs"         # train.py:97-99
+
+
+class _Probes:
+    """The fits and scores of one evaluate call: everything is enqueued first, ``read`` brings all counts back at once."""
+
+    def __init__(self, ds_name, dev):
+        self.kind, self.dev = _kind(ds_name), dev
+        self.counts, self.names, self.rows, self.clfs = [], [], [], []
+
+    def fit(self, X, y):
+        from umlh.probe import LogisticProbe
+        self.clfs.append(LogisticProbe(self.kind).fit(X, y, check_classes=False))
+        return self.clfs[-1]
+
+    def score(self, name, clf, X, y):
+        self.counts.append(clf.correct(X, y))
+        self.names.append(name)
+        self.rows.append(X.shape[0])
+
+    def read(self):
+        got = torch.stack(self.counts).cpu().tolist()
+        return {k: c / n for k, c, n in zip(self.names, got, self.rows)}
+
+
+def _fit_three(pr, emb, lab, z, tag=""):
+    """The x, y and xy probes (train.py:163-183): fitted on train, scored on val and test.  emb[t] is [N_t, zx + zy] with
+    the x block in the first zx columns: the three feature sets are views of it (the row stride travels to the kernels)."""
+    ytr = torch.from_numpy(lab["train"]).to(pr.dev)
+    yev = {t: torch.from_numpy(lab[t]).to(pr.dev) for t in ("val", "test")}
+    for name, cols in (("x", slice(0, z[0])), ("y", slice(z[0], z[0] + z[1])), ("xy", slice(0, z[0] + z[1]))):
+        clf = pr.fit(emb["train"][:, cols], ytr)
+        for t in ("val", "test"):
+            pr.score(f"{t}/score_{name}{tag}", clf, emb[t][:, cols], yev[t])
+
+
+def evaluate_raw_data(config, ds_name="mosi", device=None, return_probes=False):
+    """The raw-feature baselines (train.py:31-91): each modality's plain mean over time, probes on x, y and [x, y].
+    ``return_probes`` adds the pooled [N, dx + dy] device matrices per split and the three fitted probes."""
+    import umlh
+    lab = {t: _labels01(config[t], ds_name) for t in _TYPES}
+    _two_classes(lab["train"], "train labels")
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    with torch.cuda.device(dev):
+        emb, dims = {}, None
+        for t in _TYPES:
+            n = sum(b[0][0].shape[0] for b in config[t])
+            dims = (config[t][0][0][0].shape[-1], config[t][0][0][2].shape[-1])
+            emb[t] = torch.empty((n, dims[0] + dims[1]), dtype=torch.float32, device=dev)
+            off = 0
+            for b in config[t]:
+                x, y = b[0][0], b[0][2]
+                bs = x.shape[0]
+                umlh.masked_mean(x.float(), None, out=emb[t][off:off + bs, :dims[0]])
+                umlh.masked_mean(y.float(), None, out=emb[t][off:off + bs, dims[0]:])
+                off += bs
+        pr = _Probes(ds_name, dev)
+        _fit_three(pr, emb, lab, dims, tag="_raw")
+        got = pr.read()
+    results = {k: got[k] for k in ("val/score_x_raw", "val/score_y_raw", "test/score_x_raw", "test/score_y_raw", "test/score_xy_raw",
+                                   "val/score_xy_raw")}
+    return (results, emb, pr.clfs) if return_probes else results
+
+
+@torch.no_grad()
+def evaluate(model, config, ds_name="mosi", device="cuda:0", return_embeddings=False):
+    """The reference's evaluate (train.py:93-240) with its batch layout and result keys.  The model forward is this
+    project's eval-mode mirror; pooling, scaler statistics, fits and scores are HIP kernels, the embeddings never leave
+    the device, and all six fits (three modality-separation probes, x, y, xy) are enqueued before anything is read back.
+    The reference shuffles the rows of the modality-separation probe with np.random.permutation; the optimum of a fit does
+    not depend on row order, so no shuffle is done here.  ``separate`` is False in the reference: the *_private and
+    *_complete keys are NaN there and here.  ``return_embeddings`` adds the pooled [N, zx + zy] device matrices per split
+    and the fitted probes (separation x 3, x, y, xy)."""
+    import umlh
+    _label_fn(ds_name)
+    dev = torch.device(device)
+    model.eval()
+    lab = {t: _labels01(config[t], ds_name) for t in _TYPES}
+    _two_classes(lab["train"], "train labels")
+    emb, loss, z = {}, {}, None
+    with torch.cuda.device(dev):
+        for t in _TYPES:
+            outs, lens = [], []
+            for b in config[t]:
+                x, y, lx, ly = b[0][0], b[0][2], b[1][0].to(dev), b[1][2].to(dev)
+                outs.append(model(x.to(dev), y.to(dev), x_lengths=lx, y_lengths=ly))
+                lens.append((lx, ly))
+            z = (outs[0]["zx"].shape[-1], outs[0]["zy"].shape[-1])
+            if z[0] != z[1]:
+                raise ValueError(f"evaluate: zx and zy have different widths {z}; the modality-separation probe stacks them")
+            n = sum(o["zx"].shape[0] for o in outs)
+            emb[t] = torch.empty((n, z[0] + z[1]), dtype=torch.float32, device=dev)
+            off = 0
+            for o, (lx, ly) in zip(outs, lens):
+                bs = o["zx"].shape[0]
+                umlh.masked_mean(o["zx"], lx, out=emb[t][off:off + bs, :z[0]])
+                umlh.masked_mean(o["zy"], ly, out=emb[t][off:off + bs, z[0]:])
+                off += bs
+            loss[t] = (torch.stack([o["loss_x"].reshape(()) for o in outs]).double().mean(),
+                       torch.stack([o["loss_y"].reshape(()) for o in outs]).double().mean())
+        pr = _Probes(ds_name, dev)
+        for t in _TYPES:                                            # which modality a pooled embedding came from (train.py:146-151)
+            n = emb[t].shape[0]
+            both = torch.cat([emb[t][:, :z[0]], emb[t][:, z[0]:]], dim=0)
+            which = torch.cat([torch.zeros(n, dtype=torch.int32, device=dev), torch.ones(n, dtype=torch.int32, device=dev)])
+            pr.score(f"sep/{t}", pr.fit(both, which), both, which)
+        _fit_three(pr, emb, lab, z)
+        got = pr.read()
+        losses = torch.stack([loss["val"][0], loss["test"][0], loss["val"][1], loss["test"][1]]).cpu().tolist()
+    results = {"val/modality_separate": float(np.mean([got[f"sep/{t}"] for t in _TYPES]))}
+    results.update({k: got[k] for k in ("test/score_x", "test/score_y", "test/score_xy", "val/score_x", "val/score_y", "val/score_xy")})
+    results.update({k: float("nan") for k in _NAN_KEYS})
+    results.update({"val/loss_x": losses[0], "test/loss_x": losses[1], "val/loss_y": losses[2], "test/loss_y": losses[3]})
+    if return_embeddings:
+        return results, emb, pr.clfs
+    return results
 
 
 def alternation_alphas(epoch, step_k, train_mode, alpha_x=1.0, alpha_y=1.0):
@@ -26,10 +192,24 @@ def train(model, train_mode, train_loader_1, train_loader_2, optimizer, modaliti
           ds_name="mosi", eval_config={}, alpha_x=1.0, alpha_y=1.0, capture_embeddings_during_training=False, augment=False,
           debug=False, args=None, device="cuda:0", on_step=None):
     """Returns {'loss_x': [...], 'loss_y': [...], 'loss': [...]} with one entry per batch pair
-    (device tensors are read back once at the end)."""
+    (device tensors are read back once at the end).  With a non-empty ``eval_config`` ({'train', 'val', 'test': batch
+    lists, 'freq': int}) it evaluates as the reference does (train.py:350,440-451,519-523): ``evaluate_raw_data`` once,
+    ``evaluate`` whenever i_batch % freq == 0 and once more after the last epoch, the model back in train mode after
+    each; the dict then also holds 'raw' and 'eval' = [(epoch, i_batch, results), ...], where results are what the
+    reference logs (evaluate's keys without the *_private / *_complete ones, plus the raw baselines) and the closing
+    evaluation is the entry with i_batch = None."""
     model.train()
     dev = torch.device(device)
     rec_x, rec_y, rec_l = [], [], []
+    raw_results, evals = None, []
+    if eval_config:
+        raw_results = evaluate_raw_data(eval_config, ds_name=ds_name, device=device)
+
+    def logged(score):
+        out = {k: v for k, v in score.items() if not ("private" in k or "complete" in k)}
+        out.update(raw_results)
+        return out
+
     for epoch in range(num_epoch):
         alphas = alternation_alphas(epoch, step_k, train_mode, alpha_x, alpha_y)
         for i_batch, (b1, b2) in enumerate(zip(train_loader_1, train_loader_2)):
@@ -50,5 +230,14 @@ def train(model, train_mode, train_loader_1, train_loader_2, optimizer, modaliti
             rec_l.append(loss.detach())
             if on_step is not None:
                 on_step(epoch, i_batch, out, loss)
+            if eval_config and i_batch % eval_config["freq"] == 0:
+                evals.append((epoch, i_batch, logged(evaluate(model, eval_config, ds_name, device=device))))
+                model.train()
+        if eval_config and epoch == num_epoch - 1:
+            evals.append((epoch, None, logged(evaluate(model, eval_config, ds_name, device=device))))
+            model.train()
     stack = lambda v: torch.stack([t.reshape(()) for t in v]).cpu().tolist() if v else []
-    return {"loss_x": stack(rec_x), "loss_y": stack(rec_y), "loss": stack(rec_l)}
+    res = {"loss_x": stack(rec_x), "loss_y": stack(rec_y), "loss": stack(rec_l)}
+    if eval_config:
+        res["raw"], res["eval"] = raw_results, evals
+    return res

@@ -13,6 +13,8 @@ from .head_engine import (HeadEngine, RowBatch, column_sums, gather_rows, grad_d
                           random_permutation, to_bf16, train_steps_grouped)
 from .dp import DataParallelStepper  # noqa: F401,E402
 from . import align  # noqa: F401,E402
+from . import probe  # noqa: F401,E402
+from .probe import LogisticProbe, masked_mean  # noqa: F401,E402
 
 
 def host_cpu_budget() -> int:

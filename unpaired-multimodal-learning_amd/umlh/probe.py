@@ -1,0 +1,206 @@
+"""Linear probes on the HIP kernels of umlh_kernels_probe.hip (C ABI: ``umlh_masked_mean``, ``umlh_probe_*``).
+
+``masked_mean`` is the length-masked mean pooling of the reference's MultiBench ``evaluate`` (train.py:120-125) and, with
+``lengths=None``, the plain ``mean(axis=1)`` of ``evaluate_raw_data``.  ``LogisticProbe`` is the binary
+``LogisticRegression`` that ``evaluate`` fits (train.py:97-99): ``kind='lbfgs'`` for ``LogisticRegression(max_iter=200)``,
+``kind='liblinear'`` for ``make_pipeline(StandardScaler(), LogisticRegression(max_iter=1000, solver='liblinear'))``.  It
+returns the optimum of sklearn's objective, not sklearn's last iterate.  Every call enqueues on
+``torch.cuda.current_stream`` and returns without synchronising; only the ``n_iter_`` / ``converged_`` / ``score``
+accessors read device memory back.  Inputs follow ``umlh.align``: fp32 CUDA tensors with unit column stride are used in
+place (the row stride is passed on), other float dtypes are upcast, CPU tensors copied.  There is no CPU compute path.
+"""
+from __future__ import annotations
+
+import torch
+
+from ._lib import UmlhError, check, load_library
+from .align import _device, _features, _stream
+
+KINDS = {"lbfgs": 0, "liblinear": 1}
+MAX_FEATURES = 1024
+
+
+def masked_mean(z: torch.Tensor, lengths: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """[B, T, Z] -> fp32 [B, Z] on the device: sum_{t < len_b} z[b, t] / len_b (len_b clipped to 0..T; 0 gives NaN as the
+    reference's 0/0).  ``lengths=None``: the mean over T.  ``out``: an fp32 device view [B, Z] with unit column stride to
+    write into (a column block of a wider matrix, for instance)."""
+    if not isinstance(z, torch.Tensor) or z.ndim != 3:
+        raise ValueError(f"masked_mean: expected a 3-D tensor [B, T, Z], got {getattr(z, 'shape', type(z))}")
+    if not z.is_floating_point():
+        raise ValueError(f"masked_mean: expected a floating-point tensor, got {z.dtype}")
+    B, T, Z = z.shape
+    if B < 1 or T < 1 or Z < 1:
+        raise ValueError(f"masked_mean: empty input {tuple(z.shape)}")
+    dev = _device()
+    z = z.detach().to(device=dev, dtype=torch.float32)
+    if z.stride(2) != 1 or z.stride(0) < Z or z.stride(1) < Z:
+        z = z.contiguous()
+    if lengths is not None:
+        if lengths.numel() != B:
+            raise ValueError(f"masked_mean: {lengths.numel()} lengths for {B} sequences")
+        lengths = lengths.detach().reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
+    if out is None:
+        out = torch.empty((B, Z), dtype=torch.float32, device=dev)
+    elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (B, Z) and out.stride(1) == 1 and out.stride(0) >= Z):
+        raise ValueError("masked_mean: out must be an fp32 device view [B, Z] with unit column stride")
+    check(load_library().umlh_masked_mean(z.data_ptr(), B, T, Z, z.stride(0), z.stride(1),
+                                          lengths.data_ptr() if lengths is not None else None, out.data_ptr(), out.stride(0),
+                                          _stream(dev)), "umlh_masked_mean")
+    return out
+
+
+def _scratch(lib, n, d, max_iter, dev):
+    nbytes = lib.umlh_probe_scratch_bytes(n, d, max_iter)
+    if nbytes == 0:
+        raise UmlhError(f"umlh_probe_scratch_bytes: invalid arguments n={n} d={d} max_iter={max_iter}")
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes
+
+
+def column_stats(x: torch.Tensor) -> torch.Tensor:
+    """StandardScaler().fit(x) as a float64 device tensor [2, d]: column means, then population standard deviations with
+    values below 10 eps replaced by 1."""
+    dev = _device()
+    x = _features(x, "column_stats", dev)
+    n, d = x.shape
+    lib = load_library()
+    scratch, nbytes = _scratch(lib, n, d, 0, dev)
+    stats = torch.empty((2, d), dtype=torch.float64, device=dev)
+    check(lib.umlh_probe_column_stats(x.data_ptr(), n, d, x.stride(0), stats.data_ptr(), scratch.data_ptr(), nbytes, _stream(dev)),
+          "umlh_probe_column_stats")
+    return stats
+
+
+def _labels(y, n, dev, what):
+    if not isinstance(y, torch.Tensor):
+        y = torch.as_tensor(y)
+    if y.numel() != n:
+        raise ValueError(f"{what}: {y.numel()} labels for {n} rows")
+    return y.detach().reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+
+
+class LogisticProbe:
+    """Binary L2-regularised logistic regression fitted by the device-side Newton iteration of ``umlh_probe_fit``.
+
+    ``fit`` only enqueues; ``coef_`` ([1, d] float64) and ``intercept_`` ([1] float64) are device tensors (in the
+    standardised space for ``kind='liblinear'``, as sklearn's pipeline keeps them).  ``record()`` reads the device record
+    back: ``n_iter_``, ``converged_`` (0 = budget spent, 1 = max|gradient| <= gtol, 2 = the objective's precision floor),
+    ``max_grad_``, ``objective_``."""
+
+    def __init__(self, kind: str = "lbfgs", C: float = 1.0, max_iter: int = 30, gtol: float = 0.0, keep_objectives: bool = False):
+        if kind not in KINDS:
+            raise ValueError(f"LogisticProbe: kind={kind!r} not in {sorted(KINDS)}")
+        if not C > 0:
+            raise ValueError(f"LogisticProbe: C={C} must be positive")
+        if not 1 <= int(max_iter) <= 1000:
+            raise ValueError(f"LogisticProbe: max_iter={max_iter} outside 1..1000")
+        if not gtol >= 0:
+            raise ValueError(f"LogisticProbe: gtol={gtol} must be >= 0")
+        self.kind, self.C, self.max_iter, self.gtol, self.keep_objectives = kind, float(C), int(max_iter), float(gtol), keep_objectives
+        self._coef = self._record = self._stats = self._objectives = self._keep = self._host = None
+
+    def fit(self, X: torch.Tensor, y, check_classes: bool = True) -> "LogisticProbe":
+        """Enqueues the fit.  ``check_classes`` reads one flag back to raise ``ValueError`` when ``y`` holds a single class
+        (as sklearn does) or a label other than 0/1; pass False when the labels are known to be sound and the caller wants
+        no host synchronisation."""
+        dev = _device()
+        x = _features(X, "LogisticProbe.fit", dev)
+        n, d = x.shape
+        if n < 2:
+            raise ValueError(f"LogisticProbe.fit: needs at least 2 rows, got {n}")
+        if d > MAX_FEATURES:
+            raise ValueError(f"LogisticProbe.fit: d={d} above {MAX_FEATURES}")
+        yy = _labels(y, n, dev, "LogisticProbe.fit")
+        if check_classes:
+            lo, hi = (int(v) for v in torch.stack([yy.min(), yy.max()]).tolist())
+            if lo < 0 or hi > 1:
+                raise ValueError(f"LogisticProbe.fit: labels must be 0/1, got values in [{lo}, {hi}]")
+            if lo == hi:
+                raise ValueError(f"This solver needs samples of at least 2 classes in the data, but the data contains only one class: {lo}")
+        lib = load_library()
+        self._stats = column_stats(x) if self.kind == "liblinear" else None
+        scratch, nbytes = _scratch(lib, n, d, self.max_iter, dev)
+        self._coef = torch.empty(d + 1, dtype=torch.float64, device=dev)
+        self._record = torch.empty(24, dtype=torch.uint8, device=dev)
+        self._objectives = torch.empty(self.max_iter + 1, dtype=torch.float64, device=dev) if self.keep_objectives else None
+        check(lib.umlh_probe_fit(x.data_ptr(), n, d, x.stride(0), yy.data_ptr(),
+                                 self._stats.data_ptr() if self._stats is not None else None, KINDS[self.kind], self.C,
+                                 self.max_iter, self.gtol, self._coef.data_ptr(), self._record.data_ptr(),
+                                 self._objectives.data_ptr() if self._objectives is not None else None, scratch.data_ptr(), nbytes,
+                                 _stream(dev)), "umlh_probe_fit")
+        self._keep = (x, yy, scratch)          # this fit's own operands and scratch, alive as long as the probe
+        self._host = None
+        return self
+
+    def _fitted(self):
+        if self._coef is None:
+            raise UmlhError("LogisticProbe: fit() has not been called")
+
+    @property
+    def coef_(self) -> torch.Tensor:
+        self._fitted()
+        return self._coef[:-1].reshape(1, -1)
+
+    @property
+    def intercept_(self) -> torch.Tensor:
+        self._fitted()
+        return self._coef[-1:]
+
+    @property
+    def stats_(self):
+        """None, or the [2, d] float64 StandardScaler statistics of the 'liblinear' kind."""
+        return self._stats
+
+    def record(self) -> dict:
+        self._fitted()
+        if self._host is None:
+            raw = self._record.cpu().numpy()
+            self._host = {"n_iter": int(raw[0:4].view("<i4")[0]), "converged": int(raw[4:8].view("<i4")[0]),
+                          "max_grad": float(raw[8:16].view("<f8")[0]), "objective": float(raw[16:24].view("<f8")[0])}
+        return self._host
+
+    n_iter_ = property(lambda self: self.record()["n_iter"])
+    converged_ = property(lambda self: self.record()["converged"])
+    max_grad_ = property(lambda self: self.record()["max_grad"])
+    objective_ = property(lambda self: self.record()["objective"])
+
+    @property
+    def objectives_(self) -> torch.Tensor:
+        """The objective after 0, 1, ... accepted steps (float64 device tensor); needs ``keep_objectives=True``."""
+        self._fitted()
+        if self._objectives is None:
+            raise UmlhError("LogisticProbe: constructed without keep_objectives=True")
+        return self._objectives[: self.n_iter_ + 1]
+
+    def _score(self, X, y, want_decision, want_correct):
+        self._fitted()
+        dev = _device()
+        x = _features(X, "LogisticProbe", dev)
+        n, d = x.shape
+        if d != self._coef.numel() - 1:
+            raise ValueError(f"LogisticProbe: {d} features, fitted on {self._coef.numel() - 1}")
+        yy = _labels(y, n, dev, "LogisticProbe.score") if want_correct else None
+        dec = torch.empty(n, dtype=torch.float32, device=dev) if want_decision else None
+        correct = torch.empty((), dtype=torch.int64, device=dev) if want_correct else None
+        check(load_library().umlh_probe_score(x.data_ptr(), n, d, x.stride(0),
+                                              self._stats.data_ptr() if self._stats is not None else None, self._coef.data_ptr(),
+                                              yy.data_ptr() if yy is not None else None,
+                                              correct.data_ptr() if correct is not None else None,
+                                              dec.data_ptr() if dec is not None else None, _stream(dev)), "umlh_probe_score")
+        return dec, correct, n
+
+    def decision_function(self, X: torch.Tensor) -> torch.Tensor:
+        """fp32 device tensor [N]: w . x + b (on the standardised features for 'liblinear')."""
+        return self._score(X, None, True, False)[0]
+
+    def predict(self, X: torch.Tensor) -> torch.Tensor:
+        """int64 device tensor [N]: 1 where the decision value is > 0 (sklearn's rule), else 0."""
+        return (self.decision_function(X) > 0).to(torch.int64)
+
+    def correct(self, X: torch.Tensor, y) -> torch.Tensor:
+        """The number of correct predictions as a 0-d int64 device tensor (no host synchronisation)."""
+        return self._score(X, y, False, True)[1]
+
+    def score(self, X: torch.Tensor, y) -> float:
+        """Mean accuracy = correct / N as a Python float."""
+        _, correct, n = self._score(X, y, False, True)
+        return int(correct.item()) / n
