@@ -10,62 +10,9 @@
 #include <new>
 
 #include "umlh_common.h"
-#include "umlh_enc.h"
+#include "umlh_launch.h"
 #include "umlh_micro.h"
 #include <mutex>
-
-extern "C" {
-int umlh_micro_chunking(int d, int* nch, int* cw);
-int umlh_micro_launch(int nch, int cw, int bf16, const UmlhMicroHead* heads, int n_heads, int n_steps, int grid, hipStream_t st);
-int umlh_micro_bf16_supported(int nch, int cw);
-int umlh_f32_fwd_config(int C, int* ctw, int* wc);
-int umlh_f32_launch_fwd(const FwdArgs* a, int ctw, int wc, int grid, hipStream_t stream);
-int umlh_f32_launch_gemm(const GemmArgs* g, int ta, int tb, int splits, hipStream_t stream);
-int umlh_f32_launch_gemm_enc(const GemmArgs* g, int ta, int tb, int splits, hipStream_t stream);
-int umlh_launch_reduce_update(int mode, const float* slabs, int n_slabs, long long slab_stride, long long n,
-                              float* grad_out, float* p, float* m, float* v, const OptArgs* o, long long frozen_lo,
-                              long long frozen_hi, hipStream_t stream);
-int umlh_launch_finalize(const FinalizeArgs* f, hipStream_t stream);
-int umlh_launch_w_shadow32(const float* w, float* dst, int C, int K, int cpad, hipStream_t stream);
-int umlh_launch_head_step(const float* slabs, int n_slabs, long long slab_stride, int C, int K, float* p, float* m,
-                          float* v, const OptArgs* o, void* shadow, int cpad, const FinalizeArgs* f, float* grad_out,
-                          const DiagArgs* dg, float* shadow32, hipStream_t stream);
-int umlh_launch_zero_shot(const float* feats, const int64_t* labels, long long n, int d, int C, float* w,
-                          hipStream_t stream);
-int umlh_launch_to_bf16(const float* src, void* dst, long long n, hipStream_t stream);
-int umlh_bf16_fwd_ts(int wc, int stw);
-int umlh_launch_w_shadow(const float* w, void* dst, int C, int K, int cpad, hipStream_t stream);
-int umlh_launch_iota(long long* dst, long long n, hipStream_t stream);
-}
-
-extern "C" {
-int umlh_bf16_launch_fwd(const FwdArgsB* a, int ctw, int wc, int stw, int grid, hipStream_t stream);
-int umlh_bf16_launch_fwd_q(const FwdArgsB* a, int nq, int tiles, hipStream_t stream);
-int umlh_bf16_step_tasks(int nfwd, int M, int N, int splits, long long n_head, int with_head);
-int umlh_bf16_launch_step(const FwdArgsB* a, int ctw, int wc, int nfwd, const DwArgsB* g, int splits, unsigned* claim,
-                          unsigned long long* done, unsigned* status, unsigned epoch, int ts, int total_cols, const HeadFuse* hf,
-                          unsigned long long* timeline, int cus, int lazy, hipStream_t stream);
-int umlh_bf16_launch_dw(const DwArgsB* g, int splits, int am, int om, hipStream_t stream);
-int umlh_p2p_launch(void* const* regions, int n_ranks, int rank, float* msg, long long n, long long n_max, unsigned epoch, hipStream_t st);
-int umlh_p2p_status_offset(long long n_max, int n_ranks, unsigned long long* off);
-int umlh_enc_launch_bias_act(float* y, const float* b, long long M, int N, int relu, hipStream_t st);
-int umlh_enc_launch_relu_bwd(const float* y, float* dy, long long n, hipStream_t st);
-int umlh_enc_launch_dropout(float* x, long long n, float p, unsigned long long seed, hipStream_t st);
-int umlh_enc_launch_colsum(const float* x, int M, int N, float* out, hipStream_t st);
-int umlh_enc_launch_add_inplace(float* y, const float* x, long long n, hipStream_t st);
-int umlh_enc_launch_add_layernorm(const float* x, const float* r, const float* gamma, const float* beta, int M, int N, float eps,
-                                  float* s_out, float* y, float* mean, float* rstd, hipStream_t st);
-int umlh_enc_launch_layernorm_bwd(const float* dy, const float* s, const float* gamma, const float* mean, const float* rstd,
-                                  int M, int N, float* ds, float* dgamma, float* dbeta, hipStream_t st);
-int umlh_enc_launch_add_pos(float* x, const float* pos, int T, int B, int Z, hipStream_t st);
-int umlh_enc_launch_pos_grad(const float* dx, int T, int B, int Z, float* dpos, hipStream_t st);
-int umlh_enc_launch_gather_rows(const float* x, const int64_t* idx, int n, int Z, float* out, int scatter, hipStream_t st);
-int umlh_enc_launch_attention_fwd(const float* qkv, const int64_t* lengths, int T, int B, int Z, int H, float p,
-                                  unsigned long long seed, const unsigned long long* seed_ptr, float* ctx, float* lse, hipStream_t st);
-int umlh_enc_launch_attention_bwd(const float* qkv, const int64_t* lengths, const float* lse, const float* dctx, int T, int B,
-                                  int Z, int H, float p, unsigned long long seed, const unsigned long long* seed_ptr, float* dqkv, hipStream_t st);
-int umlh_bf16_launch_transpose_shadow(const float* src, int R, int Cc, int ldd, void* dst, int mode, hipStream_t stream);
-}
 
 static thread_local char g_err[512] = "";
 static int device_cus(int dev);
@@ -175,10 +122,8 @@ static bool make_layout(const umlh_config_t& c, Layout& L) {
     // slower than the 1-D kernel at cfg2 (umlh_kernels_bf16.hip) -> opt-in, UMLH_BF16_FWD2D=1, whenever the shape allows.
     L.fwd_nq = 0; L.xch = 0;
     if (c.precision == UMLH_PREC_BF16 && c.num_classes > 256 && c.d_shared % 256 == 0 && c.d_shared <= 512) {
-        const char* e = getenv("UMLH_BF16_FWD2D");
-        const int mode = e ? atoi(e) : -1;
         const int nq = (c.num_classes + 255) / 256;
-        if (mode == 1) {
+        if (env_int("UMLH_BF16_FWD2D", 0) == 1) {
             L.fwd_nq = nq;
             L.xch = take(2LL * (L.ldz / 128 + 2) * nq * 4 * 128);      // 8-byte granules
         }
@@ -222,17 +167,12 @@ struct umlh_handle_s {
     int step_lazy;              // UMLH_STEP_LAZY=1 (tests): see StepShape::lazy
     int step_grid;              // persistent workgroups of the one-launch step (CUs of the device; UMLH_STEP_GRID overrides)
     long long step_launches;    // one-launch steps taken (tests assert the path that ran)
-    const HeadFuse* pending_head;   // set by train_step_impl: the update may ride in the same launch (step_bf16)
-    bool head_fused_done;       // forward_backward took it
     // state carried from umlh_grad_step to umlh_apply_update
     int last_rows_img, last_rows_txt;
     bool iota_ready;            // bf16: identity row-id table in the workspace initialised
     bool shadow_fresh;          // bf16: the W shadow was written by the previous step's update kernel
-    float* diag_dst;            // where this step's 4 gradient diagnostics go (written by the head-step launch)
-    int n_slabs_img;            // dW_head slabs that hold image rows (the rest hold text rows)
     bool diagnostics;           // umlh_enable_diagnostics
     int  diag_cols = 0;         // umlh_set_diagnostic_columns (0 = every column of w_head)
-    float* row_stats;           // per-row {CE, correct} output of the next forward (umlh_eval_rows), else NULL
     int dbg_fwd, dbg_dw;        // timing-only ablation / cycle-stamp switches (UMLH_DBG_FWD / UMLH_DBG_DW), read once at create
     hipEvent_t ev[UMLH_N_PHASES + 1];   // phase boundaries, valid when profiling
     bool profiling;
@@ -258,9 +198,6 @@ struct umlh_handle_s {
     bool comm_owned;
     hipStream_t comm_stream;    // second stream: the head-gradient all-reduce of a 2-layer head runs beside the img_proj backward GEMMs
     hipEvent_t ev_head_ready, ev_head_done;
-    bool overlap_pending;       // forward_backward calls dp_after_head() behind the dW_head GEMM
-    const umlh_hyper_t* overlap_hy;
-    const umlh_batch_t* overlap_img; const umlh_batch_t* overlap_txt;
     int device;                 // HIP device the handle was created on: every launching entry point runs there
     int global_rows_img, global_rows_txt;   // global row counts of the last umlh_grad_step (gate the update on every rank alike)
 };
@@ -333,24 +270,21 @@ int umlh_create(const umlh_config_t* cfg, umlh_handle_t* out) {
     h->bound = false;
     h->ts = umlh_f32_fwd_config(cfg->num_classes, &h->ctw, &h->wc);
     h->stw = 1;
-    { const char* d = getenv("UMLH_DBG_FWD"); h->dbg_fwd = d ? atoi(d) : 0; }
-    { const char* d = getenv("UMLH_DBG_DW"); h->dbg_dw = d ? atoi(d) : 0; }
+    h->dbg_fwd = env_int("UMLH_DBG_FWD", 0);
+    h->dbg_dw = env_int("UMLH_DBG_DW", 0);
     if (cfg->precision == UMLH_PREC_BF16) {
         // two 32-sample tiles per wave would halve the L2->CU stream of the head weight, but measured
         // slower on MI355X (51 vs 26 us at cfg2: half the CUs idle, VGPR-limited ring) -> opt-in only
-        const char* e = getenv("UMLH_BF16_STW");
-        int want = e ? atoi(e) : 1;
-        if (h->wc == 8 && h->ctw >= 2 && want == 2) h->stw = 2;
+        if (h->wc == 8 && h->ctw >= 2 && env_int("UMLH_BF16_STW", 1) == 2) h->stw = 2;
         h->ts = umlh_bf16_fwd_ts(h->wc, h->stw);
         if (L.fwd_nq) h->ts = 128;
     }
     h->fwd_epoch = 0;
     h->fuse_epoch = 0;
-    h->pending_head = nullptr; h->head_fused_done = false;
-    { const char* e = getenv("UMLH_DBG_STEP"); h->dbg_step = (e && atoi(e) == 1) ? 1 : 0; }
+    h->dbg_step = env_int("UMLH_DBG_STEP", 0) == 1;
     h->step_grid = 0; h->step_launches = 0;
-    { const char* e = getenv("UMLH_STEP_LAZY"); h->step_lazy = (e && atoi(e) == 1) ? 1 : 0; }
-    { const char* e = getenv("UMLH_BF16_FUSE"); h->fuse = e ? atoi(e) : 2; }   // 2 (default): the whole step as one launch; 1: forward + dW as one; 0: separate launches
+    h->step_lazy = env_int("UMLH_STEP_LAZY", 0) == 1;
+    h->fuse = env_int("UMLH_BF16_FUSE", 2);   // 2 (default): the whole step as one launch; 1: forward + dW as one; 0: separate launches
     h->last_rows_img = h->last_rows_txt = 0;
     h->global_rows_img = h->global_rows_txt = 0;
     h->profiling = false;
@@ -358,15 +292,15 @@ int umlh_create(const umlh_config_t* cfg, umlh_handle_t* out) {
     h->micro_launches = 0;
     h->frozen_proj_row = -1;
     h->dp_diag = false; h->n_ranks = 1; h->ar_fn = nullptr; h->ar_ctx = nullptr; h->comm = nullptr; h->comm_owned = false;
-    h->comm_stream = nullptr; h->overlap_pending = false;
+    h->comm_stream = nullptr;
     h->p2p_on = 0; h->p2p_rank = 0; h->p2p_epoch = 0; memset(h->p2p_region, 0, sizeof(h->p2p_region));
-    { const char* e = getenv("UMLH_FORCE_DP"); h->dp_force = (e && atoi(e) == 1) ? 1 : 0; }
+    h->dp_force = env_int("UMLH_FORCE_DP", 0) == 1;
     h->stage = nullptr; h->stage_bytes = 0; h->stage_next = 0;
-    { const char* e = getenv("UMLH_MICRO"); h->micro_off = (e && atoi(e) == 0) ? 1 : 0; }
+    h->micro_off = env_int("UMLH_MICRO", 1) == 0;
     h->device = 0;
     (void)hipGetDevice(&h->device);
-    h->step_grid = device_cus(h->device);
-    { const char* e = getenv("UMLH_STEP_GRID"); if (e && atoi(e) > 0) h->step_grid = atoi(e); }   // fewer workgroups than tasks is always correct (tests: partial residency)
+    const int grid_env = env_int("UMLH_STEP_GRID", 0);
+    h->step_grid = grid_env > 0 ? grid_env : device_cus(h->device);   // fewer workgroups than tasks is always correct (tests: partial residency)
     memset(&h->buf, 0, sizeof(h->buf));
     *out = h;
     return UMLH_OK;
@@ -419,6 +353,11 @@ int umlh_destroy(umlh_handle_t h) {
 }
 
 static inline float* ws(umlh_handle_t h, long long off) { return static_cast<float*>(h->buf.workspace) + off; }
+static inline int class_pad(const umlh_handle_s* h) { return 32 * h->ctw * h->wc; }   // class rows of the W shadows (whole 32-class tiles per wave)
+// ticket of the gradient-diagnostics reduction, behind the [head_step blocks][4] partials (head_step_kernel leaves it at 0)
+static inline unsigned* diag_ticket(umlh_handle_t h) {
+    return reinterpret_cast<unsigned*>(ws(h, h->L.diag_part) + 4 * ((h->L.n_head + 1023) / 1024 + 2));
+}
 
 // gradient message layout (see umlh_grad_step): head part, img_proj part, then g_scales(2) + scalars
 static inline long long frozen_lo(const umlh_handle_s* h) { return h->frozen_proj_row < 0 ? 0 : (long long)h->frozen_proj_row * h->cfg.d_img; }
@@ -444,10 +383,9 @@ int umlh_bind(umlh_handle_t h, const umlh_buffers_t* b) {
     h->bound = true;
     h->iota_ready = false;
     h->shadow_fresh = false;
-    {                             // ticket of the gradient-diagnostics reduction (head_step_kernel leaves it at 0 after every launch)
+    {
         DeviceGuard dg_(h->device);
-        const long long np = 4 * ((h->L.n_head + 1023) / 1024 + 2);
-        if (hipMemset(ws(h, h->L.diag_part) + np, 0, 64 * sizeof(float)) != hipSuccess) return fail(UMLH_E_HIP, "umlh_bind: clearing the diagnostics ticket failed");
+        if (hipMemset(diag_ticket(h), 0, 64 * sizeof(float)) != hipSuccess) return fail(UMLH_E_HIP, "umlh_bind: clearing the diagnostics ticket failed");
     }
     if (h->L.fuse_flags) {        // done granules / claim words / status of the one-launch step: tag 0 = never written
         DeviceGuard dg_(h->device);
@@ -602,9 +540,6 @@ int umlh_optimizer_step(int32_t optimizer, float* param, const float* grad, floa
     return UMLH_OK;
 }
 
-extern "C" int umlh_launch_multi_opt(int n, float* const* p, const float* const* g, float* const* m, float* const* v, const long long* cnt,
-                                     const OptArgs* o, hipStream_t stream);
-
 int umlh_optimizer_step_multi(int32_t optimizer, int32_t n_tensors, float* const* params, const float* const* grads, float* const* m,
                               float* const* v, const int64_t* n, double lr, int64_t step, double beta1, double beta2, double eps,
                               double momentum, double weight_decay, void* stream) {
@@ -629,17 +564,6 @@ int umlh_optimizer_step_multi(int32_t optimizer, int32_t n_tensors, float* const
         HIPCHK(umlh_launch_multi_opt(k, params + t0, grads + t0, m + t0, v ? v + t0 : nullptr, cnt, &o, (hipStream_t)stream), "optimizer step (multi)");
     }
     return UMLH_OK;
-}
-
-extern "C" {
-int umlh_seq_launch_fwd(const float* z, const float* w, const float* b, const float* x, const int64_t* lengths, int B, int T,
-                        int Z, int D, float* recon, float* dres, float* row_partial, float* loss_cnt, hipStream_t st);
-int umlh_seq_launch_bwd(const float* z, const float* w, const float* dres, const float* loss_cnt, const float* grad_out, int B,
-                        int T, int Z, int D, float* dz, float* dw, float* db, int with_params, hipStream_t st);
-int umlh_seq_launch_l2norm(const float* x, int n, int D, float* y, float* norm, hipStream_t st);
-int umlh_seq_launch_nce_rows(float* dots, int n, float inv_temp, float* row_loss, float* loss, hipStream_t st);
-int umlh_seq_launch_l2norm_bwd(const float* dy, const float* y, const float* norm, const float* grad_out, float scale, int n, int D,
-                               float* dx, hipStream_t st);
 }
 
 int umlh_seq_mse_forward(const float* z, const float* w, const float* bias, const float* x, const int64_t* lengths, int32_t B,
@@ -726,8 +650,6 @@ int umlh_infonce_backward(const float* pred_hat, const float* target_hat, const 
     return UMLH_OK;
 }
 
-extern "C" int umlh_launch_feistel_perm(long long n, unsigned long long seed, long long* out, hipStream_t stream);
-
 int umlh_random_permutation(int64_t n, uint64_t seed, int64_t* out, void* stream) {
     if (n < 0 || (n > 0 && !out)) return fail(UMLH_E_INVALID, "umlh_random_permutation: bad arguments");
     HIPCHK(umlh_launch_feistel_perm(n, seed, reinterpret_cast<long long*>(out), (hipStream_t)stream), "feistel perm");
@@ -735,18 +657,6 @@ int umlh_random_permutation(int64_t n, uint64_t seed, int64_t* out, void* stream
 }
 
 // ---- alignment metrics (kernels: umlh_kernels_align.hip); every check precedes the first HIP call ----
-extern "C" {
-int umlh_align_knn_splits(long long n, int splits);
-unsigned long long umlh_align_knn_bytes(long long n, int topk, int splits);
-unsigned long long umlh_align_mutual_bytes(long long n);
-unsigned long long umlh_align_cka_bytes(long long n, int da, int db, int splits);
-int umlh_align_launch_knn(const float* x, long long n, int d, int ldx, int topk, int splits, int* knn, float* scores, void* scratch,
-                          hipStream_t st);
-int umlh_align_launch_mutual(const int* ka, const int* kb, long long n, int topk, double* out, void* scratch, hipStream_t st);
-int umlh_align_launch_cka(const float* a, int lda, int da, const float* b, int ldb, int db, long long n, int splits, double* out4,
-                          void* scratch, hipStream_t st);
-}
-
 static const int64_t ALIGN_MAX_ROWS = (int64_t)1 << 30;   // int32 indices with room for the tile and sentinel arithmetic
 
 uint64_t umlh_align_scratch_bytes(int64_t n, int32_t d_a, int32_t d_b, int32_t topk, int32_t splits) {
@@ -858,16 +768,14 @@ int umlh_gemm_f32_epi(const float* A, const float* B, float* out, int M, int N, 
     g.k_chunk = chunk;
     g.slab_stride = (long long)M * N;
     if (ns_out) *ns_out = ns;
-    static const bool legacy = [] { const char* e = getenv("UMLH_ENC_GEMM"); return e && atoi(e) == 0; }();   // timing comparisons
-    auto launch = legacy ? umlh_f32_launch_gemm : umlh_f32_launch_gemm_enc;
     if (!defer && ns == 1) {
         g.out = out;
         if (epi) g.epi = *epi;
-        HIPCHK(launch(&g, ta, tb, 1, stream), "gemm_enc (epilogue)");
+        HIPCHK(umlh_f32_launch_gemm_enc(&g, ta, tb, 1, stream), "gemm_enc (epilogue)");
         return UMLH_OK;
     }
     g.out = slabs;
-    HIPCHK(launch(&g, ta, tb, ns, stream), "gemm_enc (slabs)");
+    HIPCHK(umlh_f32_launch_gemm_enc(&g, ta, tb, ns, stream), "gemm_enc (slabs)");
     if (defer) return UMLH_OK;
     Epilogue none;
     memset(&none, 0, sizeof(none));
@@ -958,297 +866,345 @@ int umlh_attention_backward(const float* qkv, const int64_t* lengths, const floa
     return UMLH_OK;
 }
 
-static int dp_after_head(umlh_handle_t h, int n_slabs_head, hipStream_t st);
+#define RC(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
 
-// Everything of a step up to (not including) the parameter update.
-static int forward_backward(umlh_handle_t h, const umlh_batch_t* img, const umlh_batch_t* txt,
-                            const umlh_hyper_t* hy, bool want_grad, hipStream_t st, int* n_slabs_head,
-                            int* n_slabs_proj) {
+// One forward/backward: what it takes besides the handle and what it leaves behind, passed by reference through its stages.
+// Filled by train_step_impl, grad_step_impl and the eval entry points; nothing of it outlives the call.
+struct StepCall {
+    // in
+    const umlh_batch_t* img; const umlh_batch_t* txt; const umlh_hyper_t* hy;
+    bool want_grad;                     // false: forward only (evaluation)
+    hipStream_t st;
+    const HeadFuse* head = nullptr;     // linear bf16 head: the update (or the slab sum into the gradient message) may ride in the one-launch step
+    bool overlap = false;               // data-parallel 2-layer head: the head all-reduce starts behind dW_head (dp_after_head)
+    float* row_stats = nullptr;         // per-row {CE, correct} output of the forward (umlh_eval_rows)
+    // derived by forward_backward: rows, forward blocks and padded dZ^T columns of the image / text segment
+    int ri, rt, nb0, nb1, r0p, r1p;
+    // out
+    int n_slabs_head = 0, n_slabs_proj = 0;   // split-K slabs the dW_head / dW_proj GEMMs wrote
+    int n_slabs_img = 0;                // dW_head slabs that hold image rows (the rest hold text rows)
+    bool head_done = false;             // `head` rode in the launch: nothing is left to reduce or update
+};
+
+static int dp_after_head(umlh_handle_t h, const StepCall& x);
+
+static inline u16* ws16(umlh_handle_t h, long long off) { return reinterpret_cast<u16*>(ws(h, off)); }
+static inline int64_t* ws_iota(umlh_handle_t h) { return reinterpret_cast<int64_t*>(ws(h, h->L.iota)); }
+static inline unsigned long long* ws_stamps(umlh_handle_t h) { return reinterpret_cast<unsigned long long*>(ws(h, h->L.dbg)); }
+
+// The two modalities' rows as the forward kernels see them (SegDesc / SegDescB).  `gathered`: the image features were
+// already gathered by the projection (H, row r = batch row r); an absent modality keeps its zeroed descriptor.
+template <class Seg, class T>
+static void fill_segs(Seg* seg, umlh_handle_t h, const StepCall& x, const T* feats_img, bool gathered, const T* feats_txt) {
+    if (x.ri > 0) {
+        seg[0].feats = feats_img; seg[0].feat_index = gathered ? nullptr : x.img->index;
+        seg[0].labels = x.img->labels; seg[0].label_index = x.img->index; seg[0].ld = h->cfg.d_shared; seg[0].rows = x.ri;
+        seg[0].w_over_rows = x.hy->img_alpha / (float)x.img->global_rows;
+    }
+    seg[0].scale_ptr = h->buf.scales; seg[0].col0 = 0; seg[0].blk0 = 0;
+    if (x.rt > 0) {
+        seg[1].feats = feats_txt; seg[1].feat_index = x.txt->index;
+        seg[1].labels = x.txt->labels; seg[1].label_index = x.txt->index; seg[1].ld = h->cfg.d_shared; seg[1].rows = x.rt;
+        seg[1].w_over_rows = x.hy->alpha / (float)x.txt->global_rows;
+    }
+    seg[1].scale_ptr = h->buf.scales + 1; seg[1].col0 = x.r0p; seg[1].blk0 = x.nb0;
+}
+
+// ---- bf16 mode ----
+// The GEMM loaders are branch-free: every pointer must be dereferenceable, also for an absent modality or a dense
+// (index-less) batch -> identity row ids + a zero page from the workspace
+static DwArgsB dw_base_args(umlh_handle_t h) {
+    DwArgsB g;
+    memset(&g, 0, sizeof(g));
+    g.zeros = ws16(h, h->L.zeros); g.bcs = 64; g.a_rows = ws_iota(h); g.nsplit = g.nsplit1 = 1;
+    g.dbg = h->dbg_dw;
+    if (g.dbg >= 16) { g.dbg -= 16; g.stamps = ws_stamps(h); }   // +16: cycle stamps
+    return g;
+}
+
+// H = X_img W_proj^T  (head.py:79): rows gathered by the batch index, bf16 row-major [r][d_shared] out.  W_proj^T is a
+// per-step bf16 shadow of the fp32 master (6.5 MB at cfg3, against ~180 GFLOP of GEMMs per step).
+static int bf16_proj_forward(umlh_handle_t h, const StepCall& x) {
+    const umlh_config_t& c = h->cfg;
+    u16* wpt16 = ws16(h, h->L.wpt16);
+    HIPCHK(umlh_bf16_launch_transpose_shadow(h->buf.w_proj, c.d_shared, c.d_img, c.d_shared, wpt16, 0, x.st), "W_proj^T shadow");
+    DwArgsB g = dw_base_args(h);
+    g.A = static_cast<const u16*>(x.img->feats_bf16); g.lda = c.d_img; g.a_rows = x.img->index ? x.img->index : ws_iota(h);
+    g.B = g.B2 = wpt16; g.k_rows = g.k_rows2 = ws_iota(h); g.ldb = g.ldb2 = c.d_shared;
+    g.M = x.ri; g.N = c.d_shared; g.K = c.d_img;
+    g.k_chunk = (int)round_up(c.d_img, 256); g.k_switch = c.d_img; g.k_valid1 = c.d_img; g.k_valid2 = 0;
+    g.out16 = ws16(h, h->L.h); g.ldo = c.d_shared;
+    if (g.k_chunk > 4096) return fail(UMLH_E_INVALID, "bf16 img_proj: d_img %d > 4096 unsupported", c.d_img);
+    HIPCHK(umlh_bf16_launch_dw(&g, 1, 1, 1, x.st), "proj forward (bf16)");
+    return UMLH_OK;
+}
+
+// Fills `fb` and launches the forward unless it is to ride in the one-launch step (`fused`, then bf16_dw_head launches it).
+static int bf16_forward_ce(umlh_handle_t h, const StepCall& x, bool proj, FwdArgsB& fb, bool& fused) {
     const umlh_config_t& c = h->cfg;
     const Layout& L = h->L;
-    const int ri = img ? img->rows : 0, rt = txt ? txt->rows : 0;
-    const int TS = h->ts;
-    const int nb0 = fwd_blocks_img(h, ri), nb1 = (rt + TS - 1) / TS;
-    const int r0p = nb0 * TS, r1p = nb1 * TS;
-    float* H = ws(h, L.h);
-    float* dzt = ws(h, L.dzt);
-
-    if (c.precision == UMLH_PREC_BF16) {
-        if ((ri > 0 && !img->feats_bf16) || (rt > 0 && !txt->feats_bf16))
-            return fail(UMLH_E_INVALID, "bf16 mode: batch.feats_bf16 is required (umlh_to_bf16 of the feature table)");
-        u16* w16 = reinterpret_cast<u16*>(ws(h, L.w16));
-        u16* dz16 = reinterpret_cast<u16*>(dzt);
-        u16* h16 = reinterpret_cast<u16*>(H);                                  // bf16 H = X W_proj^T, row-major [r][d_shared]
-        u16* dht16 = reinterpret_cast<u16*>(ws(h, L.dht));                     // bf16 dH^T, chunk-major [r/64][d_shared^128][64]
-        const u16* zeros16 = reinterpret_cast<const u16*>(ws(h, L.zeros));
-        const int dsp = (int)round_up(c.d_shared, 128);
-        const bool proj = c.has_proj && ri > 0;
-        mark(h, 0, st);
-        // the GEMM loaders are branch-free: every pointer must be dereferenceable, also for an absent
-        // modality or a dense (index-less) batch -> identity row ids + a zero page from the workspace
-        int64_t* iota = reinterpret_cast<int64_t*>(ws(h, L.iota));
-        if (!h->iota_ready) {
-            HIPCHK(umlh_launch_iota(reinterpret_cast<long long*>(iota), L.n_iota, st), "iota");
-            HIPCHK((int)hipMemsetAsync(ws(h, L.zeros), 0, 64 * sizeof(float), st), "zero page");
-            h->iota_ready = true;
-        }
-        auto base_args = [&]() {
-            DwArgsB g;
-            memset(&g, 0, sizeof(g));
-            g.zeros = zeros16; g.bcs = 64; g.a_rows = iota; g.nsplit = g.nsplit1 = 1;
-            g.dbg = h->dbg_dw;
-            if (g.dbg >= 16) { g.dbg -= 16; g.stamps = reinterpret_cast<unsigned long long*>(ws(h, L.dbg)); }   // +16: cycle stamps
-            return g;
-        };
-        if (proj) {
-            // H = X_img W_proj^T  (head.py:79): rows gathered by the batch index, bf16 out.  W_proj^T is a
-            // per-step bf16 shadow of the fp32 master (6.5 MB at cfg3, against ~180 GFLOP of GEMMs per step).
-            u16* wpt16 = reinterpret_cast<u16*>(ws(h, L.wpt16));
-            HIPCHK(umlh_bf16_launch_transpose_shadow(h->buf.w_proj, c.d_shared, c.d_img, c.d_shared, wpt16, 0, st), "W_proj^T shadow");
-            DwArgsB g = base_args();
-            g.A = static_cast<const u16*>(img->feats_bf16); g.lda = c.d_img; g.a_rows = img->index ? img->index : iota;
-            g.B = g.B2 = wpt16; g.k_rows = g.k_rows2 = iota; g.ldb = g.ldb2 = c.d_shared;
-            g.M = ri; g.N = c.d_shared; g.K = c.d_img;
-            g.k_chunk = (int)round_up(c.d_img, 256); g.k_switch = c.d_img; g.k_valid1 = c.d_img; g.k_valid2 = 0;
-            g.out16 = h16; g.ldo = c.d_shared;
-            if (g.k_chunk > 4096) return fail(UMLH_E_INVALID, "bf16 img_proj: d_img %d > 4096 unsupported", c.d_img);
-            HIPCHK(umlh_bf16_launch_dw(&g, 1, 1, 1, st), "proj forward (bf16)");
-        }
-        // bf16 shadow of the fp32 master weight, refreshed every call (the caller may have
-        // rewritten w_head: load_state_dict, zero-shot init)
-        const int cpad = 32 * h->ctw * h->wc;
-        const int crows = (int)round_up(c.num_classes, 128);
-        // refreshed here unless the previous step of the same umlh_train_steps call just wrote it
-        // from its update kernel (between calls the caller may have rewritten w_head)
-        if (!h->shadow_fresh)
-            HIPCHK(umlh_launch_w_shadow(h->buf.w_head, w16, c.num_classes, c.d_shared, cpad, st), "w_shadow");
-        h->shadow_fresh = false;
-        mark(h, 1, st);
-        FwdArgsB fb;
-        memset(&fb, 0, sizeof(fb));
-        SegDescB& b0 = fb.seg[0];
-        SegDescB& b1 = fb.seg[1];
-        if (ri > 0) {
-            b0.feats = proj ? h16 : static_cast<const u16*>(img->feats_bf16);
-            b0.feat_index = proj ? nullptr : img->index;
-            b0.labels = img->labels; b0.label_index = img->index; b0.ld = c.d_shared; b0.rows = ri;
-            b0.w_over_rows = hy->img_alpha / (float)img->global_rows;
-        }
-        b0.scale_ptr = h->buf.scales; b0.col0 = 0; b0.blk0 = 0;
-        if (rt > 0) {
-            b1.feats = static_cast<const u16*>(txt->feats_bf16); b1.feat_index = txt->index;
-            b1.labels = txt->labels; b1.label_index = txt->index; b1.ld = c.d_shared; b1.rows = rt;
-            b1.w_over_rows = hy->alpha / (float)txt->global_rows;
-        }
-        b1.scale_ptr = h->buf.scales + 1; b1.col0 = r0p; b1.blk0 = nb0;
-        fb.W = w16; fb.C = c.num_classes; fb.K = c.d_shared;
-        fb.dzt = want_grad ? dz16 : nullptr; fb.crows = crows;
-        fb.partials = ws(h, L.partials);
-        fb.dbg = h->dbg_fwd;
-        fb.learn = c.learnable_temp;
-        fb.row_stats = h->row_stats;
-        fb.stamps = (fb.dbg == 9 || fb.dbg >= 20) ? reinterpret_cast<unsigned long long*>(ws(h, L.dbg)) : nullptr;
-        if (L.fwd_nq) {
-            fb.xch = reinterpret_cast<unsigned long long*>(ws(h, L.xch));
-            if (++h->fwd_epoch == 0) h->fwd_epoch = 1;
-            fb.epoch = h->fwd_epoch;
-            fb.wtiles = cpad / 32;
-            fb.ntiles = nb0 + nb1;
-            HIPCHK(umlh_bf16_launch_fwd_q(&fb, L.fwd_nq, nb0 + nb1, st), "fwd_ce_bf16_q");
-        }
-        // forward + dW as one launch (linear head, 1-D forward, write-through stores).  In profiling mode the interval
-        // mark 1 -> 2 is then empty and mark 2 -> 3 holds the one launch.
-        // (not while the stream is being captured into a HIP graph: the granules' epoch tag is a launch argument, a replay
-        // would find the previous replay's tags and pass its gates early)
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        const bool capturing = h->fuse && hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
-        // (the coherent loads address dZ^T and the slabs through 32-bit buffer offsets)
-        const bool fits32 = (unsigned long long)((r0p + r1p + 63) / 64) * crows * 128ull < (1ull << 31) &&
-                            (unsigned long long)L.scap_head * L.n_head * 4ull < (1ull << 31);
-        const bool fused = h->fuse && !capturing && fits32 && want_grad && !proj && !L.fwd_nq && h->stw == 1 && L.fuse_flags &&
-                           !umlh_plain_stores() && fb.dbg == 0 && h->dbg_dw == 0;
-        if (!L.fwd_nq && !fused)
-        HIPCHK(umlh_bf16_launch_fwd(&fb, h->ctw, h->wc, h->stw, nb0 + nb1, st), "fwd_ce_bf16");
-        mark(h, 2, st);
-        *n_slabs_head = 0; *n_slabs_proj = 0;
-        if (!want_grad) return UMLH_OK;
-        // ---- dW_head = dZ^T [H or X_img ; X_txt] ----
-        {
-            // chunk: multiples of 4 x 64 columns (4-stage pipeline), at most 4096 (row ids of a split live in LDS)
-            SplitPlan sp = plan_splits(r0p, r1p, L.scap_head, 256, 256);
-            if (sp.chunk > 4096) { sp.chunk = 4096; sp.n_img = (r0p + 4095) / 4096; sp.n_txt = (r1p + 4095) / 4096; }
-            const int splits = sp.n_img + sp.n_txt;
-            if (splits > L.scap_head)
-                return fail(UMLH_E_INVALID, "bf16 dW: %d + %d reduction rows need more than %d split-K slabs", r0p, r1p, L.scap_head);
-            const u16* any16 = ri > 0 ? static_cast<const u16*>(img->feats_bf16) : static_cast<const u16*>(txt->feats_bf16);
-            DwArgsB g = base_args();
-            g.A = dz16; g.lda = crows;
-            g.B = proj ? h16 : (ri > 0 ? static_cast<const u16*>(img->feats_bf16) : any16);
-            g.k_rows = (ri > 0 && img->index && !proj) ? img->index : iota; g.ldb = c.d_shared;
-            g.B2 = rt > 0 ? static_cast<const u16*>(txt->feats_bf16) : any16;
-            g.k_rows2 = (rt > 0 && txt->index) ? txt->index : iota; g.ldb2 = c.d_shared;
-            g.out = ws(h, L.slabs_head); g.ldo = c.d_shared;
-            g.M = c.num_classes; g.N = c.d_shared; g.K = r0p + r1p;
-            g.k_chunk = sp.chunk; g.k_switch = r0p; g.k_valid1 = ri; g.k_valid2 = rt; g.slab_stride = L.n_head;
-            g.nsplit = splits; g.nsplit1 = sp.n_img; h->n_slabs_img = sp.n_img;
-            const int ndw_blocks = ((c.d_shared + 127) / 128) * ((c.num_classes + 127) / 128) * splits;
-            const bool with_head = fused && h->pending_head && h->fuse >= 2;
-            if (fused && umlh_bf16_step_tasks(nb0 + nb1, g.M, g.N, splits, L.n_head, with_head) <= L.ctl_tasks) {
-                // forward + dW (+ update + finalize) as ONE launch of persistent workgroups over claimed tasks (StepCtl)
-                if (h->fuse_epoch > 0xFFFFFF00u) {            // tag wrap (2^32 launches): start the epoch-tagged words over
-                    HIPCHK((int)hipMemsetAsync(ws(h, L.fuse_flags), 0, sizeof(float) * (size_t)(3 * L.ctl_tasks), st), "step control words");
-                    h->fuse_epoch = 0;
-                }
-                ++h->fuse_epoch;
-                HeadFuse hf;
-                if (with_head) { hf = *h->pending_head; hf.n_slabs = splits; hf.n_slabs_img = sp.n_img; }
-                unsigned long long* done = reinterpret_cast<unsigned long long*>(ws(h, L.fuse_flags));
-                unsigned* claim = reinterpret_cast<unsigned*>(done + L.ctl_tasks);
-                unsigned* status = claim + L.ctl_tasks;
-                const int ntask = umlh_bf16_step_tasks(nb0 + nb1, g.M, g.N, splits, L.n_head, with_head);
-                HIPCHK(umlh_bf16_launch_step(&fb, h->ctw, h->wc, nb0 + nb1, &g, splits, claim, done, status, h->fuse_epoch, TS,
-                                             (nb0 + nb1) * TS, with_head ? &hf : nullptr,
-                                             (h->dbg_step && 4LL * ntask <= 64LL * L.max_blocks)
-                                                 ? reinterpret_cast<unsigned long long*>(ws(h, L.dbg)) : nullptr, h->step_grid, h->step_lazy, st), "step_bf16");
-                h->head_fused_done = with_head;
-                h->step_launches++;
-            } else {
-                if (fused) HIPCHK(umlh_bf16_launch_fwd(&fb, h->ctw, h->wc, h->stw, nb0 + nb1, st), "fwd_ce_bf16");
-                HIPCHK(umlh_bf16_launch_dw(&g, splits, 0, 0, st), "dw_bf16");
-            }
-            *n_slabs_head = splits;
-        }
-        mark(h, 3, st);
-        if (h->overlap_pending) { int rc2 = dp_after_head(h, *n_slabs_head, st); if (rc2) return rc2; }
-        if (proj) {
-            // dH^T[n][r] = sum_c W_head[c][n] dZ^T[c][r]  (image columns), bf16 chunk-major out
-            u16* wht16 = reinterpret_cast<u16*>(ws(h, L.wht16));
-            HIPCHK(umlh_bf16_launch_transpose_shadow(h->buf.w_head, c.num_classes, c.d_shared, dsp, wht16, 1, st), "W_head^T shadow");
-            const int kc = (int)round_up(c.num_classes, 64);
-            DwArgsB g = base_args();
-            g.A = wht16; g.lda = dsp;
-            g.B = g.B2 = dz16; g.k_rows = g.k_rows2 = iota; g.ldb = g.ldb2 = 64; g.bcs = crows * 64;
-            g.M = c.d_shared; g.N = r0p; g.K = kc;
-            g.k_chunk = (int)round_up(kc, 256); g.k_switch = kc; g.k_valid1 = c.num_classes; g.k_valid2 = 0;
-            g.out16 = dht16; g.ldo = dsp;
-            HIPCHK(umlh_bf16_launch_dw(&g, 1, 0, 2, st), "dH^T (bf16)");
-            // dW_proj[n][k] = sum_r dH^T[n][r] X_img[r][k]
-            SplitPlan sp = plan_splits(r0p, 0, L.scap_proj, 256, 256);
-            if (sp.chunk > 4096) { sp.chunk = 4096; sp.n_img = (r0p + 4095) / 4096; }
-            if (sp.n_img > L.scap_proj)
-                return fail(UMLH_E_INVALID, "bf16 dW_proj: %d reduction rows need more than %d split-K slabs", r0p, L.scap_proj);
-            DwArgsB p = base_args();
-            p.A = dht16; p.lda = dsp;
-            p.B = p.B2 = static_cast<const u16*>(img->feats_bf16); p.k_rows = p.k_rows2 = img->index ? img->index : iota;
-            p.ldb = p.ldb2 = c.d_img;
-            p.M = c.d_shared; p.N = c.d_img; p.K = r0p;
-            p.k_chunk = sp.chunk; p.k_switch = r0p; p.k_valid1 = ri; p.k_valid2 = 0;
-            p.out = ws(h, L.slabs_proj); p.ldo = c.d_img; p.slab_stride = L.n_proj;
-            p.nsplit = p.nsplit1 = sp.n_img;
-            HIPCHK(umlh_bf16_launch_dw(&p, sp.n_img, 0, 0, st), "dW_proj (bf16)");
-            *n_slabs_proj = sp.n_img;
-        }
-        mark(h, 4, st);
-        return UMLH_OK;
+    const int nb = x.nb0 + x.nb1, crows = (int)round_up(c.num_classes, 128);
+    memset(&fb, 0, sizeof(fb));
+    fill_segs(fb.seg, h, x, x.ri > 0 ? (proj ? ws16(h, L.h) : static_cast<const u16*>(x.img->feats_bf16)) : nullptr, proj,
+              x.rt > 0 ? static_cast<const u16*>(x.txt->feats_bf16) : nullptr);
+    fb.W = ws16(h, L.w16); fb.C = c.num_classes; fb.K = c.d_shared;
+    fb.dzt = x.want_grad ? ws16(h, L.dzt) : nullptr; fb.crows = crows;
+    fb.partials = ws(h, L.partials);
+    fb.dbg = h->dbg_fwd;
+    fb.learn = c.learnable_temp;
+    fb.row_stats = x.row_stats;
+    fb.stamps = (fb.dbg == 9 || fb.dbg >= 20) ? ws_stamps(h) : nullptr;
+    if (L.fwd_nq) {
+        fb.xch = reinterpret_cast<unsigned long long*>(ws(h, L.xch));
+        if (++h->fwd_epoch == 0) h->fwd_epoch = 1;
+        fb.epoch = h->fwd_epoch;
+        fb.wtiles = class_pad(h) / 32;
+        fb.ntiles = nb;
+        HIPCHK(umlh_bf16_launch_fwd_q(&fb, L.fwd_nq, nb, x.st), "fwd_ce_bf16_q");
     }
+    // forward + dW as one launch (linear head, 1-D forward, write-through stores).  In profiling mode the interval
+    // mark 1 -> 2 is then empty and mark 2 -> 3 holds the one launch.
+    // (not while the stream is being captured into a HIP graph: the granules' epoch tag is a launch argument, a replay
+    // would find the previous replay's tags and pass its gates early)
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    const bool capturing = h->fuse && hipStreamIsCapturing(x.st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+    // (the coherent loads address dZ^T and the slabs through 32-bit buffer offsets)
+    const bool fits32 = (unsigned long long)((x.r0p + x.r1p + 63) / 64) * crows * 128ull < (1ull << 31) &&
+                        (unsigned long long)L.scap_head * L.n_head * 4ull < (1ull << 31);
+    fused = h->fuse && !capturing && fits32 && x.want_grad && !proj && !L.fwd_nq && h->stw == 1 && L.fuse_flags &&
+            !umlh_plain_stores() && fb.dbg == 0 && h->dbg_dw == 0;
+    if (!L.fwd_nq && !fused) HIPCHK(umlh_bf16_launch_fwd(&fb, h->ctw, h->wc, h->stw, nb, x.st), "fwd_ce_bf16");
+    return UMLH_OK;
+}
 
+// dW_head = dZ^T [H or X_img ; X_txt] as split-K slabs; `fused`: together with the forward (and x.head) as ONE launch
+static int bf16_dw_head(umlh_handle_t h, StepCall& x, bool proj, const FwdArgsB& fb, bool fused) {
+    const umlh_config_t& c = h->cfg;
+    const Layout& L = h->L;
+    const umlh_batch_t* img = x.img; const umlh_batch_t* txt = x.txt;
+    const int ri = x.ri, rt = x.rt, r0p = x.r0p, r1p = x.r1p, nb = x.nb0 + x.nb1;
+    // chunk: multiples of 4 x 64 columns (4-stage pipeline), at most 4096 (row ids of a split live in LDS)
+    SplitPlan sp = plan_splits(r0p, r1p, L.scap_head, 256, 256);
+    if (sp.chunk > 4096) { sp.chunk = 4096; sp.n_img = (r0p + 4095) / 4096; sp.n_txt = (r1p + 4095) / 4096; }
+    const int splits = sp.n_img + sp.n_txt;
+    if (splits > L.scap_head)
+        return fail(UMLH_E_INVALID, "bf16 dW: %d + %d reduction rows need more than %d split-K slabs", r0p, r1p, L.scap_head);
+    const u16* any16 = ri > 0 ? static_cast<const u16*>(img->feats_bf16) : static_cast<const u16*>(txt->feats_bf16);
+    int64_t* iota = ws_iota(h);
+    DwArgsB g = dw_base_args(h);
+    g.A = ws16(h, L.dzt); g.lda = (int)round_up(c.num_classes, 128);
+    g.B = proj ? ws16(h, L.h) : (ri > 0 ? static_cast<const u16*>(img->feats_bf16) : any16);
+    g.k_rows = (ri > 0 && img->index && !proj) ? img->index : iota; g.ldb = c.d_shared;
+    g.B2 = rt > 0 ? static_cast<const u16*>(txt->feats_bf16) : any16;
+    g.k_rows2 = (rt > 0 && txt->index) ? txt->index : iota; g.ldb2 = c.d_shared;
+    g.out = ws(h, L.slabs_head); g.ldo = c.d_shared;
+    g.M = c.num_classes; g.N = c.d_shared; g.K = r0p + r1p;
+    g.k_chunk = sp.chunk; g.k_switch = r0p; g.k_valid1 = ri; g.k_valid2 = rt; g.slab_stride = L.n_head;
+    g.nsplit = splits; g.nsplit1 = sp.n_img; x.n_slabs_img = sp.n_img;
+    const bool with_head = fused && x.head && h->fuse >= 2;
+    const int ntask = umlh_bf16_step_tasks(nb, g.M, g.N, splits, L.n_head, with_head);
+    if (fused && ntask <= L.ctl_tasks) {
+        // forward + dW (+ update + finalize) as ONE launch of persistent workgroups over claimed tasks (StepCtl)
+        if (h->fuse_epoch > 0xFFFFFF00u) {            // tag wrap (2^32 launches): start the epoch-tagged words over
+            HIPCHK((int)hipMemsetAsync(ws(h, L.fuse_flags), 0, sizeof(float) * (size_t)(3 * L.ctl_tasks), x.st), "step control words");
+            h->fuse_epoch = 0;
+        }
+        ++h->fuse_epoch;
+        HeadFuse hf;
+        if (with_head) { hf = *x.head; hf.n_slabs = splits; hf.n_slabs_img = sp.n_img; }
+        unsigned long long* done = reinterpret_cast<unsigned long long*>(ws(h, L.fuse_flags));
+        unsigned* claim = reinterpret_cast<unsigned*>(done + L.ctl_tasks);
+        unsigned* status = claim + L.ctl_tasks;
+        HIPCHK(umlh_bf16_launch_step(&fb, h->ctw, h->wc, nb, &g, splits, claim, done, status, h->fuse_epoch, h->ts, nb * h->ts,
+                                     with_head ? &hf : nullptr, (h->dbg_step && 4LL * ntask <= 64LL * L.max_blocks) ? ws_stamps(h) : nullptr,
+                                     h->step_grid, h->step_lazy, x.st), "step_bf16");
+        x.head_done = with_head;
+        h->step_launches++;
+    } else {
+        if (fused) HIPCHK(umlh_bf16_launch_fwd(&fb, h->ctw, h->wc, h->stw, nb, x.st), "fwd_ce_bf16");
+        HIPCHK(umlh_bf16_launch_dw(&g, splits, 0, 0, x.st), "dw_bf16");
+    }
+    x.n_slabs_head = splits;
+    return UMLH_OK;
+}
+
+// dH^T = W_head^T dZ^T (image columns), then dW_proj = dH^T X_img as split-K slabs
+static int bf16_proj_backward(umlh_handle_t h, StepCall& x) {
+    const umlh_config_t& c = h->cfg;
+    const Layout& L = h->L;
+    const int crows = (int)round_up(c.num_classes, 128), dsp = (int)round_up(c.d_shared, 128), r0p = x.r0p;
+    int64_t* iota = ws_iota(h);
+    // dH^T[n][r] = sum_c W_head[c][n] dZ^T[c][r]  (image columns), bf16 chunk-major [r/64][d_shared^128][64] out
+    u16* wht16 = ws16(h, L.wht16);
+    u16* dht16 = ws16(h, L.dht);
+    HIPCHK(umlh_bf16_launch_transpose_shadow(h->buf.w_head, c.num_classes, c.d_shared, dsp, wht16, 1, x.st), "W_head^T shadow");
+    const int kc = (int)round_up(c.num_classes, 64);
+    DwArgsB g = dw_base_args(h);
+    g.A = wht16; g.lda = dsp;
+    g.B = g.B2 = ws16(h, L.dzt); g.k_rows = g.k_rows2 = iota; g.ldb = g.ldb2 = 64; g.bcs = crows * 64;
+    g.M = c.d_shared; g.N = r0p; g.K = kc;
+    g.k_chunk = (int)round_up(kc, 256); g.k_switch = kc; g.k_valid1 = c.num_classes; g.k_valid2 = 0;
+    g.out16 = dht16; g.ldo = dsp;
+    HIPCHK(umlh_bf16_launch_dw(&g, 1, 0, 2, x.st), "dH^T (bf16)");
+    // dW_proj[n][k] = sum_r dH^T[n][r] X_img[r][k]
+    SplitPlan sp = plan_splits(r0p, 0, L.scap_proj, 256, 256);
+    if (sp.chunk > 4096) { sp.chunk = 4096; sp.n_img = (r0p + 4095) / 4096; }
+    if (sp.n_img > L.scap_proj)
+        return fail(UMLH_E_INVALID, "bf16 dW_proj: %d reduction rows need more than %d split-K slabs", r0p, L.scap_proj);
+    DwArgsB p = dw_base_args(h);
+    p.A = dht16; p.lda = dsp;
+    p.B = p.B2 = static_cast<const u16*>(x.img->feats_bf16); p.k_rows = p.k_rows2 = x.img->index ? x.img->index : iota;
+    p.ldb = p.ldb2 = c.d_img;
+    p.M = c.d_shared; p.N = c.d_img; p.K = r0p;
+    p.k_chunk = sp.chunk; p.k_switch = r0p; p.k_valid1 = x.ri; p.k_valid2 = 0;
+    p.out = ws(h, L.slabs_proj); p.ldo = c.d_img; p.slab_stride = L.n_proj;
+    p.nsplit = p.nsplit1 = sp.n_img;
+    HIPCHK(umlh_bf16_launch_dw(&p, sp.n_img, 0, 0, x.st), "dW_proj (bf16)");
+    x.n_slabs_proj = sp.n_img;
+    return UMLH_OK;
+}
+
+static int forward_backward_bf16(umlh_handle_t h, StepCall& x) {
+    const umlh_config_t& c = h->cfg;
+    hipStream_t st = x.st;
+    if ((x.ri > 0 && !x.img->feats_bf16) || (x.rt > 0 && !x.txt->feats_bf16))
+        return fail(UMLH_E_INVALID, "bf16 mode: batch.feats_bf16 is required (umlh_to_bf16 of the feature table)");
+    const bool proj = c.has_proj && x.ri > 0;
     mark(h, 0, st);
-    if (ri > 0 && c.has_proj) HIPCHK(launch_proj_forward(h, img, H, st), "proj forward");
+    if (!h->iota_ready) {                      // identity row ids + zero page of dw_base_args, once per bind
+        HIPCHK(umlh_launch_iota(reinterpret_cast<long long*>(ws_iota(h)), h->L.n_iota, st), "iota");
+        HIPCHK((int)hipMemsetAsync(ws(h, h->L.zeros), 0, 64 * sizeof(float), st), "zero page");
+        h->iota_ready = true;
+    }
+    if (proj) RC(bf16_proj_forward(h, x));
+    // bf16 shadow of the fp32 master weight: refreshed here unless the previous step of the same umlh_train_steps call just
+    // wrote it from its update kernel (between calls the caller may have rewritten w_head: load_state_dict, zero-shot init)
+    if (!h->shadow_fresh)
+        HIPCHK(umlh_launch_w_shadow(h->buf.w_head, ws16(h, h->L.w16), c.num_classes, c.d_shared, class_pad(h), st), "w_shadow");
+    h->shadow_fresh = false;
     mark(h, 1, st);
+    FwdArgsB fb;
+    bool fused = false;
+    RC(bf16_forward_ce(h, x, proj, fb, fused));
+    mark(h, 2, st);
+    if (!x.want_grad) return UMLH_OK;
+    RC(bf16_dw_head(h, x, proj, fb, fused));
+    mark(h, 3, st);
+    if (x.overlap) RC(dp_after_head(h, x));
+    if (proj) RC(bf16_proj_backward(h, x));
+    mark(h, 4, st);
+    return UMLH_OK;
+}
 
+// ---- fp32 mode ----
+static int f32_forward_ce(umlh_handle_t h, const StepCall& x) {
+    const umlh_config_t& c = h->cfg;
+    const Layout& L = h->L;
     FwdArgs fa;
     memset(&fa, 0, sizeof(fa));
-    SegDesc& s0 = fa.seg[0];
-    SegDesc& s1 = fa.seg[1];
-    if (ri > 0) {
-        s0.feats = c.has_proj ? H : img->feats;
-        s0.feat_index = c.has_proj ? nullptr : img->index;
-        s0.labels = img->labels; s0.label_index = img->index;
-        s0.ld = c.d_shared; s0.rows = ri;
-        s0.w_over_rows = hy->img_alpha / (float)img->global_rows;
-    }
-    s0.scale_ptr = h->buf.scales; s0.col0 = 0; s0.blk0 = 0;
-    if (rt > 0) {
-        s1.feats = txt->feats; s1.feat_index = txt->index;
-        s1.labels = txt->labels; s1.label_index = txt->index;
-        s1.ld = c.d_shared; s1.rows = rt;
-        s1.w_over_rows = hy->alpha / (float)txt->global_rows;
-    }
-    s1.scale_ptr = h->buf.scales + 1; s1.col0 = r0p; s1.blk0 = nb0;
+    fill_segs(fa.seg, h, x, x.ri > 0 ? (c.has_proj ? ws(h, L.h) : x.img->feats) : nullptr, c.has_proj != 0,
+              x.rt > 0 ? x.txt->feats : nullptr);
     fa.W = h->buf.w_head; fa.C = c.num_classes; fa.K = c.d_shared;
-    fa.dzt = want_grad ? dzt : nullptr; fa.ldz = L.ldz;
+    fa.dzt = x.want_grad ? ws(h, L.dzt) : nullptr; fa.ldz = L.ldz;
     fa.partials = ws(h, L.partials);
-    fa.row_stats = h->row_stats;
-    fa.stamps = (h->dbg_fwd == 9 || h->dbg_fwd >= 20) ? reinterpret_cast<unsigned long long*>(ws(h, L.dbg)) : nullptr;
+    fa.row_stats = x.row_stats;
+    fa.stamps = (h->dbg_fwd == 9 || h->dbg_fwd >= 20) ? ws_stamps(h) : nullptr;
     fa.dbg = h->dbg_fwd;
     fa.learn = c.learnable_temp;
     if (L.w32s) {
         // refreshed here unless the previous step of the same umlh_train_steps call (or the data-parallel update) just wrote
         // it from its update kernel (between calls the caller may have rewritten w_head)
         if (!h->shadow_fresh)
-            HIPCHK(umlh_launch_w_shadow32(h->buf.w_head, ws(h, L.w32s), c.num_classes, c.d_shared, 32 * h->ctw * h->wc, st), "w_shadow32");
+            HIPCHK(umlh_launch_w_shadow32(h->buf.w_head, ws(h, L.w32s), c.num_classes, c.d_shared, class_pad(h), x.st), "w_shadow32");
         h->shadow_fresh = false;
         fa.Ws = ws(h, L.w32s);
         fa.x3 = umlh_f32_x3();
     }
-    HIPCHK(umlh_f32_launch_fwd(&fa, h->ctw, h->wc, nb0 + nb1, st), "fwd_ce");
-    mark(h, 2, st);
-    if (!want_grad) return UMLH_OK;
+    HIPCHK(umlh_f32_launch_fwd(&fa, h->ctw, h->wc, x.nb0 + x.nb1, x.st), "fwd_ce");
+    return UMLH_OK;
+}
 
-    // dW_head[c][k] = sum_r dZ^T[c][r] F[r][k]  over image rows then text rows
-    const int rcols = r0p + r1p;
-    {
-        const SplitPlan sp = plan_splits(r0p, r1p, L.scap_head, KT, 64);
-        const int chunk = sp.chunk, splits = sp.n_img + sp.n_txt;
-        if (splits > L.scap_head)
-            return fail(UMLH_E_INVALID, "dW: %d + %d reduction rows need more than %d split-K slabs", r0p, r1p, L.scap_head);
-        GemmArgs g;
-        memset(&g, 0, sizeof(g));
-        g.A = dzt; g.lda = L.ldz;
-        g.M = c.num_classes; g.N = c.d_shared; g.K = rcols;
-        g.B = c.has_proj ? H : (img ? img->feats : nullptr);
-        g.k_rows = c.has_proj ? nullptr : (img ? img->index : nullptr);
-        g.ldb = c.d_shared;
-        g.B2 = txt ? txt->feats : nullptr; g.k_rows2 = txt ? txt->index : nullptr; g.ldb2 = c.d_shared;
-        g.k_switch = r0p; g.k_valid1 = ri; g.k_valid2 = rt;
-        g.out = ws(h, L.slabs_head); g.ldo = c.d_shared;
-        g.k_chunk = chunk; g.slab_stride = L.n_head; g.alpha = 1.f; g.nsplit1 = sp.n_img; h->n_slabs_img = sp.n_img;
-        HIPCHK(umlh_f32_launch_gemm(&g, 0, 1, splits, st), "dW_head gemm");
-        *n_slabs_head = splits;
-    }
+// dW_head[c][k] = sum_r dZ^T[c][r] F[r][k]  over image rows then text rows
+static int f32_dw_head(umlh_handle_t h, StepCall& x) {
+    const umlh_config_t& c = h->cfg;
+    const Layout& L = h->L;
+    const SplitPlan sp = plan_splits(x.r0p, x.r1p, L.scap_head, KT, 64);
+    const int splits = sp.n_img + sp.n_txt;
+    if (splits > L.scap_head)
+        return fail(UMLH_E_INVALID, "dW: %d + %d reduction rows need more than %d split-K slabs", x.r0p, x.r1p, L.scap_head);
+    GemmArgs g;
+    memset(&g, 0, sizeof(g));
+    g.A = ws(h, L.dzt); g.lda = L.ldz;
+    g.M = c.num_classes; g.N = c.d_shared; g.K = x.r0p + x.r1p;
+    g.B = c.has_proj ? ws(h, L.h) : (x.img ? x.img->feats : nullptr);
+    g.k_rows = c.has_proj ? nullptr : (x.img ? x.img->index : nullptr);
+    g.ldb = c.d_shared;
+    g.B2 = x.txt ? x.txt->feats : nullptr; g.k_rows2 = x.txt ? x.txt->index : nullptr; g.ldb2 = c.d_shared;
+    g.k_switch = x.r0p; g.k_valid1 = x.ri; g.k_valid2 = x.rt;
+    g.out = ws(h, L.slabs_head); g.ldo = c.d_shared;
+    g.k_chunk = sp.chunk; g.slab_stride = L.n_head; g.alpha = 1.f; g.nsplit1 = sp.n_img; x.n_slabs_img = sp.n_img;
+    HIPCHK(umlh_f32_launch_gemm(&g, 0, 1, splits, x.st), "dW_head gemm");
+    x.n_slabs_head = splits;
+    return UMLH_OK;
+}
+
+// dH^T = W_head^T dZ^T (image columns only), then dW_proj = dH^T X_img[index] as split-K slabs
+static int f32_proj_backward(umlh_handle_t h, StepCall& x) {
+    const umlh_config_t& c = h->cfg;
+    const Layout& L = h->L;
+    const int ri = x.ri;
+    float* dht = ws(h, L.dht);
+    GemmArgs g;
+    memset(&g, 0, sizeof(g));
+    g.A = h->buf.w_head; g.lda = c.d_shared;            // A(m=n, k=c) = W[c][n]  (k-major)
+    g.B = ws(h, L.dzt); g.ldb = L.ldz;                  // B(n=r, k=c) = dZ^T[c][r]
+    g.M = c.d_shared; g.N = ri; g.K = c.num_classes;
+    g.out = dht; g.ldo = L.rcap_img;
+    g.k_chunk = g.K; g.alpha = 1.f;
+    g.k_switch = INT_MAX; g.k_valid1 = g.K;
+    HIPCHK(umlh_f32_launch_gemm(&g, 1, 1, 1, x.st), "dH gemm");
+    int chunk = (int)round_up((ri + L.scap_proj - 1) / L.scap_proj, KT);
+    if (chunk < 64) chunk = 64;
+    const int splits = (ri + chunk - 1) / chunk;
+    GemmArgs p;
+    memset(&p, 0, sizeof(p));
+    p.A = dht; p.lda = L.rcap_img;
+    p.B = x.img->feats; p.k_rows = x.img->index; p.ldb = c.d_img;
+    p.M = c.d_shared; p.N = c.d_img; p.K = ri;
+    p.out = ws(h, L.slabs_proj); p.ldo = c.d_img;
+    p.k_chunk = chunk; p.slab_stride = L.n_proj; p.alpha = 1.f;
+    p.k_switch = INT_MAX; p.k_valid1 = ri;
+    HIPCHK(umlh_f32_launch_gemm(&p, 0, 1, splits, x.st), "dW_proj gemm");
+    x.n_slabs_proj = splits;
+    return UMLH_OK;
+}
+
+static int forward_backward_f32(umlh_handle_t h, StepCall& x) {
+    hipStream_t st = x.st;
+    const bool proj = h->cfg.has_proj && x.ri > 0;
+    mark(h, 0, st);
+    if (proj) HIPCHK(launch_proj_forward(h, x.img, ws(h, h->L.h), st), "proj forward");
+    mark(h, 1, st);
+    RC(f32_forward_ce(h, x));
+    mark(h, 2, st);
+    if (!x.want_grad) return UMLH_OK;
+    RC(f32_dw_head(h, x));
     mark(h, 3, st);
-    if (h->overlap_pending) { int rc2 = dp_after_head(h, *n_slabs_head, st); if (rc2) return rc2; }
-    *n_slabs_proj = 0;
-    if (c.has_proj && ri > 0) {
-        // dH^T[n][r] = sum_c W_head[c][n] dZ^T[c][r]   (image columns only)
-        float* dht = ws(h, L.dht);
-        GemmArgs g;
-        memset(&g, 0, sizeof(g));
-        g.A = h->buf.w_head; g.lda = c.d_shared;            // A(m=n, k=c) = W[c][n]  (k-major)
-        g.B = dzt; g.ldb = L.ldz;                           // B(n=r, k=c) = dZ^T[c][r]
-        g.M = c.d_shared; g.N = ri; g.K = c.num_classes;
-        g.out = dht; g.ldo = L.rcap_img;
-        g.k_chunk = g.K; g.alpha = 1.f;
-        g.k_switch = INT_MAX; g.k_valid1 = g.K;
-        HIPCHK(umlh_f32_launch_gemm(&g, 1, 1, 1, st), "dH gemm");
-        // dW_proj[n][k] = sum_r dH^T[n][r] X_img[index[r]][k]
-        int want = L.scap_proj;
-        int chunk = (int)round_up((ri + want - 1) / want, KT);
-        if (chunk < 64) chunk = 64;
-        int splits = (ri + chunk - 1) / chunk;
-        GemmArgs p;
-        memset(&p, 0, sizeof(p));
-        p.A = dht; p.lda = L.rcap_img;
-        p.B = img->feats; p.k_rows = img->index; p.ldb = c.d_img;
-        p.M = c.d_shared; p.N = c.d_img; p.K = ri;
-        p.out = ws(h, L.slabs_proj); p.ldo = c.d_img;
-        p.k_chunk = chunk; p.slab_stride = L.n_proj; p.alpha = 1.f;
-        p.k_switch = INT_MAX; p.k_valid1 = ri;
-        HIPCHK(umlh_f32_launch_gemm(&p, 0, 1, splits, st), "dW_proj gemm");
-        *n_slabs_proj = splits;
-    }
+    if (x.overlap) RC(dp_after_head(h, x));
+    if (proj) RC(f32_proj_backward(h, x));
     mark(h, 4, st);
     return UMLH_OK;
+}
+
+// Everything of a step up to (not including) the parameter update.
+static int forward_backward(umlh_handle_t h, StepCall& x) {
+    x.ri = x.img ? x.img->rows : 0;
+    x.rt = x.txt ? x.txt->rows : 0;
+    x.nb0 = fwd_blocks_img(h, x.ri);
+    x.nb1 = (x.rt + h->ts - 1) / h->ts;
+    x.r0p = x.nb0 * h->ts;
+    x.r1p = x.nb1 * h->ts;
+    return h->cfg.precision == UMLH_PREC_BF16 ? forward_backward_bf16(h, x) : forward_backward_f32(h, x);
 }
 
 static FinalizeArgs make_finalize(umlh_handle_t h, const umlh_batch_t* img, const umlh_batch_t* txt,
@@ -1292,42 +1248,53 @@ static int check_step(umlh_handle_t h, const umlh_batch_t* img, const umlh_batch
     return UMLH_OK;
 }
 
+// The head part of a one-launch step (linear bf16 head): the update in place, or (grad_out != NULL, the data-parallel
+// split step) the slab sum into the gradient message with nothing updated.  The launch fills in the slab counts.
+static HeadFuse make_head_fuse(umlh_handle_t h, const OptArgs& o, const FinalizeArgs& f, float* grad_out) {
+    HeadFuse hf;
+    memset(&hf, 0, sizeof(hf));
+    hf.slabs = ws(h, h->L.slabs_head); hf.slab_stride = h->L.n_head; hf.C = h->cfg.num_classes; hf.K = h->cfg.d_shared;
+    hf.cpad = class_pad(h); hf.o = o; hf.f = f;
+    hf.grad_out = grad_out;
+    if (!grad_out) { hf.p = h->buf.w_head; hf.m = h->buf.m_head; hf.v = h->buf.v_head; hf.shadow = ws16(h, h->L.w16); }
+    return hf;
+}
+static inline bool head_fuse_shape(const umlh_handle_s* h) {
+    return h->cfg.precision == UMLH_PREC_BF16 && !h->cfg.has_proj && h->cfg.d_shared % 8 == 0;
+}
+
+// head_step_kernel as a plain slab sum: no diagnostics, image slabs [0, n_slabs_img) summed before the text slabs
+static DiagArgs diag_off(int n_slabs_img) {
+    DiagArgs d;
+    d.dst = nullptr; d.n_slabs_img = n_slabs_img; d.inv_w0 = d.inv_w1 = 0.f; d.part = nullptr; d.ticket = nullptr;
+    return d;
+}
+
 static int train_step_impl(umlh_handle_t h, const umlh_batch_t* img, const umlh_batch_t* txt, const umlh_hyper_t* hy,
                            float* scalars_out, hipStream_t st, bool keep_shadow) {
-    int sh = 0, sp = 0;
     // gradient diagnostics: written to the caller's scalar row (or the workspace tail) by the head-step launch
     h->dp_diag = false;
     float* tail = ws(h, h->L.grads) + msg_tail_off(h);
-    h->diag_dst = h->diagnostics ? (scalars_out ? scalars_out : tail + 2) + UMLH_N_CORE_SCALARS : nullptr;
+    float* diag_dst = h->diagnostics ? (scalars_out ? scalars_out : tail + 2) + UMLH_N_CORE_SCALARS : nullptr;
     const umlh_config_t& c = h->cfg;
     OptArgs o = make_opt(h->cfg, *hy);
     FinalizeArgs f = make_finalize(h, img, txt, hy, true, scalars_out, true);
     // the update (and the step scalars) may ride in the forward + dW launch: linear bf16 head, no gradient diagnostics
     // (in profiling mode the interval mark 2 -> 3 then holds the whole step and the others are empty)
+    StepCall x{img, txt, hy, true, st};
     HeadFuse hfuse;
-    memset(&hfuse, 0, sizeof(hfuse));
-    h->head_fused_done = false;
-    h->pending_head = nullptr;
-    if (c.precision == UMLH_PREC_BF16 && !c.has_proj && c.d_shared % 8 == 0 && !h->diag_dst) {
-        hfuse.slabs = ws(h, h->L.slabs_head); hfuse.slab_stride = h->L.n_head; hfuse.C = c.num_classes; hfuse.K = c.d_shared;
-        hfuse.p = h->buf.w_head; hfuse.m = h->buf.m_head; hfuse.v = h->buf.v_head;
-        hfuse.shadow = reinterpret_cast<unsigned short*>(ws(h, h->L.w16)); hfuse.cpad = 32 * h->ctw * h->wc;
-        hfuse.o = o; hfuse.f = f;
-        h->pending_head = &hfuse;
-    }
-    int rc = forward_backward(h, img, txt, hy, true, st, &sh, &sp);
-    h->pending_head = nullptr;
-    if (rc) return rc;
-    if (h->head_fused_done) {
-        h->head_fused_done = false;
+    if (head_fuse_shape(h) && !diag_dst) { hfuse = make_head_fuse(h, o, f, nullptr); x.head = &hfuse; }
+    RC(forward_backward(h, x));
+    if (x.head_done) {
         h->shadow_fresh = keep_shadow;
         mark(h, 5, st);
         return UMLH_OK;
     }
+    const int sh = x.n_slabs_head, sp = x.n_slabs_proj;
     DiagArgs dg;
-    dg.dst = h->diag_dst; dg.n_slabs_img = h->n_slabs_img;
+    dg.dst = diag_dst; dg.n_slabs_img = x.n_slabs_img;
     dg.part = ws(h, h->L.diag_part);
-    dg.ticket = reinterpret_cast<unsigned*>(dg.part + 4 * ((h->L.n_head + 1023) / 1024 + 2));
+    dg.ticket = diag_ticket(h);
     dg.inv_w0 = hy->img_alpha != 0.f ? 1.f / hy->img_alpha : 0.f;
     dg.inv_w1 = hy->alpha != 0.f ? 1.f / hy->alpha : 0.f;
     dg.cols = h->diag_cols;
@@ -1336,7 +1303,7 @@ static int train_step_impl(umlh_handle_t h, const umlh_batch_t* img, const umlh_
         const bool bf = c.precision == UMLH_PREC_BF16;
         HIPCHK(umlh_launch_head_step(ws(h, h->L.slabs_head), sh, h->L.n_head, c.num_classes, c.d_shared, h->buf.w_head,
                                      h->buf.m_head, h->buf.v_head, &o, bf ? ws(h, h->L.w16) : nullptr,
-                                     32 * h->ctw * h->wc, &f, nullptr, &dg, h->L.w32s ? ws(h, h->L.w32s) : nullptr, st), "head step");
+                                     class_pad(h), &f, nullptr, &dg, h->L.w32s ? ws(h, h->L.w32s) : nullptr, st), "head step");
         h->shadow_fresh = (bf || h->L.w32s) && keep_shadow;
     } else {
         HIPCHK(umlh_launch_finalize(&f, st), "finalize");
@@ -1451,7 +1418,7 @@ static int micro_launch_group(const MicroItem* it, int n, int k0, int n_steps, h
         d.scalars_out = it[i].scalars_out ? it[i].scalars_out + (size_t)k0 * UMLH_N_SCALARS : nullptr;
         d.xchg = reinterpret_cast<unsigned long long*>(ws(h, h->L.mc_xchg));
         d.status = reinterpret_cast<unsigned*>(ws(h, h->L.mc_flags)) + 64;
-        static const bool dbg_micro = [] { const char* e = getenv("UMLH_DBG_MICRO"); return e && atoi(e) == 1; }();
+        static const bool dbg_micro = env_int("UMLH_DBG_MICRO", 0) == 1;
         d.stamps = (dbg_micro && (long long)h->L.max_blocks * 128 * sizeof(float) >= (size_t)h->L.mc_nwg * 96)
                        ? reinterpret_cast<unsigned long long*>(ws(h, h->L.dbg)) : nullptr;
         d.epoch0 = h->micro_epoch;
@@ -1778,23 +1745,23 @@ static int dp_allreduce(umlh_handle_t h, float* buf, long long n, hipStream_t st
 // diagnostics are on (finetune.py:190-191,203-206 need the GLOBAL per-modality gradients: dot products and norms are
 // not linear in the ranks' partial sums, so the two sums travel separately and the update kernel forms the diagnostics
 // from the all-reduced pair).
-static int dp_reduce_head(umlh_handle_t h, const umlh_batch_t* img, const umlh_batch_t* txt, const umlh_hyper_t* hy, int sh,
-                          hipStream_t st) {
-    OptArgs o = make_opt(h->cfg, *hy);
-    FinalizeArgs f = make_finalize(h, img, txt, hy, true, nullptr, false);
+static int dp_reduce_head(umlh_handle_t h, const StepCall& x) {
+    hipStream_t st = x.st;
+    const int sh = x.n_slabs_head, si = x.n_slabs_img < sh ? x.n_slabs_img : sh;
+    OptArgs o = make_opt(h->cfg, *x.hy);
+    FinalizeArgs f = make_finalize(h, x.img, x.txt, x.hy, true, nullptr, false);
     float* grads = ws(h, h->L.grads);
     const long long nh = h->L.n_head;
     if (h->dp_diag) {
-        const int si = h->n_slabs_img < sh ? h->n_slabs_img : sh;
         FinalizeArgs f2 = f;
         f2.partials = nullptr;                           // the step scalars are formed once (first launch)
-        DiagArgs none; none.dst = nullptr; none.n_slabs_img = si; none.inv_w0 = none.inv_w1 = 0.f; none.part = nullptr; none.ticket = nullptr;
+        DiagArgs none = diag_off(si);
         if (si > 0) HIPCHK(umlh_launch_head_step(ws(h, h->L.slabs_head), si, nh, h->cfg.num_classes, h->cfg.d_shared, nullptr, nullptr,
-                                                 nullptr, &o, nullptr, 32 * h->ctw * h->wc, &f, grads, &none, nullptr, st), "reduce head (image rows)");
+                                                 nullptr, &o, nullptr, class_pad(h), &f, grads, &none, nullptr, st), "reduce head (image rows)");
         else HIPCHK((int)hipMemsetAsync(grads, 0, sizeof(float) * nh, st), "zero image gradient");
         none.n_slabs_img = 0;
         if (sh - si > 0) HIPCHK(umlh_launch_head_step(ws(h, h->L.slabs_head) + (size_t)si * nh, sh - si, nh, h->cfg.num_classes, h->cfg.d_shared,
-                                                      nullptr, nullptr, nullptr, &o, nullptr, 32 * h->ctw * h->wc, si > 0 ? &f2 : &f, grads + nh,
+                                                      nullptr, nullptr, nullptr, &o, nullptr, class_pad(h), si > 0 ? &f2 : &f, grads + nh,
                                                       &none, nullptr, st), "reduce head (text rows)");
         else HIPCHK((int)hipMemsetAsync(grads + nh, 0, sizeof(float) * nh, st), "zero text gradient");
         return UMLH_OK;
@@ -1802,10 +1769,9 @@ static int dp_reduce_head(umlh_handle_t h, const umlh_batch_t* img, const umlh_b
     if (h->cfg.d_shared % 8 == 0) {
         // image slabs and text slabs are summed separately, then added: the order of the fused step and of the one-launch
         // gradient (step_update_task), so the message is bit-identical whichever launch form wrote it
-        DiagArgs order; order.dst = nullptr; order.n_slabs_img = h->n_slabs_img < sh ? h->n_slabs_img : sh;
-        order.inv_w0 = order.inv_w1 = 0.f; order.part = nullptr; order.ticket = nullptr;
+        DiagArgs order = diag_off(si);
         HIPCHK(umlh_launch_head_step(ws(h, h->L.slabs_head), sh, nh, h->cfg.num_classes, h->cfg.d_shared, nullptr, nullptr, nullptr, &o,
-                                     nullptr, 32 * h->ctw * h->wc, &f, grads, &order, nullptr, st), "reduce head");
+                                     nullptr, class_pad(h), &f, grads, &order, nullptr, st), "reduce head");
     } else {
         HIPCHK(umlh_launch_finalize(&f, st), "finalize");
         HIPCHK(umlh_launch_reduce_update(0, ws(h, h->L.slabs_head), sh, nh, nh, grads, nullptr, nullptr, nullptr, &o, 0, 0, st), "reduce head");
@@ -1815,14 +1781,12 @@ static int dp_reduce_head(umlh_handle_t h, const umlh_batch_t* img, const umlh_b
 
 // 2-layer head, data parallel: the head gradient is complete behind the dW_head GEMM; its all-reduce (12.8 MB at cfg3)
 // runs on the second stream beside the img_proj backward GEMMs (dH^T, dW_proj) of the step's stream.
-static int dp_after_head(umlh_handle_t h, int n_slabs_head, hipStream_t st) {
-    h->overlap_pending = false;
-    int rc = dp_reduce_head(h, h->overlap_img, h->overlap_txt, h->overlap_hy, n_slabs_head, st);
-    if (rc) return rc;
+static int dp_after_head(umlh_handle_t h, const StepCall& x) {
+    hipStream_t st = x.st;
+    RC(dp_reduce_head(h, x));
     HIPCHK((int)hipEventRecord(h->ev_head_ready, st), "data parallel: event record");
     HIPCHK((int)hipStreamWaitEvent(h->comm_stream, h->ev_head_ready, 0), "data parallel: stream wait");
-    rc = dp_allreduce(h, ws(h, h->L.grads), msg_head_len(h), h->comm_stream);
-    if (rc) return rc;
+    RC(dp_allreduce(h, ws(h, h->L.grads), msg_head_len(h), h->comm_stream));
     HIPCHK((int)hipEventRecord(h->ev_head_done, h->comm_stream), "data parallel: event record");
     return UMLH_OK;
 }
@@ -1831,7 +1795,6 @@ static int dp_after_head(umlh_handle_t h, int n_slabs_head, hipStream_t st) {
 // head part then overlaps the img_proj backward when the head has one.
 static int grad_step_impl(umlh_handle_t h, const umlh_batch_t* img, const umlh_batch_t* txt, const umlh_hyper_t* hy, hipStream_t st,
                           bool comm) {
-    int sh = 0, sp = 0;
     h->last_rows_img = img ? img->rows : 0;
     h->last_rows_txt = txt ? txt->rows : 0;
     h->global_rows_img = img ? img->global_rows : 0;
@@ -1843,29 +1806,20 @@ static int grad_step_impl(umlh_handle_t h, const umlh_batch_t* img, const umlh_b
         return comm ? dp_allreduce(h, grads, msg_len(h), st) : UMLH_OK;
     }
     if (!(hy->flags & UMLH_F_WEIGHTS_UNCHANGED)) h->shadow_fresh = false;
-    h->diag_dst = nullptr;                                // the diagnostics of a split step are formed by umlh_apply_update
+    // (the gradient diagnostics of a split step are formed by umlh_apply_update)
     const bool overlap = comm && h->cfg.has_proj && h->comm_stream != nullptr && (img ? img->rows : 0) > 0;
-    h->overlap_pending = overlap;
-    h->overlap_hy = hy; h->overlap_img = img; h->overlap_txt = txt;
+    StepCall x{img, txt, hy, true, st};
+    x.overlap = overlap;
+    OptArgs o = make_opt(h->cfg, *hy);
     // linear bf16 head: the slab sum into the message (and the step scalars) rides in the forward + dW launch
     HeadFuse hfuse;
-    memset(&hfuse, 0, sizeof(hfuse));
-    h->head_fused_done = false;
-    h->pending_head = nullptr;
-    if (h->cfg.precision == UMLH_PREC_BF16 && !h->cfg.has_proj && h->cfg.d_shared % 8 == 0 && !h->dp_diag && !overlap) {
-        hfuse.slabs = ws(h, h->L.slabs_head); hfuse.slab_stride = h->L.n_head; hfuse.C = h->cfg.num_classes; hfuse.K = h->cfg.d_shared;
-        hfuse.grad_out = grads; hfuse.cpad = 32 * h->ctw * h->wc;
-        hfuse.o = make_opt(h->cfg, *hy); hfuse.f = make_finalize(h, img, txt, hy, true, nullptr, false);
-        h->pending_head = &hfuse;
+    if (head_fuse_shape(h) && !h->dp_diag && !overlap) {
+        hfuse = make_head_fuse(h, o, make_finalize(h, img, txt, hy, true, nullptr, false), grads);
+        x.head = &hfuse;
     }
-    int rc = forward_backward(h, img, txt, hy, true, st, &sh, &sp);
-    h->pending_head = nullptr;
-    h->overlap_pending = false;
-    if (rc) return rc;
-    const bool head_done = h->head_fused_done;
-    h->head_fused_done = false;
-    if (!overlap && !head_done) { rc = dp_reduce_head(h, img, txt, hy, sh, st); if (rc) return rc; }
-    OptArgs o = make_opt(h->cfg, *hy);
+    RC(forward_backward(h, x));
+    if (!overlap && !x.head_done) RC(dp_reduce_head(h, x));
+    const int sp = x.n_slabs_proj;
     if (h->cfg.has_proj) {
         float* gp = grads + msg_head_len(h);
         if (sp > 0)
@@ -1877,12 +1831,10 @@ static int grad_step_impl(umlh_handle_t h, const umlh_batch_t* img, const umlh_b
     mark(h, 5, st);
     if (comm) {
         if (overlap) {                                    // head part is in flight on the second stream: the rest here, then join
-            rc = dp_allreduce(h, grads + msg_head_len(h), msg_len(h) - msg_head_len(h), st);
-            if (rc) return rc;
+            RC(dp_allreduce(h, grads + msg_head_len(h), msg_len(h) - msg_head_len(h), st));
             HIPCHK((int)hipStreamWaitEvent(st, h->ev_head_done, 0), "data parallel: stream wait");
         } else {
-            rc = dp_allreduce(h, grads, msg_len(h), st);
-            if (rc) return rc;
+            RC(dp_allreduce(h, grads, msg_len(h), st));
         }
     }
     return UMLH_OK;
@@ -1920,7 +1872,7 @@ static int apply_update_impl(umlh_handle_t h, const umlh_hyper_t* hy, float* sca
         DiagArgs dg;
         dg.dst = nullptr; dg.n_slabs_img = 1; dg.inv_w0 = dg.inv_w1 = 0.f;
         dg.part = ws(h, h->L.diag_part);
-        dg.ticket = reinterpret_cast<unsigned*>(dg.part + 4 * ((h->L.n_head + 1023) / 1024 + 2));
+        dg.ticket = diag_ticket(h);
         dg.cols = h->diag_cols;
         if (h->dp_diag) {
             // the two all-reduced per-modality gradients are the two "slabs" of the update kernel: it sums them, steps the
@@ -1931,7 +1883,7 @@ static int apply_update_impl(umlh_handle_t h, const umlh_hyper_t* hy, float* sca
             dg.inv_w1 = hy->alpha != 0.f ? 1.f / hy->alpha : 0.f;
         }
         HIPCHK(umlh_launch_head_step(grads, h->dp_diag ? 2 : 1, h->L.n_head, h->cfg.num_classes, h->cfg.d_shared, h->buf.w_head,
-                                     h->buf.m_head, h->buf.v_head, &o, bf ? ws(h, h->L.w16) : nullptr, 32 * h->ctw * h->wc, &f, nullptr,
+                                     h->buf.m_head, h->buf.v_head, &o, bf ? ws(h, h->L.w16) : nullptr, class_pad(h), &f, nullptr,
                                      h->dp_diag ? &dg : nullptr, h->L.w32s ? ws(h, h->L.w32s) : nullptr, st), "update head");
         h->shadow_fresh = bf || h->L.w32s;              // the next umlh_grad_step may trust it (see umlh_grad_step)
     } else {
@@ -1963,10 +1915,9 @@ int umlh_eval_batch(umlh_handle_t h, const umlh_batch_t* b, float* scalars_out, 
     umlh_hyper_t hy;
     memset(&hy, 0, sizeof(hy));
     hy.lr = 0; hy.step = 1; hy.alpha = 1.f; hy.img_alpha = 1.f;
-    int sh = 0, sp = 0;
     h->shadow_fresh = false;
-    h->diag_dst = nullptr;
-    rc = forward_backward(h, b, nullptr, &hy, false, st, &sh, &sp);
+    StepCall x{b, nullptr, &hy, false, st};
+    rc = forward_backward(h, x);
     if (rc) return rc;
     FinalizeArgs f = make_finalize(h, b, nullptr, &hy, true, scalars_out, false);
     HIPCHK(umlh_launch_finalize(&f, st), "finalize");
@@ -1983,29 +1934,13 @@ int umlh_eval_rows(umlh_handle_t h, const umlh_batch_t* b, float* row_stats, voi
     umlh_hyper_t hy;
     memset(&hy, 0, sizeof(hy));
     hy.lr = 0; hy.step = 1; hy.alpha = 1.f; hy.img_alpha = 1.f;
-    int sh = 0, sp = 0;
     h->shadow_fresh = false;
-    h->diag_dst = nullptr;
-    h->row_stats = row_stats;
-    rc = forward_backward(h, b, nullptr, &hy, false, (hipStream_t)stream, &sh, &sp);
-    h->row_stats = nullptr;
-    return rc;
+    StepCall x{b, nullptr, &hy, false, (hipStream_t)stream};
+    x.row_stats = row_stats;
+    return forward_backward(h, x);
 }
 
 // ---- linear probes (kernels: umlh_kernels_probe.hip); every check precedes the first HIP call ----
-extern "C" {
-unsigned long long umlh_probe_fit_bytes(long long n, int d, int max_iter);
-unsigned long long umlh_probe_stats_bytes(int d);
-int umlh_probe_launch_masked_mean(const float* z, int B, int T, int Z, long long ldb, long long ldt, const long long* lengths,
-                                  float* out, int ldo, hipStream_t st);
-int umlh_probe_launch_stats(const float* x, long long n, int d, int ldx, double* stats, void* scratch, hipStream_t st);
-int umlh_probe_launch_fit(const float* x, long long n, int d, int ldx, const int* y, const double* stats, int kind, double c,
-                          int max_iter, double gtol, double* coef, umlh_probe_record_t* rec, double* objectives, void* scratch,
-                          hipStream_t st);
-int umlh_probe_launch_score(const float* x, long long n, int d, int ldx, const double* stats, const double* coef, const int* y,
-                            long long* correct, float* decision, hipStream_t st);
-}
-
 static const int PROBE_MAX_D = 1024, PROBE_MAX_ITER = 1000;
 static bool probe_shape_ok(int64_t n, int32_t d, int32_t ldx) { return n >= 2 && n < ((int64_t)1 << 31) && d >= 1 && d <= PROBE_MAX_D && ldx >= d; }
 

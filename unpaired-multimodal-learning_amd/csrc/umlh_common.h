@@ -19,6 +19,11 @@ constexpr int KT = 16;
 // memory when the instruction retires instead of sitting dirty in the XCD's L2 until the end-of-kernel write-back that the
 // dependent launch waits for (microarch guide, rows 'boundary' and 'publish-large').  cfg2 bf16 step 46.7 -> 44.8 us.
 // UMLH_WT=0 in the environment selects plain stores (args.plain = 1) for A/B timing.
+// Every environment switch is read through env_int: the integer value of `name`, `def` when it is unset.
+static inline int env_int(const char* name, int def) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : def;
+}
 #if defined(__HIPCC__)
 __device__ __forceinline__ void store_wt_f32(float* p, float v) {
     asm volatile("global_store_dword %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
@@ -31,9 +36,8 @@ __device__ __forceinline__ void store_out_f32(float* p, float v, int plain) {
     if (plain) *p = v; else store_wt_f32(p, v);
 }
 #endif
-static inline int umlh_plain_stores() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("UMLH_WT"); v = (e && e[0] == '0') ? 1 : 0; }
+static inline int umlh_plain_stores() {      // (once per process)
+    static const int v = env_int("UMLH_WT", 1) == 0;
     return v;
 }
 
@@ -44,9 +48,8 @@ static inline int umlh_plain_stores() {
 // case and 2^-24 |x||w| rms (tests/test_x3_split_cpu.py) -- the size of the roundings an fp32 fma chain makes on its running sum:
 // against float64 the two forms are equally accurate (profiles/r03_x3_accuracy.txt) -- and the 32x32x16 bf16 MFMA does in 32
 // cycles what the 32x32x2 fp32 MFMA does in 8 x 64.  UMLH_F32_X3=0 keeps the fp32 MFMA.
-static inline int umlh_f32_x3() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("UMLH_F32_X3"); v = (e && e[0] == '0') ? 0 : 1; }
+static inline int umlh_f32_x3() {            // (once per process)
+    static const int v = env_int("UMLH_F32_X3", 1) != 0;
     return v;
 }
 
@@ -172,7 +175,7 @@ struct FwdArgsB {
     int   wtiles;                // fwd_ce_bf16_q: 32-class tiles per k-step of the W shadow (cpad / 32)
 };
 
-// bf16 GEMM out[m][n] = sum_k A[m][k] * B[k][n] (kernel dw_bf16<AM, OM>).  Written for dW = dZ^T F; the 2-layer
+// bf16 GEMM out[m][n] = sum_k A[m][k] * B[k][n] (kernel dw_bf16_dma<AM, OM>).  Written for dW = dZ^T F; the 2-layer
 // head's projection forward / dH^T / dW_proj reuse it through the A-source and output modes.
 //   AM 0: A column-chunk-major [K/64][lda][64] (k contiguous inside a chunk)     AM 1: A row-major, row m at A + a_rows[m]*lda
 //   OM 0: fp32 split-K slabs   OM 1: bf16 row-major out[m*ldo + n]   OM 2: bf16 chunk-major out[((n>>6)*ldo + m)*64 + (n&63)]

@@ -12,7 +12,7 @@
 #include <cstring>
 #include <new>
 #include "umlh.h"
-#include "umlh_enc.h"
+#include "umlh_launch.h"
 
 namespace {
 
@@ -21,7 +21,7 @@ inline long long ru64(long long x) { return (x + 63) / 64 * 64; }
 // Split-K factor: these GEMMs have few 64x64 output tiles and are bound by the latency of the K walk (one staged chunk per
 // iteration), so K is cut until ~768 workgroups (3 per CU, co-resident) with at least 64 reduction rows each.
 int splits_for(int m, int n, int k) {
-    static const int target = [] { const char* e = getenv("UMLH_ENC_SPLIT_WGS"); return e ? atoi(e) : 768; }();
+    static const int target = env_int("UMLH_ENC_SPLIT_WGS", 768);
     const long long tiles = (long long)((m + 63) / 64) * ((n + 63) / 64);
     if (k < 128 || tiles >= target) return 1;
     long long s = (target + tiles - 1) / tiles;
@@ -102,16 +102,11 @@ int dense_bwd_w(const float* dy, const float* x, float* dw, int M, int N, int K,
     return UMLH_OK;
 }
 
-// Second stream of a layer's backward: the weight-gradient work (dW slabs, column partials, the multi-reduce) does not feed
-// the activation-gradient chain, so it runs beside it -- forked after each producer, joined at the end of the layer.  In a
-// captured sequence the fork/join become parallel branches of the graph.
-struct SideCtx { hipStream_t s2; hipEvent_t ev[5]; };
-
+// The weight-gradient work (dW slabs, column partials, the multi-reduce) does not feed the activation-gradient chain; forking it
+// onto a second stream (parallel branches of the captured graph) measured slower than the single chain (3.15 vs 2.90 ms per
+// step at z = 40) and was removed: everything runs on `st`.
 int layer_backward_impl(const umlh_enc_layer_t* cfg, const float* const* P, const float* h_in, const int64_t* lengths, const float* saved,
-                        const float* dh_out, float* scratch, float* const* G, float* dh_in, hipStream_t st, const SideCtx* side);
-
-int layer_backward_impl(const umlh_enc_layer_t* cfg, const float* const* P, const float* h_in, const int64_t* lengths, const float* saved,
-                        const float* dh_out, float* scratch, float* const* G, float* dh_in, hipStream_t st, const SideCtx* side) {
+                        const float* dh_out, float* scratch, float* const* G, float* dh_in, hipStream_t st) {
     Dims d;
     if (!dims_ok(cfg, d) || !P || !h_in || !saved || !dh_out || !scratch || !G || !dh_in) return UMLH_E_INVALID;
     const Saved S = saved_layout(d);
@@ -121,12 +116,6 @@ int layer_backward_impl(const umlh_enc_layer_t* cfg, const float* const* P, cons
     float *dinw = G[0], *dinb = G[1], *dow = G[2], *dob = G[3], *dw1 = G[4], *db1 = G[5], *dw2 = G[6], *db2 = G[7],
           *dg1 = G[8], *dbe1 = G[9], *dg2 = G[10], *dbe2 = G[11];
     float* slabs = scratch + X.slabs;
-    hipStream_t sw = side ? side->s2 : st;          // stream of the weight-gradient work
-    auto fork = [&](int i) -> int {
-        if (!side) return 0;
-        if (hipEventRecord(side->ev[i], st) != hipSuccess || hipStreamWaitEvent(side->s2, side->ev[i], 0) != hipSuccess) return UMLH_E_HIP;
-        return 0;
-    };
     const uint64_t sd = cfg->seed;
     const unsigned long long* sp = reinterpret_cast<const unsigned long long*>(cfg->seed_device);
     const long long mz = (long long)M * Z;
@@ -143,42 +132,37 @@ int layer_backward_impl(const umlh_enc_layer_t* cfg, const float* const* P, cons
     // h_out = norm2(s2), s2 = x1 + dropout3(f): ds2, df = dropout3(ds2)
     HC(umlh_enc_launch_layernorm_bwd_rows_fused(dh_out, 1, 0, nullptr, nullptr, saved + S.s2, g2, saved + S.mean2, saved + S.rstd2, M, Z,
                                                 ds2, df, cfg->p, sd + 3, sp, st));
-    RC(fork(0));
-    HC(umlh_enc_launch_ln_cols_partial(dh_out, saved + S.s2, saved + S.mean2, saved + S.rstd2, df, M, Z, d.chunk, p_g2, p_be2, p_b2, sw));
+    HC(umlh_enc_launch_ln_cols_partial(dh_out, saved + S.s2, saved + S.mean2, saved + S.rstd2, df, M, Z, d.chunk, p_g2, p_be2, p_b2, st));
     col(p_g2, dg2, Z); col(p_be2, dbe2, Z); col(p_b2, db2, Z);
     // f = hid w2^T + b2, hid = dropout2(relu(x1 w1^T + b1))
-    RC(dense_bwd_w(df, saved + S.hid, dw2, M, Z, F, scratch + X.pw2, red, sw));
+    RC(dense_bwd_w(df, saved + S.hid, dw2, M, Z, F, scratch + X.pw2, red, st));
     Epilogue e = epi_none();
     e.gate = saved + S.hid; e.on = 1;
     epi_dropout(e, cfg->p, sd + 2, sp);
     RC(dense_bwd_x(df, w2, dhid, M, Z, F, e, slabs, 0, &ns, st));
-    RC(fork(1));
-    RC(dense_bwd_w(dhid, saved + S.x1, dw1, M, F, Z, scratch + X.pw1, red, sw));
-    HC(umlh_enc_launch_colsum_partial(dhid, M, F, d.chunk, p_b1, sw));
+    RC(dense_bwd_w(dhid, saved + S.x1, dw1, M, F, Z, scratch + X.pw1, red, st));
+    HC(umlh_enc_launch_colsum_partial(dhid, M, F, d.chunk, p_b1, st));
     col(p_b1, db1, F);
     RC(dense_bwd_x(dhid, w1, nullptr, M, F, Z, epi_none(), slabs, 1, &ns, st));
     // x1 = norm1(s1), s1 = h_in + dropout1(a): dx1 = slabs + ds2 (residual fan-in), ds1, da = dropout1(ds1)
-    float* da = scratch + X.f;                         // (not df's buffer: the side stream may still be reading df)
+    float* da = scratch + X.f;
     HC(umlh_enc_launch_layernorm_bwd_rows_fused(slabs, ns, mz, ds2, dx1, saved + S.s1, g1, saved + S.mean1, saved + S.rstd1, M, Z,
                                                 ds1, da, cfg->p, sd + 1, sp, st));
-    RC(fork(2));
-    HC(umlh_enc_launch_ln_cols_partial(dx1, saved + S.s1, saved + S.mean1, saved + S.rstd1, da, M, Z, d.chunk, p_g1, p_be1, p_ob, sw));
+    HC(umlh_enc_launch_ln_cols_partial(dx1, saved + S.s1, saved + S.mean1, saved + S.rstd1, da, M, Z, d.chunk, p_g1, p_be1, p_ob, st));
     col(p_g1, dg1, Z); col(p_be1, dbe1, Z); col(p_ob, dob, Z);
     // a = att out_w^T + out_b
-    RC(dense_bwd_w(da, saved + S.att, dow, M, Z, Z, scratch + X.pwo, red, sw));
+    RC(dense_bwd_w(da, saved + S.att, dow, M, Z, Z, scratch + X.pwo, red, st));
     float* datt = ds2;                                 // ds2 is dead
     RC(dense_bwd_x(da, out_w, datt, M, Z, Z, epi_none(), slabs, 0, &ns, st));
     HC(umlh_enc_launch_attention_bwd(saved + S.qkv, lengths, saved + S.lse, datt, d.T, d.B, Z, d.H, cfg->p, sd, sp, dqkv, st));
     // qkv = h_in in_w^T + in_b
-    RC(fork(3));
-    RC(dense_bwd_w(dqkv, h_in, dinw, M, 3 * Z, Z, scratch + X.pwin, red, sw));
-    HC(umlh_enc_launch_colsum_partial(dqkv, M, 3 * Z, d.chunk, p_inb, sw));
+    RC(dense_bwd_w(dqkv, h_in, dinw, M, 3 * Z, Z, scratch + X.pwin, red, st));
+    HC(umlh_enc_launch_colsum_partial(dqkv, M, 3 * Z, d.chunk, p_inb, st));
     col(p_inb, dinb, 3 * Z);
     e = epi_none();
     e.add = ds1; e.on = 1;                             // residual fan-in at the layer input
     RC(dense_bwd_x(dqkv, in_w, dh_in, M, 3 * Z, Z, e, slabs, 0, &ns, st));
-    HC(umlh_enc_launch_multi_reduce(&red, sw));
-    if (side && (hipEventRecord(side->ev[4], side->s2) != hipSuccess || hipStreamWaitEvent(st, side->ev[4], 0) != hipSuccess)) return UMLH_E_HIP;   // join
+    HC(umlh_enc_launch_multi_reduce(&red, st));
     return UMLH_OK;
 }
 
@@ -238,7 +222,7 @@ int umlh_encoder_layer_forward(const umlh_enc_layer_t* cfg, const float* const* 
 
 int umlh_encoder_layer_backward(const umlh_enc_layer_t* cfg, const float* const* P, const float* h_in, const int64_t* lengths,
                                 const float* saved, const float* dh_out, float* scratch, float* const* G, float* dh_in, void* stream) {
-    return layer_backward_impl(cfg, P, h_in, lengths, saved, dh_out, scratch, G, dh_in, (hipStream_t)stream, nullptr);
+    return layer_backward_impl(cfg, P, h_in, lengths, saved, dh_out, scratch, G, dh_in, (hipStream_t)stream);
 }
 
 // the whole layer stack in one call: layer li reads (li ? h + (li-1)*M*Z : h0), writes h + li*M*Z and saved + li*saved_floats;
@@ -260,7 +244,7 @@ int umlh_encoder_stack_forward(const umlh_enc_layer_t* cfg, int32_t n_layers, co
 // of h0 is left in dh0
 static int stack_backward_impl(const umlh_enc_layer_t* cfg, int32_t n_layers, const float* const* P, const float* h0,
                                const int64_t* lengths, const float* saved, const float* h, const float* dh_out, float* scratch,
-                               float* const* G, float* dh, float* dh0, hipStream_t st, const SideCtx* side) {
+                               float* const* G, float* dh, float* dh0, hipStream_t st) {
     Dims d;
     if (!dims_ok(cfg, d) || n_layers < 1 || !P || !h0 || !saved || !h || !dh_out || !scratch || !G || !dh || !dh0) return UMLH_E_INVALID;
     const long long nsv = saved_layout(d).total, mz = d.M * d.Z;
@@ -269,7 +253,7 @@ static int stack_backward_impl(const umlh_enc_layer_t* cfg, int32_t n_layers, co
     for (int li = n_layers - 1; li >= 0; --li) {
         lc.seed = cfg->seed + 7919ull * (uint64_t)li;
         float* out = li == 0 ? dh0 : dh + (li & 1) * mz;
-        RC(layer_backward_impl(&lc, P + 12 * li, li ? h + (li - 1) * mz : h0, lengths, saved + li * nsv, g, scratch, G + 12 * li, out, st, side));
+        RC(layer_backward_impl(&lc, P + 12 * li, li ? h + (li - 1) * mz : h0, lengths, saved + li * nsv, g, scratch, G + 12 * li, out, st));
         g = out;
     }
     return UMLH_OK;
@@ -278,7 +262,7 @@ static int stack_backward_impl(const umlh_enc_layer_t* cfg, int32_t n_layers, co
 int umlh_encoder_stack_backward(const umlh_enc_layer_t* cfg, int32_t n_layers, const float* const* P, const float* h0,
                                 const int64_t* lengths, const float* saved, const float* h, const float* dh_out, float* scratch,
                                 float* const* G, float* dh, float* dh0, void* stream) {
-    return stack_backward_impl(cfg, n_layers, P, h0, lengths, saved, h, dh_out, scratch, G, dh, dh0, (hipStream_t)stream, nullptr);
+    return stack_backward_impl(cfg, n_layers, P, h0, lengths, saved, h, dh_out, scratch, G, dh, dh0, (hipStream_t)stream);
 }
 
 // ---- encoder plan: the stack on fixed buffers, replayed from HIP graphs ----
@@ -290,8 +274,6 @@ struct umlh_enc_plan_s {
     float* ws;
     long long o_h0, o_lens, o_seed, o_hs, o_saved, o_scratch, o_dhout, o_dhtmp, o_dh0, o_grads, total;
     hipStream_t cap;
-    SideCtx side;                // second stream + fork/join events of the backward
-    bool has_side;
     hipGraphExec_t exec[2];
     int calls[2];
 };
@@ -338,9 +320,6 @@ int umlh_encoder_plan_create(const umlh_enc_layer_t* cfg, int32_t n_layers, cons
         delete[] p->P; delete[] p->G; delete p;
         return UMLH_E_HIP;
     }
-    p->has_side = hipStreamCreateWithFlags(&p->side.s2, hipStreamNonBlocking) == hipSuccess;
-    for (int i = 0; i < 5 && p->has_side; ++i)
-        if (hipEventCreateWithFlags(&p->side.ev[i], hipEventDisableTiming) != hipSuccess) p->has_side = false;   // (falls back to one stream)
     *out = p;
     return UMLH_OK;
 }
@@ -358,16 +337,13 @@ static int plan_enqueue(umlh_enc_plan_t p, int dir, hipStream_t st) {
     float* w = p->ws;
     const int64_t* lens = p->has_lengths ? reinterpret_cast<const int64_t*>(w + p->o_lens) : nullptr;
     if (dir == 0) return umlh_encoder_stack_forward(&p->cfg, p->n_layers, p->P, w + p->o_h0, lens, w + p->o_saved, w + p->o_scratch, w + p->o_hs, st);
-    // Forking the weight-gradient work onto the side stream is OFF by default: measured on MI355X / ROCm 7.2 the forked graph
-    // is slower than the single chain (3.15 vs 2.90 ms per step at z = 40; its launch also costs ~1 ms more host time).
-    static const bool no_fork = [] { const char* e = getenv("UMLH_ENC_FORK"); return !(e && atoi(e) == 1); }();
     return stack_backward_impl(&p->cfg, p->n_layers, p->P, w + p->o_h0, lens, w + p->o_saved, w + p->o_hs, w + p->o_dhout,
-                               w + p->o_scratch, p->G, w + p->o_dhtmp, w + p->o_dh0, st, (p->has_side && !no_fork) ? &p->side : nullptr);
+                               w + p->o_scratch, p->G, w + p->o_dhtmp, w + p->o_dh0, st);
 }
 
 // call 0: plain launches (also sets the kernels' attributes, which a capture cannot); call 1: capture + instantiate; then replay
 static int plan_run(umlh_enc_plan_t p, int dir, hipStream_t st) {
-    static const bool no_graph = [] { const char* e = getenv("UMLH_ENC_GRAPH"); return e && atoi(e) == 0; }();
+    static const bool no_graph = env_int("UMLH_ENC_GRAPH", 1) == 0;
     const int call = p->calls[dir]++;
     if (call == 0 || no_graph) return plan_enqueue(p, dir, st);
     if (!p->exec[dir]) {
@@ -399,7 +375,6 @@ void umlh_encoder_plan_destroy(umlh_enc_plan_t p) {
     if (!p) return;
     for (int i = 0; i < 2; ++i) if (p->exec[i]) hipGraphExecDestroy(p->exec[i]);
     hipStreamDestroy(p->cap);
-    if (p->has_side) { for (int i = 0; i < 5; ++i) hipEventDestroy(p->side.ev[i]); hipStreamDestroy(p->side.s2); }
     delete[] p->P; delete[] p->G;
     delete p;
 }

@@ -15,6 +15,7 @@
 // given `splits`.  knn is bitwise independent of `splits` as well: column chunks start on 256-column tile boundaries,
 // every score is the same fma chain wherever it is computed, and the kept lists are exact top-k under a strict order.
 #include "umlh_common.h"
+#include "umlh_launch.h"
 #include <climits>
 
 namespace {

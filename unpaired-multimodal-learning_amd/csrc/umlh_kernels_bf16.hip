@@ -7,8 +7,9 @@
 //
 //   to_bf16        fp32 -> bf16 shadow copies (head weight each step, feature tables once)
 //   fwd_ce_bf16    fused  X W^T * scale -> softmax-CE -> dZ^T (bf16), loss / top-1 / dscale
-//   dw_bf16        dW = dZ^T F with the k-strided operand read through ds_read_b64_tr_b16
+//   dw_bf16_dma    dW = dZ^T F, both operands by LDS-DMA, the k-strided one read through ds_read_b64_tr_b16
 #include "umlh_common.h"
+#include "umlh_launch.h"
 #include <type_traits>
 #include <atomic>
 #include <cstring>
@@ -888,22 +889,17 @@ __global__ __launch_bounds__(512) void fwd_ce_bf16_q(FwdArgsB a) {
 
 // --------------------------------------------------------------------------- //
 // dW[m][n] = sum_r dZ^T[m][r] * F[r][n]   (bf16 operands, fp32 split-K slabs)
-// 128x128 tile, 4 waves (2x2) of 64x64.  A rows are k-contiguous (ds_read_b128);
+// 128x128 tile, 8 waves (2x4) of 64x32.  A rows are k-contiguous (ds_read_b128);
 // the feature rows F are k-major in memory, so the B fragment (8 consecutive k for one
 // column) comes from the hardware transposing read ds_read_b64_tr_b16.
 // --------------------------------------------------------------------------- //
 constexpr int DBM = 128, DBN = 128;
-constexpr int DKT = 64;     // reduction rows (dZ^T columns) per chunk = one column chunk of dZ^T
-constexpr int RSA = 72;     // shorts per LDS row of the dZ^T tile: 128 B data + 16 B pad (9 x 16 B: conflict-free b128)
-constexpr int RSF = 160;    // shorts per LDS row of the F tile: 256 B data + 64 B pad (4 k-rows -> 4 bank quarters)
-
-constexpr int DNS = 4;      // register stages: 3 chunks (96 KiB per CU) in flight while one is consumed
+constexpr int DKT = 64;     // reduction rows (dZ^T columns) per column chunk of dZ^T
+constexpr int DNS = 4;      // a split's k_chunk is a multiple of DKT * DNS = 256 rows (two LDS-DMA chunks)
 constexpr int DIDS = 4096;  // max reduction rows per workgroup (row ids staged in LDS)
 constexpr int DMASK = (int)0x80000000;
 
-// 512 threads = 8 waves (2 along M x 4 along N, 64x32 outputs each): two waves per SIMD, so one
-// wave's address arithmetic / LDS traffic overlaps the other's MFMAs (with 4 waves per CU every
-// phase of a chunk was serialised: 2.9k VALU instructions per wave and 22 us measured).
+// 512 threads = 8 waves (2 along M x 4 along N, 64x32 outputs each): two waves per SIMD.
 // GATED (the single-launch forward + dW below): the dZ^T loads wait until the forward blocks that write this split's columns
 // have published their granules; everything that does not depend on dZ^T (row ids, the first feature chunks) is issued first.
 // device-coherent (sc1) 16-byte load through a raw buffer descriptor: reads what another XCD's workgroup wrote through to memory
@@ -916,262 +912,9 @@ __device__ __forceinline__ u32x4 load_coherent_b128(__amdgpu_buffer_rsrc_t rsrc,
 struct DwGate { StepCtl ctl; int fwd_base, self_base;   // task ids of forward block 0 / dW block 0 of this launch
                 int ts, total_cols;
                 unsigned long long* timeline; };          // UMLH_DBG_STEP=1: [task][4] s_memrealtime stamps (100 MHz): start, gate open, end
-constexpr int DW_LDS_BYTES = 2 * DBM * RSA * 2 + 2 * DKT * RSF * 2 + DIDS * 4;   // two A tiles, two F tiles, the split's row ids
-
-// Returns TW_OK when the tile is written; GATED only: TW_ABORT (a wait gave up: nothing stored) or the id of a forward task
-// this workgroup has TAKEN while waiting (nobody held it): the caller runs it and calls again (nothing was stored yet).
-template <int AM, int OM, bool GATED>
-__device__ __forceinline__ int dw_bf16_body(const DwArgsB& g, const int vbid, const DwGate& gate, unsigned char* lds, int* sh_rc) {
-    // two LDS buffers: chunk c+1 is written while chunk c is consumed -> ONE barrier per chunk
-    u16 (*At)[DBM * RSA] = reinterpret_cast<u16 (*)[DBM * RSA]>(lds);
-    u16 (*Ft)[DKT * RSF] = reinterpret_cast<u16 (*)[DKT * RSF]>(lds + 2 * DBM * RSA * 2);
-    int* ids = reinterpret_cast<int*>(lds + 2 * DBM * RSA * 2 + 2 * DKT * RSF * 2);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 2, wn = wave & 3;
-    const int h = lane >> 5, l31 = lane & 31;
-    const int g16 = lane >> 4, q4 = (lane & 15) >> 2, p4 = lane & 3;
-    // XCD-aware decode of the 1-D grid: workgroups b and b+8 share an XCD (round-robin dispatch),
-    // so split z = b % nsplit keeps every tile of one K-split -- which all re-read the same dZ^T
-    // columns and feature rows -- on ONE XCD's L2 (speed only; any placement is correct).
-    const int nx = (g.N + DBN - 1) / DBN;
-    const int bid = vbid;
-    const int z = bid % g.nsplit, t = bid / g.nsplit;
-    const int m0 = (t / nx) * DBM, n0 = (t % nx) * DBN;
-    // modality-aligned split-K: slabs [0, nsplit1) cover the image rows [0, k_switch), the rest the text
-    // rows [k_switch, K) -- their sums stay separable (per-modality gradient diagnostics)
-    const int kb = z < g.nsplit1 ? z * g.k_chunk : g.k_switch + (z - g.nsplit1) * g.k_chunk;    // multiple of DKT
-    const int ke = min(z < g.nsplit1 ? g.k_switch : g.K, kb + g.k_chunk);
-    const int nchunks = g.k_chunk / DKT;                // multiple of DNS
-
-    f32x16 acc[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[i][e] = 0.f;
-#define DSTAMP(i) do { if (g.stamps && lane == 0) g.stamps[((size_t)vbid * 8 + wave) * 8 + (i)] = __builtin_readcyclecounter(); } while (0)
-    DSTAMP(0);
-    if (GATED && gate.timeline && tid == 0) gate.timeline[(size_t)(gate.self_base + vbid) * 4 + 0] = __builtin_amdgcn_s_memrealtime();
-
-    struct Stage { u32x4 a[2]; u32x4 f[2]; };
-    Stage st[DNS];
-    // per-thread invariants of the two A pieces and two F pieces it stages per chunk
-    //   A piece p (0..1023): tile row p>>3, 16-B column p&7;   F piece p: chunk row p>>4, 16-B column p&15
-    const int mclamp = g.M - 1 - m0;                    // rows >= M: garbage that is never stored
-    const u16* a_thr[2];
-    int a_col[2], f_row[2], f_col[2];
-    bool f_colok[2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        int p = tid + 512 * q;
-        a_col[q] = 8 * (p & 7);
-        if (AM == 0) a_thr[q] = g.A + ((size_t)m0 + min(p >> 3, mclamp)) * 64 + a_col[q];
-        else a_thr[q] = g.A + (size_t)g.a_rows[m0 + min(p >> 3, mclamp)] * g.lda + a_col[q];
-        f_row[q] = p >> 4;
-        const int col = min(n0 + 8 * (p & 15), g.N - 8);
-        f_col[q] = (col >> 6) * g.bcs + (col & 63);     // row-major rows: bcs = 64 -> col
-        f_colok[q] = n0 + 8 * (p & 15) < g.N;
-    }
-    // GATED: dZ^T comes through a buffer descriptor with device-coherent loads (AM == 0 only)
-    __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<u16*>(g.A), 0, GATED ? (int)(((size_t)(g.K + 63) / 64) * g.lda * 128) : 0, 0x00020000);
-    auto a_load = [&](int q, int k0, size_t achunk) -> u32x4 {
-        const bool on = k0 + a_col[q] < ke && !UMLH_ABL(g.dbg & 1);
-        if (GATED) {
-            const unsigned off = (unsigned)((a_thr[q] - g.A + achunk) * 2);
-            return load_coherent_b128(a_rsrc, on ? off : 0xfffffff0u);
-        }
-        const u16* ap = on ? a_thr[q] + achunk : g.zeros;
-        return *reinterpret_cast<const u32x4*>(ap);
-    };
-    // Branch-free loads: masked pieces read a zero page (a select on the loaded value would make the
-    // compiler wait for the load right here and serialise the pipeline).
-    auto gloadA = [&](Stage& sg, int c) {
-        const int k0 = kb + c * DKT;
-        const size_t achunk = AM == 0 ? (size_t)(k0 >> 6) * g.lda * 64 : (size_t)k0;
-#pragma unroll
-        for (int q = 0; q < 2; ++q) sg.a[q] = a_load(q, k0, achunk);
-    };
-    auto gloadF = [&](Stage& sg, int c) {
-        const int k0 = kb + c * DKT;                    // whole chunk lies in one modality (k_switch % 64 == 0)
-        const bool seg2 = k0 >= g.k_switch;
-        const u16* fb = seg2 ? g.B2 : g.B;
-        const int ld = seg2 ? g.ldb2 : g.ldb;
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int rid = ids[c * DKT + f_row[q]];
-            const u16* fp = (rid != DMASK && f_colok[q] && !UMLH_ABL(g.dbg & 2)) ? fb + (size_t)rid * ld + f_col[q] : g.zeros;
-            sg.f[q] = *reinterpret_cast<const u32x4*>(fp);
-        }
-    };
-    auto gload = [&](Stage& sg, int c) { gloadA(sg, c); gloadF(sg, c); };
-    auto lstore = [&](const Stage& sg, int buf) {
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            int p = tid + 512 * q;
-            *reinterpret_cast<u32x4*>(At[buf] + (p >> 3) * RSA + 8 * (p & 7)) = sg.a[q];
-            *reinterpret_cast<u32x4*>(Ft[buf] + (p >> 4) * RSF + 8 * (p & 15)) = sg.f[q];
-        }
-    };
-    const int a_off = (wm * 64 + l31) * RSA + h * 8;
-    const int f_off = (8 * h + q4) * RSF + wn * 32 + (g16 & 1) * 16 + 4 * p4;
-    auto compute = [&](int buf) {
-        const u16* a_frag = At[buf] + a_off;
-        const u16* f_frag = Ft[buf] + f_off;
-#pragma unroll
-        for (int s = 0; s < DKT / 16; ++s) {
-            bf16x8 av[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) av[i] = *reinterpret_cast<const bf16x8*>(a_frag + i * 32 * RSA + s * 16);
-            // 16-lane group g16: column block (g16&1) of the 32-wide tile, k half h = g16>>1;
-            // lane 4q+p addresses row q, columns 4p..4p+3; it receives column (lane&15), rows 0..3.
-            const u16* base = f_frag + s * 16 * RSF;
-            s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base));
-            s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + 4 * RSF));
-            s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-            const bf16x8 bv = __builtin_bit_cast(bf16x8, v);
-#pragma unroll
-            for (int i = 0; i < 2; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[i], bv, acc[i], 0, 0, 0);
-        }
-    };
-
-    // row ids of this split -> LDS once (no dependent global loads inside the pipeline); DMASK marks a
-    // masked (padding / out-of-range) row.  The id-independent dZ^T loads of the first DNS chunks are
-    // issued first so their latency overlaps this round trip.
-    const int lastc = nchunks - 1;
-    if (!GATED) {
-#pragma unroll
-        for (int d = 0; d < DNS; ++d) gloadA(st[d], min(d, lastc));
-    }
-    for (int i = tid; i < g.k_chunk; i += 512) {
-        int k = kb + i;
-        bool seg2 = k >= g.k_switch;
-        int kl = seg2 ? k - g.k_switch : k;
-        int lim = seg2 ? g.k_valid2 : g.k_valid1;
-        const int64_t* ip = seg2 ? g.k_rows2 : g.k_rows;
-        bool valid = k < ke && kl < lim;
-        ids[i] = valid ? (int)ip[kl] : DMASK;
-    }
-    __syncthreads();
-    DSTAMP(1);
-#pragma unroll
-    for (int d = 0; d < DNS; ++d) gloadF(st[d], min(d, lastc));
-    if (GATED) {
-        // forward block b writes columns [b * ts, (b + 1) * ts) of dZ^T (image blocks first, text columns start at a multiple
-        // of ts); this split reads [kb, ke).  One sweep = all granules of the range in flight (tasks_wait, umlh_common.h).
-        if (wave == 0) {
-            const int b0 = kb / gate.ts, nb = (min(ke, gate.total_cols) - kb + gate.ts - 1) / gate.ts;
-            const int rc = nb > 0 ? tasks_wait(gate.ctl, gate.fwd_base + b0, nb, lane, 1u) : TW_OK;
-            if (lane == 0) *sh_rc = rc;
-        }
-        __syncthreads();
-        const int rc = *sh_rc;
-        __syncthreads();                                // (the word is rewritten by the next wait)
-        if (rc != TW_OK) return rc;
-        if (gate.timeline && tid == 0) gate.timeline[(size_t)(gate.self_base + vbid) * 4 + 1] = __builtin_amdgcn_s_memrealtime();
-#pragma unroll
-        for (int d = 0; d < DNS; ++d) gloadA(st[d], min(d, lastc));
-    }
-    lstore(st[0], 0);                                   // chunk 0 -> buffer 0
-    gload(st[0], min(DNS, lastc));
-    __syncthreads();
-    DSTAMP(2);
-    // iteration for chunk c (buffer c&1): stage chunk c+1 into the other buffer, refill its register
-    // stage with chunk c+1+DNS, run the MFMAs of chunk c, one barrier.  DNS is even, so (c+1)&1 and
-    // the stage index (c+1)%DNS are compile-time constants inside the unrolled body.
-    // Staging is interleaved with the MFMAs, one piece per k-step: {fragment reads, MFMA, ds_write of
-    // piece s of chunk c+1, MFMA, global load of piece s of chunk c+1+DNS}.  Issued as separate phases
-    // (all stores, all loads, then all MFMAs) the eight waves move in lockstep between barriers and the
-    // LDS-store transfer (13 cycles per ds_write_b128 per wave) is never hidden behind matrix work.
-    static_assert(DKT / 16 == 4, "one staging piece (a0, a1, f0, f1) per k-step");
-    auto store_piece = [&](const Stage& sg, int buf, int pc) {
-        const int q = pc & 1, pidx = tid + 512 * q;
-        if (pc < 2) *reinterpret_cast<u32x4*>(At[buf] + (pidx >> 3) * RSA + 8 * (pidx & 7)) = sg.a[q];
-        else        *reinterpret_cast<u32x4*>(Ft[buf] + (pidx >> 4) * RSF + 8 * (pidx & 15)) = sg.f[q];
-    };
-    auto load_piece = [&](Stage& sg, int c, int pc, const int (&rids)[2]) {
-        const int q = pc & 1;
-        const int k0 = kb + c * DKT;
-        if (pc < 2) {
-            const size_t achunk = AM == 0 ? (size_t)(k0 >> 6) * g.lda * 64 : (size_t)k0;
-            sg.a[q] = a_load(q, k0, achunk);
-        } else {
-            const bool seg2 = k0 >= g.k_switch;
-            const u16* fb = seg2 ? g.B2 : g.B;
-            const int ld = seg2 ? g.ldb2 : g.ldb;
-            const int rid = rids[q];
-            const u16* fp = (rid != DMASK && f_colok[q] && !UMLH_ABL(g.dbg & 2)) ? fb + (size_t)rid * ld + f_col[q] : g.zeros;
-            sg.f[q] = *reinterpret_cast<const u32x4*>(fp);
-        }
-    };
-    for (int c = 0; c < (UMLH_ABL(g.dbg & 4) ? 0 : nchunks); c += DNS) {      // dbg bit2: skip the main loop (fixed-cost probe)
-#pragma unroll
-        for (int d = 0; d < DNS; ++d) {
-            const int nd = (d + 1) % DNS;
-            const int buf = d & 1, nbuf = (d + 1) & 1;
-            const int cnext = min(c + d + 1 + DNS, lastc);            // (past the end: a harmless re-store of the last chunk)
-            const u16* a_frag = At[buf] + a_off;
-            const u16* f_frag = Ft[buf] + f_off;
-            const int rids[2] = {ids[cnext * DKT + f_row[0]], ids[cnext * DKT + f_row[1]]};
-            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);       // row ids of the chunk to fetch
-            // fragments are read one k-step ahead of their MFMAs (two register sets): only the first k-step of
-            // a chunk -- right after the barrier that publishes its buffer -- waits on LDS latency
-            bf16x8 av[2][2], bvv[2];
-            auto load_frag = [&](int ks, int slot) {
-#pragma unroll
-                for (int i = 0; i < 2; ++i) av[slot][i] = *reinterpret_cast<const bf16x8*>(a_frag + i * 32 * RSA + ks * 16);
-                const u16* base = f_frag + ks * 16 * RSF;
-                s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base));
-                s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + 4 * RSF));
-                s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                bvv[slot] = __builtin_bit_cast(bf16x8, v);
-            };
-            load_frag(0, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-#pragma unroll
-            for (int ks = 0; ks < DKT / 16; ++ks) {
-                const int cur = ks & 1;
-                if (ks + 1 < DKT / 16) load_frag(ks + 1, cur ^ 1);
-                acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[cur][0], bvv[cur], acc[0], 0, 0, 0);
-                store_piece(st[nd], nbuf, ks);
-                acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[cur][1], bvv[cur], acc[1], 0, 0, 0);
-                load_piece(st[nd], cnext, ks, rids);
-                if (ks + 1 < DKT / 16) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);   // next k-step's fragment reads
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
-                __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);   // ds_write of the staged piece
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
-                __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   // global load of the next piece
-            }
-            __syncthreads();
-        }
-        if (c < 3 * DNS) DSTAMP(3 + c / DNS);
-    }
-    DSTAMP(6);
-
-    const int n = n0 + wn * 32 + l31;
-    if (n < g.N) {
-        float* out = g.out + (size_t)z * g.slab_stride;
-        u16* o16 = static_cast<u16*>(g.out16);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                int m = m0 + wm * 64 + i * 32 + acc_row(e, h);
-                if (m >= g.M) continue;
-                if (OM == 0) store_out_f32(out + (size_t)m * g.ldo + n, acc[i][e], g.plain);
-                else {
-                    const u16 v = f2bf(acc[i][e]);
-                    if (OM == 1) o16[(size_t)m * g.ldo + n] = v;
-                    else o16[((size_t)(n >> 6) * g.ldo + m) * 64 + (n & 63)] = v;
-                }
-            }
-    }
-    DSTAMP(7);
-    if (GATED && gate.timeline && tid == 0) gate.timeline[(size_t)(gate.self_base + vbid) * 4 + 2] = __builtin_amdgcn_s_memrealtime();
-    return TW_OK;
-#undef DSTAMP
-}
 
 // --------------------------------------------------------------------------- //
-// Round 3: the same tile (128 x 128, 8 waves of 64 x 32, 64 reduction rows per chunk) with BOTH operands staged by LDS-DMA
+// The dW tile (128 x 128, 8 waves of 64 x 32) with BOTH operands staged by LDS-DMA; the register-staged tile of rounds 1-2 is gone
 // (global_load_lds_dwordx4: no VGPR staging, no ds_write -- the ds_write_b128 stream, 13 cycles per wave-instruction, was
 // 416 of the old loop's ~1270 cycles per chunk, on top of 384 cycles of fragment reads for 512 cycles of MFMA).
 //   * three LDS stages of (16 KB dZ^T tile + 16 KB feature tile); a chunk's 32 one-KiB pieces are issued two chunks ahead,
@@ -1183,8 +926,10 @@ __device__ __forceinline__ int dw_bf16_body(const DwArgsB& g, const int vbid, co
 //     [16 x 16 B]: chunk ch of row r at ch ^ (((r & 3) << 2) | ((r >> 2) & 3)) -- the transposing reads (ds_read_b64_tr_b16)
 //     of 4 rows x 32 columns per half-wave are conflict-free (guide T10, image (b))
 //   * masked pieces (rows past the split, padding rows, columns past N) read a zero page through their per-lane source
-// GATED: as dw_bf16_body -- row ids and the feature tiles of the first two chunks are issued before the wait for the forward
-// tiles, the dZ^T pieces after it, with device-coherent (sc1) DMA loads.
+// GATED: row ids and the feature tiles of the first two chunks are issued before the wait for the forward tiles, the dZ^T
+// pieces after it, with device-coherent (sc1) DMA loads.
+// Returns TW_OK when the tile is written; GATED only: TW_ABORT (a wait gave up: nothing stored) or the id of a forward task
+// this workgroup has TAKEN while waiting (nobody held it): the caller runs it and calls again (nothing was stored yet).
 // --------------------------------------------------------------------------- //
 constexpr int DST = 2;                                  // LDS stages
 constexpr int DKB = 128;                                // reduction rows per chunk: the per-chunk chain (barrier, DMA issue, first fragment
@@ -1404,18 +1149,10 @@ __global__ __launch_bounds__(512) void dw_bf16_dma(DwArgsB g) {
     (void)dw_bf16_body_dma<AM, OM, false>(g, (int)blockIdx.x, none, smem_dyn, nullptr);
 }
 
-template <int AM, int OM>
-__global__ __launch_bounds__(512) void dw_bf16(DwArgsB g) {
-    __shared__ __attribute__((aligned(16))) unsigned char dw_lds[DW_LDS_BYTES];
-    DwGate none;
-    none.ctl = StepCtl{nullptr, nullptr, nullptr, 0u}; none.fwd_base = none.self_base = 0; none.ts = 32; none.total_cols = 0; none.timeline = nullptr;
-    (void)dw_bf16_body<AM, OM, false>(g, (int)blockIdx.x, none, dw_lds, nullptr);
-}
-
 // --------------------------------------------------------------------------- //
 // The whole step of a linear bf16 head as ONE launch of persistent workgroups over CLAIMED TASKS (umlh_common.h, StepCtl):
 //   phase 0  forward tiles     [0, nfwd)                       fwd_ce_bf16_body, publishes after its write-through dZ^T stores
-//   phase 1  dW tiles          [nfwd, nfwd + ndw)              dw_bf16_body<GATED>: waits for the forward tiles of its K range
+//   phase 1  dW tiles          [nfwd, nfwd + ndw)              dw_bf16_body_dma<GATED>: waits for the forward tiles of its K range
 //   phase 2  update slices     [nfwd + ndw, .. + nupd)         two 256-thread sub-blocks of head_step_kernel's work each (same
 //            + finalize        the last task                   arithmetic, same order); wait for the dW tiles of their 128-class
 //                                                              tile rows; finalize waits for every forward tile
@@ -1425,14 +1162,6 @@ __global__ __launch_bounds__(512) void dw_bf16(DwArgsB g) {
 // is taken by the first workgroup that needs its result (tasks_wait), so no wait depends on dispatch order or residency.
 // Handed-off data (dZ^T, slabs, partials) is stored write-through and read with device-coherent loads.
 // --------------------------------------------------------------------------- //
-// the dW body of the one-launch step: the LDS-DMA tile (round 3); -DUMLH_STEP_DW_OLD builds the register-staged one for A/B runs
-#ifdef UMLH_STEP_DW_OLD
-#define UMLH_STEP_DW_BODY dw_bf16_body
-#define UMLH_STEP_DW_LDS DW_LDS_BYTES
-#else
-#define UMLH_STEP_DW_BODY dw_bf16_body_dma
-#define UMLH_STEP_DW_LDS DW_DMA_LDS_BYTES
-#endif
 struct StepShape { int nfwd, ndw, nupd, nfin;
                    int lazy;      // test switch (UMLH_STEP_LAZY=1): every 4th workgroup leaves its forward and dW home tasks alone,
                                   // as if it had not been dispatched yet -- whoever needs them takes them (tasks_wait)
@@ -1559,7 +1288,7 @@ __device__ __attribute__((noinline)) void step_cold(const StepArgs* kp, int firs
         const int t = sp == 1 ? s0 : (sp == 2 ? s1 : s2);
         int rc = TW_OK;
         if (t < b_dw) { step_fwd_task<CTW, WC>(p, t, smem); --sp; continue; }
-        else if (t < b_upd) rc = UMLH_STEP_DW_BODY<0, 0, true>(p.g, t - b_dw, p.gate, smem, sh_ctl);
+        else if (t < b_upd) rc = dw_bf16_body_dma<0, 0, true>(p.g, t - b_dw, p.gate, smem, sh_ctl);
         else if (t < b_fin) rc = step_update_task<CTW, WC>(p.hf, p.gate, p.sh, t - b_upd, sh_ctl);
         else rc = step_fin_task<CTW, WC>(p, t, smem, sh_ctl);
         if (rc == TW_OK) { task_publish(ctl, t); --sp; }
@@ -1605,7 +1334,7 @@ __global__ __launch_bounds__(512) void step_bf16(StepArgs p) {
 #pragma unroll 1
     for (int i = b + G; i < p.sh.nfwd && !lazy; i += G) step_cold<CTW, WC>(kp, i, -1, 1, smem_dyn, sh_ctl);
     if (sh_ctl[5]) {
-        const int rc = UMLH_STEP_DW_BODY<0, 0, true>(p.g, b, p.gate, smem_dyn, sh_ctl);   // the same dynamic LDS, laid out for dW
+        const int rc = dw_bf16_body_dma<0, 0, true>(p.g, b, p.gate, smem_dyn, sh_ctl);   // the same dynamic LDS, laid out for dW
         if (rc == TW_OK) task_publish(ctl, b_dw + b);
         else if (rc == TW_ABORT) __syncthreads();            // status is set: this task and what depends on it is skipped
         else step_cold<CTW, WC>(kp, rc, b_dw + b, 0, smem_dyn, sh_ctl);   // a forward tile nobody had taken: run it, then this tile from the start (nothing was stored)
@@ -1720,7 +1449,7 @@ int umlh_bf16_launch_transpose_shadow(const float* src, int R, int Cc, int ldd, 
 #define STEP_CASE(CT, W)                                                                                           \
     if (ctw == CT && wc == W) {                                                                                    \
         size_t sm = fwd_smem_bytes_b(CT, W, 1);                                                                    \
-        if (sm < (size_t)UMLH_STEP_DW_LDS) sm = UMLH_STEP_DW_LDS;                                                  \
+        if (sm < (size_t)DW_DMA_LDS_BYTES) sm = DW_DMA_LDS_BYTES;                                                  \
         static std::atomic<unsigned long long> attr_done{0};  /* bit d: done on device d (the attribute is per device) */ \
         if (!((attr_done.load(std::memory_order_acquire) >> (dev_ & 63)) & 1ULL)) {                                \
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&step_bf16<CT, W>),                   \
@@ -1754,10 +1483,9 @@ int umlh_bf16_launch_step(const FwdArgsB* a, int ctw, int wc, int nfwd, const Dw
     HeadFuse h;
     memset(&h, 0, sizeof(h));
     StepShape shp = {nfwd, ndw, 0, 0, lazy, 0, 0};
-    {   // forward tiles of a K range on the workgroups of "its" XCD (StepShape::fs; UMLH_STEP_XCD=0: tile b on workgroup b)
-        static const bool xcd_map = [] { const char* e = getenv("UMLH_STEP_XCD"); return !(e && atoi(e) == 0); }();
+    {   // forward tiles of a K range on the workgroups of "its" XCD (StepShape::fs; 0 = tile b on workgroup b where that does not apply)
         const int per = ts > 0 && g->k_chunk % ts == 0 ? g->k_chunk / ts : 0;
-        if (xcd_map && splits > 1 && per > 0 && nfwd == per * splits && g->k_switch == g->nsplit1 * g->k_chunk) { shp.fs = splits; shp.fper = per; }
+        if (splits > 1 && per > 0 && nfwd == per * splits && g->k_switch == g->nsplit1 * g->k_chunk) { shp.fs = splits; shp.fper = per; }
     }
     if (hf) {
         h = *hf;
@@ -1802,19 +1530,10 @@ int umlh_bf16_launch_dw(const DwArgsB* g, int splits, int am, int om, hipStream_
     dim3 grid(((g->N + DBN - 1) / DBN) * ((g->M + DBM - 1) / DBM) * splits);
     DwArgsB c = *g;
     c.plain = umlh_plain_stores();
-    // UMLH_BF16_DW=0: the register-staged tile of rounds 1-2 (A/B timing); default: the LDS-DMA tile
-    static const bool old_tile = [] { const char* e = getenv("UMLH_BF16_DW"); return e && atoi(e) == 0; }();
-    if (!old_tile) {
-        int dev_ = 0;
-        (void)hipGetDevice(&dev_);
-        DW_DMA_CASE(0, 0) DW_DMA_CASE(1, 1) DW_DMA_CASE(0, 2)
-        return (int)hipErrorInvalidValue;
-    }
-    if (am == 0 && om == 0) hipLaunchKernelGGL((dw_bf16<0, 0>), grid, dim3(512), 0, stream, c);
-    else if (am == 1 && om == 1) hipLaunchKernelGGL((dw_bf16<1, 1>), grid, dim3(512), 0, stream, c);
-    else if (am == 0 && om == 2) hipLaunchKernelGGL((dw_bf16<0, 2>), grid, dim3(512), 0, stream, c);
-    else return (int)hipErrorInvalidValue;
-    return (int)hipGetLastError();
+    int dev_ = 0;
+    (void)hipGetDevice(&dev_);
+    DW_DMA_CASE(0, 0) DW_DMA_CASE(1, 1) DW_DMA_CASE(0, 2)
+    return (int)hipErrorInvalidValue;
 }
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 // latency/HBM-bound row kernels -- one wave per token row, LDS only where rows are shared (attention);
 // nothing here is reshaped to reach MFMA.
 #include "umlh_common.h"
+#include "umlh_launch.h"
 #include <atomic>
 
 namespace {

@@ -13,6 +13,7 @@
 //   finalize       per-step scalars + the two learnable logit scales
 //   zero_shot      head.py:22-37
 #include "umlh_common.h"
+#include "umlh_launch.h"
 #include <cstdlib>
 #include <atomic>
 
@@ -1762,14 +1763,14 @@ int umlh_f32_launch_fwd(const FwdArgs* a, int ctw, int wc, int grid, hipStream_t
         if (a->seg[s].rows > 0) fast = fast && a->seg[s].ld % 4 == 0 && aligned16(a->seg[s].feats);
     // MODE 2 (W streamed from the fragment-major shadow): the caller keeps the shadow current (umlh_launch_w_shadow32 /
     // the update kernel) and passes it in a->Ws; UMLH_F32_FWD=1 keeps the LDS-staged kernel for A/B timing
-    static const bool no_stream = [] { const char* e = getenv("UMLH_F32_FWD"); return e && atoi(e) == 1; }();
+    static const bool no_stream = env_int("UMLH_F32_FWD", 0) == 1;
     const int mode = !fast ? 0 : ((a->Ws != nullptr && a->K % (2 * KT) == 0 && !no_stream) ? (a->x3 ? 3 : 2) : 1);
     FWD_CASE(1, 1) FWD_CASE(1, 2) FWD_CASE(1, 4) FWD_CASE(1, 8) FWD_CASE(2, 8) FWD_CASE(4, 8)
     return (int)hipErrorInvalidValue;
 }
 
 static bool dw_f32_applies(const GemmArgs* g, int ta, int tb) {
-    static const bool off = [] { const char* e = getenv("UMLH_F32_DW"); return e && atoi(e) == 0; }();   // timing comparisons
+    static const bool off = env_int("UMLH_F32_DW", 1) == 0;   // timing comparisons
     if (off || ta != 0 || tb != 1 || g->a_rows || g->epi.on) return false;
     if ((long long)g->M * g->N < 8LL * 128 * 128 || g->N < 4 || g->N % 4 || g->lda < 4) return false;
     if (g->k_chunk > DWKIDS) return false;
@@ -1801,7 +1802,7 @@ int umlh_f32_launch_gemm(const GemmArgs* g, int ta, int tb, int splits, hipStrea
     }
     // 64x64 tiles when the 128x128 grid would leave most of the 256 CUs with a single 4-wave workgroup
     long long wg128 = (long long)((g->N + 127) / 128) * ((g->M + 127) / 128) * splits;
-    static const int tm_env = [] { const char* e = getenv("UMLH_F32_TM"); return e ? atoi(e) : 0; }();   // tile override for tuning runs
+    static const int tm_env = env_int("UMLH_F32_TM", 0);   // tile override for tuning runs
     const int tm = (tm_env == 1 || tm_env == 2) ? tm_env : (wg128 < 768 ? 1 : 2);
     const int t = 64 * tm;
     dim3 grid((g->N + t - 1) / t, (g->M + t - 1) / t, splits);
@@ -1821,9 +1822,8 @@ int umlh_f32_launch_gemm_enc(const GemmArgs* g, int ta, int tb, int splits, hipS
     {
         const char* e = getenv("UMLH_DBG_GEMM_STAMPS");
         static int last_sel = -2;
-        const char* sel = getenv("UMLH_DBG_GEMM_CALL");            // index of the gemm_enc launch to stamp
         static int call = 0;
-        unsigned long long* ptr = (e && sel && atoi(sel) == call) ? (unsigned long long*)strtoull(e, nullptr, 0) : nullptr;
+        unsigned long long* ptr = (e && env_int("UMLH_DBG_GEMM_CALL", -1) == call)   /* index of the gemm_enc launch to stamp */ ? (unsigned long long*)strtoull(e, nullptr, 0) : nullptr;
         (void)last_sel;
         ++call;
         hipMemcpyToSymbolAsync(HIP_SYMBOL(g_gemm_stamps), &ptr, sizeof(ptr), 0, hipMemcpyHostToDevice, stream);

@@ -22,6 +22,7 @@
 // All workgroups of a launch must be co-resident (spin waits): the host launches at most one workgroup per CU and
 // chains micro launches of one process on one device; every spin is bounded and reports through a status word.
 #include "umlh_common.h"
+#include "umlh_launch.h"
 #include <atomic>
 #include "umlh_micro.h"
 #include <type_traits>

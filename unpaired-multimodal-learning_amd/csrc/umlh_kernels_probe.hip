@@ -22,6 +22,7 @@
 // `halt` is set every remaining launch returns at its first instruction.  Nothing uses a float atomic, a grid barrier or
 // a host read.
 #include "umlh_common.h"
+#include "umlh_launch.h"
 #include <cfloat>
 #include <cmath>
 

@@ -7,6 +7,7 @@
 #include <stdint.h>
 #include <string.h>
 #include "umlh_common.h"
+#include "umlh_launch.h"
 
 // row r = (b, t): recon[r][d] = bias[d] + sum_k z[r][k] W[d][k];  masked residual vs x[b][t+1].
 __global__ __launch_bounds__(128) void seq_mse_fwd_kernel(const float* __restrict__ z, const float* __restrict__ w,
@@ -116,7 +117,6 @@ __global__ __launch_bounds__(256) void seq_mse_scale_kernel(float* __restrict__ 
     if (i < n) dw[i] *= 2.f * grad_out[0] / loss_cnt[1];
 }
 
-extern "C" int umlh_f32_launch_gemm(const GemmArgs* g, int ta, int tb, int splits, hipStream_t stream);
 
 extern "C" {
 int umlh_seq_launch_fwd(const float* z, const float* w, const float* b, const float* x, const int64_t* lengths, int B, int T,

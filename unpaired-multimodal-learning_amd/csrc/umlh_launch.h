@@ -1,0 +1,124 @@
+// Internal launch interface: every extern "C" function that a .hip file defines for the host code (kernel launchers and their
+// *_config / *_bytes / *_tasks / *_supported helpers), declared exactly once.  Every file that defines one and every file that
+// calls one includes this header, so a prototype that drifts from its definition is a compile error (the names are
+// extern "C": a drifted prototype would still link).  Not part of the C ABI (include/umlh.h).
+#pragma once
+#include "umlh_common.h"
+#include "umlh_micro.h"
+
+extern "C" {
+// ---- umlh_kernels_f32.hip: fp32 head step, generic fp32 GEMMs, optimizer / finalize kernels ----
+int umlh_launch_w_shadow32(const float* w, float* dst, int C, int K, int cpad, hipStream_t stream);
+int umlh_f32_fwd_config(int C, int* ctw, int* wc);
+int umlh_f32_launch_fwd(const FwdArgs* a, int ctw, int wc, int grid, hipStream_t stream);
+int umlh_f32_launch_gemm(const GemmArgs* g, int ta, int tb, int splits, hipStream_t stream);
+int umlh_f32_launch_gemm_enc(const GemmArgs* g, int ta, int tb, int splits, hipStream_t stream);
+int umlh_launch_reduce_update(int mode, const float* slabs, int n_slabs, long long slab_stride, long long n, float* grad_out,
+                              float* p, float* m, float* v, const OptArgs* o, long long frozen_lo, long long frozen_hi,
+                              hipStream_t stream);
+int umlh_launch_multi_opt(int n, float* const* p, const float* const* g, float* const* m, float* const* v, const long long* cnt,
+                          const OptArgs* o, hipStream_t stream);
+int umlh_launch_head_step(const float* slabs, int n_slabs, long long slab_stride, int C, int K, float* p, float* m, float* v,
+                          const OptArgs* o, void* shadow, int cpad, const FinalizeArgs* f, float* grad_out, const DiagArgs* dg,
+                          float* shadow32, hipStream_t stream);
+int umlh_launch_feistel_perm(long long n, unsigned long long seed, long long* out, hipStream_t stream);
+int umlh_launch_finalize(const FinalizeArgs* f, hipStream_t stream);
+int umlh_launch_zero_shot(const float* feats, const int64_t* labels, long long n, int d, int C, float* w, hipStream_t stream);
+// ---- umlh_kernels_bf16.hip: bf16 head step ----
+int umlh_launch_to_bf16(const float* src, void* dst, long long n, hipStream_t stream);
+int umlh_launch_iota(long long* dst, long long n, hipStream_t stream);
+int umlh_launch_w_shadow(const float* w, void* dst, int C, int K, int cpad, hipStream_t stream);
+int umlh_bf16_fwd_ts(int wc, int stw);
+int umlh_bf16_launch_fwd_q(const FwdArgsB* a, int nq, int tiles, hipStream_t stream);
+int umlh_bf16_launch_fwd(const FwdArgsB* a, int ctw, int wc, int stw, int grid, hipStream_t stream);
+int umlh_bf16_launch_transpose_shadow(const float* src, int R, int Cc, int ldd, void* dst, int mode, hipStream_t stream);
+int umlh_bf16_step_tasks(int nfwd, int M, int N, int splits, long long n_head, int with_head);
+int umlh_bf16_launch_step(const FwdArgsB* a, int ctw, int wc, int nfwd, const DwArgsB* g, int splits, unsigned* claim,
+                          unsigned long long* done, unsigned* status, unsigned epoch, int ts, int total_cols,
+                          const HeadFuse* hf, unsigned long long* timeline, int cus, int lazy, hipStream_t stream);
+int umlh_bf16_launch_dw(const DwArgsB* g, int splits, int am, int om, hipStream_t stream);
+// ---- umlh_kernels_micro.hip: micro-step path ----
+int umlh_micro_chunking(int d, int* nch, int* cw);
+int umlh_micro_bf16_supported(int nch, int cw);
+int umlh_micro_launch(int nch, int cw, int bf16, const UmlhMicroHead* heads, int n_heads, int n_steps, int grid,
+                      hipStream_t st);
+// ---- umlh_p2p.hip: direct peer-to-peer all-reduce (its public entry points are in umlh.h) ----
+int umlh_p2p_launch(void* const* regions, int n_ranks, int rank, float* msg, long long n, long long n_max, unsigned epoch,
+                    hipStream_t st);
+int umlh_p2p_status_offset(long long n_max, int n_ranks, unsigned long long* off);
+// ---- umlh_kernels_seq.hip: sequence decoder MSE / InfoNCE ----
+int umlh_seq_launch_fwd(const float* z, const float* w, const float* b, const float* x, const int64_t* lengths, int B, int T,
+                        int Z, int D, float* recon, float* dres, float* row_partial, float* loss_cnt, hipStream_t st);
+int umlh_seq_launch_bwd(const float* z, const float* w, const float* dres, const float* loss_cnt, const float* grad_out, int B,
+                        int T, int Z, int D, float* dz, float* dw, float* db, int with_params, hipStream_t st);
+int umlh_seq_launch_l2norm(const float* x, int n, int D, float* y, float* norm, hipStream_t st);
+int umlh_seq_launch_nce_rows(float* dots, int n, float inv_temp, float* row_loss, float* loss, hipStream_t st);
+int umlh_seq_launch_l2norm_bwd(const float* dy, const float* y, const float* norm, const float* grad_out, float scale, int n,
+                               int D, float* dx, hipStream_t st);
+// ---- umlh_kernels_enc.hip: MultiBench encoder layers ----
+int umlh_enc_launch_bias_act(float* y, const float* b, long long M, int N, int relu, hipStream_t st);
+int umlh_enc_launch_relu_bwd(const float* y, float* dy, long long n, hipStream_t st);
+int umlh_enc_launch_dropout(float* x, long long n, float p, unsigned long long seed, hipStream_t st);
+int umlh_enc_launch_add_inplace(float* y, const float* x, long long n, hipStream_t st);
+int umlh_enc_launch_colsum(const float* x, int M, int N, float* out, hipStream_t st);
+int umlh_enc_launch_add_layernorm(const float* x, const float* r, const float* gamma, const float* beta, int M, int N,
+                                  float eps, float* s_out, float* y, float* mean, float* rstd, hipStream_t st);
+int umlh_enc_launch_layernorm_bwd(const float* dy, const float* s, const float* gamma, const float* mean, const float* rstd,
+                                  int M, int N, float* ds, float* dgamma, float* dbeta, hipStream_t st);
+int umlh_enc_launch_reduce_epilogue(const float* slabs, int ns, long long stride, long long total, int N, const Epilogue* e,
+                                    float* out, hipStream_t st);
+// out[m*ldo + n] (m < M, n < N) = sum of ns slabs (slab s at slabs + s*stride, same row stride ldo); columns [N, ldo) untouched
+int umlh_enc_launch_reduce_window(const float* slabs, int ns, long long stride, int M, int N, int ldo, float* out,
+                                  hipStream_t st);
+int umlh_enc_launch_add_layernorm_fused(const float* x, int ns, long long stride, const Epilogue* e, const float* gamma,
+                                        const float* beta, int M, int N, float eps, float* s_out, float* y, float* mean,
+                                        float* rstd, hipStream_t st);
+int umlh_enc_launch_layernorm_bwd_rows_fused(const float* dy, int ns, long long stride, const float* add, float* dy_out,
+                                             const float* s, const float* gamma, const float* mean, const float* rstd, int M,
+                                             int N, float* ds, float* dsd, float p, unsigned long long seed,
+                                             const unsigned long long* seed_ptr, hipStream_t st);
+int umlh_enc_launch_colsum_partial(const float* x, int M, int N, int chunk, float* part, hipStream_t st);
+int umlh_enc_launch_ln_cols_partial(const float* dy, const float* s, const float* mean, const float* rstd, const float* dsd,
+                                    int M, int N, int chunk, float* part_g, float* part_b, float* part_d, hipStream_t st);
+int umlh_enc_launch_multi_reduce(MultiReduceArgs* a, hipStream_t st);
+int umlh_enc_launch_set_u64(unsigned long long* dst, unsigned long long v, hipStream_t st);
+float umlh_enc_drop_inv_keep(float p);
+unsigned umlh_enc_drop_thresh(float p);
+int umlh_enc_launch_add_pos(float* x, const float* pos, int T, int B, int Z, hipStream_t st);
+int umlh_enc_launch_pos_grad(const float* dx, int T, int B, int Z, float* dpos, hipStream_t st);
+int umlh_enc_launch_gather_rows(const float* x, const int64_t* idx, int n, int Z, float* out, int scatter, hipStream_t st);
+int umlh_enc_launch_attention_fwd(const float* qkv, const int64_t* lengths, int T, int B, int Z, int H, float p,
+                                  unsigned long long seed, const unsigned long long* seed_ptr, float* ctx, float* lse,
+                                  hipStream_t st);
+int umlh_enc_launch_attention_bwd(const float* qkv, const int64_t* lengths, const float* lse, const float* dctx, int T, int B,
+                                  int Z, int H, float p, unsigned long long seed, const unsigned long long* seed_ptr,
+                                  float* dqkv, hipStream_t st);
+// ---- umlh_kernels_align.hip: alignment metrics ----
+int umlh_align_knn_splits(long long n, int splits);
+unsigned long long umlh_align_knn_bytes(long long n, int topk, int splits);
+unsigned long long umlh_align_mutual_bytes(long long n);
+unsigned long long umlh_align_cka_bytes(long long n, int da, int db, int splits);
+int umlh_align_launch_knn(const float* x, long long n, int d, int ldx, int topk, int splits, int* knn, float* scores,
+                          void* scratch, hipStream_t st);
+int umlh_align_launch_mutual(const int* ka, const int* kb, long long n, int topk, double* out, void* scratch, hipStream_t st);
+int umlh_align_launch_cka(const float* a, int lda, int da, const float* b, int ldb, int db, long long n, int splits,
+                          double* out4, void* scratch, hipStream_t st);
+// ---- umlh_kernels_probe.hip: linear probes ----
+unsigned long long umlh_probe_fit_bytes(long long n, int d, int max_iter);
+unsigned long long umlh_probe_stats_bytes(int d);
+int umlh_probe_launch_masked_mean(const float* z, int B, int T, int Z, long long ldb, long long ldt, const long long* lengths,
+                                  float* out, int ldo, hipStream_t st);
+int umlh_probe_launch_stats(const float* x, long long n, int d, int ldx, double* stats, void* scratch, hipStream_t st);
+int umlh_probe_launch_fit(const float* x, long long n, int d, int ldx, const int* y, const double* stats, int kind, double c,
+                          int max_iter, double gtol, double* coef, umlh_probe_record_t* rec, double* objectives, void* scratch,
+                          hipStream_t st);
+int umlh_probe_launch_score(const float* x, long long n, int d, int ldx, const double* stats, const double* coef, const int* y,
+                            long long* correct, float* decision, hipStream_t st);
+
+// ---- umlh_api.cpp, for umlh_encoder.cpp ----
+// out[M,N] (ldo == N) = epilogue(A B^T) with the operand layouts of umlh_gemm_f32.  `splits` K-slabs go to `slabs`
+// ([ns][M*N], ns returned in *ns_out).  defer != 0: the raw slabs (ns >= 1) are left for the consumer, `out` and `epi` unused;
+// else one slab applies `epi` in the GEMM, more launch the slab reduction with `epi`.
+int umlh_gemm_f32_epi(const float* A, const float* B, float* out, int M, int N, int K, int lda, int ldb, int ta, int tb,
+                      const Epilogue* epi, int splits, float* slabs, int defer, int* ns_out, hipStream_t stream);
+}

@@ -22,6 +22,7 @@
 // UNMEASURED ON A MULTI-GPU NODE: built and tested with two processes on ONE GPU (tests/test_dp_gpu.py); RCCL stays the default
 // transport, this one is attached explicitly (umlh_p2p_attach / HeadEngine.init_p2p / UMLH_DP_P2P=1 in bench.py).
 #include "umlh_common.h"
+#include "umlh_launch.h"
 #include <cstring>
 
 constexpr int P2P_W = 64;            // workgroups (= parts per slice)

@@ -95,7 +95,7 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
     """Cross-compile the HIP sources for gfx950 into umlh/libumlh.so (in-tree, so the
     binary travels with the repo snapshot to the GPU box)."""
     srcs = [os.path.join(_CSRC, s) for s in SOURCES]
-    deps = srcs + [os.path.join(_CSRC, h) for h in ("umlh_common.h", "umlh_micro.h", "umlh_enc.h")] + [os.path.join(_INCLUDE, "umlh.h")]
+    deps = srcs + [os.path.join(_CSRC, h) for h in os.listdir(_CSRC) if h.endswith(".h")] + [os.path.join(_INCLUDE, "umlh.h")]
     if not force and os.path.exists(_SO) and all(os.path.getmtime(_SO) >= os.path.getmtime(d) for d in deps):
         return _SO
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
