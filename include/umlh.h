@@ -150,7 +150,7 @@ typedef struct {
 #define UMLH_N_SCALARS    12
 
 const char* umlh_last_error(void);
-int  umlh_version(void);        /* ABI revision: 3 = round 2 (grouped / micro / data-parallel / encoder-plan / InfoNCE entry points); 4 = round 3 (umlh_step_status / umlh_step_launches, umlh_p2p_*); 5 = umlh_align_* (CKA, k-NN, mutual k-NN); 6 = umlh_masked_mean, umlh_probe_* (linear probes of MultiBench evaluate) */
+int  umlh_version(void);        /* ABI revision: 3 = round 2 (grouped / micro / data-parallel / encoder-plan / InfoNCE entry points); 4 = round 3 (umlh_step_status / umlh_step_launches, umlh_p2p_*); 5 = umlh_align_* (CKA, k-NN, mutual k-NN); 6 = umlh_masked_mean, umlh_probe_* (linear probes of MultiBench evaluate); 7 = umlh_align_cka_unbiased / _cka_rbf / _cknna / _list_stats */
 
 /* Bytes of workspace a handle with this config needs (0 on invalid config). */
 uint64_t umlh_workspace_bytes(const umlh_config_t* cfg);
@@ -501,6 +501,49 @@ int  umlh_align_mutual_knn(const int32_t* knn_a, const int32_t* knn_b, int64_t n
  * out4 = {hsic_kl / (sqrt(hsic_kk * hsic_ll) + 1e-6), hsic_kl, hsic_kk, hsic_ll} in double; no 1/(n-1)^2 factor. */
 int  umlh_align_cka(const float* a, int32_t lda, int32_t d_a, const float* b, int32_t ldb, int32_t d_b, int64_t n,
                     int32_t splits, double* out4, void* scratch, uint64_t scratch_bytes, void* stream);
+
+/* The other metrics of AlignmentMetrics, with a scratch query of their own (umlh_align_scratch_bytes keeps its values). */
+#define UMLH_ALIGN_CKA_UNBIASED 0
+#define UMLH_ALIGN_CKA_RBF      1
+#define UMLH_ALIGN_CKNNA        2
+#define UMLH_ALIGN_LIST_STATS   3
+
+/* Scratch bytes of the entry point `kind` (above) with these arguments: O(n*splits + tiles + d^2), no n^2 term.  The CKA
+ * kinds ignore topk, the list kinds ignore d_a, d_b and splits.  0 on invalid arguments (unknown kind, n < 1, n < 4 for the
+ * unbiased CKA, d < 1, splits < 0, topk outside 1..32 (CKNNA: 2..32) or topk >= n). */
+uint64_t umlh_align_ext_scratch_bytes(int32_t kind, int64_t n, int32_t d_a, int32_t d_b, int32_t topk, int32_t splits);
+/* AlignmentMetrics.unbiased_cka(a, b) = cka(kernel_metric='ip', unbiased=True) (metrics.py:96-125 with hsic_unbiased
+ * :230-249) in feature space.  hsic_unbiased of a linear kernel is invariant under a translation of the features, so the
+ * features are centred on load as in umlh_align_cka; with centred rows x_i, y_i and m = n:
+ * sum K~ . L~ = ||Ac^T Bc||_F^2 - sum_i |x_i|^2 |y_i|^2, (K~ 1)_i = x_i . (sum_j x_j) - |x_i|^2 (the column sums are those of
+ * the rounded centred values), 1^T K~ L~ 1 = (K~ 1) . (L~ 1).  out4 = {hsic_kl / (sqrt(hsic_kk * hsic_ll) + 1e-6), hsic_kl,
+ * hsic_kk, hsic_ll} in double.  n >= 4 (the m - 3 divisor). */
+int  umlh_align_cka_unbiased(const float* a, int32_t lda, int32_t d_a, const float* b, int32_t ldb, int32_t d_b, int64_t n,
+                             int32_t splits, double* out4, void* scratch, uint64_t scratch_bytes, void* stream);
+/* AlignmentMetrics.cka(a, b, kernel_metric='rbf', rbf_sigma=sigma, unbiased=...) (metrics.py:103-119): K_ij =
+ * exp(-|a_i - a_j|^2 / (2 sigma^2)), L likewise from b; the n x n pairs are streamed in 32 x 256 tiles (Gram tiles of the
+ * column-centred rows on the f32 MFMA, squared distances clamped at 0, full-accuracy fp32 exp; the diagonal is exactly 1 for
+ * the biased form and left out of the unbiased one) and reduced to sum K.L, K.K, L.L and the row sums K1, L1 in double.
+ * biased (hsic_biased :252-255): trace(K H L H) = sum K.L - (2/n) K1.L1 + (1^T K 1)(1^T L 1)/n^2; unbiased: :230-249, n >= 4.
+ * out4 as above.  sigma > 0 and finite. */
+int  umlh_align_cka_rbf(const float* a, int32_t lda, int32_t d_a, const float* b, int32_t ldb, int32_t d_b, int64_t n,
+                        double sigma, int32_t unbiased, int32_t splits, double* out4, void* scratch, uint64_t scratch_bytes,
+                        void* stream);
+/* AlignmentMetrics.cknna(a, b, topk, distance_agnostic=False, unbiased=True) (metrics.py:180-227) from the neighbour lists
+ * and scores of umlh_align_knn on a and on b (self excluded there: the reference's -inf diagonal).  With S(i) = knn_a(i) n
+ * knn_b(i), M_ij = K_ij [j in S(i)], P_ij = L_ij [j in S(i)]: sim_kl = hsic_unbiased(M, P) (:230-249; M and P are not
+ * symmetric: the first term is sum_ij M_ij P_ji), sim_kk with S = knn_a and M = P, sim_ll likewise on b.
+ * out4 = {sim_kl / (sqrt(sim_kk * sim_ll) + 1e-6), sim_kl, sim_kk, sim_ll} in double; a negative product under the root gives
+ * NaN as in the reference.  2 <= topk <= 32 ("CKNNA requires topk >= 2", :184-185), topk < n, n >= 4. */
+int  umlh_align_cknna(const int32_t* knn_a, const float* scores_a, const int32_t* knn_b, const float* scores_b, int64_t n,
+                      int32_t topk, double* out4, void* scratch, uint64_t scratch_bytes, void* stream);
+/* cycle_knn (metrics.py:39-51, :258-269), lcs_knn (:88-92, :288-308) and edit_distance_knn (:164-176) given both neighbour
+ * lists int32 [n, topk].  Per row: hit = i is among knn_a[knn_b[i, p], q]; the length of the longest common subsequence of
+ * knn_a[i, :] and knn_b[i, :]; their Levenshtein distance with unit costs.  rows: int32 [n, 3] = {hit, lcs, distance} or NULL.
+ * out3 = {mean hit, mean LCS length (not divided by topk, as the reference returns it), 1 - mean distance / topk} in double
+ * from integer sums.  1 <= topk <= 32, topk < n. */
+int  umlh_align_list_stats(const int32_t* knn_a, const int32_t* knn_b, int64_t n, int32_t topk, int32_t* rows, double* out3,
+                           void* scratch, uint64_t scratch_bytes, void* stream);
 
 /* ---- linear probes of the MultiBench evaluate() (MultiBench/train.py:31-91,93-240): masked mean pooling, StandardScaler
  * statistics, an L2-regularised BINARY logistic regression fitted on the device, and its score.  Features are row-major fp32

@@ -223,7 +223,7 @@ static inline void mark(umlh_handle_t h, int i, hipStream_t st) {
 }
 
 const char* umlh_last_error(void) { return g_err; }
-int umlh_version(void) { return 6; }   // 3: round 2 (grouped / micro / data-parallel / encoder-plan / InfoNCE entry points, umlh_enc_layer_t.seed_device, umlh_seq_mse_backward scratch); 4: round 3 (umlh_step_status / _launches, umlh_p2p_*); 5: umlh_align_*; 6: umlh_masked_mean, umlh_probe_*
+int umlh_version(void) { return 7; }   // 3: round 2 (grouped / micro / data-parallel / encoder-plan / InfoNCE entry points, umlh_enc_layer_t.seed_device, umlh_seq_mse_backward scratch); 4: round 3 (umlh_step_status / _launches, umlh_p2p_*); 5: umlh_align_*; 6: umlh_masked_mean, umlh_probe_*; 7: umlh_align_cka_unbiased / _cka_rbf / _cknna / _list_stats
 
 int umlh_freeze_proj_row(umlh_handle_t h, int32_t row) {
     if (!h) return fail(UMLH_E_INVALID, "umlh_freeze_proj_row: null handle");
@@ -714,6 +714,92 @@ int umlh_align_cka(const float* a, int32_t lda, int32_t d_a, const float* b, int
         return fail(UMLH_E_INVALID, "umlh_align_cka: scratch of %llu bytes, %llu needed", (unsigned long long)scratch_bytes,
                     (unsigned long long)need);
     HIPCHK(umlh_align_launch_cka(a, lda, d_a, b, ldb, d_b, n, splits, out4, scratch, (hipStream_t)stream), "umlh_align_cka");
+    return UMLH_OK;
+}
+
+// ---- the other alignment metrics (kernels: umlh_kernels_align_ext.hip); every check precedes the first HIP call ----
+static bool align_topk_ok(int64_t n, int32_t topk, int32_t lo) { return topk >= lo && topk <= 32 && topk < n && n <= ALIGN_MAX_ROWS; }
+
+uint64_t umlh_align_ext_scratch_bytes(int32_t kind, int64_t n, int32_t d_a, int32_t d_b, int32_t topk, int32_t splits) {
+    if (n < 1 || n > ALIGN_MAX_ROWS) return 0;
+    switch (kind) {
+    case UMLH_ALIGN_CKA_UNBIASED:
+        return (n < 4 || d_a < 1 || d_b < 1 || splits < 0) ? 0 : umlh_align_ext_cka_unbiased_bytes(n, d_a, d_b, splits);
+    case UMLH_ALIGN_CKA_RBF:
+        return (d_a < 1 || d_b < 1 || splits < 0) ? 0 : umlh_align_ext_rbf_bytes(n, d_a, d_b, splits);
+    case UMLH_ALIGN_CKNNA:
+        return (n < 4 || !align_topk_ok(n, topk, 2)) ? 0 : umlh_align_ext_cknna_bytes(n);
+    case UMLH_ALIGN_LIST_STATS:
+        return !align_topk_ok(n, topk, 1) ? 0 : umlh_align_ext_list_bytes(n);
+    }
+    return 0;
+}
+
+// the shared checks of the two feature-space CKA forms; 0 = fine
+static int check_cka_ext(const char* who, const float* a, int32_t lda, int32_t d_a, const float* b, int32_t ldb, int32_t d_b, int64_t n,
+                         int32_t unbiased, int32_t splits, const double* out4, const void* scratch) {
+    if (!a || !b || !out4 || !scratch) return fail(UMLH_E_INVALID, "%s: null pointer (a, b, out4 and scratch are required)", who);
+    if (d_a < 1 || d_b < 1 || lda < d_a || ldb < d_b)
+        return fail(UMLH_E_INVALID, "%s: d_a=%d lda=%d d_b=%d ldb=%d (need 1 <= d <= ld)", who, d_a, lda, d_b, ldb);
+    if (n < 1 || n > ALIGN_MAX_ROWS) return fail(UMLH_E_INVALID, "%s: n=%lld rows (need 1 <= n <= 2^30)", who, (long long)n);
+    if (unbiased && n < 4) return fail(UMLH_E_INVALID, "%s: n=%lld rows, the unbiased HSIC divides by n - 3 (need n >= 4)", who, (long long)n);
+    if (splits < 0) return fail(UMLH_E_INVALID, "%s: splits=%d < 0", who, splits);
+    return UMLH_OK;
+}
+
+int umlh_align_cka_unbiased(const float* a, int32_t lda, int32_t d_a, const float* b, int32_t ldb, int32_t d_b, int64_t n,
+                            int32_t splits, double* out4, void* scratch, uint64_t scratch_bytes, void* stream) {
+    if (int e = check_cka_ext("umlh_align_cka_unbiased", a, lda, d_a, b, ldb, d_b, n, 1, splits, out4, scratch)) return e;
+    const uint64_t need = umlh_align_ext_cka_unbiased_bytes(n, d_a, d_b, splits);
+    if (scratch_bytes < need)
+        return fail(UMLH_E_INVALID, "umlh_align_cka_unbiased: scratch of %llu bytes, %llu needed", (unsigned long long)scratch_bytes,
+                    (unsigned long long)need);
+    HIPCHK(umlh_align_ext_launch_cka_unbiased(a, lda, d_a, b, ldb, d_b, n, splits, out4, scratch, (hipStream_t)stream),
+           "umlh_align_cka_unbiased");
+    return UMLH_OK;
+}
+
+int umlh_align_cka_rbf(const float* a, int32_t lda, int32_t d_a, const float* b, int32_t ldb, int32_t d_b, int64_t n, double sigma,
+                       int32_t unbiased, int32_t splits, double* out4, void* scratch, uint64_t scratch_bytes, void* stream) {
+    if (int e = check_cka_ext("umlh_align_cka_rbf", a, lda, d_a, b, ldb, d_b, n, unbiased, splits, out4, scratch)) return e;
+    if (!(sigma > 0.0) || !std::isfinite(sigma)) return fail(UMLH_E_INVALID, "umlh_align_cka_rbf: sigma=%g (need a finite sigma > 0)", sigma);
+    const uint64_t need = umlh_align_ext_rbf_bytes(n, d_a, d_b, splits);
+    if (scratch_bytes < need)
+        return fail(UMLH_E_INVALID, "umlh_align_cka_rbf: scratch of %llu bytes, %llu needed", (unsigned long long)scratch_bytes,
+                    (unsigned long long)need);
+    HIPCHK(umlh_align_ext_launch_rbf(a, lda, d_a, b, ldb, d_b, n, sigma, unbiased ? 1 : 0, splits, out4, scratch, (hipStream_t)stream),
+           "umlh_align_cka_rbf");
+    return UMLH_OK;
+}
+
+int umlh_align_cknna(const int32_t* knn_a, const float* scores_a, const int32_t* knn_b, const float* scores_b, int64_t n, int32_t topk,
+                     double* out4, void* scratch, uint64_t scratch_bytes, void* stream) {
+    if (!knn_a || !scores_a || !knn_b || !scores_b || !out4 || !scratch)
+        return fail(UMLH_E_INVALID, "umlh_align_cknna: null pointer (both lists, both scores, out4 and scratch are required)");
+    if (topk < 2) return fail(UMLH_E_INVALID, "umlh_align_cknna: CKNNA requires topk >= 2 (topk=%d)", topk);
+    if (topk > 32) return fail(UMLH_E_INVALID, "umlh_align_cknna: topk=%d outside 2..32", topk);
+    if (n <= topk || n < 4 || n > ALIGN_MAX_ROWS)
+        return fail(UMLH_E_INVALID, "umlh_align_cknna: n=%lld rows for topk=%d (need topk < n, 4 <= n <= 2^30)", (long long)n, topk);
+    const uint64_t need = umlh_align_ext_cknna_bytes(n);
+    if (scratch_bytes < need)
+        return fail(UMLH_E_INVALID, "umlh_align_cknna: scratch of %llu bytes, %llu needed", (unsigned long long)scratch_bytes,
+                    (unsigned long long)need);
+    HIPCHK(umlh_align_ext_launch_cknna(knn_a, scores_a, knn_b, scores_b, n, topk, out4, scratch, (hipStream_t)stream), "umlh_align_cknna");
+    return UMLH_OK;
+}
+
+int umlh_align_list_stats(const int32_t* knn_a, const int32_t* knn_b, int64_t n, int32_t topk, int32_t* rows, double* out3,
+                          void* scratch, uint64_t scratch_bytes, void* stream) {
+    if (!knn_a || !knn_b || !out3 || !scratch)
+        return fail(UMLH_E_INVALID, "umlh_align_list_stats: null pointer (knn_a, knn_b, out3 and scratch are required)");
+    if (topk < 1 || topk > 32) return fail(UMLH_E_INVALID, "umlh_align_list_stats: topk=%d outside 1..32", topk);
+    if (n <= topk || n > ALIGN_MAX_ROWS)
+        return fail(UMLH_E_INVALID, "umlh_align_list_stats: n=%lld rows for topk=%d (need topk < n <= 2^30)", (long long)n, topk);
+    const uint64_t need = umlh_align_ext_list_bytes(n);
+    if (scratch_bytes < need)
+        return fail(UMLH_E_INVALID, "umlh_align_list_stats: scratch of %llu bytes, %llu needed", (unsigned long long)scratch_bytes,
+                    (unsigned long long)need);
+    HIPCHK(umlh_align_ext_launch_list_stats(knn_a, knn_b, n, topk, rows, out3, scratch, (hipStream_t)stream), "umlh_align_list_stats");
     return UMLH_OK;
 }
 

@@ -422,7 +422,7 @@ static CkaPlan cka_plan(long long n, int da, int db, int splits) {
     if (splits <= 0 && r > nb / 4) r = nb / 4;   // auto: at least 128 rows per chunk
     if (r > CK_MAX_RCHUNKS) r = CK_MAX_RCHUNKS;
     p.rchunks = (int)(r < 1 ? 1 : (r > nb ? nb : r));
-    p.sum_chunks = (int)(n < CK_SUM_CHUNKS * 64 ? (n + 63) / 64 : CK_SUM_CHUNKS);
+    p.sum_chunks = umlh_align_cka_sum_chunks(n);
     p.colsum = 0;
     p.cross = align_up((long long)p.sum_chunks * (da + db) * 8);
     p.tile_sq = p.cross + align_up((long long)p.tiles * p.rchunks * 1024 * 8);
@@ -455,8 +455,22 @@ int umlh_align_launch_mutual(const int* ka, const int* kb, long long n, int topk
     return (int)hipGetLastError();
 }
 
-int umlh_align_launch_cka(const float* a, int lda, int da, const float* b, int ldb, int db, long long n, int splits, double* out4,
-                          void* scratch, hipStream_t st) {
+int umlh_align_cka_sum_chunks(long long n) { return (int)(n < CK_SUM_CHUNKS * 64 ? (n + 63) / 64 : CK_SUM_CHUNKS); }
+
+long long umlh_align_cka_tile_sq_offset(long long n, int da, int db, int splits) { return cka_plan(n, da, db, splits).tile_sq; }
+
+int umlh_align_launch_colsum(const float* a, int lda, int da, const float* b, int ldb, int db, long long n, double* partial,
+                             hipStream_t st) {
+    const int chunks = umlh_align_cka_sum_chunks(n);
+    hipLaunchKernelGGL(cka_colsum, dim3((unsigned)((da + db + 63) / 64), (unsigned)chunks), dim3(256), 0, st, a, lda, da, b, ldb, db,
+                       (int)n, chunks, partial);
+    return (int)hipGetLastError();
+}
+
+// The column sums (scratch + 0: [sum_chunks][da + db]) and the squared Frobenius sum of every 32x32 tile of Ac^T Bc, Ac^T Ac,
+// Bc^T Bc (scratch + tile_sq offset: ta*tb, then ta*ta, then tb*tb tiles); cka_final or the unbiased form finishes from them.
+int umlh_align_launch_cka_products(const float* a, int lda, int da, const float* b, int ldb, int db, long long n, int splits,
+                                   void* scratch, hipStream_t st) {
     const CkaPlan p = cka_plan(n, da, db, splits);
     CkaArgs g;
     g.a = a; g.b = b; g.lda = lda; g.ldb = ldb; g.da = da; g.db = db; g.ta = p.ta; g.tb = p.tb;
@@ -468,7 +482,15 @@ int umlh_align_launch_cka(const float* a, int lda, int da, const float* b, int l
                        db, (int)n, p.sum_chunks, (double*)g.colsum);
     hipLaunchKernelGGL(cka_cross, dim3((unsigned)p.tiles, (unsigned)p.rchunks), dim3(256), 0, st, g);
     hipLaunchKernelGGL(cka_tile_sq, dim3((unsigned)p.tiles), dim3(256), 0, st, g.cross, p.rchunks, g.tile_sq);
-    hipLaunchKernelGGL(cka_final, dim3(1), dim3(256), 0, st, g.tile_sq, p.ta, p.tb, out4);
+    return (int)hipGetLastError();
+}
+
+int umlh_align_launch_cka(const float* a, int lda, int da, const float* b, int ldb, int db, long long n, int splits, double* out4,
+                          void* scratch, hipStream_t st) {
+    const CkaPlan p = cka_plan(n, da, db, splits);
+    const int e = umlh_align_launch_cka_products(a, lda, da, b, ldb, db, n, splits, scratch, st);
+    if (e) return e;
+    hipLaunchKernelGGL(cka_final, dim3(1), dim3(256), 0, st, (const double*)((char*)scratch + p.tile_sq), p.ta, p.tb, out4);
     return (int)hipGetLastError();
 }
 

@@ -103,6 +103,25 @@ int umlh_align_launch_knn(const float* x, long long n, int d, int ldx, int topk,
 int umlh_align_launch_mutual(const int* ka, const int* kb, long long n, int topk, double* out, void* scratch, hipStream_t st);
 int umlh_align_launch_cka(const float* a, int lda, int da, const float* b, int ldb, int db, long long n, int splits,
                           double* out4, void* scratch, hipStream_t st);
+int umlh_align_cka_sum_chunks(long long n);
+long long umlh_align_cka_tile_sq_offset(long long n, int da, int db, int splits);
+int umlh_align_launch_colsum(const float* a, int lda, int da, const float* b, int ldb, int db, long long n, double* partial,
+                             hipStream_t st);
+int umlh_align_launch_cka_products(const float* a, int lda, int da, const float* b, int ldb, int db, long long n, int splits,
+                                   void* scratch, hipStream_t st);
+// ---- umlh_kernels_align_ext.hip: unbiased / RBF CKA, CKNNA, k-NN list statistics ----
+unsigned long long umlh_align_ext_cka_unbiased_bytes(long long n, int da, int db, int splits);
+unsigned long long umlh_align_ext_rbf_bytes(long long n, int da, int db, int splits);
+unsigned long long umlh_align_ext_cknna_bytes(long long n);
+unsigned long long umlh_align_ext_list_bytes(long long n);
+int umlh_align_ext_launch_cka_unbiased(const float* a, int lda, int da, const float* b, int ldb, int db, long long n, int splits,
+                                       double* out4, void* scratch, hipStream_t st);
+int umlh_align_ext_launch_rbf(const float* a, int lda, int da, const float* b, int ldb, int db, long long n, double sigma,
+                              int unbiased, int splits, double* out4, void* scratch, hipStream_t st);
+int umlh_align_ext_launch_cknna(const int* ka, const float* sa, const int* kb, const float* sb, long long n, int topk, double* out4,
+                                void* scratch, hipStream_t st);
+int umlh_align_ext_launch_list_stats(const int* ka, const int* kb, long long n, int topk, int* rows, double* out3, void* scratch,
+                                     hipStream_t st);
 // ---- umlh_kernels_probe.hip: linear probes ----
 unsigned long long umlh_probe_fit_bytes(long long n, int d, int max_iter);
 unsigned long long umlh_probe_stats_bytes(int d);

@@ -2,8 +2,9 @@
 on the HIP kernels of ``umlh.align``.
 
 Built: ``cka`` with ``kernel_metric='ip'`` and ``unbiased=False`` (what every caller uses), ``mutual_knn`` and
-``compute_nearest_neighbors``.  The other names of ``SUPPORTED_METRICS`` raise ``NotImplementedError``; unknown names
-raise ``ValueError`` as the reference does.  Like the reference's ``.item()``, ``measure`` returns Python floats.
+``compute_nearest_neighbors``.  The other names of ``SUPPORTED_METRICS`` raise ``NotImplementedError`` here (all but
+``svcca`` run as HIP kernels through ``umlh.align.measure``, which takes the same names and keyword arguments); unknown
+names raise ``ValueError`` as the reference does.  Like the reference's ``.item()``, ``measure`` returns Python floats.
 
 Neighbours are by raw inner product with self excluded; exact ties go to the smaller column index (the reference leaves
 that order to torch's sort).  Importing this module does not touch the GPU.
@@ -19,7 +20,8 @@ BUILT_METRICS = ("mutual_knn", "cka")
 
 def _not_built(what: str):
     raise NotImplementedError(f"{what} is not built here; supported: AlignmentMetrics.cka(kernel_metric='ip', unbiased=False), "
-                              "AlignmentMetrics.mutual_knn, compute_nearest_neighbors")
+                              "AlignmentMetrics.mutual_knn, compute_nearest_neighbors; the other metrics are in "
+                              "umlh.align.measure(metric, feats_A, feats_B, **kwargs)")
 
 
 class AlignmentMetrics:

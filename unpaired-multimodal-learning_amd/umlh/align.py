@@ -5,10 +5,16 @@
 (:96-119, :252-255).  Every call enqueues on ``torch.cuda.current_stream`` and returns device tensors without
 synchronising.  Inputs: fp32 CUDA tensors with unit column stride are used in place (the row stride is passed on);
 other float dtypes are upcast and CPU tensors copied to the current device.  There is no CPU compute path.
+
+The kernels of umlh_kernels_align_ext.hip add the rest of the reference's ``AlignmentMetrics``: ``unbiased_cka`` (:122-125
+with hsic_unbiased :230-249), ``rbf_cka`` (``cka(kernel_metric='rbf')``, biased and unbiased, :103-119), ``cknna`` (:180-227),
+``cycle_knn`` (:39-51), ``lcs_knn`` (:88-92) and ``edit_distance_knn`` (:164-176), and ``measure`` dispatches the reference's
+metric names and keyword arguments to all of them.  Not built: ``svcca`` and the ``distance_agnostic`` / biased CKNNA.
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import torch
 
@@ -123,3 +129,177 @@ def cka_terms(a: torch.Tensor, b: torch.Tensor, splits: int = 0) -> torch.Tensor
 def cka(a: torch.Tensor, b: torch.Tensor, splits: int = 0) -> torch.Tensor:
     """AlignmentMetrics.cka(a, b, kernel_metric='ip'): a 0-d float64 device tensor."""
     return cka_terms(a, b, splits)[0]
+
+
+# ---- unbiased / RBF CKA, CKNNA and the list statistics (umlh_kernels_align_ext.hip) ----
+KIND_CKA_UNBIASED, KIND_CKA_RBF, KIND_CKNNA, KIND_LIST_STATS = range(4)
+
+
+def _ext_scratch(lib, kind, n, d_a, d_b, topk, splits, dev):
+    nbytes = lib.umlh_align_ext_scratch_bytes(kind, n, d_a, d_b, topk, splits)
+    if nbytes == 0:
+        raise UmlhError(f"umlh_align_ext_scratch_bytes: invalid arguments kind={kind} n={n} d_a={d_a} d_b={d_b} topk={topk} "
+                        f"splits={splits}")
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes
+
+
+def _check_pair(a, b, what: str, splits: int, min_rows: int = 1) -> None:
+    if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor)) or a.ndim != 2 or b.ndim != 2 or a.shape[0] != b.shape[0]:
+        raise ValueError(f"{what}: features of shapes {tuple(getattr(a, 'shape', ()))} and {tuple(getattr(b, 'shape', ()))} "
+                         "(need 2-D with the same N)")
+    if splits < 0:
+        raise ValueError(f"{what}: splits={splits} < 0")
+    if a.shape[0] < min_rows:
+        raise ValueError(f"{what}: N={a.shape[0]} rows, the unbiased HSIC divides by N - 3 (need N >= {min_rows})")
+
+
+def unbiased_cka_terms(a: torch.Tensor, b: torch.Tensor, splits: int = 0) -> torch.Tensor:
+    """float64 device tensor [4] = {cka, hsic_kl, hsic_kk, hsic_ll} with the unbiased HSIC of the linear kernel."""
+    _check_pair(a, b, "unbiased_cka", splits, 4)
+    dev = _device()
+    xa, xb = _features(a, "unbiased_cka", dev), _features(b, "unbiased_cka", dev)
+    n = xa.shape[0]
+    lib = load_library()
+    scratch, nbytes = _ext_scratch(lib, KIND_CKA_UNBIASED, n, xa.shape[1], xb.shape[1], 0, splits, dev)
+    out = torch.empty(4, dtype=torch.float64, device=dev)
+    check(lib.umlh_align_cka_unbiased(xa.data_ptr(), xa.stride(0), xa.shape[1], xb.data_ptr(), xb.stride(0), xb.shape[1], n, splits,
+                                      out.data_ptr(), scratch.data_ptr(), nbytes, _stream(dev)), "umlh_align_cka_unbiased")
+    return out
+
+
+def unbiased_cka(a: torch.Tensor, b: torch.Tensor, splits: int = 0) -> torch.Tensor:
+    """AlignmentMetrics.unbiased_cka(a, b): a 0-d float64 device tensor."""
+    return unbiased_cka_terms(a, b, splits)[0]
+
+
+def rbf_cka_terms(a: torch.Tensor, b: torch.Tensor, sigma: float = 1.0, unbiased: bool = False, splits: int = 0) -> torch.Tensor:
+    """float64 device tensor [4] = {cka, hsic_kl, hsic_kk, hsic_ll} for K_ij = exp(-|a_i - a_j|^2 / (2 sigma^2))."""
+    _check_pair(a, b, "rbf_cka", splits, 4 if unbiased else 1)
+    sigma = float(sigma)
+    if not (sigma > 0.0 and math.isfinite(sigma)):
+        raise ValueError(f"rbf_cka: sigma={sigma} (need a finite sigma > 0)")
+    dev = _device()
+    xa, xb = _features(a, "rbf_cka", dev), _features(b, "rbf_cka", dev)
+    n = xa.shape[0]
+    lib = load_library()
+    scratch, nbytes = _ext_scratch(lib, KIND_CKA_RBF, n, xa.shape[1], xb.shape[1], 0, splits, dev)
+    out = torch.empty(4, dtype=torch.float64, device=dev)
+    check(lib.umlh_align_cka_rbf(xa.data_ptr(), xa.stride(0), xa.shape[1], xb.data_ptr(), xb.stride(0), xb.shape[1], n, sigma,
+                                 int(bool(unbiased)), splits, out.data_ptr(), scratch.data_ptr(), nbytes, _stream(dev)),
+          "umlh_align_cka_rbf")
+    return out
+
+
+def rbf_cka(a: torch.Tensor, b: torch.Tensor, sigma: float = 1.0, unbiased: bool = False, splits: int = 0) -> torch.Tensor:
+    """AlignmentMetrics.cka(a, b, kernel_metric='rbf', rbf_sigma=sigma, unbiased=unbiased): a 0-d float64 device tensor."""
+    return rbf_cka_terms(a, b, sigma, unbiased, splits)[0]
+
+
+def _check_cknna_topk(topk: int, n: int) -> None:
+    if topk < 2:
+        raise ValueError(f"CKNNA requires topk >= 2 (topk={topk})")
+    _check_topk(topk, n, "cknna")
+    if n < 4:
+        raise ValueError(f"cknna: N={n} rows, the unbiased HSIC divides by N - 3 (need N >= 4)")
+
+
+def cknna_terms(a: torch.Tensor, b: torch.Tensor, topk: int, splits: int = 0) -> torch.Tensor:
+    """float64 device tensor [4] = {cknna, sim_kl, sim_kk, sim_ll} (unbiased, not distance agnostic)."""
+    _check_pair(a, b, "cknna", splits)
+    topk = int(topk)
+    n = a.shape[0]
+    _check_cknna_topk(topk, n)
+    ka, sa = knn(a, topk, splits, return_scores=True)
+    kb, sb = knn(b, topk, splits, return_scores=True)
+    dev = ka.device
+    lib = load_library()
+    scratch, nbytes = _ext_scratch(lib, KIND_CKNNA, n, 1, 1, topk, 0, dev)
+    out = torch.empty(4, dtype=torch.float64, device=dev)
+    check(lib.umlh_align_cknna(ka.data_ptr(), sa.data_ptr(), kb.data_ptr(), sb.data_ptr(), n, topk, out.data_ptr(),
+                               scratch.data_ptr(), nbytes, _stream(dev)), "umlh_align_cknna")
+    return out
+
+
+def cknna(a: torch.Tensor, b: torch.Tensor, topk: int, splits: int = 0) -> torch.Tensor:
+    """AlignmentMetrics.cknna(a, b, topk): a 0-d float64 device tensor."""
+    return cknna_terms(a, b, topk, splits)[0]
+
+
+def list_stats(knn_a: torch.Tensor, knn_b: torch.Tensor, return_rows: bool = False):
+    """float64 device tensor [3] = {cycle_knn, lcs_knn, edit_distance_knn} of two int32 [N, k] neighbour lists (and the
+    per-row int32 [N, 3] = {hit, LCS length, Levenshtein distance} when ``return_rows``)."""
+    if not (isinstance(knn_a, torch.Tensor) and isinstance(knn_b, torch.Tensor)) or knn_a.shape != knn_b.shape or knn_a.ndim != 2:
+        raise ValueError(f"list_stats: neighbour lists of shapes {tuple(getattr(knn_a, 'shape', ()))} and "
+                         f"{tuple(getattr(knn_b, 'shape', ()))}")
+    n, topk = knn_a.shape
+    _check_topk(topk, n, "list_stats")
+    dev = _device()
+    ka = knn_a.to(device=dev, dtype=torch.int32).contiguous()
+    kb = knn_b.to(device=dev, dtype=torch.int32).contiguous()
+    lib = load_library()
+    scratch, nbytes = _ext_scratch(lib, KIND_LIST_STATS, n, 1, 1, topk, 0, dev)
+    out = torch.empty(3, dtype=torch.float64, device=dev)
+    rows = torch.empty((n, 3), dtype=torch.int32, device=dev) if return_rows else None
+    check(lib.umlh_align_list_stats(ka.data_ptr(), kb.data_ptr(), n, topk, rows.data_ptr() if rows is not None else None,
+                                    out.data_ptr(), scratch.data_ptr(), nbytes, _stream(dev)), "umlh_align_list_stats")
+    return (out, rows) if return_rows else out
+
+
+def _list_stat(a, b, topk, splits, which, what):
+    _check_pair(a, b, what, splits)
+    _check_topk(int(topk), a.shape[0], what)
+    return list_stats(knn(a, topk, splits), knn(b, topk, splits))[which]
+
+
+def cycle_knn(a: torch.Tensor, b: torch.Tensor, topk: int, splits: int = 0) -> torch.Tensor:
+    """AlignmentMetrics.cycle_knn(a, b, topk): the share of rows i found among knn_a[knn_b[i]]; a 0-d float64 device tensor."""
+    return _list_stat(a, b, topk, splits, 0, "cycle_knn")
+
+
+def lcs_knn(a: torch.Tensor, b: torch.Tensor, topk: int, splits: int = 0) -> torch.Tensor:
+    """AlignmentMetrics.lcs_knn(a, b, topk): the mean LCS length of the two neighbour lists (not divided by topk)."""
+    return _list_stat(a, b, topk, splits, 1, "lcs_knn")
+
+
+def edit_distance_knn(a: torch.Tensor, b: torch.Tensor, topk: int, splits: int = 0) -> torch.Tensor:
+    """AlignmentMetrics.edit_distance_knn(a, b, topk): 1 - mean Levenshtein distance of the two neighbour lists / topk."""
+    return _list_stat(a, b, topk, splits, 2, "edit_distance_knn")
+
+
+SUPPORTED_METRICS = ("cycle_knn", "mutual_knn", "lcs_knn", "cka", "unbiased_cka", "cknna", "svcca", "edit_distance_knn")
+
+
+def _cka_any(feats_A, feats_B, kernel_metric="ip", rbf_sigma=1.0, unbiased=False):
+    if kernel_metric == "ip":
+        return unbiased_cka(feats_A, feats_B) if unbiased else cka(feats_A, feats_B)
+    if kernel_metric == "rbf":
+        return rbf_cka(feats_A, feats_B, rbf_sigma, unbiased)
+    raise ValueError(f"Invalid kernel metric {kernel_metric}")
+
+
+def _cknna_any(feats_A, feats_B, topk=None, distance_agnostic=False, unbiased=True):
+    if distance_agnostic:
+        raise NotImplementedError("cknna(distance_agnostic=True) is not built: the reference itself raises there (it calls "
+                                  ".item() on an N x N tensor)")
+    if not unbiased:
+        raise NotImplementedError("cknna(unbiased=False) is not built: it needs a top-k that includes self and the dense "
+                                  "centred HSIC")
+    if topk is None:
+        raise ValueError("cknna: topk is required (1 < topk <= 32)")
+    return cknna(feats_A, feats_B, topk)
+
+
+def _svcca(*args, **kwargs):
+    raise NotImplementedError("svcca is not built: it is a randomised SVD followed by scikit-learn's CCA, neither of which "
+                              "has a HIP path here")
+
+
+def measure(metric: str, feats_A: torch.Tensor, feats_B: torch.Tensor, **kwargs) -> float:
+    """AlignmentMetrics.measure(metric, feats_A, feats_B, **kwargs) (metrics.py:28-35) with the reference's metric names and
+    keyword arguments (topk, kernel_metric, rbf_sigma, unbiased, distance_agnostic); a Python float like its ``.item()``."""
+    if metric not in SUPPORTED_METRICS:
+        raise ValueError(f"Unrecognized metric: {metric}")
+    fn = {"cycle_knn": cycle_knn, "mutual_knn": mutual_knn, "lcs_knn": lcs_knn, "edit_distance_knn": edit_distance_knn,
+          "cka": _cka_any, "unbiased_cka": lambda a, b, **kw: _cka_any(a, b, **{**kw, "unbiased": True}),
+          "cknna": _cknna_any, "svcca": _svcca}[metric]
+    return float(fn(feats_A, feats_B, **kwargs).item())
