@@ -150,7 +150,7 @@ typedef struct {
 #define UMLH_N_SCALARS    12
 
 const char* umlh_last_error(void);
-int  umlh_version(void);        /* ABI revision: 3 = round 2 (grouped / micro / data-parallel / encoder-plan / InfoNCE entry points); 4 = round 3 (umlh_step_status / umlh_step_launches, umlh_p2p_*); 5 = umlh_align_* (CKA, k-NN, mutual k-NN); 6 = umlh_masked_mean, umlh_probe_* (linear probes of MultiBench evaluate); 7 = umlh_align_cka_unbiased / _cka_rbf / _cknna / _list_stats */
+int  umlh_version(void);        /* ABI revision: 3 = round 2 (grouped / micro / data-parallel / encoder-plan / InfoNCE entry points); 4 = round 3 (umlh_step_status / umlh_step_launches, umlh_p2p_*); 5 = umlh_align_* (CKA, k-NN, mutual k-NN); 6 = umlh_masked_mean, umlh_probe_* (linear probes of MultiBench evaluate); 7 = umlh_align_cka_unbiased / _cka_rbf / _cknna / _list_stats; 8 = umlh_spectral_scratch_bytes, umlh_svdvals, umlh_effective_rank, umlh_effective_rank_seq */
 
 /* Bytes of workspace a handle with this config needs (0 on invalid config). */
 uint64_t umlh_workspace_bytes(const umlh_config_t* cfg);
@@ -594,6 +594,37 @@ int  umlh_probe_fit(const float* x, int64_t n, int32_t d, int32_t ldx, const int
  * decision > 0.  decision: NULL or n floats.  correct: NULL or one int64 = #{i : prediction_i == y_i} (y required then). */
 int  umlh_probe_score(const float* x, int64_t n, int32_t d, int32_t ldx, const double* stats, const double* coef,
                       const int32_t* y, int64_t* correct, float* decision, void* stream);
+
+/* ---- ABI v8: singular values and effective rank of fp32 feature matrices (MultiBench/utilis.py:27-36, the per-step
+ * diagnostic of MultiBench/train.py:386-389).  sigma(A) = sqrt(eig(A^T A)): the d x d Gram is accumulated in fp64 from the
+ * fp32 rows (their products are exact there), tridiagonalised by Householder reflections and its eigenvalues found by
+ * bisection on Sturm counts with a fixed iteration count, all on the device.  Only the min(rows, d) largest eigenvalues are
+ * used (an n x d matrix with n < d has n singular values; the other eigenvalues are rounding noise around zero), negative
+ * ones are clamped to 0 before the root.  effective rank = exp(-sum p log(p + eps)), p = sigma / sum sigma, in fp64 in a fixed
+ * order: zero valid rows give 1 (empty sums), an all-zero matrix gives NaN (0/0), as the reference's arithmetic does.
+ * Rows are split into chunks = min(ceil(n / 256), max(1, 128 / batch)) per matrix; each chunk writes a d x d fp64 slab
+ * and a second pass sums the slabs in chunk order: no float atomics, results are bitwise reproducible for given arguments.
+ * Envelope: 1 <= d <= 512, 1 <= batch <= 65535, n >= 1, batch * n < 2^31; a[m, r, c] is read at a[m*ld_batch + r*ld_row + c]
+ * with ld_row >= d and strides that do not make rows overlap.  Every argument check happens before any HIP call; `scratch`
+ * is caller device memory of umlh_spectral_scratch_bytes(batch, n, d) bytes; results are device doubles written on `stream`. */
+
+/* Scratch bytes: 8 d^2 (batch * chunks + batch) rounded up to 256-byte regions: O(chunks d^2 + batch d^2), no n x d term
+ * (n enters through the chunk count only).  0 on invalid arguments.  The sequence form uses (1, b * t_len, d). */
+uint64_t umlh_spectral_scratch_bytes(int32_t batch, int64_t n, int32_t d);
+/* torch.linalg.svdvals(a) for a [batch, n, d]: sv[batch, min(n, d)], descending. */
+int  umlh_svdvals(const float* a, int32_t batch, int64_t n, int32_t d, int64_t ld_batch, int64_t ld_row, double* sv, void* scratch,
+                  uint64_t scratch_bytes, void* stream);
+/* compute_effective_rank(a, eps) (utilis.py:27-36): erank[batch]; sv_or_null: NULL or [batch, min(n, d)] as umlh_svdvals. */
+int  umlh_effective_rank(const float* a, int32_t batch, int64_t n, int32_t d, int64_t ld_batch, int64_t ld_row, double eps,
+                         double* erank, double* sv_or_null, void* scratch, uint64_t scratch_bytes, void* stream);
+/* The effective rank of the valid rows of a block of sequences pooled into ONE matrix (train.py:380-389 flattens the same
+ * way): z[b, t, c] is read at z[b*ldb + t*ldt + c] (any non-overlapping strides >= d, so a [T, B, d] block or a column block
+ * of a wider tensor is used in place); row (b, t) counts iff t < clamp(lengths[b], 0, t_len) - drop_last (lengths = NULL:
+ * t_len everywhere).  Rows that do not count enter the Gram as zeros: no compaction, no host sync.  out2 = {effective rank,
+ * number of valid rows}; sv_or_null: NULL or d doubles, the min(rows, d) singular values then zeros.  drop_last >= 0. */
+int  umlh_effective_rank_seq(const float* z, int32_t b, int32_t t_len, int32_t d, int64_t ldb, int64_t ldt, const int64_t* lengths,
+                             int32_t drop_last, double eps, double* out2, double* sv_or_null, void* scratch, uint64_t scratch_bytes,
+                             void* stream);
 
 #ifdef __cplusplus
 }

@@ -223,7 +223,7 @@ static inline void mark(umlh_handle_t h, int i, hipStream_t st) {
 }
 
 const char* umlh_last_error(void) { return g_err; }
-int umlh_version(void) { return 7; }   // 3: round 2 (grouped / micro / data-parallel / encoder-plan / InfoNCE entry points, umlh_enc_layer_t.seed_device, umlh_seq_mse_backward scratch); 4: round 3 (umlh_step_status / _launches, umlh_p2p_*); 5: umlh_align_*; 6: umlh_masked_mean, umlh_probe_*; 7: umlh_align_cka_unbiased / _cka_rbf / _cknna / _list_stats
+int umlh_version(void) { return 8; }   // 3: round 2 (grouped / micro / data-parallel / encoder-plan / InfoNCE entry points, umlh_enc_layer_t.seed_device, umlh_seq_mse_backward scratch); 4: round 3 (umlh_step_status / _launches, umlh_p2p_*); 5: umlh_align_*; 6: umlh_masked_mean, umlh_probe_*; 7: umlh_align_cka_unbiased / _cka_rbf / _cknna / _list_stats; 8: umlh_spectral_scratch_bytes, umlh_svdvals, umlh_effective_rank, umlh_effective_rank_seq
 
 int umlh_freeze_proj_row(umlh_handle_t h, int32_t row) {
     if (!h) return fail(UMLH_E_INVALID, "umlh_freeze_proj_row: null handle");
@@ -800,6 +800,81 @@ int umlh_align_list_stats(const int32_t* knn_a, const int32_t* knn_b, int64_t n,
         return fail(UMLH_E_INVALID, "umlh_align_list_stats: scratch of %llu bytes, %llu needed", (unsigned long long)scratch_bytes,
                     (unsigned long long)need);
     HIPCHK(umlh_align_ext_launch_list_stats(knn_a, knn_b, n, topk, rows, out3, scratch, (hipStream_t)stream), "umlh_align_list_stats");
+    return UMLH_OK;
+}
+
+// ---- singular values and effective rank (kernels: umlh_kernels_spectral.hip); every check precedes the first HIP call ----
+static const int SPECTRAL_MAX_D = 512, SPECTRAL_MAX_BATCH = 65535;
+
+static bool spectral_shape_ok(int64_t batch, int64_t n, int32_t d) {
+    return batch >= 1 && batch <= SPECTRAL_MAX_BATCH && n >= 1 && n < ((int64_t)1 << 31) && batch * n < ((int64_t)1 << 31) && d >= 1 &&
+           d <= SPECTRAL_MAX_D;
+}
+
+uint64_t umlh_spectral_scratch_bytes(int32_t batch, int64_t n, int32_t d) {
+    return spectral_shape_ok(batch, n, d) ? umlh_spectral_bytes(batch, n, d) : 0;
+}
+
+// two nested strides cover `outer` x `inner` rows of d floats without overlap in one of the two nestings
+static bool spectral_strides_ok(int64_t outer, int64_t inner, int32_t d, int64_t so, int64_t si) {
+    if (si < d || (outer > 1 && so < d)) return false;
+    if (outer <= 1 || inner <= 1) return true;
+    return so >= (inner - 1) * si + d || si >= (outer - 1) * so + d;
+}
+
+// the shared checks of the two dense forms; 0 = fine
+static int check_spectral(const char* who, const float* a, int32_t batch, int64_t n, int32_t d, int64_t ld_batch, int64_t ld_row,
+                          const void* out, const void* scratch, uint64_t scratch_bytes) {
+    if (!a || !out || !scratch) return fail(UMLH_E_INVALID, "%s: null pointer (the input, the output and scratch are required)", who);
+    if (d < 1 || d > SPECTRAL_MAX_D) return fail(UMLH_E_INVALID, "%s: d=%d outside 1..%d", who, d, SPECTRAL_MAX_D);
+    if (!spectral_shape_ok(batch, n, d))
+        return fail(UMLH_E_INVALID, "%s: batch=%d n=%lld (need 1 <= batch <= %d, n >= 1, batch * n < 2^31)", who, batch, (long long)n,
+                    SPECTRAL_MAX_BATCH);
+    if (ld_row < d) return fail(UMLH_E_INVALID, "%s: ld_row=%lld < d=%d", who, (long long)ld_row, d);
+    if (!spectral_strides_ok(batch, n, d, ld_batch, ld_row))
+        return fail(UMLH_E_INVALID, "%s: ld_batch=%lld ld_row=%lld overlap for batch=%d n=%lld d=%d", who, (long long)ld_batch,
+                    (long long)ld_row, batch, (long long)n, d);
+    const uint64_t need = umlh_spectral_bytes(batch, n, d);
+    if (scratch_bytes < need)
+        return fail(UMLH_E_INVALID, "%s: scratch of %llu bytes, %llu needed", who, (unsigned long long)scratch_bytes, (unsigned long long)need);
+    return UMLH_OK;
+}
+
+int umlh_svdvals(const float* a, int32_t batch, int64_t n, int32_t d, int64_t ld_batch, int64_t ld_row, double* sv, void* scratch,
+                 uint64_t scratch_bytes, void* stream) {
+    if (int e = check_spectral("umlh_svdvals", a, batch, n, d, ld_batch, ld_row, sv, scratch, scratch_bytes)) return e;
+    HIPCHK(umlh_spectral_launch(a, batch, n, (int)n, ld_batch, 0, ld_row, nullptr, 0, d, 0.0, nullptr, nullptr, sv,
+                                (int)(n < d ? n : d), scratch, (hipStream_t)stream), "umlh_svdvals");
+    return UMLH_OK;
+}
+
+int umlh_effective_rank(const float* a, int32_t batch, int64_t n, int32_t d, int64_t ld_batch, int64_t ld_row, double eps, double* erank,
+                        double* sv_or_null, void* scratch, uint64_t scratch_bytes, void* stream) {
+    if (int e = check_spectral("umlh_effective_rank", a, batch, n, d, ld_batch, ld_row, erank, scratch, scratch_bytes)) return e;
+    if (!(eps >= 0.0) || !std::isfinite(eps)) return fail(UMLH_E_INVALID, "umlh_effective_rank: eps=%g (need a finite eps >= 0)", eps);
+    HIPCHK(umlh_spectral_launch(a, batch, n, (int)n, ld_batch, 0, ld_row, nullptr, 0, d, eps, erank, nullptr, sv_or_null,
+                                (int)(n < d ? n : d), scratch, (hipStream_t)stream), "umlh_effective_rank");
+    return UMLH_OK;
+}
+
+int umlh_effective_rank_seq(const float* z, int32_t b, int32_t t_len, int32_t d, int64_t ldb, int64_t ldt, const int64_t* lengths,
+                            int32_t drop_last, double eps, double* out2, double* sv_or_null, void* scratch, uint64_t scratch_bytes,
+                            void* stream) {
+    const char* who = "umlh_effective_rank_seq";
+    if (!z || !out2 || !scratch) return fail(UMLH_E_INVALID, "%s: null pointer (z, out2 and scratch are required)", who);
+    if (d < 1 || d > SPECTRAL_MAX_D) return fail(UMLH_E_INVALID, "%s: d=%d outside 1..%d", who, d, SPECTRAL_MAX_D);
+    if (b < 1 || t_len < 1 || !spectral_shape_ok(1, (int64_t)b * t_len, d))
+        return fail(UMLH_E_INVALID, "%s: b=%d t_len=%d (need b >= 1, t_len >= 1, b * t_len < 2^31)", who, b, t_len);
+    if (ldt < d || ldb < d) return fail(UMLH_E_INVALID, "%s: ldb=%lld ldt=%lld shorter than d=%d", who, (long long)ldb, (long long)ldt, d);
+    if (!spectral_strides_ok(b, t_len, d, ldb, ldt))
+        return fail(UMLH_E_INVALID, "%s: ldb=%lld ldt=%lld overlap for b=%d t_len=%d d=%d", who, (long long)ldb, (long long)ldt, b, t_len, d);
+    if (drop_last < 0) return fail(UMLH_E_INVALID, "%s: drop_last=%d < 0", who, drop_last);
+    if (!(eps >= 0.0) || !std::isfinite(eps)) return fail(UMLH_E_INVALID, "%s: eps=%g (need a finite eps >= 0)", who, eps);
+    const uint64_t need = umlh_spectral_bytes(1, (int64_t)b * t_len, d);
+    if (scratch_bytes < need)
+        return fail(UMLH_E_INVALID, "%s: scratch of %llu bytes, %llu needed", who, (unsigned long long)scratch_bytes, (unsigned long long)need);
+    HIPCHK(umlh_spectral_launch(z, 1, (int64_t)b * t_len, t_len, 0, ldb, ldt, reinterpret_cast<const long long*>(lengths), drop_last, d,
+                                eps, out2, out2 + 1, sv_or_null, d, scratch, (hipStream_t)stream), who);
     return UMLH_OK;
 }
 

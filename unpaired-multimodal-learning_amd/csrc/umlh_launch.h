@@ -133,6 +133,12 @@ int umlh_probe_launch_fit(const float* x, long long n, int d, int ldx, const int
                           hipStream_t st);
 int umlh_probe_launch_score(const float* x, long long n, int d, int ldx, const double* stats, const double* coef, const int* y,
                             long long* correct, float* decision, hipStream_t st);
+// ---- umlh_kernels_spectral.hip: fp64 Gram, symmetric eigenvalues, singular values and effective rank ----
+int umlh_spectral_chunks(int batch, long long n);
+unsigned long long umlh_spectral_bytes(int batch, long long n, int d);
+int umlh_spectral_launch(const float* a, int batch, long long rows, int period, long long sm, long long so, long long si,
+                         const long long* lengths, int drop_last, int d, double eps, double* erank, double* rows_out, double* sv,
+                         int sv_ld, void* scratch, hipStream_t st);
 
 // ---- umlh_api.cpp, for umlh_encoder.cpp ----
 // out[M,N] (ldo == N) = epilogue(A B^T) with the operand layouts of umlh_gemm_f32.  `splits` K-slabs go to `slabs`

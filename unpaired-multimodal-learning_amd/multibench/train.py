@@ -3,8 +3,10 @@ INDEPENDENTLY shuffled loaders zipped, x loss switched off while epoch <= step_k
 loss = alpha_x*loss_x + alpha_y*loss_y, one optimizer step per batch pair, and the reference's
 ``evaluate`` / ``evaluate_raw_data`` (train.py:31-240): every train / val / test batch through the model
 in eval mode, masked-mean pooling and binary logistic probes, all on the HIP kernels of ``umlh.probe``.
-The other per-batch diagnostics of the reference (covariance / svdvals effective rank, wandb, the
-embedding capture: train.py:386-389,428-443,452-515) are outside this port."""
+``train(effective_rank=True)`` adds the reference's per-step effective rank of the predicted y rows and of a fixed sample
+of the y modality (train.py:302-345,380-389) on the HIP kernels of ``umlh.spectral``.  The other per-batch diagnostics of
+the reference (the covariance matrices it forms and drops, wandb, the embedding capture: train.py:386,388,428-443,452-515)
+are outside this port."""
 from __future__ import annotations
 
 import copy
@@ -188,19 +190,49 @@ def _unpack(batch, modality, ds_name, which):
     return (batch[0].float(), batch[2]) if which == 0 else (batch[1].float(), batch[3])
 
 
+def _fixed_sample_rank(loader, modality, ds_name, dev, n_samples=1000):
+    """Effective rank of the valid rows (t < len) of the first ``n_samples`` sequences of a deep copy of ``loader``, y side
+    only (train.py:302-345,387): a 0-d float64 device tensor.  Batches may differ in T; each is padded with zero rows, which
+    the row predicate leaves out anyway."""
+    import umlh
+    seqs, lens, left = [], [], n_samples
+    for batch in copy.deepcopy(loader):
+        y, ly = _unpack(batch, modality, ds_name, 1)
+        y = y.unsqueeze(1) if y.ndim == 2 else y
+        seqs.append(y[:left].to(dev))
+        lens.append(torch.as_tensor(ly)[:left].reshape(-1).to(dev))
+        left -= seqs[-1].shape[0]
+        if left <= 0:
+            break
+    if not seqs:
+        raise ValueError("train(effective_rank=True): train_loader_2 yields no batch")
+    T = max(s.shape[1] for s in seqs)
+    block = torch.cat([torch.nn.functional.pad(s, (0, 0, 0, T - s.shape[1])) for s in seqs], dim=0)
+    with torch.cuda.device(dev):
+        return umlh.effective_rank_seq(block, torch.cat(lens), drop_last=0)[0]
+
+
 def train(model, train_mode, train_loader_1, train_loader_2, optimizer, modalities=[0, 2], num_epoch=100, step_k=30,
           ds_name="mosi", eval_config={}, alpha_x=1.0, alpha_y=1.0, capture_embeddings_during_training=False, augment=False,
-          debug=False, args=None, device="cuda:0", on_step=None):
+          debug=False, args=None, device="cuda:0", on_step=None, effective_rank=False):
     """Returns {'loss_x': [...], 'loss_y': [...], 'loss': [...]} with one entry per batch pair
     (device tensors are read back once at the end).  With a non-empty ``eval_config`` ({'train', 'val', 'test': batch
     lists, 'freq': int}) it evaluates as the reference does (train.py:350,440-451,519-523): ``evaluate_raw_data`` once,
     ``evaluate`` whenever i_batch % freq == 0 and once more after the last epoch, the model back in train mode after
     each; the dict then also holds 'raw' and 'eval' = [(epoch, i_batch, results), ...], where results are what the
     reference logs (evaluate's keys without the *_private / *_complete ones, plus the raw baselines) and the closing
-    evaluation is the entry with i_batch = None."""
+    evaluation is the entry with i_batch = None.
+
+    ``effective_rank=True`` with 'y' in ``train_mode`` adds 'pred_effective_rank_y': per batch pair the effective rank
+    (utilis.py:27-36) of the rows y_recon[b, t], t < len_b - 1, of the step's own forward (train.py:381-389), enqueued on the
+    training stream and read back at the end with the losses; and 'gt_effective_rank_y': that of the valid rows of the
+    first up-to-1000 sequences of a copy of ``train_loader_2`` (train.py:302-345,387), a constant the reference recomputes
+    every step and this loop computes once."""
     model.train()
     dev = torch.device(device)
-    rec_x, rec_y, rec_l = [], [], []
+    rec_x, rec_y, rec_l, rec_rank = [], [], [], []
+    want_rank = bool(effective_rank) and "y" in train_mode
+    gt_rank = _fixed_sample_rank(train_loader_2, modalities[1], ds_name, dev) if want_rank else None
     raw_results, evals = None, []
     if eval_config:
         raw_results = evaluate_raw_data(eval_config, ds_name=ds_name, device=device)
@@ -228,6 +260,10 @@ def train(model, train_mode, train_loader_1, train_loader_2, optimizer, modaliti
             rec_x.append(out["loss_x"].detach())
             rec_y.append(out["loss_y"].detach())
             rec_l.append(loss.detach())
+            if want_rank:
+                import umlh
+                with torch.cuda.device(dev):
+                    rec_rank.append(umlh.effective_rank_seq(out["y_recon"].detach(), l2, drop_last=1)[0])
             if on_step is not None:
                 on_step(epoch, i_batch, out, loss)
             if eval_config and i_batch % eval_config["freq"] == 0:
@@ -238,6 +274,9 @@ def train(model, train_mode, train_loader_1, train_loader_2, optimizer, modaliti
             model.train()
     stack = lambda v: torch.stack([t.reshape(()) for t in v]).cpu().tolist() if v else []
     res = {"loss_x": stack(rec_x), "loss_y": stack(rec_y), "loss": stack(rec_l)}
+    if want_rank:
+        res["pred_effective_rank_y"] = stack(rec_rank)
+        res["gt_effective_rank_y"] = float(gt_rank.cpu())
     if eval_config:
         res["raw"], res["eval"] = raw_results, evals
     return res

@@ -15,6 +15,8 @@ from .dp import DataParallelStepper  # noqa: F401,E402
 from . import align  # noqa: F401,E402
 from . import probe  # noqa: F401,E402
 from .probe import LogisticProbe, masked_mean  # noqa: F401,E402
+from . import spectral  # noqa: F401,E402
+from .spectral import effective_rank, effective_rank_seq, svdvals  # noqa: F401,E402
 
 
 def host_cpu_budget() -> int:

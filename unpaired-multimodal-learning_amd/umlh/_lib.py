@@ -20,7 +20,7 @@ PREC_IDS = {"fp32": 0, "bf16": 1}
 N_CORE_SCALARS = 8
 N_SCALARS = 12
 
-SOURCES = ["umlh_p2p.hip", "umlh_kernels_f32.hip", "umlh_kernels_bf16.hip", "umlh_kernels_micro.hip", "umlh_kernels_seq.hip", "umlh_kernels_enc.hip", "umlh_kernels_align.hip", "umlh_kernels_align_ext.hip", "umlh_kernels_probe.hip", "umlh_api.cpp", "umlh_encoder.cpp"]
+SOURCES = ["umlh_p2p.hip", "umlh_kernels_f32.hip", "umlh_kernels_bf16.hip", "umlh_kernels_micro.hip", "umlh_kernels_seq.hip", "umlh_kernels_enc.hip", "umlh_kernels_align.hip", "umlh_kernels_align_ext.hip", "umlh_kernels_probe.hip", "umlh_kernels_spectral.hip", "umlh_api.cpp", "umlh_encoder.cpp"]
 EXPORTS = ["umlh_last_error", "umlh_version", "umlh_enable_diagnostics", "umlh_set_diagnostic_columns", "umlh_freeze_proj_row", "umlh_workspace_bytes", "umlh_create", "umlh_destroy", "umlh_bind",
            "umlh_zero_shot_init", "umlh_logits", "umlh_train_step", "umlh_grad_step", "umlh_grad_buffer",
            "umlh_apply_update", "umlh_eval_batch", "umlh_eval_rows", "umlh_project", "umlh_optimizer_step",
@@ -37,7 +37,8 @@ EXPORTS = ["umlh_last_error", "umlh_version", "umlh_enable_diagnostics", "umlh_s
            "umlh_encoder_plan_backward", "umlh_encoder_plan_destroy",
            "umlh_align_scratch_bytes", "umlh_align_knn", "umlh_align_mutual_knn", "umlh_align_cka",
            "umlh_align_ext_scratch_bytes", "umlh_align_cka_unbiased", "umlh_align_cka_rbf", "umlh_align_cknna", "umlh_align_list_stats",
-           "umlh_masked_mean", "umlh_probe_scratch_bytes", "umlh_probe_column_stats", "umlh_probe_fit", "umlh_probe_score"]
+           "umlh_masked_mean", "umlh_probe_scratch_bytes", "umlh_probe_column_stats", "umlh_probe_fit", "umlh_probe_score",
+           "umlh_spectral_scratch_bytes", "umlh_svdvals", "umlh_effective_rank", "umlh_effective_rank_seq"]
 
 
 class UmlhError(RuntimeError):
@@ -227,12 +228,18 @@ def load_library():
     lib.umlh_probe_column_stats.argtypes = [vp, i64, i32, i32, vp, vp, u64, vp]
     lib.umlh_probe_fit.argtypes = [vp, i64, i32, i32, vp, vp, i32, C.c_double, i32, C.c_double, vp, vp, vp, vp, u64, vp]
     lib.umlh_probe_score.argtypes = [vp, i64, i32, i32, vp, vp, vp, vp, vp, vp]
+    lib.umlh_spectral_scratch_bytes.restype = u64
+    lib.umlh_spectral_scratch_bytes.argtypes = [i32, i64, i32]
+    lib.umlh_svdvals.argtypes = [vp, i32, i64, i32, i64, i64, vp, vp, u64, vp]
+    lib.umlh_effective_rank.argtypes = [vp, i32, i64, i32, i64, i64, C.c_double, vp, vp, vp, u64, vp]
+    lib.umlh_effective_rank_seq.argtypes = [vp, i32, i32, i32, i64, i64, vp, i32, C.c_double, vp, vp, vp, u64, vp]
     lib.umlh_profile_enable.argtypes = [vp, C.c_int]
     lib.umlh_profile_read.argtypes = [vp, C.POINTER(C.c_float)]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("umlh_last_error", "umlh_workspace_bytes", "umlh_encoder_layer_saved_floats", "umlh_encoder_layer_scratch_floats",
-                        "umlh_align_scratch_bytes", "umlh_align_ext_scratch_bytes", "umlh_probe_scratch_bytes"):
+                        "umlh_align_scratch_bytes", "umlh_align_ext_scratch_bytes", "umlh_probe_scratch_bytes",
+                        "umlh_spectral_scratch_bytes"):
             fn.restype = C.c_int
     _LIB = lib
     return lib
