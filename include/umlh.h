@@ -150,7 +150,7 @@ typedef struct {
 #define UMLH_N_SCALARS    12
 
 const char* umlh_last_error(void);
-int  umlh_version(void);        /* ABI revision: 3 = round 2 (grouped / micro / data-parallel / encoder-plan / InfoNCE entry points); 4 = round 3 (umlh_step_status / umlh_step_launches, umlh_p2p_*); 5 = umlh_align_* (CKA, k-NN, mutual k-NN); 6 = umlh_masked_mean, umlh_probe_* (linear probes of MultiBench evaluate); 7 = umlh_align_cka_unbiased / _cka_rbf / _cknna / _list_stats; 8 = umlh_spectral_scratch_bytes, umlh_svdvals, umlh_effective_rank, umlh_effective_rank_seq */
+int  umlh_version(void);        /* ABI revision: 3 = round 2 (grouped / micro / data-parallel / encoder-plan / InfoNCE entry points); 4 = round 3 (umlh_step_status / umlh_step_launches, umlh_p2p_*); 5 = umlh_align_* (CKA, k-NN, mutual k-NN); 6 = umlh_masked_mean, umlh_probe_* (linear probes of MultiBench evaluate); 7 = umlh_align_cka_unbiased / _cka_rbf / _cknna / _list_stats; 8 = umlh_spectral_scratch_bytes, umlh_svdvals, umlh_effective_rank, umlh_effective_rank_seq; 9 = umlh_subspace_scratch_bytes, umlh_principal_subspace, umlh_svcca */
 
 /* Bytes of workspace a handle with this config needs (0 on invalid config). */
 uint64_t umlh_workspace_bytes(const umlh_config_t* cfg);
@@ -625,6 +625,33 @@ int  umlh_effective_rank(const float* a, int32_t batch, int64_t n, int32_t d, in
 int  umlh_effective_rank_seq(const float* z, int32_t b, int32_t t_len, int32_t d, int64_t ldb, int64_t ldt, const int64_t* lengths,
                              int32_t drop_last, double eps, double* out2, double* sv_or_null, void* scratch, uint64_t scratch_bytes,
                              void* stream);
+
+/* ---- principal subspaces and SVCCA ----
+ * The top-q eigenpairs of a feature Gram, on the machinery above: the tridiagonalisation keeps its reflectors, bisection
+ * brackets the eigenvalues, inverse iteration on the tridiagonal (re-orthogonalised within clusters of close eigenvalues) gives
+ * its eigenvectors and the reflectors are applied in reverse.  Each vector's largest-magnitude component is positive (the first
+ * one on ties).  Standardised means the reference's per-column (x - mean) / (std + 1e-8) with the unbiased std
+ * (MultiBench/metrics.py:132-135): column means in a first pass, the centred Gram Gc in a second, G = D Gc D with
+ * D_j = 1 / (sqrt(Gc_jj / (n - 1)) + 1e-8); a constant column is an exactly zero row and column of G.
+ * Envelope: 2 <= n < 2^31, 1 <= d <= 512, 1 <= q <= min(n, d_a, d_b, 64), d <= ld < 2^31.  Every argument check happens before
+ * any HIP call; fixed iteration counts and summation orders: results are bitwise reproducible for given arguments. */
+
+/* Scratch bytes of umlh_svcca, or of umlh_principal_subspace when d_b = 0 (then d_a = d): O(chunks max(d)^2), no n x d term.
+ * 0 on invalid arguments. */
+uint64_t umlh_subspace_scratch_bytes(int64_t n, int32_t d_a, int32_t d_b, int32_t q);
+/* evals[q] (descending) and evecs[d, q] (row-major, orthonormal columns): the top-q eigenpairs of the standardised Gram
+ * (standardize = 1) or of the plain a^T a (standardize = 0: sqrt(evals) are the first q values of umlh_svdvals). */
+int  umlh_principal_subspace(const float* a, int64_t n, int32_t d, int64_t ld_row, int32_t q, int32_t standardize, double* evals,
+                             double* evecs, void* scratch, uint64_t scratch_bytes, void* stream);
+/* AlignmentMetrics.svcca(a, b, cca_dim = q) (metrics.py:129-160) in closed form: the mean of the canonical correlations rho
+ * between the top-q left singular subspaces of the two standardised views, rho = sqrt(eig(M^T M)) clamped to [0, 1] with
+ * M = L_a^(-1/2) V_a^T C V_b L_b^(-1/2), (L, V) the top-q eigenpairs of each standardised Gram and C the standardised
+ * cross-Gram.  out[1]; rho_or_null: NULL or [q], descending; evals_or_null: NULL or [2, q].  Equals the reference's value when
+ * sigma_q > sigma_(q+1) in both views; at a tie the subspace is not unique and the answer is deterministic but arbitrary.
+ * NaN when lambda_q <= d 2^-53 lambda_1 in either view (numerical rank below q, an all-constant view included) or when an
+ * input is not finite. */
+int  umlh_svcca(const float* a, const float* b, int64_t n, int32_t d_a, int32_t d_b, int64_t ld_a, int64_t ld_b, int32_t q,
+                double* out, double* rho_or_null, double* evals_or_null, void* scratch, uint64_t scratch_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -223,7 +223,7 @@ static inline void mark(umlh_handle_t h, int i, hipStream_t st) {
 }
 
 const char* umlh_last_error(void) { return g_err; }
-int umlh_version(void) { return 8; }   // 3: round 2 (grouped / micro / data-parallel / encoder-plan / InfoNCE entry points, umlh_enc_layer_t.seed_device, umlh_seq_mse_backward scratch); 4: round 3 (umlh_step_status / _launches, umlh_p2p_*); 5: umlh_align_*; 6: umlh_masked_mean, umlh_probe_*; 7: umlh_align_cka_unbiased / _cka_rbf / _cknna / _list_stats; 8: umlh_spectral_scratch_bytes, umlh_svdvals, umlh_effective_rank, umlh_effective_rank_seq
+int umlh_version(void) { return 9; }   // 3: round 2 (grouped / micro / data-parallel / encoder-plan / InfoNCE entry points, umlh_enc_layer_t.seed_device, umlh_seq_mse_backward scratch); 4: round 3 (umlh_step_status / _launches, umlh_p2p_*); 5: umlh_align_*; 6: umlh_masked_mean, umlh_probe_*; 7: umlh_align_cka_unbiased / _cka_rbf / _cknna / _list_stats; 8: umlh_spectral_scratch_bytes, umlh_svdvals, umlh_effective_rank, umlh_effective_rank_seq; 9: umlh_subspace_scratch_bytes, umlh_principal_subspace, umlh_svcca
 
 int umlh_freeze_proj_row(umlh_handle_t h, int32_t row) {
     if (!h) return fail(UMLH_E_INVALID, "umlh_freeze_proj_row: null handle");
@@ -875,6 +875,61 @@ int umlh_effective_rank_seq(const float* z, int32_t b, int32_t t_len, int32_t d,
         return fail(UMLH_E_INVALID, "%s: scratch of %llu bytes, %llu needed", who, (unsigned long long)scratch_bytes, (unsigned long long)need);
     HIPCHK(umlh_spectral_launch(z, 1, (int64_t)b * t_len, t_len, 0, ldb, ldt, reinterpret_cast<const long long*>(lengths), drop_last, d,
                                 eps, out2, out2 + 1, sv_or_null, d, scratch, (hipStream_t)stream), who);
+    return UMLH_OK;
+}
+
+// ---- principal subspaces and SVCCA (kernels: umlh_kernels_spectral.hip); every check precedes the first HIP call ----
+static const int SUBSPACE_MAX_Q = 64;
+
+// d_b = 0: the single-matrix op.  The row stride is an int in the column-statistics kernels, hence ld < 2^31.
+static bool subspace_shape_ok(int64_t n, int32_t d_a, int32_t d_b, int32_t q) {
+    if (n < 2 || n >= ((int64_t)1 << 31) || d_a < 1 || d_a > SPECTRAL_MAX_D || d_b < 0 || d_b > SPECTRAL_MAX_D) return false;
+    const int64_t lim = std::min<int64_t>(std::min<int64_t>(n, d_a), std::min<int64_t>(d_b ? d_b : d_a, SUBSPACE_MAX_Q));
+    return q >= 1 && q <= lim;
+}
+
+uint64_t umlh_subspace_scratch_bytes(int64_t n, int32_t d_a, int32_t d_b, int32_t q) {
+    return subspace_shape_ok(n, d_a, d_b, q) ? umlh_subspace_bytes(n, d_a, d_b, q) : 0;
+}
+
+// the checks of one view; 0 = fine
+static int check_view(const char* who, const char* name, int32_t d, int64_t ld) {
+    if (d < 1 || d > SPECTRAL_MAX_D) return fail(UMLH_E_INVALID, "%s: d_%s=%d outside 1..%d", who, name, d, SPECTRAL_MAX_D);
+    if (ld < d || ld >= ((int64_t)1 << 31))
+        return fail(UMLH_E_INVALID, "%s: ld_%s=%lld (need d_%s=%d <= ld < 2^31)", who, name, (long long)ld, name, d);
+    return UMLH_OK;
+}
+
+int umlh_principal_subspace(const float* a, int64_t n, int32_t d, int64_t ld_row, int32_t q, int32_t standardize, double* evals,
+                            double* evecs, void* scratch, uint64_t scratch_bytes, void* stream) {
+    const char* who = "umlh_principal_subspace";
+    if (!a || !evals || !evecs || !scratch) return fail(UMLH_E_INVALID, "%s: null pointer (a, evals, evecs and scratch are required)", who);
+    if (n < 2 || n >= ((int64_t)1 << 31)) return fail(UMLH_E_INVALID, "%s: n=%lld (need 2 <= n < 2^31)", who, (long long)n);
+    if (int e = check_view(who, "a", d, ld_row)) return e;
+    if (!subspace_shape_ok(n, d, 0, q))
+        return fail(UMLH_E_INVALID, "%s: q=%d outside 1..min(n, d, %d) for n=%lld d=%d", who, q, SUBSPACE_MAX_Q, (long long)n, d);
+    if (standardize != 0 && standardize != 1) return fail(UMLH_E_INVALID, "%s: standardize=%d (need 0 or 1)", who, standardize);
+    const uint64_t need = umlh_subspace_bytes(n, d, 0, q);
+    if (scratch_bytes < need)
+        return fail(UMLH_E_INVALID, "%s: scratch of %llu bytes, %llu needed", who, (unsigned long long)scratch_bytes, (unsigned long long)need);
+    HIPCHK(umlh_subspace_launch(a, n, d, ld_row, q, standardize, evals, evecs, scratch, (hipStream_t)stream), who);
+    return UMLH_OK;
+}
+
+int umlh_svcca(const float* a, const float* b, int64_t n, int32_t d_a, int32_t d_b, int64_t ld_a, int64_t ld_b, int32_t q, double* out,
+               double* rho_or_null, double* evals_or_null, void* scratch, uint64_t scratch_bytes, void* stream) {
+    const char* who = "umlh_svcca";
+    if (!a || !b || !out || !scratch) return fail(UMLH_E_INVALID, "%s: null pointer (a, b, out and scratch are required)", who);
+    if (n < 2 || n >= ((int64_t)1 << 31)) return fail(UMLH_E_INVALID, "%s: n=%lld (need 2 <= n < 2^31)", who, (long long)n);
+    if (int e = check_view(who, "a", d_a, ld_a)) return e;
+    if (int e = check_view(who, "b", d_b, ld_b)) return e;
+    if (!subspace_shape_ok(n, d_a, d_b, q))
+        return fail(UMLH_E_INVALID, "%s: q=%d outside 1..min(n, d_a, d_b, %d) for n=%lld d_a=%d d_b=%d", who, q, SUBSPACE_MAX_Q,
+                    (long long)n, d_a, d_b);
+    const uint64_t need = umlh_subspace_bytes(n, d_a, d_b, q);
+    if (scratch_bytes < need)
+        return fail(UMLH_E_INVALID, "%s: scratch of %llu bytes, %llu needed", who, (unsigned long long)scratch_bytes, (unsigned long long)need);
+    HIPCHK(umlh_svcca_launch(a, b, n, d_a, d_b, ld_a, ld_b, q, out, rho_or_null, evals_or_null, scratch, (hipStream_t)stream), who);
     return UMLH_OK;
 }
 

@@ -562,14 +562,23 @@ int umlh_probe_launch_masked_mean(const float* z, int B, int T, int Z, long long
     return (int)hipGetLastError();
 }
 
-int umlh_probe_launch_stats(const float* x, long long n, int d, int ldx, double* stats, void* scratch, hipStream_t st) {
+// pass 0: stats[0, d) = column means; pass 1: stats[d, 2d) = column scales about those means
+static void launch_stats_pass(int pass, const float* x, long long n, int d, int ldx, double* stats, void* scratch, hipStream_t st) {
     double* partial = (double*)scratch;
     const int chunks = (int)std::min<long long>(PB_STAT_CHUNKS, n);
     const dim3 grid((unsigned)((d + 63) / 64), (unsigned)chunks);
-    for (int pass = 0; pass < 2; ++pass) {
-        hipLaunchKernelGGL(pb_colsum, grid, dim3(256), 0, st, x, n, d, ldx, chunks, pass ? (const double*)stats : nullptr, partial);
-        hipLaunchKernelGGL(pb_stats_final, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, st, (const double*)partial, n, d, chunks, pass, stats);
-    }
+    hipLaunchKernelGGL(pb_colsum, grid, dim3(256), 0, st, x, n, d, ldx, chunks, pass ? (const double*)stats : nullptr, partial);
+    hipLaunchKernelGGL(pb_stats_final, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, st, (const double*)partial, n, d, chunks, pass, stats);
+}
+
+int umlh_probe_launch_stats(const float* x, long long n, int d, int ldx, double* stats, void* scratch, hipStream_t st) {
+    launch_stats_pass(0, x, n, d, ldx, stats, scratch, st);
+    launch_stats_pass(1, x, n, d, ldx, stats, scratch, st);
+    return (int)hipGetLastError();
+}
+
+int umlh_probe_launch_means(const float* x, long long n, int d, int ldx, double* mean, void* scratch, hipStream_t st) {
+    launch_stats_pass(0, x, n, d, ldx, mean, scratch, st);
     return (int)hipGetLastError();
 }
 

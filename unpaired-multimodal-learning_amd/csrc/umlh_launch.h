@@ -128,6 +128,8 @@ unsigned long long umlh_probe_stats_bytes(int d);
 int umlh_probe_launch_masked_mean(const float* z, int B, int T, int Z, long long ldb, long long ldt, const long long* lengths,
                                   float* out, int ldo, hipStream_t st);
 int umlh_probe_launch_stats(const float* x, long long n, int d, int ldx, double* stats, void* scratch, hipStream_t st);
+// the first pass of umlh_probe_launch_stats alone: mean[d], same scratch
+int umlh_probe_launch_means(const float* x, long long n, int d, int ldx, double* mean, void* scratch, hipStream_t st);
 int umlh_probe_launch_fit(const float* x, long long n, int d, int ldx, const int* y, const double* stats, int kind, double c,
                           int max_iter, double gtol, double* coef, umlh_probe_record_t* rec, double* objectives, void* scratch,
                           hipStream_t st);
@@ -139,6 +141,12 @@ unsigned long long umlh_spectral_bytes(int batch, long long n, int d);
 int umlh_spectral_launch(const float* a, int batch, long long rows, int period, long long sm, long long so, long long si,
                          const long long* lengths, int drop_last, int d, double eps, double* erank, double* rows_out, double* sv,
                          int sv_ld, void* scratch, hipStream_t st);
+// top-q eigenpairs of a feature Gram and SVCCA; d_b = 0 in umlh_subspace_bytes: the single-matrix op
+unsigned long long umlh_subspace_bytes(long long n, int da, int db, int q);
+int umlh_subspace_launch(const float* a, long long n, int d, long long ld, int q, int standardize, double* evals, double* evecs,
+                         void* scratch, hipStream_t st);
+int umlh_svcca_launch(const float* a, const float* b, long long n, int da, int db, long long lda, long long ldb, int q, double* out,
+                      double* rho, double* evals, void* scratch, hipStream_t st);
 
 // ---- umlh_api.cpp, for umlh_encoder.cpp ----
 // out[M,N] (ldo == N) = epilogue(A B^T) with the operand layouts of umlh_gemm_f32.  `splits` K-slabs go to `slabs`

@@ -3,8 +3,8 @@ on the HIP kernels of ``umlh.align``.
 
 Built: ``cka`` with ``kernel_metric='ip'`` and ``unbiased=False`` (what every caller uses), ``mutual_knn`` and
 ``compute_nearest_neighbors``.  The other names of ``SUPPORTED_METRICS`` raise ``NotImplementedError`` here (all but
-``svcca`` run as HIP kernels through ``umlh.align.measure``, which takes the same names and keyword arguments); unknown
-names raise ``ValueError`` as the reference does.  Like the reference's ``.item()``, ``measure`` returns Python floats.
+``svcca`` run as HIP kernels through ``umlh.align.measure``, which takes the same names and keyword arguments; ``svcca``
+is ``umlh.align.svcca(feats_A, feats_B, cca_dim)``); unknown names raise ``ValueError`` as the reference does.  Like the reference's ``.item()``, ``measure`` returns Python floats.
 
 Neighbours are by raw inner product with self excluded; exact ties go to the smaller column index (the reference leaves
 that order to torch's sort).  Importing this module does not touch the GPU.

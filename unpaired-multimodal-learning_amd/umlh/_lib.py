@@ -38,7 +38,8 @@ EXPORTS = ["umlh_last_error", "umlh_version", "umlh_enable_diagnostics", "umlh_s
            "umlh_align_scratch_bytes", "umlh_align_knn", "umlh_align_mutual_knn", "umlh_align_cka",
            "umlh_align_ext_scratch_bytes", "umlh_align_cka_unbiased", "umlh_align_cka_rbf", "umlh_align_cknna", "umlh_align_list_stats",
            "umlh_masked_mean", "umlh_probe_scratch_bytes", "umlh_probe_column_stats", "umlh_probe_fit", "umlh_probe_score",
-           "umlh_spectral_scratch_bytes", "umlh_svdvals", "umlh_effective_rank", "umlh_effective_rank_seq"]
+           "umlh_spectral_scratch_bytes", "umlh_svdvals", "umlh_effective_rank", "umlh_effective_rank_seq",
+           "umlh_subspace_scratch_bytes", "umlh_principal_subspace", "umlh_svcca"]
 
 
 class UmlhError(RuntimeError):
@@ -233,13 +234,17 @@ def load_library():
     lib.umlh_svdvals.argtypes = [vp, i32, i64, i32, i64, i64, vp, vp, u64, vp]
     lib.umlh_effective_rank.argtypes = [vp, i32, i64, i32, i64, i64, C.c_double, vp, vp, vp, u64, vp]
     lib.umlh_effective_rank_seq.argtypes = [vp, i32, i32, i32, i64, i64, vp, i32, C.c_double, vp, vp, vp, u64, vp]
+    lib.umlh_subspace_scratch_bytes.restype = u64
+    lib.umlh_subspace_scratch_bytes.argtypes = [i64, i32, i32, i32]
+    lib.umlh_principal_subspace.argtypes = [vp, i64, i32, i64, i32, i32, vp, vp, vp, u64, vp]
+    lib.umlh_svcca.argtypes = [vp, vp, i64, i32, i32, i64, i64, i32, vp, vp, vp, vp, u64, vp]
     lib.umlh_profile_enable.argtypes = [vp, C.c_int]
     lib.umlh_profile_read.argtypes = [vp, C.POINTER(C.c_float)]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("umlh_last_error", "umlh_workspace_bytes", "umlh_encoder_layer_saved_floats", "umlh_encoder_layer_scratch_floats",
                         "umlh_align_scratch_bytes", "umlh_align_ext_scratch_bytes", "umlh_probe_scratch_bytes",
-                        "umlh_spectral_scratch_bytes"):
+                        "umlh_spectral_scratch_bytes", "umlh_subspace_scratch_bytes"):
             fn.restype = C.c_int
     _LIB = lib
     return lib

@@ -9,7 +9,10 @@ other float dtypes are upcast and CPU tensors copied to the current device.  The
 The kernels of umlh_kernels_align_ext.hip add the rest of the reference's ``AlignmentMetrics``: ``unbiased_cka`` (:122-125
 with hsic_unbiased :230-249), ``rbf_cka`` (``cka(kernel_metric='rbf')``, biased and unbiased, :103-119), ``cknna`` (:180-227),
 ``cycle_knn`` (:39-51), ``lcs_knn`` (:88-92) and ``edit_distance_knn`` (:164-176), and ``measure`` dispatches the reference's
-metric names and keyword arguments to all of them.  Not built: ``svcca`` and the ``distance_agnostic`` / biased CKNNA.
+metric names and keyword arguments to all of them.  Not built: the ``distance_agnostic`` / biased CKNNA.
+
+``svcca`` (:129-160) runs on the kernels of umlh_kernels_spectral.hip (C ABI: ``umlh_svcca``) in closed form: see its
+docstring and DESIGN section 13.  ``measure("svcca", ...)`` is not routed to it yet and still raises NotImplementedError.
 """
 from __future__ import annotations
 
@@ -18,6 +21,7 @@ import math
 
 import torch
 
+from . import spectral
 from ._lib import UmlhError, check, load_library
 
 MAX_TOPK = 32
@@ -289,9 +293,50 @@ def _cknna_any(feats_A, feats_B, topk=None, distance_agnostic=False, unbiased=Tr
     return cknna(feats_A, feats_B, topk)
 
 
+def svcca_terms(a: torch.Tensor, b: torch.Tensor, cca_dim: int = 10):
+    """``(value, rho[q], evals[2, q])`` of ``svcca`` with q = cca_dim: the mean canonical correlation (0-d), the canonical
+    correlations (descending, clamped to [0, 1]) and the top-q eigenvalues of the two standardised Grams; float64 device tensors."""
+    if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor)) or a.ndim != 2 or b.ndim != 2 or a.shape[0] != b.shape[0]:
+        raise ValueError(f"svcca: features of shapes {tuple(getattr(a, 'shape', ()))} and {tuple(getattr(b, 'shape', ()))} "
+                         "(need 2-D with the same N)")
+    n, d_a = spectral._view(a, "svcca")
+    _, d_b = spectral._view(b, "svcca")
+    q = spectral._check_q(cca_dim, min(n, d_a, d_b), "svcca")
+    dev = _device()
+    xa, xb = spectral._rows_in_place(a, dev), spectral._rows_in_place(b, dev)
+    lib = load_library()
+    nbytes = lib.umlh_subspace_scratch_bytes(n, d_a, d_b, q)
+    if nbytes == 0:
+        raise UmlhError(f"umlh_subspace_scratch_bytes: invalid arguments n={n} d_a={d_a} d_b={d_b} q={q}")
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out = torch.empty((), dtype=torch.float64, device=dev)
+    rho = torch.empty(q, dtype=torch.float64, device=dev)
+    evals = torch.empty((2, q), dtype=torch.float64, device=dev)
+    check(lib.umlh_svcca(xa.data_ptr(), xb.data_ptr(), n, d_a, d_b, xa.stride(0), xb.stride(0), q, out.data_ptr(), rho.data_ptr(),
+                         evals.data_ptr(), scratch.data_ptr(), nbytes, _stream(dev)), "umlh_svcca")
+    return out, rho, evals
+
+
+def svcca(a: torch.Tensor, b: torch.Tensor, cca_dim: int = 10) -> torch.Tensor:
+    """AlignmentMetrics.svcca(a, b, cca_dim) (MultiBench/metrics.py:129-160) in closed form: a 0-d float64 device tensor.
+
+    The reference standardises every column ((x - mean) / (unbiased std + 1e-8)), takes the top-q left singular vectors of each
+    view with a randomised SVD and runs scikit-learn's CCA on them.  Those bases are centred and orthonormal and CCA does not
+    change under an invertible map of either one, so its value is the mean singular value of U_a^T U_b.  This is computed
+    from the two d x d standardised Grams, their top-q eigenpairs and the d_a x d_b cross-Gram, all in fp64; nothing N x q is
+    formed.  2 <= N < 2^31, d <= 512, cca_dim <= min(N, d_a, d_b, 64).
+
+    * The value equals the reference's when sigma_q > sigma_(q+1) in both standardised views.  At a tie the subspace is not
+      unique: the reference's value then depends on its random test matrix; this one is deterministic but arbitrary.
+    * NaN when the numerical rank of a view is below q (lambda_q <= d 2^-53 lambda_1, an all-constant view included; the
+      reference returns noise there) and when an input holds a NaN or Inf.
+    * The reference's 1e-10 * randn jitter (:153-154) has no counterpart."""
+    return svcca_terms(a, b, cca_dim)[0]
+
+
 def _svcca(*args, **kwargs):
-    raise NotImplementedError("svcca is not built: it is a randomised SVD followed by scikit-learn's CCA, neither of which "
-                              "has a HIP path here")
+    raise NotImplementedError("svcca is not routed through measure(): call umlh.align.svcca(a, b, cca_dim), the closed-form "
+                              "fp64 HIP path")
 
 
 def measure(metric: str, feats_A: torch.Tensor, feats_B: torch.Tensor, **kwargs) -> float:

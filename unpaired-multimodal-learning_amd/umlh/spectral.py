@@ -1,5 +1,5 @@
-"""Singular values and effective rank on the HIP kernels of umlh_kernels_spectral.hip (C ABI: ``umlh_svdvals``,
-``umlh_effective_rank``, ``umlh_effective_rank_seq``).
+"""Singular values, effective rank and principal subspaces on the HIP kernels of umlh_kernels_spectral.hip (C ABI:
+``umlh_svdvals``, ``umlh_effective_rank``, ``umlh_effective_rank_seq``, ``umlh_principal_subspace``).
 
 ``svdvals`` is ``torch.linalg.svdvals`` for [n, d] or [batch, n, d] fp32 matrices with d <= 512, ``effective_rank`` the
 reference's ``compute_effective_rank`` (MultiBench/utilis.py:27-36) and ``effective_rank_seq`` the same number for the valid
@@ -8,16 +8,21 @@ values are the roots of the eigenvalues of the fp64 Gram matrix; results are flo
 on ``torch.cuda.current_stream`` and returns without synchronising.  fp32 device tensors with unit column stride are read in
 place through their strides; other float dtypes are upcast and CPU tensors copied to the current device.  There is no CPU
 compute path.
+
+``principal_subspace`` returns the top-q eigenpairs of the Gram ``a^T a`` of an [n, d] matrix, or of the Gram of its
+standardised columns (the PCA of the correlation matrix times n - 1): see its docstring and DESIGN section 13.
 """
 from __future__ import annotations
 
 import ctypes as C
+import operator
 
 import torch
 
 from ._lib import UmlhError, check, load_library
 
 MAX_D = 512
+MAX_Q = 64
 CHUNK_ROWS = 256
 MAX_CHUNKS = 128
 
@@ -155,3 +160,60 @@ def effective_rank_seq(z: torch.Tensor, lengths: torch.Tensor | None = None, dro
                                       sv.data_ptr() if sv is not None else None, scratch.data_ptr(), nbytes, _stream(dev)),
           "umlh_effective_rank_seq")
     return (out, sv) if return_svdvals else out
+
+
+def _view(a, what: str):
+    """The checks of one [n, d] view that need no device -> (n, d)."""
+    if not isinstance(a, torch.Tensor) or a.ndim != 2:
+        raise ValueError(f"{what}: expected a 2-D tensor [n, d], got {getattr(a, 'shape', type(a))}")
+    if not a.is_floating_point():
+        raise ValueError(f"{what}: expected a floating-point tensor, got {a.dtype}")
+    n, d = a.shape
+    if not 2 <= n < 2 ** 31:
+        raise ValueError(f"{what}: n={n} rows (need 2 <= n < 2^31)")
+    if not 1 <= d <= MAX_D:
+        raise ValueError(f"{what}: d={d} outside 1..{MAX_D}")
+    return n, d
+
+
+def _check_q(q, limit: int, what: str) -> int:
+    try:
+        q = operator.index(q)
+    except TypeError:
+        raise ValueError(f"{what}: q={q!r} is not an integer") from None
+    if not 1 <= q <= min(limit, MAX_Q):
+        raise ValueError(f"{what}: q={q} outside 1..{min(limit, MAX_Q)} (min of n, d and {MAX_Q})")
+    return q
+
+
+def _rows_in_place(a: torch.Tensor, dev: torch.device) -> torch.Tensor:
+    """A 2-D fp32 device view with unit column stride and a row stride in d..2^31 - 1."""
+    a = a.detach().to(device=dev, dtype=torch.float32)
+    if a.stride(1) != 1 or not a.shape[1] <= a.stride(0) < 2 ** 31:
+        a = a.contiguous()
+    return a
+
+
+def principal_subspace(a: torch.Tensor, q: int, standardize: bool = False):
+    """The top-q eigenpairs of the Gram of an [n, d] matrix: ``(evals[q], evecs[d, q])``, float64 device tensors, eigenvalues
+    descending, eigenvectors in columns, orthonormal, each with its largest-magnitude component positive.
+
+    ``standardize=False``: the Gram is ``a^T a``, so ``evals.sqrt()`` are the first q values of ``svdvals(a)``.
+    ``standardize=True``: the columns are first centred and divided by (unbiased std + 1e-8), as the reference's SVCCA does
+    (MultiBench/metrics.py:132-135); a constant column is then exactly zero.  ``a @ evecs / evals.sqrt()`` of the standardised
+    matrix are its top-q left singular vectors.  2 <= n < 2^31, d <= 512, q <= min(n, d, 64).  Eigenvectors of eigenvalues that
+    are equal (to rounding) span the right subspace but are otherwise arbitrary; a NaN or Inf in the input makes everything NaN."""
+    n, d = _view(a, "principal_subspace")
+    q = _check_q(q, min(n, d), "principal_subspace")
+    dev = _device()
+    x = _rows_in_place(a, dev)
+    lib = load_library()
+    nbytes = lib.umlh_subspace_scratch_bytes(n, d, 0, q)
+    if nbytes == 0:
+        raise UmlhError(f"umlh_subspace_scratch_bytes: invalid arguments n={n} d={d} q={q}")
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    evals = torch.empty(q, dtype=torch.float64, device=dev)
+    evecs = torch.empty((d, q), dtype=torch.float64, device=dev)
+    check(lib.umlh_principal_subspace(x.data_ptr(), n, d, x.stride(0), q, int(bool(standardize)), evals.data_ptr(), evecs.data_ptr(),
+                                      scratch.data_ptr(), nbytes, _stream(dev)), "umlh_principal_subspace")
+    return evals, evecs
