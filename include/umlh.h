@@ -371,12 +371,15 @@ int  umlh_infonce_backward(const float* pred_hat, const float* target_hat, const
 int  umlh_gemm_f32(const float* A, const float* B, float* out, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldb,
                    int32_t ldo, int32_t ta, int32_t tb, const int64_t* a_rows, const int64_t* k_rows, float alpha,
                    int32_t splits, float* slabs, void* stream);
-/* y[m][n] = act(y[m][n] + bias[n]) in place (bias may be NULL; relu != 0: max(.,0)) */
+/* y[m][n] = act(y[m][n] + bias[n]) in place (bias may be NULL; relu != 0: fmaxf(., 0) -- whatever is not > 0 becomes +0.0, a
+ * NaN included, which torch.relu would keep) */
 int  umlh_bias_act(float* y, const float* bias, int64_t M, int32_t N, int32_t relu, void* stream);
 /* dy[i] = y[i] > 0 ? dy[i] : 0 in place */
 int  umlh_relu_backward(const float* y, float* dy, int64_t n, void* stream);
-/* x[i] = keep_i ? x[i]/(1-p) : 0 in place; keep_i is a pure function of (seed, i): the same call on the
- * gradient is the backward pass.  p == 0: no-op. */
+/* x[i] = keep_i ? x[i] * (1.f/(1.f-p)) : 0 in place; keep_i is a pure function of (seed, i): the same call on the
+ * gradient is the backward pass.  p == 0: no-op.  `seed` names a mask STREAM and i is the flat element index; every dropout of
+ * the encoder draws from such a stream, so the mask of any of them is what this call leaves of a tensor of ones with the same p
+ * and seed (tests/test_encoder_kernels_gpu.py builds its float64 references from exactly that). */
 int  umlh_dropout(float* x, int64_t n, float p, uint64_t seed, void* stream);
 /* y[i] += x[i]  (gradient fan-in of a residual branch) */
 int  umlh_add_inplace(float* y, const float* x, int64_t n, void* stream);
@@ -395,7 +398,11 @@ int  umlh_positions_backward(const float* dx, int32_t T, int32_t B, int32_t Z, f
 int  umlh_gather_rows(const float* x, const int64_t* idx, int32_t n, int32_t Z, float* out, int32_t scatter, void* stream);
 /* Causal multi-head self-attention with key padding over packed in-projections qkv [T,B,3Z] (torch
  * MultiheadAttention layout), H heads; lengths int64[B] or NULL.  ctx [T,B,Z] (heads concatenated, before
- * out_proj), lse [B,H,T] saved for the backward.  p/seed: attention-probability dropout.  T <= 128, Z/H <= 64. */
+ * out_proj), lse [B,H,T] saved for the backward.  p/seed: attention-probability dropout: the probability of (query t, key j) of batch b, head h is element
+ * ((b*H + h)*T + t)*T + j of stream `seed`; it multiplies the NORMALISED probabilities (lse and the softmax denominator run
+ * over all visible keys, kept or not); in the backward dv sums the dropped probabilities and dS is built from the undropped
+ * ones.  Key j is visible to query t iff j <= t and j < lengths[b]; padded query rows are computed like any other; dk and dv
+ * rows of padded keys are exactly 0.  T <= 128, Z/H <= 64. */
 int  umlh_attention_forward(const float* qkv, const int64_t* lengths, int32_t T, int32_t B, int32_t Z, int32_t H, float p,
                             uint64_t seed, float* ctx, float* lse, void* stream);
 int  umlh_attention_backward(const float* qkv, const int64_t* lengths, const float* lse, const float* dctx, int32_t T, int32_t B,
@@ -404,7 +411,8 @@ int  umlh_attention_backward(const float* qkv, const int64_t* lengths, const flo
 /* One whole post-norm nn.TransformerEncoderLayer (MultiBench/models.py:57-60: d_model = Z, nhead = H, dim_feedforward = d_ff,
  * relu, dropout p, causal + key-padding mask), forward / backward, as ONE call each: the launch sequence the host mirror
  * used to drive op by op is enqueued from C (same kernels, same arithmetic, same dropout seeds: seed for the attention
- * probabilities, seed+1 / +2 / +3 for dropout1 / the FFN dropout / dropout2).
+ * probabilities (element index as in umlh_attention_forward), seed+1 / +2 / +3 for dropout1 / the FFN dropout / dropout2, each
+ * indexed by the flat element m*N + n of its [M, N] activation: [M, Z], [M, d_ff], [M, Z]).
  *   params[12] = in_proj_weight [3Z,Z], in_proj_bias, out_proj.weight [Z,Z], out_proj.bias, linear1.weight [d_ff,Z],
  *                linear1.bias, linear2.weight [Z,d_ff], linear2.bias, norm1.weight, norm1.bias, norm2.weight, norm2.bias
  *   h_in / h_out [T*B, Z] token rows m = t*B + b;  saved: caller buffer of umlh_encoder_layer_saved_floats(cfg) floats that
