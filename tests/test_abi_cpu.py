@@ -1,5 +1,6 @@
 """CPU-side checks of the C-ABI shared library: it builds for gfx950, loads, and
-exports every symbol include/umlh.h declares (no compute without a GPU)."""
+exports every symbol include/umlh.h declares (no compute without a GPU); the ctypes
+prototype table of umlh/_lib.py agrees with the header, declaration by declaration."""
 import ctypes as C
 import os
 import re
@@ -77,3 +78,83 @@ def test_encoder_ops_validate_arguments_before_touching_the_gpu(lib):
     assert rc != 0 and b"envelope" in lib.umlh_last_error()
     assert lib.umlh_dropout(fake, 10, C.c_float(1.5), C.c_uint64(1), None) != 0
     assert lib.umlh_eval_rows(None, None, None, None) != 0
+
+
+# ---- the ctypes prototype table against include/umlh.h (no GPU, no build) ----
+_C_CLASSES = {"int": "i32", "int32_t": "i32", "int64_t": "i64", "uint64_t": "u64", "float": "float", "double": "double",
+              "void": "none", "umlh_handle_t": "pointer", "umlh_enc_plan_t": "pointer", "umlh_allreduce_fn": "pointer"}
+
+
+def _c_class(ctype: str) -> str:
+    if "*" in ctype or "[" in ctype:
+        return "pointer"
+    return _C_CLASSES[ctype.replace("const", "").strip()]
+
+
+def _ctypes_class(t) -> str:
+    if t is None:
+        return "none"
+    if t in (C.c_void_p, C.c_char_p) or issubclass(t, (C._Pointer, C._CFuncPtr)):
+        return "pointer"
+    return {C.c_int32: "i32", C.c_int64: "i64", C.c_uint64: "u64", C.c_float: "float", C.c_double: "double"}[t]
+
+
+def header_prototypes() -> dict:
+    """name -> (return class, [argument classes]) of every umlh_* declaration of include/umlh.h."""
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "umlh.h")).read(), flags=re.S)
+    out = {}
+    for ret, name, args in re.findall(r"^[ \t]*([A-Za-z_][\w \t]*?\**)[ \t]*\b(umlh_\w+)[ \t]*\(([^()]*)\)[ \t]*;", hdr, flags=re.M):
+        args = [a.strip() for a in args.split(",")]
+        if args == ["void"]:
+            args = []
+        # a parameter is `type name` or `type name[n]`: drop the name, keep what makes it a pointer
+        out[name] = (_c_class(ret), [_c_class(re.sub(r"\b\w+[ \t]*(\[\w*\])?$", r"\1", a)) for a in args])
+    return out
+
+
+def prototype_mismatches(table: dict) -> list:
+    """Every way ``table`` (name -> (restype, argtypes or None)) differs from the header, as sorted strings."""
+    hdr, bad = header_prototypes(), []
+    bad += [f"{n}: declared in umlh.h, missing from the table" for n in hdr.keys() - table.keys()]
+    bad += [f"{n}: in the table, not declared in umlh.h" for n in table.keys() - hdr.keys()]
+    for name in hdr.keys() & table.keys():
+        restype, argtypes = table[name]
+        if _ctypes_class(restype) != hdr[name][0]:
+            bad.append(f"{name}: returns {hdr[name][0]}, restype {getattr(restype, '__name__', restype)}")
+        if argtypes is None:
+            bad.append(f"{name}: no argtypes")
+        elif [_ctypes_class(t) for t in argtypes] != hdr[name][1]:
+            bad.append(f"{name}: takes {hdr[name][1]}, argtypes {[_ctypes_class(t) for t in argtypes]}")
+    return sorted(bad)
+
+
+def test_header_parse_finds_every_declaration():
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "umlh.h")).read(), flags=re.S)
+    protos = header_prototypes()
+    assert set(protos) == set(re.findall(r"\b(umlh_[a-z0-9_]+)\s*\(", hdr))     # every name that is followed by `(`
+    assert protos["umlh_encoder_plan_offsets"] == ("i32", ["pointer", "pointer"])                      # uint64_t offsets[6]
+    assert protos["umlh_last_error"] == ("pointer", []) and protos["umlh_encoder_plan_destroy"] == ("none", ["pointer"])
+    assert protos["umlh_p2p_region_bytes"] == ("u64", ["i64", "i32"])
+    assert protos["umlh_set_allreduce"] == ("i32", ["pointer", "pointer", "pointer", "i32"])
+
+
+def test_prototype_table_matches_the_header():
+    from umlh import _lib
+    assert _lib.EXPORTS == list(_lib.PROTOTYPES)
+    assert prototype_mismatches(_lib.PROTOTYPES) == []
+
+
+def test_loaded_library_carries_the_table(lib):
+    from umlh import _lib
+    for name, (restype, argtypes) in _lib.PROTOTYPES.items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+    assert lib.umlh_encoder_plan_destroy.restype is None
+    assert lib.umlh_version.argtypes == []
+    for name in ("umlh_p2p_region_bytes", "umlh_seq_mse_backward_scratch_floats", "umlh_encoder_plan_floats"):
+        assert getattr(lib, name).restype is C.c_uint64, name
+
+
+def test_size_queries_do_not_truncate_at_32_bits(lib):
+    # a region for n floats cannot be smaller than n floats (csrc/umlh_p2p.hip: 2 * n_ranks slices of >= n / n_ranks floats)
+    assert lib.umlh_p2p_region_bytes(1 << 31, 1) >= 4 * (1 << 31)

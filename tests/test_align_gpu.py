@@ -205,3 +205,18 @@ def test_gaussian_replay_alignment_matches_reference(gold):
         delta = 2 * 2e-4 * np.sqrt(x.shape[1]) * (nrm + nrm.max()) + R.tau(x)
         slack += int((gold[f"toy/set_gap_{v}_k10"] <= delta).sum())
     assert abs(log["val_mknn"][-1] - float(gold["toy/ref_mknn_k10"])) <= 1e-6 + slack / n
+
+
+def test_cka_is_enqueued_on_the_current_stream():
+    """The wrappers hand the kernels torch's CURRENT stream: issued under a side stream and read after synchronising only that
+    stream, the result has the bits of the default-stream run."""
+    from umlh import align
+    g = torch.Generator().manual_seed(7)
+    a, b = torch.randn(64, 8, generator=g).to(DEV), torch.randn(64, 8, generator=g).to(DEV)
+    want = align.cka_terms(a, b).cpu()
+    side = torch.cuda.Stream(device=DEV)
+    with torch.cuda.stream(side):
+        got = align.cka_terms(a, b)
+        side.synchronize()
+        got = got.cpu()
+    assert torch.equal(got.view(torch.int64), want.view(torch.int64)), (got, want)

@@ -3,12 +3,14 @@ transformer encoder, next-step prediction loss (reference: MultiBench/models.py:
 assembly MultiBench/main.py:117-121)."""
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 import torch
 import torch.nn.functional as F
 from torch import nn
+
+from umlh._glue import ptr, stream
+from umlh._lib import check, load_library
 
 
 class Linear(nn.Module):
@@ -121,8 +123,7 @@ class _InfoNCE(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, p, t, temperature):
-        import umlh
-        lib = umlh.load_library()
+        lib = load_library()
         p, t = (v.detach().to(torch.float32).contiguous() for v in (p, t))
         n, D = p.shape
         dev = p.device
@@ -130,26 +131,21 @@ class _InfoNCE(torch.autograd.Function):
         pnorm, row_loss = torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
         probs = torch.empty(n, n, dtype=torch.float32, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        vp = lambda v: C.c_void_p(v.data_ptr())
-        umlh._lib.check(lib.umlh_infonce_forward(vp(p), vp(t), n, D, float(temperature), vp(phat), vp(that), vp(pnorm), vp(probs), vp(row_loss),
-                                                 vp(loss), st), "umlh_infonce_forward")
+        check(lib.umlh_infonce_forward(ptr(p), ptr(t), n, D, float(temperature), ptr(phat), ptr(that), ptr(pnorm), ptr(probs), ptr(row_loss),
+                                       ptr(loss), stream(dev)), "umlh_infonce_forward")
         ctx.save_for_backward(phat, that, pnorm, probs)
         ctx.temperature = float(temperature)
         return loss
 
     @staticmethod
     def backward(ctx, g):
-        import umlh
-        lib = umlh.load_library()
+        lib = load_library()
         phat, that, pnorm, probs = ctx.saved_tensors
         n, D = phat.shape
         g = g.detach().to(torch.float32).reshape(1).contiguous()
         dhat, dp = torch.empty_like(phat), torch.empty_like(phat)
-        st = C.c_void_p(torch.cuda.current_stream(phat.device).cuda_stream)
-        vp = lambda v: C.c_void_p(v.data_ptr())
-        umlh._lib.check(lib.umlh_infonce_backward(vp(phat), vp(that), vp(pnorm), vp(probs), vp(g), n, D, ctx.temperature, vp(dhat), vp(dp), st),
-                        "umlh_infonce_backward")
+        check(lib.umlh_infonce_backward(ptr(phat), ptr(that), ptr(pnorm), ptr(probs), ptr(g), n, D, ctx.temperature, ptr(dhat), ptr(dp),
+                                        stream(phat.device)), "umlh_infonce_backward")
         return dp, None, None
 
 
@@ -178,8 +174,7 @@ class _DecoderNextStepMSE(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, w, b, x, lengths):
-        import umlh
-        lib = umlh.load_library()
+        lib = load_library()
         B, T, Z = z.shape
         D = w.shape[0]
         z, w, b, x = (t.detach().to(torch.float32).contiguous() for t in (z, w, b, x))
@@ -188,10 +183,8 @@ class _DecoderNextStepMSE(torch.autograd.Function):
         dres = torch.empty(B * T * D, dtype=torch.float32, device=z.device)
         part = torch.empty(B * T, dtype=torch.float32, device=z.device)
         loss_cnt = torch.empty(2, dtype=torch.float32, device=z.device)
-        st = C.c_void_p(torch.cuda.current_stream(z.device).cuda_stream)
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        umlh._lib.check(lib.umlh_seq_mse_forward(p(z), p(w), p(b), p(x), p(lens), B, T, Z, D, p(recon), p(dres), p(part),
-                                                 p(loss_cnt), st), "umlh_seq_mse_forward")
+        check(lib.umlh_seq_mse_forward(ptr(z), ptr(w), ptr(b), ptr(x), ptr(lens), B, T, Z, D, ptr(recon), ptr(dres), ptr(part),
+                                       ptr(loss_cnt), stream(z.device)), "umlh_seq_mse_forward")
         ctx.save_for_backward(z, w, dres, loss_cnt)
         ctx.shape = (B, T, Z, D)
         ctx.mark_non_differentiable(recon)
@@ -199,19 +192,16 @@ class _DecoderNextStepMSE(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_loss, _g_recon):
-        import umlh
-        lib = umlh.load_library()
+        lib = load_library()
         z, w, dres, loss_cnt = ctx.saved_tensors
         B, T, Z, D = ctx.shape
         g = g_loss.detach().to(torch.float32).reshape(1).contiguous()
         dz = torch.empty(B, T, Z, dtype=torch.float32, device=z.device)
         dw = torch.empty(D, Z, dtype=torch.float32, device=z.device)
         db = torch.empty(D, dtype=torch.float32, device=z.device)
-        st = C.c_void_p(torch.cuda.current_stream(z.device).cuda_stream)
-        p = lambda t: C.c_void_p(t.data_ptr())
         scratch = torch.empty(int(lib.umlh_seq_mse_backward_scratch_floats(B, T, Z, D)), dtype=torch.float32, device=z.device)
-        umlh._lib.check(lib.umlh_seq_mse_backward(p(z), p(w), p(dres), p(loss_cnt), p(g), B, T, Z, D, p(dz), p(dw), p(db), p(scratch), st),
-                        "umlh_seq_mse_backward")
+        check(lib.umlh_seq_mse_backward(ptr(z), ptr(w), ptr(dres), ptr(loss_cnt), ptr(g), B, T, Z, D, ptr(dz), ptr(dw), ptr(db), ptr(scratch),
+                                        stream(z.device)), "umlh_seq_mse_backward")
         return dz, dw, db, None, None
 
 
@@ -279,12 +269,8 @@ class UML(nn.Module):
 
     @staticmethod
     def _time_mean(h):
-        import umlh
-        from umlh._lib import check
         h = h.detach().to(torch.float32).contiguous()
         B, T, Z = h.shape
         out = torch.empty(B, Z, dtype=torch.float32, device=h.device)
-        st = C.c_void_p(torch.cuda.current_stream(h.device).cuda_stream)
-        check(umlh.load_library().umlh_positions_backward(C.c_void_p(h.data_ptr()), B, T, Z, C.c_void_p(out.data_ptr()), st),
-              "umlh_positions_backward")
+        check(load_library().umlh_positions_backward(ptr(h), B, T, Z, ptr(out), stream(h.device)), "umlh_positions_backward")
         return out / T

@@ -21,25 +21,6 @@ N_CORE_SCALARS = 8
 N_SCALARS = 12
 
 SOURCES = ["umlh_p2p.hip", "umlh_kernels_f32.hip", "umlh_kernels_bf16.hip", "umlh_kernels_micro.hip", "umlh_kernels_seq.hip", "umlh_kernels_enc.hip", "umlh_kernels_align.hip", "umlh_kernels_align_ext.hip", "umlh_kernels_probe.hip", "umlh_kernels_spectral.hip", "umlh_api.cpp", "umlh_encoder.cpp"]
-EXPORTS = ["umlh_last_error", "umlh_version", "umlh_enable_diagnostics", "umlh_set_diagnostic_columns", "umlh_freeze_proj_row", "umlh_workspace_bytes", "umlh_create", "umlh_destroy", "umlh_bind",
-           "umlh_zero_shot_init", "umlh_logits", "umlh_train_step", "umlh_grad_step", "umlh_grad_buffer",
-           "umlh_apply_update", "umlh_eval_batch", "umlh_eval_rows", "umlh_project", "umlh_optimizer_step",
-           "umlh_profile_enable", "umlh_profile_read", "umlh_to_bf16",
-           "umlh_train_steps", "umlh_train_steps_grouped", "umlh_micro_status", "umlh_micro_launches", "umlh_step_status", "umlh_step_launches", "umlh_p2p_region_bytes", "umlh_p2p_alloc", "umlh_p2p_free", "umlh_p2p_export", "umlh_p2p_open", "umlh_p2p_close", "umlh_p2p_attach", "umlh_comm_unique_id", "umlh_comm_init_rank",
-           "umlh_set_comm", "umlh_set_allreduce", "umlh_seq_mse_forward", "umlh_seq_mse_backward", "umlh_seq_mse_backward_scratch_floats", "umlh_infonce_forward", "umlh_infonce_backward",
-           "umlh_random_permutation", "umlh_debug_buffer",
-           "umlh_gemm_f32", "umlh_add_inplace", "umlh_bias_act", "umlh_relu_backward", "umlh_dropout", "umlh_colsum",
-           "umlh_add_layernorm_forward", "umlh_layernorm_backward", "umlh_add_positions", "umlh_positions_backward",
-           "umlh_gather_rows", "umlh_attention_forward", "umlh_attention_backward", "umlh_optimizer_step_multi",
-           "umlh_encoder_layer_saved_floats", "umlh_encoder_layer_scratch_floats", "umlh_encoder_layer_forward",
-           "umlh_encoder_layer_backward", "umlh_encoder_stack_forward", "umlh_encoder_stack_backward",
-           "umlh_encoder_plan_floats", "umlh_encoder_plan_create", "umlh_encoder_plan_offsets", "umlh_encoder_plan_forward",
-           "umlh_encoder_plan_backward", "umlh_encoder_plan_destroy",
-           "umlh_align_scratch_bytes", "umlh_align_knn", "umlh_align_mutual_knn", "umlh_align_cka",
-           "umlh_align_ext_scratch_bytes", "umlh_align_cka_unbiased", "umlh_align_cka_rbf", "umlh_align_cknna", "umlh_align_list_stats",
-           "umlh_masked_mean", "umlh_probe_scratch_bytes", "umlh_probe_column_stats", "umlh_probe_fit", "umlh_probe_score",
-           "umlh_spectral_scratch_bytes", "umlh_svdvals", "umlh_effective_rank", "umlh_effective_rank_seq",
-           "umlh_subspace_scratch_bytes", "umlh_principal_subspace", "umlh_svcca"]
 
 
 class UmlhError(RuntimeError):
@@ -90,6 +71,127 @@ class Hyper(C.Structure):
                 ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
+def _prototypes() -> dict:
+    """name -> (restype, argtypes) of every declaration of include/umlh.h, in the header's order and sections.
+    tests/test_abi_cpu.py parses the header and holds this table to it, both ways."""
+    rc, vp, i32, i64, u64, f32, f64 = C.c_int, C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_double
+    P, pv = C.POINTER, C.POINTER(C.c_void_p)
+    cfg, batch, hyper, stream, enc = P(Config), P(Batch), P(Hyper), P(Stream), P(EncLayer)
+    return {
+        "umlh_last_error": (C.c_char_p, ()),
+        "umlh_version": (rc, ()),
+        # handle
+        "umlh_workspace_bytes": (u64, (cfg,)),
+        "umlh_create": (rc, (cfg, pv)),
+        "umlh_destroy": (rc, (vp,)),
+        "umlh_bind": (rc, (vp, P(Buffers))),
+        "umlh_enable_diagnostics": (rc, (vp, i32)),
+        "umlh_set_diagnostic_columns": (rc, (vp, i32)),
+        "umlh_freeze_proj_row": (rc, (vp, i32)),
+        # forward pieces and the fused step
+        "umlh_zero_shot_init": (rc, (vp, vp, vp, i64, vp)),
+        "umlh_logits": (rc, (vp, batch, C.c_int, vp, vp)),
+        "umlh_project": (rc, (vp, batch, vp, vp)),
+        "umlh_train_step": (rc, (vp, batch, batch, hyper, vp, vp)),
+        # multi-step, grouped and micro-step launches
+        "umlh_train_steps": (rc, (vp, stream, stream, i32, P(f64), i64, f32, f32, vp, vp)),
+        "umlh_train_steps_grouped": (rc, (P(GroupItem), i32, i32, vp)),
+        "umlh_micro_status": (rc, (vp, P(i32))),
+        "umlh_micro_launches": (rc, (vp, P(i64))),
+        "umlh_step_status": (rc, (vp, P(i32))),
+        # peer-to-peer all-reduce
+        "umlh_p2p_region_bytes": (u64, (i64, i32)),
+        "umlh_p2p_alloc": (rc, (u64, pv)),
+        "umlh_p2p_free": (rc, (vp,)),
+        "umlh_p2p_export": (rc, (vp, vp)),
+        "umlh_p2p_open": (rc, (vp, pv)),
+        "umlh_p2p_close": (rc, (vp,)),
+        "umlh_p2p_attach": (rc, (vp, pv, i32, i32)),
+        "umlh_step_launches": (rc, (vp, P(i64))),
+        # data-parallel transport and split step
+        "umlh_comm_unique_id": (rc, (vp,)),
+        "umlh_comm_init_rank": (rc, (vp, vp, i32, i32)),
+        "umlh_set_comm": (rc, (vp, vp, i32)),
+        "umlh_set_allreduce": (rc, (vp, ALLREDUCE_FN, vp, i32)),
+        "umlh_grad_step": (rc, (vp, batch, batch, hyper, vp)),
+        "umlh_grad_buffer": (rc, (vp, pv, P(u64))),
+        "umlh_debug_buffer": (rc, (vp, pv, P(u64))),
+        "umlh_apply_update": (rc, (vp, hyper, vp, vp)),
+        # evaluation, profiling, bf16 shadow
+        "umlh_eval_batch": (rc, (vp, batch, vp, vp)),
+        "umlh_eval_rows": (rc, (vp, batch, vp, vp)),
+        "umlh_profile_enable": (rc, (vp, C.c_int)),
+        "umlh_profile_read": (rc, (vp, P(f32))),
+        "umlh_to_bf16": (rc, (vp, vp, i64, vp)),
+        # MultiBench critics: next-step MSE decoder, InfoNCE
+        "umlh_seq_mse_forward": (rc, (vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp)),
+        "umlh_seq_mse_backward": (rc, (vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp)),
+        "umlh_seq_mse_backward_scratch_floats": (u64, (i32, i32, i32, i32)),
+        "umlh_infonce_forward": (rc, (vp, vp, i32, i32, f32, vp, vp, vp, vp, vp, vp, vp)),
+        "umlh_infonce_backward": (rc, (vp, vp, vp, vp, vp, i32, i32, f32, vp, vp, vp)),
+        # MultiBench shared encoder: ops
+        "umlh_gemm_f32": (rc, (vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, f32, i32, vp, vp)),
+        "umlh_bias_act": (rc, (vp, vp, i64, i32, i32, vp)),
+        "umlh_relu_backward": (rc, (vp, vp, i64, vp)),
+        "umlh_dropout": (rc, (vp, i64, f32, u64, vp)),
+        "umlh_add_inplace": (rc, (vp, vp, i64, vp)),
+        "umlh_colsum": (rc, (vp, i32, i32, vp, vp)),
+        "umlh_add_layernorm_forward": (rc, (vp, vp, vp, vp, i32, i32, f32, vp, vp, vp, vp, vp)),
+        "umlh_layernorm_backward": (rc, (vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp)),
+        "umlh_add_positions": (rc, (vp, vp, i32, i32, i32, vp)),
+        "umlh_positions_backward": (rc, (vp, i32, i32, i32, vp, vp)),
+        "umlh_gather_rows": (rc, (vp, vp, i32, i32, vp, i32, vp)),
+        "umlh_attention_forward": (rc, (vp, vp, i32, i32, i32, i32, f32, u64, vp, vp, vp)),
+        "umlh_attention_backward": (rc, (vp, vp, vp, vp, i32, i32, i32, i32, f32, u64, vp, vp)),
+        # MultiBench shared encoder: layer, stack, plan
+        "umlh_encoder_layer_saved_floats": (u64, (enc,)),
+        "umlh_encoder_layer_scratch_floats": (u64, (enc,)),
+        "umlh_encoder_layer_forward": (rc, (enc, pv, vp, vp, vp, vp, vp, vp)),
+        "umlh_encoder_layer_backward": (rc, (enc, pv, vp, vp, vp, vp, vp, pv, vp, vp)),
+        "umlh_encoder_stack_forward": (rc, (enc, i32, pv, vp, vp, vp, vp, vp, vp)),
+        "umlh_encoder_stack_backward": (rc, (enc, i32, pv, vp, vp, vp, vp, vp, vp, pv, vp, vp, vp)),
+        "umlh_encoder_plan_floats": (u64, (enc, i32)),
+        "umlh_encoder_plan_create": (rc, (enc, i32, pv, i32, vp, pv)),
+        "umlh_encoder_plan_offsets": (rc, (vp, P(u64))),
+        "umlh_encoder_plan_forward": (rc, (vp, u64, vp)),
+        "umlh_encoder_plan_backward": (rc, (vp, vp)),
+        "umlh_encoder_plan_destroy": (None, (vp,)),
+        # permutation, standalone optimizer
+        "umlh_random_permutation": (rc, (i64, u64, vp, vp)),
+        "umlh_optimizer_step": (rc, (i32, vp, vp, vp, vp, i64, f64, i64, f64, f64, f64, f64, f64, vp)),
+        "umlh_optimizer_step_multi": (rc, (i32, i32, pv, pv, pv, pv, P(i64), f64, i64, f64, f64, f64, f64, f64, vp)),
+        # alignment metrics
+        "umlh_align_scratch_bytes": (u64, (i64, i32, i32, i32, i32)),
+        "umlh_align_knn": (rc, (vp, i64, i32, i32, i32, i32, vp, vp, vp, u64, vp)),
+        "umlh_align_mutual_knn": (rc, (vp, vp, i64, i32, vp, vp, u64, vp)),
+        "umlh_align_cka": (rc, (vp, i32, i32, vp, i32, i32, i64, i32, vp, vp, u64, vp)),
+        "umlh_align_ext_scratch_bytes": (u64, (i32, i64, i32, i32, i32, i32)),
+        "umlh_align_cka_unbiased": (rc, (vp, i32, i32, vp, i32, i32, i64, i32, vp, vp, u64, vp)),
+        "umlh_align_cka_rbf": (rc, (vp, i32, i32, vp, i32, i32, i64, f64, i32, i32, vp, vp, u64, vp)),
+        "umlh_align_cknna": (rc, (vp, vp, vp, vp, i64, i32, vp, vp, u64, vp)),
+        "umlh_align_list_stats": (rc, (vp, vp, i64, i32, vp, vp, vp, u64, vp)),
+        # linear probes
+        "umlh_masked_mean": (rc, (vp, i32, i32, i32, i64, i64, vp, vp, i32, vp)),
+        "umlh_probe_scratch_bytes": (u64, (i64, i32, i32)),
+        "umlh_probe_column_stats": (rc, (vp, i64, i32, i32, vp, vp, u64, vp)),
+        "umlh_probe_fit": (rc, (vp, i64, i32, i32, vp, vp, i32, f64, i32, f64, vp, vp, vp, vp, u64, vp)),
+        "umlh_probe_score": (rc, (vp, i64, i32, i32, vp, vp, vp, vp, vp, vp)),
+        # singular values and effective rank
+        "umlh_spectral_scratch_bytes": (u64, (i32, i64, i32)),
+        "umlh_svdvals": (rc, (vp, i32, i64, i32, i64, i64, vp, vp, u64, vp)),
+        "umlh_effective_rank": (rc, (vp, i32, i64, i32, i64, i64, f64, vp, vp, vp, u64, vp)),
+        "umlh_effective_rank_seq": (rc, (vp, i32, i32, i32, i64, i64, vp, i32, f64, vp, vp, vp, u64, vp)),
+        # principal subspaces and SVCCA
+        "umlh_subspace_scratch_bytes": (u64, (i64, i32, i32, i32)),
+        "umlh_principal_subspace": (rc, (vp, i64, i32, i64, i32, i32, vp, vp, vp, u64, vp)),
+        "umlh_svcca": (rc, (vp, vp, i64, i32, i32, i64, i64, i32, vp, vp, vp, vp, u64, vp)),
+    }
+
+
+PROTOTYPES = _prototypes()
+EXPORTS = list(PROTOTYPES)
+
+
 def lib_path() -> str:
     return _SO
 
@@ -128,124 +230,9 @@ def load_library():
         raise UmlhError(f"{_SO} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                         "(hipcc --offload-arch=gfx950). The HIP extension is mandatory; there is no CPU fallback.")
     lib = C.CDLL(_SO)
-    vp, i32, i64, u64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64
-    lib.umlh_last_error.restype = C.c_char_p
-    lib.umlh_last_error.argtypes = []
-    lib.umlh_version.restype = C.c_int
-    lib.umlh_workspace_bytes.restype = u64
-    lib.umlh_workspace_bytes.argtypes = [C.POINTER(Config)]
-    lib.umlh_create.argtypes = [C.POINTER(Config), C.POINTER(vp)]
-    lib.umlh_destroy.argtypes = [vp]
-    lib.umlh_bind.argtypes = [vp, C.POINTER(Buffers)]
-    lib.umlh_enable_diagnostics.argtypes = [vp, C.c_int32]
-    lib.umlh_set_diagnostic_columns.argtypes = [vp, C.c_int32]
-    lib.umlh_freeze_proj_row.argtypes = [vp, C.c_int32]
-    lib.umlh_eval_rows.argtypes = [vp, C.POINTER(Batch), vp, vp]
-    i32, f32 = C.c_int32, C.c_float
-    lib.umlh_gemm_f32.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, f32, i32, vp, vp]
-    lib.umlh_bias_act.argtypes = [vp, vp, i64, i32, i32, vp]
-    lib.umlh_add_inplace.argtypes = [vp, vp, i64, vp]
-    lib.umlh_relu_backward.argtypes = [vp, vp, i64, vp]
-    lib.umlh_dropout.argtypes = [vp, i64, f32, u64, vp]
-    lib.umlh_colsum.argtypes = [vp, i32, i32, vp, vp]
-    lib.umlh_add_layernorm_forward.argtypes = [vp, vp, vp, vp, i32, i32, f32, vp, vp, vp, vp, vp]
-    lib.umlh_layernorm_backward.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
-    lib.umlh_add_positions.argtypes = [vp, vp, i32, i32, i32, vp]
-    lib.umlh_positions_backward.argtypes = [vp, i32, i32, i32, vp, vp]
-    lib.umlh_gather_rows.argtypes = [vp, vp, i32, i32, vp, i32, vp]
-    lib.umlh_attention_forward.argtypes = [vp, vp, i32, i32, i32, i32, f32, u64, vp, vp, vp]
-    lib.umlh_attention_backward.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, f32, u64, vp, vp]
-    lib.umlh_zero_shot_init.argtypes = [vp, vp, vp, i64, vp]
-    lib.umlh_logits.argtypes = [vp, C.POINTER(Batch), C.c_int, vp, vp]
-    lib.umlh_train_step.argtypes = [vp, C.POINTER(Batch), C.POINTER(Batch), C.POINTER(Hyper), vp, vp]
-    lib.umlh_grad_step.argtypes = [vp, C.POINTER(Batch), C.POINTER(Batch), C.POINTER(Hyper), vp]
-    lib.umlh_grad_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
-    lib.umlh_apply_update.argtypes = [vp, C.POINTER(Hyper), vp, vp]
-    lib.umlh_eval_batch.argtypes = [vp, C.POINTER(Batch), vp, vp]
-    lib.umlh_project.argtypes = [vp, C.POINTER(Batch), vp, vp]
-    lib.umlh_optimizer_step.argtypes = [i32, vp, vp, vp, vp, i64, C.c_double, i64, C.c_double, C.c_double,
-                                        C.c_double, C.c_double, C.c_double, vp]
-    lib.umlh_to_bf16.argtypes = [vp, vp, i64, vp]
-    pv = C.POINTER(vp)
-    lib.umlh_optimizer_step_multi.argtypes = [i32, i32, pv, pv, pv, pv, C.POINTER(i64), C.c_double, i64, C.c_double, C.c_double,
-                                              C.c_double, C.c_double, C.c_double, vp]
-    lib.umlh_encoder_layer_saved_floats.restype = u64
-    lib.umlh_encoder_layer_saved_floats.argtypes = [C.POINTER(EncLayer)]
-    lib.umlh_encoder_layer_scratch_floats.restype = u64
-    lib.umlh_encoder_layer_scratch_floats.argtypes = [C.POINTER(EncLayer)]
-    lib.umlh_encoder_layer_forward.argtypes = [C.POINTER(EncLayer), pv, vp, vp, vp, vp, vp, vp]
-    lib.umlh_encoder_layer_backward.argtypes = [C.POINTER(EncLayer), pv, vp, vp, vp, vp, vp, pv, vp, vp]
-    lib.umlh_encoder_stack_forward.argtypes = [C.POINTER(EncLayer), i32, pv, vp, vp, vp, vp, vp, vp]
-    lib.umlh_encoder_stack_backward.argtypes = [C.POINTER(EncLayer), i32, pv, vp, vp, vp, vp, vp, vp, pv, vp, vp, vp]
-    lib.umlh_encoder_plan_floats.restype = u64
-    lib.umlh_encoder_plan_floats.argtypes = [C.POINTER(EncLayer), i32]
-    lib.umlh_encoder_plan_create.argtypes = [C.POINTER(EncLayer), i32, pv, i32, vp, C.POINTER(vp)]
-    lib.umlh_encoder_plan_offsets.argtypes = [vp, C.POINTER(u64)]
-    lib.umlh_encoder_plan_forward.argtypes = [vp, u64, vp]
-    lib.umlh_encoder_plan_backward.argtypes = [vp, vp]
-    lib.umlh_encoder_plan_destroy.restype = None
-    lib.umlh_encoder_plan_destroy.argtypes = [vp]
-    lib.umlh_train_steps.argtypes = [vp, C.POINTER(Stream), C.POINTER(Stream), i32, C.POINTER(C.c_double), i64,
-                                     C.c_float, C.c_float, vp, vp]
-    lib.umlh_train_steps_grouped.argtypes = [C.POINTER(GroupItem), i32, i32, vp]
-    lib.umlh_micro_status.argtypes = [vp, C.POINTER(C.c_int32)]
-    lib.umlh_micro_launches.argtypes = [vp, C.POINTER(C.c_int64)]
-    lib.umlh_step_status.argtypes = [vp, C.POINTER(C.c_int32)]
-    lib.umlh_step_launches.argtypes = [vp, C.POINTER(C.c_int64)]
-    lib.umlh_p2p_region_bytes.restype = u64
-    lib.umlh_p2p_region_bytes.argtypes = [i64, i32]
-    lib.umlh_p2p_alloc.argtypes = [u64, C.POINTER(vp)]
-    lib.umlh_p2p_free.argtypes = [vp]
-    lib.umlh_p2p_export.argtypes = [vp, vp]
-    lib.umlh_p2p_open.argtypes = [vp, C.POINTER(vp)]
-    lib.umlh_p2p_close.argtypes = [vp]
-    lib.umlh_p2p_attach.argtypes = [vp, C.POINTER(vp), i32, i32]
-    lib.umlh_comm_unique_id.argtypes = [vp]
-    lib.umlh_comm_init_rank.argtypes = [vp, vp, i32, i32]
-    lib.umlh_set_comm.argtypes = [vp, vp, i32]
-    lib.umlh_set_allreduce.argtypes = [vp, ALLREDUCE_FN, vp, i32]
-    lib.umlh_seq_mse_forward.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
-    lib.umlh_seq_mse_backward.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
-    lib.umlh_infonce_forward.argtypes = [vp, vp, i32, i32, C.c_float, vp, vp, vp, vp, vp, vp, vp]
-    lib.umlh_infonce_backward.argtypes = [vp, vp, vp, vp, vp, i32, i32, C.c_float, vp, vp, vp]
-    lib.umlh_seq_mse_backward_scratch_floats.restype = u64
-    lib.umlh_seq_mse_backward_scratch_floats.argtypes = [i32, i32, i32, i32]
-    lib.umlh_random_permutation.argtypes = [i64, u64, vp, vp]
-    lib.umlh_debug_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
-    lib.umlh_align_scratch_bytes.restype = u64
-    lib.umlh_align_scratch_bytes.argtypes = [i64, i32, i32, i32, i32]
-    lib.umlh_align_knn.argtypes = [vp, i64, i32, i32, i32, i32, vp, vp, vp, u64, vp]
-    lib.umlh_align_mutual_knn.argtypes = [vp, vp, i64, i32, vp, vp, u64, vp]
-    lib.umlh_align_cka.argtypes = [vp, i32, i32, vp, i32, i32, i64, i32, vp, vp, u64, vp]
-    lib.umlh_align_ext_scratch_bytes.restype = u64
-    lib.umlh_align_ext_scratch_bytes.argtypes = [i32, i64, i32, i32, i32, i32]
-    lib.umlh_align_cka_unbiased.argtypes = [vp, i32, i32, vp, i32, i32, i64, i32, vp, vp, u64, vp]
-    lib.umlh_align_cka_rbf.argtypes = [vp, i32, i32, vp, i32, i32, i64, C.c_double, i32, i32, vp, vp, u64, vp]
-    lib.umlh_align_cknna.argtypes = [vp, vp, vp, vp, i64, i32, vp, vp, u64, vp]
-    lib.umlh_align_list_stats.argtypes = [vp, vp, i64, i32, vp, vp, vp, u64, vp]
-    lib.umlh_masked_mean.argtypes = [vp, i32, i32, i32, i64, i64, vp, vp, i32, vp]
-    lib.umlh_probe_scratch_bytes.restype = u64
-    lib.umlh_probe_scratch_bytes.argtypes = [i64, i32, i32]
-    lib.umlh_probe_column_stats.argtypes = [vp, i64, i32, i32, vp, vp, u64, vp]
-    lib.umlh_probe_fit.argtypes = [vp, i64, i32, i32, vp, vp, i32, C.c_double, i32, C.c_double, vp, vp, vp, vp, u64, vp]
-    lib.umlh_probe_score.argtypes = [vp, i64, i32, i32, vp, vp, vp, vp, vp, vp]
-    lib.umlh_spectral_scratch_bytes.restype = u64
-    lib.umlh_spectral_scratch_bytes.argtypes = [i32, i64, i32]
-    lib.umlh_svdvals.argtypes = [vp, i32, i64, i32, i64, i64, vp, vp, u64, vp]
-    lib.umlh_effective_rank.argtypes = [vp, i32, i64, i32, i64, i64, C.c_double, vp, vp, vp, u64, vp]
-    lib.umlh_effective_rank_seq.argtypes = [vp, i32, i32, i32, i64, i64, vp, i32, C.c_double, vp, vp, vp, u64, vp]
-    lib.umlh_subspace_scratch_bytes.restype = u64
-    lib.umlh_subspace_scratch_bytes.argtypes = [i64, i32, i32, i32]
-    lib.umlh_principal_subspace.argtypes = [vp, i64, i32, i64, i32, i32, vp, vp, vp, u64, vp]
-    lib.umlh_svcca.argtypes = [vp, vp, i64, i32, i32, i64, i64, i32, vp, vp, vp, vp, u64, vp]
-    lib.umlh_profile_enable.argtypes = [vp, C.c_int]
-    lib.umlh_profile_read.argtypes = [vp, C.POINTER(C.c_float)]
-    for name in EXPORTS:
+    for name, (restype, argtypes) in PROTOTYPES.items():
         fn = getattr(lib, name)
-        if name not in ("umlh_last_error", "umlh_workspace_bytes", "umlh_encoder_layer_saved_floats", "umlh_encoder_layer_scratch_floats",
-                        "umlh_align_scratch_bytes", "umlh_align_ext_scratch_bytes", "umlh_probe_scratch_bytes",
-                        "umlh_spectral_scratch_bytes", "umlh_subspace_scratch_bytes"):
-            fn.restype = C.c_int
+        fn.restype, fn.argtypes = restype, list(argtypes)
     _LIB = lib
     return lib
 

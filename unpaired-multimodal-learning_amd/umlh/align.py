@@ -16,45 +16,19 @@ docstring and DESIGN section 13.  ``measure("svcca", ...)`` is not routed to it 
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 import torch
 
+from . import _glue as glue
 from . import spectral
-from ._lib import UmlhError, check, load_library
+from ._lib import check, load_library
 
 MAX_TOPK = 32
 
 
 def _device() -> torch.device:
-    if not torch.cuda.is_available():
-        raise RuntimeError("umlh.align needs a GPU: the metrics run only as HIP kernels")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _features(t: torch.Tensor, what: str, dev: torch.device) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor) or t.ndim != 2:
-        raise ValueError(f"{what}: expected a 2-D tensor [N, d], got {getattr(t, 'shape', type(t))}")
-    if not t.is_floating_point():
-        raise ValueError(f"{what}: expected a floating-point tensor, got {t.dtype}")
-    if t.shape[0] < 1 or t.shape[1] < 1:
-        raise ValueError(f"{what}: empty features {tuple(t.shape)}")
-    t = t.detach().to(device=dev, dtype=torch.float32)
-    if t.stride(1) != 1 or t.stride(0) < t.shape[1]:
-        t = t.contiguous()
-    return t
-
-
-def _stream(dev: torch.device):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _scratch(lib, n, d_a, d_b, topk, splits, dev):
-    nbytes = lib.umlh_align_scratch_bytes(n, d_a, d_b, topk, splits)
-    if nbytes == 0:
-        raise UmlhError(f"umlh_align_scratch_bytes: invalid arguments n={n} d_a={d_a} d_b={d_b} topk={topk} splits={splits}")
-    return torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes
+    return glue.device("umlh.align", "the metrics run only as HIP kernels")
 
 
 def _check_topk(topk: int, n: int, what: str) -> None:
@@ -62,6 +36,16 @@ def _check_topk(topk: int, n: int, what: str) -> None:
         raise ValueError(f"{what}: topk={topk} outside 1..{MAX_TOPK}")
     if topk >= n:
         raise ValueError(f"{what}: topk={topk} needs more than topk rows (got N={n})")
+
+
+def _check_pair(a, b, what: str, splits: int, min_rows: int = 1) -> None:
+    if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor)) or a.ndim != 2 or b.ndim != 2 or a.shape[0] != b.shape[0]:
+        raise ValueError(f"{what}: features of shapes {tuple(getattr(a, 'shape', ()))} and {tuple(getattr(b, 'shape', ()))} "
+                         "(need 2-D with the same N)")
+    if splits < 0:
+        raise ValueError(f"{what}: splits={splits} < 0")
+    if a.shape[0] < min_rows:
+        raise ValueError(f"{what}: N={a.shape[0]} rows, the unbiased HSIC divides by N - 3 (need N >= {min_rows})")
 
 
 def knn(feats: torch.Tensor, topk: int, splits: int = 0, return_scores: bool = False):
@@ -74,15 +58,14 @@ def knn(feats: torch.Tensor, topk: int, splits: int = 0, return_scores: bool = F
     if splits < 0:
         raise ValueError(f"knn: splits={splits} < 0")
     dev = _device()
-    x = _features(feats, "knn", dev)
+    x = glue.features(feats, "knn", dev)
     lib = load_library()
     d = x.shape[1]
-    scratch, nbytes = _scratch(lib, n, d, d, topk, splits, dev)
+    scratch, nbytes = glue.scratch("umlh_align_scratch_bytes", dev, n=n, d_a=d, d_b=d, topk=topk, splits=splits)
     out = torch.empty((n, topk), dtype=torch.int32, device=dev)
     scores = torch.empty((n, topk), dtype=torch.float32, device=dev) if return_scores else None
-    check(lib.umlh_align_knn(x.data_ptr(), n, d, x.stride(0), topk, splits, out.data_ptr(),
-                             scores.data_ptr() if scores is not None else None, scratch.data_ptr(), nbytes, _stream(dev)),
-          "umlh_align_knn")
+    check(lib.umlh_align_knn(x.data_ptr(), n, d, x.stride(0), topk, splits, out.data_ptr(), glue.ptr(scores), scratch.data_ptr(),
+                             nbytes, glue.stream(dev)), "umlh_align_knn")
     return (out, scores) if return_scores else out
 
 
@@ -96,37 +79,31 @@ def mutual_knn_lists(knn_a: torch.Tensor, knn_b: torch.Tensor) -> torch.Tensor:
     ka = knn_a.to(device=dev, dtype=torch.int32).contiguous()
     kb = knn_b.to(device=dev, dtype=torch.int32).contiguous()
     lib = load_library()
-    scratch, nbytes = _scratch(lib, n, 1, 1, 0, 0, dev)
+    scratch, nbytes = glue.scratch("umlh_align_scratch_bytes", dev, n=n, d_a=1, d_b=1, topk=0, splits=0)
     out = torch.empty((), dtype=torch.float64, device=dev)
     check(lib.umlh_align_mutual_knn(ka.data_ptr(), kb.data_ptr(), n, topk, out.data_ptr(), scratch.data_ptr(), nbytes,
-                                    _stream(dev)), "umlh_align_mutual_knn")
+                                    glue.stream(dev)), "umlh_align_mutual_knn")
     return out
 
 
 def mutual_knn(a: torch.Tensor, b: torch.Tensor, topk: int = 10, splits: int = 0) -> torch.Tensor:
     """AlignmentMetrics.mutual_knn(a, b, topk): a 0-d float64 device tensor."""
-    if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor)) or a.ndim != 2 or b.ndim != 2 or a.shape[0] != b.shape[0]:
-        raise ValueError(f"mutual_knn: features of shapes {tuple(getattr(a, 'shape', ()))} and {tuple(getattr(b, 'shape', ()))} "
-                         "(need 2-D with the same N)")
+    _check_pair(a, b, "mutual_knn", splits)
     _check_topk(int(topk), a.shape[0], "mutual_knn")
     return mutual_knn_lists(knn(a, topk, splits), knn(b, topk, splits))
 
 
 def cka_terms(a: torch.Tensor, b: torch.Tensor, splits: int = 0) -> torch.Tensor:
     """float64 device tensor [4] = {cka, hsic_kl, hsic_kk, hsic_ll} (biased HSIC, linear kernel, no normalisation)."""
-    if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor)) or a.ndim != 2 or b.ndim != 2 or a.shape[0] != b.shape[0]:
-        raise ValueError(f"cka: features of shapes {tuple(getattr(a, 'shape', ()))} and {tuple(getattr(b, 'shape', ()))} "
-                         "(need 2-D with the same N)")
-    if splits < 0:
-        raise ValueError(f"cka: splits={splits} < 0")
+    _check_pair(a, b, "cka", splits)
     dev = _device()
-    xa, xb = _features(a, "cka", dev), _features(b, "cka", dev)
+    xa, xb = glue.features(a, "cka", dev), glue.features(b, "cka", dev)
     n = xa.shape[0]
     lib = load_library()
-    scratch, nbytes = _scratch(lib, n, xa.shape[1], xb.shape[1], 0, splits, dev)
+    scratch, nbytes = glue.scratch("umlh_align_scratch_bytes", dev, n=n, d_a=xa.shape[1], d_b=xb.shape[1], topk=0, splits=splits)
     out = torch.empty(4, dtype=torch.float64, device=dev)
     check(lib.umlh_align_cka(xa.data_ptr(), xa.stride(0), xa.shape[1], xb.data_ptr(), xb.stride(0), xb.shape[1], n, splits,
-                             out.data_ptr(), scratch.data_ptr(), nbytes, _stream(dev)), "umlh_align_cka")
+                             out.data_ptr(), scratch.data_ptr(), nbytes, glue.stream(dev)), "umlh_align_cka")
     return out
 
 
@@ -139,35 +116,18 @@ def cka(a: torch.Tensor, b: torch.Tensor, splits: int = 0) -> torch.Tensor:
 KIND_CKA_UNBIASED, KIND_CKA_RBF, KIND_CKNNA, KIND_LIST_STATS = range(4)
 
 
-def _ext_scratch(lib, kind, n, d_a, d_b, topk, splits, dev):
-    nbytes = lib.umlh_align_ext_scratch_bytes(kind, n, d_a, d_b, topk, splits)
-    if nbytes == 0:
-        raise UmlhError(f"umlh_align_ext_scratch_bytes: invalid arguments kind={kind} n={n} d_a={d_a} d_b={d_b} topk={topk} "
-                        f"splits={splits}")
-    return torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes
-
-
-def _check_pair(a, b, what: str, splits: int, min_rows: int = 1) -> None:
-    if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor)) or a.ndim != 2 or b.ndim != 2 or a.shape[0] != b.shape[0]:
-        raise ValueError(f"{what}: features of shapes {tuple(getattr(a, 'shape', ()))} and {tuple(getattr(b, 'shape', ()))} "
-                         "(need 2-D with the same N)")
-    if splits < 0:
-        raise ValueError(f"{what}: splits={splits} < 0")
-    if a.shape[0] < min_rows:
-        raise ValueError(f"{what}: N={a.shape[0]} rows, the unbiased HSIC divides by N - 3 (need N >= {min_rows})")
-
-
 def unbiased_cka_terms(a: torch.Tensor, b: torch.Tensor, splits: int = 0) -> torch.Tensor:
     """float64 device tensor [4] = {cka, hsic_kl, hsic_kk, hsic_ll} with the unbiased HSIC of the linear kernel."""
     _check_pair(a, b, "unbiased_cka", splits, 4)
     dev = _device()
-    xa, xb = _features(a, "unbiased_cka", dev), _features(b, "unbiased_cka", dev)
+    xa, xb = glue.features(a, "unbiased_cka", dev), glue.features(b, "unbiased_cka", dev)
     n = xa.shape[0]
     lib = load_library()
-    scratch, nbytes = _ext_scratch(lib, KIND_CKA_UNBIASED, n, xa.shape[1], xb.shape[1], 0, splits, dev)
+    scratch, nbytes = glue.scratch("umlh_align_ext_scratch_bytes", dev, kind=KIND_CKA_UNBIASED, n=n, d_a=xa.shape[1], d_b=xb.shape[1],
+                                   topk=0, splits=splits)
     out = torch.empty(4, dtype=torch.float64, device=dev)
     check(lib.umlh_align_cka_unbiased(xa.data_ptr(), xa.stride(0), xa.shape[1], xb.data_ptr(), xb.stride(0), xb.shape[1], n, splits,
-                                      out.data_ptr(), scratch.data_ptr(), nbytes, _stream(dev)), "umlh_align_cka_unbiased")
+                                      out.data_ptr(), scratch.data_ptr(), nbytes, glue.stream(dev)), "umlh_align_cka_unbiased")
     return out
 
 
@@ -183,13 +143,14 @@ def rbf_cka_terms(a: torch.Tensor, b: torch.Tensor, sigma: float = 1.0, unbiased
     if not (sigma > 0.0 and math.isfinite(sigma)):
         raise ValueError(f"rbf_cka: sigma={sigma} (need a finite sigma > 0)")
     dev = _device()
-    xa, xb = _features(a, "rbf_cka", dev), _features(b, "rbf_cka", dev)
+    xa, xb = glue.features(a, "rbf_cka", dev), glue.features(b, "rbf_cka", dev)
     n = xa.shape[0]
     lib = load_library()
-    scratch, nbytes = _ext_scratch(lib, KIND_CKA_RBF, n, xa.shape[1], xb.shape[1], 0, splits, dev)
+    scratch, nbytes = glue.scratch("umlh_align_ext_scratch_bytes", dev, kind=KIND_CKA_RBF, n=n, d_a=xa.shape[1], d_b=xb.shape[1],
+                                   topk=0, splits=splits)
     out = torch.empty(4, dtype=torch.float64, device=dev)
     check(lib.umlh_align_cka_rbf(xa.data_ptr(), xa.stride(0), xa.shape[1], xb.data_ptr(), xb.stride(0), xb.shape[1], n, sigma,
-                                 int(bool(unbiased)), splits, out.data_ptr(), scratch.data_ptr(), nbytes, _stream(dev)),
+                                 int(bool(unbiased)), splits, out.data_ptr(), scratch.data_ptr(), nbytes, glue.stream(dev)),
           "umlh_align_cka_rbf")
     return out
 
@@ -217,10 +178,10 @@ def cknna_terms(a: torch.Tensor, b: torch.Tensor, topk: int, splits: int = 0) ->
     kb, sb = knn(b, topk, splits, return_scores=True)
     dev = ka.device
     lib = load_library()
-    scratch, nbytes = _ext_scratch(lib, KIND_CKNNA, n, 1, 1, topk, 0, dev)
+    scratch, nbytes = glue.scratch("umlh_align_ext_scratch_bytes", dev, kind=KIND_CKNNA, n=n, d_a=1, d_b=1, topk=topk, splits=0)
     out = torch.empty(4, dtype=torch.float64, device=dev)
     check(lib.umlh_align_cknna(ka.data_ptr(), sa.data_ptr(), kb.data_ptr(), sb.data_ptr(), n, topk, out.data_ptr(),
-                               scratch.data_ptr(), nbytes, _stream(dev)), "umlh_align_cknna")
+                               scratch.data_ptr(), nbytes, glue.stream(dev)), "umlh_align_cknna")
     return out
 
 
@@ -241,11 +202,11 @@ def list_stats(knn_a: torch.Tensor, knn_b: torch.Tensor, return_rows: bool = Fal
     ka = knn_a.to(device=dev, dtype=torch.int32).contiguous()
     kb = knn_b.to(device=dev, dtype=torch.int32).contiguous()
     lib = load_library()
-    scratch, nbytes = _ext_scratch(lib, KIND_LIST_STATS, n, 1, 1, topk, 0, dev)
+    scratch, nbytes = glue.scratch("umlh_align_ext_scratch_bytes", dev, kind=KIND_LIST_STATS, n=n, d_a=1, d_b=1, topk=topk, splits=0)
     out = torch.empty(3, dtype=torch.float64, device=dev)
     rows = torch.empty((n, 3), dtype=torch.int32, device=dev) if return_rows else None
-    check(lib.umlh_align_list_stats(ka.data_ptr(), kb.data_ptr(), n, topk, rows.data_ptr() if rows is not None else None,
-                                    out.data_ptr(), scratch.data_ptr(), nbytes, _stream(dev)), "umlh_align_list_stats")
+    check(lib.umlh_align_list_stats(ka.data_ptr(), kb.data_ptr(), n, topk, glue.ptr(rows), out.data_ptr(), scratch.data_ptr(), nbytes,
+                                    glue.stream(dev)), "umlh_align_list_stats")
     return (out, rows) if return_rows else out
 
 
@@ -296,24 +257,19 @@ def _cknna_any(feats_A, feats_B, topk=None, distance_agnostic=False, unbiased=Tr
 def svcca_terms(a: torch.Tensor, b: torch.Tensor, cca_dim: int = 10):
     """``(value, rho[q], evals[2, q])`` of ``svcca`` with q = cca_dim: the mean canonical correlation (0-d), the canonical
     correlations (descending, clamped to [0, 1]) and the top-q eigenvalues of the two standardised Grams; float64 device tensors."""
-    if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor)) or a.ndim != 2 or b.ndim != 2 or a.shape[0] != b.shape[0]:
-        raise ValueError(f"svcca: features of shapes {tuple(getattr(a, 'shape', ()))} and {tuple(getattr(b, 'shape', ()))} "
-                         "(need 2-D with the same N)")
-    n, d_a = spectral._view(a, "svcca")
-    _, d_b = spectral._view(b, "svcca")
-    q = spectral._check_q(cca_dim, min(n, d_a, d_b), "svcca")
+    _check_pair(a, b, "svcca", 0)
+    n, d_a = spectral.check_view(a, "svcca")
+    _, d_b = spectral.check_view(b, "svcca")
+    q = spectral.check_q(cca_dim, min(n, d_a, d_b), "svcca")
     dev = _device()
-    xa, xb = spectral._rows_in_place(a, dev), spectral._rows_in_place(b, dev)
+    xa, xb = spectral.rows_in_place(a, dev), spectral.rows_in_place(b, dev)
     lib = load_library()
-    nbytes = lib.umlh_subspace_scratch_bytes(n, d_a, d_b, q)
-    if nbytes == 0:
-        raise UmlhError(f"umlh_subspace_scratch_bytes: invalid arguments n={n} d_a={d_a} d_b={d_b} q={q}")
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    scratch, nbytes = glue.scratch("umlh_subspace_scratch_bytes", dev, n=n, d_a=d_a, d_b=d_b, q=q)
     out = torch.empty((), dtype=torch.float64, device=dev)
     rho = torch.empty(q, dtype=torch.float64, device=dev)
     evals = torch.empty((2, q), dtype=torch.float64, device=dev)
     check(lib.umlh_svcca(xa.data_ptr(), xb.data_ptr(), n, d_a, d_b, xa.stride(0), xb.stride(0), q, out.data_ptr(), rho.data_ptr(),
-                         evals.data_ptr(), scratch.data_ptr(), nbytes, _stream(dev)), "umlh_svcca")
+                         evals.data_ptr(), scratch.data_ptr(), nbytes, glue.stream(dev)), "umlh_svcca")
     return out, rho, evals
 
 

@@ -13,6 +13,7 @@ from typing import Optional
 import torch
 
 from . import _lib
+from ._glue import ptr, ptr_array, stream
 from ._lib import Batch, Buffers, Config, Hyper, OPT_IDS, PREC_IDS, N_SCALARS, Stream, UmlhError, check
 
 
@@ -37,10 +38,6 @@ class RowBatch:
         if self.rows is not None:
             return int(self.rows)
         return int(self.index.numel() if self.index is not None else self.feats.shape[0])
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 class HeadEngine:
@@ -119,9 +116,9 @@ class HeadEngine:
                 if cur is not None and tuple(cur.shape) != tuple(v.shape):
                     raise UmlhError(f"rebind({k}): shape {tuple(v.shape)} != {tuple(cur.shape)}")
             setattr(self, k, v)
-        b = Buffers(_ptr(self.w_head), _ptr(self.m_head), _ptr(self.v_head), _ptr(self.w_proj), _ptr(self.m_proj),
-                    _ptr(self.v_proj), _ptr(self.scales), _ptr(self.m_scales), _ptr(self.v_scales),
-                    _ptr(self.workspace), self.workspace.numel() * 4)
+        b = Buffers(ptr(self.w_head), ptr(self.m_head), ptr(self.v_head), ptr(self.w_proj), ptr(self.m_proj),
+                    ptr(self.v_proj), ptr(self.scales), ptr(self.m_scales), ptr(self.v_scales),
+                    ptr(self.workspace), self.workspace.numel() * 4)
         check(self.lib.umlh_bind(self.handle, C.byref(b)), "umlh_bind")
 
     def close(self) -> None:
@@ -136,9 +133,6 @@ class HeadEngine:
             pass
 
     # -- helpers -------------------------------------------------------------------
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def _from_width(self, f, dim):
         """User-visible width of rows headed for a ``dim``-wide operand of a head with bias, or None (no bias / rows that
         already have the engine's width)."""
@@ -201,7 +195,7 @@ class HeadEngine:
                 f16 = b.feats_bf16 = to_bf16(f)
             if f16.dtype != torch.bfloat16 or f16.shape != f.shape or not f16.is_contiguous() or f16.device != self.device:
                 raise UmlhError("feats_bf16 must be a contiguous bf16 tensor shaped like feats on the engine's device")
-        return Batch(_ptr(f), _ptr(y), _ptr(b.index), rows, int(b.global_rows or rows), _ptr(f16))
+        return Batch(ptr(f), ptr(y), ptr(b.index), rows, int(b.global_rows or rows), ptr(f16))
 
     @staticmethod
     def _ref(x):
@@ -216,7 +210,7 @@ class HeadEngine:
         tl = text_labels.to(self.device, torch.int64).contiguous()
         if tf.shape[1] != self.d_shared:
             raise UmlhError(f"text features have dim {tf.shape[1]}, head expects {self.d_shared}")
-        check(self.lib.umlh_zero_shot_init(self.handle, _ptr(tf), _ptr(tl), tf.shape[0], self._stream()),
+        check(self.lib.umlh_zero_shot_init(self.handle, ptr(tf), ptr(tl), tf.shape[0], stream(self.device)),
               "umlh_zero_shot_init")
         torch.cuda.current_stream(self.device).synchronize()   # tf/tl are temporaries
 
@@ -225,7 +219,7 @@ class HeadEngine:
         b = self._batch(batch, dim)
         out = torch.empty(batch.n_rows(), self.num_classes, dtype=torch.float32, device=self.device)
         if b is not None:
-            check(self.lib.umlh_logits(self.handle, C.byref(b), modality, _ptr(out), self._stream()), "umlh_logits")
+            check(self.lib.umlh_logits(self.handle, C.byref(b), modality, ptr(out), stream(self.device)), "umlh_logits")
         return out
 
     def project(self, batch: RowBatch) -> torch.Tensor:
@@ -233,7 +227,7 @@ class HeadEngine:
         b = self._batch(batch, self.d_img)
         out = torch.empty(batch.n_rows(), self.d_shared, dtype=torch.float32, device=self.device)
         if b is not None:
-            check(self.lib.umlh_project(self.handle, C.byref(b), _ptr(out), self._stream()), "umlh_project")
+            check(self.lib.umlh_project(self.handle, C.byref(b), ptr(out), stream(self.device)), "umlh_project")
         return out
 
     def enable_diagnostics(self, on: bool = True) -> None:
@@ -248,8 +242,8 @@ class HeadEngine:
         bi, bt = self._batch(img, self.d_img), self._batch(txt, self.d_shared)
         hy = Hyper(float(lr), int(step), float(alpha), float(img_alpha), 0, 0)
         so = scalars_out if scalars_out is not None else self._scalars
-        check(self.lib.umlh_train_step(self.handle, self._ref(bi), self._ref(bt), C.byref(hy), _ptr(so),
-                                       self._stream()), "umlh_train_step")
+        check(self.lib.umlh_train_step(self.handle, self._ref(bi), self._ref(bt), C.byref(hy), ptr(so),
+                                       stream(self.device)), "umlh_train_step")
         return so
 
     def _make_stream(self, table, batches, dim, cap, n):
@@ -286,7 +280,7 @@ class HeadEngine:
             raise UmlhError("train_steps: index slices do not match their batch sizes")
         offs = offs_np.ctypes.data_as(C.POINTER(C.c_int32))
         keep = (f, y, f16, idx, offs_np)
-        return Stream(_ptr(f), _ptr(f16), _ptr(y), _ptr(idx), offs), keep
+        return Stream(ptr(f), ptr(f16), ptr(y), ptr(idx), offs), keep
 
     def train_steps(self, img_table, img_index_batches, txt_table, txt_index_batches, lrs, first_step: int,
                     alpha: float = 1.0, img_alpha: float = 1.0, scalars_out: Optional[torch.Tensor] = None) -> None:
@@ -315,7 +309,7 @@ class HeadEngine:
             lock.acquire()
         try:
             rc = self.lib.umlh_train_steps(self.handle, self._ref(si), self._ref(st), n, lr_arr, int(first_step),
-                                           float(alpha), float(img_alpha), _ptr(scalars_out), self._stream())
+                                           float(alpha), float(img_alpha), ptr(scalars_out), stream(self.device))
         finally:
             if lock is not None:
                 lock.release()
@@ -366,7 +360,7 @@ class HeadEngine:
         last apply_update/train_step (lets a bf16 engine reuse the weight shadow its update kernel wrote)."""
         bi, bt = self._batch(img, self.d_img), self._batch(txt, self.d_shared)
         hy = Hyper(0.0, 1, float(alpha), float(img_alpha), 1 if weights_unchanged else 0, 0)
-        check(self.lib.umlh_grad_step(self.handle, self._ref(bi), self._ref(bt), C.byref(hy), self._stream()),
+        check(self.lib.umlh_grad_step(self.handle, self._ref(bi), self._ref(bt), C.byref(hy), stream(self.device)),
               "umlh_grad_step")
         return self.grad_buffer()
 
@@ -393,7 +387,7 @@ class HeadEngine:
             bt.index, bt.rows, bt.global_rows = idx_txt.data_ptr(), idx_txt.numel(), global_txt
         hy = self._hy
         hy.alpha, hy.img_alpha, hy.flags = alpha, img_alpha, 1 if weights_unchanged else 0
-        check(self.lib.umlh_grad_step(self.handle, self._ref(bi), self._ref(bt), C.byref(hy), self._stream()),
+        check(self.lib.umlh_grad_step(self.handle, self._ref(bi), self._ref(bt), C.byref(hy), stream(self.device)),
               "umlh_grad_step")
 
     def grad_buffer(self) -> torch.Tensor:
@@ -495,7 +489,7 @@ class HeadEngine:
                      img_alpha: float = 1.0):
         hy = Hyper(float(lr), int(step), float(alpha), float(img_alpha), 0, 0)
         so = scalars_out if scalars_out is not None else self._scalars
-        check(self.lib.umlh_apply_update(self.handle, C.byref(hy), _ptr(so), self._stream()), "umlh_apply_update")
+        check(self.lib.umlh_apply_update(self.handle, C.byref(hy), ptr(so), stream(self.device)), "umlh_apply_update")
         return so
 
     PHASES = ("proj_fwd", "fwd_ce", "dw_head", "proj_bwd", "reduce_update")
@@ -515,13 +509,13 @@ class HeadEngine:
         n = batch.n_rows()
         if out is None:
             out = torch.empty(n, 2, dtype=torch.float32, device=self.device)
-        check(self.lib.umlh_eval_rows(self.handle, self._ref(b), _ptr(out), self._stream()), "umlh_eval_rows")
+        check(self.lib.umlh_eval_rows(self.handle, self._ref(b), ptr(out), stream(self.device)), "umlh_eval_rows")
         return out
 
     def eval_batch(self, batch: RowBatch, scalars_out: Optional[torch.Tensor] = None):
         b = self._batch(batch, self.d_img)
         so = scalars_out if scalars_out is not None else self._scalars
-        check(self.lib.umlh_eval_batch(self.handle, self._ref(b), _ptr(so), self._stream()), "umlh_eval_batch")
+        check(self.lib.umlh_eval_batch(self.handle, self._ref(b), ptr(so), stream(self.device)), "umlh_eval_batch")
         return so
 
 
@@ -546,11 +540,11 @@ def train_steps_grouped(jobs, n_steps: int) -> None:
         so = job.get("scalars_out")
         items[j] = GroupItem(e.handle, C.pointer(si) if si is not None else None, C.pointer(st) if st is not None else None,
                              lr_arr, int(job["first_step"]), float(job.get("alpha", 1.0)), float(job.get("img_alpha", 1.0)),
-                             _ptr(so))
+                             ptr(so))
         keep.append((si, st, ki, kt, lr_arr, so))
         e._keepalive = (ki, kt)
     e0 = jobs[0]["engine"]
-    check(e0.lib.umlh_train_steps_grouped(items, len(jobs), int(n_steps), e0._stream()), "umlh_train_steps_grouped")
+    check(e0.lib.umlh_train_steps_grouped(items, len(jobs), int(n_steps), stream(e0.device)), "umlh_train_steps_grouped")
 
 
 def grad_diagnostics(scalars, n_elements: int, rows_img: int = 1, rows_txt: int = 1) -> dict:
@@ -576,8 +570,8 @@ def gather_rows(x: torch.Tensor, index: torch.Tensor) -> torch.Tensor:
     """out[j] = x[index[j]] for a contiguous fp32 [N, d] device table (``umlh_gather_rows``)."""
     lib = _lib.load_library()
     out = torch.empty(index.numel(), x.shape[1], dtype=torch.float32, device=x.device)
-    st = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-    check(lib.umlh_gather_rows(_ptr(x), _ptr(index), index.numel(), x.shape[1], _ptr(out), 0, st), "umlh_gather_rows")
+    st = stream(x.device)
+    check(lib.umlh_gather_rows(ptr(x), ptr(index), index.numel(), x.shape[1], ptr(out), 0, st), "umlh_gather_rows")
     return out
 
 
@@ -585,8 +579,8 @@ def column_sums(x: torch.Tensor) -> torch.Tensor:
     """sum over the rows of a contiguous fp32 [M, N] device matrix (``umlh_colsum``)."""
     lib = _lib.load_library()
     out = torch.empty(x.shape[1], dtype=torch.float32, device=x.device)
-    st = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-    check(lib.umlh_colsum(_ptr(x), x.shape[0], x.shape[1], _ptr(out), st), "umlh_colsum")
+    st = stream(x.device)
+    check(lib.umlh_colsum(ptr(x), x.shape[0], x.shape[1], ptr(out), st), "umlh_colsum")
     return out
 
 
@@ -598,8 +592,8 @@ def optimizer_step(name: str, param: torch.Tensor, grad: torch.Tensor, m: torch.
     for t in (param, grad, m) + ((v,) if v is not None else ()):
         if t.dtype != torch.float32 or not t.is_contiguous() or t.device.type != "cuda":
             raise UmlhError("optimizer_step: contiguous fp32 GPU tensors required")
-    st = C.c_void_p(torch.cuda.current_stream(param.device).cuda_stream)
-    check(lib.umlh_optimizer_step(OPT_IDS[name], _ptr(param), _ptr(grad), _ptr(m), _ptr(v), param.numel(),
+    st = stream(param.device)
+    check(lib.umlh_optimizer_step(OPT_IDS[name], ptr(param), ptr(grad), ptr(m), ptr(v), param.numel(),
                                   float(lr), int(step), float(betas[0]), float(betas[1]), float(eps), float(momentum),
                                   float(weight_decay), st), "umlh_optimizer_step")
 
@@ -621,10 +615,10 @@ def optimizer_step_multi(name: str, params, grads, ms, vs, *, lr: float, step: i
         for t in (params[i], g, ms[i]) + (() if sgd else (vs[i],)):
             if t.dtype != torch.float32 or not t.is_contiguous() or t.device.type != "cuda":
                 raise UmlhError("optimizer_step_multi: contiguous fp32 GPU tensors required")
-    arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])
     cnt = (C.c_int64 * n)(*[p.numel() for p in params])
-    st = C.c_void_p(torch.cuda.current_stream(params[0].device).cuda_stream)
-    check(lib.umlh_optimizer_step_multi(OPT_IDS[name], n, arr(params), arr(fixed), arr(ms), None if sgd else arr(vs), cnt,
+    st = stream(params[0].device)
+    check(lib.umlh_optimizer_step_multi(OPT_IDS[name], n, ptr_array(params), ptr_array(fixed), ptr_array(ms),
+                                        None if sgd else ptr_array(vs), cnt,
                                         float(lr), int(step), float(betas[0]), float(betas[1]), float(eps), float(momentum),
                                         float(weight_decay), st), "umlh_optimizer_step_multi")
 
@@ -635,8 +629,8 @@ def to_bf16(t: torch.Tensor) -> torch.Tensor:
     if t.dtype != torch.float32 or not t.is_contiguous() or t.device.type != "cuda":
         raise UmlhError("to_bf16: contiguous fp32 GPU tensor required")
     out = torch.empty(t.shape, dtype=torch.bfloat16, device=t.device)
-    st = C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-    check(lib.umlh_to_bf16(_ptr(t), _ptr(out), t.numel(), st), "umlh_to_bf16")
+    st = stream(t.device)
+    check(lib.umlh_to_bf16(ptr(t), ptr(out), t.numel(), st), "umlh_to_bf16")
     return out
 
 
@@ -644,6 +638,6 @@ def random_permutation(n: int, seed: int, device) -> torch.Tensor:
     """int64 permutation of 0..n-1 drawn on the device by ``umlh_random_permutation`` (sort-free)."""
     lib = _lib.load_library()
     out = torch.empty(n, dtype=torch.int64, device=device)
-    st = C.c_void_p(torch.cuda.current_stream(out.device).cuda_stream)
-    check(lib.umlh_random_permutation(int(n), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(out), st), "umlh_random_permutation")
+    st = stream(out.device)
+    check(lib.umlh_random_permutation(int(n), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(out), st), "umlh_random_permutation")
     return out

@@ -13,11 +13,15 @@ from __future__ import annotations
 
 import torch
 
+from . import _glue as glue
 from ._lib import UmlhError, check, load_library
-from .align import _device, _features, _stream
 
 KINDS = {"lbfgs": 0, "liblinear": 1}
 MAX_FEATURES = 1024
+
+
+def _device() -> torch.device:
+    return glue.device("umlh.align", "the metrics run only as HIP kernels")
 
 
 def masked_mean(z: torch.Tensor, lengths: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
@@ -43,29 +47,21 @@ def masked_mean(z: torch.Tensor, lengths: torch.Tensor | None = None, out: torch
         out = torch.empty((B, Z), dtype=torch.float32, device=dev)
     elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (B, Z) and out.stride(1) == 1 and out.stride(0) >= Z):
         raise ValueError("masked_mean: out must be an fp32 device view [B, Z] with unit column stride")
-    check(load_library().umlh_masked_mean(z.data_ptr(), B, T, Z, z.stride(0), z.stride(1),
-                                          lengths.data_ptr() if lengths is not None else None, out.data_ptr(), out.stride(0),
-                                          _stream(dev)), "umlh_masked_mean")
+    check(load_library().umlh_masked_mean(z.data_ptr(), B, T, Z, z.stride(0), z.stride(1), glue.ptr(lengths), out.data_ptr(),
+                                          out.stride(0), glue.stream(dev)), "umlh_masked_mean")
     return out
-
-
-def _scratch(lib, n, d, max_iter, dev):
-    nbytes = lib.umlh_probe_scratch_bytes(n, d, max_iter)
-    if nbytes == 0:
-        raise UmlhError(f"umlh_probe_scratch_bytes: invalid arguments n={n} d={d} max_iter={max_iter}")
-    return torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes
 
 
 def column_stats(x: torch.Tensor) -> torch.Tensor:
     """StandardScaler().fit(x) as a float64 device tensor [2, d]: column means, then population standard deviations with
     values below 10 eps replaced by 1."""
     dev = _device()
-    x = _features(x, "column_stats", dev)
+    x = glue.features(x, "column_stats", dev)
     n, d = x.shape
     lib = load_library()
-    scratch, nbytes = _scratch(lib, n, d, 0, dev)
+    scratch, nbytes = glue.scratch("umlh_probe_scratch_bytes", dev, n=n, d=d, max_iter=0)
     stats = torch.empty((2, d), dtype=torch.float64, device=dev)
-    check(lib.umlh_probe_column_stats(x.data_ptr(), n, d, x.stride(0), stats.data_ptr(), scratch.data_ptr(), nbytes, _stream(dev)),
+    check(lib.umlh_probe_column_stats(x.data_ptr(), n, d, x.stride(0), stats.data_ptr(), scratch.data_ptr(), nbytes, glue.stream(dev)),
           "umlh_probe_column_stats")
     return stats
 
@@ -103,7 +99,7 @@ class LogisticProbe:
         (as sklearn does) or a label other than 0/1; pass False when the labels are known to be sound and the caller wants
         no host synchronisation."""
         dev = _device()
-        x = _features(X, "LogisticProbe.fit", dev)
+        x = glue.features(X, "LogisticProbe.fit", dev)
         n, d = x.shape
         if n < 2:
             raise ValueError(f"LogisticProbe.fit: needs at least 2 rows, got {n}")
@@ -118,15 +114,13 @@ class LogisticProbe:
                 raise ValueError(f"This solver needs samples of at least 2 classes in the data, but the data contains only one class: {lo}")
         lib = load_library()
         self._stats = column_stats(x) if self.kind == "liblinear" else None
-        scratch, nbytes = _scratch(lib, n, d, self.max_iter, dev)
+        scratch, nbytes = glue.scratch("umlh_probe_scratch_bytes", dev, n=n, d=d, max_iter=self.max_iter)
         self._coef = torch.empty(d + 1, dtype=torch.float64, device=dev)
         self._record = torch.empty(24, dtype=torch.uint8, device=dev)
         self._objectives = torch.empty(self.max_iter + 1, dtype=torch.float64, device=dev) if self.keep_objectives else None
-        check(lib.umlh_probe_fit(x.data_ptr(), n, d, x.stride(0), yy.data_ptr(),
-                                 self._stats.data_ptr() if self._stats is not None else None, KINDS[self.kind], self.C,
+        check(lib.umlh_probe_fit(x.data_ptr(), n, d, x.stride(0), yy.data_ptr(), glue.ptr(self._stats), KINDS[self.kind], self.C,
                                  self.max_iter, self.gtol, self._coef.data_ptr(), self._record.data_ptr(),
-                                 self._objectives.data_ptr() if self._objectives is not None else None, scratch.data_ptr(), nbytes,
-                                 _stream(dev)), "umlh_probe_fit")
+                                 glue.ptr(self._objectives), scratch.data_ptr(), nbytes, glue.stream(dev)), "umlh_probe_fit")
         self._keep = (x, yy, scratch)          # this fit's own operands and scratch, alive as long as the probe
         self._host = None
         return self
@@ -174,18 +168,15 @@ class LogisticProbe:
     def _score(self, X, y, want_decision, want_correct):
         self._fitted()
         dev = _device()
-        x = _features(X, "LogisticProbe", dev)
+        x = glue.features(X, "LogisticProbe", dev)
         n, d = x.shape
         if d != self._coef.numel() - 1:
             raise ValueError(f"LogisticProbe: {d} features, fitted on {self._coef.numel() - 1}")
         yy = _labels(y, n, dev, "LogisticProbe.score") if want_correct else None
         dec = torch.empty(n, dtype=torch.float32, device=dev) if want_decision else None
         correct = torch.empty((), dtype=torch.int64, device=dev) if want_correct else None
-        check(load_library().umlh_probe_score(x.data_ptr(), n, d, x.stride(0),
-                                              self._stats.data_ptr() if self._stats is not None else None, self._coef.data_ptr(),
-                                              yy.data_ptr() if yy is not None else None,
-                                              correct.data_ptr() if correct is not None else None,
-                                              dec.data_ptr() if dec is not None else None, _stream(dev)), "umlh_probe_score")
+        check(load_library().umlh_probe_score(x.data_ptr(), n, d, x.stride(0), glue.ptr(self._stats), self._coef.data_ptr(),
+                                              glue.ptr(yy), glue.ptr(correct), glue.ptr(dec), glue.stream(dev)), "umlh_probe_score")
         return dec, correct, n
 
     def decision_function(self, X: torch.Tensor) -> torch.Tensor:

@@ -14,12 +14,12 @@ standardised columns (the PCA of the correlation matrix times n - 1): see its do
 """
 from __future__ import annotations
 
-import ctypes as C
 import operator
 
 import torch
 
-from ._lib import UmlhError, check, load_library
+from . import _glue as glue
+from ._lib import check, load_library
 
 MAX_D = 512
 MAX_Q = 64
@@ -33,13 +33,7 @@ def chunk_count(batch: int, n: int) -> int:
 
 
 def _device() -> torch.device:
-    if not torch.cuda.is_available():
-        raise RuntimeError("umlh.spectral needs a GPU: the spectrum is computed only by HIP kernels")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _stream(dev: torch.device):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    return glue.device("umlh.spectral", "the spectrum is computed only by HIP kernels")
 
 
 def _no_overlap(outer: int, inner: int, d: int, so: int, si: int) -> bool:
@@ -77,23 +71,16 @@ def _in_place(a: torch.Tensor, dev: torch.device) -> torch.Tensor:
     return a
 
 
-def _scratch(lib, batch, n, d, dev):
-    nbytes = lib.umlh_spectral_scratch_bytes(batch, n, d)
-    if nbytes == 0:
-        raise UmlhError(f"umlh_spectral_scratch_bytes: invalid arguments batch={batch} n={n} d={d}")
-    return torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes
-
-
 def svdvals(a: torch.Tensor) -> torch.Tensor:
     """torch.linalg.svdvals(a): float64 device tensor [min(n, d)] or [batch, min(n, d)], descending."""
     batch, n, d, batched = _matrix(a, "svdvals")
     dev = _device()
     x = _in_place(a, dev)
     lib = load_library()
-    scratch, nbytes = _scratch(lib, batch, n, d, dev)
+    scratch, nbytes = glue.scratch("umlh_spectral_scratch_bytes", dev, batch=batch, n=n, d=d)
     sv = torch.empty((batch, min(n, d)), dtype=torch.float64, device=dev)
     check(lib.umlh_svdvals(x.data_ptr(), batch, n, d, x.stride(0), x.stride(1), sv.data_ptr(), scratch.data_ptr(), nbytes,
-                           _stream(dev)), "umlh_svdvals")
+                           glue.stream(dev)), "umlh_svdvals")
     return sv if batched else sv[0]
 
 
@@ -112,11 +99,11 @@ def effective_rank(a: torch.Tensor, eps: float = 1e-6, return_svdvals: bool = Fa
     dev = _device()
     x = _in_place(a, dev)
     lib = load_library()
-    scratch, nbytes = _scratch(lib, batch, n, d, dev)
+    scratch, nbytes = glue.scratch("umlh_spectral_scratch_bytes", dev, batch=batch, n=n, d=d)
     out = torch.empty(batch, dtype=torch.float64, device=dev)
     sv = torch.empty((batch, min(n, d)), dtype=torch.float64, device=dev) if return_svdvals else None
     check(lib.umlh_effective_rank(x.data_ptr(), batch, n, d, x.stride(0), x.stride(1), eps, out.data_ptr(),
-                                  sv.data_ptr() if sv is not None else None, scratch.data_ptr(), nbytes, _stream(dev)),
+                                  glue.ptr(sv), scratch.data_ptr(), nbytes, glue.stream(dev)),
           "umlh_effective_rank")
     out = out if batched else out[0]
     if return_svdvals:
@@ -152,17 +139,16 @@ def effective_rank_seq(z: torch.Tensor, lengths: torch.Tensor | None = None, dro
     if lengths is not None:
         lengths = lengths.detach().reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
     lib = load_library()
-    scratch, nbytes = _scratch(lib, 1, B * T, d, dev)
+    scratch, nbytes = glue.scratch("umlh_spectral_scratch_bytes", dev, batch=1, n=B * T, d=d)
     out = torch.empty(2, dtype=torch.float64, device=dev)
     sv = torch.empty(d, dtype=torch.float64, device=dev) if return_svdvals else None
-    check(lib.umlh_effective_rank_seq(x.data_ptr(), B, T, d, x.stride(0), x.stride(1),
-                                      lengths.data_ptr() if lengths is not None else None, drop_last, eps, out.data_ptr(),
-                                      sv.data_ptr() if sv is not None else None, scratch.data_ptr(), nbytes, _stream(dev)),
+    check(lib.umlh_effective_rank_seq(x.data_ptr(), B, T, d, x.stride(0), x.stride(1), glue.ptr(lengths), drop_last, eps,
+                                      out.data_ptr(), glue.ptr(sv), scratch.data_ptr(), nbytes, glue.stream(dev)),
           "umlh_effective_rank_seq")
     return (out, sv) if return_svdvals else out
 
 
-def _view(a, what: str):
+def check_view(a, what: str):
     """The checks of one [n, d] view that need no device -> (n, d)."""
     if not isinstance(a, torch.Tensor) or a.ndim != 2:
         raise ValueError(f"{what}: expected a 2-D tensor [n, d], got {getattr(a, 'shape', type(a))}")
@@ -176,7 +162,7 @@ def _view(a, what: str):
     return n, d
 
 
-def _check_q(q, limit: int, what: str) -> int:
+def check_q(q, limit: int, what: str) -> int:
     try:
         q = operator.index(q)
     except TypeError:
@@ -186,7 +172,7 @@ def _check_q(q, limit: int, what: str) -> int:
     return q
 
 
-def _rows_in_place(a: torch.Tensor, dev: torch.device) -> torch.Tensor:
+def rows_in_place(a: torch.Tensor, dev: torch.device) -> torch.Tensor:
     """A 2-D fp32 device view with unit column stride and a row stride in d..2^31 - 1."""
     a = a.detach().to(device=dev, dtype=torch.float32)
     if a.stride(1) != 1 or not a.shape[1] <= a.stride(0) < 2 ** 31:
@@ -203,17 +189,14 @@ def principal_subspace(a: torch.Tensor, q: int, standardize: bool = False):
     (MultiBench/metrics.py:132-135); a constant column is then exactly zero.  ``a @ evecs / evals.sqrt()`` of the standardised
     matrix are its top-q left singular vectors.  2 <= n < 2^31, d <= 512, q <= min(n, d, 64).  Eigenvectors of eigenvalues that
     are equal (to rounding) span the right subspace but are otherwise arbitrary; a NaN or Inf in the input makes everything NaN."""
-    n, d = _view(a, "principal_subspace")
-    q = _check_q(q, min(n, d), "principal_subspace")
+    n, d = check_view(a, "principal_subspace")
+    q = check_q(q, min(n, d), "principal_subspace")
     dev = _device()
-    x = _rows_in_place(a, dev)
+    x = rows_in_place(a, dev)
     lib = load_library()
-    nbytes = lib.umlh_subspace_scratch_bytes(n, d, 0, q)
-    if nbytes == 0:
-        raise UmlhError(f"umlh_subspace_scratch_bytes: invalid arguments n={n} d={d} q={q}")
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    scratch, nbytes = glue.scratch("umlh_subspace_scratch_bytes", dev, n=n, d_a=d, d_b=0, q=q)
     evals = torch.empty(q, dtype=torch.float64, device=dev)
     evecs = torch.empty((d, q), dtype=torch.float64, device=dev)
     check(lib.umlh_principal_subspace(x.data_ptr(), n, d, x.stride(0), q, int(bool(standardize)), evals.data_ptr(), evecs.data_ptr(),
-                                      scratch.data_ptr(), nbytes, _stream(dev)), "umlh_principal_subspace")
+                                      scratch.data_ptr(), nbytes, glue.stream(dev)), "umlh_principal_subspace")
     return evals, evecs
