@@ -150,7 +150,7 @@ typedef struct {
 #define UMLH_N_SCALARS    12
 
 const char* umlh_last_error(void);
-int  umlh_version(void);        /* ABI revision: 3 = round 2 (grouped / micro / data-parallel / encoder-plan / InfoNCE entry points); 4 = round 3 (umlh_step_status / umlh_step_launches, umlh_p2p_*); 5 = umlh_align_* (CKA, k-NN, mutual k-NN); 6 = umlh_masked_mean, umlh_probe_* (linear probes of MultiBench evaluate); 7 = umlh_align_cka_unbiased / _cka_rbf / _cknna / _list_stats; 8 = umlh_spectral_scratch_bytes, umlh_svdvals, umlh_effective_rank, umlh_effective_rank_seq; 9 = umlh_subspace_scratch_bytes, umlh_principal_subspace, umlh_svcca */
+int  umlh_version(void);        /* ABI revision: 3 = round 2 (grouped / micro / data-parallel / encoder-plan / InfoNCE entry points); 4 = round 3 (umlh_step_status / umlh_step_launches, umlh_p2p_*); 5 = umlh_align_* (CKA, k-NN, mutual k-NN); 6 = umlh_masked_mean, umlh_probe_* (linear probes of MultiBench evaluate); 7 = umlh_align_cka_unbiased / _cka_rbf / _cknna / _list_stats; 8 = umlh_spectral_scratch_bytes, umlh_svdvals, umlh_effective_rank, umlh_effective_rank_seq; 9 = umlh_subspace_scratch_bytes, umlh_principal_subspace, umlh_svcca; 10 = umlh_seq_compact, umlh_paired_cosine_scratch_bytes, umlh_paired_cosine */
 
 /* Bytes of workspace a handle with this config needs (0 on invalid config). */
 uint64_t umlh_workspace_bytes(const umlh_config_t* cfg);
@@ -660,6 +660,26 @@ int  umlh_principal_subspace(const float* a, int64_t n, int32_t d, int64_t ld_ro
  * input is not finite. */
 int  umlh_svcca(const float* a, const float* b, int64_t n, int32_t d_a, int32_t d_b, int64_t ld_a, int64_t ld_b, int32_t q,
                 double* out, double* rho_or_null, double* evals_or_null, void* scratch, uint64_t scratch_bytes, void* stream);
+
+/* ---- ABI v10: the two device operations of the MultiBench embedding capture (MultiBench/train.py:300-347,456-512; DESIGN
+ * section 14).  Every argument check happens before any HIP call; everything runs on `stream`; outputs are device memory;
+ * no float atomics: results are bitwise reproducible for given arguments, independent of stream and of the device's CU count. */
+
+/* Valid rows of a block of sequences, packed: z[b, t, c] is read at z[b*ldb + t*ldt + c]. Row (b, t) counts iff
+ * t < clamp(lengths[b], 0, t_len) - drop_last (lengths = NULL: t_len everywhere) -- the predicate of umlh_effective_rank_seq.
+ * It is written bit for bit to out[(sum_{b' < b} rows(b') + t) * ldo + c]. Rows whose index is >= out_rows are not written;
+ * rows_total[0] (device int64, always written) is the number of valid rows, so a caller can detect a mismatch.
+ * No scratch, no host sync.  1 <= b <= 65535, t_len >= 1, d >= 1, non-overlapping ldb, ldt >= d, ldo >= d, drop_last >= 0,
+ * out_rows >= 0; out must not overlap z. */
+int  umlh_seq_compact(const float* z, int32_t b, int32_t t_len, int32_t d, int64_t ldb, int64_t ldt, const int64_t* lengths,
+                      int32_t drop_last, float* out, int64_t ldo, int64_t out_rows, int64_t* rows_total, void* stream);
+
+uint64_t umlh_paired_cosine_scratch_bytes(int64_t n, int32_t d);   /* 0 on invalid arguments */
+/* out2 = {mean_i cos_i, sum_i cos_i}, cos_i = (a_i / max(|a_i|, eps)) . (b_i / max(|b_i|, eps)): each norm is clamped on
+ * its own, as torch's F.cosine_similarity does (not the product). Dot products and squared norms are accumulated in fp64
+ * from the fp32 rows. rows_or_null: NULL or n floats, cos_i rounded to fp32. n >= 1, d >= 1, lda, ldb >= d, eps >= 0. */
+int  umlh_paired_cosine(const float* a, int64_t lda, const float* b, int64_t ldb, int64_t n, int32_t d, double eps,
+                        double* out2, float* rows_or_null, void* scratch, uint64_t scratch_bytes, void* stream);
 
 #ifdef __cplusplus
 }

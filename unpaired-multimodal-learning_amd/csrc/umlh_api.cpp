@@ -223,7 +223,7 @@ static inline void mark(umlh_handle_t h, int i, hipStream_t st) {
 }
 
 const char* umlh_last_error(void) { return g_err; }
-int umlh_version(void) { return 9; }   // 3: round 2 (grouped / micro / data-parallel / encoder-plan / InfoNCE entry points, umlh_enc_layer_t.seed_device, umlh_seq_mse_backward scratch); 4: round 3 (umlh_step_status / _launches, umlh_p2p_*); 5: umlh_align_*; 6: umlh_masked_mean, umlh_probe_*; 7: umlh_align_cka_unbiased / _cka_rbf / _cknna / _list_stats; 8: umlh_spectral_scratch_bytes, umlh_svdvals, umlh_effective_rank, umlh_effective_rank_seq; 9: umlh_subspace_scratch_bytes, umlh_principal_subspace, umlh_svcca
+int umlh_version(void) { return 10; }   // 3: round 2 (grouped / micro / data-parallel / encoder-plan / InfoNCE entry points, umlh_enc_layer_t.seed_device, umlh_seq_mse_backward scratch); 4: round 3 (umlh_step_status / _launches, umlh_p2p_*); 5: umlh_align_*; 6: umlh_masked_mean, umlh_probe_*; 7: umlh_align_cka_unbiased / _cka_rbf / _cknna / _list_stats; 8: umlh_spectral_scratch_bytes, umlh_svdvals, umlh_effective_rank, umlh_effective_rank_seq; 9: umlh_subspace_scratch_bytes, umlh_principal_subspace, umlh_svcca; 10: umlh_seq_compact, umlh_paired_cosine_scratch_bytes, umlh_paired_cosine
 
 int umlh_freeze_proj_row(umlh_handle_t h, int32_t row) {
     if (!h) return fail(UMLH_E_INVALID, "umlh_freeze_proj_row: null handle");
@@ -930,6 +930,49 @@ int umlh_svcca(const float* a, const float* b, int64_t n, int32_t d_a, int32_t d
     if (scratch_bytes < need)
         return fail(UMLH_E_INVALID, "%s: scratch of %llu bytes, %llu needed", who, (unsigned long long)scratch_bytes, (unsigned long long)need);
     HIPCHK(umlh_svcca_launch(a, b, n, d_a, d_b, ld_a, ld_b, q, out, rho_or_null, evals_or_null, scratch, (hipStream_t)stream), who);
+    return UMLH_OK;
+}
+
+// ---- embedding capture (kernels: umlh_kernels_capture.hip); every check precedes the first HIP call ----
+static const int CAPTURE_MAX_B = 65535;
+
+int umlh_seq_compact(const float* z, int32_t b, int32_t t_len, int32_t d, int64_t ldb, int64_t ldt, const int64_t* lengths,
+                     int32_t drop_last, float* out, int64_t ldo, int64_t out_rows, int64_t* rows_total, void* stream) {
+    const char* who = "umlh_seq_compact";
+    if (!z || !out) return fail(UMLH_E_INVALID, "%s: null pointer (z and out are required)", who);
+    if (!rows_total) return fail(UMLH_E_INVALID, "%s: rows_total is NULL (the row count is always written)", who);
+    if (d < 1) return fail(UMLH_E_INVALID, "%s: d=%d < 1", who, d);
+    if (b < 1 || b > CAPTURE_MAX_B) return fail(UMLH_E_INVALID, "%s: b=%d outside 1..%d", who, b, CAPTURE_MAX_B);
+    if (t_len < 1) return fail(UMLH_E_INVALID, "%s: t_len=%d < 1", who, t_len);
+    if (ldt < d) return fail(UMLH_E_INVALID, "%s: ldt=%lld < d=%d", who, (long long)ldt, d);
+    if (ldb < d) return fail(UMLH_E_INVALID, "%s: ldb=%lld < d=%d", who, (long long)ldb, d);
+    if (!spectral_strides_ok(b, t_len, d, ldb, ldt))
+        return fail(UMLH_E_INVALID, "%s: ldb=%lld ldt=%lld overlap for b=%d t_len=%d d=%d", who, (long long)ldb, (long long)ldt, b, t_len, d);
+    if (drop_last < 0) return fail(UMLH_E_INVALID, "%s: drop_last=%d < 0", who, drop_last);
+    if (ldo < d) return fail(UMLH_E_INVALID, "%s: ldo=%lld < d=%d", who, (long long)ldo, d);
+    if (out_rows < 0) return fail(UMLH_E_INVALID, "%s: out_rows=%lld < 0", who, (long long)out_rows);
+    HIPCHK(umlh_capture_launch_compact(z, b, t_len, d, ldb, ldt, reinterpret_cast<const long long*>(lengths), drop_last, out, ldo, out_rows,
+                                       reinterpret_cast<long long*>(rows_total), (hipStream_t)stream), who);
+    return UMLH_OK;
+}
+
+uint64_t umlh_paired_cosine_scratch_bytes(int64_t n, int32_t d) {
+    return n >= 1 && d >= 1 ? umlh_capture_cosine_bytes(n) : 0;
+}
+
+int umlh_paired_cosine(const float* a, int64_t lda, const float* b, int64_t ldb, int64_t n, int32_t d, double eps, double* out2,
+                       float* rows_or_null, void* scratch, uint64_t scratch_bytes, void* stream) {
+    const char* who = "umlh_paired_cosine";
+    if (!a || !b || !out2 || !scratch) return fail(UMLH_E_INVALID, "%s: null pointer (a, b, out2 and scratch are required)", who);
+    if (n < 1) return fail(UMLH_E_INVALID, "%s: n=%lld rows (need n >= 1)", who, (long long)n);
+    if (d < 1) return fail(UMLH_E_INVALID, "%s: d=%d < 1", who, d);
+    if (lda < d) return fail(UMLH_E_INVALID, "%s: lda=%lld < d=%d", who, (long long)lda, d);
+    if (ldb < d) return fail(UMLH_E_INVALID, "%s: ldb=%lld < d=%d", who, (long long)ldb, d);
+    if (!(eps >= 0.0)) return fail(UMLH_E_INVALID, "%s: eps=%g (need eps >= 0)", who, eps);
+    const uint64_t need = umlh_capture_cosine_bytes(n);
+    if (scratch_bytes < need)
+        return fail(UMLH_E_INVALID, "%s: scratch of %llu bytes, %llu needed", who, (unsigned long long)scratch_bytes, (unsigned long long)need);
+    HIPCHK(umlh_capture_launch_cosine(a, lda, b, ldb, n, d, eps, out2, rows_or_null, scratch, (hipStream_t)stream), who);
     return UMLH_OK;
 }
 

@@ -147,6 +147,12 @@ int umlh_subspace_launch(const float* a, long long n, int d, long long ld, int q
                          void* scratch, hipStream_t st);
 int umlh_svcca_launch(const float* a, const float* b, long long n, int da, int db, long long lda, long long ldb, int q, double* out,
                       double* rho, double* evals, void* scratch, hipStream_t st);
+// ---- umlh_kernels_capture.hip: ragged row compaction, mean paired cosine ----
+unsigned long long umlh_capture_cosine_bytes(long long n);
+int umlh_capture_launch_compact(const float* z, int B, int T, int d, long long ldb, long long ldt, const long long* lengths,
+                                int drop_last, float* out, long long ldo, long long out_rows, long long* rows_total, hipStream_t st);
+int umlh_capture_launch_cosine(const float* a, long long lda, const float* b, long long ldb, long long n, int d, double eps,
+                               double* out2, float* rows, void* scratch, hipStream_t st);
 
 // ---- umlh_api.cpp, for umlh_encoder.cpp ----
 // out[M,N] (ldo == N) = epilogue(A B^T) with the operand layouts of umlh_gemm_f32.  `splits` K-slabs go to `slabs`

@@ -4,9 +4,11 @@ loss = alpha_x*loss_x + alpha_y*loss_y, one optimizer step per batch pair, and t
 ``evaluate`` / ``evaluate_raw_data`` (train.py:31-240): every train / val / test batch through the model
 in eval mode, masked-mean pooling and binary logistic probes, all on the HIP kernels of ``umlh.probe``.
 ``train(effective_rank=True)`` adds the reference's per-step effective rank of the predicted y rows and of a fixed sample
-of the y modality (train.py:302-345,380-389) on the HIP kernels of ``umlh.spectral``.  The other per-batch diagnostics of
-the reference (the covariance matrices it forms and drops, wandb, the embedding capture: train.py:386,388,428-443,452-515)
-are outside this port."""
+of the y modality (train.py:302-345,380-389) on the HIP kernels of ``umlh.spectral``.
+``train(capture_embeddings_during_training=True)`` adds the reference's embedding capture (train.py:300-347,456-512,533-536):
+a fixed sample of sequence pairs through the model at every in-loop evaluation, its valid rows packed by ``umlh.seq_compact``
+and compared by ``umlh.align`` and ``umlh.paired_cosine`` (``multibench.capture``).  The other per-batch diagnostics of the
+reference (the covariance matrices it forms and drops, wandb: train.py:386,388,428-443) are outside this port."""
 from __future__ import annotations
 
 import copy
@@ -190,11 +192,18 @@ def _unpack(batch, modality, ds_name, which):
     return (batch[0].float(), batch[2]) if which == 0 else (batch[1].float(), batch[3])
 
 
-def _fixed_sample_rank(loader, modality, ds_name, dev, n_samples=1000):
-    """Effective rank of the valid rows (t < len) of the first ``n_samples`` sequences of a deep copy of ``loader``, y side
-    only (train.py:302-345,387): a 0-d float64 device tensor.  Batches may differ in T; each is padded with zero rows, which
-    the row predicate leaves out anyway."""
+def _sample_rank(seqs, lens, dev):
+    """Effective rank of the valid rows (t < len) of per-batch [b, T, d] device blocks pooled into one matrix: a 0-d float64
+    device tensor.  Batches may differ in T; each is padded with zero rows, which the row predicate leaves out anyway."""
     import umlh
+    T = max(s.shape[1] for s in seqs)
+    block = torch.cat([torch.nn.functional.pad(s, (0, 0, 0, T - s.shape[1])) for s in seqs], dim=0)
+    with torch.cuda.device(dev):
+        return umlh.effective_rank_seq(block, torch.cat(lens), drop_last=0)[0]
+
+
+def _fixed_sample_rank(loader, modality, ds_name, dev, n_samples=1000):
+    """``_sample_rank`` of the first ``n_samples`` sequences of a deep copy of ``loader``, y side only (train.py:302-345,387)."""
     seqs, lens, left = [], [], n_samples
     for batch in copy.deepcopy(loader):
         y, ly = _unpack(batch, modality, ds_name, 1)
@@ -206,10 +215,7 @@ def _fixed_sample_rank(loader, modality, ds_name, dev, n_samples=1000):
             break
     if not seqs:
         raise ValueError("train(effective_rank=True): train_loader_2 yields no batch")
-    T = max(s.shape[1] for s in seqs)
-    block = torch.cat([torch.nn.functional.pad(s, (0, 0, 0, T - s.shape[1])) for s in seqs], dim=0)
-    with torch.cuda.device(dev):
-        return umlh.effective_rank_seq(block, torch.cat(lens), drop_last=0)[0]
+    return _sample_rank(seqs, lens, dev)
 
 
 def train(model, train_mode, train_loader_1, train_loader_2, optimizer, modalities=[0, 2], num_epoch=100, step_k=30,
@@ -227,12 +233,30 @@ def train(model, train_mode, train_loader_1, train_loader_2, optimizer, modaliti
     (utilis.py:27-36) of the rows y_recon[b, t], t < len_b - 1, of the step's own forward (train.py:381-389), enqueued on the
     training stream and read back at the end with the losses; and 'gt_effective_rank_y': that of the valid rows of the
     first up-to-1000 sequences of a copy of ``train_loader_2`` (train.py:302-345,387), a constant the reference recomputes
-    every step and this loop computes once."""
+    every step and this loop computes once.
+
+    ``capture_embeddings_during_training=True`` (needs a non-empty ``eval_config``: the reference captures only inside its
+    evaluation branch) takes the reference's fixed sample of up to 1000 sequence pairs once (``multibench.capture``,
+    train.py:302-347) and, after every in-loop evaluation, runs it through the model and adds the eleven ``val/cka_*``,
+    ``val/mknn_*`` and ``val/cos_sim_*`` values of train.py:492-512 to that entry of 'eval' (not to the closing one, as in the
+    reference).  The dict then also holds 'embeddings' = {'x1': [E, N, z], 'x2': [E, N, z] (fp32 device stacks of the packed zx
+    and zy rows, one per capture, in capture order), 'x1_label', 'x2_label'} (train.py:533-536).  With ``effective_rank`` as
+    well, 'gt_effective_rank_y' is computed from the capture's y sample, as the reference does (:345,:387)."""
     model.train()
     dev = torch.device(device)
     rec_x, rec_y, rec_l, rec_rank = [], [], [], []
     want_rank = bool(effective_rank) and "y" in train_mode
-    gt_rank = _fixed_sample_rank(train_loader_2, modalities[1], ds_name, dev) if want_rank else None
+    capture, cap_x, cap_y = None, [], []
+    if capture_embeddings_during_training:
+        from .capture import EmbeddingCapture, take_fixed_samples
+        if not eval_config:
+            raise ValueError("train(capture_embeddings_during_training=True) needs an eval_config: the capture runs after each "
+                             "in-loop evaluation (train.py:440-457)")
+        capture = EmbeddingCapture(take_fixed_samples(train_loader_1, train_loader_2, modalities, ds_name), dev)
+    if want_rank and capture is not None:
+        gt_rank = _sample_rank(capture.x2, capture.l2, dev)
+    else:
+        gt_rank = _fixed_sample_rank(train_loader_2, modalities[1], ds_name, dev) if want_rank else None
     raw_results, evals = None, []
     if eval_config:
         raw_results = evaluate_raw_data(eval_config, ds_name=ds_name, device=device)
@@ -268,6 +292,11 @@ def train(model, train_mode, train_loader_1, train_loader_2, optimizer, modaliti
                 on_step(epoch, i_batch, out, loss)
             if eval_config and i_batch % eval_config["freq"] == 0:
                 evals.append((epoch, i_batch, logged(evaluate(model, eval_config, ds_name, device=device))))
+                if capture is not None:
+                    values, zx, zy = capture.measure(model)
+                    evals[-1][2].update(values)
+                    cap_x.append(zx)
+                    cap_y.append(zy)
                 model.train()
         if eval_config and epoch == num_epoch - 1:
             evals.append((epoch, None, logged(evaluate(model, eval_config, ds_name, device=device))))
@@ -279,4 +308,7 @@ def train(model, train_mode, train_loader_1, train_loader_2, optimizer, modaliti
         res["gt_effective_rank_y"] = float(gt_rank.cpu())
     if eval_config:
         res["raw"], res["eval"] = raw_results, evals
+    if capture is not None:
+        res["embeddings"] = {"x1": torch.stack(cap_x) if cap_x else None, "x2": torch.stack(cap_y) if cap_y else None,
+                             "x1_label": capture.labels[0], "x2_label": capture.labels[1]}
     return res

@@ -18,6 +18,8 @@ from .probe import LogisticProbe, masked_mean  # noqa: F401,E402
 from . import spectral  # noqa: F401,E402
 from .spectral import effective_rank, effective_rank_seq, principal_subspace, svdvals  # noqa: F401,E402
 from .align import svcca, svcca_terms  # noqa: F401,E402
+from . import capture  # noqa: F401,E402
+from .capture import paired_cosine, seq_compact  # noqa: F401,E402
 
 
 def host_cpu_budget() -> int:
