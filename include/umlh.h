@@ -150,7 +150,7 @@ typedef struct {
 #define UMLH_N_SCALARS    12
 
 const char* umlh_last_error(void);
-int  umlh_version(void);        /* ABI revision: 3 = round 2 (grouped / micro / data-parallel / encoder-plan / InfoNCE entry points); 4 = round 3 (umlh_step_status / umlh_step_launches, umlh_p2p_*); 5 = umlh_align_* (CKA, k-NN, mutual k-NN); 6 = umlh_masked_mean, umlh_probe_* (linear probes of MultiBench evaluate); 7 = umlh_align_cka_unbiased / _cka_rbf / _cknna / _list_stats; 8 = umlh_spectral_scratch_bytes, umlh_svdvals, umlh_effective_rank, umlh_effective_rank_seq; 9 = umlh_subspace_scratch_bytes, umlh_principal_subspace, umlh_svcca; 10 = umlh_seq_compact, umlh_paired_cosine_scratch_bytes, umlh_paired_cosine */
+int  umlh_version(void);        /* ABI revision: 3 = round 2 (grouped / micro / data-parallel / encoder-plan / InfoNCE entry points); 4 = round 3 (umlh_step_status / umlh_step_launches, umlh_p2p_*); 5 = umlh_align_* (CKA, k-NN, mutual k-NN); 6 = umlh_masked_mean, umlh_probe_* (linear probes of MultiBench evaluate); 7 = umlh_align_cka_unbiased / _cka_rbf / _cknna / _list_stats; 8 = umlh_spectral_scratch_bytes, umlh_svdvals, umlh_effective_rank, umlh_effective_rank_seq; 9 = umlh_subspace_scratch_bytes, umlh_principal_subspace, umlh_svcca; 10 = umlh_seq_compact, umlh_paired_cosine_scratch_bytes, umlh_paired_cosine; 11 = umlh_seq_step_stats_scratch_bytes, umlh_seq_step_stats */
 
 /* Bytes of workspace a handle with this config needs (0 on invalid config). */
 uint64_t umlh_workspace_bytes(const umlh_config_t* cfg);
@@ -680,6 +680,34 @@ uint64_t umlh_paired_cosine_scratch_bytes(int64_t n, int32_t d);   /* 0 on inval
  * from the fp32 rows. rows_or_null: NULL or n floats, cos_i rounded to fp32. n >= 1, d >= 1, lda, ldb >= d, eps >= 0. */
 int  umlh_paired_cosine(const float* a, int64_t lda, const float* b, int64_t ldb, int64_t n, int32_t d, double eps,
                         double* out2, float* rows_or_null, void* scratch, uint64_t scratch_bytes, void* stream);
+
+/* ---- ABI v11: the per-step logged statistics of the MultiBench training loop (MultiBench/train.py:403-426):
+ * train/trivial_loss_* ("predict the next frame by copying this one") and train/recon_y_loss (the masked next-step MSE of the
+ * reconstruction) of a block of padded sequences, in one pass.  x[b, t, c] is read at x[b*ldb + t*ldt + c], recon[b, t, c] at
+ * recon[b*ldb_r + t*ldt_r + c] (floats).  With len_b = clamp(lengths[b], 0, t_len) (lengths = NULL: t_len everywhere) and every
+ * sum over b, 0 <= t < t_len - 1 and all d columns:
+ *   trivial_num = sum [t < len_b]     (x[b,t,c]     - x[b,t+1,c])^2,   trivial_cnt = d * #{(b,t): t < len_b}
+ *   recon_num   = sum [t + 1 < len_b] (recon[b,t,c] - x[b,t+1,c])^2,   recon_cnt   = d * #{(b,t): t + 1 < len_b}
+ *   out4 = {trivial_num / (trivial_cnt + 1e-8), trivial_cnt, recon_num / (recon_cnt + 1e-8), recon_cnt}   (device doubles)
+ * The two masks differ ON PURPOSE, as in the reference: it weights the trivial loss by mask[:, :-1], so the pair
+ * (len_b - 1, len_b), which reaches one row into the padding, counts; recon_y_loss uses mask[:, 1:], where that pair does not.
+ * recon_or_null = NULL: slots 2 and 3 are 0.  t_len = 1: no pair exists, all four slots are 0 (the reference's trivial branch for
+ * T = 1 gives 0 where it does not raise, its recon_y_loss 0 / 1e-8).
+ * A pair its predicate excludes is skipped, not multiplied by zero: Inf or NaN in x rows t > len_b or in recon rows
+ * t >= len_b - 1 does not reach the result.  The reference's 0 * Inf would make both values NaN there; its loaders pad with
+ * zeros, where the two agree.
+ * Differences, squares and sums are fp64 from the fp32 inputs, counts exact integers; no float atomics; the grid and every
+ * summation order are functions of (b, t_len, d) alone, so results are bitwise reproducible across calls, streams and the two
+ * load paths (16-byte loads when d, all strides and both base addresses are multiples of 16 bytes, 4-byte loads otherwise) and
+ * do not depend on the CU count.  No sequential chain of additions is longer than 4096 terms: the error against exact arithmetic
+ * is below (4096 + log2(partials) + 4) 2^-53 < 5e-13 relative.  Two launches (partial sums into scratch, a fixed-order final),
+ * no host sync.  Every argument check happens before any HIP call.
+ * Envelope: 1 <= b <= 65535, t_len >= 1, d >= 1, non-overlapping ldb, ldt >= d as umlh_effective_rank_seq allows (the same for
+ * ldb_r, ldt_r when recon is given), and b * ceil((t_len - 1) / 64) * ceil(d / 1024) <= 2^22 partial sums. */
+uint64_t umlh_seq_step_stats_scratch_bytes(int32_t b, int32_t t_len, int32_t d);   /* 0 on invalid arguments */
+int  umlh_seq_step_stats(const float* x, int64_t ldb, int64_t ldt, const float* recon_or_null, int64_t ldb_r, int64_t ldt_r,
+                         int32_t b, int32_t t_len, int32_t d, const int64_t* lengths, double* out4, void* scratch,
+                         uint64_t scratch_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -223,7 +223,7 @@ static inline void mark(umlh_handle_t h, int i, hipStream_t st) {
 }
 
 const char* umlh_last_error(void) { return g_err; }
-int umlh_version(void) { return 10; }   // 3: round 2 (grouped / micro / data-parallel / encoder-plan / InfoNCE entry points, umlh_enc_layer_t.seed_device, umlh_seq_mse_backward scratch); 4: round 3 (umlh_step_status / _launches, umlh_p2p_*); 5: umlh_align_*; 6: umlh_masked_mean, umlh_probe_*; 7: umlh_align_cka_unbiased / _cka_rbf / _cknna / _list_stats; 8: umlh_spectral_scratch_bytes, umlh_svdvals, umlh_effective_rank, umlh_effective_rank_seq; 9: umlh_subspace_scratch_bytes, umlh_principal_subspace, umlh_svcca; 10: umlh_seq_compact, umlh_paired_cosine_scratch_bytes, umlh_paired_cosine
+int umlh_version(void) { return 11; }   // 3: round 2 (grouped / micro / data-parallel / encoder-plan / InfoNCE entry points, umlh_enc_layer_t.seed_device, umlh_seq_mse_backward scratch); 4: round 3 (umlh_step_status / _launches, umlh_p2p_*); 5: umlh_align_*; 6: umlh_masked_mean, umlh_probe_*; 7: umlh_align_cka_unbiased / _cka_rbf / _cknna / _list_stats; 8: umlh_spectral_scratch_bytes, umlh_svdvals, umlh_effective_rank, umlh_effective_rank_seq; 9: umlh_subspace_scratch_bytes, umlh_principal_subspace, umlh_svcca; 10: umlh_seq_compact, umlh_paired_cosine_scratch_bytes, umlh_paired_cosine; 11: umlh_seq_step_stats_scratch_bytes, umlh_seq_step_stats
 
 int umlh_freeze_proj_row(umlh_handle_t h, int32_t row) {
     if (!h) return fail(UMLH_E_INVALID, "umlh_freeze_proj_row: null handle");
@@ -973,6 +973,48 @@ int umlh_paired_cosine(const float* a, int64_t lda, const float* b, int64_t ldb,
     if (scratch_bytes < need)
         return fail(UMLH_E_INVALID, "%s: scratch of %llu bytes, %llu needed", who, (unsigned long long)scratch_bytes, (unsigned long long)need);
     HIPCHK(umlh_capture_launch_cosine(a, lda, b, ldb, n, d, eps, out2, rows_or_null, scratch, (hipStream_t)stream), who);
+    return UMLH_OK;
+}
+
+// ---- per-step logged statistics (kernels: umlh_kernels_stepstats.hip); every check precedes the first HIP call ----
+static bool step_stats_shape_ok(int32_t b, int32_t t_len, int32_t d) {
+    return b >= 1 && b <= CAPTURE_MAX_B && t_len >= 1 && d >= 1 && umlh_stepstats_partials(b, t_len, d) >= 0;
+}
+
+uint64_t umlh_seq_step_stats_scratch_bytes(int32_t b, int32_t t_len, int32_t d) {
+    return step_stats_shape_ok(b, t_len, d) ? umlh_stepstats_bytes(b, t_len, d) : 0;
+}
+
+// the stride checks of one [b, t_len, d] view; 0 = fine
+static int check_seq_view(const char* who, const char* ldb_name, const char* ldt_name, int32_t b, int32_t t_len, int32_t d, int64_t ldb,
+                          int64_t ldt) {
+    if (ldt < d) return fail(UMLH_E_INVALID, "%s: %s=%lld < d=%d", who, ldt_name, (long long)ldt, d);
+    if (ldb < d) return fail(UMLH_E_INVALID, "%s: %s=%lld < d=%d", who, ldb_name, (long long)ldb, d);
+    if (!spectral_strides_ok(b, t_len, d, ldb, ldt))
+        return fail(UMLH_E_INVALID, "%s: %s=%lld %s=%lld overlap for b=%d t_len=%d d=%d", who, ldb_name, (long long)ldb, ldt_name,
+                    (long long)ldt, b, t_len, d);
+    return UMLH_OK;
+}
+
+int umlh_seq_step_stats(const float* x, int64_t ldb, int64_t ldt, const float* recon_or_null, int64_t ldb_r, int64_t ldt_r, int32_t b,
+                        int32_t t_len, int32_t d, const int64_t* lengths, double* out4, void* scratch, uint64_t scratch_bytes,
+                        void* stream) {
+    const char* who = "umlh_seq_step_stats";
+    if (!x || !out4 || !scratch) return fail(UMLH_E_INVALID, "%s: null pointer (x, out4 and scratch are required)", who);
+    if (d < 1) return fail(UMLH_E_INVALID, "%s: d=%d < 1", who, d);
+    if (b < 1 || b > CAPTURE_MAX_B) return fail(UMLH_E_INVALID, "%s: b=%d outside 1..%d", who, b, CAPTURE_MAX_B);
+    if (t_len < 1) return fail(UMLH_E_INVALID, "%s: t_len=%d < 1", who, t_len);
+    if (!step_stats_shape_ok(b, t_len, d))
+        return fail(UMLH_E_INVALID, "%s: b=%d t_len=%d d=%d too large (need b * ceil((t_len - 1) / 64) * ceil(d / 1024) <= 2^22)", who, b,
+                    t_len, d);
+    if (int e = check_seq_view(who, "ldb", "ldt", b, t_len, d, ldb, ldt)) return e;
+    if (recon_or_null)
+        if (int e = check_seq_view(who, "ldb_r", "ldt_r", b, t_len, d, ldb_r, ldt_r)) return e;
+    const uint64_t need = umlh_stepstats_bytes(b, t_len, d);
+    if (scratch_bytes < need)
+        return fail(UMLH_E_INVALID, "%s: scratch of %llu bytes, %llu needed", who, (unsigned long long)scratch_bytes, (unsigned long long)need);
+    HIPCHK(umlh_stepstats_launch(x, ldb, ldt, recon_or_null, ldb_r, ldt_r, b, t_len, d, reinterpret_cast<const long long*>(lengths), out4,
+                                 scratch, (hipStream_t)stream), who);
     return UMLH_OK;
 }
 

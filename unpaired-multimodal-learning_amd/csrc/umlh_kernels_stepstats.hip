@@ -1,0 +1,217 @@
+// The per-step logged statistics of the MultiBench training loop (reference: MultiBench/train.py:403-426) for gfx950: the
+// "copy this frame" baseline error of a padded [B, T, d] block and the masked next-step error of its reconstruction, in one
+// pass over the two tensors.
+//
+//   trivial_num = sum [t < len_b]     (x[b,t,c]     - x[b,t+1,c])^2      the reference's mask[:, :-1]: the pair (len_b - 1, len_b),
+//                                                                         one row into the padding, counts
+//   recon_num   = sum [t + 1 < len_b] (recon[b,t,c] - x[b,t+1,c])^2      the reference's mask[:, 1:]: that pair does not count
+//   over b, 0 <= t < T - 1, all d columns; len_b = clamp(lengths[b], 0, T).  The two masks differ on purpose.
+//   A pair the predicate excludes is SKIPPED (its rows are not even loaded), not multiplied by zero: Inf or NaN in x rows
+//   t > len_b and recon rows t >= len_b - 1 does not reach the result.  The reference's 0 * Inf would give NaN there; its
+//   loaders pad with zeros, where the two agree.
+//
+//   stats_partial<V>  workgroup (b, 64-pair-row chunk, 1024-column chunk), 256 threads.  A thread owns one quad of four
+//                     adjacent columns and walks a run of pair rows t ascending with row t + 1 kept in registers: x[b,t+1,:] is
+//                     loaded once and serves both statistics and the next pair's x[b,t,:] (only the first row of a run is loaded
+//                     twice).  The 256 threads are LANES quad owners x 256 / LANES row runs, LANES the power of two
+//                     >= min(ceil(d / 4), 256) (at least 4), so narrow blocks still fill the workgroup: a run is LANES / 4
+//                     rows.  V = float4 when d, every stride and every base address are multiples of 16 bytes (ldt == d
+//                     with d % 4 == 0 is the usual instance; widths 35 and 371 are not), else four 4-byte loads of the same
+//                     quad: the two paths add the same numbers in the same order and give the same bits.
+//                     Differences, squares and sums in fp64 (the fp32 differences are exact there).  Per thread one chain of at
+//                     most 64 rows x 4 columns = 256 additions per statistic, then a butterfly across the wave and the four
+//                     wave sums added in wave order into partial[2 g], partial[2 g + 1].
+//   stats_final       one workgroup of 1024 threads: thread k adds partials k * per .. (k + 1) * per - 1 in index order,
+//                     per = ceil(P / 1024) <= 4096 (the longest sequential chain of the layout: 4096 terms), a butterfly
+//                     across each wave, the 16 wave sums in wave order.  The two pair counts are integer sums over the
+//                     clamped lengths (exact, any order).  out4 = {trivial_num / (trivial_cnt + 1e-8), trivial_cnt,
+//                     recon_num / (recon_cnt + 1e-8), recon_cnt}.
+//
+// No float atomics, no grid barrier, no host read.  The grid and every summation order are functions of (b, t_len, d) alone:
+// results are bitwise reproducible across calls, streams and load paths, and do not depend on the CU count.
+// Error against exact arithmetic: (4096 + log2(P) + 4) 2^-53 relative (all terms are >= 0), below 5e-13.
+#include "umlh_common.h"
+#include "umlh_launch.h"
+
+namespace {
+
+constexpr int SS_ROWS = 64;               // pair rows per workgroup
+constexpr int SS_QUADS = 256;             // column quads per workgroup (1024 columns)
+constexpr int SS_FINAL_THREADS = 1024;
+constexpr int SS_FINAL_CHAIN = 4096;      // most partials one thread of the final adds in sequence
+constexpr long long SS_MAX_PARTIALS = (long long)SS_FINAL_THREADS * SS_FINAL_CHAIN;
+
+__device__ __forceinline__ long long ss_len(const long long* __restrict__ lengths, int b, int T) {
+    const long long len = lengths ? lengths[b] : T;
+    return len < 0 ? 0 : (len > T ? T : len);
+}
+
+__device__ __forceinline__ double ss_wave_sum(double v) {
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;                                              // the same bits in every lane
+}
+
+struct Quad { float v[4]; };
+
+// columns 4q .. 4q + 3 of one row; n = how many of them exist (1..4)
+template <typename V>
+__device__ __forceinline__ Quad ss_load(const float* __restrict__ row, int n) {
+    Quad q;
+    if constexpr (sizeof(V) == 16) {
+        const float4 f = *reinterpret_cast<const float4*>(row);
+        q.v[0] = f.x; q.v[1] = f.y; q.v[2] = f.z; q.v[3] = f.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) q.v[j] = j < n ? row[j] : 0.0f;
+    }
+    return q;
+}
+
+template <typename V>
+__global__ __launch_bounds__(256) void stats_partial(const float* __restrict__ x, long long ldb, long long ldt,
+                                                     const float* __restrict__ recon, long long ldb_r, long long ldt_r, int T, int d,
+                                                     const long long* __restrict__ lengths, int col_chunks, int lanes,
+                                                     double* __restrict__ partial) {
+    __shared__ double wsum[2][4];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int rc = blockIdx.x / col_chunks, cc = blockIdx.x - rc * col_chunks;
+    const long long len = ss_len(lengths, b, T);
+    const int pairs = (int)(len < T - 1 ? len : T - 1);                 // pairs t < pairs count for the trivial statistic
+    const int run = lanes / 4, lane_q = tid & (lanes - 1), group = tid / lanes;    // rows per run = 64 * lanes / 256
+    const int t_begin = rc * SS_ROWS + group * run;
+    int t_end = t_begin + run;
+    if (t_end > pairs) t_end = pairs;
+    double tri = 0.0, rec = 0.0;
+    for (int q = cc * SS_QUADS + lane_q; q < (cc + 1) * SS_QUADS && 4 * q < d && t_begin < t_end; q += lanes) {
+        const int n = d - 4 * q < 4 ? d - 4 * q : 4;
+        const float* xp = x + (long long)b * ldb + (long long)t_begin * ldt + 4 * q;
+        const float* rp = recon ? recon + (long long)b * ldb_r + (long long)t_begin * ldt_r + 4 * q : nullptr;
+        Quad cur = ss_load<V>(xp, n);
+        for (int t = t_begin; t < t_end; ++t) {
+            xp += ldt;
+            const Quad nxt = ss_load<V>(xp, n);                          // row t + 1 <= pairs <= T - 1
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const double e = (double)cur.v[j] - (double)nxt.v[j];
+                if (j < n) tri += e * e;
+            }
+            if (rp && t + 1 < len) {                                      // recon row t < len - 1
+                const Quad r = ss_load<V>(rp, n);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const double e = (double)r.v[j] - (double)nxt.v[j];
+                    if (j < n) rec += e * e;
+                }
+            }
+            if (rp) rp += ldt_r;
+            cur = nxt;
+        }
+    }
+    tri = ss_wave_sum(tri);
+    rec = ss_wave_sum(rec);
+    if ((tid & 63) == 0) {
+        wsum[0][tid >> 6] = tri;
+        wsum[1][tid >> 6] = rec;
+    }
+    __syncthreads();
+    if (tid < 2) {
+        const long long g = ((long long)b * gridDim.x + blockIdx.x);
+        partial[2 * g + tid] = ((wsum[tid][0] + wsum[tid][1]) + wsum[tid][2]) + wsum[tid][3];
+    }
+}
+
+__global__ __launch_bounds__(SS_FINAL_THREADS) void stats_final(const double* __restrict__ partial, long long n_partials, int B, int T,
+                                                                int d, const long long* __restrict__ lengths, int with_recon,
+                                                                double* __restrict__ out4) {
+    __shared__ double wsum[2][SS_FINAL_THREADS / 64];
+    __shared__ long long wcnt[2][SS_FINAL_THREADS / 64];
+    const int tid = threadIdx.x, wave = tid >> 6;
+    const long long per = (n_partials + SS_FINAL_THREADS - 1) / SS_FINAL_THREADS;
+    long long hi = (tid + 1) * per;
+    if (hi > n_partials) hi = n_partials;
+    double tri = 0.0, rec = 0.0;
+    for (long long i = tid * per; i < hi; ++i) {
+        tri += partial[2 * i];
+        rec += partial[2 * i + 1];
+    }
+    long long n_tri = 0, n_rec = 0;
+    for (int b = tid; b < B; b += SS_FINAL_THREADS) {
+        const long long len = ss_len(lengths, b, T);
+        n_tri += len < T - 1 ? len : T - 1;
+        n_rec += len > 0 ? len - 1 : 0;
+    }
+    tri = ss_wave_sum(tri);
+    rec = ss_wave_sum(rec);
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) {
+        n_tri += __shfl_xor(n_tri, m, 64);
+        n_rec += __shfl_xor(n_rec, m, 64);
+    }
+    if ((tid & 63) == 0) {
+        wsum[0][wave] = tri;
+        wsum[1][wave] = rec;
+        wcnt[0][wave] = n_tri;
+        wcnt[1][wave] = n_rec;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double s0 = wsum[0][0], s1 = wsum[1][0];
+        long long c0 = wcnt[0][0], c1 = wcnt[1][0];
+        for (int w = 1; w < SS_FINAL_THREADS / 64; ++w) {
+            s0 += wsum[0][w];
+            s1 += wsum[1][w];
+            c0 += wcnt[0][w];
+            c1 += wcnt[1][w];
+        }
+        const double cnt0 = (double)c0 * (double)d, cnt1 = (double)c1 * (double)d;
+        out4[0] = s0 / (cnt0 + 1e-8);
+        out4[1] = cnt0;
+        out4[2] = with_recon ? s1 / (cnt1 + 1e-8) : 0.0;
+        out4[3] = with_recon ? cnt1 : 0.0;
+    }
+}
+
+inline long long ss_row_chunks(int T) { return ((long long)T - 1 + SS_ROWS - 1) / SS_ROWS; }
+inline long long ss_col_chunks(int d) { return ((long long)d + 4 * SS_QUADS - 1) / (4 * SS_QUADS); }
+inline bool ss_mult4(long long v) { return v % 4 == 0; }
+inline bool ss_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+}  // namespace
+
+// partial sums of one call: b * ceil((t_len - 1) / 64) * ceil(d / 1024); -1 when the final's chains would pass 4096 terms
+extern "C" long long umlh_stepstats_partials(int B, int T, int d) {
+    const long long per_seq = ss_row_chunks(T) * ss_col_chunks(d);
+    if (per_seq > SS_MAX_PARTIALS) return -1;
+    const long long p = per_seq * B;
+    return p > SS_MAX_PARTIALS ? -1 : p;
+}
+
+extern "C" unsigned long long umlh_stepstats_bytes(int B, int T, int d) {
+    const long long p = umlh_stepstats_partials(B, T, d);
+    return ((unsigned long long)(p > 0 ? p : 1) * 2 * sizeof(double) + 255) / 256 * 256;
+}
+
+extern "C" int umlh_stepstats_launch(const float* x, long long ldb, long long ldt, const float* recon, long long ldb_r, long long ldt_r,
+                                     int B, int T, int d, const long long* lengths, double* out4, void* scratch, hipStream_t st) {
+    double* partial = reinterpret_cast<double*>(scratch);
+    const long long p = umlh_stepstats_partials(B, T, d);
+    if (p > 0) {                                                          // t_len == 1 has no pair: the final alone writes zeros
+        const int quads = (d + 3) / 4;
+        int lanes = 4;
+        while (lanes < quads && lanes < SS_QUADS) lanes *= 2;
+        const int col_chunks = (int)ss_col_chunks(d);
+        const bool wide = ss_mult4(d) && ss_mult4(ldb) && ss_mult4(ldt) && ss_aligned16(x) &&
+                          (!recon || (ss_mult4(ldb_r) && ss_mult4(ldt_r) && ss_aligned16(recon)));
+        const dim3 grid((unsigned)(ss_row_chunks(T) * col_chunks), (unsigned)B);
+        if (wide)
+            hipLaunchKernelGGL(stats_partial<float4>, grid, dim3(256), 0, st, x, ldb, ldt, recon, ldb_r, ldt_r, T, d, lengths, col_chunks,
+                               lanes, partial);
+        else
+            hipLaunchKernelGGL(stats_partial<float>, grid, dim3(256), 0, st, x, ldb, ldt, recon, ldb_r, ldt_r, T, d, lengths, col_chunks,
+                               lanes, partial);
+    }
+    hipLaunchKernelGGL(stats_final, dim3(1), dim3(SS_FINAL_THREADS), 0, st, (const double*)partial, p > 0 ? p : 0, B, T, d, lengths,
+                       recon ? 1 : 0, out4);
+    return (int)hipGetLastError();
+}

@@ -153,6 +153,11 @@ int umlh_capture_launch_compact(const float* z, int B, int T, int d, long long l
                                 int drop_last, float* out, long long ldo, long long out_rows, long long* rows_total, hipStream_t st);
 int umlh_capture_launch_cosine(const float* a, long long lda, const float* b, long long ldb, long long n, int d, double eps,
                                double* out2, float* rows, void* scratch, hipStream_t st);
+// ---- umlh_kernels_stepstats.hip: per-step logged statistics (trivial next-frame error, masked reconstruction error) ----
+long long umlh_stepstats_partials(int B, int T, int d);       // partial sums of one call; -1: more than the final kernel takes
+unsigned long long umlh_stepstats_bytes(int B, int T, int d);
+int umlh_stepstats_launch(const float* x, long long ldb, long long ldt, const float* recon, long long ldb_r, long long ldt_r, int B, int T,
+                          int d, const long long* lengths, double* out4, void* scratch, hipStream_t st);
 
 // ---- umlh_api.cpp, for umlh_encoder.cpp ----
 // out[M,N] (ldo == N) = epilogue(A B^T) with the operand layouts of umlh_gemm_f32.  `splits` K-slabs go to `slabs`

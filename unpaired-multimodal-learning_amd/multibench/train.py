@@ -7,8 +7,11 @@ in eval mode, masked-mean pooling and binary logistic probes, all on the HIP ker
 of the y modality (train.py:302-345,380-389) on the HIP kernels of ``umlh.spectral``.
 ``train(capture_embeddings_during_training=True)`` adds the reference's embedding capture (train.py:300-347,456-512,533-536):
 a fixed sample of sequence pairs through the model at every in-loop evaluation, its valid rows packed by ``umlh.seq_compact``
-and compared by ``umlh.align`` and ``umlh.paired_cosine`` (``multibench.capture``).  The other per-batch diagnostics of the
-reference (the covariance matrices it forms and drops, wandb: train.py:386,388,428-443) are outside this port."""
+and compared by ``umlh.align`` and ``umlh.paired_cosine`` (``multibench.capture``).
+``train(step_diagnostics=True)`` records the remaining ``train/*`` values the reference logs after every optimizer step
+(train.py:403-439): the trivial next-frame losses and ``recon_y_loss`` on the HIP kernel of ``umlh.seq_step_stats``, and the
+norms, ``loss_private`` and ``diff_next_*`` the forward already returns.  The covariance matrices the reference forms and drops
+(train.py:386,388) and wandb itself are outside this port."""
 from __future__ import annotations
 
 import copy
@@ -218,9 +221,29 @@ def _fixed_sample_rank(loader, modality, ds_name, dev, n_samples=1000):
     return _sample_rank(seqs, lens, dev)
 
 
+def _record_diagnostics(diag, out, x1, l1, x2, l2, dev):
+    """Appends one step's logged values (train.py:403-433) to the lists of ``diag`` as 0-d device tensors; nothing is read back.
+    x and y take one ``umlh.seq_step_stats`` call each, y's with ``y_recon`` so that its rows t + 1 serve both statistics.
+    The two loss norms need no device work: ``train`` takes |loss| of the values it reads back anyway."""
+    import umlh
+    seq = lambda t: t.unsqueeze(1) if t.ndim == 2 else t
+    put = lambda k, v: diag.setdefault(k, []).append(v.detach())
+    with torch.cuda.device(dev):
+        if x1 is not None:
+            put("trivial_loss_x", umlh.seq_step_stats(seq(x1), l1)[umlh.stepstats.TRIVIAL])
+        if x2 is not None:
+            s = umlh.seq_step_stats(seq(x2), l2, recon=out["y_recon"].detach())
+            put("trivial_loss_y", s[umlh.stepstats.TRIVIAL])
+            put("recon_y_loss", s[umlh.stepstats.RECON])
+    put("loss_private", out["loss_private"])
+    for k in ("diff_next_x", "diff_next_y"):
+        if out[k] is not None:
+            put(k, out[k])
+
+
 def train(model, train_mode, train_loader_1, train_loader_2, optimizer, modalities=[0, 2], num_epoch=100, step_k=30,
           ds_name="mosi", eval_config={}, alpha_x=1.0, alpha_y=1.0, capture_embeddings_during_training=False, augment=False,
-          debug=False, args=None, device="cuda:0", on_step=None, effective_rank=False):
+          debug=False, args=None, device="cuda:0", step_diagnostics=False, on_step=None, effective_rank=False):
     """Returns {'loss_x': [...], 'loss_y': [...], 'loss': [...]} with one entry per batch pair
     (device tensors are read back once at the end).  With a non-empty ``eval_config`` ({'train', 'val', 'test': batch
     lists, 'freq': int}) it evaluates as the reference does (train.py:350,440-451,519-523): ``evaluate_raw_data`` once,
@@ -241,11 +264,18 @@ def train(model, train_mode, train_loader_1, train_loader_2, optimizer, modaliti
     ``val/mknn_*`` and ``val/cos_sim_*`` values of train.py:492-512 to that entry of 'eval' (not to the closing one, as in the
     reference).  The dict then also holds 'embeddings' = {'x1': [E, N, z], 'x2': [E, N, z] (fp32 device stacks of the packed zx
     and zy rows, one per capture, in capture order), 'x1_label', 'x2_label'} (train.py:533-536).  With ``effective_rank`` as
-    well, 'gt_effective_rank_y' is computed from the capture's y sample, as the reference does (:345,:387)."""
+    well, 'gt_effective_rank_y' is computed from the capture's y sample, as the reference does (:345,:387).
+
+    ``step_diagnostics=True`` adds the other values the reference logs at every step (train.py:403-439), one list per key and
+    one entry per batch pair, enqueued on the training stream and read back at the end with the losses: 'trivial_loss_x' (with
+    'x' in ``train_mode``) and 'trivial_loss_y', 'recon_y_loss' (with 'y' in it) from ``umlh.seq_step_stats`` on the step's own
+    inputs and ``y_recon``; 'loss_x_norm', 'loss_y_norm' (``torch.norm`` of a 0-d tensor is |loss|: taken from the losses read back); 'loss_private'; and
+    'diff_next_x' / 'diff_next_y' for the modalities present."""
     model.train()
     dev = torch.device(device)
     rec_x, rec_y, rec_l, rec_rank = [], [], [], []
     want_rank = bool(effective_rank) and "y" in train_mode
+    diag = {} if step_diagnostics else None
     capture, cap_x, cap_y = None, [], []
     if capture_embeddings_during_training:
         from .capture import EmbeddingCapture, take_fixed_samples
@@ -288,6 +318,8 @@ def train(model, train_mode, train_loader_1, train_loader_2, optimizer, modaliti
                 import umlh
                 with torch.cuda.device(dev):
                     rec_rank.append(umlh.effective_rank_seq(out["y_recon"].detach(), l2, drop_last=1)[0])
+            if diag is not None:
+                _record_diagnostics(diag, out, x1, l1, x2, l2, dev)
             if on_step is not None:
                 on_step(epoch, i_batch, out, loss)
             if eval_config and i_batch % eval_config["freq"] == 0:
@@ -306,6 +338,9 @@ def train(model, train_mode, train_loader_1, train_loader_2, optimizer, modaliti
     if want_rank:
         res["pred_effective_rank_y"] = stack(rec_rank)
         res["gt_effective_rank_y"] = float(gt_rank.cpu())
+    if diag is not None:
+        res.update({k: stack(v) for k, v in diag.items()})
+        res["loss_x_norm"], res["loss_y_norm"] = [abs(v) for v in res["loss_x"]], [abs(v) for v in res["loss_y"]]
     if eval_config:
         res["raw"], res["eval"] = raw_results, evals
     if capture is not None:

@@ -20,6 +20,8 @@ from .spectral import effective_rank, effective_rank_seq, principal_subspace, sv
 from .align import svcca, svcca_terms  # noqa: F401,E402
 from . import capture  # noqa: F401,E402
 from .capture import paired_cosine, seq_compact  # noqa: F401,E402
+from . import stepstats  # noqa: F401,E402
+from .stepstats import seq_step_stats  # noqa: F401,E402
 
 
 def host_cpu_budget() -> int:

@@ -20,7 +20,7 @@ PREC_IDS = {"fp32": 0, "bf16": 1}
 N_CORE_SCALARS = 8
 N_SCALARS = 12
 
-SOURCES = ["umlh_p2p.hip", "umlh_kernels_f32.hip", "umlh_kernels_bf16.hip", "umlh_kernels_micro.hip", "umlh_kernels_seq.hip", "umlh_kernels_enc.hip", "umlh_kernels_align.hip", "umlh_kernels_align_ext.hip", "umlh_kernels_probe.hip", "umlh_kernels_spectral.hip", "umlh_kernels_capture.hip", "umlh_api.cpp", "umlh_encoder.cpp"]
+SOURCES = ["umlh_p2p.hip", "umlh_kernels_f32.hip", "umlh_kernels_bf16.hip", "umlh_kernels_micro.hip", "umlh_kernels_seq.hip", "umlh_kernels_enc.hip", "umlh_kernels_align.hip", "umlh_kernels_align_ext.hip", "umlh_kernels_probe.hip", "umlh_kernels_spectral.hip", "umlh_kernels_capture.hip", "umlh_kernels_stepstats.hip", "umlh_api.cpp", "umlh_encoder.cpp"]
 
 
 class UmlhError(RuntimeError):
@@ -189,6 +189,9 @@ def _prototypes() -> dict:
         "umlh_seq_compact": (rc, (vp, i32, i32, i32, i64, i64, vp, i32, vp, i64, i64, vp, vp)),
         "umlh_paired_cosine_scratch_bytes": (u64, (i64, i32)),
         "umlh_paired_cosine": (rc, (vp, i64, vp, i64, i64, i32, f64, vp, vp, vp, u64, vp)),
+        # per-step logged statistics: trivial next-frame error, masked reconstruction error
+        "umlh_seq_step_stats_scratch_bytes": (u64, (i32, i32, i32)),
+        "umlh_seq_step_stats": (rc, (vp, i64, i64, vp, i64, i64, i32, i32, i32, vp, vp, vp, u64, vp)),
     }
 
 
