@@ -306,3 +306,57 @@ def test_train_loop_with_bias_head(precision, monkeypatch):
     assert a["iter"] == b["iter"] and abs(a["val_acc"] - b["val_acc"]) <= 0.01
     tol = 2e-4 if precision == "fp32" else 2e-2
     np.testing.assert_allclose(a["train_scalars"][:, :2].numpy(), b["train_scalars"][:, :2].numpy(), atol=tol, rtol=tol)
+
+
+def test_late_early_stop_leaves_host_state_as_an_unpipelined_ending():
+    """train() reads an evaluation one block late.  Run A stops at the evaluation of iteration 20 (lr so small that no fp32
+    weight moves: it ties with iteration 0, patience 1) after the block 21..40 has been enqueued, and must take that block
+    back; run B, from the same seeds, simply ends on iteration 20 (max_iters 21, scheduler still built for 200).  Both
+    leave optimizer, scheduler, generator and loaders in the same state."""
+    import finetune as ft
+    from engine.datasets.utils import FeatureLoader, FeatureTable
+    from engine.models.head import UMLClip
+    from engine.optimizer.optim import build_optimizer
+    from engine.optimizer.scheduler import build_lr_scheduler
+    tr, va, te, (xt, yt), C = _toy_dataset()
+    tables = {"train": FeatureTable(*tr, DEV), "val": FeatureTable(*va, DEV), "test": FeatureTable(*te, DEV),
+              "text": FeatureTable(xt, yt, DEV)}
+
+    def run(max_iters, patience):
+        torch.manual_seed(7)
+        gen = torch.Generator()
+        gen.manual_seed(7)
+        model = UMLClip(tr[0].shape[1], C, logit_scale_init=4.60517, bias=False, learnable_temp=False).to(DEV)
+        optimizer = build_optimizer(model.parameters(), "adamw", 1e-12, 0.0)
+        scheduler = build_lr_scheduler(optimizer, "cosine", 50, 200, warmup_type="linear", warmup_lr=1e-12)
+        il = FeatureLoader(tables["train"], 16, shuffle=True, kind="image", generator=gen)
+        tl = FeatureLoader(tables["text"], 16, shuffle=True, kind="text", generator=gen)
+        vl = FeatureLoader(tables["val"], 16, shuffle=False, generator=gen)
+        tel = FeatureLoader(tables["test"], 16, shuffle=False, generator=gen)
+        out = ft.train(model, il, tl, vl, tel, optimizer, scheduler, device=DEV, max_iters=max_iters, eval_freq=20,
+                       patience=patience)
+        return out, optimizer, scheduler, gen, il, tl
+
+    a, b = run(200, 1), run(21, 100)
+    assert a[0]["iter"] == 0                                       # the tie at 20 did not count as an improvement ...
+    assert len(a[0]["train_scalars"]) == len(b[0]["train_scalars"]) == 21    # ... and both runs end on iteration 20
+    (oa, opt_a, sch_a, gen_a, il_a, tl_a), (ob, opt_b, sch_b, gen_b, il_b, tl_b) = a, b
+    assert opt_a.step_count == opt_b.step_count == 21
+    assert sch_a.last_epoch == sch_b.last_epoch
+    assert torch.equal(gen_a.get_state(), gen_b.get_state())
+    sa, sb = list(opt_a.state.values()), list(opt_b.state.values())
+    assert len(sa) == len(sb) > 0
+    n_tensors = 0
+    for pa, pb in zip(sa, sb):
+        assert pa.keys() == pb.keys()
+        for k in pa:
+            if torch.is_tensor(pa[k]):
+                assert torch.equal(pa[k], pb[k]), k
+                n_tensors += 1
+            else:
+                assert pa[k] == pb[k], k
+    assert n_tensors > 0
+    assert torch.equal(oa["train_scalars"], ob["train_scalars"])
+    for la, lb in ((il_a, il_b), (tl_a, tl_b)):                     # the next batch each training loader would hand out
+        assert torch.equal(next(la.iter_index()), next(lb.iter_index()))
+    assert torch.equal(gen_a.get_state(), gen_b.get_state())

@@ -284,3 +284,18 @@ def test_head_optimizer_step_refuses_packed_bias_views_with_a_clear_error():
     opt = build_optimizer([w], "adamw", 1e-3, 0.01)
     with pytest.raises(umlh.UmlhError, match="packed"):
         opt.step()
+
+
+def test_run_settle_applies_the_reference_early_stopping_rule():
+    """The one place the fine-tune loops decide best snapshot and early stop (finetune._Run.settle, used by train and
+    train_grouped) follows the reference's rule (finetune.py:247-271): strict '>', the counter resets on improvement, the
+    run stops when the counter reaches the patience."""
+    from finetune import _Run
+    run = _Run(max_iters=1000, patience=2)
+    seen = []
+    for i_eval, acc in ((0, 0.50), (100, 0.50), (200, 0.60), (300, 0.60), (400, 0.55)):
+        stop = run.settle(i_eval, 1.0 - acc, acc)
+        seen.append((stop, run.out["iter"], run.no_improve))
+    assert seen == [(False, 0, 0), (False, 0, 1), (False, 200, 0), (False, 200, 1), (True, 200, 2)]
+    assert (run.out["iter"], run.out["val_acc"], run.out["val_loss"]) == (200, 0.60, 1.0 - 0.60)
+    assert not run.live and run.last_i == 400      # stopped AT the evaluation that ran out of patience

@@ -122,10 +122,6 @@ def feature_direction_sim(model, img_rows, txt_rows):
     return float(fi @ ft) / den if den > 0 else float("nan")
 
 
-def _state_dict_cpu(model):
-    return {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
-
-
 def _state_dict_snapshot(model):
     """Best-model snapshot (finetune.py:249) kept ON THE DEVICE: an asynchronous clone instead of a device-to-host copy
     and a host sync at every evaluation point; it is moved to the CPU once, when train() returns it."""
@@ -200,111 +196,161 @@ def _rewind(r, optimizer, scheduler):
     scheduler.step(r["epoch"])
 
 
+class _Run:
+    """One head's training state, driven by ``train`` (alone) and ``train_grouped`` (many in lockstep): position, the
+    per-step scalars, the best evaluation so far and the patience counter.
+
+    Evaluation results may be read one block LATE: the evaluation and its device-to-host copy are enqueued, then the next
+    training block, and only then does the host wait for the copy -- the GPU goes from the evaluation straight into the
+    next block instead of idling while the host reads, decides and prepares.  If the late result says "early stop",
+    everything the extra block advanced is rewound to the evaluation point (loader positions and RNG streams, optimizer /
+    scheduler counters and moments; the weights are replaced by the best snapshot anyway), so every object is left exactly
+    as the reference's loop would leave it (finetune.py:247-271)."""
+
+    def __init__(self, *, max_iters, patience, alpha=1.0, precision="fp32", model=None, val_loader=None, test_loader=None,
+                 optimizer=None, scheduler=None, img_src=None, txt_src=None, engine=None, scalars=None, name=None):
+        self.max_iters, self.patience, self.alpha, self.precision, self.name = max_iters, patience, alpha, precision, name
+        self.model, self.val_loader, self.test_loader = model, val_loader, test_loader
+        self.optimizer, self.scheduler = optimizer, scheduler
+        self.img_src, self.txt_src, self.engine, self.scalars = img_src, txt_src, engine, scalars
+        self.out = {"iter": None, "val_acc": None, "model": None, "val_classwise": None, "val_loss": None,
+                    "model_records": []}
+        self.i, self.last_i = 0, -1     # iteration being run / last iteration that counts
+        self.live = max_iters > 0       # False once the head has stopped early or run all its iterations
+        self.no_improve = 0
+        self.snap = None                # device snapshot of the evaluation that has not been settled yet
+        self.back = None                # rewind point of the block drawn since that evaluation began
+
+    @classmethod
+    def of(cls, model, image_loader, text_loader, val_loader, test_loader, optimizer, scheduler, max_iters, alpha, patience,
+           precision, diagnostics, name=None):
+        """The state of a run of ``train`` with these arguments, with its row sources, engine and scalar buffer."""
+        model.train()
+        assert image_loader is not None or text_loader is not None, "At least one of the loaders should be provided"
+        dev = model.head.weight.device
+        img_src = _RowSource(image_loader, dev, "image", precision) if image_loader is not None else None
+        txt_src = _RowSource(text_loader, dev, "text", precision) if text_loader is not None else None
+        engine = model.fused_engine(optimizer, max_rows_img=img_src.capacity if img_src else 32,
+                                    max_rows_txt=txt_src.capacity if txt_src else 32, precision=precision)
+        # (heads with bias: the engine restricts the diagnostics to the weight columns of the packed [weight | bias | padding]
+        # rows -- the reference's are over head.weight only, finetune.py:190-191)
+        engine.enable_diagnostics(diagnostics)
+        return cls(max_iters=max_iters, patience=patience, alpha=alpha, precision=precision, model=model,
+                   val_loader=val_loader, test_loader=test_loader, optimizer=optimizer, scheduler=scheduler,
+                   img_src=img_src, txt_src=txt_src, engine=engine, name=name,
+                   scalars=torch.zeros(max_iters, umlh.N_SCALARS, dtype=torch.float32, device=dev))
+
+    @property
+    def indexed(self):
+        return all(src is None or src.indexed for src in (self.img_src, self.txt_src))
+
+    def next_block(self, eval_freq, rewindable=False):
+        """Draw all steps up to and including the next evaluation point (or the final iteration) and advance the optimizer's
+        step count, the scheduler and ``i`` past them; returns (n, the keyword arguments of ``HeadEngine.train_steps``).
+        ``rewindable``: an evaluation is still unread -- take the rewind point ``settle`` needs if it turns out a stop."""
+        self.back = _rewind_point(self.img_src, self.txt_src, self.optimizer, self.scheduler) if rewindable else None
+        i_end = _block_end(self.i, self.max_iters, eval_freq)
+        n = i_end - self.i + 1
+        bi, bt = _draw_block(self.img_src, self.txt_src, n)
+        opt, sch, img, txt = self.optimizer, self.scheduler, self.img_src, self.txt_src
+        kw = dict(img_table=img.table(self.precision) if img else None, img_index_batches=bi,
+                  txt_table=txt.table(self.precision) if txt else None, txt_index_batches=bt, lrs=sch.lr_table(n),
+                  first_step=opt.step_count + 1, alpha=self.alpha, img_alpha=1.0, scalars_out=self.scalars[self.i:self.i + n])
+        opt.step_count += n
+        sch.step(sch.last_epoch + n)
+        self.i = self.last_i = i_end
+        return n, kw
+
+    def advance(self):
+        self.i += 1
+        self.live = self.live and self.i < self.max_iters
+
+    def begin_eval(self):
+        """Evaluation at iteration ``i``: keeps the device snapshot a new best would need and returns the (model, loader)
+        pairs and the step's scalar row for ``validate_many_begin`` (the caller puts the model in eval mode around it)."""
+        self.snap = _state_dict_snapshot(self.model)          # device-side clone; moved to the CPU by finish()
+        self.back = None
+        pairs = [(self.model, self.val_loader)] + ([(self.model, self.test_loader)] if self.test_loader is not None else [])
+        return pairs, self.scalars[self.i]
+
+    def settle(self, i_eval, val_loss, val_acc):
+        """Bookkeeping of the evaluation begun at iteration ``i_eval``: strict-improvement best, patience.  True = the head
+        stops at ``i_eval``; a block drawn since the evaluation began is taken back."""
+        snap, self.snap = self.snap, None
+        if self.out["val_acc"] is None or val_acc > self.out["val_acc"]:
+            self.out.update(iter=i_eval, val_acc=val_acc, val_loss=val_loss, model=snap)
+            self.no_improve = 0
+        else:
+            self.no_improve += 1
+        if self.no_improve < self.patience:
+            return False
+        if self.back is not None:
+            _rewind(self.back, self.optimizer, self.scheduler)
+        self.live = False
+        self.i = self.last_i = i_eval
+        return True
+
+    def finish(self):
+        """Status check, best weights back into the model; the returned dict holds them (on the CPU) and the per-step
+        losses / accuracies (``train_scalars``, an extension)."""
+        _check_micro(self.engine)
+        self.model.load_state_dict(self.out["model"])
+        self.out["model"] = _to_cpu(self.out["model"])
+        self.out["train_scalars"] = self.scalars[:self.last_i + 1].cpu()
+        return self.out
+
+
 def train(model, image_loader, text_loader, val_loader, test_loader, optimizer, scheduler, device="cuda",
           max_iters=1000, alpha=1.0, eval_freq=EVAL_FREQ, patience=5, capture_features_during_training=False,
           features_pth="./", args=None, logger=None, precision="fp32", diagnostics=None):
-    out = {"iter": None, "val_acc": None, "model": None, "val_classwise": None, "val_loss": None,
-           "model_records": []}
-    model.train()
-    assert image_loader is not None or text_loader is not None, "At least one of the loaders should be provided"
-    if capture_features_during_training:
-        print("=> capture_features_during_training is a logging-only diagnostic; not on the fused path (ignored)")
-    dev = model.head.weight.device
-    img_src = _RowSource(image_loader, dev, "image", precision) if image_loader is not None else None
-    txt_src = _RowSource(text_loader, dev, "text", precision) if text_loader is not None else None
-    engine = model.fused_engine(optimizer, max_rows_img=img_src.capacity if img_src else 32,
-                                max_rows_txt=txt_src.capacity if txt_src else 32, precision=precision)
     # per-step gradient diagnostics (finetune.py:190-191,203-206): the reference computes them on every
     # step; here they cost ~2.5 us per step, so they are on when a logger asks for them (or on request)
     want_diag = bool(diagnostics) if diagnostics is not None else logger is not None
-    # (heads with bias: the engine restricts them to the weight columns of the packed [weight | bias | padding] rows -- the
-    # reference's diagnostics are over head.weight only, finetune.py:190-191)
-    engine.enable_diagnostics(want_diag)
-    scalars = torch.zeros(max_iters, umlh.N_SCALARS, dtype=torch.float32, device=dev)
-    no_improve = 0
-    img_alpha = 1.0
-    last_i = -1
-    blockwise = logger is None and (img_src is None or img_src.indexed) and (txt_src is None or txt_src.indexed)
+    run = _Run.of(model, image_loader, text_loader, val_loader, test_loader, optimizer, scheduler, max_iters, alpha,
+                  patience, precision, want_diag)
+    if capture_features_during_training:
+        print("=> capture_features_during_training is a logging-only diagnostic; not on the fused path (ignored)")
+    img_src, txt_src, engine, scalars = run.img_src, run.txt_src, run.engine, run.scalars
+    blockwise = logger is None and run.indexed
 
-    # Evaluation points (finetune.py:247-271).  Blockwise runs read an evaluation's results one block LATE: the evaluation and
-    # its device-to-host copy are enqueued, then the next training block, and only then does the host wait for the copy --
-    # the GPU goes from the evaluation straight into the next block instead of idling while the host reads, decides and
-    # prepares.  If the late result says "early stop", everything the extra block advanced is rewound to the evaluation
-    # point (loader positions and RNG streams, optimizer / scheduler counters and moments; the weights are replaced by the
-    # best snapshot anyway), so train() leaves every object exactly as the reference's loop would.
-    def eval_begin(i):
-        snap = _state_dict_snapshot(model)                    # device-side clone; moved to the CPU on return
-        model.eval()
-        h = validate_many_begin([(model, val_loader)] + ([(model, test_loader)] if test_loader is not None else []),
-                                extra=[scalars[i]])
-        model.train()
-        return {"i": i, "snap": snap, "h": h}
-
-    def eval_end(p):
-        """Bookkeeping of the evaluation at iteration p["i"]; True = stop training."""
-        nonlocal no_improve
-        i = p["i"]
-        res, (s,) = validate_many_end(p["h"])
+    def eval_end(i, handle):
+        """Reads the evaluation begun at iteration i, settles it and reports as the reference does; True = stop training."""
+        res, (s,) = validate_many_end(handle)
         val_loss, val_acc = res[0]
-        testlog = f" | Test Acc: {res[1][1]:.4f}" if test_loader is not None else ""
-        if out["val_acc"] is None or val_acc > out["val_acc"]:
-            out.update(iter=i, val_acc=val_acc, val_loss=val_loss, model=p["snap"])
-            no_improve = 0
-        else:
-            no_improve += 1
+        stop = run.settle(i, val_loss, val_acc)
         if logger is not None:
             logger.log({"val/val_loss": val_loss, "val/val_acc": val_acc, "iter": i})
         _check_micro(engine, s, f" at iter {i}")
+        testlog = f" | Test Acc: {res[1][1]:.4f}" if test_loader is not None else ""
         print(f"Iter {i} | Img Loss: {s[umlh.S_LOSS_IMG]:.4f} | Text Loss: {s[umlh.S_LOSS_TXT]:.4f} | "
               f"Img Acc: {s[umlh.S_ACC_IMG]:.4f} | Text Acc: {s[umlh.S_ACC_TXT]:.4f} | Val Loss: {val_loss:.4f} | "
-              f"Val Acc {val_acc:.4f}{testlog} | Count {no_improve}/{patience}")
-        if no_improve >= patience:
+              f"Val Acc {val_acc:.4f}{testlog} | Count {run.no_improve}/{patience}")
+        if stop:
             print(f"=> Early stopping at Iter {i}")
-            return True
-        return False
+        return stop
 
-    def rewind_point():
-        return _rewind_point(img_src, txt_src, optimizer, scheduler)
-
-    def rewind(r):
-        _rewind(r, optimizer, scheduler)
-
-    pending = None            # evaluation whose results have not been read yet (blockwise runs only)
-    stopped = False
-    i = 0
-    while i < max_iters:
+    pending = None            # (iteration, handle) of the evaluation whose results have not been read yet (blockwise runs only)
+    while run.live:
         if blockwise:
             # all steps up to and including the next evaluation point in ONE C call:
             # no Python, no host sync between steps
-            back = rewind_point() if pending is not None else None
-            i_end = _block_end(i, max_iters, eval_freq)
-            n = i_end - i + 1
-            bi, bt = _draw_block(img_src, txt_src, n)
-            lrs = scheduler.lr_table(n)
-            engine.train_steps(img_src.table(precision) if img_src else None, bi,
-                               txt_src.table(precision) if txt_src else None, bt, lrs,
-                               first_step=optimizer.step_count + 1, alpha=alpha, img_alpha=img_alpha,
-                               scalars_out=scalars[i:i + n])
-            optimizer.step_count += n
-            scheduler.step(scheduler.last_epoch + n)
+            n, kw = run.next_block(eval_freq, rewindable=pending is not None)
+            engine.train_steps(**kw)
             if pending is not None:
                 p, pending = pending, None
-                if eval_end(p):                               # the block just enqueued ran past an early stop: take it back
-                    rewind(back)
-                    last_i = p["i"]
-                    stopped = True
+                if eval_end(*p):                              # the block just enqueued ran past an early stop: taken back
                     break
-            i = i_end
         else:
             img_rows = img_src.next() if img_src is not None else None
             txt_rows = txt_src.next() if txt_src is not None else None
             if logger is not None:                   # with the pre-update projection, as the reference (:182-183)
                 feat_sim = feature_direction_sim(model, img_rows, txt_rows)
             engine.train_step(img_rows, txt_rows, lr=optimizer.param_groups[0]["lr"], step=optimizer.step_count + 1,
-                              alpha=alpha, img_alpha=img_alpha, scalars_out=scalars[i])
+                              alpha=alpha, img_alpha=1.0, scalars_out=scalars[run.i])
             optimizer.step_count += 1
             scheduler.step()
-        last_i = i
+            run.last_i = run.i
+        i = run.i
         if logger is not None:
             s = scalars[i].cpu()                      # host sync: only when a logger asks for per-step values
             # finetune.py:236-240 (the CKA / mutual-kNN / in-class-distance entries belong to the
@@ -317,23 +363,20 @@ def train(model, image_loader, text_loader, val_loader, test_loader, optimizer, 
                         "train/txt_grad_norm": gd["txt_grad_norm"], "train/grad_agreement_rate": gd["grad_agreement_rate"],
                         "train/feature_direction_sim": feat_sim})
         if i % eval_freq == 0:
-            p = eval_begin(i)
+            pairs, row = run.begin_eval()
+            model.eval()
+            p = (i, validate_many_begin(pairs, extra=[row]))
+            model.train()
             if blockwise and i + 1 < max_iters:
                 pending = p                                   # read after the next block has been enqueued
-            elif eval_end(p):
-                stopped = True
+            elif eval_end(*p):
                 break
-        i += 1
-    if pending is not None and not stopped:
-        eval_end(pending)
-    _check_micro(engine)
-    model.load_state_dict(out["model"])
-    out["model"] = _to_cpu(out["model"])
+        run.advance()
+    out = run.finish()
     val_loss, val_acc = validate(model, val_loader, device=device)
     if logger is not None:
         logger.log({"val/best_val_loss": val_loss, "val/best_val_acc": val_acc, "iter": out["iter"]})
     print(f"=> Best Val Loss {val_loss:.4f}, Val Acc {val_acc:.4f} at Iter {out['iter']}")
-    out["train_scalars"] = scalars[:last_i + 1].cpu()   # per-step losses / accuracies (extension)
     return out
 
 
@@ -345,76 +388,36 @@ def train_grouped(runs, device="cuda", eval_freq=EVAL_FREQ, precision="fp32"):
     exact semantics of ``train`` (evaluation cadence, strict-improvement best snapshot, patience, restored weights,
     returned dict); ``runs`` = dicts with the arguments of ``train`` (model, image_loader, text_loader, val_loader,
     test_loader, optimizer, scheduler, max_iters, alpha, patience)."""
-    st = []
-    for r in runs:
-        model = r["model"]
-        model.train()
-        assert r.get("image_loader") is not None or r.get("text_loader") is not None, "At least one of the loaders should be provided"
-        dev = model.head.weight.device
-        img_src = _RowSource(r["image_loader"], dev, "image", precision) if r.get("image_loader") is not None else None
-        txt_src = _RowSource(r["text_loader"], dev, "text", precision) if r.get("text_loader") is not None else None
-        if not all(src is None or src.indexed for src in (img_src, txt_src)):
-            raise umlh.UmlhError("train_grouped needs FeatureLoader inputs (device-resident tables)")
-        engine = model.fused_engine(r["optimizer"], max_rows_img=img_src.capacity if img_src else 32,
-                                    max_rows_txt=txt_src.capacity if txt_src else 32, precision=precision)
-        engine.enable_diagnostics(False)
-        st.append(dict(r, img_src=img_src, txt_src=txt_src, engine=engine, i=0, last_i=-1, no_improve=0, live=True,
-                       scalars=torch.zeros(r["max_iters"], umlh.N_SCALARS, dtype=torch.float32, device=dev),
-                       out={"iter": None, "val_acc": None, "model": None, "val_classwise": None, "val_loss": None,
-                            "model_records": []}))
+    st = [_Run.of(r["model"], r.get("image_loader"), r.get("text_loader"), r["val_loader"], r.get("test_loader"),
+                  r["optimizer"], r["scheduler"], r["max_iters"], r["alpha"], r["patience"], precision, False,
+                  name=r.get("name", k)) for k, r in enumerate(runs)]
+    if not all(h.indexed for h in st):
+        raise umlh.UmlhError("train_grouped needs FeatureLoader inputs (device-resident tables)")
     # Evaluation results are read one round LATE, as in train(): a round enqueues the next block of every live head first and
-    # only then waits for the previous round's evaluation copy, so the GPU runs while the host reads, decides and prepares.
-    # A head whose late result is an early stop has its extra block rewound (loader / RNG / optimizer state; the weights are
-    # replaced by its best snapshot at the end).  Needs private loader generators (a generator shared between heads cannot be
-    # rewound for one of them): otherwise every round reads its own evaluation before the next block is drawn.
-    def private(h):
-        return all(src is None or getattr(src.loader, "generator", None) is not None for src in (h["img_src"], h["txt_src"]))
-    pipelined = all(private(h) for h in st)
+    # only then waits for the previous round's evaluation copy.  Needs private loader generators (a generator shared between
+    # heads cannot be rewound for one of them): otherwise every round reads its own evaluation before the next block is drawn.
+    pipelined = all(src is None or getattr(src.loader, "generator", None) is not None
+                    for h in st for src in (h.img_src, h.txt_src))
 
     def settle(due, at, handle):
-        """Bookkeeping of the evaluations `handle` holds (head h evaluated at iteration at[k]): best snapshot, patience; a head
-        that stops is rewound to its evaluation point if a block was enqueued for it since."""
+        """Reads the evaluations `handle` holds (head due[k] evaluated at iteration at[k]) and settles each head's."""
         res, ex = validate_many_end(handle)
         k = 0
-        for j, (h, i_eval) in enumerate(zip(due, at)):
-            if j < len(ex) and not bool(torch.isfinite(ex[j]).all()):   # (status words are read for every head when the sweep ends)
-                _check_micro(h["engine"], ex[j], f" at iter {i_eval} of grid point {h.get('name', j)}")
-            val_loss, val_acc = res[k]
-            k += 2 if h.get("test_loader") is not None else 1
-            out = h["out"]
-            if out["val_acc"] is None or val_acc > out["val_acc"]:
-                out.update(iter=i_eval, val_acc=val_acc, val_loss=val_loss, model=h.pop("snap"))
-                h["no_improve"] = 0
-            else:
-                h["no_improve"] += 1
-                h.pop("snap")
-            if h["no_improve"] >= h["patience"]:                    # early stopping of this head at i_eval
-                if h["live"] and h.get("back") is not None:         # ... one block ago: take that block back
-                    _rewind(h["back"], h["optimizer"], h["scheduler"])
-                h["live"] = False
-                h["i"] = h["last_i"] = i_eval
+        for h, i_eval, s in zip(due, at, ex):
+            if not bool(torch.isfinite(s).all()):                   # (status words are read for every head when the sweep ends)
+                _check_micro(h.engine, s, f" at iter {i_eval} of grid point {h.name}")
+            h.settle(i_eval, *res[k])
+            k += 2 if h.test_loader is not None else 1
 
     pending = None                      # (due heads, their evaluation iterations, validate_many_begin handle)
-    while any(h["live"] for h in st) or pending is not None:
+    while any(h.live for h in st) or pending is not None:
         # ---- one block per live head: all steps up to and including its next evaluation point ----
         by_n = {}
         awaited = {id(h) for h in pending[0]} if pending is not None else set()
         for h in st:
-            if not h["live"]:
-                continue
-            opt, sch = h["optimizer"], h["scheduler"]
-            h["back"] = _rewind_point(h["img_src"], h["txt_src"], opt, sch) if id(h) in awaited else None
-            i_end = _block_end(h["i"], h["max_iters"], eval_freq)
-            n = i_end - h["i"] + 1
-            bi, bt = _draw_block(h["img_src"], h["txt_src"], n)
-            job = dict(engine=h["engine"], img_table=h["img_src"].table(precision) if h["img_src"] else None, img_index_batches=bi,
-                       txt_table=h["txt_src"].table(precision) if h["txt_src"] else None, txt_index_batches=bt,
-                       lrs=sch.lr_table(n), first_step=opt.step_count + 1, alpha=h["alpha"], img_alpha=1.0,
-                       scalars_out=h["scalars"][h["i"]:h["i"] + n])
-            by_n.setdefault(n, []).append(job)
-            opt.step_count += n
-            sch.step(sch.last_epoch + n)
-            h["i"] = h["last_i"] = i_end
+            if h.live:
+                n, kw = h.next_block(eval_freq, rewindable=id(h) in awaited)
+                by_n.setdefault(n, []).append(dict(kw, engine=h.engine))
         for n, jobs in by_n.items():
             umlh.train_steps_grouped(jobs, n)
         # ---- the previous round's evaluations (the blocks above are already running) ----
@@ -422,37 +425,25 @@ def train_grouped(runs, device="cuda", eval_freq=EVAL_FREQ, precision="fp32"):
             p, pending = pending, None
             settle(*p)
         # ---- evaluation points (every live head sits on one, or on its final iteration) ----
-        due = [h for h in st if h["live"] and h["i"] % eval_freq == 0]
+        due = [h for h in st if h.live and h.i % eval_freq == 0]
         if due:
             pairs, extra = [], []
             for h in due:
-                h["snap"] = _state_dict_snapshot(h["model"])
-                h["model"].eval()
-                pairs.append((h["model"], h["val_loader"]))
-                if h.get("test_loader") is not None:
-                    pairs.append((h["model"], h["test_loader"]))
-                extra.append(h["scalars"][h["i"]])
+                head_pairs, row = h.begin_eval()
+                h.model.eval()
+                pairs += head_pairs
+                extra.append(row)
             handle = validate_many_begin(pairs, extra=extra)
             for h in due:
-                h["model"].train()
-                h["back"] = None
-            pending = (due, [h["i"] for h in due], handle)
+                h.model.train()
+            pending = (due, [h.i for h in due], handle)
             if not pipelined:                                       # shared generators: decide before the next block is drawn
                 p, pending = pending, None
                 settle(*p)
         for h in st:
-            if h["live"]:
-                h["i"] += 1
-                if h["i"] >= h["max_iters"]:
-                    h["live"] = False
-    outs = []
-    for h in st:
-        _check_micro(h["engine"])
-        h["model"].load_state_dict(h["out"]["model"])
-        h["out"]["model"] = _to_cpu(h["out"]["model"])
-        h["out"]["train_scalars"] = h["scalars"][:h["last_i"] + 1].cpu()
-        outs.append(h["out"])
-    return outs
+            if h.live:
+                h.advance()
+    return [h.finish() for h in st]
 
 
 EVAL_SLAB = 4096     # rows per forward launch of a whole-table evaluation
@@ -545,20 +536,7 @@ def validate_many(pairs, extra=None):
     first (``_eval_enqueue``), then all per-row statistics come back in a single device-to-host copy.  Used at the
     evaluation points of ``train`` (val + test) and of the grouped sweep (every head's val + test).  ``extra``: device
     float tensors (e.g. the step's scalar rows) that ride on the same copy; returns (results, extras on the CPU)."""
-    extra = list(extra or [])
-    if not all(_slab_evaluable(ld) for _, ld in pairs):
-        return [validate(m, ld) for m, ld in pairs], [e.cpu() for e in extra]
-    stats = [_eval_enqueue(m, ld) for m, ld in pairs]
-    flat = torch.cat([st.reshape(-1) for st in stats] + [e.reshape(-1).to(torch.float32) for e in extra]).cpu()
-    out, pos = [], 0
-    for (m, ld), st in zip(pairs, stats):
-        out.append(_eval_finish(flat[pos:pos + st.numel()].reshape(-1, 2), ld.batch_size))
-        pos += st.numel()
-    ex = []
-    for e in extra:
-        ex.append(flat[pos:pos + e.numel()].reshape(e.shape))
-        pos += e.numel()
-    return out, ex
+    return validate_many_end(validate_many_begin(pairs, extra))
 
 
 def validate(model, val_loader, device="cuda"):
@@ -625,6 +603,40 @@ def wants_zero_shot_init(classifier_init, modality, common_dim, text_indim):
                                               (modality == "image" and int(common_dim or 0) == int(text_indim)))
 
 
+def _build_model(tables, hparams, num_classes, modality, use_clip, clip_logit, text_indim):
+    """The head of one grid point, on the CPU, initialised from the global RNG (reference :343-346)."""
+    d_img, d_txt = tables["train"].features.shape[1], tables["text"].features.shape[1]
+    if use_clip:
+        return UMLClip(d_img, num_classes, logit_scale_init=clip_logit, bias=False, learnable_temp=hparams["learnable_temp"])
+    tin = (d_txt if text_indim is None else text_indim) if modality == "crossmodal" else (text_indim or 0)
+    return UML(d_img, tin, num_classes, bias=False, learnable_temp=hparams["learnable_temp"])
+
+
+def _build_run(tables, text_ds, hparams, *, num_classes, modality, classifier_init, use_clip, clip_logit, text_indim,
+               device, generator, order_rng, common_dim=None, model=None):
+    """One grid point with the reference's wiring (:343-391), as the arguments of ``train``: (model, image_loader,
+    text_loader, val_loader, test_loader, optimizer, scheduler); the test loader is always built.  The order -- model,
+    ``.to(device)``, zero-shot init, optimizer, scheduler, loaders -- is the order of the RNG draws, which the bit-for-bit
+    equality of farm, grouped and isolated runs rests on."""
+    if model is None:
+        model = _build_model(tables, hparams, num_classes, modality, use_clip, clip_logit, text_indim)
+    model.to(device)
+    if common_dim is None:
+        common_dim = 0 if modality == "crossmodal" else (text_indim or 0)
+    if wants_zero_shot_init(classifier_init, modality, common_dim, tables["text"].features.shape[1]):
+        model.zero_shot_init(text_ds)
+    optimizer = build_optimizer(model.parameters(), hparams["optim"], hparams["lr"], hparams["weight_decay"])
+    scheduler = build_lr_scheduler(optimizer, hparams["lr_scheduler"], hparams["warmup_iter"], hparams["max_iter"],
+                                   warmup_type=hparams["warmup_type"], warmup_lr=hparams["warmup_min_lr"])
+    bs = hparams["batch_size"]
+    kw = {"order_rng": order_rng, "generator": generator}
+    image_loader = FeatureLoader(tables["train"], bs, shuffle=True, kind="image", **kw) if modality != "text" else None
+    text_loader = FeatureLoader(tables["text"], bs, shuffle=True, kind="text", **kw) if modality != "image" else None
+    val_loader = FeatureLoader(tables["val"], bs, shuffle=False, kind="image", **kw)
+    test_loader = FeatureLoader(tables["test"], bs, shuffle=False, kind="image", **kw)
+    return model, image_loader, text_loader, val_loader, test_loader, optimizer, scheduler
+
+
 def setup_feature_run(img_train, img_val, img_test, text_ds, hparams, *, num_classes, modality="crossmodal",
                       alpha=1.0, classifier_init="zeroshot", use_clip=False, clip_logit=4.60517, text_indim=None,
                       device="cuda:0", eval_test=True, precision="fp32", eval_freq=EVAL_FREQ, tables=None,
@@ -637,36 +649,12 @@ def setup_feature_run(img_train, img_val, img_test, text_ds, hparams, *, num_cla
     are what the concurrent sweep passes in.  ``text_indim`` is ``args.text_indim`` in crossmodal mode and
     ``args.common_dim`` otherwise (the second argument of ``UML(...)``, reference :343-346); ``common_dim``
     overrides the latter."""
-    d_img = img_train[0].shape[1]
-    d_txt = text_ds.input_tensor.shape[1]
-    if model is not None:
-        pass
-    elif use_clip:
-        model = UMLClip(d_img, num_classes, logit_scale_init=clip_logit, bias=False,
-                        learnable_temp=hparams["learnable_temp"])
-    else:
-        tin = (d_txt if text_indim is None else text_indim) if modality == "crossmodal" else (text_indim or 0)
-        model = UML(d_img, tin, num_classes, bias=False, learnable_temp=hparams["learnable_temp"])
     if tables is None:
         tables = feature_tables(img_train, img_val, img_test, text_ds, device)
-    model.to(device)
-    if common_dim is None:
-        common_dim = 0 if modality == "crossmodal" else (text_indim or 0)
-    if wants_zero_shot_init(classifier_init, modality, common_dim, d_txt):
-        model.zero_shot_init(text_ds)
-    optimizer = build_optimizer(model.parameters(), hparams["optim"], hparams["lr"], hparams["weight_decay"])
-    scheduler = build_lr_scheduler(optimizer, hparams["lr_scheduler"], hparams["warmup_iter"], hparams["max_iter"],
-                                   warmup_type=hparams["warmup_type"], warmup_lr=hparams["warmup_min_lr"])
-    bs = hparams["batch_size"]
-    kw = {"order_rng": order_rng, "generator": generator}
-    image_loader = FeatureLoader(tables["train"], bs, shuffle=True, kind="image", **kw)
-    text_loader = FeatureLoader(tables["text"], bs, shuffle=True, kind="text", **kw)
-    if modality == "image":
-        text_loader = None
-    elif modality == "text":
-        image_loader = None
-    val_loader = FeatureLoader(tables["val"], bs, shuffle=False, kind="image", **kw)
-    test_loader = FeatureLoader(tables["test"], bs, shuffle=False, kind="image", **kw)
+    model, image_loader, text_loader, val_loader, test_loader, optimizer, scheduler = _build_run(
+        tables, text_ds, hparams, num_classes=num_classes, modality=modality, classifier_init=classifier_init, use_clip=use_clip,
+        clip_logit=clip_logit, text_indim=text_indim, common_dim=common_dim, device=device, generator=generator,
+        order_rng=order_rng, model=model)
     result = train(model, image_loader, text_loader, val_loader, test_loader if eval_test else None, optimizer,
                    scheduler, device=device, max_iters=hparams["max_iter"], alpha=alpha, eval_freq=eval_freq,
                    patience=hparams["patience"], precision=precision)
@@ -700,24 +688,35 @@ def savedir(outdir, dataset, encoder, train_shot, seed, text_type, text_shots, i
     return os.path.join(outdir, benchname, encoder.replace("/", "-"), mod_name, init_mode)
 
 
-def setup(datasets, hparams, args):
-    """One hyper-parameter point: build model / optimizer / scheduler / loaders, train, test, save
-    ``test_result.pth`` (skipped when it exists and FLAG is 0, reference :330-333)."""
-    ckpt_dir = os.path.join(args.savepath, hparam_str(hparams["optim"], hparams["lr"], hparams["weight_decay"],
-                                                      hparams["batch_size"], hparams["max_iter"], hparams["dropout"],
-                                                      hparams["learnable_temp"]))
+def _point_args(args):
+    """What a grid point's model and loaders take from ``args``, as keywords of ``setup_feature_run`` / ``_build_run``."""
+    text_indim = getattr(args, "text_indim", None) if args.modality == "crossmodal" else getattr(args, "common_dim", 0)
+    return dict(num_classes=args.nclasses, modality=args.modality, classifier_init=args.classifier_init,
+                use_clip=args.use_clip, clip_logit=args.logit, text_indim=text_indim)
+
+
+def _result_file(savepath, hparams):
+    """(path of a grid point's ``test_result.pth`` in its own, newly made directory, the result stored there or None).  An
+    existing file is loaded instead of running the point again unless FLAG is set (reference :330-333)."""
+    ckpt_dir = os.path.join(savepath, hparam_str(hparams["optim"], hparams["lr"], hparams["weight_decay"], hparams["batch_size"],
+                                                 hparams["max_iter"], hparams["dropout"], hparams["learnable_temp"]))
     os.makedirs(ckpt_dir, exist_ok=True)
     test_path = os.path.join(ckpt_dir, "test_result.pth")
     if os.path.exists(test_path) and not FLAG:
         print(f"=> Skipping {ckpt_dir} as it already exists!")
-        return torch.load(test_path, map_location="cpu", weights_only=True)
+        return test_path, torch.load(test_path, map_location="cpu", weights_only=True)
+    return test_path, None
+
+
+def setup(datasets, hparams, args):
+    """One hyper-parameter point: build model / optimizer / scheduler / loaders, train, test, save
+    ``test_result.pth`` (skipped when it exists and FLAG is 0, reference :330-333)."""
+    test_path, done = _result_file(args.savepath, hparams)
+    if done is not None:
+        return done
     res = setup_feature_run(datasets["img_tr"], datasets["img_val"], datasets["img_te"], datasets["text_ds"], hparams,
-                            num_classes=args.nclasses, modality=args.modality, alpha=args.alpha,
-                            classifier_init=args.classifier_init, use_clip=args.use_clip, clip_logit=args.logit,
-                            text_indim=getattr(args, "text_indim", None) if args.modality == "crossmodal"
-                            else getattr(args, "common_dim", 0), device=args.device,
-                            eval_test=getattr(args, "eval_test", True), precision=getattr(args, "precision", "fp32"),
-                            tables=datasets.get("tables"))
+                            alpha=args.alpha, device=args.device, eval_test=getattr(args, "eval_test", True),
+                            precision=getattr(args, "precision", "fp32"), tables=datasets.get("tables"), **_point_args(args))
     test_dict = {"test_acc": res["test_acc"], "val_acc": res["val_acc"], "model": res["model"], "iter": res["iter"]}
     print(f"=> Test Acc: {res['test_acc']:.4f}")
     torch.save(test_dict, test_path)
@@ -767,6 +766,16 @@ def farm_seed(base_seed, idx):
     return (int(base_seed) if base_seed is not None and int(base_seed) >= 0 else 0) * 100003 + 7919 * (idx + 1)
 
 
+def _sweep_tables(datasets, args):
+    """The device tables the points of a grouped or farmed sweep share, with their bf16 shadows in bf16 mode."""
+    tables = feature_tables(datasets["img_tr"], datasets["img_val"], datasets["img_te"], datasets["text_ds"],
+                            torch.device(args.device))
+    if getattr(args, "precision", "fp32") == "bf16":
+        for t in tables.values():
+            t.features_bf16()
+    return tables
+
+
 def sweep_grouped(datasets, hyperparams, args):
     """The sweep as ONE grouped job (``args.sweep_mode = "grouped"``): every grid point becomes a head of the same
     persistent launches (``train_grouped`` / ``umlh_train_steps_grouped``), all reading the same device-resident
@@ -774,52 +783,22 @@ def sweep_grouped(datasets, hyperparams, args):
     draws its loader orders from a private generator seeded by ``farm_seed(args.seed, k)`` and initialises its model
     under that seed, so a point's result is independent of which other points run beside it: it equals the isolated run
     of that point (``setup_feature_run`` with the same generator) bit for bit."""
-    from engine.models.head import UML, UMLClip
     points = _grid(hyperparams)
     dev = torch.device(args.device)
     precision = getattr(args, "precision", "fp32")
-    tables = feature_tables(datasets["img_tr"], datasets["img_val"], datasets["img_te"], datasets["text_ds"], dev)
-    if precision == "bf16":
-        for t in tables.values():
-            t.features_bf16()
-    d_img, d_txt = tables["train"].features.shape[1], tables["text"].features.shape[1]
-    text_indim = getattr(args, "text_indim", None) if args.modality == "crossmodal" else getattr(args, "common_dim", 0)
-    common_dim = 0 if args.modality == "crossmodal" else (text_indim or 0)
+    tables = _sweep_tables(datasets, args)
     runs, slots = [], []
     results = [None] * len(points)
     for idx, hp in enumerate(points):
-        ckpt_dir = os.path.join(args.savepath, hparam_str(hp["optim"], hp["lr"], hp["weight_decay"], hp["batch_size"],
-                                                          hp["max_iter"], hp["dropout"], hp["learnable_temp"]))
-        os.makedirs(ckpt_dir, exist_ok=True)
-        test_path = os.path.join(ckpt_dir, "test_result.pth")
-        if os.path.exists(test_path) and not FLAG:
-            print(f"=> Skipping {ckpt_dir} as it already exists!")
-            results[idx] = torch.load(test_path, map_location="cpu", weights_only=True)
+        test_path, results[idx] = _result_file(args.savepath, hp)
+        if results[idx] is not None:
             continue
         torch.manual_seed(farm_seed(args.seed, idx))
-        if args.use_clip:
-            model = UMLClip(d_img, args.nclasses, logit_scale_init=args.logit, bias=False, learnable_temp=hp["learnable_temp"])
-        else:
-            tin = (d_txt if text_indim is None else text_indim) if args.modality == "crossmodal" else (text_indim or 0)
-            model = UML(d_img, tin, args.nclasses, bias=False, learnable_temp=hp["learnable_temp"])
-        model.to(dev)
-        if wants_zero_shot_init(args.classifier_init, args.modality, common_dim, d_txt):
-            model.zero_shot_init(datasets["text_ds"])
-        optimizer = build_optimizer(model.parameters(), hp["optim"], hp["lr"], hp["weight_decay"])
-        scheduler = build_lr_scheduler(optimizer, hp["lr_scheduler"], hp["warmup_iter"], hp["max_iter"],
-                                       warmup_type=hp["warmup_type"], warmup_lr=hp["warmup_min_lr"])
         gen = torch.Generator()
         gen.manual_seed(farm_seed(args.seed, idx))
-        kw = {"order_rng": getattr(args, "order_rng", "torch-cpu"), "generator": gen}
-        bs = hp["batch_size"]
-        image_loader = FeatureLoader(tables["train"], bs, shuffle=True, kind="image", **kw)
-        text_loader = FeatureLoader(tables["text"], bs, shuffle=True, kind="text", **kw)
-        if args.modality == "image":
-            text_loader = None
-        elif args.modality == "text":
-            image_loader = None
-        val_loader = FeatureLoader(tables["val"], bs, shuffle=False, kind="image", **kw)
-        test_loader = FeatureLoader(tables["test"], bs, shuffle=False, kind="image", **kw)
+        model, image_loader, text_loader, val_loader, test_loader, optimizer, scheduler = _build_run(
+            tables, datasets["text_ds"], hp, device=dev, generator=gen,
+            order_rng=getattr(args, "order_rng", "torch-cpu"), **_point_args(args))
         runs.append(dict(model=model, image_loader=image_loader, text_loader=text_loader, val_loader=val_loader,
                          test_loader=test_loader if getattr(args, "eval_test", True) else None, optimizer=optimizer,
                          scheduler=scheduler, max_iters=hp["max_iter"], alpha=args.alpha, patience=hp["patience"],
@@ -852,55 +831,38 @@ def sweep_farm(datasets, hyperparams, args, workers):
     ``farm_seed(args.seed, k)``: results are reproducible and independent of scheduling, but not
     batch-for-batch those of the sequential order (``sweep_workers=1`` keeps that)."""
     from concurrent.futures import ThreadPoolExecutor
-    from engine.models.head import UML, UMLClip
     points = _grid(hyperparams)
     dev = torch.device(args.device)
-    tables = feature_tables(datasets["img_tr"], datasets["img_val"], datasets["img_te"], datasets["text_ds"], dev)
-    if getattr(args, "precision", "fp32") == "bf16":
-        for t in tables.values():
-            t.features_bf16()
-    d_img, d_txt = tables["train"].features.shape[1], tables["text"].features.shape[1]
-    text_indim = getattr(args, "text_indim", None) if args.modality == "crossmodal" else getattr(args, "common_dim", 0)
+    tables = _sweep_tables(datasets, args)
+    point_args = _point_args(args)
     jobs = []
     for idx, hp in enumerate(points):                      # models built here, in order: deterministic inits
-        ckpt_dir = os.path.join(args.savepath, hparam_str(hp["optim"], hp["lr"], hp["weight_decay"], hp["batch_size"],
-                                                          hp["max_iter"], hp["dropout"], hp["learnable_temp"]))
-        os.makedirs(ckpt_dir, exist_ok=True)
-        test_path = os.path.join(ckpt_dir, "test_result.pth")
-        if os.path.exists(test_path) and not FLAG:
-            jobs.append((idx, hp, test_path, None))
-            continue
-        torch.manual_seed(farm_seed(args.seed, idx))
-        if args.use_clip:
-            model = UMLClip(d_img, args.nclasses, logit_scale_init=args.logit, bias=False, learnable_temp=hp["learnable_temp"])
-        else:
-            tin = (d_txt if text_indim is None else text_indim) if args.modality == "crossmodal" else (text_indim or 0)
-            model = UML(d_img, tin, args.nclasses, bias=False, learnable_temp=hp["learnable_temp"])
-        jobs.append((idx, hp, test_path, model))
+        test_path, done = _result_file(args.savepath, hp)
+        model = None
+        if done is None:
+            torch.manual_seed(farm_seed(args.seed, idx))
+            model = _build_model(tables, hp, args.nclasses, args.modality, args.use_clip, args.logit, point_args["text_indim"])
+        jobs.append((idx, hp, test_path, model, done))
     main_stream = torch.cuda.current_stream(dev)
 
     def run(job):
-        idx, hp, test_path, model = job
-        if model is None:
-            print(f"=> Skipping {os.path.dirname(test_path)} as it already exists!")
-            return torch.load(test_path, map_location="cpu", weights_only=True)
+        idx, hp, test_path, model, done = job
+        if done is not None:
+            return done
         gen = torch.Generator()
         gen.manual_seed(farm_seed(args.seed, idx))
         stream = torch.cuda.Stream(dev)
         stream.wait_stream(main_stream)                    # the shared tables were uploaded there
         with torch.cuda.stream(stream):
             res = setup_feature_run(datasets["img_tr"], datasets["img_val"], datasets["img_te"], datasets["text_ds"], hp,
-                                    num_classes=args.nclasses, modality=args.modality, alpha=args.alpha,
-                                    classifier_init=args.classifier_init, use_clip=args.use_clip, clip_logit=args.logit,
-                                    text_indim=text_indim, device=dev, eval_test=getattr(args, "eval_test", True),
+                                    alpha=args.alpha, device=dev, eval_test=getattr(args, "eval_test", True),
                                     precision=getattr(args, "precision", "fp32"), tables=tables, generator=gen,
-                                    order_rng=getattr(args, "order_rng", "torch-cpu"), model=model)
+                                    order_rng=getattr(args, "order_rng", "torch-cpu"), model=model, **point_args)
             stream.synchronize()
         test_dict = {"test_acc": res["test_acc"], "val_acc": res["val_acc"], "model": res["model"], "iter": res["iter"]}
         torch.save(test_dict, test_path)
         return test_dict
 
-    import threading
     import umlh.head_engine as _he
     _he.ENQUEUE_LOCK = threading.Lock()
     try:
