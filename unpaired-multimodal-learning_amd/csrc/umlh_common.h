@@ -331,6 +331,53 @@ __device__ __forceinline__ Split3 split3_pair(float a, float b) {
 }
 
 // --------------------------------------------------------------------------------------------------------------- //
+// Sum of the split-K slabs of 4 consecutive elements for the update slices of the one-launch step (step_update_task).
+// ld(s) loads slab s (there: a device-coherent buffer load).  The order is THE documented one: gi = 0.f + slabs [0, n_img)
+// in ascending index, gt = 0.f + slabs [n_img, n) in ascending index (the caller adds gi + gt).  The loads of a group of up
+// to SLAB_GROUP slabs are all issued into registers of their own before the first of them is added: written as one loop,
+// load - wait - add - branch kept ONE 16-byte load per thread in flight, n round trips in series.  n and n_img are run-time
+// values, uniform over the launch; a slab beyond n is neither loaded nor added.
+// head_step_kernel and reduce_update keep their loops: in those two the same helper measured slower.
+// --------------------------------------------------------------------------------------------------------------- //
+constexpr int SLAB_GROUP = 8;
+// (eight named registers, not an array: as f32x4v r[8] the compiler formed ONE 32-dword value that was copied whole behind
+// every load.  n and n_img are uniform, and the compiler turns each guarded accumulate into selects on the accumulators; kept
+// behind scalar branches instead, the adds cost the one-launch step's forward tile six more spilled registers)
+#define UMLH_SLAB_ADD(j, s0, n, n_img, gi, gt)     \
+    if (s0 + j < n_img) gi += r##j;               \
+    if (s0 + j >= n_img && s0 + j < n) gt += r##j;
+#define UMLH_SLAB_ADD8(s0, n, n_img, gi, gt)                                                                            \
+    UMLH_SLAB_ADD(0, s0, n, n_img, gi, gt) UMLH_SLAB_ADD(1, s0, n, n_img, gi, gt) UMLH_SLAB_ADD(2, s0, n, n_img, gi, gt) \
+    UMLH_SLAB_ADD(3, s0, n, n_img, gi, gt) UMLH_SLAB_ADD(4, s0, n, n_img, gi, gt) UMLH_SLAB_ADD(5, s0, n, n_img, gi, gt) \
+    UMLH_SLAB_ADD(6, s0, n, n_img, gi, gt) UMLH_SLAB_ADD(7, s0, n, n_img, gi, gt)
+template <class LD>
+__device__ __forceinline__ void slab_sum(const LD& ld, int n, int n_img, f32x4v& gi, f32x4v& gt) {
+    if (n_img > n) n_img = n;
+    for (int s0 = 0; s0 < n; s0 += SLAB_GROUP) {
+        f32x4v r0, r1, r2, r3, r4, r5, r6, r7;
+        if (n - s0 >= SLAB_GROUP) {
+            // a whole group: eight unconditional loads, so the waits are COUNTED (vmcnt(7) .. vmcnt(0)) and the selects of
+            // slab j run while slabs j + 1 .. 7 are still on their way (behind conditional loads there is ONE vmcnt(0) and
+            // all the selects come after the last byte: measured slower than the serial loop this replaces)
+            r0 = ld(s0); r1 = ld(s0 + 1); r2 = ld(s0 + 2); r3 = ld(s0 + 3);
+            r4 = ld(s0 + 4); r5 = ld(s0 + 5); r6 = ld(s0 + 6); r7 = ld(s0 + 7);
+#define UMLH_SLAB_ADD_FULL(j) if (s0 + j < n_img) gi += r##j; else gt += r##j;
+            UMLH_SLAB_ADD_FULL(0) UMLH_SLAB_ADD_FULL(1) UMLH_SLAB_ADD_FULL(2) UMLH_SLAB_ADD_FULL(3)
+            UMLH_SLAB_ADD_FULL(4) UMLH_SLAB_ADD_FULL(5) UMLH_SLAB_ADD_FULL(6) UMLH_SLAB_ADD_FULL(7)
+#undef UMLH_SLAB_ADD_FULL
+        } else {
+#define UMLH_SLAB_LOAD(j) if (s0 + j < n) r##j = ld(s0 + j);
+            UMLH_SLAB_LOAD(0) UMLH_SLAB_LOAD(1) UMLH_SLAB_LOAD(2) UMLH_SLAB_LOAD(3)
+            UMLH_SLAB_LOAD(4) UMLH_SLAB_LOAD(5) UMLH_SLAB_LOAD(6) UMLH_SLAB_LOAD(7)
+#undef UMLH_SLAB_LOAD
+            UMLH_SLAB_ADD8(s0, n, n_img, gi, gt)
+        }
+    }
+}
+#undef UMLH_SLAB_ADD8
+#undef UMLH_SLAB_ADD
+
+// --------------------------------------------------------------------------------------------------------------- //
 // Claimed tasks of a one-launch step (step_bf16, step_f32).  The launch is a grid of persistent workgroups; the work
 // is a list of TASKS (forward tiles, dW tiles, update slices, finalize) with dependencies that only point at earlier
 // phases.  Nothing here depends on dispatch order, workgroup -> XCD placement or on the whole grid being resident:

@@ -1204,10 +1204,8 @@ __device__ __forceinline__ int step_update_task(const HeadFuse& hf, const DwGate
         {
             __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(hf.slabs), 0,
                                                                           (int)((size_t)hf.n_slabs * hf.slab_stride * 4), 0x00020000);
-            for (int sI = 0; sI < hf.n_slabs_img; ++sI)
-                gi += __builtin_bit_cast(f32x4v, load_coherent_b128(rs, (unsigned)(((size_t)sI * hf.slab_stride + i) * 4)));
-            for (int sI = hf.n_slabs_img; sI < hf.n_slabs; ++sI)
-                gt += __builtin_bit_cast(f32x4v, load_coherent_b128(rs, (unsigned)(((size_t)sI * hf.slab_stride + i) * 4)));
+            slab_sum([&](int s) { return __builtin_bit_cast(f32x4v, load_coherent_b128(rs, (unsigned)(((size_t)s * hf.slab_stride + i) * 4))); },
+                     hf.n_slabs, hf.n_slabs_img, gi, gt);
         }
         const f32x4v g0 = gi + gt;
         if (!upd) {
