@@ -36,6 +36,34 @@ def test_version_and_workspace_query(lib):
     assert lib.umlh_workspace_bytes(C.byref(too_many)) == 0
 
 
+# umlh_workspace_bytes as the build before the region descriptions of csrc/umlh_api.cpp returned it (the partition must not
+# move when a region's size is restated): (d_img, d_shared, C, has_proj, learnable_temp, optimizer, precision, rows img, rows txt).
+# Together the configurations reach every optional region: both precisions, img_proj, the fp32 fragment-major shadow (d % 32 == 0)
+# and its absence, the one-launch control words, the micro-step regions, the 2-D forward's exchange region.
+WORKSPACE_BYTES = [
+    ("fp32_lin_d512_c1000", (512, 512, 1000, 0, 0, 2, 0, 4096, 4096), {}, 56907776),
+    ("bf16_lin_d512_c1000", (512, 512, 1000, 0, 0, 2, 1, 4096, 4096), {}, 38908160),
+    ("bf16_mlp_1024_3200_c1000", (1024, 3200, 1000, 1, 0, 2, 1, 4096, 4096), {}, 244837376),
+    ("fp32_mlp_40_56_c12", (40, 56, 12, 1, 1, 2, 0, 512, 128), {}, 1040896),
+    ("fp32_lin_d30_c101", (30, 30, 101, 0, 1, 2, 0, 512, 128), {}, 1124864),
+    ("bf16_lin_d512_c1000_fwd2d", (512, 512, 1000, 0, 0, 2, 1, 4096, 4096), {"UMLH_BF16_FWD2D": "1"}, 39989504),
+    ("fp32_lin_d512_c1024", (512, 512, 1024, 0, 0, 2, 0, 4096, 4096), {}, 58191104),
+    ("bf16_lin_d512_c1024", (512, 512, 1024, 0, 0, 2, 1, 4096, 4096), {}, 39405056),
+    ("fp32_lin_d512_c1000_rows_1_0", (512, 512, 1000, 0, 0, 2, 0, 1, 0), {}, 25032704),
+    ("bf16_lin_d512_c1000_rows_1_0", (512, 512, 1000, 0, 0, 2, 1, 1, 0), {}, 22496512),
+]
+
+
+@pytest.mark.parametrize("shape,env,expected", [c[1:] for c in WORKSPACE_BYTES], ids=[c[0] for c in WORKSPACE_BYTES])
+def test_workspace_bytes_are_pinned(lib, monkeypatch, shape, env, expected):
+    from umlh._lib import Config
+    monkeypatch.delenv("UMLH_BF16_FWD2D", raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    cfg = Config(*shape, 0.9, 0.999, 1e-8, 0.9, 0.01)
+    assert lib.umlh_workspace_bytes(C.byref(cfg)) == expected
+
+
 def test_null_and_unbound_calls_fail_with_message(lib):
     assert lib.umlh_create(None, None) < 0
     assert b"umlh_create" in lib.umlh_last_error()

@@ -212,6 +212,27 @@ def test_split_grad_then_update_equals_fused_step():
         np.testing.assert_allclose(a.cpu().numpy(), b.cpu().numpy(), atol=1e-7, rtol=1e-6)
 
 
+def test_update_of_a_head_whose_width_is_no_multiple_of_8():
+    """d_shared % 8 != 0: the head is updated by the finalize and reduce_update launches instead of the one head-step launch.
+    (a) the fused step equals grad_step + apply_update there too (the tolerances of
+    test_split_grad_then_update_equals_fused_step); (b) three AdamW steps agree with the oracle (the tolerance of
+    test_trajectory_against_reference_golden)."""
+    rng = np.random.default_rng(20)
+    st, xi, yi, xt, yt, ii, ti = _random_case(rng, 20, 20, 5, 30, 30, 7, 9, False, True, 3.0)
+    e1 = _engine(st, wd=0.01)
+    e2 = _engine(st, wd=0.01)
+    ref, opt = st.copy(), O.OptState("adamw", 0.01)
+    for k in range(3):
+        e1.train_step(_rb(xi, yi, ii), _rb(xt, yt, ti), lr=1e-3, step=k + 1, alpha=0.5)
+        e2.grad_step(_rb(xi, yi, ii), _rb(xt, yt, ti), alpha=0.5)
+        e2.apply_update(lr=1e-3, step=k + 1)
+        O.optimizer_step(ref, O.step_grads(ref, xi[ii], yi[ii], xt[ti], yt[ti], 0.5).grads, opt, 1e-3)
+    torch.cuda.synchronize()
+    for a, b in [(e1.w_head, e2.w_head), (e1.m_head, e2.m_head), (e1.scales, e2.scales)]:
+        np.testing.assert_allclose(a.cpu().numpy(), b.cpu().numpy(), atol=1e-7, rtol=1e-6)
+    np.testing.assert_allclose(e1.w_head.cpu().numpy(), ref.w_head, atol=3e-6, rtol=3e-5)
+
+
 def test_full_size_cfg2_step_against_oracle():
     """BASELINE config 2 shape: d=512, C=1000, 4096 image + 4096 text rows gathered from
     larger tables, AdamW; two steps vs the oracle, plus the CE-gradient property

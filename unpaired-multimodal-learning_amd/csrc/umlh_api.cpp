@@ -29,9 +29,9 @@ static inline long long round_up(long long x, long long m) { return (x + m - 1) 
 
 struct Layout {                 // workspace partition, in floats from the base
     long long dzt, h, dht, slabs_head, slabs_proj, partials, diag_part, grads, w16, iota, zeros, dbg, wpt16, wht16, xch, fuse_flags, w32s, total;
-    long long ctl_tasks;        // one-launch step: task capacity of the control region at fuse_flags: [cap] u64 done, [cap] u32 claim, [16] u32 status
+    long long ctl_tasks;        // one-launch step: task capacity of the control region at fuse_flags (step_ctl_at)
     int fwd_nq;                 // bf16 2-D forward (fwd_ce_bf16_q): class groups per row tile, 0 = the 1-D kernel
-    long long mc_flags, mc_xchg, mc_ext, mc_tab, mc_desc;   // micro-step region (umlh_kernels_micro.hip); mc_flags = 0: unsupported shape
+    long long mc_flags, mc_xchg, mc_tab, mc_desc;   // micro-step region (umlh_micro.h); mc_flags = 0: unsupported shape
     int mc_nwg, mc_nch, mc_cw;
     long long n_iota;
     int rcap_img, rcap_txt, ldz;     // padded row capacities
@@ -71,10 +71,21 @@ static SplitPlan plan_splits(int r0, int r1, int want, int quantum, int min_chun
     return sp;
 }
 
-// per-launch tables of one head: int offs_img[MAXS + 1], int offs_txt[MAXS + 1], OptArgs opt[MAXS]
-static long long micro_table_floats() {
-    return 2LL * (UMLH_MICRO_MAX_STEPS + 1) + 2 + (long long)UMLH_MICRO_MAX_STEPS * (sizeof(OptArgs) / sizeof(float));
-}
+// ---- region descriptions: the size (in floats) and inner layout of every workspace region that more than one place has to
+// know, each stated once.  make_layout sizes the regions with them; umlh_bind, the launches and the status / buffer queries
+// find their words through them.  (The control words of the one-launch step: umlh_common.h; the micro-step regions: umlh_micro.h.) ----
+// exchange granules (8 bytes) of the bf16 2-D forward
+static long long xch_floats(const Layout& L) { return 2LL * (L.ldz / 128 + 2) * L.fwd_nq * 4 * 128; }
+// gradient diagnostics: [head_step blocks][4] partial sums, then the ticket (diag_ticket)
+static long long diag_part_floats(const Layout& L) { return 4 * ((L.n_head + 1023) / 1024 + 2); }
+static const int DIAG_TICKET_FLOATS = 64;
+// diagnostic stamps: [blocks][8 waves][8] u64
+static long long dbg_floats(const Layout& L) { return (long long)L.max_blocks * 128; }
+// gradient message [g_head | g_proj | g_scales(2) | scalars]; `diag`: the image and the text gradient of the head travel
+// separately ([g_img | g_txt | ...], see dp_reduce_head).  The region holds the longer form.
+static long long msg_head_floats(const Layout& L, bool diag) { return diag ? 2 * L.n_head : L.n_head; }
+static long long msg_floats(const Layout& L, bool diag) { return msg_head_floats(L, diag) + L.n_proj + 2 + UMLH_N_SCALARS; }
+static long long msg_cap_floats(const Layout& L) { return msg_floats(L, true); }
 
 static bool make_layout(const umlh_config_t& c, Layout& L) {
     if (c.d_img < 1 || c.d_shared < 1 || c.num_classes < 1 || c.num_classes > 1024) return false;
@@ -105,16 +116,15 @@ static bool make_layout(const umlh_config_t& c, Layout& L) {
     L.slabs_head = take((long long)L.scap_head * L.n_head);
     L.slabs_proj = take((long long)L.scap_proj * L.n_proj);
     L.partials = take((long long)L.max_blocks * 4);
-    L.diag_part = take(4 * ((L.n_head + 1023) / 1024 + 2) + 64);     // gradient diagnostics: [head_step blocks][4] partials, then the ticket
-    L.grads = take(2 * L.n_head + L.n_proj + 2 + UMLH_N_SCALARS);    // 2 x n_head: the data-parallel message carries the image and
-                                                                     // the text gradient separately when diagnostics are on
+    L.diag_part = take(diag_part_floats(L) + DIAG_TICKET_FLOATS);
+    L.grads = take(msg_cap_floats(L));
     L.w16 = take(c.precision == UMLH_PREC_BF16 ? 1024LL * c.d_shared / 2 : 0);   // bf16 chunk-major shadow of w_head (<= 1024 class rows)
     L.n_iota = L.rcap_img > L.rcap_txt ? L.rcap_img : L.rcap_txt;     // identity row ids: batch rows, classes, image-feature columns
     if (L.n_iota < 1024) L.n_iota = 1024;
     if (L.n_iota < c.d_img) L.n_iota = c.d_img;
     L.iota = take(c.precision == UMLH_PREC_BF16 ? 2LL * L.n_iota : 0);   // int64 0..n_iota-1
     L.zeros = take(64);
-    L.dbg = take((long long)L.max_blocks * 128);         // diagnostic stamps: [blocks][8 waves][8] u64
+    L.dbg = take(dbg_floats(L));
     const bool bfp = c.precision == UMLH_PREC_BF16 && c.has_proj;
     L.wpt16 = take(bfp ? (L.n_proj + 1) / 2 : 0);         // bf16 W_proj^T [d_img][d_shared]
     L.wht16 = take(bfp ? 1024LL * round_up(c.d_shared, 128) / 2 : 0);   // bf16 W_head^T by class chunks [16][d_shared^128][64]
@@ -122,10 +132,9 @@ static bool make_layout(const umlh_config_t& c, Layout& L) {
     // slower than the 1-D kernel at cfg2 (umlh_kernels_bf16.hip) -> opt-in, UMLH_BF16_FWD2D=1, whenever the shape allows.
     L.fwd_nq = 0; L.xch = 0;
     if (c.precision == UMLH_PREC_BF16 && c.num_classes > 256 && c.d_shared % 256 == 0 && c.d_shared <= 512) {
-        const int nq = (c.num_classes + 255) / 256;
         if (env_int("UMLH_BF16_FWD2D", 0) == 1) {
-            L.fwd_nq = nq;
-            L.xch = take(2LL * (L.ldz / 128 + 2) * nq * 4 * 128);      // 8-byte granules
+            L.fwd_nq = (c.num_classes + 255) / 256;
+            L.xch = take(xch_floats(L));
         }
     }
     // fp32 mode: fragment-major fp32 shadow of w_head for the streamed forward (fwd_ce_f32 MODE 2): [K/16][cpad/32][64][8] floats
@@ -134,19 +143,18 @@ static bool make_layout(const umlh_config_t& c, Layout& L) {
         int ctw = 0, wc = 0;
         if (umlh_f32_fwd_config(c.num_classes, &ctw, &wc) > 0) L.w32s = take((long long)c.d_shared * 32 * ctw * wc * 3 / 2);   // (x3: three bf16 planes = 1.5x the fp32 shadow)
     }
-    // one-launch step (step_bf16): per task one done granule (u64) and one claim word (u32), then the status words
+    // one-launch step (step_bf16): the control words of every task it may have
     L.ctl_tasks = L.max_blocks + 4096 + L.n_head / 2048 + 8;
-    L.fuse_flags = c.precision == UMLH_PREC_BF16 && !c.has_proj ? take(3LL * L.ctl_tasks + 16) : 0;
+    L.fuse_flags = c.precision == UMLH_PREC_BF16 && !c.has_proj ? take(step_ctl_floats(L.ctl_tasks)) : 0;
     // micro-step path: linear head whose width has a supported chunking (bf16 operand mode: widths that are multiples of 128)
-    L.mc_flags = L.mc_xchg = L.mc_ext = L.mc_tab = L.mc_desc = 0;
+    L.mc_flags = L.mc_xchg = L.mc_tab = L.mc_desc = 0;
     L.mc_nwg = (c.num_classes + UMLH_MICRO_CS - 1) / UMLH_MICRO_CS;
     L.mc_nch = L.mc_cw = 0;
     if (!c.has_proj && umlh_micro_chunking(c.d_shared, &L.mc_nch, &L.mc_cw) &&
         (c.precision == UMLH_PREC_FP32 || umlh_micro_bf16_supported(L.mc_nch, L.mc_cw))) {
-        L.mc_flags = take(64 + 64);                                              // [nwg <= 64] epoch flags, then the status word
-        L.mc_xchg = take(2LL * L.mc_nwg * 5 * UMLH_MICRO_MAX_ROWS * 2);       // 8-byte granules
-        L.mc_ext = 0;
-        L.mc_tab = take(micro_table_floats());
+        L.mc_flags = take(sizeof(UmlhMicroFlags) / sizeof(float));
+        L.mc_xchg = take(umlh_micro_xchg_floats(L.mc_nwg));                      // (directly behind the flags: bind zeroes both at once)
+        L.mc_tab = take(sizeof(UmlhMicroTable) / sizeof(float));
         L.mc_desc = take((long long)UMLH_MICRO_MAX_HEADS * sizeof(UmlhMicroHead) / sizeof(float) + 16);
     }
     L.total = off;
@@ -356,15 +364,20 @@ static inline float* ws(umlh_handle_t h, long long off) { return static_cast<flo
 static inline int class_pad(const umlh_handle_s* h) { return 32 * h->ctw * h->wc; }   // class rows of the W shadows (whole 32-class tiles per wave)
 // ticket of the gradient-diagnostics reduction, behind the [head_step blocks][4] partials (head_step_kernel leaves it at 0)
 static inline unsigned* diag_ticket(umlh_handle_t h) {
-    return reinterpret_cast<unsigned*>(ws(h, h->L.diag_part) + 4 * ((h->L.n_head + 1023) / 1024 + 2));
+    return reinterpret_cast<unsigned*>(ws(h, h->L.diag_part) + diag_part_floats(h->L));
 }
 
 // gradient message layout (see umlh_grad_step): head part, img_proj part, then g_scales(2) + scalars
 static inline long long frozen_lo(const umlh_handle_s* h) { return h->frozen_proj_row < 0 ? 0 : (long long)h->frozen_proj_row * h->cfg.d_img; }
 static inline long long frozen_hi(const umlh_handle_s* h) { return h->frozen_proj_row < 0 ? 0 : (long long)(h->frozen_proj_row + 1) * h->cfg.d_img; }
-static inline long long msg_head_len(const umlh_handle_s* h) { return h->dp_diag ? 2 * h->L.n_head : h->L.n_head; }
+static inline long long msg_head_len(const umlh_handle_s* h) { return msg_head_floats(h->L, h->dp_diag); }
 static inline long long msg_tail_off(const umlh_handle_s* h) { return msg_head_len(h) + h->L.n_proj; }
-static inline long long msg_len(const umlh_handle_s* h) { return msg_tail_off(h) + 2 + UMLH_N_SCALARS; }
+static inline long long msg_len(const umlh_handle_s* h) { return msg_floats(h->L, h->dp_diag); }
+// the message form umlh_grad_step uses: per-modality head gradients when the diagnostics are on and head_step_kernel can form them
+static inline bool split_diag(const umlh_handle_s* h) { return h->diagnostics && h->cfg.d_shared % 8 == 0; }
+// the control words of the one-launch step / the micro path's status word
+static inline StepCtl step_ctl(umlh_handle_t h) { return step_ctl_at(ws(h, h->L.fuse_flags), h->L.ctl_tasks); }
+static inline unsigned* micro_status(umlh_handle_t h) { return &reinterpret_cast<UmlhMicroFlags*>(ws(h, h->L.mc_flags))->status; }
 
 int umlh_bind(umlh_handle_t h, const umlh_buffers_t* b) {
     if (!h || !b) return fail(UMLH_E_INVALID, "umlh_bind: null argument");
@@ -385,23 +398,23 @@ int umlh_bind(umlh_handle_t h, const umlh_buffers_t* b) {
     h->shadow_fresh = false;
     {
         DeviceGuard dg_(h->device);
-        if (hipMemset(diag_ticket(h), 0, 64 * sizeof(float)) != hipSuccess) return fail(UMLH_E_HIP, "umlh_bind: clearing the diagnostics ticket failed");
+        if (hipMemset(diag_ticket(h), 0, DIAG_TICKET_FLOATS * sizeof(float)) != hipSuccess) return fail(UMLH_E_HIP, "umlh_bind: clearing the diagnostics ticket failed");
     }
     if (h->L.fuse_flags) {        // done granules / claim words / status of the one-launch step: tag 0 = never written
         DeviceGuard dg_(h->device);
-        if (hipMemset(ws(h, h->L.fuse_flags), 0, sizeof(float) * (size_t)(3 * h->L.ctl_tasks + 16)) != hipSuccess)
+        if (hipMemset(ws(h, h->L.fuse_flags), 0, sizeof(float) * (size_t)step_ctl_floats(h->L.ctl_tasks)) != hipSuccess)
             return fail(UMLH_E_HIP, "umlh_bind: clearing the step control words failed");
         h->fuse_epoch = 0;
     }
     if (h->L.fwd_nq) {            // exchange granules of the 2-D forward: tag 0 = never written
         DeviceGuard dg_(h->device);
-        if (hipMemset(ws(h, h->L.xch), 0, sizeof(float) * 2 * (size_t)(h->L.ldz / 128 + 2) * h->L.fwd_nq * 4 * 128) != hipSuccess)
+        if (hipMemset(ws(h, h->L.xch), 0, sizeof(float) * (size_t)xch_floats(h->L)) != hipSuccess)
             return fail(UMLH_E_HIP, "umlh_bind: clearing the forward exchange region failed");
         h->fwd_epoch = 0;
     }
     if (h->L.mc_flags) {          // epoch flags, status word and exchange records start from zero (bind time only)
         DeviceGuard dg_(h->device);
-        const size_t n = (size_t)(h->L.mc_tab - h->L.mc_flags) * sizeof(float);
+        const size_t n = sizeof(UmlhMicroFlags) + (size_t)umlh_micro_xchg_floats(h->L.mc_nwg) * sizeof(float);
         if (hipMemset(ws(h, h->L.mc_flags), 0, n) != hipSuccess) return fail(UMLH_E_HIP, "umlh_bind: clearing the micro-step region failed");
         h->micro_epoch = 0;
     }
@@ -1306,18 +1319,17 @@ static int bf16_dw_head(umlh_handle_t h, StepCall& x, bool proj, const FwdArgsB&
     const int ntask = umlh_bf16_step_tasks(nb, g.M, g.N, splits, L.n_head, with_head);
     if (fused && ntask <= L.ctl_tasks) {
         // forward + dW (+ update + finalize) as ONE launch of persistent workgroups over claimed tasks (StepCtl)
-        if (h->fuse_epoch > 0xFFFFFF00u) {            // tag wrap (2^32 launches): start the epoch-tagged words over
-            HIPCHK((int)hipMemsetAsync(ws(h, L.fuse_flags), 0, sizeof(float) * (size_t)(3 * L.ctl_tasks), x.st), "step control words");
+        const StepCtl ctl = step_ctl(h);
+        if (h->fuse_epoch > 0xFFFFFF00u) {            // tag wrap (2^32 launches): start the epoch-tagged words over (the status stays)
+            HIPCHK((int)hipMemsetAsync(ctl.done, 0, step_ctl_tag_bytes(ctl), x.st), "step control words");
             h->fuse_epoch = 0;
         }
         ++h->fuse_epoch;
         HeadFuse hf;
         if (with_head) { hf = *x.head; hf.n_slabs = splits; hf.n_slabs_img = sp.n_img; }
-        unsigned long long* done = reinterpret_cast<unsigned long long*>(ws(h, L.fuse_flags));
-        unsigned* claim = reinterpret_cast<unsigned*>(done + L.ctl_tasks);
-        unsigned* status = claim + L.ctl_tasks;
-        HIPCHK(umlh_bf16_launch_step(&fb, h->ctw, h->wc, nb, &g, splits, claim, done, status, h->fuse_epoch, h->ts, nb * h->ts,
-                                     with_head ? &hf : nullptr, (h->dbg_step && 4LL * ntask <= 64LL * L.max_blocks) ? ws_stamps(h) : nullptr,
+        const bool timeline = h->dbg_step && 8LL * ntask <= dbg_floats(L);      // 4 u64 stamps per task
+        HIPCHK(umlh_bf16_launch_step(&fb, h->ctw, h->wc, nb, &g, splits, ctl.claim, ctl.done, ctl.status, h->fuse_epoch, h->ts, nb * h->ts,
+                                     with_head ? &hf : nullptr, timeline ? ws_stamps(h) : nullptr,
                                      h->step_grid, h->step_lazy, x.st), "step_bf16");
         x.head_done = with_head;
         h->step_launches++;
@@ -1549,15 +1561,21 @@ static int check_step(umlh_handle_t h, const umlh_batch_t* img, const umlh_batch
     return UMLH_OK;
 }
 
-// The head part of a one-launch step (linear bf16 head): the update in place, or (grad_out != NULL, the data-parallel
-// split step) the slab sum into the gradient message with nothing updated.  The launch fills in the slab counts.
-static HeadFuse make_head_fuse(umlh_handle_t h, const OptArgs& o, const FinalizeArgs& f, float* grad_out) {
+// The head reduce of a step, in the one form every launch of it takes (head_step_kernel through umlh_launch_head_step, or
+// riding in the one-launch step of a linear bf16 head): `n_slabs` slabs of n_head floats at `slabs`, `stride` apart, are summed
+// and the head is updated in place, or (grad_out != NULL, the data-parallel split step) the sum goes to grad_out with nothing
+// updated.  The one-launch step fills in the slab counts itself.
+static HeadFuse make_head_fuse(umlh_handle_t h, const OptArgs& o, const FinalizeArgs& f, const float* slabs, int n_slabs,
+                               long long stride, float* grad_out) {
     HeadFuse hf;
     memset(&hf, 0, sizeof(hf));
-    hf.slabs = ws(h, h->L.slabs_head); hf.slab_stride = h->L.n_head; hf.C = h->cfg.num_classes; hf.K = h->cfg.d_shared;
+    hf.slabs = slabs; hf.n_slabs = n_slabs; hf.slab_stride = stride; hf.C = h->cfg.num_classes; hf.K = h->cfg.d_shared;
     hf.cpad = class_pad(h); hf.o = o; hf.f = f;
     hf.grad_out = grad_out;
-    if (!grad_out) { hf.p = h->buf.w_head; hf.m = h->buf.m_head; hf.v = h->buf.v_head; hf.shadow = ws16(h, h->L.w16); }
+    if (!grad_out) {
+        hf.p = h->buf.w_head; hf.m = h->buf.m_head; hf.v = h->buf.v_head;
+        hf.shadow = h->cfg.precision == UMLH_PREC_BF16 ? ws16(h, h->L.w16) : nullptr;     // the next step's bf16 W shadow
+    }
     return hf;
 }
 static inline bool head_fuse_shape(const umlh_handle_s* h) {
@@ -1570,6 +1588,59 @@ static DiagArgs diag_off(int n_slabs_img) {
     d.dst = nullptr; d.n_slabs_img = n_slabs_img; d.inv_w0 = d.inv_w1 = 0.f; d.part = nullptr; d.ticket = nullptr;
     return d;
 }
+// ... with the gradient diagnostics of the step written to `dst` (NULL: the plain slab sum)
+static DiagArgs diag_live(umlh_handle_t h, const umlh_hyper_t* hy, float* dst, int n_slabs_img) {
+    DiagArgs d = diag_off(n_slabs_img);
+    if (!dst) return d;
+    d.dst = dst;
+    d.part = ws(h, h->L.diag_part);
+    d.ticket = diag_ticket(h);
+    d.cols = h->diag_cols;
+    d.inv_w0 = hy->img_alpha != 0.f ? 1.f / hy->img_alpha : 0.f;
+    d.inv_w1 = hy->alpha != 0.f ? 1.f / hy->alpha : 0.f;
+    return d;
+}
+
+// Update the head from `n` slabs: the split-K slabs of dW_head (train_step_impl) or the one or two parts of the all-reduced
+// gradient message (apply_update_impl).  `keep_shadow`: the W shadow the update kernel writes is the next forward's.
+static int update_head(umlh_handle_t h, const float* slabs, int n, const OptArgs& o, const FinalizeArgs& f, const DiagArgs& dg,
+                       bool keep_shadow, const char* what, hipStream_t st) {
+    const HeadFuse hf = make_head_fuse(h, o, f, slabs, n, h->L.n_head, nullptr);
+    if (hf.K % 8 == 0) {
+        // one launch: slab sum + optimizer + next step's W shadow (bf16 / fp32 fragment-major) + scalars / logit scales
+        float* shadow32 = h->L.w32s ? ws(h, h->L.w32s) : nullptr;
+        HIPCHK(umlh_launch_head_step(&hf, &dg, shadow32, st), what);
+        h->shadow_fresh = (hf.shadow || shadow32) && keep_shadow;
+    } else {
+        // (the two launches touch disjoint memory: the message tail, scalars and logit scales / the head weight and moments)
+        HIPCHK(umlh_launch_finalize(&f, st), "finalize");
+        HIPCHK(umlh_launch_reduce_update(1, slabs, n, hf.slab_stride, h->L.n_head, nullptr, hf.p, hf.m, hf.v, &o, 0, 0, st), "update head");
+    }
+    return UMLH_OK;
+}
+
+// Sum `n` head slabs (the first `n_img` hold image rows) into `out`, a head-sized part of the gradient message.  Image slabs
+// and text slabs are summed separately, then added: the order of the fused step and of the one-launch gradient
+// (step_update_task), so the message is bit-identical whichever launch form wrote it.
+static int sum_head_slabs(umlh_handle_t h, const float* slabs, int n, int n_img, const OptArgs& o, const FinalizeArgs& f, float* out,
+                          const char* what, hipStream_t st) {
+    const HeadFuse hf = make_head_fuse(h, o, f, slabs, n, h->L.n_head, out);
+    if (hf.K % 8 == 0) {
+        const DiagArgs order = diag_off(n_img);
+        HIPCHK(umlh_launch_head_step(&hf, &order, nullptr, st), what);
+    } else {
+        HIPCHK(umlh_launch_finalize(&f, st), "finalize");
+        HIPCHK(umlh_launch_reduce_update(0, slabs, n, hf.slab_stride, h->L.n_head, out, nullptr, nullptr, nullptr, &o, 0, 0, st), what);
+    }
+    return UMLH_OK;
+}
+
+// Update img_proj from `n` slabs of n_proj floats (split-K slabs of dW_proj, or the all-reduced message part)
+static int update_proj(umlh_handle_t h, const float* slabs, int n, const OptArgs& o, hipStream_t st) {
+    HIPCHK(umlh_launch_reduce_update(1, slabs, n, h->L.n_proj, h->L.n_proj, nullptr, h->buf.w_proj, h->buf.m_proj, h->buf.v_proj, &o,
+                                     frozen_lo(h), frozen_hi(h), st), "update proj");
+    return UMLH_OK;
+}
 
 static int train_step_impl(umlh_handle_t h, const umlh_batch_t* img, const umlh_batch_t* txt, const umlh_hyper_t* hy,
                            float* scalars_out, hipStream_t st, bool keep_shadow) {
@@ -1577,43 +1648,21 @@ static int train_step_impl(umlh_handle_t h, const umlh_batch_t* img, const umlh_
     h->dp_diag = false;
     float* tail = ws(h, h->L.grads) + msg_tail_off(h);
     float* diag_dst = h->diagnostics ? (scalars_out ? scalars_out : tail + 2) + UMLH_N_CORE_SCALARS : nullptr;
-    const umlh_config_t& c = h->cfg;
     OptArgs o = make_opt(h->cfg, *hy);
     FinalizeArgs f = make_finalize(h, img, txt, hy, true, scalars_out, true);
     // the update (and the step scalars) may ride in the forward + dW launch: linear bf16 head, no gradient diagnostics
     // (in profiling mode the interval mark 2 -> 3 then holds the whole step and the others are empty)
     StepCall x{img, txt, hy, true, st};
     HeadFuse hfuse;
-    if (head_fuse_shape(h) && !diag_dst) { hfuse = make_head_fuse(h, o, f, nullptr); x.head = &hfuse; }
+    if (head_fuse_shape(h) && !diag_dst) { hfuse = make_head_fuse(h, o, f, ws(h, h->L.slabs_head), 0, h->L.n_head, nullptr); x.head = &hfuse; }
     RC(forward_backward(h, x));
     if (x.head_done) {
         h->shadow_fresh = keep_shadow;
         mark(h, 5, st);
         return UMLH_OK;
     }
-    const int sh = x.n_slabs_head, sp = x.n_slabs_proj;
-    DiagArgs dg;
-    dg.dst = diag_dst; dg.n_slabs_img = x.n_slabs_img;
-    dg.part = ws(h, h->L.diag_part);
-    dg.ticket = diag_ticket(h);
-    dg.inv_w0 = hy->img_alpha != 0.f ? 1.f / hy->img_alpha : 0.f;
-    dg.inv_w1 = hy->alpha != 0.f ? 1.f / hy->alpha : 0.f;
-    dg.cols = h->diag_cols;
-    if (c.d_shared % 8 == 0) {
-        // one launch: slab sum + optimizer + (bf16) next step's W shadow + scalars / logit scales
-        const bool bf = c.precision == UMLH_PREC_BF16;
-        HIPCHK(umlh_launch_head_step(ws(h, h->L.slabs_head), sh, h->L.n_head, c.num_classes, c.d_shared, h->buf.w_head,
-                                     h->buf.m_head, h->buf.v_head, &o, bf ? ws(h, h->L.w16) : nullptr,
-                                     class_pad(h), &f, nullptr, &dg, h->L.w32s ? ws(h, h->L.w32s) : nullptr, st), "head step");
-        h->shadow_fresh = (bf || h->L.w32s) && keep_shadow;
-    } else {
-        HIPCHK(umlh_launch_finalize(&f, st), "finalize");
-        HIPCHK(umlh_launch_reduce_update(1, ws(h, h->L.slabs_head), sh, h->L.n_head, h->L.n_head, nullptr,
-                                         h->buf.w_head, h->buf.m_head, h->buf.v_head, &o, 0, 0, st), "update head");
-    }
-    if (sp > 0)
-        HIPCHK(umlh_launch_reduce_update(1, ws(h, h->L.slabs_proj), sp, h->L.n_proj, h->L.n_proj, nullptr,
-                                         h->buf.w_proj, h->buf.m_proj, h->buf.v_proj, &o, frozen_lo(h), frozen_hi(h), st), "update proj");
+    RC(update_head(h, ws(h, h->L.slabs_head), x.n_slabs_head, o, f, diag_live(h, hy, diag_dst, x.n_slabs_img), keep_shadow, "head step", st));
+    if (x.n_slabs_proj > 0) RC(update_proj(h, ws(h, h->L.slabs_proj), x.n_slabs_proj, o, st));
     mark(h, 5, st);
     return UMLH_OK;
 }
@@ -1653,7 +1702,7 @@ static bool micro_eligible(umlh_handle_t h, const umlh_stream_t* img, const umlh
 }
 
 static int micro_stage(umlh_handle_t h, unsigned char** out) {
-    const size_t need = (size_t)micro_table_floats() * sizeof(float) + (size_t)UMLH_MICRO_MAX_HEADS * sizeof(UmlhMicroHead) + 64;
+    const size_t need = sizeof(UmlhMicroTable) + (size_t)UMLH_MICRO_MAX_HEADS * sizeof(UmlhMicroHead) + 64;
     if (!h->stage) {
         if (hipHostMalloc(reinterpret_cast<void**>(&h->stage), 2 * need, hipHostMallocDefault) != hipSuccess)
             return fail(UMLH_E_HIP, "micro step: pinned staging allocation failed");
@@ -1681,46 +1730,42 @@ static int micro_launch_group(const MicroItem* it, int n, int k0, int n_steps, h
     unsigned char* stage0 = nullptr;
     const int sidx0 = micro_stage(h0, &stage0);
     if (sidx0 < 0) return sidx0;
-    const size_t tab_bytes = (size_t)micro_table_floats() * sizeof(float);
-    UmlhMicroHead* descs = reinterpret_cast<UmlhMicroHead*>(stage0 + tab_bytes);
+    UmlhMicroHead* descs = reinterpret_cast<UmlhMicroHead*>(stage0 + sizeof(UmlhMicroTable));
     int grid = 0;
     for (int i = 0; i < n; ++i) {
         umlh_handle_t h = it[i].h;
         unsigned char* stg = stage0;
         int sidx = sidx0;
         if (i > 0) { sidx = micro_stage(h, &stg); if (sidx < 0) return sidx; }
-        int* offs_i = reinterpret_cast<int*>(stg);
-        int* offs_t = offs_i + UMLH_MICRO_MAX_STEPS + 1;
-        OptArgs* opt = reinterpret_cast<OptArgs*>(offs_t + UMLH_MICRO_MAX_STEPS + 1 + 2);
+        UmlhMicroTable* tab = reinterpret_cast<UmlhMicroTable*>(stg);
         for (int k = 0; k <= n_steps; ++k) {
-            offs_i[k] = it[i].img ? it[i].img->offsets[k0 + k] : 0;
-            offs_t[k] = it[i].txt ? it[i].txt->offsets[k0 + k] : 0;
+            tab->offs[0][k] = it[i].img ? it[i].img->offsets[k0 + k] : 0;
+            tab->offs[1][k] = it[i].txt ? it[i].txt->offsets[k0 + k] : 0;
         }
         for (int k = 0; k < n_steps; ++k) {
             umlh_hyper_t hy;
             memset(&hy, 0, sizeof(hy));
             hy.lr = it[i].lr[k0 + k]; hy.step = it[i].first_step + k0 + k;
-            opt[k] = make_opt(h->cfg, hy);
+            tab->opt[k] = make_opt(h->cfg, hy);
         }
-        float* dtab = ws(h, h->L.mc_tab);
-        HIPCHK((int)hipMemcpyAsync(dtab, stg, tab_bytes, hipMemcpyHostToDevice, st), "micro step: table upload");
+        UmlhMicroTable* dtab = reinterpret_cast<UmlhMicroTable*>(ws(h, h->L.mc_tab));
+        HIPCHK((int)hipMemcpyAsync(dtab, tab, sizeof(UmlhMicroTable), hipMemcpyHostToDevice, st), "micro step: table upload");
         if (i > 0) HIPCHK((int)hipEventRecord(h->stage_ev[sidx], st), "micro step: staging event");
         UmlhMicroHead& d = descs[i];
         memset(&d, 0, sizeof(d));
         const umlh_stream_t* s2[2] = {it[i].img, it[i].txt};
-        int* doffs[2] = {reinterpret_cast<int*>(dtab), reinterpret_cast<int*>(dtab) + UMLH_MICRO_MAX_STEPS + 1};
         for (int m = 0; m < 2; ++m) {
             if (!s2[m]) continue;
-            d.feats[m] = s2[m]->feats; d.labels[m] = s2[m]->labels; d.index[m] = s2[m]->index; d.offs[m] = doffs[m];
+            d.feats[m] = s2[m]->feats; d.labels[m] = s2[m]->labels; d.index[m] = s2[m]->index; d.offs[m] = dtab->offs[m];
         }
         d.w = h->buf.w_head; d.m = h->buf.m_head; d.v = h->buf.v_head;
         d.scales = h->buf.scales; d.m_scales = h->buf.m_scales; d.v_scales = h->buf.v_scales;
-        d.opt = reinterpret_cast<const OptArgs*>(reinterpret_cast<int*>(dtab) + 2 * (UMLH_MICRO_MAX_STEPS + 1) + 2);
+        d.opt = dtab->opt;
         d.scalars_out = it[i].scalars_out ? it[i].scalars_out + (size_t)k0 * UMLH_N_SCALARS : nullptr;
         d.xchg = reinterpret_cast<unsigned long long*>(ws(h, h->L.mc_xchg));
-        d.status = reinterpret_cast<unsigned*>(ws(h, h->L.mc_flags)) + 64;
+        d.status = micro_status(h);
         static const bool dbg_micro = env_int("UMLH_DBG_MICRO", 0) == 1;
-        d.stamps = (dbg_micro && (long long)h->L.max_blocks * 128 * sizeof(float) >= (size_t)h->L.mc_nwg * 96)
+        d.stamps = (dbg_micro && dbg_floats(h->L) * sizeof(float) >= (size_t)h->L.mc_nwg * 96)
                        ? reinterpret_cast<unsigned long long*>(ws(h, h->L.dbg)) : nullptr;
         d.epoch0 = h->micro_epoch;
         h->micro_epoch += (unsigned)n_steps;
@@ -1777,7 +1822,7 @@ int umlh_micro_status(umlh_handle_t h, int32_t* status_out) {
     if (!h->L.mc_flags) return UMLH_OK;
     DeviceGuard dg_(h->device);
     unsigned v = 0;
-    HIPCHK((int)hipMemcpy(&v, reinterpret_cast<unsigned*>(ws(h, h->L.mc_flags)) + 64, sizeof(v), hipMemcpyDeviceToHost), "umlh_micro_status");
+    HIPCHK((int)hipMemcpy(&v, micro_status(h), sizeof(v), hipMemcpyDeviceToHost), "umlh_micro_status");
     *status_out = (int32_t)v;
     return UMLH_OK;
 }
@@ -1789,13 +1834,11 @@ int umlh_step_status(umlh_handle_t h, int32_t* status_out) {
     status_out[0] = status_out[1] = status_out[2] = status_out[3] = 0;
     DeviceGuard dg_(h->device);
     if (h->L.fuse_flags) {
-        const unsigned* st = reinterpret_cast<const unsigned*>(reinterpret_cast<unsigned long long*>(ws(h, h->L.fuse_flags)) + h->L.ctl_tasks) + h->L.ctl_tasks;
-        HIPCHK((int)hipMemcpy(status_out, st, 4 * sizeof(int32_t), hipMemcpyDeviceToHost), "umlh_step_status");
+        HIPCHK((int)hipMemcpy(status_out, step_ctl(h).status, 4 * sizeof(int32_t), hipMemcpyDeviceToHost), "umlh_step_status");
     }
     if (status_out[0] == 0 && h->p2p_on) {       // the direct all-reduce's waits (30 s bound: a peer that never arrives)
         unsigned long long off = 0;
-        const long long n_max = 2 * h->L.n_head + h->L.n_proj + 2 + UMLH_N_SCALARS;
-        if (umlh_p2p_status_offset(n_max, h->n_ranks, &off) == 0) {
+        if (umlh_p2p_status_offset(msg_cap_floats(h->L), h->n_ranks, &off) == 0) {
             unsigned v = 0;
             HIPCHK((int)hipMemcpy(&v, static_cast<unsigned char*>(h->p2p_region[h->p2p_rank]) + off, sizeof(v), hipMemcpyDeviceToHost), "umlh_step_status");
             if (v) { status_out[0] = 2; status_out[1] = (int32_t)(v >> 8); status_out[2] = (int32_t)h->p2p_epoch; status_out[3] = (int32_t)(v & 255u); }
@@ -1867,10 +1910,7 @@ int umlh_train_step(umlh_handle_t h, const umlh_batch_t* img, const umlh_batch_t
 int umlh_train_steps(umlh_handle_t h, const umlh_stream_t* img, const umlh_stream_t* txt, int32_t n_steps,
                      const double* lr, int64_t first_step, float alpha, float img_alpha, float* scalars_out,
                      void* stream) {
-    if (!h || !h->bound) return fail(UMLH_E_UNBOUND, "umlh_train_steps: handle not bound");
-    if (n_steps < 0 || !lr || (!img && !txt)) return fail(UMLH_E_INVALID, "umlh_train_steps: bad arguments");
-    if ((img && (!img->offsets || !img->index)) || (txt && (!txt->offsets || !txt->index)))
-        return fail(UMLH_E_INVALID, "umlh_train_steps: index/offsets required");
+    RC(check_streams(h, img, txt, n_steps, lr, "umlh_train_steps"));
     DeviceGuard dg_(h->device);
     const bool dp = h->n_ranks > 1 || h->dp_force;
     if (dp && h->n_ranks > 1 && !h->comm && !h->ar_fn && !h->p2p_on)
@@ -2024,8 +2064,7 @@ static int dp_allreduce(umlh_handle_t h, float* buf, long long n, hipStream_t st
     if (n <= 0) return UMLH_OK;
     if (h->p2p_on) {                 // direct reduce-scatter + all-gather over the peers' mapped regions (umlh_p2p.hip)
         if (++h->p2p_epoch == 0) h->p2p_epoch = 1;
-        const long long n_max = 2 * h->L.n_head + h->L.n_proj + 2 + UMLH_N_SCALARS;
-        HIPCHK(umlh_p2p_launch(h->p2p_region, h->n_ranks, h->p2p_rank, buf, n, n_max, h->p2p_epoch, st), "p2p all-reduce");
+        HIPCHK(umlh_p2p_launch(h->p2p_region, h->n_ranks, h->p2p_rank, buf, n, msg_cap_floats(h->L), h->p2p_epoch, st), "p2p all-reduce");
         return UMLH_OK;
     }
     if (h->ar_fn) {
@@ -2049,34 +2088,18 @@ static int dp_allreduce(umlh_handle_t h, float* buf, long long n, hipStream_t st
 static int dp_reduce_head(umlh_handle_t h, const StepCall& x) {
     hipStream_t st = x.st;
     const int sh = x.n_slabs_head, si = x.n_slabs_img < sh ? x.n_slabs_img : sh;
-    OptArgs o = make_opt(h->cfg, *x.hy);
-    FinalizeArgs f = make_finalize(h, x.img, x.txt, x.hy, true, nullptr, false);
+    const OptArgs o = make_opt(h->cfg, *x.hy);
+    const FinalizeArgs f = make_finalize(h, x.img, x.txt, x.hy, true, nullptr, false);
+    const float* slabs = ws(h, h->L.slabs_head);
     float* grads = ws(h, h->L.grads);
     const long long nh = h->L.n_head;
-    if (h->dp_diag) {
-        FinalizeArgs f2 = f;
-        f2.partials = nullptr;                           // the step scalars are formed once (first launch)
-        DiagArgs none = diag_off(si);
-        if (si > 0) HIPCHK(umlh_launch_head_step(ws(h, h->L.slabs_head), si, nh, h->cfg.num_classes, h->cfg.d_shared, nullptr, nullptr,
-                                                 nullptr, &o, nullptr, class_pad(h), &f, grads, &none, nullptr, st), "reduce head (image rows)");
-        else HIPCHK((int)hipMemsetAsync(grads, 0, sizeof(float) * nh, st), "zero image gradient");
-        none.n_slabs_img = 0;
-        if (sh - si > 0) HIPCHK(umlh_launch_head_step(ws(h, h->L.slabs_head) + (size_t)si * nh, sh - si, nh, h->cfg.num_classes, h->cfg.d_shared,
-                                                      nullptr, nullptr, nullptr, &o, nullptr, class_pad(h), si > 0 ? &f2 : &f, grads + nh,
-                                                      &none, nullptr, st), "reduce head (text rows)");
-        else HIPCHK((int)hipMemsetAsync(grads + nh, 0, sizeof(float) * nh, st), "zero text gradient");
-        return UMLH_OK;
-    }
-    if (h->cfg.d_shared % 8 == 0) {
-        // image slabs and text slabs are summed separately, then added: the order of the fused step and of the one-launch
-        // gradient (step_update_task), so the message is bit-identical whichever launch form wrote it
-        DiagArgs order = diag_off(si);
-        HIPCHK(umlh_launch_head_step(ws(h, h->L.slabs_head), sh, nh, h->cfg.num_classes, h->cfg.d_shared, nullptr, nullptr, nullptr, &o,
-                                     nullptr, class_pad(h), &f, grads, &order, nullptr, st), "reduce head");
-    } else {
-        HIPCHK(umlh_launch_finalize(&f, st), "finalize");
-        HIPCHK(umlh_launch_reduce_update(0, ws(h, h->L.slabs_head), sh, nh, nh, grads, nullptr, nullptr, nullptr, &o, 0, 0, st), "reduce head");
-    }
+    if (!h->dp_diag) return sum_head_slabs(h, slabs, sh, si, o, f, grads, "reduce head", st);
+    FinalizeArgs f2 = f;
+    f2.partials = nullptr;                               // the step scalars are formed once (first launch)
+    if (si > 0) RC(sum_head_slabs(h, slabs, si, si, o, f, grads, "reduce head (image rows)", st));
+    else HIPCHK((int)hipMemsetAsync(grads, 0, sizeof(float) * nh, st), "zero image gradient");
+    if (sh - si > 0) RC(sum_head_slabs(h, slabs + (size_t)si * nh, sh - si, 0, o, si > 0 ? f2 : f, grads + nh, "reduce head (text rows)", st));
+    else HIPCHK((int)hipMemsetAsync(grads + nh, 0, sizeof(float) * nh, st), "zero text gradient");
     return UMLH_OK;
 }
 
@@ -2100,7 +2123,7 @@ static int grad_step_impl(umlh_handle_t h, const umlh_batch_t* img, const umlh_b
     h->last_rows_txt = txt ? txt->rows : 0;
     h->global_rows_img = img ? img->global_rows : 0;
     h->global_rows_txt = txt ? txt->global_rows : 0;
-    h->dp_diag = h->diagnostics && h->cfg.d_shared % 8 == 0;
+    h->dp_diag = split_diag(h);
     float* grads = ws(h, h->L.grads);
     if (h->last_rows_img + h->last_rows_txt == 0) {       // no local row: this rank contributes zeros to the all-reduce
         HIPCHK((int)hipMemsetAsync(grads, 0, sizeof(float) * msg_len(h), st), "zero gradient buffer");
@@ -2115,7 +2138,7 @@ static int grad_step_impl(umlh_handle_t h, const umlh_batch_t* img, const umlh_b
     // linear bf16 head: the slab sum into the message (and the step scalars) rides in the forward + dW launch
     HeadFuse hfuse;
     if (head_fuse_shape(h) && !h->dp_diag && !overlap) {
-        hfuse = make_head_fuse(h, o, make_finalize(h, img, txt, hy, true, nullptr, false), grads);
+        hfuse = make_head_fuse(h, o, make_finalize(h, img, txt, hy, true, nullptr, false), ws(h, h->L.slabs_head), 0, h->L.n_head, grads);
         x.head = &hfuse;
     }
     RC(forward_backward(h, x));
@@ -2152,15 +2175,14 @@ int umlh_grad_step(umlh_handle_t h, const umlh_batch_t* img, const umlh_batch_t*
 int umlh_debug_buffer(umlh_handle_t h, void** device_ptr, uint64_t* n_bytes) {
     if (!h || !h->bound) return fail(UMLH_E_UNBOUND, "umlh_debug_buffer: handle not bound");
     if (device_ptr) *device_ptr = ws(h, h->L.dbg);
-    if (n_bytes) *n_bytes = (uint64_t)h->L.max_blocks * 128 * sizeof(float);
+    if (n_bytes) *n_bytes = (uint64_t)dbg_floats(h->L) * sizeof(float);
     return UMLH_OK;
 }
 
 int umlh_grad_buffer(umlh_handle_t h, float** device_ptr, uint64_t* n_floats) {
     if (!h || !h->bound) return fail(UMLH_E_UNBOUND, "umlh_grad_buffer: handle not bound");
     if (device_ptr) *device_ptr = ws(h, h->L.grads);
-    const bool diag = h->diagnostics && h->cfg.d_shared % 8 == 0;        // the layout umlh_grad_step will use
-    if (n_floats) *n_floats = (uint64_t)((diag ? 2 : 1) * h->L.n_head + h->L.n_proj + 2 + UMLH_N_SCALARS);
+    if (n_floats) *n_floats = (uint64_t)msg_floats(h->L, split_diag(h));         // the layout umlh_grad_step will use
     return UMLH_OK;
 }
 
@@ -2168,33 +2190,12 @@ static int apply_update_impl(umlh_handle_t h, const umlh_hyper_t* hy, float* sca
     OptArgs o = make_opt(h->cfg, *hy);
     float* grads = ws(h, h->L.grads);
     FinalizeArgs f = make_finalize(h, nullptr, nullptr, hy, false, scalars_out, true);
-    if (h->cfg.d_shared % 8 == 0) {
-        const bool bf = h->cfg.precision == UMLH_PREC_BF16;
-        DiagArgs dg;
-        dg.dst = nullptr; dg.n_slabs_img = 1; dg.inv_w0 = dg.inv_w1 = 0.f;
-        dg.part = ws(h, h->L.diag_part);
-        dg.ticket = diag_ticket(h);
-        dg.cols = h->diag_cols;
-        if (h->dp_diag) {
-            // the two all-reduced per-modality gradients are the two "slabs" of the update kernel: it sums them, steps the
-            // weights and accumulates dot / norms / sign agreement of the GLOBAL gradients (finetune.py:203-206)
-            float* dst = (scalars_out ? scalars_out : f.tail + 2) + UMLH_N_CORE_SCALARS;
-            dg.dst = dst;
-            dg.inv_w0 = hy->img_alpha != 0.f ? 1.f / hy->img_alpha : 0.f;
-            dg.inv_w1 = hy->alpha != 0.f ? 1.f / hy->alpha : 0.f;
-        }
-        HIPCHK(umlh_launch_head_step(grads, h->dp_diag ? 2 : 1, h->L.n_head, h->cfg.num_classes, h->cfg.d_shared, h->buf.w_head,
-                                     h->buf.m_head, h->buf.v_head, &o, bf ? ws(h, h->L.w16) : nullptr, class_pad(h), &f, nullptr,
-                                     h->dp_diag ? &dg : nullptr, h->L.w32s ? ws(h, h->L.w32s) : nullptr, st), "update head");
-        h->shadow_fresh = bf || h->L.w32s;              // the next umlh_grad_step may trust it (see umlh_grad_step)
-    } else {
-        HIPCHK(umlh_launch_reduce_update(1, grads, 1, h->L.n_head, h->L.n_head, nullptr, h->buf.w_head, h->buf.m_head,
-                                         h->buf.v_head, &o, 0, 0, st), "update head");
-        HIPCHK(umlh_launch_finalize(&f, st), "finalize");
-    }
-    if (h->cfg.has_proj && h->global_rows_img > 0)
-        HIPCHK(umlh_launch_reduce_update(1, grads + msg_head_len(h), 1, h->L.n_proj, h->L.n_proj, nullptr, h->buf.w_proj,
-                                         h->buf.m_proj, h->buf.v_proj, &o, frozen_lo(h), frozen_hi(h), st), "update proj");
+    // dp_diag: the two all-reduced per-modality gradients are the two "slabs" of the update kernel: it sums them, steps the
+    // weights and accumulates dot / norms / sign agreement of the GLOBAL gradients (finetune.py:203-206).
+    // (the shadow the update writes: the next umlh_grad_step may trust it, see umlh_grad_step)
+    float* diag_dst = h->dp_diag ? (scalars_out ? scalars_out : f.tail + 2) + UMLH_N_CORE_SCALARS : nullptr;
+    RC(update_head(h, grads, h->dp_diag ? 2 : 1, o, f, diag_live(h, hy, diag_dst, 1), true, "update head", st));
+    if (h->cfg.has_proj && h->global_rows_img > 0) RC(update_proj(h, grads + msg_head_len(h), 1, o, st));
     return UMLH_OK;
 }
 
@@ -2205,40 +2206,33 @@ int umlh_apply_update(umlh_handle_t h, const umlh_hyper_t* hy, float* scalars_ou
     return apply_update_impl(h, hy, scalars_out, (hipStream_t)stream);
 }
 
-int umlh_eval_batch(umlh_handle_t h, const umlh_batch_t* b, float* scalars_out, void* stream) {
-    if (!h || !h->bound) return fail(UMLH_E_UNBOUND, "umlh_eval_batch: handle not bound");
-    if (!b || !scalars_out) return fail(UMLH_E_INVALID, "umlh_eval_batch: null argument");
+// Forward only over one batch of image-side rows: the step scalars (umlh_eval_batch) or the per-row {CE, correct} (umlh_eval_rows)
+static int eval_impl(umlh_handle_t h, const umlh_batch_t* b, float* scalars_out, float* row_stats, void* stream, const char* who) {
+    if (!h || !h->bound) return fail(UMLH_E_UNBOUND, "%s: handle not bound", who);
+    if (!b || (!scalars_out && !row_stats)) return fail(UMLH_E_INVALID, "%s: null argument", who);
     DeviceGuard dg_(h->device);
-    int rc = check_batch(h, b, h->cfg.max_rows_img, "umlh_eval_batch");
-    if (rc) return rc;
-    if (b->rows == 0) return fail(UMLH_E_INVALID, "umlh_eval_batch: empty batch");
+    RC(check_batch(h, b, h->cfg.max_rows_img, who));
+    if (b->rows == 0) return fail(UMLH_E_INVALID, "%s: empty batch", who);
     hipStream_t st = (hipStream_t)stream;
     umlh_hyper_t hy;
     memset(&hy, 0, sizeof(hy));
     hy.lr = 0; hy.step = 1; hy.alpha = 1.f; hy.img_alpha = 1.f;
     h->shadow_fresh = false;
     StepCall x{b, nullptr, &hy, false, st};
-    rc = forward_backward(h, x);
-    if (rc) return rc;
+    x.row_stats = row_stats;
+    RC(forward_backward(h, x));
+    if (!scalars_out) return UMLH_OK;
     FinalizeArgs f = make_finalize(h, b, nullptr, &hy, true, scalars_out, false);
     HIPCHK(umlh_launch_finalize(&f, st), "finalize");
     return UMLH_OK;
 }
 
+int umlh_eval_batch(umlh_handle_t h, const umlh_batch_t* b, float* scalars_out, void* stream) {
+    return eval_impl(h, b, scalars_out, nullptr, stream, "umlh_eval_batch");
+}
+
 int umlh_eval_rows(umlh_handle_t h, const umlh_batch_t* b, float* row_stats, void* stream) {
-    if (!h || !h->bound) return fail(UMLH_E_UNBOUND, "umlh_eval_rows: handle not bound");
-    if (!b || !row_stats) return fail(UMLH_E_INVALID, "umlh_eval_rows: null argument");
-    DeviceGuard dg_(h->device);
-    int rc = check_batch(h, b, h->cfg.max_rows_img, "umlh_eval_rows");
-    if (rc) return rc;
-    if (b->rows == 0) return fail(UMLH_E_INVALID, "umlh_eval_rows: empty batch");
-    umlh_hyper_t hy;
-    memset(&hy, 0, sizeof(hy));
-    hy.lr = 0; hy.step = 1; hy.alpha = 1.f; hy.img_alpha = 1.f;
-    h->shadow_fresh = false;
-    StepCall x{b, nullptr, &hy, false, (hipStream_t)stream};
-    x.row_stats = row_stats;
-    return forward_backward(h, x);
+    return eval_impl(h, b, nullptr, row_stats, stream, "umlh_eval_rows");
 }
 
 // ---- linear probes (kernels: umlh_kernels_probe.hip); every check precedes the first HIP call ----

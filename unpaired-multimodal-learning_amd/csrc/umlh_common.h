@@ -401,6 +401,17 @@ struct StepCtl {
     unsigned* status;            // [4]: code (0 = ok), task waited on, epoch, phase
     unsigned epoch;              // never 0
 };
+// The region the host gives them in a handle's workspace, for `cap` tasks: [cap] u64 done, [cap] u32 claim, then 16 u32 of
+// status (the kernel uses the first 4).  done and claim are epoch-tagged and may be restarted together (tag wrap); the status is
+// sticky and cleared at bind only.
+constexpr int UMLH_CTL_STATUS_WORDS = 16;
+static inline long long step_ctl_floats(long long cap) { return 3 * cap + UMLH_CTL_STATUS_WORDS; }
+static inline StepCtl step_ctl_at(float* base, long long cap) {      // (the epoch is the launch's)
+    unsigned long long* done = reinterpret_cast<unsigned long long*>(base);
+    unsigned* claim = reinterpret_cast<unsigned*>(done + cap);
+    return StepCtl{claim, done, claim + cap, 0u};
+}
+static inline size_t step_ctl_tag_bytes(const StepCtl& c) { return (size_t)(reinterpret_cast<char*>(c.status) - reinterpret_cast<char*>(c.done)); }
 constexpr int TW_OK = -1, TW_ABORT = -2;
 constexpr unsigned long long UMLH_SPIN_TICKS = 5000000ull;     // 50 ms of s_memrealtime (100 MHz)
 

@@ -1865,20 +1865,19 @@ int umlh_launch_multi_opt(int n, float* const* p, const float* const* g, float* 
     return (int)hipGetLastError();
 }
 
-int umlh_launch_head_step(const float* slabs, int n_slabs, long long slab_stride, int C, int K, float* p, float* m,
-                          float* v, const OptArgs* o, void* shadow, int cpad, const FinalizeArgs* f, float* grad_out,
-                          const DiagArgs* dg, float* shadow32, hipStream_t stream) {
-    long long n4 = (long long)C * K / 4;
+// hf: the slabs, the head (or grad_out) and the optimizer / finalize arguments, as make_head_fuse fills them (n_sub, dw_per_row
+// and n_slabs_img belong to the one-launch step: the slab order of this launch is dg's)
+int umlh_launch_head_step(const HeadFuse* hf, const DiagArgs* dg, float* shadow32, hipStream_t stream) {
+    long long n4 = (long long)hf->C * hf->K / 4;
     int blocks = (int)((n4 + 255) / 256) + 1;                 // + the finalize block
-    DiagArgs d;
-    if (dg) d = *dg; else { d.dst = nullptr; d.n_slabs_img = n_slabs; d.inv_w0 = d.inv_w1 = 0.f; d.part = nullptr; d.ticket = nullptr; d.cols = 0; }
+    DiagArgs d = *dg;
     if (d.dst && (!d.part || !d.ticket)) return (int)hipErrorInvalidValue;
-    if (d.n_slabs_img > n_slabs) d.n_slabs_img = n_slabs;
-    OptArgs oc = *o;
+    if (d.n_slabs_img > hf->n_slabs) d.n_slabs_img = hf->n_slabs;
+    OptArgs oc = hf->o;
     oc.plain = umlh_plain_stores();
     oc.x3 = umlh_f32_x3();
-    hipLaunchKernelGGL(head_step_kernel, dim3(blocks), dim3(256), 0, stream, slabs, n_slabs, slab_stride, C, K, p, m, v, oc,
-                       (unsigned short*)shadow, cpad, *f, grad_out, d, shadow32);
+    hipLaunchKernelGGL(head_step_kernel, dim3(blocks), dim3(256), 0, stream, hf->slabs, hf->n_slabs, hf->slab_stride, hf->C, hf->K,
+                       hf->p, hf->m, hf->v, oc, hf->shadow, hf->cpad, hf->f, hf->grad_out, d, shadow32);
     return (int)hipGetLastError();
 }
 

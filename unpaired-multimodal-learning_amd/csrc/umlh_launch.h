@@ -18,9 +18,7 @@ int umlh_launch_reduce_update(int mode, const float* slabs, int n_slabs, long lo
                               hipStream_t stream);
 int umlh_launch_multi_opt(int n, float* const* p, const float* const* g, float* const* m, float* const* v, const long long* cnt,
                           const OptArgs* o, hipStream_t stream);
-int umlh_launch_head_step(const float* slabs, int n_slabs, long long slab_stride, int C, int K, float* p, float* m, float* v,
-                          const OptArgs* o, void* shadow, int cpad, const FinalizeArgs* f, float* grad_out, const DiagArgs* dg,
-                          float* shadow32, hipStream_t stream);
+int umlh_launch_head_step(const HeadFuse* hf, const DiagArgs* dg, float* shadow32, hipStream_t stream);
 int umlh_launch_feistel_perm(long long n, unsigned long long seed, long long* out, hipStream_t stream);
 int umlh_launch_finalize(const FinalizeArgs* f, hipStream_t stream);
 int umlh_launch_zero_shot(const float* feats, const int64_t* labels, long long n, int d, int C, float* w, hipStream_t stream);

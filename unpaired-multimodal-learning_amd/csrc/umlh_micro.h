@@ -1,6 +1,7 @@
 // Descriptor of one head of a micro-step launch (umlh_kernels_micro.hip); filled by umlh_api.cpp, read by the kernel
 // from a device array.
 #pragma once
+#include <cstddef>
 #include "umlh_common.h"
 
 #define UMLH_MICRO_CS        16     /* classes per workgroup (one 16-row MFMA tile)                       */
@@ -26,3 +27,26 @@ struct UmlhMicroHead {
     int   learnable, opt_kind;
     float w_img, w_txt;             // loss weights (img_alpha, alpha)
 };
+
+// ---- the micro-step regions of a handle's workspace, as the host lays them out (the kernel only ever sees the pointers
+// of UmlhMicroHead into them) ----
+// Per-launch tables of one head: staged in pinned host memory, copied to the workspace in one piece.
+struct UmlhMicroTable {
+    int     offs[2][UMLH_MICRO_MAX_STEPS + 1];   // UmlhMicroHead::offs of the image / text stream
+    int     pad[2];
+    OptArgs opt[UMLH_MICRO_MAX_STEPS];           // UmlhMicroHead::opt
+};
+static_assert(sizeof(UmlhMicroTable) % sizeof(float) == 0, "the workspace is partitioned in floats");
+static_assert(offsetof(UmlhMicroTable, opt) == (2 * (UMLH_MICRO_MAX_STEPS + 1) + 2) * sizeof(int), "opt follows the two offset tables");
+static_assert(sizeof(UmlhMicroTable) == offsetof(UmlhMicroTable, opt) + UMLH_MICRO_MAX_STEPS * sizeof(OptArgs), "no tail padding");
+
+// Epoch flags and the status word; zeroed at bind together with the exchange granules that follow it in the workspace.
+struct UmlhMicroFlags {
+    unsigned epoch[64];             // [nwg <= 64]
+    unsigned status;                // UmlhMicroHead::status
+    unsigned pad[63];
+};
+static_assert(sizeof(UmlhMicroFlags) == 128 * sizeof(float), "a whole number of 64-float workspace granules");
+
+// exchange granules of one head (UmlhMicroHead::xchg), in floats
+static inline long long umlh_micro_xchg_floats(int nwg) { return 2LL * nwg * 5 * UMLH_MICRO_MAX_ROWS * 2; }
