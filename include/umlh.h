@@ -709,6 +709,57 @@ int  umlh_seq_step_stats(const float* x, int64_t ldb, int64_t ldt, const float* 
                          int32_t b, int32_t t_len, int32_t d, const int64_t* lengths, double* out4, void* scratch,
                          uint64_t scratch_bytes, void* stream);
 
+/* ---- rollout and spectral-bias spectra of the MultiBench loop (MultiBench/train.py:245-292).  Additive to
+ * ABI v11: umlh_version() is unchanged, callers detect the feature by these symbols.  Every argument check happens before any
+ * HIP call; everything runs on `stream`; outputs are device memory; no float atomics, no workgroup waits on another one. */
+
+#define UMLH_ROLLOUT_MAX_LAYERS 16
+#define UMLH_ROLLOUT_MAX_LDS    (160 * 1024)
+#define UMLH_SPECTRUM_MAX_T     1024
+
+typedef struct {
+    int32_t Z;          /* encoder width                                   1..512   */
+    int32_t d_ff;       /* feed-forward width                              1..2048  */
+    int32_t D;          /* modality width (in- and out-projection)         1..1024  */
+    int32_t n_layers;   /* 0..UMLH_ROLLOUT_MAX_LAYERS                               */
+    int32_t steps;      /* generated frames                                0..4096  */
+    float   eps;        /* LayerNorm eps, >= 0                                      */
+} umlh_rollout_cfg_t;
+
+/* The reference's rollout() for one modality in one launch.  At T = 1 the causal softmax over a single key is exactly 1, so a
+ * layer's attention is out_proj(v_proj(h)) and every row evolves on its own.  For row r, with the 12 tensors per layer in the
+ * order of umlh_encoder_layer_forward (W_v, b_v = rows 2Z..3Z-1 of in_proj_weight / in_proj_bias):
+ *   cur_0 = x0[r]                                                     x0[r, c] read at x0[r*ldx + c]
+ *   for s = 1..steps:
+ *     h = Wc (W_in cur_{s-1} + b_in) + pos0                           conv_w_or_null [Z, Z], pos0_or_null [Z]: absent when NULL
+ *     per layer: a = W_o (W_v h + b_v) + b_o;  h = LN1(h + a);  f = W_2 relu(W_1 h + b_1) + b_2;  h = LN2(h + f)
+ *     cur_s = W_out h + b_out
+ *   out[r*ldb + s*ldt + c] = cur_s[c] for s = 0..steps (s = 0 is the seed itself, the reference's pred_x = [x]).
+ * Post-norm, biased variance from the differences to the mean, rsqrt(var + eps); relu is fmaxf(v, 0) (NaN -> 0); no dropout:
+ * the reference's rollout runs in eval mode.  Products on the fp32 MFMA, fp32 accumulation in one fma chain per output whose
+ * order depends on the two lengths of the product alone (blocks of 16 k ascending; inside a block k = k0 + i, k0 + 4 + i,
+ * k0 + 8 + i, k0 + 12 + i for i = 0..3; a product with fewer than 8 tiles of 16 outputs cuts its blocks into up to 8 contiguous
+ * runs whose sums are added in run order).  A workgroup owns 16 rows and reads nothing another workgroup writes: a row's trajectory is
+ * bitwise the same whatever n, its index in the batch, the stream and the CU count.
+ * Envelope: 1 <= Z <= 512, 1 <= d_ff <= 2048, 1 <= D <= 1024, 0 <= n_layers <= 16, 0 <= steps <= 4096, 1 <= n <= 2^20,
+ * ldx >= D, ldt >= D, ldb >= steps*ldt + D (rows of out do not overlap); out may alias x0 only as a whole: x0[r] being out[r, 0, :] itself.  Weights are dense row-major
+ * ([out, in], as nn.Linear keeps them).  There is no fallback: a shape outside the envelope is UMLH_E_INVALID. */
+int  umlh_rollout(const umlh_rollout_cfg_t* cfg, const float* const* P, const float* conv_w_or_null, const float* pos0_or_null,
+                  const float* w_in, const float* b_in, const float* w_out, const float* b_out, const float* x0, int64_t ldx,
+                  int64_t n, float* out, int64_t ldb, int64_t ldt, void* stream);
+
+/* torch.abs(torch.fft.rfft(x, dim=1)).mean(dim=(0, 2)) of a [b, t_len, d] block read at x[b*ldb + t*ldt + c], T = t_len:
+ *   out[k] = (1 / (b d)) sum_{b,c} | sum_t x[b,t,c] e^{-2 pi i k t / T} |    for k = 0..T/2      (T/2 + 1 device doubles)
+ * A direct DFT: cos / sin(2 pi ((k t) mod T) / T) from an fp64 table built once per workgroup, products and sums in fp64 from
+ * the fp32 inputs, t ascending.  Two launches (partial sums into scratch, a fixed-order final), no host sync, no lengths mask
+ * (the reference has none).  The grid and every summation order are functions of (b, t_len, d) alone: results are bitwise
+ * reproducible across calls and streams and do not depend on the CU count.  No sequential chain of additions is longer than
+ * 4096 terms.  Envelope: 1 <= t_len <= 1024, d >= 1, 1 <= b <= 2^20, non-overlapping ldb, ldt >= d as umlh_seq_step_stats
+ * allows, and ceil(b / 16) * ceil(d / 16) <= 2^20 partial vectors. */
+uint64_t umlh_seq_spectrum_scratch_bytes(int32_t b, int32_t t_len, int32_t d);   /* 0 on invalid arguments */
+int  umlh_seq_spectrum(const float* x, int64_t ldb, int64_t ldt, int32_t b, int32_t t_len, int32_t d, double* out, void* scratch,
+                       uint64_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

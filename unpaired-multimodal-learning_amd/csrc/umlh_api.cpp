@@ -1031,6 +1031,62 @@ int umlh_seq_step_stats(const float* x, int64_t ldb, int64_t ldt, const float* r
     return UMLH_OK;
 }
 
+// ---- rollout and spectra (kernels: umlh_kernels_rollout.hip); every check precedes the first HIP call ----
+int umlh_rollout(const umlh_rollout_cfg_t* cfg, const float* const* P, const float* conv_w_or_null, const float* pos0_or_null,
+                 const float* w_in, const float* b_in, const float* w_out, const float* b_out, const float* x0, int64_t ldx, int64_t n,
+                 float* out, int64_t ldb, int64_t ldt, void* stream) {
+    const char* who = "umlh_rollout";
+    if (!cfg) return fail(UMLH_E_INVALID, "%s: cfg is NULL", who);
+    if (!w_in || !b_in || !w_out || !b_out || !x0 || !out)
+        return fail(UMLH_E_INVALID, "%s: null pointer (w_in, b_in, w_out, b_out, x0 and out are required)", who);
+    if (cfg->Z < 1 || cfg->Z > 512) return fail(UMLH_E_INVALID, "%s: Z=%d outside the envelope 1..512", who, cfg->Z);
+    if (cfg->d_ff < 1 || cfg->d_ff > 2048) return fail(UMLH_E_INVALID, "%s: d_ff=%d outside the envelope 1..2048", who, cfg->d_ff);
+    if (cfg->D < 1 || cfg->D > 1024) return fail(UMLH_E_INVALID, "%s: D=%d outside the envelope 1..1024", who, cfg->D);
+    if (cfg->n_layers < 0 || cfg->n_layers > UMLH_ROLLOUT_MAX_LAYERS)
+        return fail(UMLH_E_INVALID, "%s: n_layers=%d outside 0..%d", who, cfg->n_layers, UMLH_ROLLOUT_MAX_LAYERS);
+    if (cfg->steps < 0 || cfg->steps > 4096) return fail(UMLH_E_INVALID, "%s: steps=%d outside 0..4096", who, cfg->steps);
+    if (!(cfg->eps >= 0.0f)) return fail(UMLH_E_INVALID, "%s: eps=%g (need eps >= 0)", who, (double)cfg->eps);
+    if (n < 1 || n > ((int64_t)1 << 20)) return fail(UMLH_E_INVALID, "%s: n=%lld rows (need 1 <= n <= 2^20)", who, (long long)n);
+    if (cfg->n_layers > 0 && !P) return fail(UMLH_E_INVALID, "%s: P is NULL with n_layers=%d", who, cfg->n_layers);
+    for (int i = 0; i < 12 * cfg->n_layers; ++i)
+        if (!P[i]) return fail(UMLH_E_INVALID, "%s: P[%d] is NULL (12 tensors per layer)", who, i);
+    if (ldx < cfg->D) return fail(UMLH_E_INVALID, "%s: ldx=%lld < D=%d", who, (long long)ldx, cfg->D);
+    if (ldt < cfg->D) return fail(UMLH_E_INVALID, "%s: ldt=%lld < D=%d", who, (long long)ldt, cfg->D);
+    if (ldb < (int64_t)cfg->steps * ldt + cfg->D)
+        return fail(UMLH_E_INVALID, "%s: ldb=%lld < steps*ldt + D = %lld (rows of out would overlap)", who, (long long)ldb,
+                    (long long)((int64_t)cfg->steps * ldt + cfg->D));
+    if (umlh_rollout_lds_bytes(cfg->Z, cfg->d_ff, cfg->D) > UMLH_ROLLOUT_MAX_LDS)
+        return fail(UMLH_E_INVALID, "%s: Z=%d D=%d outside the envelope (LDS)", who, cfg->Z, cfg->D);
+    HIPCHK(umlh_rollout_launch(cfg, P, conv_w_or_null, pos0_or_null, w_in, b_in, w_out, b_out, x0, ldx, n, out, ldb, ldt,
+                               (hipStream_t)stream), who);
+    return UMLH_OK;
+}
+
+static bool spectrum_shape_ok(int32_t b, int32_t t_len, int32_t d) {
+    return b >= 1 && b <= (1 << 20) && t_len >= 1 && t_len <= UMLH_SPECTRUM_MAX_T && d >= 1 && umlh_spectrum_partials(b, t_len, d) >= 0;
+}
+
+uint64_t umlh_seq_spectrum_scratch_bytes(int32_t b, int32_t t_len, int32_t d) {
+    return spectrum_shape_ok(b, t_len, d) ? umlh_spectrum_bytes(b, t_len, d) : 0;
+}
+
+int umlh_seq_spectrum(const float* x, int64_t ldb, int64_t ldt, int32_t b, int32_t t_len, int32_t d, double* out, void* scratch,
+                      uint64_t scratch_bytes, void* stream) {
+    const char* who = "umlh_seq_spectrum";
+    if (!x || !out || !scratch) return fail(UMLH_E_INVALID, "%s: null pointer (x, out and scratch are required)", who);
+    if (d < 1) return fail(UMLH_E_INVALID, "%s: d=%d < 1", who, d);
+    if (b < 1 || b > (1 << 20)) return fail(UMLH_E_INVALID, "%s: b=%d outside 1..2^20", who, b);
+    if (t_len < 1 || t_len > UMLH_SPECTRUM_MAX_T) return fail(UMLH_E_INVALID, "%s: t_len=%d outside 1..%d", who, t_len, UMLH_SPECTRUM_MAX_T);
+    if (!spectrum_shape_ok(b, t_len, d))
+        return fail(UMLH_E_INVALID, "%s: b=%d d=%d too large (need ceil(b / 16) * ceil(d / 16) <= 2^20)", who, b, d);
+    if (int e = check_seq_view(who, "ldb", "ldt", b, t_len, d, ldb, ldt)) return e;
+    const uint64_t need = umlh_spectrum_bytes(b, t_len, d);
+    if (scratch_bytes < need)
+        return fail(UMLH_E_INVALID, "%s: scratch of %llu bytes, %llu needed", who, (unsigned long long)scratch_bytes, (unsigned long long)need);
+    HIPCHK(umlh_spectrum_launch(x, ldb, ldt, b, t_len, d, out, scratch, (hipStream_t)stream), who);
+    return UMLH_OK;
+}
+
 int umlh_to_bf16(const float* src, void* dst, int64_t n, void* stream) {
     if (!src || !dst || n < 0) return fail(UMLH_E_INVALID, "umlh_to_bf16: bad arguments");
     HIPCHK(umlh_launch_to_bf16(src, dst, n, (hipStream_t)stream), "to_bf16");

@@ -156,6 +156,14 @@ long long umlh_stepstats_partials(int B, int T, int d);       // partial sums of
 unsigned long long umlh_stepstats_bytes(int B, int T, int d);
 int umlh_stepstats_launch(const float* x, long long ldb, long long ldt, const float* recon, long long ldb_r, long long ldt_r, int B, int T,
                           int d, const long long* lengths, double* out4, void* scratch, hipStream_t st);
+// ---- umlh_kernels_rollout.hip: one-launch rollout, spectral-bias spectra ----
+unsigned long long umlh_rollout_lds_bytes(int Z, int dff, int D);
+int umlh_rollout_launch(const umlh_rollout_cfg_t* cfg, const float* const* P, const float* conv_w, const float* pos0, const float* w_in,
+                        const float* b_in, const float* w_out, const float* b_out, const float* x0, long long ldx, long long n, float* out,
+                        long long ldb, long long ldt, hipStream_t st);
+long long umlh_spectrum_partials(int B, int T, int d);        // partial vectors of one call; -1: more than the final kernel takes
+unsigned long long umlh_spectrum_bytes(int B, int T, int d);
+int umlh_spectrum_launch(const float* x, long long ldb, long long ldt, int B, int T, int d, double* out, void* scratch, hipStream_t st);
 
 // ---- umlh_api.cpp, for umlh_encoder.cpp ----
 // out[M,N] (ldo == N) = epilogue(A B^T) with the operand layouts of umlh_gemm_f32.  `splits` K-slabs go to `slabs`

@@ -10,8 +10,11 @@ a fixed sample of sequence pairs through the model at every in-loop evaluation, 
 and compared by ``umlh.align`` and ``umlh.paired_cosine`` (``multibench.capture``).
 ``train(step_diagnostics=True)`` records the remaining ``train/*`` values the reference logs after every optimizer step
 (train.py:403-439): the trivial next-frame losses and ``recon_y_loss`` on the HIP kernel of ``umlh.seq_step_stats``, and the
-norms, ``loss_private`` and ``diff_next_*`` the forward already returns.  The covariance matrices the reference forms and drops
-(train.py:386,388) and wandb itself are outside this port."""
+norms, ``loss_private`` and ``diff_next_*`` the forward already returns.
+``rollout`` (train.py:268-292) generates every step of every row in one launch of ``umlh.rollout_rows``; ``spectral_bias`` /
+``analyze_spectral_bias`` (train.py:245-266) take their spectra from ``umlh.seq_spectrum``; ``train(rollout_spectra=True)`` is
+the reference's block train.py:474-482.  The covariance matrices the reference forms and drops (train.py:386,388) and wandb
+itself are outside this port."""
 from __future__ import annotations
 
 import copy
@@ -241,9 +244,107 @@ def _record_diagnostics(diag, out, x1, l1, x2, l2, dev):
             put(k, out[k])
 
 
+# ---- rollout and spectral bias (train.py:245-292) ----
+def _rollout_params(model, proj_in, dec):
+    """The arguments of ``umlh.rollout_rows`` for one modality of ``model``."""
+    from .encoder import layer_params
+    enc = model.encoder
+    if getattr(enc, "out_last", False):
+        raise ValueError("rollout: the encoder returns only its last token (out_last=True); the decoder needs [B, T, Z] "
+                         "(the reference's own indexing fails there)")
+    pos0 = None
+    if enc.pos_embd:
+        pos0 = enc.pos_embedding.weight[0] if enc.pos_learnable else enc.pos_table[0]
+    layers = enc.transformer.layers
+    lp = [t for layer in layers for t in layer_params(layer)]
+    eps = float(layers[0].norm1.eps) if len(layers) else 1e-5
+    return proj_in.fc.weight, proj_in.fc.bias, enc.conv.weight if enc.conv1d else None, pos0, lp, eps, dec.fc.weight, dec.fc.bias
+
+
+@torch.no_grad()
+def rollout(model, x, y, steps=10):
+    """The reference's rollout (train.py:268-292): each input [B, T0, D] is continued from its LAST frame for ``steps``
+    frames through in-projection, shared encoder and decoder, and returned as [B, T0 + steps, D] (the input followed by the
+    generated frames); an input that is None gives None.  All steps of a modality are one launch of ``umlh.rollout_rows``,
+    which writes the generated frames straight into the result.  Puts the model into eval mode and, like the reference,
+    leaves it there."""
+    import umlh
+    model.eval()
+    preds = []
+    for seq, proj_in, dec in ((x, model.xproj_in, model.decoders[0]), (y, model.yproj_in, model.decoders[1])):
+        if seq is None:
+            preds.append(None)
+            continue
+        if seq.ndim != 3:
+            raise ValueError(f"rollout: expected [B, T0, D] inputs, got {tuple(seq.shape)}")
+        if not seq.is_cuda:
+            raise RuntimeError("rollout runs on the HIP kernels only: move the model and inputs to the GPU")
+        w_in, b_in, conv_w, pos0, lp, eps, w_out, b_out = _rollout_params(model, proj_in, dec)
+        B, T0, D = seq.shape
+        steps = int(steps)
+        with torch.cuda.device(seq.device):
+            full = torch.empty((B, T0 + steps, D), dtype=torch.float32, device=seq.device)
+            full[:, :T0] = seq
+            umlh.rollout_rows(full[:, T0 - 1], w_in, b_in, conv_w, pos0, lp, eps, w_out, b_out, steps, out=full[:, T0 - 1:])
+        preds.append(full)
+    return preds[0], preds[1]
+
+
+def spectral_bias(ground_truth, prediction):
+    """(mag_gt, mag_pred) of train.py:246-251: ``abs(rfft(., dim=1)).mean(dim=(0, 2))`` of the two [B, T, D] blocks, float64
+    device tensors from ``umlh.seq_spectrum``."""
+    import umlh
+
+    def one(t):
+        if not t.is_cuda:
+            return umlh.seq_spectrum(t)                     # moved to the current device
+        with torch.cuda.device(t.device):
+            return umlh.seq_spectrum(t)
+    return one(ground_truth.detach()), one(prediction.detach())
+
+
+def analyze_spectral_bias(ground_truth, prediction, loss_value, iteration, modality_name='modality', postfix=""):
+    """The reference's analyze_spectral_bias (train.py:245-266): the two spectra from the HIP kernel, drawn into the
+    reference's log-log figure ``spectral_analysis{postfix}/spectral_analysis_{modality_name}_{iteration}_loss_{loss:.4f}.png``
+    when matplotlib can be imported (it is not a dependency: without it no file is written).  Always returns
+    (mag_gt, mag_pred)."""
+    import os
+    mag_gt, mag_pred = spectral_bias(ground_truth, prediction)
+    try:
+        import matplotlib.pyplot as plt
+    except ImportError:
+        return mag_gt, mag_pred
+    gt, pred = mag_gt.cpu(), mag_pred.cpu()
+    freqs = torch.arange(gt.shape[0])
+    plt.figure(figsize=(10, 6))
+    plt.plot(freqs, gt, label='Ground Truth (High Freq Source)', alpha=0.8, color='black')
+    plt.plot(freqs, pred, label='Prediction (Transformer Output)', alpha=0.8, color='red', linestyle='--')
+    plt.xscale('log')
+    plt.yscale('log')
+    plt.title(f'Spectral Analysis: {modality_name} (Log-Log Scale)')
+    plt.xlabel('Frequency (Log scale)')
+    plt.ylabel('Magnitude (Log scale)')
+    plt.legend()
+    plt.grid(True, which="both", ls="-", alpha=0.2)
+    os.makedirs(f'spectral_analysis{postfix}', exist_ok=True)
+    plt.savefig(f'spectral_analysis{postfix}/spectral_analysis_{modality_name}_{iteration}_loss_{loss_value:.4f}.png', dpi=300)
+    return mag_gt, mag_pred
+
+
+def _capture_spectra(model, capture):
+    """train.py:474-482 with sample_idx = 0: the first batch of the fixed sample rolled out from its first frames for T - 1
+    steps, and the spectra of the sample and of the rollout, per modality."""
+    x, y = capture.x1[0], capture.x2[0]
+    x_pred, _ = rollout(model, x[:, :1], None, steps=x.shape[1] - 1)
+    _, y_pred = rollout(model, None, y[:, :1], steps=y.shape[1] - 1)
+    x_gt, x_pr = spectral_bias(x, x_pred)
+    y_gt, y_pr = spectral_bias(y, y_pred)
+    return {"x_gt": x_gt, "x_pred": x_pr, "y_gt": y_gt, "y_pred": y_pr}
+
+
 def train(model, train_mode, train_loader_1, train_loader_2, optimizer, modalities=[0, 2], num_epoch=100, step_k=30,
           ds_name="mosi", eval_config={}, alpha_x=1.0, alpha_y=1.0, capture_embeddings_during_training=False, augment=False,
-          debug=False, args=None, device="cuda:0", step_diagnostics=False, on_step=None, effective_rank=False):
+          debug=False, args=None, device="cuda:0", step_diagnostics=False, rollout_spectra=False, on_step=None, effective_rank=False):
     """Returns {'loss_x': [...], 'loss_y': [...], 'loss': [...]} with one entry per batch pair
     (device tensors are read back once at the end).  With a non-empty ``eval_config`` ({'train', 'val', 'test': batch
     lists, 'freq': int}) it evaluates as the reference does (train.py:350,440-451,519-523): ``evaluate_raw_data`` once,
@@ -270,7 +371,16 @@ def train(model, train_mode, train_loader_1, train_loader_2, optimizer, modaliti
     one entry per batch pair, enqueued on the training stream and read back at the end with the losses: 'trivial_loss_x' (with
     'x' in ``train_mode``) and 'trivial_loss_y', 'recon_y_loss' (with 'y' in it) from ``umlh.seq_step_stats`` on the step's own
     inputs and ``y_recon``; 'loss_x_norm', 'loss_y_norm' (``torch.norm`` of a 0-d tensor is |loss|: taken from the losses read back); 'loss_private'; and
-    'diff_next_x' / 'diff_next_y' for the modalities present."""
+    'diff_next_x' / 'diff_next_y' for the modalities present.
+
+    ``rollout_spectra=True`` (needs ``capture_embeddings_during_training=True``) is the reference's block train.py:474-482: after
+    each in-loop capture the first batch of the fixed sample (its ``sample_idx = 0``) is rolled out from its first frames for
+    T - 1 steps per modality (``rollout``) and 'spectra' gets (epoch, i_batch, {'x_gt', 'x_pred', 'y_gt', 'y_pred'}), the
+    float64 spectra of ``spectral_bias`` as host lists.  No figure is drawn.  With the flag off nothing changes."""
+    if rollout_spectra and not capture_embeddings_during_training:
+        raise ValueError("train(rollout_spectra=True) needs capture_embeddings_during_training=True: the reference rolls out "
+                         "the capture's fixed sample (train.py:457-482)")
+    spectra = []
     model.train()
     dev = torch.device(device)
     rec_x, rec_y, rec_l, rec_rank = [], [], [], []
@@ -329,6 +439,8 @@ def train(model, train_mode, train_loader_1, train_loader_2, optimizer, modaliti
                     evals[-1][2].update(values)
                     cap_x.append(zx)
                     cap_y.append(zy)
+                    if rollout_spectra:
+                        spectra.append((epoch, i_batch, _capture_spectra(model, capture)))
                 model.train()
         if eval_config and epoch == num_epoch - 1:
             evals.append((epoch, None, logged(evaluate(model, eval_config, ds_name, device=device))))
@@ -346,4 +458,6 @@ def train(model, train_mode, train_loader_1, train_loader_2, optimizer, modaliti
     if capture is not None:
         res["embeddings"] = {"x1": torch.stack(cap_x) if cap_x else None, "x2": torch.stack(cap_y) if cap_y else None,
                              "x1_label": capture.labels[0], "x2_label": capture.labels[1]}
+    if rollout_spectra:
+        res["spectra"] = [(e, i, {k: v.cpu().tolist() for k, v in sp.items()}) for e, i, sp in spectra]
     return res

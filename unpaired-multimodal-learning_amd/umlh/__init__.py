@@ -22,6 +22,8 @@ from . import capture  # noqa: F401,E402
 from .capture import paired_cosine, seq_compact  # noqa: F401,E402
 from . import stepstats  # noqa: F401,E402
 from .stepstats import seq_step_stats  # noqa: F401,E402
+from . import rollout  # noqa: F401,E402
+from .rollout import rollout_rows, seq_spectrum  # noqa: F401,E402
 
 
 def host_cpu_budget() -> int:

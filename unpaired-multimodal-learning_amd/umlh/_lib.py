@@ -20,7 +20,7 @@ PREC_IDS = {"fp32": 0, "bf16": 1}
 N_CORE_SCALARS = 8
 N_SCALARS = 12
 
-SOURCES = ["umlh_p2p.hip", "umlh_kernels_f32.hip", "umlh_kernels_bf16.hip", "umlh_kernels_micro.hip", "umlh_kernels_seq.hip", "umlh_kernels_enc.hip", "umlh_kernels_align.hip", "umlh_kernels_align_ext.hip", "umlh_kernels_probe.hip", "umlh_kernels_spectral.hip", "umlh_kernels_capture.hip", "umlh_kernels_stepstats.hip", "umlh_api.cpp", "umlh_encoder.cpp"]
+SOURCES = ["umlh_p2p.hip", "umlh_kernels_f32.hip", "umlh_kernels_bf16.hip", "umlh_kernels_micro.hip", "umlh_kernels_seq.hip", "umlh_kernels_enc.hip", "umlh_kernels_align.hip", "umlh_kernels_align_ext.hip", "umlh_kernels_probe.hip", "umlh_kernels_spectral.hip", "umlh_kernels_capture.hip", "umlh_kernels_stepstats.hip", "umlh_kernels_rollout.hip", "umlh_api.cpp", "umlh_encoder.cpp"]
 
 
 class UmlhError(RuntimeError):
@@ -69,6 +69,11 @@ class EncLayer(C.Structure):
 class Hyper(C.Structure):
     _fields_ = [("lr", C.c_double), ("step", C.c_int64), ("alpha", C.c_float), ("img_alpha", C.c_float),
                 ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RolloutCfg(C.Structure):
+    _fields_ = [("Z", C.c_int32), ("d_ff", C.c_int32), ("D", C.c_int32), ("n_layers", C.c_int32), ("steps", C.c_int32),
+                ("eps", C.c_float)]
 
 
 def _prototypes() -> dict:
@@ -192,6 +197,10 @@ def _prototypes() -> dict:
         # per-step logged statistics: trivial next-frame error, masked reconstruction error
         "umlh_seq_step_stats_scratch_bytes": (u64, (i32, i32, i32)),
         "umlh_seq_step_stats": (rc, (vp, i64, i64, vp, i64, i64, i32, i32, i32, vp, vp, vp, u64, vp)),
+        # rollout and spectral-bias spectra
+        "umlh_rollout": (rc, (P(RolloutCfg), pv, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp, i64, i64, vp)),
+        "umlh_seq_spectrum_scratch_bytes": (u64, (i32, i32, i32)),
+        "umlh_seq_spectrum": (rc, (vp, i64, i64, i32, i32, i32, vp, vp, u64, vp)),
     }
 
 
