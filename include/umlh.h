@@ -603,6 +603,43 @@ int  umlh_probe_fit(const float* x, int64_t n, int32_t d, int32_t ldx, const int
 int  umlh_probe_score(const float* x, int64_t n, int32_t d, int32_t ldx, const double* stats, const double* coef,
                       const int32_t* y, int64_t* correct, float* decision, void* stream);
 
+/* ---- k-nearest-neighbour probe: the 'knn' branch of the MultiBench make_classifier (MultiBench/train.py:99-100,
+ * KNeighborsClassifier() = Euclidean metric, uniform weights).  Additive to ABI v11: umlh_version() is
+ * unchanged, callers detect the feature by these symbols.  train is row-major fp32 [n_train, d] with row stride ld_train >= d,
+ * query fp32 [n_query, d] with row stride ld_query >= d.  No n_query x n_train array is formed and no reduction uses a float
+ * atomic.  Every argument check happens before any HIP call; everything runs on `stream`; outputs are device memory.
+ * Envelope: 1 <= k <= 24, k <= n_train < 2^31, 1 <= n_query < 2^31, d >= 1, splits >= 0 (0 = auto); anything else is
+ * UMLH_E_INVALID.
+ *
+ * Order rule: per query row the k train rows with the smallest Euclidean distance, ordered by (squared distance ascending,
+ * train index ascending) -- exact ties go to the smaller index, the rule of umlh_align_knn.
+ * Two stages.  (1) Candidates: the score |t|^2 - 2 q.t ascending (|q|^2 is constant per row) with q.t on the f32 MFMA (a
+ * k-ordered fp32 fma chain) and |t|^2 one fp32 fma chain; the kc = min(k + 8, n_train) best under the strict order (score,
+ * index) are kept by the 32-row strip / 256-column tile / column-chunk scheme of umlh_align_knn.  (2) The candidates' squared
+ * distances are re-evaluated as sum_k (q_k - t_k)^2 in double from the fp32 inputs in a fixed order and re-ranked by (that
+ * value, index); the first k are the answer and dist is the square root of the double value rounded to fp32.  Near-duplicate
+ * points therefore carry no cancellation noise.  The result is bitwise independent of `splits` and reproducible across calls
+ * and streams.
+ * Index-range guarantee: every value written to idx lies in [0, n_train), whatever the data.  List slots that no train row
+ * filled (n_train < k + 8; a query row of NaNs, whose comparisons are all false) are never used as addresses; output positions
+ * they leave open get the position's own index and a NaN distance.  Results for rows that contain NaN / Inf are otherwise
+ * unspecified; other rows are unaffected. */
+
+/* Scratch bytes of the search with these arguments: O(n_query * kc * splits + n_train), no n_query * n_train term.  0 on
+ * invalid arguments. */
+uint64_t umlh_knn_scratch_bytes(int64_t n_train, int64_t n_query, int32_t d, int32_t k, int32_t splits);
+/* idx int32 [n_query, k]; dist fp32 [n_query, k] or NULL; both dense. */
+int  umlh_knn_search(const float* train, int64_t n_train, int32_t ld_train, const float* query, int64_t n_query, int32_t ld_query,
+                     int32_t d, int32_t k, int32_t splits, int32_t* idx, float* dist, void* scratch, uint64_t scratch_bytes,
+                     void* stream);
+/* The uniform vote of KNeighborsClassifier.predict over idx int32 [n_query, k] (1 <= k <= 24): pred[i] = the label value with
+ * the most occurrences among train_labels[idx[i, :]]; a count tie goes to the smallest label value (sklearn's argmax over the
+ * sorted classes_).  train_labels int32 [n_train], any values >= 0: no class table is needed.  An idx value outside
+ * [0, n_train) is not dereferenced and casts no vote.  Outputs, each optional but at least one required: pred int32 [n_query],
+ * votes int32 [n_query] (the winner's count), correct (one int64 = #{pred == y}, integer sums; needs y int32 [n_query]). */
+int  umlh_knn_vote(const int32_t* idx, int64_t n_query, int32_t k, const int32_t* train_labels, int64_t n_train, const int32_t* y,
+                   int32_t* pred, int32_t* votes, int64_t* correct, void* stream);
+
 /* ---- ABI v8: singular values and effective rank of fp32 feature matrices (MultiBench/utilis.py:27-36, the per-step
  * diagnostic of MultiBench/train.py:386-389).  sigma(A) = sqrt(eig(A^T A)): the d x d Gram is accumulated in fp64 from the
  * fp32 rows (their products are exact there), tridiagonalised by Householder reflections and its eigenvalues found by

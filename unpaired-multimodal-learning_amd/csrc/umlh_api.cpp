@@ -2352,3 +2352,51 @@ int umlh_probe_score(const float* x, int64_t n, int32_t d, int32_t ldx, const do
     HIPCHK(umlh_probe_launch_score(x, n, d, ldx, stats, coef, y, (long long*)correct, decision, (hipStream_t)stream), "umlh_probe_score");
     return UMLH_OK;
 }
+
+// ---- k-nearest-neighbour probe (kernels: umlh_kernels_knn.hip); every check precedes the first HIP call ----
+static const int KNN_MAX_K = 24;
+static const int64_t KNN_MAX_ROWS = ((int64_t)1 << 31) - 1;
+
+static bool knn_shape_ok(int64_t n_train, int64_t n_query, int32_t k) {
+    return k >= 1 && k <= KNN_MAX_K && n_train >= k && n_train <= KNN_MAX_ROWS && n_query >= 1 && n_query <= KNN_MAX_ROWS;
+}
+
+uint64_t umlh_knn_scratch_bytes(int64_t n_train, int64_t n_query, int32_t d, int32_t k, int32_t splits) {
+    if (!knn_shape_ok(n_train, n_query, k) || d < 1 || splits < 0) return 0;
+    return umlh_knn_bytes(n_train, n_query, k, splits);
+}
+
+int umlh_knn_search(const float* train, int64_t n_train, int32_t ld_train, const float* query, int64_t n_query, int32_t ld_query,
+                    int32_t d, int32_t k, int32_t splits, int32_t* idx, float* dist, void* scratch, uint64_t scratch_bytes,
+                    void* stream) {
+    if (!train || !query || !idx || !scratch)
+        return fail(UMLH_E_INVALID, "umlh_knn_search: null pointer (train, query, idx and scratch are required)");
+    if (k < 1 || k > KNN_MAX_K) return fail(UMLH_E_INVALID, "umlh_knn_search: k=%d outside 1..%d", k, KNN_MAX_K);
+    if (!knn_shape_ok(n_train, n_query, k))
+        return fail(UMLH_E_INVALID, "umlh_knn_search: n_train=%lld n_query=%lld for k=%d (need k <= n_train < 2^31, 1 <= n_query < 2^31)",
+                    (long long)n_train, (long long)n_query, k);
+    if (d < 1 || ld_train < d || ld_query < d)
+        return fail(UMLH_E_INVALID, "umlh_knn_search: d=%d ld_train=%d ld_query=%d (need 1 <= d <= ld)", d, ld_train, ld_query);
+    if (splits < 0) return fail(UMLH_E_INVALID, "umlh_knn_search: splits=%d < 0", splits);
+    const uint64_t need = umlh_knn_bytes(n_train, n_query, k, splits);
+    if (scratch_bytes < need)
+        return fail(UMLH_E_INVALID, "umlh_knn_search: scratch of %llu bytes, %llu needed", (unsigned long long)scratch_bytes,
+                    (unsigned long long)need);
+    if ((reinterpret_cast<uintptr_t>(scratch) & 3) != 0) return fail(UMLH_E_INVALID, "umlh_knn_search: scratch must be 4-byte aligned");
+    HIPCHK(umlh_knn_launch_search(train, n_train, ld_train, query, n_query, ld_query, d, k, splits, idx, dist, scratch,
+                                  (hipStream_t)stream), "umlh_knn_search");
+    return UMLH_OK;
+}
+
+int umlh_knn_vote(const int32_t* idx, int64_t n_query, int32_t k, const int32_t* train_labels, int64_t n_train, const int32_t* y,
+                  int32_t* pred, int32_t* votes, int64_t* correct, void* stream) {
+    if (!idx || !train_labels) return fail(UMLH_E_INVALID, "umlh_knn_vote: null pointer (idx and train_labels are required)");
+    if (!pred && !votes && !correct) return fail(UMLH_E_INVALID, "umlh_knn_vote: nothing to compute (pred, votes and correct are all NULL)");
+    if (correct && !y) return fail(UMLH_E_INVALID, "umlh_knn_vote: correct needs the labels y");
+    if (k < 1 || k > KNN_MAX_K) return fail(UMLH_E_INVALID, "umlh_knn_vote: k=%d outside 1..%d", k, KNN_MAX_K);
+    if (n_train < 1 || n_train > KNN_MAX_ROWS || n_query < 1 || n_query > KNN_MAX_ROWS)
+        return fail(UMLH_E_INVALID, "umlh_knn_vote: n_train=%lld n_query=%lld (need 1 <= n < 2^31)", (long long)n_train, (long long)n_query);
+    HIPCHK(umlh_knn_launch_vote(idx, n_query, k, train_labels, n_train, y, pred, votes, (long long*)correct, (hipStream_t)stream),
+           "umlh_knn_vote");
+    return UMLH_OK;
+}

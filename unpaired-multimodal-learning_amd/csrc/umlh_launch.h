@@ -133,6 +133,12 @@ int umlh_probe_launch_fit(const float* x, long long n, int d, int ldx, const int
                           hipStream_t st);
 int umlh_probe_launch_score(const float* x, long long n, int d, int ldx, const double* stats, const double* coef, const int* y,
                             long long* correct, float* decision, hipStream_t st);
+// ---- umlh_kernels_knn.hip: k-nearest-neighbour probe ----
+unsigned long long umlh_knn_bytes(long long nt, long long nq, int k, int splits);
+int umlh_knn_launch_search(const float* train, long long nt, int ldt, const float* query, long long nq, int ldq, int d, int k,
+                           int splits, int* idx, float* dist, void* scratch, hipStream_t st);
+int umlh_knn_launch_vote(const int* idx, long long nq, int k, const int* labels, long long nt, const int* y, int* pred, int* votes,
+                         long long* correct, hipStream_t st);
 // ---- umlh_kernels_spectral.hip: fp64 Gram, symmetric eigenvalues, singular values and effective rank ----
 int umlh_spectral_chunks(int batch, long long n);
 unsigned long long umlh_spectral_bytes(int batch, long long n, int d);

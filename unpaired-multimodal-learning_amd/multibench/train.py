@@ -76,9 +76,15 @@ class _Probes:
         self.kind, self.dev = _kind(ds_name), dev
         self.counts, self.names, self.rows, self.clfs = [], [], [], []
 
-    def fit(self, X, y):
-        from umlh.probe import LogisticProbe
-        self.clfs.append(LogisticProbe(self.kind).fit(X, y, check_classes=False))
+    def fit(self, X, y, classifier_type="logistic"):
+        """make_classifier(classifier_type, ds_name) of the reference (train.py:96-102), fitted."""
+        from umlh.probe import KNeighborsProbe, LogisticProbe
+        if classifier_type == "logistic":
+            self.clfs.append(LogisticProbe(self.kind).fit(X, y, check_classes=False))
+        elif classifier_type == "knn":
+            self.clfs.append(KNeighborsProbe().fit(X, y))
+        else:
+            raise ValueError(f"Unsupported classifier type: {classifier_type}")
         return self.clfs[-1]
 
     def score(self, name, clf, X, y):
@@ -91,13 +97,13 @@ class _Probes:
         return {k: c / n for k, c, n in zip(self.names, got, self.rows)}
 
 
-def _fit_three(pr, emb, lab, z, tag=""):
+def _fit_three(pr, emb, lab, z, tag="", classifier_type="logistic"):
     """The x, y and xy probes (train.py:163-183): fitted on train, scored on val and test.  emb[t] is [N_t, zx + zy] with
     the x block in the first zx columns: the three feature sets are views of it (the row stride travels to the kernels)."""
     ytr = torch.from_numpy(lab["train"]).to(pr.dev)
     yev = {t: torch.from_numpy(lab[t]).to(pr.dev) for t in ("val", "test")}
     for name, cols in (("x", slice(0, z[0])), ("y", slice(z[0], z[0] + z[1])), ("xy", slice(0, z[0] + z[1]))):
-        clf = pr.fit(emb["train"][:, cols], ytr)
+        clf = pr.fit(emb["train"][:, cols], ytr, classifier_type)
         for t in ("val", "test"):
             pr.score(f"{t}/score_{name}{tag}", clf, emb[t][:, cols], yev[t])
 
@@ -131,16 +137,24 @@ def evaluate_raw_data(config, ds_name="mosi", device=None, return_probes=False):
 
 
 @torch.no_grad()
-def evaluate(model, config, ds_name="mosi", device="cuda:0", return_embeddings=False):
+def evaluate(model, config, ds_name="mosi", device="cuda:0", return_embeddings=False, classifier_types=("logistic",)):
     """The reference's evaluate (train.py:93-240) with its batch layout and result keys.  The model forward is this
     project's eval-mode mirror; pooling, scaler statistics, fits and scores are HIP kernels, the embeddings never leave
     the device, and all six fits (three modality-separation probes, x, y, xy) are enqueued before anything is read back.
     The reference shuffles the rows of the modality-separation probe with np.random.permutation; the optimum of a fit does
     not depend on row order, so no shuffle is done here.  ``separate`` is False in the reference: the *_private and
     *_complete keys are NaN there and here.  ``return_embeddings`` adds the pooled [N, zx + zy] device matrices per split
-    and the fitted probes (separation x 3, x, y, xy)."""
+    and the fitted probes (separation x 3, then x, y, xy per classifier type).
+    ``classifier_types`` is the list the reference's loop iterates (train.py:165): 'logistic' or 'knn'
+    (``umlh.KNeighborsProbe()``, train.py:99-100); a later type overwrites the score keys of an earlier one, as
+    ``results.update`` inside that loop does, and any other name raises the reference's ValueError.  The modality-separation
+    probe is always logistic (train.py:151)."""
     import umlh
     _label_fn(ds_name)
+    classifier_types = tuple(classifier_types)
+    for ct in classifier_types:
+        if ct not in ("logistic", "knn"):
+            raise ValueError(f"Unsupported classifier type: {ct}")
     dev = torch.device(device)
     model.eval()
     lab = {t: _labels01(config[t], ds_name) for t in _TYPES}
@@ -172,7 +186,8 @@ def evaluate(model, config, ds_name="mosi", device="cuda:0", return_embeddings=F
             both = torch.cat([emb[t][:, :z[0]], emb[t][:, z[0]:]], dim=0)
             which = torch.cat([torch.zeros(n, dtype=torch.int32, device=dev), torch.ones(n, dtype=torch.int32, device=dev)])
             pr.score(f"sep/{t}", pr.fit(both, which), both, which)
-        _fit_three(pr, emb, lab, z)
+        for ct in classifier_types:
+            _fit_three(pr, emb, lab, z, classifier_type=ct)
         got = pr.read()
         losses = torch.stack([loss["val"][0], loss["test"][0], loss["val"][1], loss["test"][1]]).cpu().tolist()
     results = {"val/modality_separate": float(np.mean([got[f"sep/{t}"] for t in _TYPES]))}
@@ -347,7 +362,7 @@ def train(model, train_mode, train_loader_1, train_loader_2, optimizer, modaliti
           debug=False, args=None, device="cuda:0", step_diagnostics=False, rollout_spectra=False, on_step=None, effective_rank=False):
     """Returns {'loss_x': [...], 'loss_y': [...], 'loss': [...]} with one entry per batch pair
     (device tensors are read back once at the end).  With a non-empty ``eval_config`` ({'train', 'val', 'test': batch
-    lists, 'freq': int}) it evaluates as the reference does (train.py:350,440-451,519-523): ``evaluate_raw_data`` once,
+    lists, 'freq': int, optionally 'classifier_types': the probes of ``evaluate``, default ('logistic',)}) it evaluates as the reference does (train.py:350,440-451,519-523): ``evaluate_raw_data`` once,
     ``evaluate`` whenever i_batch % freq == 0 and once more after the last epoch, the model back in train mode after
     each; the dict then also holds 'raw' and 'eval' = [(epoch, i_batch, results), ...], where results are what the
     reference logs (evaluate's keys without the *_private / *_complete ones, plus the raw baselines) and the closing
@@ -398,6 +413,7 @@ def train(model, train_mode, train_loader_1, train_loader_2, optimizer, modaliti
     else:
         gt_rank = _fixed_sample_rank(train_loader_2, modalities[1], ds_name, dev) if want_rank else None
     raw_results, evals = None, []
+    classifier_types = tuple(eval_config.get("classifier_types", ("logistic",)))
     if eval_config:
         raw_results = evaluate_raw_data(eval_config, ds_name=ds_name, device=device)
 
@@ -433,7 +449,7 @@ def train(model, train_mode, train_loader_1, train_loader_2, optimizer, modaliti
             if on_step is not None:
                 on_step(epoch, i_batch, out, loss)
             if eval_config and i_batch % eval_config["freq"] == 0:
-                evals.append((epoch, i_batch, logged(evaluate(model, eval_config, ds_name, device=device))))
+                evals.append((epoch, i_batch, logged(evaluate(model, eval_config, ds_name, device=device, classifier_types=classifier_types))))
                 if capture is not None:
                     values, zx, zy = capture.measure(model)
                     evals[-1][2].update(values)
@@ -443,7 +459,7 @@ def train(model, train_mode, train_loader_1, train_loader_2, optimizer, modaliti
                         spectra.append((epoch, i_batch, _capture_spectra(model, capture)))
                 model.train()
         if eval_config and epoch == num_epoch - 1:
-            evals.append((epoch, None, logged(evaluate(model, eval_config, ds_name, device=device))))
+            evals.append((epoch, None, logged(evaluate(model, eval_config, ds_name, device=device, classifier_types=classifier_types))))
             model.train()
     stack = lambda v: torch.stack([t.reshape(()) for t in v]).cpu().tolist() if v else []
     res = {"loss_x": stack(rec_x), "loss_y": stack(rec_y), "loss": stack(rec_l)}

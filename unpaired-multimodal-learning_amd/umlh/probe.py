@@ -4,7 +4,8 @@
 ``lengths=None``, the plain ``mean(axis=1)`` of ``evaluate_raw_data``.  ``LogisticProbe`` is the binary
 ``LogisticRegression`` that ``evaluate`` fits (train.py:97-99): ``kind='lbfgs'`` for ``LogisticRegression(max_iter=200)``,
 ``kind='liblinear'`` for ``make_pipeline(StandardScaler(), LogisticRegression(max_iter=1000, solver='liblinear'))``.  It
-returns the optimum of sklearn's objective, not sklearn's last iterate.  Every call enqueues on
+returns the optimum of sklearn's objective, not sklearn's last iterate.  ``KNeighborsProbe`` is the ``KNeighborsClassifier()``
+of the same factory (train.py:99-100) on the kernels of umlh_kernels_knn.hip (``umlh_knn_*``).  Every call enqueues on
 ``torch.cuda.current_stream`` and returns without synchronising; only the ``n_iter_`` / ``converged_`` / ``score``
 accessors read device memory back.  Inputs follow ``umlh.align``: fp32 CUDA tensors with unit column stride are used in
 place (the row stride is passed on), other float dtypes are upcast, CPU tensors copied.  There is no CPU compute path.
@@ -22,6 +23,9 @@ MAX_FEATURES = 1024
 
 def _device() -> torch.device:
     return glue.device("umlh.align", "the metrics run only as HIP kernels")
+
+
+MAX_NEIGHBORS = 24
 
 
 def masked_mean(z: torch.Tensor, lengths: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
@@ -194,4 +198,74 @@ class LogisticProbe:
     def score(self, X: torch.Tensor, y) -> float:
         """Mean accuracy = correct / N as a Python float."""
         _, correct, n = self._score(X, y, False, True)
+        return int(correct.item()) / n
+
+
+class KNeighborsProbe:
+    """``KNeighborsClassifier(n_neighbors=k)`` with sklearn's defaults (Euclidean metric, uniform weights) on
+    ``umlh_knn_search`` / ``umlh_knn_vote``.  Neighbours are ordered by (squared distance, train index): exact ties go to the
+    smaller index.  A vote tie goes to the smallest label value.  Labels are integers >= 0 of any values (multi-class).
+    ``splits`` (0 = auto) is the number of column chunks of the candidate pass; no result depends on it.
+
+    ``fit`` keeps the fp32 device matrix (in place when it has unit column stride; the row stride travels) and int32 labels and
+    makes no host synchronisation; nothing else does either, except ``score``."""
+
+    def __init__(self, n_neighbors: int = 5, splits: int = 0):
+        if not 1 <= int(n_neighbors) <= MAX_NEIGHBORS:
+            raise ValueError(f"KNeighborsProbe: n_neighbors={n_neighbors} outside 1..{MAX_NEIGHBORS}")
+        if int(splits) < 0:
+            raise ValueError(f"KNeighborsProbe: splits={splits} must be >= 0")
+        self.n_neighbors, self.splits = int(n_neighbors), int(splits)
+        self._x = self._y = None
+
+    def fit(self, X: torch.Tensor, y) -> "KNeighborsProbe":
+        dev = _device()
+        x = glue.features(X, "KNeighborsProbe.fit", dev)
+        if x.shape[0] < self.n_neighbors:
+            raise ValueError(f"Expected n_neighbors <= n_samples_fit, but n_neighbors = {self.n_neighbors}, n_samples_fit = {x.shape[0]}")
+        self._x, self._y = x, _labels(y, x.shape[0], dev, "KNeighborsProbe.fit")
+        return self
+
+    def _search(self, X, want_dist):
+        if self._x is None:
+            raise UmlhError("KNeighborsProbe: fit() has not been called")
+        dev = _device()
+        x = glue.features(X, "KNeighborsProbe", dev)
+        (nt, d), nq, k = self._x.shape, x.shape[0], self.n_neighbors
+        if x.shape[1] != d:
+            raise ValueError(f"KNeighborsProbe: {x.shape[1]} features, fitted on {d}")
+        scratch, nbytes = glue.scratch("umlh_knn_scratch_bytes", dev, n_train=nt, n_query=nq, d=d, k=k, splits=self.splits)
+        idx = torch.empty((nq, k), dtype=torch.int32, device=dev)
+        dist = torch.empty((nq, k), dtype=torch.float32, device=dev) if want_dist else None
+        check(load_library().umlh_knn_search(self._x.data_ptr(), nt, self._x.stride(0), x.data_ptr(), nq, x.stride(0), d, k, self.splits,
+                                             idx.data_ptr(), glue.ptr(dist), scratch.data_ptr(), nbytes, glue.stream(dev)),
+              "umlh_knn_search")
+        return idx, dist, dev
+
+    def _vote(self, X, y, want_pred, want_correct):
+        idx, _, dev = self._search(X, False)
+        nq = idx.shape[0]
+        yy = _labels(y, nq, dev, "KNeighborsProbe.score") if want_correct else None
+        pred = torch.empty(nq, dtype=torch.int32, device=dev) if want_pred else None
+        correct = torch.empty((), dtype=torch.int64, device=dev) if want_correct else None
+        check(load_library().umlh_knn_vote(idx.data_ptr(), nq, self.n_neighbors, self._y.data_ptr(), self._y.numel(), glue.ptr(yy),
+                                           glue.ptr(pred), None, glue.ptr(correct), glue.stream(dev)), "umlh_knn_vote")
+        return pred, correct, nq
+
+    def kneighbors(self, X: torch.Tensor, return_distance: bool = True):
+        """(dist fp32 [N, k], idx int64 [N, k]) device tensors, or idx alone with ``return_distance=False``."""
+        idx, dist, _ = self._search(X, return_distance)
+        return (dist, idx.to(torch.int64)) if return_distance else idx.to(torch.int64)
+
+    def predict(self, X: torch.Tensor) -> torch.Tensor:
+        """int64 device tensor [N]: the most frequent label among the k neighbours, ties to the smallest label value."""
+        return self._vote(X, None, True, False)[0].to(torch.int64)
+
+    def correct(self, X: torch.Tensor, y) -> torch.Tensor:
+        """The number of correct predictions as a 0-d int64 device tensor (no host synchronisation)."""
+        return self._vote(X, y, False, True)[1]
+
+    def score(self, X: torch.Tensor, y) -> float:
+        """Mean accuracy = correct / N as a Python float."""
+        _, correct, n = self._vote(X, y, False, True)
         return int(correct.item()) / n
