@@ -797,6 +797,42 @@ uint64_t umlh_seq_spectrum_scratch_bytes(int32_t b, int32_t t_len, int32_t d);  
 int  umlh_seq_spectrum(const float* x, int64_t ldb, int64_t ldt, int32_t b, int32_t t_len, int32_t d, double* out, void* scratch,
                        uint64_t scratch_bytes, void* stream);
 
+/* ---- class index and class statistics of the fine-tune loop's feature capture (vision_language/finetune.py:222-231; DESIGN
+ * section 18).  Additive to ABI v11: umlh_version() is unchanged, callers detect the feature by these symbols.  Every argument
+ * check happens before any HIP call and names the function and the argument; everything runs on `stream`; outputs are device
+ * memory; no float atomics: results are bitwise reproducible across calls, streams and CU counts. */
+
+/* A stable counting sort of the rows by label.  order (int32, room for n entries) lists the rows whose label lies in
+ * [0, n_class), grouped by class in ascending class order and in ascending row order inside a class; offsets (int64,
+ * n_class + 1 entries): class c is order[offsets[c] .. offsets[c + 1]), offsets[n_class] the number of listed rows.  A row with
+ * any other label appears nowhere (the reference's `== label` never selects it); entries of order past offsets[n_class] are
+ * not written.  Five enqueues (one memset, four launches over blocks of 256 rows), no host sync; meant to run once per run.
+ * Envelope: 1 <= n < 2^31, n_class >= 1, ceil(n / 256) * n_class <= 2^28 (the block-by-class count table in scratch). */
+uint64_t umlh_class_index_scratch_bytes(int64_t n, int32_t n_class);          /* 0 on invalid arguments */
+int  umlh_class_index(const int64_t* labels, int64_t n, int32_t n_class, int32_t* order, int64_t* offsets,
+                      void* scratch, uint64_t scratch_bytes, void* stream);
+
+/* Per class c, with R_c the rows order[offsets[c] .. offsets[c + 1]) of feats (row i at feats[i*ld .. i*ld + d)):
+ *   means[c*ld_means + j] = (float)(sum_{i in R_c} x_ij / |R_c|), the sum in fp64 over R_c in order's sequence (cut into chunks
+ *                           of 256 rows, 4 interleaved partial sums per chunk, added in a fixed order), rounded once to fp32;
+ *   dist[c]               = (1 / |R_c|) sum_{i in R_c} sqrt(sum_j (x_ij - means[c, j])^2) in fp64 against the fp32 mean that was
+ *                           written: the differences are formed explicitly (two fp32 values subtract exactly in fp64), squared,
+ *                           summed in fp64 and passed through an fp64 sqrt -- never |x|^2 - 2 x.m + |m|^2;
+ *   out2                  = {sum_c dist[c] / n_class, number of empty classes}.
+ * An empty class gives a NaN mean row and a NaN dist[c] (the mean of an empty slice), so out2[0] is NaN if any class is empty,
+ * as np.mean of the reference's list is.  A non-finite value in a row reaches that row's class only.
+ * The plan is not trusted: offsets is read through its running maximum clamped to [0, n] (disjoint ranges whatever it holds;
+ * unchanged when it is a valid plan), and an entry of order outside [0, n) is skipped and does not count towards |R_c|.  order
+ * must have room for n entries.  Nothing is written outside means[c, 0 .. d), dist[0 .. n_class) and out2[0 .. 2).
+ * A class of any size works: one of at most 256 rows is read twice, back to back, by one workgroup; a longer one is spread
+ * over one workgroup per 256 rows.  Both load paths (16-byte loads when d, ld, ld_means and both base addresses are multiples
+ * of 16 bytes, 4-byte loads otherwise) add in the same order.  At most five launches, no host sync.
+ * Envelope: 1 <= n < 2^31, d >= 1, n_class >= 1, ld >= d, ld_means >= d, means must not overlap feats. */
+uint64_t umlh_class_stats_scratch_bytes(int64_t n, int32_t d, int32_t n_class);   /* 0 on invalid arguments */
+int  umlh_class_stats(const float* feats, int64_t ld, int64_t n, int32_t d, const int32_t* order, const int64_t* offsets,
+                      int32_t n_class, float* means, int64_t ld_means, double* dist, double* out2,
+                      void* scratch, uint64_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -989,6 +989,63 @@ int umlh_paired_cosine(const float* a, int64_t lda, const float* b, int64_t ldb,
     return UMLH_OK;
 }
 
+// ---- class index and class statistics (kernels: umlh_kernels_classstats.hip); every check precedes the first HIP call ----
+static bool class_index_shape_ok(int64_t n, int32_t n_class) { return n >= 1 && n <= INT_MAX && n_class >= 1; }
+
+uint64_t umlh_class_index_scratch_bytes(int64_t n, int32_t n_class) {
+    return class_index_shape_ok(n, n_class) ? umlh_classindex_bytes(n, n_class) : 0;
+}
+
+int umlh_class_index(const int64_t* labels, int64_t n, int32_t n_class, int32_t* order, int64_t* offsets, void* scratch,
+                     uint64_t scratch_bytes, void* stream) {
+    const char* who = "umlh_class_index";
+    if (!labels) return fail(UMLH_E_INVALID, "%s: labels is NULL", who);
+    if (!order) return fail(UMLH_E_INVALID, "%s: order is NULL", who);
+    if (!offsets) return fail(UMLH_E_INVALID, "%s: offsets is NULL", who);
+    if (!scratch) return fail(UMLH_E_INVALID, "%s: scratch is NULL", who);
+    if (n < 1 || n > INT_MAX) return fail(UMLH_E_INVALID, "%s: n=%lld rows (need 1 <= n < 2^31)", who, (long long)n);
+    if (n_class < 1) return fail(UMLH_E_INVALID, "%s: n_class=%d < 1", who, n_class);
+    const uint64_t need = umlh_classindex_bytes(n, n_class);
+    if (need == 0)
+        return fail(UMLH_E_INVALID, "%s: n=%lld with n_class=%d needs more than 2^28 block counts (ceil(n / 256) * n_class)", who,
+                    (long long)n, n_class);
+    if (scratch_bytes < need)
+        return fail(UMLH_E_INVALID, "%s: scratch of %llu bytes, %llu needed", who, (unsigned long long)scratch_bytes, (unsigned long long)need);
+    HIPCHK(umlh_classindex_launch(reinterpret_cast<const long long*>(labels), n, n_class, order, reinterpret_cast<long long*>(offsets),
+                                  scratch, (hipStream_t)stream), who);
+    return UMLH_OK;
+}
+
+uint64_t umlh_class_stats_scratch_bytes(int64_t n, int32_t d, int32_t n_class) {
+    return class_index_shape_ok(n, n_class) && d >= 1 ? umlh_classstats_bytes(n, d, n_class) : 0;
+}
+
+int umlh_class_stats(const float* feats, int64_t ld, int64_t n, int32_t d, const int32_t* order, const int64_t* offsets, int32_t n_class,
+                     float* means, int64_t ld_means, double* dist, double* out2, void* scratch, uint64_t scratch_bytes, void* stream) {
+    const char* who = "umlh_class_stats";
+    if (!feats) return fail(UMLH_E_INVALID, "%s: feats is NULL", who);
+    if (!order) return fail(UMLH_E_INVALID, "%s: order is NULL", who);
+    if (!offsets) return fail(UMLH_E_INVALID, "%s: offsets is NULL", who);
+    if (!means) return fail(UMLH_E_INVALID, "%s: means is NULL", who);
+    if (!dist) return fail(UMLH_E_INVALID, "%s: dist is NULL", who);
+    if (!out2) return fail(UMLH_E_INVALID, "%s: out2 is NULL", who);
+    if (!scratch) return fail(UMLH_E_INVALID, "%s: scratch is NULL", who);
+    if (n < 1 || n > INT_MAX) return fail(UMLH_E_INVALID, "%s: n=%lld rows (need 1 <= n < 2^31)", who, (long long)n);
+    if (d < 1) return fail(UMLH_E_INVALID, "%s: d=%d < 1", who, d);
+    if (n_class < 1) return fail(UMLH_E_INVALID, "%s: n_class=%d < 1", who, n_class);
+    if (ld < d) return fail(UMLH_E_INVALID, "%s: ld=%lld < d=%d", who, (long long)ld, d);
+    if (ld_means < d) return fail(UMLH_E_INVALID, "%s: ld_means=%lld < d=%d", who, (long long)ld_means, d);
+    const uintptr_t f0 = reinterpret_cast<uintptr_t>(feats), f1 = f0 + ((uint64_t)(n - 1) * (uint64_t)ld + (uint64_t)d) * sizeof(float);
+    const uintptr_t m0 = reinterpret_cast<uintptr_t>(means), m1 = m0 + ((uint64_t)(n_class - 1) * (uint64_t)ld_means + (uint64_t)d) * sizeof(float);
+    if (m0 < f1 && f0 < m1) return fail(UMLH_E_INVALID, "%s: means overlaps feats", who);
+    const uint64_t need = umlh_classstats_bytes(n, d, n_class);
+    if (scratch_bytes < need)
+        return fail(UMLH_E_INVALID, "%s: scratch of %llu bytes, %llu needed", who, (unsigned long long)scratch_bytes, (unsigned long long)need);
+    HIPCHK(umlh_classstats_launch(feats, ld, n, d, order, reinterpret_cast<const long long*>(offsets), n_class, means, ld_means, dist, out2,
+                                  scratch, (hipStream_t)stream), who);
+    return UMLH_OK;
+}
+
 // ---- per-step logged statistics (kernels: umlh_kernels_stepstats.hip); every check precedes the first HIP call ----
 static bool step_stats_shape_ok(int32_t b, int32_t t_len, int32_t d) {
     return b >= 1 && b <= CAPTURE_MAX_B && t_len >= 1 && d >= 1 && umlh_stepstats_partials(b, t_len, d) >= 0;

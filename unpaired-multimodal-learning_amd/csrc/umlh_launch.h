@@ -157,6 +157,13 @@ int umlh_capture_launch_compact(const float* z, int B, int T, int d, long long l
                                 int drop_last, float* out, long long ldo, long long out_rows, long long* rows_total, hipStream_t st);
 int umlh_capture_launch_cosine(const float* a, long long lda, const float* b, long long ldb, long long n, int d, double eps,
                                double* out2, float* rows, void* scratch, hipStream_t st);
+// ---- umlh_kernels_classstats.hip: stable counting sort of rows by label, per-class mean rows and in-class distances ----
+unsigned long long umlh_classindex_bytes(long long n, int n_class);      // 0: the block-by-class count table would pass 1 GiB
+int umlh_classindex_launch(const long long* labels, long long n, int n_class, int* order, long long* offsets, void* scratch,
+                           hipStream_t st);
+unsigned long long umlh_classstats_bytes(long long n, int d, int n_class);
+int umlh_classstats_launch(const float* feats, long long ld, long long n, int d, const int* order, const long long* offsets,
+                           int n_class, float* means, long long ld_means, double* dist, double* out2, void* scratch, hipStream_t st);
 // ---- umlh_kernels_stepstats.hip: per-step logged statistics (trivial next-frame error, masked reconstruction error) ----
 long long umlh_stepstats_partials(int B, int T, int d);       // partial sums of one call; -1: more than the final kernel takes
 unsigned long long umlh_stepstats_bytes(int B, int T, int d);

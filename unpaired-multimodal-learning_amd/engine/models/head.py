@@ -339,15 +339,19 @@ class UML(_HeadBase):
         else:
             self.img_scale, self.txt_scale = self._scales[0], self._scales[1]
 
-    def extract_features(self, images):
+    def extract_features(self, images, out=None):
+        """``out`` (an extension): a contiguous fp32 [rows, shared_dim] device tensor the features are written into -- by the
+        projection kernel itself where there is one -- and which is returned."""
         feats = self.vision_model(images)
         if self.img_proj is None:
-            return feats
+            return feats if out is None else out.copy_(feats)
         import umlh
         feats = feats.to(torch.float32).contiguous()
         dummy = torch.zeros(feats.shape[0], dtype=torch.int64, device=feats.device)
-        h = self._infer_engine(feats.shape[0]).project(umlh.RowBatch(feats, dummy))
-        return h[:, :self.shared_dim].contiguous() if self._bias else h      # (the packed projection appends [1 | 0...])
+        if self._bias:                                                        # (the packed projection appends [1 | 0...])
+            h = self._infer_engine(feats.shape[0]).project(umlh.RowBatch(feats, dummy))[:, :self.shared_dim]
+            return h.contiguous() if out is None else out.copy_(h)
+        return self._infer_engine(feats.shape[0]).project(umlh.RowBatch(feats, dummy), out=out)
 
 
 class UMLClip(_HeadBase):
@@ -362,6 +366,7 @@ class UMLClip(_HeadBase):
         self.logit_scale = torch.tensor(float(logit_scale_init))      # fixed scale (head.py:125)
         self._pack_head()
 
-    def extract_features(self, images):
-        """Missing in the reference class although train() calls it; identity here."""
-        return self.vision_model(images)
+    def extract_features(self, images, out=None):
+        """Missing in the reference class although train() calls it; identity here.  ``out``: as in UML."""
+        feats = self.vision_model(images)
+        return feats if out is None else out.copy_(feats)

@@ -11,12 +11,19 @@ no host synchronisation inside a step).
 What the reference does per step only for logging (two extra backward passes for
 per-modality gradient statistics :190-191,200-206, a second backbone forward :183)
 is not on this path.
+
+``capture_features_during_training=True`` (:127-155, 208-233, 280-287) runs ``feature_capture.FeatureCapture`` after
+every step, on the per-step path.  One deviation: the reference draws its image sample as a seed-1 16-shot split of the raw
+dataset through an image loader (``get_few_shot_image_samples``); raw images are outside this build, so
+``take_capture_samples`` takes the first 16 rows of each class of the image table instead, or the caller passes
+``capture_samples``.
 """
 from __future__ import annotations
 
 import os
 import sys
 import threading
+from types import SimpleNamespace
 from typing import Optional
 
 import torch
@@ -27,6 +34,7 @@ from engine.models.head import UML, UMLClip  # noqa: F401
 from engine.optimizer.default import HYPER_DICT  # noqa: F401
 from engine.optimizer.optim import build_optimizer  # noqa: F401
 from engine.optimizer.scheduler import build_lr_scheduler  # noqa: F401
+from feature_capture import FeatureCapture
 from metrics import AlignmentMetrics, cka, mknn  # noqa: F401  finetune.py:111-118 (CKA and mKNN metrics)
 
 EVAL_FREQ = 100   # evaluate on the val set every 100 iterations (early stopping)
@@ -41,6 +49,36 @@ def fetch_next(loader, loader_iter):
         loader_iter = iter(loader)
         batch = next(loader_iter)
     return batch, loader_iter
+
+
+def get_n_text_features(text_loader, n):
+    """The first ``n`` rows the text loader delivers, with their labels (finetune.py:96-108).  It iterates the loader, so it
+    consumes the loader's RNG draws exactly as the reference does; ``train`` calls it before the training iterators are made."""
+    text_samples, text_labels = [], []
+    for i, batch in enumerate(text_loader):
+        if (i + 1) * text_loader.batch_size >= n:
+            text_samples.append(batch[0][:n - i * text_loader.batch_size])
+            text_labels.append(batch[1][:n - i * text_loader.batch_size])
+            break
+        text_features, labels, _ = batch
+        text_samples.append(text_features)
+        text_labels.append(labels)
+    return torch.cat(text_samples, dim=0), torch.cat(text_labels, dim=0)
+
+
+def take_capture_samples(image_loader, shot=16):
+    """(rows, labels) of the first ``shot`` rows of each class of the image loader's table, in table order: this build's
+    stand-in for the reference's ``get_few_shot_image_samples(args, shot=16)`` (finetune.py:79-94, a seed-1 few-shot split
+    of the raw dataset, which is outside this path).  One host read of the labels; runs once per run."""
+    table = getattr(image_loader, "table", None)
+    if table is None:
+        raise umlh.UmlhError("take_capture_samples needs a FeatureLoader (a device-resident table); pass capture_samples to train()")
+    y = table.labels.cpu()
+    by_class = torch.argsort(y, stable=True)
+    ys = y[by_class]
+    first = torch.searchsorted(ys, ys, right=False)                  # position of each class's first row in the sorted order
+    keep = by_class[torch.arange(ys.numel()) - first < shot].sort().values.to(table.device)
+    return table.features[keep], table.labels[keep]
 
 
 class _RowSource:
@@ -302,16 +340,29 @@ class _Run:
 
 def train(model, image_loader, text_loader, val_loader, test_loader, optimizer, scheduler, device="cuda",
           max_iters=1000, alpha=1.0, eval_freq=EVAL_FREQ, patience=5, capture_features_during_training=False,
-          features_pth="./", args=None, logger=None, precision="fp32", diagnostics=None):
+          features_pth="./", args=None, logger=None, precision="fp32", diagnostics=None, capture_samples=None,
+          capture_options=None):
+    """``capture_samples``: the (rows, labels) of the image sample of the feature capture (default:
+    ``take_capture_samples(image_loader, 16)``); ``capture_options``: keyword arguments of ``FeatureCapture``
+    (``keep_features``, ``strict``).  Both are read only with ``capture_features_during_training``."""
+    capture = None
+    if capture_features_during_training:
+        # finetune.py:127-155: the samples are drawn BEFORE the training iterators exist (the text sample iterates the text
+        # loader once, which consumes its RNG draws); the raw features are saved right away
+        print(f"=> Ready to save captured features during training at {features_pth}")
+        n_class = args.nclasses if args is not None else model.head.weight.shape[0]
+        rows, labels = capture_samples if capture_samples is not None else take_capture_samples(image_loader, shot=16)
+        text_rows, text_labels = get_n_text_features(text_loader, n=1000) if text_loader is not None else (None, None)
+        capture = FeatureCapture(model, rows, labels, text_rows, n_class, text_labels=text_labels, **(capture_options or {}))
+        capture.save_raw(features_pth)
     # per-step gradient diagnostics (finetune.py:190-191,203-206): the reference computes them on every
     # step; here they cost ~2.5 us per step, so they are on when a logger asks for them (or on request)
     want_diag = bool(diagnostics) if diagnostics is not None else logger is not None
     run = _Run.of(model, image_loader, text_loader, val_loader, test_loader, optimizer, scheduler, max_iters, alpha,
                   patience, precision, want_diag)
-    if capture_features_during_training:
-        print("=> capture_features_during_training is a logging-only diagnostic; not on the fused path (ignored)")
     img_src, txt_src, engine, scalars = run.img_src, run.txt_src, run.engine, run.scalars
-    blockwise = logger is None and run.indexed
+    blockwise = logger is None and run.indexed and capture is None
+    captured = torch.zeros(max_iters, 3, dtype=torch.float64, device=scalars.device) if capture is not None else None
 
     def eval_end(i, handle):
         """Reads the evaluation begun at iteration i, settles it and reports as the reference does; True = stop training."""
@@ -351,17 +402,25 @@ def train(model, image_loader, text_loader, val_loader, test_loader, optimizer, 
             scheduler.step()
             run.last_i = run.i
         i = run.i
+        if capture is not None:                       # after the update of step i (finetune.py:194 is followed by :209)
+            torch.stack(capture.step(), out=captured[i])
         if logger is not None:
-            s = scalars[i].cpu()                      # host sync: only when a logger asks for per-step values
-            # finetune.py:236-240 (the CKA / mutual-kNN / in-class-distance entries belong to the
-            # feature-capture mode, which is outside this path)
+            if capture is None:
+                s = scalars[i].cpu()                  # host sync: only when a logger asks for per-step values
+            else:                                     # the capture's three scalars ride on the same read
+                s = torch.cat([scalars[i].double(), captured[i]]).cpu()
+                cap, s = s[umlh.N_SCALARS:], s[:umlh.N_SCALARS].float()
             gd = umlh.grad_diagnostics(s, model.head.weight.numel(), 0 if img_src is None else 1, 0 if txt_src is None else 1)
-            logger.log({"train/image_loss": float(s[umlh.S_LOSS_IMG]), "train/text_loss": float(s[umlh.S_LOSS_TXT]),
-                        "train/image_acc": float(s[umlh.S_ACC_IMG]), "train/text_acc": float(s[umlh.S_ACC_TXT]),
-                        "train/lr": scheduler.get_last_lr()[0],
-                        "train/grad_direction_sim": gd["grad_direction_sim"], "train/img_grad_norm": gd["img_grad_norm"],
-                        "train/txt_grad_norm": gd["txt_grad_norm"], "train/grad_agreement_rate": gd["grad_agreement_rate"],
-                        "train/feature_direction_sim": feat_sim})
+            row = {"train/image_loss": float(s[umlh.S_LOSS_IMG]), "train/text_loss": float(s[umlh.S_LOSS_TXT]),
+                   "train/image_acc": float(s[umlh.S_ACC_IMG]), "train/text_acc": float(s[umlh.S_ACC_TXT]),
+                   "train/lr": scheduler.get_last_lr()[0],
+                   "train/grad_direction_sim": gd["grad_direction_sim"], "train/img_grad_norm": gd["img_grad_norm"],
+                   "train/txt_grad_norm": gd["txt_grad_norm"], "train/grad_agreement_rate": gd["grad_agreement_rate"],
+                   "train/feature_direction_sim": feat_sim}
+            if capture is not None:                   # finetune.py:241-243
+                row.update({"train/cka_score": float(cap[1]), "train/mknn_score": float(cap[2]),
+                            "train/inclass_distance": float(cap[0])})
+            logger.log(row)
         if i % eval_freq == 0:
             pairs, row = run.begin_eval()
             model.eval()
@@ -377,6 +436,10 @@ def train(model, image_loader, text_loader, val_loader, test_loader, optimizer, 
     if logger is not None:
         logger.log({"val/best_val_loss": val_loss, "val/best_val_acc": val_acc, "iter": out["iter"]})
     print(f"=> Best Val Loss {val_loss:.4f}, Val Acc {val_acc:.4f} at Iter {out['iter']}")
+    if capture is not None:                           # finetune.py:280-287
+        capture.save(features_pth)
+        out["capture_scalars"] = captured[:run.last_i + 1].cpu()     # (an extension, like train_scalars): per step
+                                                                      # {inclass_distance, cka_score, mknn_score}
     return out
 
 
@@ -640,7 +703,8 @@ def _build_run(tables, text_ds, hparams, *, num_classes, modality, classifier_in
 def setup_feature_run(img_train, img_val, img_test, text_ds, hparams, *, num_classes, modality="crossmodal",
                       alpha=1.0, classifier_init="zeroshot", use_clip=False, clip_logit=4.60517, text_indim=None,
                       device="cuda:0", eval_test=True, precision="fp32", eval_freq=EVAL_FREQ, tables=None,
-                      generator=None, order_rng="torch-cpu", model=None, common_dim=None):
+                      generator=None, order_rng="torch-cpu", model=None, common_dim=None,
+                      capture_features_during_training=False, features_pth="./", capture_samples=None):
     """``setup()`` (finetune.py:323-404) for pre-extracted features: builds the model,
     optimizer, scheduler and the four loaders with the reference's wiring, trains, tests.
 
@@ -648,7 +712,8 @@ def setup_feature_run(img_train, img_val, img_test, text_ds, hparams, *, num_cla
     ``feature_tables``), ``generator`` (private seed source of the loaders) and a pre-built ``model``
     are what the concurrent sweep passes in.  ``text_indim`` is ``args.text_indim`` in crossmodal mode and
     ``args.common_dim`` otherwise (the second argument of ``UML(...)``, reference :343-346); ``common_dim``
-    overrides the latter."""
+    overrides the latter.  ``capture_features_during_training`` (the reference's setup() hard-codes True, :386; off here
+    unless asked for), ``features_pth`` and ``capture_samples`` are passed on to ``train``."""
     if tables is None:
         tables = feature_tables(img_train, img_val, img_test, text_ds, device)
     model, image_loader, text_loader, val_loader, test_loader, optimizer, scheduler = _build_run(
@@ -657,7 +722,9 @@ def setup_feature_run(img_train, img_val, img_test, text_ds, hparams, *, num_cla
         order_rng=order_rng, model=model)
     result = train(model, image_loader, text_loader, val_loader, test_loader if eval_test else None, optimizer,
                    scheduler, device=device, max_iters=hparams["max_iter"], alpha=alpha, eval_freq=eval_freq,
-                   patience=hparams["patience"], precision=precision)
+                   patience=hparams["patience"], precision=precision,
+                   capture_features_during_training=capture_features_during_training, features_pth=features_pth,
+                   args=SimpleNamespace(nclasses=num_classes), capture_samples=capture_samples)
     test_loss, test_acc = validate(model, test_loader, device=device)
     return {"test_acc": test_acc, "test_loss": test_loss, "val_acc": result["val_acc"], "model": result["model"],
             "iter": result["iter"], "train_scalars": result["train_scalars"]}
@@ -708,15 +775,18 @@ def _result_file(savepath, hparams):
     return test_path, None
 
 
-def setup(datasets, hparams, args):
+def setup(datasets, hparams, args, capture_features_during_training=False):
     """One hyper-parameter point: build model / optimizer / scheduler / loaders, train, test, save
-    ``test_result.pth`` (skipped when it exists and FLAG is 0, reference :330-333)."""
+    ``test_result.pth`` (skipped when it exists and FLAG is 0, reference :330-333).  ``capture_features_during_training``
+    (default off; the reference hard-codes True, :386) writes the captured features next to the result file."""
     test_path, done = _result_file(args.savepath, hparams)
     if done is not None:
         return done
     res = setup_feature_run(datasets["img_tr"], datasets["img_val"], datasets["img_te"], datasets["text_ds"], hparams,
                             alpha=args.alpha, device=args.device, eval_test=getattr(args, "eval_test", True),
-                            precision=getattr(args, "precision", "fp32"), tables=datasets.get("tables"), **_point_args(args))
+                            precision=getattr(args, "precision", "fp32"), tables=datasets.get("tables"),
+                            capture_features_during_training=capture_features_during_training,
+                            features_pth=os.path.dirname(test_path), **_point_args(args))
     test_dict = {"test_acc": res["test_acc"], "val_acc": res["val_acc"], "model": res["model"], "iter": res["iter"]}
     print(f"=> Test Acc: {res['test_acc']:.4f}")
     torch.save(test_dict, test_path)

@@ -19,7 +19,7 @@ from . import spectral  # noqa: F401,E402
 from .spectral import effective_rank, effective_rank_seq, principal_subspace, svdvals  # noqa: F401,E402
 from .align import svcca, svcca_terms  # noqa: F401,E402
 from . import capture  # noqa: F401,E402
-from .capture import paired_cosine, seq_compact  # noqa: F401,E402
+from .capture import class_index, class_stats, paired_cosine, seq_compact  # noqa: F401,E402
 from . import stepstats  # noqa: F401,E402
 from .stepstats import seq_step_stats  # noqa: F401,E402
 from . import rollout  # noqa: F401,E402

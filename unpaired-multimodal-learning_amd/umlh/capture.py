@@ -7,6 +7,11 @@ bit for bit, which the reference does with one ``.item()`` and one slice per seq
 ``torch.cuda.current_stream`` and returns device tensors; only ``seq_compact`` without ``out`` and ``rows`` reads anything
 back (see there).  fp32 device tensors with unit column stride are read in place through their strides; other float dtypes
 are upcast and CPU tensors copied to the current device.  There is no CPU compute path.
+
+``class_index`` and ``class_stats`` (kernels: umlh_kernels_classstats.hip; C ABI: ``umlh_class_index``, ``umlh_class_stats``) are
+the class-grouped part of the fine-tune loop's feature capture (vision_language/finetune.py:222-231): a stable counting sort of
+the sample's rows by label, built once per run, and per class the mean row and the mean distance of the class's rows to it,
+which the reference forms in a Python loop with one ``nonzero``, two reductions and one ``.item()`` per class.
 """
 from __future__ import annotations
 
@@ -103,3 +108,62 @@ def paired_cosine(a: torch.Tensor, b: torch.Tensor, eps: float = 1e-8, return_ro
     check(load_library().umlh_paired_cosine(xa.data_ptr(), xa.stride(0), xb.data_ptr(), xb.stride(0), n, d, eps, out.data_ptr(),
                                             glue.ptr(rows), scratch.data_ptr(), nbytes, glue.stream(dev)), "umlh_paired_cosine")
     return (out[0], rows) if return_rows else out[0]
+
+
+def class_index(labels: torch.Tensor, n_class: int):
+    """Rows grouped by label -> ``(order, offsets)``: ``order`` (int32 [n]) lists the rows whose label lies in [0, n_class),
+    classes ascending and rows ascending inside a class; class c is ``order[offsets[c]:offsets[c + 1]]`` (``offsets`` int64
+    [n_class + 1]).  Rows with any other label appear nowhere and the entries of ``order`` past ``offsets[n_class]`` are not
+    written.  Device tensors, no host sync."""
+    if not isinstance(labels, torch.Tensor) or labels.ndim != 1 or labels.numel() < 1:
+        raise ValueError(f"class_index: expected a non-empty 1-D label tensor, got {getattr(labels, 'shape', type(labels))}")
+    if labels.is_floating_point() or labels.is_complex() or labels.dtype == torch.bool:
+        raise ValueError(f"class_index: expected integer labels, got {labels.dtype}")
+    n_class = int(n_class)
+    if n_class < 1:
+        raise ValueError(f"class_index: n_class={n_class} < 1")
+    dev = _device()
+    y = labels.detach().to(device=dev, dtype=torch.int64).contiguous()
+    n = y.numel()
+    scratch, nbytes = glue.scratch("umlh_class_index_scratch_bytes", dev, n=n, n_class=n_class)
+    order = torch.empty(n, dtype=torch.int32, device=dev)
+    offsets = torch.empty(n_class + 1, dtype=torch.int64, device=dev)
+    check(load_library().umlh_class_index(y.data_ptr(), n, n_class, order.data_ptr(), offsets.data_ptr(), scratch.data_ptr(), nbytes,
+                                          glue.stream(dev)), "umlh_class_index")
+    return order, offsets
+
+
+def class_stats(feats: torch.Tensor, order: torch.Tensor, offsets: torch.Tensor, n_class: int, means_out: torch.Tensor | None = None):
+    """Per class c with rows ``order[offsets[c]:offsets[c + 1]]`` of ``feats`` [n, d] -> ``(means, dist, out2)``: ``means`` fp32
+    [n_class, d] the class mean rows (fp64 sums, rounded once), ``dist`` float64 [n_class] the mean over the class's rows of
+    their distance to the mean that was written, ``out2`` float64 [2] = {mean over classes of dist, number of empty classes}.
+    An empty class gives a NaN row and a NaN distance, so ``out2[0]`` is NaN when a class is empty.  ``feats`` with unit column
+    stride is read in place through its row stride; ``means_out``: an fp32 device matrix [n_class, d] with unit column stride
+    (a column block of a wider one will do), written in place and returned.  Device tensors, no host sync."""
+    dev = _device()
+    x = glue.features(feats, "class_stats", dev)
+    n, d = x.shape
+    n_class = int(n_class)
+    if n_class < 1:
+        raise ValueError(f"class_stats: n_class={n_class} < 1")
+    if not isinstance(order, torch.Tensor) or order.ndim != 1 or order.numel() < n:
+        raise ValueError(f"class_stats: order must be a 1-D tensor with room for {n} rows, got {getattr(order, 'shape', type(order))}")
+    if not isinstance(offsets, torch.Tensor) or offsets.ndim != 1 or offsets.numel() != n_class + 1:
+        raise ValueError(f"class_stats: offsets must hold n_class + 1 = {n_class + 1} entries, got {getattr(offsets, 'shape', type(offsets))}")
+    order = order.detach().to(device=dev, dtype=torch.int32).contiguous()
+    offsets = offsets.detach().to(device=dev, dtype=torch.int64).contiguous()
+    if means_out is None:
+        means = torch.empty((n_class, d), dtype=torch.float32, device=dev)
+    else:
+        means = means_out
+        if (not isinstance(means, torch.Tensor) or means.ndim != 2 or tuple(means.shape) != (n_class, d) or means.dtype != torch.float32
+                or means.device != dev or means.stride(1) != 1 or means.stride(0) < d):
+            raise ValueError(f"class_stats: means_out must be an fp32 [{n_class}, {d}] matrix on {dev} with unit column stride and a "
+                             f"row stride >= {d}")
+    scratch, nbytes = glue.scratch("umlh_class_stats_scratch_bytes", dev, n=n, d=d, n_class=n_class)
+    dist = torch.empty(n_class, dtype=torch.float64, device=dev)
+    out2 = torch.empty(2, dtype=torch.float64, device=dev)
+    check(load_library().umlh_class_stats(x.data_ptr(), x.stride(0), n, d, order.data_ptr(), offsets.data_ptr(), n_class,
+                                          means.data_ptr(), means.stride(0), dist.data_ptr(), out2.data_ptr(), scratch.data_ptr(),
+                                          nbytes, glue.stream(dev)), "umlh_class_stats")
+    return means, dist, out2

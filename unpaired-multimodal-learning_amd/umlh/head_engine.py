@@ -222,10 +222,15 @@ class HeadEngine:
             check(self.lib.umlh_logits(self.handle, C.byref(b), modality, ptr(out), stream(self.device)), "umlh_logits")
         return out
 
-    def project(self, batch: RowBatch) -> torch.Tensor:
-        """img_proj(feats) -> [rows, d_shared]  (engine/models/head.py:87-90)."""
+    def project(self, batch: RowBatch, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """img_proj(feats) -> [rows, d_shared]  (engine/models/head.py:87-90); ``out``: a contiguous fp32 [rows, d_shared]
+        tensor on the engine's device to write into (a row slice of a larger block will do)."""
         b = self._batch(batch, self.d_img)
-        out = torch.empty(batch.n_rows(), self.d_shared, dtype=torch.float32, device=self.device)
+        if out is None:
+            out = torch.empty(batch.n_rows(), self.d_shared, dtype=torch.float32, device=self.device)
+        elif (tuple(out.shape) != (batch.n_rows(), self.d_shared) or out.dtype != torch.float32 or out.device != self.device
+              or not out.is_contiguous()):
+            raise ValueError(f"project: out must be a contiguous fp32 [{batch.n_rows()}, {self.d_shared}] tensor on {self.device}")
         if b is not None:
             check(self.lib.umlh_project(self.handle, C.byref(b), ptr(out), stream(self.device)), "umlh_project")
         return out
