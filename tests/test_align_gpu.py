@@ -71,6 +71,42 @@ def test_ties_follow_score_desc_index_asc_for_any_splits(n, d, k):
         np.testing.assert_array_equal(s_.cpu().numpy(), want_s)
 
 
+@pytest.mark.parametrize("n,d,k", [(255, 7, 1), (256, 1, 32), (257, 33, 24), (2048, 7, 32), (33, 3, 32), (6, 1, 5)])
+def test_tile_boundary_and_width_edges_are_exact(n, d, k):
+    """One column short of a tile, a whole tile, one column over, eight tiles; list widths 1, 24 and 32 (the widest), k = n - 1
+    (every other row is a neighbour) and n below one strip.  Integer features: every fp32 score is exact."""
+    from umlh import align
+    x = _tie_features(n, d, n + d)
+    full = x.astype(np.float64) @ x.T.astype(np.float64)
+    np.fill_diagonal(full, -np.inf)
+    want_i = np.stack([np.lexsort((np.arange(n), -full[r]))[:k] for r in range(n)])
+    want_s = np.take_along_axis(full, want_i, 1).astype(np.float32)
+    xd = dev(x)
+    for splits in (1, 2, 3, 0):
+        i_, s_ = align.knn(xd, k, splits=splits, return_scores=True)
+        np.testing.assert_array_equal(i_.cpu().numpy(), want_i, err_msg=f"splits={splits}")
+        np.testing.assert_array_equal(s_.cpu().numpy(), want_s, err_msg=f"splits={splits}")
+
+
+def test_a_nan_row_fills_only_its_own_list():
+    """A NaN score beats nothing: the NaN row's list stays unfilled (indices >= n at -inf), no row lists it, and a row whose
+    clean list did not hold it keeps its bits."""
+    from umlh import align
+    n, d, k, bad = 300, 9, 5, 13
+    x = np.random.default_rng(7).standard_normal((n, d)).astype(np.float32)
+    xn = x.copy()
+    xn[bad] = np.nan
+    for splits in (1, 3):
+        clean_i, clean_s = (t.cpu().numpy() for t in align.knn(dev(x), k, splits=splits, return_scores=True))
+        i_, s_ = (t.cpu().numpy() for t in align.knn(dev(xn), k, splits=splits, return_scores=True))
+        assert (i_[bad] >= n).all() and (s_[bad] == -np.inf).all(), (splits, i_[bad], s_[bad])
+        others = np.arange(n) != bad
+        assert not (i_[others] == bad).any(), splits
+        free = others & ~(clean_i == bad).any(1)
+        assert 0 < free.sum() < n - 1
+        assert np.array_equal(i_[free], clean_i[free]) and np.array_equal(s_[free].view(np.int32), clean_s[free].view(np.int32)), splits
+
+
 def test_split_independence_on_random_features():
     from umlh import align
     g = np.random.default_rng(5)

@@ -35,6 +35,12 @@ __device__ __forceinline__ void store_out_f32x4(float* p, f32x4v v, int plain) {
 __device__ __forceinline__ void store_out_f32(float* p, float v, int plain) {
     if (plain) *p = v; else store_wt_f32(p, v);
 }
+// Sum over the 64 lanes in a fixed xor butterfly (32, 16, .., 1): the same bits in every lane.
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
 #endif
 static inline int umlh_plain_stores() {      // (once per process)
     static const int v = env_int("UMLH_WT", 1) == 0;

@@ -16,207 +16,37 @@
 // every score is the same fma chain wherever it is computed, and the kept lists are exact top-k under a strict order.
 #include "umlh_common.h"
 #include "umlh_launch.h"
+#include "umlh_topk.h"
 #include <climits>
 
 namespace {
-
-constexpr int KN_ROWS = 32;              // rows of a workgroup's strip
-constexpr int KN_COLS = 256;             // columns of a tile: 4 waves x 64
-constexpr int KN_LD = KN_COLS + 1;       // score tile row stride (floats): the filter's reads are conflict-free
-constexpr int KN_KMAX = 32;
-constexpr int KN_KLD = KN_KMAX + 1;      // list row stride
-constexpr int KN_TARGET_WG = 512;        // auto splits: about two workgroups per CU of the 256
-constexpr int KN_MAX_SPLITS = 1024;       // (grid y)
 
 constexpr int CK_TARGET_WG = 512;
 constexpr int CK_SUM_CHUNKS = 64;        // row chunks of the column sums
 constexpr int CK_MAX_RCHUNKS = 4096;     // (grid y)
 
-__device__ __forceinline__ bool kn_better(float s, int j, float ts, int tj) { return s > ts || (s == ts && j < tj); }
+// One matrix against itself: raw inner products, column i left out of row i's list.
+struct KnnSelf : TopkOperands {
+    static constexpr bool EXCLUDE_SELF = true;
+    __device__ float col_term(long long) const { return 0.f; }
+    __device__ static float score(float acc, float) { return acc; }
+};
 
-// x[row][k .. k+3], zero outside [0, n) x [0, d)
-template <bool VEC>
-__device__ __forceinline__ f32x4v kn_load4(const float* __restrict__ x, long long row, long long n, int k, int d, int ldx) {
-    f32x4v v = {0.f, 0.f, 0.f, 0.f};
-    if (row < n) {
-        const float* p = x + row * (long long)ldx + k;
-        if (VEC) {
-            if (k < d) v = *reinterpret_cast<const f32x4v*>(p);
-        } else {
-            if (k < d) v[0] = p[0];
-            if (k + 1 < d) v[1] = p[1];
-            if (k + 2 < d) v[2] = p[2];
-            if (k + 3 < d) v[3] = p[3];
-        }
-    }
-    return v;
-}
-
-// One workgroup: rows [r0, r0 + 32) x the column tiles [t0, t1) of chunk blockIdx.y.  Wave w computes the 32 x 64 score
-// block of columns w*64.. of a tile with two 32x32 accumulators.  The k loop runs in blocks of 8: lane half h supplies
-// k = 8kb + 4h + s to MFMA step s, for A (the strip rows) and B (the tile rows) alike, so every score is the same fixed
-// permutation of its fma chain.  Epilogue per tile: scores -> LDS; each (row, 32-column part) thread keeps the candidates
-// that beat the row's current k-th entry (on a chunk's first tile also not worse than the k-th best of the 32 group-of-8
-// maxima of the tile, a valid lower bound); then the list is rebuilt from the old list plus the survivors by rank
-// counting, which is exact and independent of the order the survivors were appended in.
+// Stage 1 (topk_tiles, umlh_topk.h): rows [32 blockIdx.x, +32) x the column tiles of chunk blockIdx.y -> one partial list.
 template <bool VEC>
 __global__ __launch_bounds__(256) void knn_tiles(const float* __restrict__ x, int n, int d, int ldx, int topk, int ntiles,
                                                  int splits, float* __restrict__ part_s, int* __restrict__ part_i) {
-    __shared__ float tile[KN_ROWS * KN_LD];
-    __shared__ float ls[2][KN_ROWS * KN_KLD];
-    __shared__ int li[2][KN_ROWS * KN_KLD];
-    __shared__ unsigned char surv[KN_ROWS * KN_COLS];
-    __shared__ int cnt[KN_ROWS];
-    __shared__ float gms[KN_ROWS * KN_KLD];          // first tile: group maxima, then the tile bound in column 0
-    __shared__ int gmi[KN_ROWS * KN_KLD];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, c32 = lane & 31;
-    const int r0 = blockIdx.x * KN_ROWS, split = blockIdx.y;
-    const int t0 = (int)((long long)split * ntiles / splits), t1 = (int)((long long)(split + 1) * ntiles / splits);
-    for (int e = tid; e < KN_ROWS * KN_KLD; e += 256) {
-        ls[0][e] = -INFINITY;
-        li[0][e] = INT_MAX - (e % KN_KLD);           // distinct sentinels: ranks stay unique
-    }
-    if (tid < KN_ROWS) cnt[tid] = 0;
-    int cur = 0;
-    const int nk = (d + 7) / 8;
-    for (int t = t0; t < t1; ++t) {
-        const int cb = t * KN_COLS;
-        const long long ra = r0 + c32, rb0 = cb + wave * 64 + c32, rb1 = rb0 + 32;
-        f32x16 acc0 = {}, acc1 = {};
-        f32x4v a = kn_load4<VEC>(x, ra, n, 4 * h, d, ldx), b0 = kn_load4<VEC>(x, rb0, n, 4 * h, d, ldx),
-               b1 = kn_load4<VEC>(x, rb1, n, 4 * h, d, ldx);
-        for (int kb = 0; kb < nk; ++kb) {
-            const int kn = (kb + 1) * 8 + 4 * h;     // next block (zero past d: no access)
-            const f32x4v an = kn_load4<VEC>(x, ra, n, kn, d, ldx), b0n = kn_load4<VEC>(x, rb0, n, kn, d, ldx),
-                         b1n = kn_load4<VEC>(x, rb1, n, kn, d, ldx);
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], b0[s], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], b1[s], acc1, 0, 0, 0);
-            }
-            a = an; b0 = b0n; b1 = b1n;
-        }
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {               // acc[q]: row 8(q/4) + 4h + q%4, column c32 (the last rebuild ended on a barrier)
-            const int i = 8 * (q >> 2) + 4 * h + (q & 3);
-            tile[i * KN_LD + wave * 64 + c32] = acc0[q];
-            tile[i * KN_LD + wave * 64 + 32 + c32] = acc1[q];
-        }
-        __syncthreads();
-        const int fr = tid & 31, part = tid >> 5, gi = r0 + fr;      // filter mapping: row fr, columns part*32 ..
-        const float* cls = ls[cur];
-        const int* cli = li[cur];
-        float bs = -INFINITY;                        // tile bound (first tile of the chunk only)
-        int bj = INT_MAX;
-        if (t == t0) {
-            for (int g = 0; g < 4; ++g) {
-                float ms = -INFINITY;
-                int mj = INT_MAX - KN_KMAX - (part * 4 + g);
-                for (int m = 0; m < 8; ++m) {
-                    const int c = part * 32 + g * 8 + m, j = cb + c;
-                    const float s = tile[fr * KN_LD + c];
-                    if (j < n && j != gi && kn_better(s, j, ms, mj)) { ms = s; mj = j; }
-                }
-                gms[fr * KN_KLD + part * 4 + g] = ms;
-                gmi[fr * KN_KLD + part * 4 + g] = mj;
-            }
-            __syncthreads();
-            const int rr = tid >> 3, sub = tid & 7;
-            float ws = 0.f;
-            int wj = 0, hit = 0;
-            for (int m = sub; m < 32; m += 8) {      // rank of each group maximum among the 32
-                const float s = gms[rr * KN_KLD + m];
-                const int j = gmi[rr * KN_KLD + m];
-                int rank = 0;
-                for (int q = 0; q < 32; ++q) rank += kn_better(gms[rr * KN_KLD + q], gmi[rr * KN_KLD + q], s, j);
-                if (rank == topk - 1) { ws = s; wj = j; hit = 1; }
-            }
-            __syncthreads();
-            if (hit) { gms[rr * KN_KLD] = ws; gmi[rr * KN_KLD] = wj; }
-            __syncthreads();
-            bs = gms[fr * KN_KLD];
-            bj = gmi[fr * KN_KLD];
-        }
-        if (gi < n) {
-            const float ts = cls[fr * KN_KLD + topk - 1];
-            const int tj = cli[fr * KN_KLD + topk - 1];
-            for (int m = 0; m < 32; ++m) {
-                const int c = part * 32 + m, j = cb + c;
-                if (j >= n) break;
-                const float s = tile[fr * KN_LD + c];
-                if (j != gi && kn_better(s, j, ts, tj) && !kn_better(bs, bj, s, j)) {
-                    const int p = atomicAdd(&cnt[fr], 1);
-                    surv[fr * KN_COLS + p] = (unsigned char)c;
-                }
-            }
-        }
-        __syncthreads();
-        {   // rebuild: row rr's candidates are its k list entries and its survivors; rank < k goes to position rank
-            const int rr = tid >> 3, sub = tid & 7, m_all = topk + cnt[rr];
-            float* nls = ls[cur ^ 1];
-            int* nli = li[cur ^ 1];
-            auto cand = [&](int m, float& s, int& j) {
-                if (m < topk) { s = cls[rr * KN_KLD + m]; j = cli[rr * KN_KLD + m]; }
-                else { const int c = surv[rr * KN_COLS + m - topk]; s = tile[rr * KN_LD + c]; j = cb + c; }
-            };
-            for (int m = sub; m < m_all; m += 8) {
-                float s;
-                int j;
-                cand(m, s, j);
-                int rank = 0;
-                for (int q = 0; q < m_all; ++q) {
-                    float s2;
-                    int j2;
-                    cand(q, s2, j2);
-                    rank += kn_better(s2, j2, s, j);
-                }
-                if (rank < topk) { nls[rr * KN_KLD + rank] = s; nli[rr * KN_KLD + rank] = j; }
-            }
-            __syncthreads();
-            if (tid < KN_ROWS) cnt[tid] = 0;
-            cur ^= 1;
-        }
-    }
-    for (int e = tid; e < KN_ROWS * topk; e += 256) {
-        const int r = e / topk, q = e - r * topk;
-        if (r0 + r < n) {
-            const long long o = ((long long)split * n + r0 + r) * topk + q;
-            part_s[o] = ls[cur][r * KN_KLD + q];
-            part_i[o] = li[cur][r * KN_KLD + q];
-        }
-    }
+    topk_tiles<VEC>(KnnSelf{{x, x, n, ldx, n, ldx, d, topk}}, ntiles, splits, part_s, part_i);
 }
 
-// Thread per row: the chunks' sorted lists merged pairwise in chunk order (exact under the strict order).
+// Stage 2 (topk_merge).  A list entry that no column filled (a row of NaN scores) is published as INT_MAX - e, e >= 0: never
+// a row index, since n <= 2^30.
 __global__ __launch_bounds__(64) void knn_merge(const float* __restrict__ part_s, const int* __restrict__ part_i, int n, int topk,
                                                 int splits, int* __restrict__ knn, float* __restrict__ scores) {
-    __shared__ float bs[2][64 * KN_KLD];
-    __shared__ int bi[2][64 * KN_KLD];
-    const int tid = threadIdx.x;
-    const long long row = (long long)blockIdx.x * 64 + tid;
-    if (row >= n) return;
-    float* cs = &bs[0][tid * KN_KLD];
-    int* ci = &bi[0][tid * KN_KLD];
-    float* ns = &bs[1][tid * KN_KLD];
-    int* ni = &bi[1][tid * KN_KLD];
-    for (int q = 0; q < topk; ++q) { cs[q] = part_s[row * topk + q]; ci[q] = part_i[row * topk + q]; }
-    for (int s = 1; s < splits; ++s) {
-        const float* ps = part_s + ((long long)s * n + row) * topk;
-        const int* pi = part_i + ((long long)s * n + row) * topk;
-        int ia = 0, ib = 0;
-        for (int q = 0; q < topk; ++q) {             // ia + ib = q < topk: both stay in range
-            const float sa = cs[ia], sb = ps[ib];
-            const int ja = ci[ia], jb = pi[ib];
-            if (kn_better(sa, ja, sb, jb)) { ns[q] = sa; ni[q] = ja; ++ia; }
-            else { ns[q] = sb; ni[q] = jb; ++ib; }
-        }
-        float* ts = cs; cs = ns; ns = ts;
-        int* ti = ci; ci = ni; ni = ti;
-    }
-    for (int q = 0; q < topk; ++q) {
-        knn[row * topk + q] = ci[q];
-        if (scores) scores[row * topk + q] = cs[q];
-    }
+    topk_merge(part_s, part_i, n, topk, splits, [=](long long o, float s, int j) {
+        knn[o] = j < 0 ? INT_MAX - (-1 - j) : j;
+        if (scores) scores[o] = s;
+    });
 }
 
 __global__ __launch_bounds__(256) void mutual_count(const int* __restrict__ ka, const int* __restrict__ kb, int n, int topk,
@@ -390,19 +220,12 @@ __global__ __launch_bounds__(256) void cka_final(const double* __restrict__ tile
     }
 }
 
-inline long long align_up(long long x) { return (x + 255) / 256 * 256; }
-
 }  // namespace
 
 // ---- plans and launchers (validation is the caller's: umlh_api.cpp) ----
 extern "C" {
 
-int umlh_align_knn_splits(long long n, int splits) {
-    const long long ntiles = (n + KN_COLS - 1) / KN_COLS, strips = (n + KN_ROWS - 1) / KN_ROWS;
-    long long s = splits > 0 ? splits : (KN_TARGET_WG + strips - 1) / strips;
-    if (s > KN_MAX_SPLITS) s = KN_MAX_SPLITS;
-    return (int)(s < 1 ? 1 : (s > ntiles ? ntiles : s));
-}
+int umlh_align_knn_splits(long long n, int splits) { return topk_splits(n, n, splits); }
 
 unsigned long long umlh_align_knn_bytes(long long n, int topk, int splits) {
     return (unsigned long long)(2 * align_up((long long)umlh_align_knn_splits(n, splits) * n * topk * 4));
@@ -436,10 +259,10 @@ unsigned long long umlh_align_cka_bytes(long long n, int da, int db, int splits)
 
 int umlh_align_launch_knn(const float* x, long long n, int d, int ldx, int topk, int splits, int* knn, float* scores, void* scratch,
                           hipStream_t st) {
-    const int s = umlh_align_knn_splits(n, splits), ntiles = (int)((n + KN_COLS - 1) / KN_COLS);
+    const int s = umlh_align_knn_splits(n, splits), ntiles = (int)((n + TK_COLS - 1) / TK_COLS);
     float* ps = (float*)scratch;
     int* pi = (int*)((char*)scratch + align_up((long long)s * n * topk * 4));
-    const dim3 grid((unsigned)((n + KN_ROWS - 1) / KN_ROWS), (unsigned)s);
+    const dim3 grid((unsigned)((n + TK_ROWS - 1) / TK_ROWS), (unsigned)s);
     const bool vec = (d % 4 == 0) && (ldx % 4 == 0) && (((uintptr_t)x & 15) == 0);
     if (vec) hipLaunchKernelGGL(knn_tiles<true>, grid, dim3(256), 0, st, x, (int)n, d, ldx, topk, ntiles, s, ps, pi);
     else hipLaunchKernelGGL(knn_tiles<false>, grid, dim3(256), 0, st, x, (int)n, d, ldx, topk, ntiles, s, ps, pi);

@@ -21,16 +21,14 @@
 // Nothing here forms an N x N array and no reduction uses a float atomic: results are bitwise reproducible for a given `splits`.
 #include "umlh_common.h"
 #include "umlh_launch.h"
+#include "umlh_topk.h"
 
 namespace {
 
-constexpr int RB_ROWS = 32;              // rows of a workgroup's strip (as knn_tiles)
-constexpr int RB_COLS = 256;             // columns of a tile: 4 waves x 64
 constexpr int NSUM = 12;
 constexpr int LS_KMAX = 32;
 constexpr int LS_LD = LS_KMAX + 1;
 
-inline long long align_up(long long x) { return (x + 255) / 256 * 256; }
 inline int up4(int d) { return (d + 3) / 4 * 4; }
 
 // Sum of v over the 256 threads in a fixed tree (every thread calls; every thread gets the sum).
@@ -178,25 +176,13 @@ __device__ __forceinline__ f32x4v rb_load4(const float* __restrict__ x, const fl
     return v;
 }
 
-// The 32 x 64 block of centred inner products (rows ra = strip row c32, columns rb0 / rb1 = the wave's columns c32 / 32 + c32):
-// the k loop of knn_tiles, lane half h supplying k = 8kb + 4h + s to MFMA step s.
+// The 32 x 64 block of centred inner products of one view: the k loop of the k-NN tiles (gram_32x64, umlh_topk.h) on the
+// mean-centring loader.  The strips and tiles are the k-NN pass's as well (TK_ROWS x TK_COLS, umlh_align_knn_splits).
 template <bool VEC>
 __device__ __forceinline__ void rb_gram(const float* __restrict__ x, const float* __restrict__ mean, long long n, int d, int ldx,
                                         long long ra, long long rb0, long long rb1, int h, f32x16& acc0, f32x16& acc1) {
-    const int nk = (d + 7) / 8;
-    f32x4v a = rb_load4<VEC>(x, mean, ra, n, 4 * h, d, ldx), b0 = rb_load4<VEC>(x, mean, rb0, n, 4 * h, d, ldx),
-           b1 = rb_load4<VEC>(x, mean, rb1, n, 4 * h, d, ldx);
-    for (int kb = 0; kb < nk; ++kb) {
-        const int kn = (kb + 1) * 8 + 4 * h;         // next block (zero past d: no access)
-        const f32x4v an = rb_load4<VEC>(x, mean, ra, n, kn, d, ldx), b0n = rb_load4<VEC>(x, mean, rb0, n, kn, d, ldx),
-                     b1n = rb_load4<VEC>(x, mean, rb1, n, kn, d, ldx);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], b0[s], acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], b1[s], acc1, 0, 0, 0);
-        }
-        a = an; b0 = b0n; b1 = b1n;
-    }
+    const auto load = [&](long long row, int k) { return rb_load4<VEC>(x, mean, row, n, k, d, ldx); };
+    gram_32x64(load, load, d, ra, rb0, rb1, h, acc0, acc1);
 }
 
 struct RbfArgs {
@@ -220,15 +206,15 @@ __device__ __forceinline__ float rb_value(float acc, float ni, float nj, float g
 
 template <bool VEC>
 __global__ __launch_bounds__(256) void rbf_tiles(RbfArgs g) {
-    __shared__ float rn[2][RB_ROWS];
-    __shared__ double rs[4][RB_ROWS][2];
+    __shared__ float rn[2][TK_ROWS];
+    __shared__ double rs[4][TK_ROWS][2];
     __shared__ double red[256];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, c32 = lane & 31;
     const int n = g.n, da4 = (g.da + 3) / 4 * 4;
-    const long long r0 = (long long)blockIdx.x * RB_ROWS;
+    const long long r0 = (long long)blockIdx.x * TK_ROWS;
     const int split = blockIdx.y;
     const int t0 = (int)((long long)split * g.ntiles / g.splits), t1 = (int)((long long)(split + 1) * g.ntiles / g.splits);
-    if (tid < 2 * RB_ROWS) {
+    if (tid < 2 * TK_ROWS) {
         const int v = tid >> 5, i = tid & 31;
         rn[v][i] = r0 + i < n ? g.norms[(long long)v * n + r0 + i] : 0.f;
     }
@@ -238,7 +224,7 @@ __global__ __launch_bounds__(256) void rbf_tiles(RbfArgs g) {
 #pragma unroll
     for (int q = 0; q < 16; ++q) { rowk[q] = 0.0; rowl[q] = 0.0; }
     for (int t = t0; t < t1; ++t) {
-        const long long ra = r0 + c32, rb0 = (long long)t * RB_COLS + wave * 64 + c32, rb1 = rb0 + 32;
+        const long long ra = r0 + c32, rb0 = (long long)t * TK_COLS + wave * 64 + c32, rb1 = rb0 + 32;
         float kv0[16], kv1[16];
         {
             f32x16 acc0 = {}, acc1 = {};
@@ -284,9 +270,9 @@ __global__ __launch_bounds__(256) void rbf_tiles(RbfArgs g) {
         }
     }
     __syncthreads();
-    if (tid < 2 * RB_ROWS) {
+    if (tid < 2 * TK_ROWS) {
         const int i = tid >> 1, v = tid & 1;
-        g.rowpart[(((long long)split * g.strips) * RB_ROWS + r0 + i) * 2 + v] = ((rs[0][i][v] + rs[1][i][v]) + rs[2][i][v]) + rs[3][i][v];
+        g.rowpart[(((long long)split * g.strips) * TK_ROWS + r0 + i) * 2 + v] = ((rs[0][i][v] + rs[1][i][v]) + rs[2][i][v]) + rs[3][i][v];
     }
     const long long nwg = (long long)g.splits * g.strips, wg = (long long)split * g.strips + blockIdx.x;
     const double pkl = block_sum(skl, red), pkk = block_sum(skk, red), pll = block_sum(sll, red);
@@ -514,20 +500,17 @@ RbfPlan rbf_plan(long long n, int da, int db, int splits) {
     const long long dt = (long long)da + db;
     p.chunks = umlh_align_cka_sum_chunks(n);
     p.splits = umlh_align_knn_splits(n, splits);     // the same strips and tiles as the k-NN pass
-    p.ntiles = (int)((n + RB_COLS - 1) / RB_COLS);
-    p.strips = (n + RB_ROWS - 1) / RB_ROWS;
+    p.ntiles = (int)((n + TK_COLS - 1) / TK_COLS);
+    p.strips = (n + TK_ROWS - 1) / TK_ROWS;
     p.nblocks = (n + 255) / 256;
     p.mean = align_up(p.chunks * dt * 8);
     p.norms = p.mean + align_up((long long)(up4(da) + up4(db)) * 4);
     p.pair = p.norms + align_up(2 * n * 4);
     p.rowpart = p.pair + align_up(3 * p.splits * p.strips * 8);
-    p.part = p.rowpart + align_up(p.splits * p.strips * RB_ROWS * 2 * 8);
+    p.part = p.rowpart + align_up(p.splits * p.strips * TK_ROWS * 2 * 8);
     p.total = p.part + align_up(p.nblocks * NSUM * 8);
     return p;
 }
-
-template <class T>
-inline T* at(void* scratch, long long off) { return reinterpret_cast<T*>((char*)scratch + off); }
 
 }  // namespace
 
@@ -594,7 +577,7 @@ int umlh_align_ext_launch_rbf(const float* a, int lda, int da, const float* b, i
     if (vec) hipLaunchKernelGGL(rbf_tiles<true>, grid, dim3(256), 0, st, g);
     else hipLaunchKernelGGL(rbf_tiles<false>, grid, dim3(256), 0, st, g);
     double* part = at<double>(scratch, p.part);
-    hipLaunchKernelGGL(rbf_rows, dim3((unsigned)p.nblocks), dim3(256), 0, st, g.rowpart, p.splits, p.strips * RB_ROWS, (int)n, part);
+    hipLaunchKernelGGL(rbf_rows, dim3((unsigned)p.nblocks), dim3(256), 0, st, g.rowpart, p.splits, p.strips * TK_ROWS, (int)n, part);
     const long long nwg = p.splits * p.strips;
     hipLaunchKernelGGL(ext_final, dim3(1), dim3(256), 0, st, g.pair, nwg, nwg, nwg, part, p.nblocks, (double)n, unbiased, out4);
     return (int)hipGetLastError();

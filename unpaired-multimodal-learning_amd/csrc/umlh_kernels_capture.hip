@@ -65,12 +65,6 @@ __global__ __launch_bounds__(256) void cap_compact(const V* __restrict__ z, int 
     }
 }
 
-__device__ __forceinline__ double cap_wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;                                              // the same bits in every lane
-}
-
 __global__ __launch_bounds__(64 * CAP_COS_WAVES) void cap_cos_rows(const float* __restrict__ a, long long lda,
                                                                     const float* __restrict__ b, long long ldb, long long n, int d,
                                                                     double eps, float* __restrict__ rows, double* __restrict__ partial) {
@@ -89,9 +83,9 @@ __global__ __launch_bounds__(64 * CAP_COS_WAVES) void cap_cos_rows(const float* 
             aa += x * x;
             bb += y * y;
         }
-        ab = cap_wave_sum(ab);
-        aa = cap_wave_sum(aa);
-        bb = cap_wave_sum(bb);
+        ab = wave_sum_f64(ab);
+        aa = wave_sum_f64(aa);
+        bb = wave_sum_f64(bb);
         const double na = sqrt(aa), nb = sqrt(bb);
         const double cos_r = ab / ((na > eps ? na : eps) * (nb > eps ? nb : eps));   // a NaN or Inf element makes a.b NaN or the
                                                                                       // quotient Inf / Inf: NaN either way, as in torch

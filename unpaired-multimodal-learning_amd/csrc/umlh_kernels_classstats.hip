@@ -234,12 +234,6 @@ __device__ __forceinline__ void cs_col_sums(const float* __restrict__ feats, lon
     }
 }
 
-__device__ __forceinline__ double cs_wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;                                              // the same bits in every lane
-}
-
 // Sum over the wave's valid rows of |x - mean|_2, the same value in every lane.
 template <bool VEC>
 __device__ __forceinline__ double cs_row_dists(const float* __restrict__ feats, long long ld, int d, const float* mean,
@@ -269,7 +263,7 @@ __device__ __forceinline__ double cs_row_dists(const float* __restrict__ feats, 
                     q += a * a;
                 }
         }
-        acc += sqrt(cs_wave_sum(q));
+        acc += sqrt(wave_sum_f64(q));
     }
     return acc;
 }

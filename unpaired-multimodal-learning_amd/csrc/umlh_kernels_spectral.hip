@@ -34,10 +34,6 @@ constexpr int SP_EIG_THREADS = 1024;
 constexpr int SP_EIG_WAVES = SP_EIG_THREADS / 64;
 constexpr int SP_BISECT_PASSES = 30;      // interval 4^-30 of the Gershgorin width: below an ulp of any eigenvalue that matters
 
-inline long long align_up(long long x) { return (x + 255) / 256 * 256; }
-template <typename T>
-inline T* at(void* base, long long off) { return reinterpret_cast<T*>(static_cast<char*>(base) + off); }
-
 // How row r of matrix m is addressed: a + m * sm + (r / period) * so + (r % period) * si.  Dense: period = n (so unused);
 // sequence block: one matrix of b * t_len rows, period = t_len, so = ldb, si = ldt.
 struct RowMap {
@@ -130,13 +126,6 @@ __global__ __launch_bounds__(256) void spectral_reduce(const double* __restrict_
     gm[(long long)j * d + i] = v;
 }
 
-// Sum over the wave in a fixed butterfly; every lane gets it.
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 struct EigOut {
     double* erank;        // NULL or [batch]
     long long erank_ld;
@@ -196,7 +185,7 @@ __device__ __forceinline__ void sp_tridiag(double* A, int d, bool degenerate, do
         const double* x = A + (long long)k * d + k + 1;
         double ss = 0.0;
         for (int i = 1 + lane; i < m; i += 64) ss = fma(x[i], x[i], ss);
-        ss = wave_sum(ss);                                     // every wave forms the same value
+        ss = wave_sum_f64(ss);                                     // every wave forms the same value
         const double alpha = x[0];
         double tau = 0.0, beta = alpha, inv = 0.0;
         if (ss > 0.0) {
@@ -225,7 +214,7 @@ __device__ __forceinline__ void sp_tridiag(double* A, int d, bool degenerate, do
                     if (h2) s2 = fma(t0[2 * d + c], vc, s2);
                     if (h3) s3 = fma(t0[3 * d + c], vc, s3);
                 }
-                s0 = wave_sum(s0); s1 = wave_sum(s1); s2 = wave_sum(s2); s3 = wave_sum(s3);
+                s0 = wave_sum_f64(s0); s1 = wave_sum_f64(s1); s2 = wave_sum_f64(s2); s3 = wave_sum_f64(s3);
                 if (lane == 0) {
                     w[r] = tau * s0;
                     if (h1) w[r + 1] = tau * s1;
@@ -236,7 +225,7 @@ __device__ __forceinline__ void sp_tridiag(double* A, int d, bool degenerate, do
             __syncthreads();
             double pv = 0.0;
             for (int i = lane; i < m; i += 64) pv = fma(w[i], v[i], pv);
-            pv = wave_sum(pv);
+            pv = wave_sum_f64(pv);
             const double c2 = 0.5 * tau * pv;
             __syncthreads();                                   // every wave has read w before it changes
             for (int i = tid; i < m; i += SP_EIG_THREADS) w[i] = w[i] - c2 * v[i];
@@ -637,14 +626,14 @@ __global__ __launch_bounds__(SP_EIG_THREADS) void subspace_eig(EigJobs jobs) {
                     zc[m] = i < d ? z[(long long)i * SS_MAX_Q + c] : 0.0;
                     dot = fma(zc[m], zr[m], dot);
                 }
-                dot = wave_sum(dot);
+                dot = wave_sum_f64(dot);
 #pragma unroll
                 for (int m = 0; m < SP_MAX_D / 64; ++m) zr[m] = fma(-dot, zc[m], zr[m]);
             }
             double nn = 0.0;
 #pragma unroll
             for (int m = 0; m < SP_MAX_D / 64; ++m) nn = fma(zr[m], zr[m], nn);
-            nn = wave_sum(nn);
+            nn = wave_sum_f64(nn);
             const double inv = 1.0 / sqrt(nn);
 #pragma unroll
             for (int m = 0; m < SP_MAX_D / 64; ++m) {
@@ -671,7 +660,7 @@ __global__ __launch_bounds__(SP_EIG_THREADS) void subspace_eig(EigJobs jobs) {
                 hr[m] = i > k && i < d ? hv[i] : 0.0;
                 dot = fma(hr[m], zr[m], dot);
             }
-            dot = wave_sum(dot) * taus[k];
+            dot = wave_sum_f64(dot) * taus[k];
 #pragma unroll
             for (int m = 0; m < SP_MAX_D / 64; ++m) zr[m] = fma(-dot, hr[m], zr[m]);
         }

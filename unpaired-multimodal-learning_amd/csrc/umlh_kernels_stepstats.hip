@@ -46,12 +46,6 @@ __device__ __forceinline__ long long ss_len(const long long* __restrict__ length
     return len < 0 ? 0 : (len > T ? T : len);
 }
 
-__device__ __forceinline__ double ss_wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;                                              // the same bits in every lane
-}
-
 struct Quad { float v[4]; };
 
 // columns 4q .. 4q + 3 of one row; n = how many of them exist (1..4)
@@ -108,8 +102,8 @@ __global__ __launch_bounds__(256) void stats_partial(const float* __restrict__ x
             cur = nxt;
         }
     }
-    tri = ss_wave_sum(tri);
-    rec = ss_wave_sum(rec);
+    tri = wave_sum_f64(tri);
+    rec = wave_sum_f64(rec);
     if ((tid & 63) == 0) {
         wsum[0][tid >> 6] = tri;
         wsum[1][tid >> 6] = rec;
@@ -141,8 +135,8 @@ __global__ __launch_bounds__(SS_FINAL_THREADS) void stats_final(const double* __
         n_tri += len < T - 1 ? len : T - 1;
         n_rec += len > 0 ? len - 1 : 0;
     }
-    tri = ss_wave_sum(tri);
-    rec = ss_wave_sum(rec);
+    tri = wave_sum_f64(tri);
+    rec = wave_sum_f64(rec);
 #pragma unroll
     for (int m = 32; m > 0; m >>= 1) {
         n_tri += __shfl_xor(n_tri, m, 64);

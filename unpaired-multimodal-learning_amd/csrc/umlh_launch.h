@@ -6,6 +6,11 @@
 #include "umlh_common.h"
 #include "umlh_micro.h"
 
+// Scratch layouts of the metric launchers: every region starts on a 256-byte boundary; region `off` of a scratch block as T*.
+inline long long align_up(long long x) { return (x + 255) / 256 * 256; }
+template <class T>
+inline T* at(void* scratch, long long off) { return reinterpret_cast<T*>(static_cast<char*>(scratch) + off); }
+
 extern "C" {
 // ---- umlh_kernels_f32.hip: fp32 head step, generic fp32 GEMMs, optimizer / finalize kernels ----
 int umlh_launch_w_shadow32(const float* w, float* dst, int C, int K, int cpad, hipStream_t stream);
