@@ -7,8 +7,9 @@ reference's value for torch / numpy seeds 0-4 on the fp32 inputs (ref32[5]) and 
 distance from the closed form within which all ten must lie (a condition on the inputs: a case that breaks it needs a wider
 planted gap, not a wider bound).
 
-All cases are planted spectra: q latent directions of strengths 3 -> 1.5 times GAIN over unit noise, `shared` of them common
-to both views, so that sigma_(q+1) / sigma_q of each standardised view stays near 0.15 and the top-q subspace is well defined."""
+All cases are planted spectra (tests/_svcca_ref.py: gen_case): q latent directions of strengths 3 -> 1.5 times GAIN over unit
+noise, `shared` of them common to both views, so that sigma_(q+1) / sigma_q of each standardised view stays near 0.15 and the
+top-q subspace is well defined."""
 import os
 import sys
 import warnings
@@ -22,7 +23,6 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _svcca_ref as R  # noqa: E402
 from make_golden_alignment import REF, _load_ref  # noqa: E402
 
-GAIN = 8.0
 BOUND = 1e-4
 SEEDS = range(5)
 #        name     n    d_a  d_b  q   shared
@@ -33,38 +33,6 @@ CASES = (("mosei", 257, 35, 300, 10, 6),
          ("q1", 300, 20, 24, 1, 1),
          ("full", 300, 6, 6, 6, 3),
          ("same", 300, 40, 40, 10, 10))
-
-
-def planted(g, latent, d):
-    """latent[n, q] (orthogonal columns of norm sqrt(n)) -> n x d: strengths GAIN * (3 -> 1.5) along q orthonormal row
-    directions, plus noise of unit spectral scale (its largest singular value is about sqrt(n), like one latent direction of
-    strength 1)."""
-    n, q = latent.shape
-    rows = np.linalg.qr(g.standard_normal((d, q)))[0]
-    if q == 1:                         # one direction: random signs, so that no column is left to the noise alone (which the
-        rows = np.sign(rows) / np.sqrt(d)   # standardisation would scale up until sigma_2 / sigma_1 passes 0.2)
-    noise = g.standard_normal((n, d)) / (1.0 + np.sqrt(d / n))
-    return (latent * (GAIN * np.linspace(3.0, 1.5, q))) @ rows.T + noise
-
-
-def gen_case(name, n, d_a, d_b, q, shared):
-    g = np.random.default_rng(sum(map(ord, name)))
-    lat = np.linalg.qr(g.standard_normal((n, 2 * q - shared)))[0] * np.sqrt(n)
-    la = lat[:, :q]
-    lb = np.concatenate([lat[:, :shared], lat[:, q:]], axis=1)
-    a = planted(g, la, d_a)
-    if name == "same":                 # B = A W, W a column permutation times a positive diagonal: the same subspace, rho = 1
-        a32 = a.astype(np.float32)
-        return a32, (a32.astype(np.float64)[:, g.permutation(d_a)] * g.uniform(0.5, 2.0, d_a)).astype(np.float32)
-    b = planted(g, lb, d_b)
-    if name == "offset":               # means up to 50 sigma, scales over 10^3, one exactly constant column per view
-        for x in (a, b):
-            scale = np.logspace(-1.5, 1.5, x.shape[1])[g.permutation(x.shape[1])]
-            x *= scale
-            x += g.uniform(-50.0, 50.0, x.shape[1]) * x.std(axis=0)
-        a[:, 17] = 3.25
-        b[:, 40] = -0.4375
-    return a.astype(np.float32), b.astype(np.float32)
 
 
 def reference_values(mb, a, b, q, dtype):
@@ -82,7 +50,7 @@ def main():
     mb = _load_ref("ref_mb_metrics", os.path.join(REF, "MultiBench", "metrics.py"))
     parts = []
     for name, n, d_a, d_b, q, shared in CASES:
-        a, b = gen_case(name, n, d_a, d_b, q, shared)
+        a, b = R.gen_case(name, n, d_a, d_b, q, shared)
         rho = R.rho64(a, b, q)
         closed = float(rho.mean())
         ref32, ref64 = reference_values(mb, a, b, q, torch.float32), reference_values(mb, a, b, q, torch.float64)

@@ -5,6 +5,20 @@ import numpy as np
 
 TAU_SCALE = 2.0 ** -20      # decidability margin: tau_i = 2^-20 * |x_i| * max_j |x_j|
 
+# (n, d_a, d_b) at which a 32-column tile body can go wrong unseen by the recorded cases: different tile counts per view with one
+# row left in the last 32-row block and d_a rounded up to 36; a one-column view against three tiles; fewer rows than one
+# 8-row group (three of the four waves idle)
+TILE_EDGES = [(97, 33, 31), (33, 1, 65), (5, 64, 32)]
+
+
+def tile_edge_pair(n, da, db):
+    """Two float32 views of one 4-dimensional latent plus noise, off the origin; seeded by the shape."""
+    g = np.random.default_rng(10000 * n + 100 * da + db)
+    z = g.standard_normal((n, 4))
+    a = z @ g.standard_normal((4, da)) + 0.5 * g.standard_normal((n, da)) + 1.0
+    b = z @ g.standard_normal((4, db)) + 0.5 * g.standard_normal((n, db)) - 2.0
+    return a.astype(np.float32), b.astype(np.float32)
+
 
 def cka64(a, b):
     """(cka, hsic_kl, hsic_kk, hsic_ll) in float64 from the column-centred features: trace(K H L H) = |Ac^T Bc|_F^2."""

@@ -81,3 +81,39 @@ def invariance_maps(a, b):
     sa, sb = g.choice([0.5, 1.0, 2.0, 3.0, 4.0], a.shape[1]), g.choice([0.5, 1.0, 2.0, 3.0, 4.0], b.shape[1])
     ta, tb = g.integers(-25600, 25600, a.shape[1]) / 256.0, g.integers(-25600, 25600, b.shape[1]) / 256.0
     return perm, a.astype(np.float64) * sa + ta, b.astype(np.float64) * sb + tb
+
+
+# ---- planted cases: scripts/make_golden_svcca.py records them, tests/test_svcca_gpu.py generates one more ----
+GAIN = 8.0
+
+
+def planted(g, latent, d):
+    """latent[n, q] (orthogonal columns of norm sqrt(n)) -> n x d: strengths GAIN * (3 -> 1.5) along q orthonormal row
+    directions, plus noise of unit spectral scale (its largest singular value is about sqrt(n), like one latent direction of
+    strength 1)."""
+    n, q = latent.shape
+    rows = np.linalg.qr(g.standard_normal((d, q)))[0]
+    if q == 1:                         # one direction: random signs, so that no column is left to the noise alone (which the
+        rows = np.sign(rows) / np.sqrt(d)   # standardisation would scale up until sigma_2 / sigma_1 passes 0.2)
+    noise = g.standard_normal((n, d)) / (1.0 + np.sqrt(d / n))
+    return (latent * (GAIN * np.linspace(3.0, 1.5, q))) @ rows.T + noise
+
+
+def gen_case(name, n, d_a, d_b, q, shared):
+    g = np.random.default_rng(sum(map(ord, name)))
+    lat = np.linalg.qr(g.standard_normal((n, 2 * q - shared)))[0] * np.sqrt(n)
+    la = lat[:, :q]
+    lb = np.concatenate([lat[:, :shared], lat[:, q:]], axis=1)
+    a = planted(g, la, d_a)
+    if name == "same":                 # B = A W, W a column permutation times a positive diagonal: the same subspace, rho = 1
+        a32 = a.astype(np.float32)
+        return a32, (a32.astype(np.float64)[:, g.permutation(d_a)] * g.uniform(0.5, 2.0, d_a)).astype(np.float32)
+    b = planted(g, lb, d_b)
+    if name == "offset":               # means up to 50 sigma, scales over 10^3, one exactly constant column per view
+        for x in (a, b):
+            scale = np.logspace(-1.5, 1.5, x.shape[1])[g.permutation(x.shape[1])]
+            x *= scale
+            x += g.uniform(-50.0, 50.0, x.shape[1]) * x.std(axis=0)
+        a[:, 17] = 3.25
+        b[:, 40] = -0.4375
+    return a.astype(np.float32), b.astype(np.float32)

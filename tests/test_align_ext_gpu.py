@@ -65,6 +65,28 @@ def test_golden_rbf_cka(gold, ext, case, setting, unbiased):
     assert abs(got - want) <= 1e-5, (case, setting, unbiased, got, want)
 
 
+@pytest.mark.parametrize("strided", [False, True])
+@pytest.mark.parametrize("n,da,db", R.TILE_EDGES)
+def test_tile_edge_unbiased_and_rbf_cka(n, da, db, strided):
+    """The bounds of test_golden_unbiased_cka and test_golden_rbf_cka against float64 at the tile-edge shapes of
+    tests/test_align_gpu.py, for every way the rows are chunked; sigma = the mean median pairwise distance."""
+    from test_align_gpu import edge_views
+    from umlh import align
+    xa, xb = R.tile_edge_pair(n, da, db)
+    a, b = edge_views(xa, xb, strided)
+    u64, sigma = X.unbiased_cka64(xa, xb), X.median_sigma(xa, xb)
+    r64 = {u: X.rbf_cka64(xa, xb, sigma, u) for u in (False, True)}
+    for splits in (1, 3, 0):
+        out = align.unbiased_cka_terms(a, b, splits=splits).cpu().numpy()
+        print(f"unbiased_cka[{n},{da},{db},strided={strided},splits={splits}]: got {out!r} ref64 {u64!r}")
+        assert abs(out[0] - u64[0]) <= 1e-5, (splits, out[0], u64[0])
+        np.testing.assert_allclose(out[1:], u64[1:], rtol=1e-5)
+        for u in (False, True):
+            got = float(align.rbf_cka(a, b, sigma, u, splits=splits))
+            print(f"rbf_cka[{n},{da},{db},strided={strided},unbiased={u},splits={splits}]: got {got!r} ref64 {r64[u][0]!r}")
+            assert abs(got - r64[u][0]) <= 1e-5, (splits, u, got, r64[u][0])
+
+
 @pytest.mark.parametrize("k", [10, 32])
 def test_golden_cknna(gold, ext, k):
     from umlh import align

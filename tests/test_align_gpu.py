@@ -52,6 +52,33 @@ def test_golden_neighbours_and_mutual_knn(gold, case):
         assert abs(m - float(gold[f"{case}/mknn64_k{k}"])) <= 1e-12 + und / n, (case, k, m)
 
 
+def edge_views(xa, xb, strided):
+    """The pair on the device: dense, or as row-strided views whose padding columns hold NaN."""
+    if not strided:
+        return dev(xa), dev(xb)
+    out = []
+    for x, pad in ((xa, 3), (xb, 2)):
+        w = torch.full((x.shape[0], x.shape[1] + pad), float("nan"), device=DEV)
+        w[:, :x.shape[1]] = dev(x)
+        out.append(w[:, :x.shape[1]])
+    return out
+
+
+@pytest.mark.parametrize("strided", [False, True])
+@pytest.mark.parametrize("n,da,db", R.TILE_EDGES)
+def test_tile_edge_cka(n, da, db, strided):
+    """test_golden_cka's bounds against float64 at the tile-edge shapes, for every way the rows are chunked."""
+    from umlh import align
+    xa, xb = R.tile_edge_pair(n, da, db)
+    a, b = edge_views(xa, xb, strided)
+    c64 = R.cka64(xa, xb)
+    for splits in (1, 3, 0):
+        out = align.cka_terms(a, b, splits=splits).cpu().numpy()
+        print(f"cka[{n},{da},{db},strided={strided},splits={splits}]: got {out!r} ref64 {c64!r}")
+        assert abs(out[0] - c64[0]) <= 1e-5, (splits, out[0], c64[0])
+        np.testing.assert_allclose(out[1:], c64[1:], rtol=1e-5)
+
+
 def _tie_features(n, d, seed):
     g = np.random.default_rng(seed)
     return g.integers(-2, 3, (n, d)).astype(np.float32)   # every score an exact small integer: many ties

@@ -83,6 +83,23 @@ def test_column_stats():
         assert st[0][3] == 2.5 and st[0][9] == -1000.25
 
 
+@pytest.mark.parametrize("n,d,ldx", [(5, 65, 70), (257, 1, 1)])
+def test_column_stats_edges(n, d, ldx):
+    """test_column_stats's bound where the column-sum body has little to hold on to: fewer rows than row lanes times chunks
+    with a second, one-column block of columns behind NaN padding; one column over more rows than chunks."""
+    from umlh import probe
+    rng = np.random.default_rng(100 * n + d)
+    x = (rng.standard_normal((n, d)) * rng.uniform(1e-3, 50, d) + rng.standard_normal(d) * 1000).astype(np.float32)
+    wide = torch.full((n, ldx), float("nan"), device=DEV)
+    wide[:, :d] = dev(x)
+    st = probe.column_stats(wide[:, :d]).cpu().numpy()
+    mean, sd = R.column_stats(x)
+    rel_m = np.abs(st[0] - mean) / np.maximum(np.abs(mean), sd)
+    rel_s = np.abs(st[1] - sd) / sd
+    print(f"column_stats[{n},{d},{ldx}]: max rel err mean {rel_m.max():.2e} std {rel_s.max():.2e}")
+    assert rel_m.max() <= 1e-12 and rel_s.max() <= 1e-12
+
+
 # ---- fit / predict / score on the recorded cases ----
 @pytest.mark.parametrize("tag", PROBE_CASES)
 def test_fit_reaches_the_optimum_closer_than_sklearn_did(tag):
@@ -126,6 +143,61 @@ def test_fit_reaches_the_optimum_closer_than_sklearn_did(tag):
         assert abs(score - s64) <= und / n + 1e-12
         assert abs(score - sref) <= (flips + und) / n + 1e-12
         assert int(pr.correct(dev(xh), dev(yh))) == int((pred == yh).sum())
+
+
+def tile_edge_problem(d, n=97, nh=200):
+    """n training and nh held-out rows of d features off the origin, labels from a noisy linear rule; seeded by d.  With this
+    seed base the float64 Newton iteration of _probe_ref.fit reaches max|gradient| <= 4e-12 in at most 9 steps for d = 31, 32,
+    33, both kinds, with and without statistics: no fit ends at an iteration cap."""
+    rng = np.random.default_rng(4400 + d)
+    x = (rng.standard_normal((n + nh, d)) * rng.uniform(0.3, 2.0, d) + 0.5 * rng.standard_normal(d)).astype(np.float32)
+    wt = rng.standard_normal(d) / np.sqrt(d)
+    y = ((x - x.mean(0)) @ wt + 0.7 * rng.standard_normal(n + nh) > 0).astype(np.int64)
+    return x[:n], y[:n], x[n:], y[n:]
+
+
+@pytest.mark.parametrize("kind", [R.LBFGS, R.LIBLINEAR])
+@pytest.mark.parametrize("with_stats", [False, True])
+@pytest.mark.parametrize("d", [31, 32, 33])
+def test_fit_and_score_at_tile_edges(monkeypatch, d, with_stats, kind):
+    """The assertions of test_fit_reaches_the_optimum_closer_than_sklearn_did that need no recorded sklearn run, at N = 97 and
+    D = d + 1 = 32, 33, 34 columns (one 32-column tile; the intercept alone in a second tile; two ragged tiles), against the
+    float64 Newton optimum.  The statistics are switched independently of the solver kind: fit() standardises exactly when
+    its kind is named 'liblinear', so the name is mapped to the solver under test."""
+    import umlh
+    from umlh import probe
+    x, y, xh, yh = tile_edge_problem(d)
+    stats = R.column_stats(x) if with_stats else None
+    w_star, it, mg = R.fit(x, y, kind, stats=stats)
+    assert mg <= 1e-10 and it < 200
+    name = "liblinear" if with_stats else "lbfgs"
+    monkeypatch.setitem(probe.KINDS, name, kind)
+    pr = umlh.LogisticProbe(name, keep_objectives=True).fit(dev(x), dev(y))
+    w, rec = coef(pr), pr.record()
+    obj = pr.objectives_.cpu().numpy()
+    print(f"d={d} stats={with_stats} {KIND[kind]}: record {rec} (float64 Newton: {it} iterations) "
+          f"delta = max|w_gpu - w*| = {np.abs(w - w_star).max():.3e}")
+    assert rec["converged"] in (1, 2) and rec["n_iter"] == len(obj) - 1 and pr.n_iter_ == rec["n_iter"]
+    assert np.all(np.diff(obj) <= 0) and np.isfinite(obj).all()
+    assert obj[-1] == rec["objective"]
+    xa = R._aug(R.standardise(x, stats))
+    assert abs(obj[-1] - R.objective(w, xa, y.astype(np.float64), kind)) <= 1e-6 * obj[-1]
+    if with_stats:
+        st = pr.stats_.cpu().numpy()
+        np.testing.assert_allclose(st[0], stats[0], rtol=1e-12, atol=1e-12)
+        np.testing.assert_allclose(st[1], stats[1], rtol=1e-12)
+    n = len(yh)
+    dec = pr.decision_function(dev(xh)).cpu().numpy()
+    pred = pr.predict(dev(xh)).cpu().numpy()
+    d64 = R.decision(w_star, xh, stats)
+    ok = R.decidable(w_star, xh, stats, w)
+    score, s64 = pr.score(dev(xh), dev(yh)), R.score(w_star, xh, yh, stats)
+    print(f"  held out: decidable {ok.mean():.4f} max|dec - dec64| {np.abs(dec - d64).max():.2e} score {score:.4f} score64 {s64:.4f}")
+    assert np.array_equal(pred[ok], (d64 > 0).astype(np.int64)[ok])
+    assert ok.mean() >= 0.99
+    assert score == float((pred == yh).sum()) / n
+    assert abs(score - s64) <= int((~ok).sum()) / n + 1e-12
+    assert int(pr.correct(dev(xh), dev(yh))) == int((pred == yh).sum())
 
 
 def test_fit_input_rules_and_errors():

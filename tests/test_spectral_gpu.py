@@ -90,6 +90,18 @@ def test_batch_of_three_and_the_utilis_drop_in(gold):
     assert torch.equal(umlh.effective_rank(wide[:, 5:125, 8:32]), torch.from_numpy(er).to(DEV))
 
 
+def test_batch_of_three_with_two_column_tiles():
+    """batch > 1 with d > 64: three tile pairs per matrix, each matrix with its own slabs; a batch is its matrices one by one."""
+    import umlh
+    a = np.stack([_gen(40, 65 + 100 * b)[:, :65] for b in range(3)])
+    x = torch.from_numpy(a).to(DEV)
+    er, sv = umlh.effective_rank(x, return_svdvals=True)
+    assert er.shape == (3,) and sv.shape == (3, 40) and torch.equal(sv, umlh.svdvals(x))
+    for b in range(3):
+        _check(f"batch 3 x 40x65 [{b}]", sv[b].cpu().numpy(), float(er[b]), R.svdvals64(a[b]), R.erank64(a[b]), _reference_errors(a[b]))
+        assert float(umlh.effective_rank(x[b])) == float(er[b])
+
+
 def test_fewer_rows_than_columns_returns_n_values(gold):
     """The d - n surplus eigenvalues of the Gram matrix (rounding noise around zero) must not reach the entropy."""
     import umlh

@@ -54,6 +54,31 @@ def test_value_against_the_closed_form(gold, case):
         np.testing.assert_allclose(evals[k], lam64, rtol=0, atol=64 * x.shape[1] * EPS * lam64[0])
 
 
+def test_value_with_two_by_three_cross_tiles(gold):
+    """Every recorded case has d_a <= 64: one row of 64-column tiles in the rectangular cross-Gram.  A planted case of the
+    recorded kind (R.gen_case) with d_a = 65, d_b = 130 has 2 x 3 of them.  Its gap sigma_(q+1) / sigma_q stays below the 0.2
+    that R.planted is built to keep clear of, like the recorded cases'; the bound is the smallest of theirs."""
+    import umlh
+    q = 4
+    a, b = R.gen_case("tiles", 150, 65, 130, q, 2)
+    gaps = [np.linalg.svd(R.standardise64(x), compute_uv=False) for x in (a, b)]
+    ratio = max(s[q] / s[q - 1] for s in gaps)
+    bound = min(float(np.abs(gold[f"{c}/ref32"] - float(gold[f"{c}/closed64"])).max()) for c in CASES)
+    rho64 = R.rho64(a, b, q)
+    val, rho, evals = umlh.svcca_terms(_dev(a), _dev(b), q)
+    rho, evals = rho.cpu().numpy(), evals.cpu().numpy()
+    err, rerr = abs(float(val) - float(rho64.mean())), float(np.abs(rho - rho64).max())
+    print(f"tiles: sigma_(q+1)/sigma_q {ratio:.3f} svcca {float(val):.15f} closed64 {rho64.mean():.15f} error {err:.3e}, "
+          f"max rho error {rerr:.3e} (bound {bound:.3e})")
+    assert ratio < 0.2
+    assert err <= bound and rerr <= bound
+    assert (np.diff(rho) <= 0).all() and rho.min() >= 0.0 and rho.max() <= 1.0
+    assert abs(float(val) - rho.mean()) <= 4 * EPS
+    for k, x in enumerate((a, b)):
+        lam64 = R.top_eigh(R.gram64(x, True), q)[0]
+        np.testing.assert_allclose(evals[k], lam64, rtol=0, atol=64 * x.shape[1] * EPS * lam64[0])
+
+
 def _eig_input(gold, name):
     if name == "gen512":
         return R.matrix_512(), 10

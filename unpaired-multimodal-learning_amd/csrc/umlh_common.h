@@ -41,6 +41,23 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
     for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
     return v;
 }
+// op(v) over the THREADS threads of a workgroup in a fixed halving tree through red[THREADS]: every thread calls, every
+// thread gets the result.  Back-to-back calls on the same red are safe (the leading barrier); sums, max and min alike.
+struct OpSum { template <class T> __device__ T operator()(T a, T b) const { return a + b; } };
+struct OpMax { template <class T> __device__ T operator()(T a, T b) const { return a > b ? a : b; } };
+struct OpMin { template <class T> __device__ T operator()(T a, T b) const { return a < b ? a : b; } };
+template <int THREADS, class T, class Op>
+__device__ __forceinline__ T block_reduce(T v, T* red, Op op) {
+    const int tid = threadIdx.x;
+    __syncthreads();
+    red[tid] = v;
+    __syncthreads();
+    for (int w = THREADS / 2; w > 0; w >>= 1) {
+        if (tid < w) red[tid] = op(red[tid], red[tid + w]);
+        __syncthreads();
+    }
+    return red[0];
+}
 #endif
 static inline int umlh_plain_stores() {      // (once per process)
     static const int v = env_int("UMLH_WT", 1) == 0;

@@ -5,16 +5,19 @@
 //   knn_merge      merges the chunks' lists of a row -> knn int32 [N, k] (+ scores fp32 [N, k])
 //   mutual_count   |knn_a(i) n knn_b(i)| per row, integer block sums
 //   mutual_final   fixed-order sum of the block counts -> mean as double
-//   cka_colsum     column sums of A | B in double, per row chunk
+//   cka_colsum     column sums of A | B in double, per row chunk (colsum_chunk, umlh_gram.h)
 //   cka_cross      the centred cross products Ac^T Bc, Ac^T Ac, Bc^T Bc as 32x32 tiles on the f32 MFMA, per row chunk
-//                  (centred on load: never X^T Y - N mu mu^T)
+//                  (centred on load: never X^T Y - N mu mu^T): mfma32_rows_tile of umlh_gram.h on the centring loader
 //   cka_tile_sq    each finished tile (its row chunks summed in double, fixed order), squared and summed
 //   cka_final      fixed-order Frobenius sums -> {cka, hsic_kl, hsic_kk, hsic_ll}
 //
 // Nothing here forms an N x N array, and no reduction uses a float atomic: every result is bitwise reproducible for a
 // given `splits`.  knn is bitwise independent of `splits` as well: column chunks start on 256-column tile boundaries,
 // every score is the same fma chain wherever it is computed, and the kept lists are exact top-k under a strict order.
+// The tile, column-sum and chunk-sum bodies are those of umlh_gram.h (shared with umlh_kernels_probe.hip,
+// umlh_kernels_align_ext.hip and umlh_kernels_spectral.hip), the block reductions block_reduce of umlh_common.h.
 #include "umlh_common.h"
+#include "umlh_gram.h"
 #include "umlh_launch.h"
 #include "umlh_topk.h"
 #include <climits>
@@ -65,13 +68,8 @@ __global__ __launch_bounds__(256) void mutual_count(const int* __restrict__ ka, 
             c += hit;
         }
     }
-    red[tid] = c;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (tid < w) red[tid] += red[tid + w];
-        __syncthreads();
-    }
-    if (tid == 0) partial[blockIdx.x] = red[0];
+    c = block_reduce<256>(c, red, OpSum());
+    if (tid == 0) partial[blockIdx.x] = c;
 }
 
 __global__ __launch_bounds__(256) void mutual_final(const long long* __restrict__ partial, int nblocks, int n, int topk,
@@ -80,30 +78,18 @@ __global__ __launch_bounds__(256) void mutual_final(const long long* __restrict_
     const int tid = threadIdx.x;
     long long c = 0;
     for (int b = tid; b < nblocks; b += 256) c += partial[b];
-    red[tid] = c;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (tid < w) red[tid] += red[tid + w];
-        __syncthreads();
-    }
-    if (tid == 0) out[0] = (double)red[0] / ((double)n * (double)topk);
+    c = block_reduce<256>(c, red, OpSum());
+    if (tid == 0) out[0] = (double)c / ((double)n * (double)topk);
 }
 
-// Column c of A | B (c < da: A), rows of chunk blockIdx.y; 64 columns x 4 row lanes, in double.
+// Column c of A | B (c < da: A), rows of chunk blockIdx.y, in double (colsum_chunk, umlh_gram.h).
 __global__ __launch_bounds__(256) void cka_colsum(const float* __restrict__ a, int lda, int da, const float* __restrict__ b, int ldb,
                                                   int db, int n, int chunks, double* __restrict__ partial) {
-    __shared__ double red[256];
-    const int tid = threadIdx.x, cl = tid & 63, rl = tid >> 6, c = blockIdx.x * 64 + cl, dt = da + db;
-    const long long rs = (long long)blockIdx.y * n / chunks, re = (long long)(blockIdx.y + 1) * n / chunks;
-    double s = 0.0;
-    if (c < dt) {
+    colsum_chunk([=](int c) {
         const float* p = c < da ? a + c : b + (c - da);
         const long long ld = c < da ? lda : ldb;
-        for (long long r = rs + rl; r < re; r += 4) s += (double)p[r * ld];
-    }
-    red[tid] = s;
-    __syncthreads();
-    if (rl == 0 && c < dt) partial[(long long)blockIdx.y * dt + c] = ((red[cl] + red[64 + cl]) + red[128 + cl]) + red[192 + cl];
+        return [=](long long r) { return (double)p[r * ld]; };
+    }, da + db, n, chunks, partial);
 }
 
 struct CkaArgs {
@@ -117,10 +103,9 @@ struct CkaArgs {
 };
 
 // Tile blockIdx.x of the three products (A^T B: ta*tb tiles, A^T A: ta*ta, B^T B: tb*tb), rows of chunk blockIdx.y (whole
-// 32-row blocks).  Wave w takes the 8-row groups w, w+4, ... of the chunk; lane half h supplies rows 4h + s to MFMA step s.
+// 32-row blocks): mfma32_rows_tile (umlh_gram.h) on mean-centred columns; lane (h, c32) loads column c32 of the tile, rows 4h ..
 __global__ __launch_bounds__(256) void cka_cross(CkaArgs g) {
-    __shared__ float red[4][1024];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, c32 = lane & 31;
+    const int lane = threadIdx.x & 63, h = lane >> 5, c32 = lane & 31;
     int t = blockIdx.x, ti, tj;
     const float *X, *Y;
     int ldx, ldy, dx, dy, ox, oy;            // ox, oy: offsets of X's / Y's columns in the column sums
@@ -137,43 +122,21 @@ __global__ __launch_bounds__(256) void cka_cross(CkaArgs g) {
     float mean;
     {
         const int col = h ? cy : cx, lim = h ? dy : dx, off = h ? oy : ox;
-        double s = 0.0;
-        if (col < lim)
-            for (int q = 0; q < g.sum_chunks; ++q) s += g.colsum[(long long)q * dt + off + col];
-        mean = (float)(s / (double)g.n);
+        mean = (float)((col < lim ? chunk_total(g.colsum, g.sum_chunks, dt, off + col) : 0.0) / (double)g.n);
     }
     const float mx = __shfl(mean, c32), my = __shfl(mean, 32 + c32);
     const bool vx = cx < dx, vy = cy < dy;
-    const int nb = (g.n + 31) / 32;
-    const long long rs = (long long)((long long)blockIdx.y * nb / g.rchunks) * 32;
-    const long long re = min((long long)g.n, (long long)((long long)(blockIdx.y + 1) * nb / g.rchunks) * 32);
-    auto load = [&](long long base, float* xv, float* yv) {
+    long long rs, re;
+    chunk_rows32(g.n, blockIdx.y, g.rchunks, rs, re);
+    mfma32_rows_tile<true>([&](long long r0, float* xv, float* yv) {
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-            const long long r = base + 4 * h + s;
+            const long long r = r0 + s;
             const bool vr = r < re;
             xv[s] = (vr && vx) ? X[r * ldx + cx] - mx : 0.f;
             yv[s] = (vr && vy) ? Y[r * ldy + cy] - my : 0.f;
         }
-    };
-    f32x16 acc = {};
-    long long base = rs + wave * 8;
-    float xv[4], yv[4];
-    load(base, xv, yv);
-    for (; base < re; base += 32) {
-        float xn[4], yn[4];
-        load(base + 32, xn, yn);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xv[s], yv[s], acc, 0, 0, 0);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) { xv[s] = xn[s]; yv[s] = yn[s]; }
-    }
-#pragma unroll
-    for (int q = 0; q < 16; ++q) red[wave][(8 * (q >> 2) + 4 * h + (q & 3)) * 32 + c32] = acc[q];
-    __syncthreads();
-    double* out = g.cross + ((long long)blockIdx.x * g.rchunks + blockIdx.y) * 1024;
-    for (int e = tid; e < 1024; e += 256)
-        out[e] = (((double)red[0][e] + (double)red[1][e]) + (double)red[2][e]) + (double)red[3][e];
+    }, rs, re, g.cross + ((long long)blockIdx.x * g.rchunks + blockIdx.y) * 1024);
 }
 
 __global__ __launch_bounds__(256) void cka_tile_sq(const double* __restrict__ cross, int rchunks, double* __restrict__ tile_sq) {
@@ -182,35 +145,22 @@ __global__ __launch_bounds__(256) void cka_tile_sq(const double* __restrict__ cr
     const double* p = cross + (long long)blockIdx.x * rchunks * 1024;
     double sq = 0.0;
     for (int e = tid; e < 1024; e += 256) {
-        double v = 0.0;
-        for (int r = 0; r < rchunks; ++r) v += p[(long long)r * 1024 + e];
+        const double v = slab_total(p, rchunks, e);
         sq += v * v;
     }
-    red[tid] = sq;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (tid < w) red[tid] += red[tid + w];
-        __syncthreads();
-    }
-    if (tid == 0) tile_sq[blockIdx.x] = red[0];
+    sq = block_reduce<256>(sq, red, OpSum());
+    if (tid == 0) tile_sq[blockIdx.x] = sq;
 }
 
 __global__ __launch_bounds__(256) void cka_final(const double* __restrict__ tile_sq, int ta, int tb, double* __restrict__ out4) {
     __shared__ double red[256];
-    __shared__ double hs[3];
+    double hs[3];
     const int tid = threadIdx.x;
     const int lo[3] = {0, ta * tb, ta * tb + ta * ta}, hi[3] = {ta * tb, ta * tb + ta * ta, ta * tb + ta * ta + tb * tb};
     for (int p = 0; p < 3; ++p) {
         double s = 0.0;
         for (int t = lo[p] + tid; t < hi[p]; t += 256) s += tile_sq[t];
-        red[tid] = s;
-        __syncthreads();
-        for (int w = 128; w > 0; w >>= 1) {
-            if (tid < w) red[tid] += red[tid + w];
-            __syncthreads();
-        }
-        if (tid == 0) hs[p] = red[0];
-        __syncthreads();
+        hs[p] = block_reduce<256>(s, red, OpSum());
     }
     if (tid == 0) {   // metrics.py:116: hsic_kl / (sqrt(hsic_kk * hsic_ll) + 1e-6)
         out4[0] = hs[0] / (sqrt(hs[1] * hs[2]) + 1e-6);

@@ -3,6 +3,7 @@
 //
 //   ext_means        column means of A | B as fp32, from cka_colsum's chunk partials (the value cka_cross centres with)
 //   ext_center_sums  column sums of the ROUNDED centred values (not exactly zero in fp32), per row chunk, in double
+//                    (colsum_chunk of umlh_gram.h on the fl(x - mean) transform)
 //   ext_colfin       fixed-order sum of those chunks
 //   ext_rows<0>      per row |x_i|^2, |y_i|^2 and (K~1)_i = x_i . (sum_j x_j) - |x_i|^2 (fp32 products, double sums) -> block
 //                    partials of the twelve HSIC sums;  ext_rows<1>: only the squared norms, as fp32, for the RBF distances
@@ -20,6 +21,7 @@
 // The twelve HSIC sums are, for each of (K,L), (K,K), (L,L): sum M~ . P~^T, 1^T M~ 1, 1^T P~ 1, 1^T M~ P~ 1.
 // Nothing here forms an N x N array and no reduction uses a float atomic: results are bitwise reproducible for a given `splits`.
 #include "umlh_common.h"
+#include "umlh_gram.h"
 #include "umlh_launch.h"
 #include "umlh_topk.h"
 
@@ -31,19 +33,6 @@ constexpr int LS_LD = LS_KMAX + 1;
 
 inline int up4(int d) { return (d + 3) / 4 * 4; }
 
-// Sum of v over the 256 threads in a fixed tree (every thread calls; every thread gets the sum).
-__device__ __forceinline__ double block_sum(double v, double* red) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-    red[tid] = v;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (tid < w) red[tid] += red[tid + w];
-        __syncthreads();
-    }
-    return red[0];
-}
-
 // mean[0 .. da4) for A, mean[da4 .. da4 + db4) for B (d rounded up to 4, zero past d): (float)(sum / n) as cka_cross forms it.
 __global__ __launch_bounds__(256) void ext_means(const double* __restrict__ colsum, int chunks, int da, int db, int n,
                                                  float* __restrict__ mean) {
@@ -52,37 +41,25 @@ __global__ __launch_bounds__(256) void ext_means(const double* __restrict__ cols
     int c = -1;
     if (idx < da) c = idx;
     else if (idx >= da4 && idx - da4 < db) c = da + idx - da4;
-    double s = 0.0;
-    if (c >= 0)
-        for (int q = 0; q < chunks; ++q) s += colsum[(long long)q * dt + c];
-    mean[idx] = c >= 0 ? (float)(s / (double)n) : 0.f;
+    mean[idx] = c >= 0 ? (float)(chunk_total(colsum, chunks, dt, c) / (double)n) : 0.f;
 }
 
-// Column c of A | B, rows of chunk blockIdx.y: sum of fl(x - mean) in double; 64 columns x 4 row lanes (as cka_colsum).
+// Column c of A | B, rows of chunk blockIdx.y: sum of fl(x - mean) in double (colsum_chunk, umlh_gram.h, as cka_colsum).
 __global__ __launch_bounds__(256) void ext_center_sums(const float* __restrict__ a, int lda, int da, const float* __restrict__ b,
                                                        int ldb, int db, int n, int chunks, const float* __restrict__ mean,
                                                        double* __restrict__ partial) {
-    __shared__ double red[256];
-    const int tid = threadIdx.x, cl = tid & 63, rl = tid >> 6, c = blockIdx.x * 64 + cl, dt = da + db, da4 = (da + 3) / 4 * 4;
-    const long long rs = (long long)blockIdx.y * n / chunks, re = (long long)(blockIdx.y + 1) * n / chunks;
-    double s = 0.0;
-    if (c < dt) {
+    const int da4 = (da + 3) / 4 * 4;
+    colsum_chunk([=](int c) {
         const float* p = c < da ? a + c : b + (c - da);
         const long long ld = c < da ? lda : ldb;
         const float m = c < da ? mean[c] : mean[da4 + c - da];
-        for (long long r = rs + rl; r < re; r += 4) s += (double)(p[r * ld] - m);
-    }
-    red[tid] = s;
-    __syncthreads();
-    if (rl == 0 && c < dt) partial[(long long)blockIdx.y * dt + c] = ((red[cl] + red[64 + cl]) + red[128 + cl]) + red[192 + cl];
+        return [=](long long r) { return (double)(p[r * ld] - m); };
+    }, da + db, n, chunks, partial);
 }
 
 __global__ __launch_bounds__(256) void ext_colfin(const double* __restrict__ partial, int chunks, int dt, double* __restrict__ csum) {
     const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= dt) return;
-    double s = 0.0;
-    for (int q = 0; q < chunks; ++q) s += partial[(long long)q * dt + c];
-    csum[c] = s;
+    if (c < dt) csum[c] = chunk_total(partial, chunks, dt, c);
 }
 
 struct RowArgs {
@@ -151,7 +128,7 @@ __global__ __launch_bounds__(256) void ext_rows(RowArgs g) {
     }
 #pragma unroll
     for (int s = 0; s < NSUM; ++s) {
-        const double t = block_sum(v[s], red);
+        const double t = block_reduce<256>(v[s], red, OpSum());
         if (tid == 0) g.part[(long long)blockIdx.x * NSUM + s] = t;
     }
 }
@@ -275,7 +252,7 @@ __global__ __launch_bounds__(256) void rbf_tiles(RbfArgs g) {
         g.rowpart[(((long long)split * g.strips) * TK_ROWS + r0 + i) * 2 + v] = ((rs[0][i][v] + rs[1][i][v]) + rs[2][i][v]) + rs[3][i][v];
     }
     const long long nwg = (long long)g.splits * g.strips, wg = (long long)split * g.strips + blockIdx.x;
-    const double pkl = block_sum(skl, red), pkk = block_sum(skk, red), pll = block_sum(sll, red);
+    const double pkl = block_reduce<256>(skl, red, OpSum()), pkk = block_reduce<256>(skk, red, OpSum()), pll = block_reduce<256>(sll, red, OpSum());
     if (tid == 0) {
         g.pair[wg] = pkl;
         g.pair[nwg + wg] = pkk;
@@ -297,7 +274,7 @@ __global__ __launch_bounds__(256) void rbf_rows(const double* __restrict__ rowpa
     const double v[NSUM] = {0.0, k1, l1, k1 * l1, 0.0, k1, k1, k1 * k1, 0.0, l1, l1, l1 * l1};
 #pragma unroll
     for (int s = 0; s < NSUM; ++s) {
-        const double t = block_sum(v[s], red);
+        const double t = block_reduce<256>(v[s], red, OpSum());
         if (tid == 0) part[(long long)blockIdx.x * NSUM + s] = t;
     }
 }
@@ -370,7 +347,7 @@ __global__ __launch_bounds__(256) void cknna_rows(const int* __restrict__ ka, co
     }
 #pragma unroll
     for (int s = 0; s < NSUM; ++s) {
-        const double t = block_sum(v[s], red);
+        const double t = block_reduce<256>(v[s], red, OpSum());
         if (tid == 0) part[(long long)blockIdx.x * NSUM + s] = t;
     }
 }
@@ -388,7 +365,7 @@ __global__ __launch_bounds__(256) void ext_final(const double* __restrict__ seg,
         for (long long b = tid; b < nblocks; b += 256) acc += part[b * NSUM + s];
         if ((s & 3) == 0)
             for (long long e = tid; e < len[s >> 2]; e += 256) acc += seg[lo[s >> 2] + e];
-        const double t = block_sum(acc, red);
+        const double t = block_reduce<256>(acc, red, OpSum());
         if (tid == 0) tot[s] = t;
     }
     if (tid == 0) {
@@ -463,15 +440,9 @@ __global__ __launch_bounds__(256) void list_final(const long long* __restrict__ 
     for (int s = 0; s < 3; ++s) {
         long long c = 0;
         for (long long b = tid; b < nblocks; b += 256) c += part[b * 3 + s];
-        __syncthreads();
-        red[tid] = c;
-        __syncthreads();
-        for (int w = 128; w > 0; w >>= 1) {
-            if (tid < w) red[tid] += red[tid + w];
-            __syncthreads();
-        }
+        c = block_reduce<256>(c, red, OpSum());
         if (tid == 0) {
-            const double mean = (double)red[0] / (double)n;
+            const double mean = (double)c / (double)n;
             out3[s] = s < 2 ? mean : 1.0 - mean / (double)topk;   // metrics.py:51, :91 (not divided by k), :176
         }
     }

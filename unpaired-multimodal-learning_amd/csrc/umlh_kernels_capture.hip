@@ -43,13 +43,7 @@ __global__ __launch_bounds__(256) void cap_compact(const V* __restrict__ z, int 
     if (t0 >= mine && !last) return;                       // uniform over the workgroup
     long long s = 0;
     for (int i = tid; i < b; i += 256) s += cap_rows(lengths, i, T, drop_last);
-    red[tid] = s;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (tid < w) red[tid] += red[tid + w];
-        __syncthreads();
-    }
-    const long long off = red[0];
+    const long long off = block_reduce<256>(s, red, OpSum());
     if (last && tid == 0) rows_total[0] = off + mine;
     long long nrows = mine - t0;
     if (nrows <= 0) return;

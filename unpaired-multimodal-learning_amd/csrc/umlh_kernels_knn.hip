@@ -136,13 +136,8 @@ __global__ __launch_bounds__(256) void kp_vote(const int* __restrict__ idx, int 
         if (y) hit = (y[row] == best);
     }
     if (correct) {
-        red[tid] = hit;
-        __syncthreads();
-        for (int w = 128; w > 0; w >>= 1) {
-            if (tid < w) red[tid] += red[tid + w];
-            __syncthreads();
-        }
-        if (tid == 0 && red[0]) atomicAdd(correct, (unsigned long long)red[0]);      // integer: exact in any order
+        hit = block_reduce<256>(hit, red, OpSum());
+        if (tid == 0 && hit) atomicAdd(correct, (unsigned long long)hit);            // integer: exact in any order
     }
 }
 

@@ -3,12 +3,14 @@
 //
 //   pb_masked_mean   out[b, :] = sum_{t < min(len_b, T)} z[b, t, :] / min(len_b, T): one fp32 chain per element, t ascending
 //   pb_colsum        column sums (pass 0) / sums of squared deviations from the mean (pass 1) in double, per row chunk
+//                    (colsum_chunk of umlh_gram.h)
 //   pb_stats_final   fixed-order sum of the chunks -> mean | scale (population std, or 1 below 10 eps)
 //   pb_init          w = 0, z = 0, f = N log 2
 //   pb_residual      z += t_prev * u;  p = sigmoid(z);  r = p - y;  s = p (1 - p)
 //   pb_grad          X~^T r per row chunk: 32-column tiles on v_mfma_f32_32x32x2_f32, flushed to double every 64 rows
-//   pb_gram          X~^T diag(s) X~ per row chunk: upper-triangle 32x32 tiles on the f32 MFMA
-//   pb_hess          chunks summed in double (fixed order) + the ridge -> H, mirrored
+//   pb_gram          X~^T diag(s) X~ per row chunk: upper-triangle 32x32 tiles on the f32 MFMA (mfma32_rows_tile of umlh_gram.h,
+//                    the tile body of cka_cross, on the standardising loader)
+//   pb_hess          chunks summed in double (fixed order, slab_total) + the ridge -> H, mirrored
 //   pb_solve         g = sum of chunks + R w in double (fixed order); stop tests; Cholesky of H; delta = -H^-1 g
 //   pb_matvec        u = X~ delta on the f32 MFMA (also the decision values and the integer hit count of the score)
 //   pb_linesearch    sum_i log(1 + exp(-t_i (z_i + a u_i))) for a = 1, 1/2, ..., 2^-11, in double, per block
@@ -22,6 +24,7 @@
 // `halt` is set every remaining launch returns at its first instruction.  Nothing uses a float atomic, a grid barrier or
 // a host read.
 #include "umlh_common.h"
+#include "umlh_gram.h"
 #include "umlh_launch.h"
 #include <cfloat>
 #include <cmath>
@@ -111,28 +114,20 @@ __global__ __launch_bounds__(256) void pb_masked_mean(const float* __restrict__ 
 // ---- StandardScaler statistics ----
 __global__ __launch_bounds__(256) void pb_colsum(const float* __restrict__ x, long long n, int d, int ldx, int chunks,
                                                  const double* __restrict__ mean, double* __restrict__ partial) {
-    __shared__ double red[256];
-    const int tid = threadIdx.x, cl = tid & 63, rl = tid >> 6, c = blockIdx.x * 64 + cl;
-    const long long rs = (long long)blockIdx.y * n / chunks, re = (long long)(blockIdx.y + 1) * n / chunks;
-    double s = 0.0;
-    if (c < d) {
+    colsum_chunk([=](int c) {
         const double m = mean ? mean[c] : 0.0;
-        for (long long r = rs + rl; r < re; r += 4) {
+        return [=](long long r) {
             const double v = (double)x[r * ldx + c] - m;
-            s += mean ? v * v : v;
-        }
-    }
-    red[tid] = s;
-    __syncthreads();
-    if (rl == 0 && c < d) partial[(long long)blockIdx.y * d + c] = ((red[cl] + red[64 + cl]) + red[128 + cl]) + red[192 + cl];
+            return mean ? v * v : v;
+        };
+    }, d, n, chunks, partial);
 }
 
 __global__ __launch_bounds__(256) void pb_stats_final(const double* __restrict__ partial, long long n, int d, int chunks, int pass,
                                                       double* __restrict__ stats) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= d) return;
-    double s = 0.0;
-    for (int q = 0; q < chunks; ++q) s += partial[(long long)q * d + c];
+    const double s = chunk_total(partial, chunks, d, c);
     if (pass == 0) {
         stats[c] = s / (double)n;
     } else {
@@ -228,58 +223,49 @@ __global__ __launch_bounds__(256) void pb_grad(ProbeArgs g) {
         g.gpart[(long long)blockIdx.y * g.D + blockIdx.x * 32 + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
 }
 
-// Upper-triangle tile blockIdx.x = (ti <= tj) of X~^T diag(s) X~, rows of chunk blockIdx.y (whole 32-row blocks).
+// Upper-triangle tile blockIdx.x = (ti <= tj) of X~^T diag(s) X~, rows of chunk blockIdx.y (whole 32-row blocks):
+// mfma32_rows_tile (umlh_gram.h) on a = x~ s, b = x~; lane (h, c32) loads column c32 of the tile, rows 4h ..
 __global__ __launch_bounds__(256) void pb_gram(ProbeArgs g) {
     if (g.st->halt) return;
-    __shared__ float red[4][1024];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, c32 = lane & 31;
-    int t = blockIdx.x, ti = 0;
-    while (t >= g.nt - ti) { t -= g.nt - ti; ++ti; }
-    const int tj = ti + t;
+    const int lane = threadIdx.x & 63, c32 = lane & 31;
+    int ti, tj;
+    tri_tile(blockIdx.x, g.nt, ti, tj);
     const int cx = ti * 32 + c32, cy = tj * 32 + c32;
     const bool vx = cx < g.D, vy = cy < g.D, fx = cx < g.d, fy = cy < g.d;
     const bool st = g.stats != nullptr;
     const double mx = (st && fx) ? g.stats[cx] : 0.0, ix = (st && fx) ? 1.0 / g.stats[g.d + cx] : 1.0;
     const double my = (st && fy) ? g.stats[cy] : 0.0, iy = (st && fy) ? 1.0 / g.stats[g.d + cy] : 1.0;
-    const long long nb = (g.n + 31) / 32;
-    const long long rs = (long long)blockIdx.y * nb / g.rchunks * 32;
-    long long re = (long long)(blockIdx.y + 1) * nb / g.rchunks * 32;
-    if (re > g.n) re = g.n;
-    f32x16 acc = {};
-    for (long long base = rs + wave * 8; base < re; base += 32) {
-        float a[4], b[4];
+    long long rs, re;
+    chunk_rows32(g.n, blockIdx.y, g.rchunks, rs, re);
+    const auto x_tilde = [&](long long r, int c, bool feat, double m, double inv) {      // column c <= d of x~ at row r < n
+        if (!feat) return 1.f;
+        float v = g.x[r * g.ldx + c];
+        if (st) {
+            asm volatile("");                                      // keeps this a (uniform) branch: no fp64 work without statistics
+            v = (float)(((double)v - m) * inv);
+        }
+        return v;
+    };
+    mfma32_rows_tile<false>([&](long long r0, float* a, float* b) {
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-            const long long r = base + 4 * h + s;
+            const long long r = r0 + s;
             const bool vr = r < re;
-            float xa = 0.f, xb = 0.f;
-            if (vr && vx) xa = fx ? (st ? (float)(((double)g.x[r * g.ldx + cx] - mx) * ix) : g.x[r * g.ldx + cx]) : 1.f;
-            if (vr && vy) xb = fy ? (st ? (float)(((double)g.x[r * g.ldx + cy] - my) * iy) : g.x[r * g.ldx + cy]) : 1.f;
-            a[s] = vr ? xa * g.s[r] : 0.f;
-            b[s] = xb;
+            a[s] = vr ? ((vx ? x_tilde(r, cx, fx, mx, ix) : 0.f) * g.s[r]) : 0.f;
+            b[s] = (vr && vy) ? x_tilde(r, cy, fy, my, iy) : 0.f;
         }
-#pragma unroll
-        for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], b[s], acc, 0, 0, 0);
-    }
-#pragma unroll
-    for (int q = 0; q < 16; ++q) red[wave][(8 * (q >> 2) + 4 * h + (q & 3)) * 32 + c32] = acc[q];
-    __syncthreads();
-    double* out = g.cross + ((long long)blockIdx.x * g.rchunks + blockIdx.y) * 1024;
-    for (int e = tid; e < 1024; e += 256)
-        out[e] = (((double)red[0][e] + (double)red[1][e]) + (double)red[2][e]) + (double)red[3][e];
+    }, rs, re, g.cross + ((long long)blockIdx.x * g.rchunks + blockIdx.y) * 1024);
 }
 
 __global__ __launch_bounds__(256) void pb_hess(ProbeArgs g) {
     if (g.st->halt) return;
-    int t = blockIdx.x, ti = 0;
-    while (t >= g.nt - ti) { t -= g.nt - ti; ++ti; }
-    const int tj = ti + t;
+    int ti, tj;
+    tri_tile(blockIdx.x, g.nt, ti, tj);
     const double* p = g.cross + (long long)blockIdx.x * g.rchunks * 1024;
     for (int e = threadIdx.x; e < 1024; e += 256) {
         const int i = e >> 5, j = e & 31, ci = ti * 32 + i, cj = tj * 32 + j;
         if (ci >= g.D || cj >= g.D || ci > cj) continue;         // a diagonal tile keeps its upper half: H is symmetric by construction
-        double v = 0.0;
-        for (int r = 0; r < g.rchunks; ++r) v += p[(long long)r * 1024 + e];
+        double v = slab_total(p, g.rchunks, e);
         if (ci == cj) v += pb_ridge(g, ci);
         g.H[(long long)ci * g.D + cj] = v;
         g.H[(long long)cj * g.D + ci] = v;
@@ -301,20 +287,13 @@ __global__ __launch_bounds__(1024) void pb_solve(ProbeArgs g, int last) {
     const int tid = threadIdx.x, D = g.D;
     double mg = 0.0;
     for (int c = tid; c < D; c += 1024) {
-        double s = 0.0;
-        for (int q = 0; q < g.gchunks; ++q) s += g.gpart[(long long)q * D + c];
+        double s = chunk_total(g.gpart, g.gchunks, D, c);
         s += pb_ridge(g, c) * g.w[c];
         gv[c] = s;
         mg = pb_nanmax(fabs(s), mg);
     }
-    red[tid] = mg;
-    __syncthreads();
-    for (int w = 512; w > 0; w >>= 1) {
-        if (tid < w) red[tid] = pb_nanmax(red[tid], red[tid + w]);
-        __syncthreads();
-    }
+    mg = block_reduce<1024>(mg, red, [](double a, double b) { return pb_nanmax(a, b); });
     if (tid == 0) {
-        mg = red[0];
         st->max_grad = mg;
         stop = 0;
         if (mg != mg) { pb_record(g, 0); stop = 1; }
@@ -381,14 +360,8 @@ __global__ __launch_bounds__(1024) void pb_solve(ProbeArgs g, int last) {
         g.delta[c] = yv[c];
         gd += gv[c] * yv[c];
     }
-    red[tid] = gd;
-    __syncthreads();
-    for (int w = 512; w > 0; w >>= 1) {
-        if (tid < w) red[tid] += red[tid + w];
-        __syncthreads();
-    }
+    gd = block_reduce<1024>(gd, red, OpSum());
     if (tid == 0) {
-        gd = red[0];
         st->gd = gd;
         const double scale = fabs(st->f) > 1.0 ? fabs(st->f) : 1.0;
         if (!(gd < 0.0)) pb_record(g, gd == 0.0 ? 2 : 0);          // no descent direction: only the exact optimum counts
@@ -528,7 +501,7 @@ ProbePlan probe_plan(long long n, int d, int max_iter) {
     p.eblocks = (int)std::min<long long>(PB_EBLOCKS, (n + 255) / 256);
     p.gchunks = (int)std::min<long long>(PB_GCHUNKS, (n + 255) / 256);
     p.nt = (D + 31) / 32;
-    p.tiles = p.nt * (p.nt + 1) / 2;
+    p.tiles = tri_tiles(p.nt);
     const long long nb = (n + 31) / 32;
     p.rchunks = (int)std::max<long long>(1, std::min<long long>(PB_TARGET_WG / p.tiles, (nb + 3) / 4));
     unsigned long long o = 0;

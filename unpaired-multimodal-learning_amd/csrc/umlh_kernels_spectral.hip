@@ -3,15 +3,17 @@
 // numbers is exact there), which is what makes the route as accurate as an fp32 SVD: see DESIGN section 12.
 //
 //   spectral_gram    a 64 x 64 tile of the upper triangle of G = sum over valid rows of a a^T for one row chunk: fp32 rows
-//                    staged through LDS, converted on use, 4 x 4 fp64 FMA accumulators per thread, rows ascending.  Invalid
-//                    rows (the sequence predicate t < clamp(len_b, 0, T) - drop_last) are staged as zeros: no compaction.
-//   spectral_reduce  G[i][j] = G[j][i] = sum of the chunk slabs in chunk order
+//                    staged through LDS, converted on use, 4 x 4 fp64 FMA accumulators per thread, rows ascending (gram64_tile
+//                    of umlh_gram.h on the RowMap loader).  Invalid rows (the sequence predicate t < clamp(len_b, 0, T) -
+//                    drop_last) are staged as zeros: no compaction.
+//   spectral_reduce  G[i][j] = G[j][i] = sum of the chunk slabs in chunk order (slab_sum<true>)
 //   spectral_eig     one workgroup per matrix: scale by a power of two, Householder tridiagonalisation in place (global, L2
 //                    resident), bisection on Sturm counts with one eigenvalue per thread and a fixed iteration count, then the
 //                    top min(rows, d) values -> sigma = sqrt(max(lambda, 0)), p = sigma / sum sigma, exp(-sum p log(p + eps))
 //
 // Principal subspaces and SVCCA (MultiBench/metrics.py:129-160 in closed form) on the same machinery:
 //   subspace_gram         the two-operand form of spectral_gram on centred columns: Gc = (A - mu)^T (A - mu) or the cross-Gram
+//                         (the same gram64_tile, fp64 staging); subspace_reduce_rect: its chunk sum (slab_sum<false>)
 //   subspace_standardise  D Gc D with D_j = 1 / (std_j + 1e-8)
 //   subspace_eig          spectral_eig's tridiagonalisation with the reflectors kept, bisection, inverse iteration for the q
 //                         largest eigenvalues, the reflectors applied in reverse: top-q eigenpairs
@@ -21,13 +23,12 @@
 #include <cfloat>
 
 #include "umlh_common.h"
+#include "umlh_gram.h"
 #include "umlh_launch.h"
 
 namespace {
 
 constexpr int SP_MAX_D = 512;
-constexpr int SP_TILE = 64;               // Gram tile edge
-constexpr int SP_KR = 32;                 // rows staged per step
 constexpr int SP_CHUNK_ROWS = 256;        // target rows of a chunk
 constexpr int SP_MAX_CHUNKS = 128;        // chunks over all matrices of a call (at least one per matrix)
 constexpr int SP_EIG_THREADS = 1024;
@@ -51,79 +52,31 @@ __device__ __forceinline__ int valid_len(const RowMap& m, unsigned outer) {
     return (int)l - m.drop_last;
 }
 
+// gram64_tile (umlh_gram.h) on the RowMap loader: upper-triangular tile pair blockIdx.x, row chunk blockIdx.y, matrix blockIdx.z
 __global__ __launch_bounds__(256) void spectral_gram(RowMap map, int d, int chunks, double* __restrict__ slabs) {
-    __shared__ __align__(16) float sa[SP_KR][SP_TILE];
-    __shared__ __align__(16) float sb[SP_KR][SP_TILE];
-    // upper-triangular tile pair (ti <= tj) of blockIdx.x
-    const int nt = (d + SP_TILE - 1) / SP_TILE;
-    int ti = 0, rem = blockIdx.x;
-    while (rem >= nt - ti) { rem -= nt - ti; ++ti; }
-    const int tj = ti + rem;
-    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4, lc = tid & 63, lr = tid >> 6;
+    int ti, tj;
+    tri_tile(blockIdx.x, (d + G64_TILE - 1) / G64_TILE, ti, tj);
     const unsigned chunk = blockIdx.y, mat = blockIdx.z;
     const unsigned r0 = (unsigned)((unsigned long long)map.rows * chunk / chunks);
     const unsigned r1 = (unsigned)((unsigned long long)map.rows * (chunk + 1) / chunks);
     const float* base = map.a + (long long)mat * map.sm;
-    const int ca = ti * SP_TILE + lc, cb = tj * SP_TILE + lc;
-    double acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = 0.0;
-    for (unsigned rs = r0; rs < r1; rs += SP_KR) {
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < SP_KR / 4; ++q) {
-            const unsigned r = rs + lr + 4 * q;
-            float va = 0.f, vb = 0.f;
-            if (r < r1) {
-                const unsigned outer = r / map.period, inner = r - outer * map.period;
-                if ((int)inner < valid_len(map, outer)) {
-                    const float* row = base + (long long)outer * map.so + (long long)inner * map.si;
-                    if (ca < d) va = row[ca];
-                    if (cb < d) vb = row[cb];
-                }
+    const auto cols = [&](int ca, int cb) {
+        return [&map, base, ca, cb, d](unsigned r, float& va, float& vb) {
+            const unsigned outer = r / map.period, inner = r - outer * map.period;
+            if ((int)inner < valid_len(map, outer)) {
+                const float* row = base + (long long)outer * map.so + (long long)inner * map.si;
+                if (ca < d) va = row[ca];
+                if (cb < d) vb = row[cb];
             }
-            sa[lr + 4 * q][lc] = va;
-            sb[lr + 4 * q][lc] = vb;
-        }
-        __syncthreads();
-#pragma unroll 8
-        for (int k = 0; k < SP_KR; ++k) {
-            const float4 fa = *reinterpret_cast<const float4*>(&sa[k][ty * 4]);
-            const float4 fb = *reinterpret_cast<const float4*>(&sb[k][tx * 4]);
-            const double a4[4] = {(double)fa.x, (double)fa.y, (double)fa.z, (double)fa.w};
-            const double b4[4] = {(double)fb.x, (double)fb.y, (double)fb.z, (double)fb.w};
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = fma(a4[i], b4[j], acc[i][j]);
-        }
-    }
-    double* slab = slabs + ((long long)mat * chunks + chunk) * d * d;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int gi = ti * SP_TILE + ty * 4 + i;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int gj = tj * SP_TILE + tx * 4 + j;
-            if (gi < d && gj < d) slab[(long long)gi * d + gj] = acc[i][j];
-        }
-    }
+        };
+    };
+    gram64_tile<float>(cols, ti, tj, r0, r1, slabs + ((long long)mat * chunks + chunk) * d * d, d, d);
 }
 
+// G[i][j] = G[j][i] = sum of the chunk slabs of matrix blockIdx.y in chunk order
 __global__ __launch_bounds__(256) void spectral_reduce(const double* __restrict__ slabs, int d, int chunks, double* __restrict__ g) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= d * d) return;
-    const int i = idx / d, j = idx - i * d;
-    if (i > j) return;
     const long long dd = (long long)d * d;
-    const double* s = slabs + (long long)blockIdx.y * chunks * dd + idx;
-    double v = 0.0;
-    for (int c = 0; c < chunks; ++c) v += s[(long long)c * dd];
-    double* gm = g + (long long)blockIdx.y * dd;
-    gm[idx] = v;
-    gm[(long long)j * d + i] = v;
+    slab_sum<true>(slabs + (long long)blockIdx.y * chunks * dd, dd, d, chunks, g + (long long)blockIdx.y * dd);
 }
 
 struct EigOut {
@@ -266,31 +219,11 @@ __device__ __forceinline__ void sp_bisect(int d, bool degenerate, double mx, dou
         hi = dg[tid] + el + er;
         emax = er * er;
     }
-    __syncthreads();
-    if (tid < d) e2[tid] = emax;
-    red[tid] = lo;
-    __syncthreads();
-    for (int s = SP_EIG_THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] = red[tid] < red[tid + s] ? red[tid] : red[tid + s];
-        __syncthreads();
-    }
-    const double glo = red[0];
-    __syncthreads();
-    red[tid] = hi;
-    __syncthreads();
-    for (int s = SP_EIG_THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] = red[tid] > red[tid + s] ? red[tid] : red[tid + s];
-        __syncthreads();
-    }
-    const double ghi = red[0];
-    __syncthreads();
-    red[tid] = emax;
-    __syncthreads();
-    for (int s = SP_EIG_THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] = red[tid] > red[tid + s] ? red[tid] : red[tid + s];
-        __syncthreads();
-    }
-    const double pivmin = DBL_MIN * (red[0] > 1.0 ? red[0] : 1.0);
+    const double glo = block_reduce<SP_EIG_THREADS>(lo, red, OpMin());
+    if (tid < d) e2[tid] = emax;                               // behind the reduction's barriers: every neighbour has read e2
+    const double ghi = block_reduce<SP_EIG_THREADS>(hi, red, OpMax());
+    const double emx = block_reduce<SP_EIG_THREADS>(emax, red, OpMax());
+    const double pivmin = DBL_MIN * (emx > 1.0 ? emx : 1.0);
     __syncthreads();
     // thread j: the j-th largest eigenvalue = ascending index d - 1 - j; count(x) = #eigenvalues < x
     if (tid < d) {
@@ -355,26 +288,14 @@ __global__ __launch_bounds__(SP_EIG_THREADS) void spectral_eig(double* __restric
     if (out.sv && tid < out.sv_ld) out.sv[(long long)blockIdx.x * out.sv_ld + tid] = tid < keep ? sg : 0.0;
     if (out.rows_out && tid == 0) out.rows_out[0] = (double)rows;
     if (!out.erank) return;                                    // uniform
-    red[tid] = sg;
-    __syncthreads();
-    for (int s = SP_EIG_THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    const double total = red[0];
-    __syncthreads();
+    const double total = block_reduce<SP_EIG_THREADS>(sg, red, OpSum());
     double term = 0.0;
     if (tid < keep) {
         const double p = sg / total;
         term = p * log(p + out.eps);
     }
-    red[tid] = term;
-    __syncthreads();
-    for (int s = SP_EIG_THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    if (tid == 0) out.erank[(long long)blockIdx.x * out.erank_ld] = exp(-red[0]);
+    const double ent = block_reduce<SP_EIG_THREADS>(term, red, OpSum());
+    if (tid == 0) out.erank[(long long)blockIdx.x * out.erank_ld] = exp(-ent);
 }
 
 
@@ -394,76 +315,31 @@ struct Operand {
 // only (spectral_reduce mirrors them); else every tile of the d_a x d_b product.
 template <bool TRI>
 __global__ __launch_bounds__(256) void subspace_gram(Operand A, Operand B, unsigned rows, int chunks, double* __restrict__ slabs) {
-    __shared__ __align__(16) double sa[SP_KR][SP_TILE];
-    __shared__ __align__(16) double sb[SP_KR][SP_TILE];
     int ti, tj;
     if (TRI) {
-        const int nt = (A.d + SP_TILE - 1) / SP_TILE;
-        int rem = blockIdx.x;
-        ti = 0;
-        while (rem >= nt - ti) { rem -= nt - ti; ++ti; }
-        tj = ti + rem;
+        tri_tile(blockIdx.x, (A.d + G64_TILE - 1) / G64_TILE, ti, tj);
     } else {
-        const int ntb = (B.d + SP_TILE - 1) / SP_TILE;
+        const int ntb = (B.d + G64_TILE - 1) / G64_TILE;
         ti = blockIdx.x / ntb;
         tj = blockIdx.x - ti * ntb;
     }
-    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4, lc = tid & 63, lr = tid >> 6;
     const unsigned chunk = blockIdx.y;
     const unsigned r0 = (unsigned)((unsigned long long)rows * chunk / chunks);
     const unsigned r1 = (unsigned)((unsigned long long)rows * (chunk + 1) / chunks);
-    const int ca = ti * SP_TILE + lc, cb = tj * SP_TILE + lc;
-    const double ma = ca < A.d ? A.mu[ca] : 0.0, mb = cb < B.d ? B.mu[cb] : 0.0;
-    double acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = 0.0;
-    for (unsigned rs = r0; rs < r1; rs += SP_KR) {
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < SP_KR / 4; ++q) {
-            const unsigned r = rs + lr + 4 * q;
-            double va = 0.0, vb = 0.0;
-            if (r < r1) {
-                if (ca < A.d) va = (double)A.x[(long long)r * A.ld + ca] - ma;
-                if (cb < B.d) vb = (double)B.x[(long long)r * B.ld + cb] - mb;
-            }
-            sa[lr + 4 * q][lc] = va;
-            sb[lr + 4 * q][lc] = vb;
-        }
-        __syncthreads();
-#pragma unroll 8
-        for (int k = 0; k < SP_KR; ++k) {
-            double a4[4], b4[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { a4[i] = sa[k][ty * 4 + i]; b4[i] = sb[k][tx * 4 + i]; }
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = fma(a4[i], b4[j], acc[i][j]);
-        }
-    }
-    double* slab = slabs + (long long)chunk * A.d * B.d;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int gi = ti * SP_TILE + ty * 4 + i;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int gj = tj * SP_TILE + tx * 4 + j;
-            if (gi < A.d && gj < B.d) slab[(long long)gi * B.d + gj] = acc[i][j];
-        }
-    }
+    const auto cols = [&](int ca, int cb) {
+        const double ma = ca < A.d ? A.mu[ca] : 0.0, mb = cb < B.d ? B.mu[cb] : 0.0;
+        return [&A, &B, ca, cb, ma, mb](unsigned r, double& va, double& vb) {
+            if (ca < A.d) va = (double)A.x[(long long)r * A.ld + ca] - ma;
+            if (cb < B.d) vb = (double)B.x[(long long)r * B.ld + cb] - mb;
+        };
+    };
+    gram64_tile<double>(cols, ti, tj, r0, r1, slabs + (long long)chunk * A.d * B.d, A.d, B.d);
 }
 
 // the rectangular form of spectral_reduce: c = sum of the chunk slabs in chunk order
 __global__ __launch_bounds__(256) void subspace_reduce_rect(const double* __restrict__ slabs, long long total, int chunks,
                                                             double* __restrict__ c) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= total) return;
-    double v = 0.0;
-    for (int k = 0; k < chunks; ++k) v += slabs[(long long)k * total + idx];
-    c[idx] = v;
+    slab_sum<false>(slabs, total, 1, chunks, c);
 }
 
 // dst = D_r src D_c with D_j = 1 / (std_j + 1e-8), std_j = sqrt(Gc_jj / (n - 1)) read from the diagonals of the two centred
@@ -539,13 +415,7 @@ __global__ __launch_bounds__(SP_EIG_THREADS) void subspace_eig(EigJobs jobs) {
     // |T|: the largest absolute row sum
     double rs = 0.0;
     if (tid < d) rs = fabs(dg[tid]) + (tid > 0 ? fabs(ef[tid - 1]) : 0.0) + fabs(ef[tid]);
-    red[tid] = rs;
-    __syncthreads();
-    for (int s = SP_EIG_THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] = red[tid] > red[tid + s] ? red[tid] : red[tid + s];
-        __syncthreads();
-    }
-    const double tnorm = red[0];
+    const double tnorm = block_reduce<SP_EIG_THREADS>(rs, red, OpMax());
     const double floor_piv = DBL_EPSILON * tnorm;              // tnorm >= 1: the scaled matrix has a diagonal entry in [1, 2)
     // shifts (in the scaled units of T), equal ones pushed 10 ulp apart, and the first member of each vector's cluster
     if (tid == 0) {
@@ -777,8 +647,7 @@ int umlh_spectral_launch(const float* a, int batch, long long rows, int period, 
     double* slabs = at<double>(scratch, 0);
     double* g = at<double>(scratch, align_up(dd * batch * chunks));
     RowMap map{a, sm, so, si, lengths, (unsigned)rows, (unsigned)period, drop_last};
-    const int nt = (d + SP_TILE - 1) / SP_TILE;
-    hipLaunchKernelGGL(spectral_gram, dim3(nt * (nt + 1) / 2, chunks, batch), dim3(256), 0, st, map, d, chunks, slabs);
+    hipLaunchKernelGGL(spectral_gram, dim3(tri_tiles((d + G64_TILE - 1) / G64_TILE), chunks, batch), dim3(256), 0, st, map, d, chunks, slabs);
     hipLaunchKernelGGL(spectral_reduce, dim3((d * d + 255) / 256, batch), dim3(256), 0, st, slabs, d, chunks, g);
     EigOut out{erank, 1, rows_out, sv, sv_ld, eps};
     hipLaunchKernelGGL(spectral_eig, dim3(batch), dim3(SP_EIG_THREADS), 0, st, g, d, map, (int)(rows / period), out);
@@ -827,8 +696,7 @@ void standardised_gram(const float* x, long long n, int d, long long ld, double*
                        double* gc, double* g, hipStream_t st) {
     umlh_probe_launch_means(x, n, d, (int)ld, stats, stat_scr, st);
     const Operand op{x, ld, stats, d};
-    const int nt = (d + SP_TILE - 1) / SP_TILE;
-    hipLaunchKernelGGL((subspace_gram<true>), dim3(nt * (nt + 1) / 2, chunks), dim3(256), 0, st, op, op, (unsigned)n, chunks, slabs);
+    hipLaunchKernelGGL((subspace_gram<true>), dim3(tri_tiles((d + G64_TILE - 1) / G64_TILE), chunks), dim3(256), 0, st, op, op, (unsigned)n, chunks, slabs);
     hipLaunchKernelGGL(spectral_reduce, dim3((d * d + 255) / 256, 1), dim3(256), 0, st, slabs, d, chunks, gc);
     hipLaunchKernelGGL(subspace_standardise, dim3((d * d + 255) / 256), dim3(256), 0, st, gc, d, d, gc, gc, (double)(n - 1), g);
 }
@@ -848,8 +716,7 @@ int umlh_subspace_launch(const float* a, long long n, int d, long long ld, int q
                           at<double>(scratch, p.gc_a), g, st);
     } else {                                                   // the Gram of umlh_svdvals, bit for bit
         RowMap map{a, 0, 0, ld, nullptr, (unsigned)n, (unsigned)n, 0};
-        const int nt = (d + SP_TILE - 1) / SP_TILE;
-        hipLaunchKernelGGL(spectral_gram, dim3(nt * (nt + 1) / 2, p.chunks, 1), dim3(256), 0, st, map, d, p.chunks, slabs);
+        hipLaunchKernelGGL(spectral_gram, dim3(tri_tiles((d + G64_TILE - 1) / G64_TILE), p.chunks, 1), dim3(256), 0, st, map, d, p.chunks, slabs);
         hipLaunchKernelGGL(spectral_reduce, dim3((d * d + 255) / 256, 1), dim3(256), 0, st, slabs, d, p.chunks, g);
     }
     EigJobs jobs{};
@@ -868,7 +735,7 @@ int umlh_svcca_launch(const float* a, const float* b, long long n, int da, int d
     standardised_gram(a, n, da, lda, sta, at<void>(scratch, p.stat_scr), slabs, p.chunks, gca, at<double>(scratch, p.g_a), st);
     standardised_gram(b, n, db, ldb, stb, at<void>(scratch, p.stat_scr), slabs, p.chunks, gcb, at<double>(scratch, p.g_b), st);
     const Operand oa{a, lda, sta, da}, ob{b, ldb, stb, db};
-    const int nta = (da + SP_TILE - 1) / SP_TILE, ntb = (db + SP_TILE - 1) / SP_TILE;
+    const int nta = (da + G64_TILE - 1) / G64_TILE, ntb = (db + G64_TILE - 1) / G64_TILE;
     const long long total = (long long)da * db;
     hipLaunchKernelGGL((subspace_gram<false>), dim3(nta * ntb, p.chunks), dim3(256), 0, st, oa, ob, (unsigned)n, p.chunks, slabs);
     hipLaunchKernelGGL(subspace_reduce_rect, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, slabs, total, p.chunks, c);
