@@ -833,6 +833,53 @@ int  umlh_class_stats(const float* feats, int64_t ld, int64_t n, int32_t d, cons
                       int32_t n_class, float* means, int64_t ld_means, double* dist, double* out2,
                       void* scratch, uint64_t scratch_bytes, void* stream);
 
+/* ---- class-wise validation report: the top-k classes of every row and per-class counts of them (the `val_classwise` slot of
+ * the fine-tune loop's result, vision_language/finetune.py:121, which the reference never fills).  Additive to
+ * ABI v11: umlh_version() is unchanged, callers detect the feature by these symbols.  Handle-free: x is row-major fp32 [n, d]
+ * with row stride ldx >= d (feature rows), w fp32 [n_class, d] with row stride ldw >= d (the head's weight rows; the packed
+ * [weight | bias | pad] rows of a bias head are read in place with ldw > d), bias_or_null fp32 [n_class] dense,
+ * scale_dev_or_null ONE fp32 in device memory (NULL = 1; it is never read on the host).  The logit of row i and class j is
+ *   z_ij = scale * (x_i . w_j + b_j).
+ * No n x n_class array is formed and no reduction uses a float atomic.  Every argument check happens before any HIP call and
+ * names the function and the argument; everything runs on `stream`; outputs are device memory.
+ * Envelope: 1 <= k <= 24, k <= n_class < 2^31, 1 <= n < 2^31, d >= 1, ldx >= d, ldw >= d, splits >= 0 (0 = auto); anything else
+ * is UMLH_E_INVALID.
+ *
+ * Order rule: per row the k classes with the largest z, ordered by (z descending, class index ascending) -- exact ties go to
+ * the smaller index, whatever the sign of scale (a negative scale ranks by the negated pre-scale value; a zero scale ties every
+ * class and returns 0 .. k-1).
+ * Two stages.  (1) Candidates: the score sign(scale) * (x.w_j + b_j) with x.w_j on the f32 MFMA (a k-ordered fp32 fma chain, one
+ * fp32 addition of the bias); the kc = min(k + 8, n_class) best under the strict order (score descending, index ascending) are
+ * kept by the 32-row strip / 256-column tile / column-chunk scheme of umlh_align_knn.  (2) The candidates are re-evaluated as
+ * z = (double)scale * (sum_k (double)x_k (double)w_jk + (double)b_j) in a fixed order and re-ranked by (z, index); the first k
+ * are the answer and logit is z rounded once to fp32.  The result is bitwise independent of `splits` and reproducible across
+ * calls and streams.  Both load paths of stage 1 (16-byte loads when d, ldx, ldw are multiples of 4 and both base addresses of
+ * 16 bytes; 4-byte loads otherwise) form the same fma chains.
+ * Index-range guarantee: every value written to cls is -1 or lies in [0, n_class), whatever the data.  List slots that no class
+ * filled (a row containing NaN, whose comparisons are all false; NaN weight rows leaving fewer than k classes) are never used
+ * as addresses; the output positions they leave open get class -1 and a NaN logit.  Results for rows that contain Inf are
+ * otherwise unspecified; other rows are unaffected. */
+
+/* Scratch bytes of umlh_eval_topk with these arguments: O(n * kc * splits) with splits <= min(ceil(n_class / 256), 1024) and, in
+ * auto mode, splits * n <= n + 16384: no n * n_class term.  0 on invalid arguments. */
+uint64_t umlh_eval_topk_scratch_bytes(int64_t n, int64_t n_class, int32_t d, int32_t k, int32_t splits);
+/* cls int32 [n, k]; logit_or_null fp32 [n, k] or NULL; both dense, every entry is written. */
+int  umlh_eval_topk(const float* x, int64_t n, int32_t ldx, const float* w, int64_t n_class, int32_t ldw, int32_t d,
+                    const float* bias_or_null, const float* scale_dev_or_null, int32_t k, int32_t splits,
+                    int32_t* cls, float* logit_or_null, void* scratch, uint64_t scratch_bytes, void* stream);
+/* Class-wise counts from cls int32 [n, k] (dense; what umlh_eval_topk wrote, or any list) and labels int64 [n].  Every output
+ * is ADDED INTO (64-bit integer atomics: exact and reproducible in any order), so a table can be fed in slabs; the caller
+ * zeroes the outputs before the first slab.  With pred_i = cls[i, 0], for every row i:
+ *   label_i outside [0, n_class):  misc2[0] += 1, and the row counts nowhere else;
+ *   otherwise  support[label_i] += 1, and
+ *     pred_i outside [0, n_class) (the -1 of a NaN row; never used as an address):  misc2[1] += 1, nothing else;
+ *     otherwise  hit1[label_i] += (pred_i == label_i),  hitk[label_i] += (label_i among cls[i, 0 .. k)),
+ *                confusion[label_i * n_class + pred_i] += 1   (row = true class, column = predicted class).
+ * support, hit1, hitk int64 [n_class]; confusion_or_null int64 [n_class, n_class] dense or NULL (off); misc2 int64 [2].
+ * One launch, no scratch.  Envelope: 1 <= k <= 24, 1 <= n < 2^31, 1 <= n_class < 2^31. */
+int  umlh_eval_classwise(const int32_t* cls, int64_t n, int32_t k, const int64_t* labels, int64_t n_class,
+                         int64_t* support, int64_t* hit1, int64_t* hitk, int64_t* confusion_or_null, int64_t* misc2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

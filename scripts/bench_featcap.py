@@ -111,7 +111,7 @@ def capture_timings(args):
         f.write("\n".join(lines) + "\n")
 
 
-def train_flag_off(args):
+def train_flag_off(args, what="capture off"):
     import torch
     import finetune as ft
     from engine.datasets.utils import FeatureLoader, FeatureTable
@@ -141,7 +141,7 @@ def train_flag_off(args):
         return (time.perf_counter() - t0) * 1e3
     once(50)
     ts = [round(once(args.steps), 2) for _ in range(args.repeats)]
-    print(json.dumps({"what": f"train() {args.steps} steps, cfg2 shape, bf16, capture off, wall ms per run", "root": args.root,
+    print(json.dumps({"what": f"train() {args.steps} steps, cfg2 shape, bf16, {what}, wall ms per run", "root": args.root,
                       "ms": ts, "median_ms": sorted(ts)[len(ts) // 2]}), flush=True)
 
 

@@ -2457,3 +2457,49 @@ int umlh_knn_vote(const int32_t* idx, int64_t n_query, int32_t k, const int32_t*
            "umlh_knn_vote");
     return UMLH_OK;
 }
+
+// ---- class-wise validation report (kernels: umlh_kernels_evalreport.hip); every check precedes the first HIP call ----
+static bool eval_topk_shape_ok(int64_t n, int64_t n_class, int32_t k) {
+    return k >= 1 && k <= KNN_MAX_K && n_class >= k && n_class <= KNN_MAX_ROWS && n >= 1 && n <= KNN_MAX_ROWS;
+}
+
+uint64_t umlh_eval_topk_scratch_bytes(int64_t n, int64_t n_class, int32_t d, int32_t k, int32_t splits) {
+    if (!eval_topk_shape_ok(n, n_class, k) || d < 1 || splits < 0) return 0;
+    return umlh_evalreport_bytes(n, n_class, k, splits);
+}
+
+int umlh_eval_topk(const float* x, int64_t n, int32_t ldx, const float* w, int64_t n_class, int32_t ldw, int32_t d,
+                   const float* bias_or_null, const float* scale_dev_or_null, int32_t k, int32_t splits, int32_t* cls,
+                   float* logit_or_null, void* scratch, uint64_t scratch_bytes, void* stream) {
+    if (!x || !w || !cls || !scratch)
+        return fail(UMLH_E_INVALID, "umlh_eval_topk: null pointer (x, w, cls and scratch are required)");
+    if (k < 1 || k > KNN_MAX_K) return fail(UMLH_E_INVALID, "umlh_eval_topk: k=%d outside 1..%d", k, KNN_MAX_K);
+    if (!eval_topk_shape_ok(n, n_class, k))
+        return fail(UMLH_E_INVALID, "umlh_eval_topk: n=%lld n_class=%lld for k=%d (need 1 <= n < 2^31, k <= n_class < 2^31)",
+                    (long long)n, (long long)n_class, k);
+    if (d < 1 || ldx < d || ldw < d)
+        return fail(UMLH_E_INVALID, "umlh_eval_topk: d=%d ldx=%d ldw=%d (need 1 <= d <= ld)", d, ldx, ldw);
+    if (splits < 0) return fail(UMLH_E_INVALID, "umlh_eval_topk: splits=%d < 0", splits);
+    const uint64_t need = umlh_evalreport_bytes(n, n_class, k, splits);
+    if (scratch_bytes < need)
+        return fail(UMLH_E_INVALID, "umlh_eval_topk: scratch_bytes=%llu, %llu needed", (unsigned long long)scratch_bytes,
+                    (unsigned long long)need);
+    if ((reinterpret_cast<uintptr_t>(scratch) & 3) != 0) return fail(UMLH_E_INVALID, "umlh_eval_topk: scratch must be 4-byte aligned");
+    HIPCHK(umlh_evalreport_launch_topk(x, n, ldx, w, n_class, ldw, d, bias_or_null, scale_dev_or_null, k, splits, cls, logit_or_null,
+                                       scratch, (hipStream_t)stream), "umlh_eval_topk");
+    return UMLH_OK;
+}
+
+int umlh_eval_classwise(const int32_t* cls, int64_t n, int32_t k, const int64_t* labels, int64_t n_class, int64_t* support,
+                        int64_t* hit1, int64_t* hitk, int64_t* confusion_or_null, int64_t* misc2, void* stream) {
+    if (!cls || !labels || !support || !hit1 || !hitk || !misc2)
+        return fail(UMLH_E_INVALID, "umlh_eval_classwise: null pointer (cls, labels, support, hit1, hitk and misc2 are required)");
+    if (k < 1 || k > KNN_MAX_K) return fail(UMLH_E_INVALID, "umlh_eval_classwise: k=%d outside 1..%d", k, KNN_MAX_K);
+    if (n < 1 || n > KNN_MAX_ROWS || n_class < 1 || n_class > KNN_MAX_ROWS)
+        return fail(UMLH_E_INVALID, "umlh_eval_classwise: n=%lld n_class=%lld (need 1 <= n < 2^31, 1 <= n_class < 2^31)", (long long)n,
+                    (long long)n_class);
+    HIPCHK(umlh_evalreport_launch_classwise(cls, n, k, (const long long*)labels, n_class, (long long*)support, (long long*)hit1, (long long*)hitk,
+                                            (long long*)confusion_or_null, (long long*)misc2, (hipStream_t)stream),
+           "umlh_eval_classwise");
+    return UMLH_OK;
+}

@@ -169,6 +169,12 @@ int umlh_classindex_launch(const long long* labels, long long n, int n_class, in
 unsigned long long umlh_classstats_bytes(long long n, int d, int n_class);
 int umlh_classstats_launch(const float* feats, long long ld, long long n, int d, const int* order, const long long* offsets,
                            int n_class, float* means, long long ld_means, double* dist, double* out2, void* scratch, hipStream_t st);
+// ---- umlh_kernels_evalreport.hip: top-k classes per row, class-wise counters ----
+unsigned long long umlh_evalreport_bytes(long long n, long long C, int k, int splits);
+int umlh_evalreport_launch_topk(const float* x, long long n, int ldx, const float* w, long long C, int ldw, int d, const float* bias,
+                                const float* scale, int k, int splits, int* cls, float* logit, void* scratch, hipStream_t st);
+int umlh_evalreport_launch_classwise(const int* cls, long long n, int k, const long long* labels, long long C, long long* support,
+                                     long long* hit1, long long* hitk, long long* confusion, long long* misc, hipStream_t st);
 // ---- umlh_kernels_stepstats.hip: per-step logged statistics (trivial next-frame error, masked reconstruction error) ----
 long long umlh_stepstats_partials(int B, int T, int d);       // partial sums of one call; -1: more than the final kernel takes
 unsigned long long umlh_stepstats_bytes(int B, int T, int d);

@@ -1,5 +1,6 @@
-// The streaming top-k neighbour core shared by the alignment k-NN (knn_tiles / knn_merge, umlh_kernels_align.hip) and the
-// k-NN probe (kp_tiles / kp_merge, umlh_kernels_knn.hip), and the 32 x 64 Gram k loop that rbf_tiles
+// The streaming top-k neighbour core shared by the alignment k-NN (knn_tiles / knn_merge, umlh_kernels_align.hip), the
+// k-NN probe (kp_tiles / kp_merge, umlh_kernels_knn.hip) and the class report (ev_tiles / ev_merge,
+// umlh_kernels_evalreport.hip), and the 32 x 64 Gram k loop that rbf_tiles
 // (umlh_kernels_align_ext.hip) runs as well.  Device code for the .hip files only; the kernels stay where they are launched.
 //
 // A workgroup takes a strip of 32 query rows and a chunk of 256-column tiles of the train rows, scores every (row, column)
@@ -77,7 +78,8 @@ __device__ __forceinline__ void gram_32x64(const LA& load_a, const LB& load_b, i
 // <= TK_KMAX entries.  P adds
 //   static constexpr bool EXCLUDE_SELF      column j is left out of global row j's list
 //   float col_term(long long j) const       a per-column value, loaded once per tile (j may lie past nt)
-//   static float score(float acc, float t)  the ranked score from acc = q_i . t_j and the column's term
+//   float score(float acc, float t)         the ranked score from acc = q_i . t_j and the column's term (static, or const when
+//                                           it needs a value of the launch, as the sign of the class report's scale)
 struct TopkOperands {
     const float* __restrict__ qx;
     const float* __restrict__ tx;
@@ -122,8 +124,8 @@ __device__ __forceinline__ void topk_tiles(const P& p, int ntiles, int splits, f
 #pragma unroll
         for (int q = 0; q < 16; ++q) {               // acc[q]: row 8(q/4) + 4h + q%4, column c32 (the last rebuild ended on a barrier)
             const int i = 8 * (q >> 2) + 4 * h + (q & 3);
-            tile[i * TK_LD + wave * 64 + c32] = P::score(acc0[q], n0);
-            tile[i * TK_LD + wave * 64 + 32 + c32] = P::score(acc1[q], n1);
+            tile[i * TK_LD + wave * 64 + c32] = p.score(acc0[q], n0);
+            tile[i * TK_LD + wave * 64 + 32 + c32] = p.score(acc1[q], n1);
         }
         __syncthreads();
         const int fr = tid & 31, part = tid >> 5;     // filter mapping: row fr, columns part*32 ..

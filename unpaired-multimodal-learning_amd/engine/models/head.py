@@ -283,6 +283,15 @@ class _HeadBase(nn.Module):
     def extract_raw_features(self, images):
         return self.vision_model(images)
 
+    def predict_topk(self, images, k=5):
+        """(classes int32 [rows, k], logits fp32 [rows, k]) of the image logits (an extension): the k best classes per row,
+        best first, exact ties to the smaller class index (``umlh.topk_classes`` on ``extract_features``, the head's weight and
+        bias and the image scale); the [rows, C] logits are never formed.  Device tensors, no host sync."""
+        import umlh
+        with torch.no_grad():
+            feats = self.extract_features(images)
+            return umlh.topk_classes(feats, self.head.weight, self.head.bias, self._scales[0], k=k)
+
     def zero_shot_init(self, zeroshot_dataset):
         print("=> Initializing head with zero-shot weights")
         dev = self.head.weight.device

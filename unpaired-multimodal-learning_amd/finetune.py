@@ -341,10 +341,15 @@ class _Run:
 def train(model, image_loader, text_loader, val_loader, test_loader, optimizer, scheduler, device="cuda",
           max_iters=1000, alpha=1.0, eval_freq=EVAL_FREQ, patience=5, capture_features_during_training=False,
           features_pth="./", args=None, logger=None, precision="fp32", diagnostics=None, capture_samples=None,
-          capture_options=None):
+          capture_options=None, classwise=False):
     """``capture_samples``: the (rows, labels) of the image sample of the feature capture (default:
     ``take_capture_samples(image_loader, 16)``); ``capture_options``: keyword arguments of ``FeatureCapture``
-    (``keep_features``, ``strict``).  Both are read only with ``capture_features_during_training``."""
+    (``keep_features``, ``strict``).  Both are read only with ``capture_features_during_training``.
+
+    ``classwise``: True, or a dict of keyword arguments of ``validate_classwise`` (``topk``, ``confusion``), fills
+    ``out['val_classwise']`` with the class-wise report of the model the run returns: ONCE, after the best weights are back in
+    the model, next to the closing ``validate``.  Nothing is added to the loop or its evaluation points; off (the default)
+    the slot stays None as in the reference."""
     capture = None
     if capture_features_during_training:
         # finetune.py:127-155: the samples are drawn BEFORE the training iterators exist (the text sample iterates the text
@@ -436,6 +441,9 @@ def train(model, image_loader, text_loader, val_loader, test_loader, optimizer, 
     if logger is not None:
         logger.log({"val/best_val_loss": val_loss, "val/best_val_acc": val_acc, "iter": out["iter"]})
     print(f"=> Best Val Loss {val_loss:.4f}, Val Acc {val_acc:.4f} at Iter {out['iter']}")
+    cw = _classwise_kwargs(classwise)
+    if cw is not None:
+        out["val_classwise"] = validate_classwise(model, val_loader, **cw)
     if capture is not None:                           # finetune.py:280-287
         capture.save(features_pth)
         out["capture_scalars"] = captured[:run.last_i + 1].cpu()     # (an extension, like train_scalars): per step
@@ -450,7 +458,8 @@ def train_grouped(runs, device="cuda", eval_freq=EVAL_FREQ, precision="fp32"):
     head's validation / test passes are enqueued and read back with one host synchronisation.  Each head keeps the
     exact semantics of ``train`` (evaluation cadence, strict-improvement best snapshot, patience, restored weights,
     returned dict); ``runs`` = dicts with the arguments of ``train`` (model, image_loader, text_loader, val_loader,
-    test_loader, optimizer, scheduler, max_iters, alpha, patience)."""
+    test_loader, optimizer, scheduler, max_iters, alpha, patience, and optionally ``classwise``: that run's
+    ``out['val_classwise']`` is filled after its best weights are back, as in ``train``)."""
     st = [_Run.of(r["model"], r.get("image_loader"), r.get("text_loader"), r["val_loader"], r.get("test_loader"),
                   r["optimizer"], r["scheduler"], r["max_iters"], r["alpha"], r["patience"], precision, False,
                   name=r.get("name", k)) for k, r in enumerate(runs)]
@@ -506,7 +515,12 @@ def train_grouped(runs, device="cuda", eval_freq=EVAL_FREQ, precision="fp32"):
         for h in st:
             if h.live:
                 h.advance()
-    return [h.finish() for h in st]
+    outs = [h.finish() for h in st]
+    for r, h, out in zip(runs, st, outs):
+        cw = _classwise_kwargs(r.get("classwise"))
+        if cw is not None:
+            out["val_classwise"] = validate_classwise(h.model, h.val_loader, **cw)
+    return outs
 
 
 EVAL_SLAB = 4096     # rows per forward launch of a whole-table evaluation
@@ -640,6 +654,72 @@ def validate(model, val_loader, device="cuda"):
     val_loss = (s[:, umlh.S_LOSS_SUM] / counts).mean().item()
     model.train()
     return val_loss, val_acc
+
+
+def validate_classwise(model, val_loader, topk=5, confusion=False):
+    """The class-wise report of ``model`` on ``val_loader`` (what ``train(classwise=...)`` puts into ``out['val_classwise']``,
+    the slot the reference creates and never fills): a dict of CPU values --
+
+      ``support``, ``correct``, ``correct_topk``   int64 [C]: rows of each true class, and how many of them have the label as
+                                                   the best class / among the ``topk`` best classes
+      ``acc``, ``acc_topk``                        float64 [C]: the two ratios, NaN for a class without rows
+      ``mean_class_acc``, ``mean_class_acc_topk``  their means over the classes that have rows (mean per-class accuracy)
+      ``top1_acc``, ``topk_acc``                   correct / rows, over the rows with a label in [0, C)
+      ``topk``, ``n`` (all rows), ``ignored`` (rows with a label outside [0, C), counted nowhere else), ``no_prediction``
+                                                   (rows with NaN features: counted in ``support`` and ``n``, never correct)
+      ``confusion``                                int64 [C, C] when asked for: row = true class, column = best class
+
+    The best classes come from ``model.predict_topk`` (``umlh.topk_classes``: the [rows, C] logits are never formed, ties go to
+    the smaller class index) and are counted by ``umlh.class_report``.  An unshuffled ``FeatureLoader`` is evaluated as
+    ``EVAL_SLAB``-row slabs of its device table, any other loader batch by batch; all of them add into one set of device
+    counters and there is ONE host read at the end.  The slab path makes no iterator, so it draws nothing from the loader's
+    RNG.  ``topk`` is clamped to the number of classes and to the kernels' 24.
+
+    ``top1_acc`` and ``validate``'s accuracy come from different arithmetic: the fp64 re-evaluation of the candidates here,
+    the fp32 forward kernel's argmax there.  They agree except on rows whose two best logits lie within fp32 rounding of each
+    other, where either class may win there (and an exact tie goes to the smaller index here)."""
+    dev = model.head.weight.device
+    n_class = model.head.weight.shape[0]
+    k = max(1, min(int(topk), n_class, umlh.report.MAX_K))
+    model.eval()
+    counters, rows = None, 0
+    if _slab_evaluable(val_loader):
+        t = val_loader.table
+        batches = ((t.features[s0:s0 + EVAL_SLAB], t.labels[s0:s0 + EVAL_SLAB]) for s0 in range(0, len(t), EVAL_SLAB))
+    else:
+        batches = ((b["img"].to(dev, torch.float32), b["label"].to(dev)) for b in val_loader)
+    for x, y in batches:
+        cls, _ = model.predict_topk(x, k=k)
+        counters = umlh.class_report(cls, y, n_class, confusion=confusion, out=counters)
+        rows += int(y.numel())
+    model.train()
+    if counters is None:
+        raise umlh.UmlhError("validate_classwise: the loader delivered no rows")
+    names = ["support", "hit1", "hitk", "misc"] + (["confusion"] if confusion else [])
+    flat = torch.cat([counters[nm].reshape(-1) for nm in names]).cpu()                  # the one host read
+    support, correct, correct_k = (flat[j * n_class:(j + 1) * n_class].clone() for j in range(3))
+    ignored, no_pred = (int(v) for v in flat[3 * n_class:3 * n_class + 2])
+    seen = support > 0
+    nan = torch.full((n_class,), float("nan"), dtype=torch.float64)
+    acc = torch.where(seen, correct.double() / support.double(), nan)
+    acc_k = torch.where(seen, correct_k.double() / support.double(), nan)
+    labelled = int(support.sum())
+    ratio = lambda a: float(a.sum()) / labelled if labelled else float("nan")
+    out = {"support": support, "correct": correct, "correct_topk": correct_k, "acc": acc, "acc_topk": acc_k,
+           "mean_class_acc": float(acc[seen].mean()) if labelled else float("nan"),
+           "mean_class_acc_topk": float(acc_k[seen].mean()) if labelled else float("nan"),
+           "top1_acc": ratio(correct), "topk_acc": ratio(correct_k), "topk": k, "n": rows, "ignored": ignored,
+           "no_prediction": no_pred}
+    if confusion:
+        out["confusion"] = flat[3 * n_class + 2:].reshape(n_class, n_class).clone()
+    return out
+
+
+def _classwise_kwargs(classwise):
+    """``train``'s ``classwise`` argument as keyword arguments of ``validate_classwise``, or None when it is off."""
+    if isinstance(classwise, dict):
+        return dict(classwise)
+    return {} if classwise else None
 
 
 def hparam_str(optim, lr, wd, batch_size, iters, dropout, learnable_temp):

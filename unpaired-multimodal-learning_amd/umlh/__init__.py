@@ -24,6 +24,8 @@ from . import stepstats  # noqa: F401,E402
 from .stepstats import seq_step_stats  # noqa: F401,E402
 from . import rollout  # noqa: F401,E402
 from .rollout import rollout_rows, seq_spectrum  # noqa: F401,E402
+from . import report  # noqa: F401,E402
+from .report import class_report, topk_classes  # noqa: F401,E402
 
 
 def host_cpu_budget() -> int:

@@ -20,7 +20,7 @@ PREC_IDS = {"fp32": 0, "bf16": 1}
 N_CORE_SCALARS = 8
 N_SCALARS = 12
 
-SOURCES = ["umlh_p2p.hip", "umlh_kernels_f32.hip", "umlh_kernels_bf16.hip", "umlh_kernels_micro.hip", "umlh_kernels_seq.hip", "umlh_kernels_enc.hip", "umlh_kernels_align.hip", "umlh_kernels_align_ext.hip", "umlh_kernels_probe.hip", "umlh_kernels_knn.hip", "umlh_kernels_spectral.hip", "umlh_kernels_capture.hip", "umlh_kernels_stepstats.hip", "umlh_kernels_rollout.hip", "umlh_kernels_classstats.hip", "umlh_api.cpp", "umlh_encoder.cpp"]
+SOURCES = ["umlh_p2p.hip", "umlh_kernels_f32.hip", "umlh_kernels_bf16.hip", "umlh_kernels_micro.hip", "umlh_kernels_seq.hip", "umlh_kernels_enc.hip", "umlh_kernels_align.hip", "umlh_kernels_align_ext.hip", "umlh_kernels_probe.hip", "umlh_kernels_knn.hip", "umlh_kernels_spectral.hip", "umlh_kernels_capture.hip", "umlh_kernels_stepstats.hip", "umlh_kernels_rollout.hip", "umlh_kernels_classstats.hip", "umlh_kernels_evalreport.hip", "umlh_api.cpp", "umlh_encoder.cpp"]
 
 
 class UmlhError(RuntimeError):
@@ -210,6 +210,10 @@ def _prototypes() -> dict:
         "umlh_class_index": (rc, (vp, i64, i32, vp, vp, vp, u64, vp)),
         "umlh_class_stats_scratch_bytes": (u64, (i64, i32, i32)),
         "umlh_class_stats": (rc, (vp, i64, i64, i32, vp, vp, i32, vp, i64, vp, vp, vp, u64, vp)),
+        # class-wise validation report: top-k classes per row, per-class counters
+        "umlh_eval_topk_scratch_bytes": (u64, (i64, i64, i32, i32, i32)),
+        "umlh_eval_topk": (rc, (vp, i64, i32, vp, i64, i32, i32, vp, vp, i32, i32, vp, vp, vp, u64, vp)),
+        "umlh_eval_classwise": (rc, (vp, i64, i32, vp, i64, vp, vp, vp, vp, vp, vp)),
     }
 
 

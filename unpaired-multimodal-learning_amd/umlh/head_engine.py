@@ -89,7 +89,7 @@ class HeadEngine:
                 if d_img != d_shared or not 0 < self._from_txt < d_shared:
                     raise UmlhError("bias_from: a linear head needs d_img == d_shared > bias_from")
             self.bias_from = bias_from
-        self._aug_cache = {}                 # (data_ptr, rows, version, width) -> (fp32 augmented rows, bf16 shadow or None)
+        self._aug_cache = {}                 # (data_ptr, rows, version, width) -> (fp32 augmented rows, bf16 shadow or None, the source rows)
         self.w_head = torch.zeros(num_classes, d_shared, **f32)
         self.m_head = torch.zeros_like(self.w_head)
         self.v_head = torch.zeros_like(self.w_head)
@@ -145,7 +145,8 @@ class HeadEngine:
 
     def _augment(self, f: torch.Tensor, dim: int, want16: bool):
         """[N, d] feature rows -> ([N, dim] rows [x | 1 | 0...], bf16 shadow or None) for a head with bias.  Tables are
-        converted once (cached by address, row count and in-place version)."""
+        converted once (cached by address, row count and in-place version; an entry keeps its source rows alive, so the
+        address of a batch that has been dropped cannot come back as another batch's while its entry is still here)."""
         frm = self._from_width(f, dim)
         if frm is None:
             return f, None
@@ -155,13 +156,13 @@ class HeadEngine:
             a = torch.zeros(f.shape[0], dim, dtype=torch.float32, device=f.device)
             a[:, :frm] = f
             a[:, frm] = 1.0
-            hit = (a, None)
+            hit = (a, None, f)
         if want16 and hit[1] is None:
-            hit = (hit[0], to_bf16(hit[0]))
+            hit = (hit[0], to_bf16(hit[0]), hit[2])
         self._aug_cache[key] = hit           # most recently used last
         while len(self._aug_cache) > 32:
             self._aug_cache.pop(next(iter(self._aug_cache)))
-        return hit
+        return hit[:2]
 
     def _batch(self, b: Optional[RowBatch], dim: int) -> Optional[Batch]:
         if b is None:
