@@ -180,6 +180,7 @@ def test_indices_stay_in_range_with_nan_rows():
     i1, d1 = search(dev(t), dev(qn), k)
     i1, d1 = i1.cpu().numpy(), d1.cpu().numpy()
     assert i1.min() >= 0 and i1.max() < nt
+    assert np.array_equal(i1[13], np.arange(k)) and np.isnan(d1[13]).all()       # a fully open list: its own positions, NaN
     others = np.arange(nq) != 13
     assert np.array_equal(i1[others], clean_i[others]) and np.array_equal(d1[others], clean_d[others])
     pred, _, _ = vote(dev(i1), dev(np.zeros(nt, np.int32)))
@@ -196,11 +197,29 @@ def test_indices_stay_in_range_with_nan_rows():
     assert np.array_equal(i2[free], clean_i[free]) and np.array_equal(d2[free], clean_d[free])
     assert not (i2[free] == poisoned).any()
     # n_train < k + 8 with a NaN query row: the lists are shorter than the candidate width
-    i3, _ = search(dev(t[:6]), dev(qn[:20]), 5)
-    i3 = i3.cpu().numpy()
+    i3, d3 = search(dev(t[:6]), dev(qn[:20]), 5)
+    i3, d3 = i3.cpu().numpy(), d3.cpu().numpy()
     assert i3.min() >= 0 and i3.max() < 6
+    assert np.array_equal(i3[13], np.arange(5)) and np.isnan(d3[13]).all()
     want = R.kneighbors(q[:20], t[:6], 5)[1]
     assert np.array_equal(np.delete(i3, 13, 0), np.delete(want, 13, 0))
+
+
+def test_nan_train_row_with_n_train_equal_k_leaves_one_slot_open():
+    """n_train == k and one train row of NaNs: four finite neighbours in the float64 order, then position 4 as an open slot (its
+    own index, a NaN distance).  The probe's twin of the k = C NaN-weight case of tests/test_evalreport_gpu.py."""
+    rng = np.random.default_rng(8)
+    nt = k = 5
+    t, q = rng.standard_normal((nt, 3)).astype(np.float32), rng.standard_normal((3, 3)).astype(np.float32)
+    t[2] = np.nan
+    idx, dist = search(dev(t), dev(q), k)
+    idx, dist = idx.cpu().numpy(), dist.cpu().numpy()
+    finite = np.array([0, 1, 3, 4])
+    want_d2, order = R.kneighbors(q, t[finite], 4)
+    assert np.array_equal(idx[:, :4], finite[order])
+    want = np.sqrt(want_d2)
+    assert (np.abs(dist[:, :4] - want) <= 2.0 ** -22 * want).all()
+    assert (idx[:, 4] == 4).all() and np.isnan(dist[:, 4]).all()
 
 
 # ---- 5. the Python class ----

@@ -177,8 +177,9 @@ extern "C" {
 
 int umlh_align_knn_splits(long long n, int splits) { return topk_splits(n, n, splits); }
 
+// One stage, margin 0 (topk < n): the scratch is the two list slabs, which end where candidates would start.
 unsigned long long umlh_align_knn_bytes(long long n, int topk, int splits) {
-    return (unsigned long long)(2 * align_up((long long)umlh_align_knn_splits(n, splits) * n * topk * 4));
+    return (unsigned long long)topk_plan(n, n, topk, 0, splits, 0).cand;
 }
 
 unsigned long long umlh_align_mutual_bytes(long long n) { return (unsigned long long)align_up((n + 255) / 256 * 8); }
@@ -209,14 +210,12 @@ unsigned long long umlh_align_cka_bytes(long long n, int da, int db, int splits)
 
 int umlh_align_launch_knn(const float* x, long long n, int d, int ldx, int topk, int splits, int* knn, float* scores, void* scratch,
                           hipStream_t st) {
-    const int s = umlh_align_knn_splits(n, splits), ntiles = (int)((n + TK_COLS - 1) / TK_COLS);
-    float* ps = (float*)scratch;
-    int* pi = (int*)((char*)scratch + align_up((long long)s * n * topk * 4));
-    const dim3 grid((unsigned)((n + TK_ROWS - 1) / TK_ROWS), (unsigned)s);
-    const bool vec = (d % 4 == 0) && (ldx % 4 == 0) && (((uintptr_t)x & 15) == 0);
-    if (vec) hipLaunchKernelGGL(knn_tiles<true>, grid, dim3(256), 0, st, x, (int)n, d, ldx, topk, ntiles, s, ps, pi);
-    else hipLaunchKernelGGL(knn_tiles<false>, grid, dim3(256), 0, st, x, (int)n, d, ldx, topk, ntiles, s, ps, pi);
-    hipLaunchKernelGGL(knn_merge, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, ps, pi, (int)n, topk, s, knn, scores);
+    const TopkPlan p = topk_plan(n, n, topk, 0, splits, 0);
+    float* ps = at<float>(scratch, p.part_s);
+    int* pi = at<int>(scratch, p.part_i);
+    topk_launch_tiles(knn_tiles<true>, knn_tiles<false>, topk_vec_ok(d, ldx, ldx, x, x), n, p.splits, st, x, (int)n, d, ldx, topk,
+                      p.ntiles, p.splits, ps, pi);
+    hipLaunchKernelGGL(knn_merge, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, ps, pi, (int)n, topk, p.splits, knn, scores);
     return (int)hipGetLastError();
 }
 

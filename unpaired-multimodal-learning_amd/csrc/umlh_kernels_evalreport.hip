@@ -7,9 +7,9 @@
 //                chunk.  The body is topk_tiles of umlh_topk.h, which knn_tiles (umlh_kernels_align.hip) and kp_tiles
 //                (umlh_kernels_knn.hip) run as well: here the train rows are the head's weight rows, nothing is excluded.
 //   ev_merge     merges the chunks' lists of a row (topk_merge) -> candidates int32 [n, kc]
-//   ev_refine    stage 2: z = (double)scale * (sum_k (double)x_k (double)w_jk + (double)b_j) for the kc candidates of a row (one
-//                wave per row: lane l adds k = l, l + 64, ... ascending, then a fixed xor tree), re-ranked by (z desc, class
-//                index asc); the first k -> cls, z rounded once to fp32 -> logit
+//   ev_refine    stage 2: z = (double)scale * (sum_k (double)x_k (double)w_jk + (double)b_j) for the kc candidates of a row,
+//                re-ranked by (z desc, class index asc); the first k -> cls, z rounded once to fp32 -> logit.  The body is
+//                topk_refine of umlh_topk.h, which kp_refine (umlh_kernels_knn.hip) runs as well.
 //   ev_classwise per-class support / top-1 hits / top-k hits / confusion counts from cls and the labels: 64-bit integer
 //                atomics only, one per distinct (label, prediction) pair of a wave; the outputs are ADDED into
 //
@@ -17,7 +17,7 @@
 // column chunks start on 256-column tile boundaries, every score is the same fma chain wherever it is computed, and the kept
 // lists are exact top-kc under a strict total order.
 //
-// List entries that no class has filled are SENTINELS: negative indices.  A sentinel is never used as an address: ev_refine
+// List entries that no class has filled are SENTINELS (umlh_topk.h): negative indices.  A sentinel is never used as an address: ev_refine
 // tests 0 <= j < C before every gather and fills the positions that have no valid candidate (a row of NaNs, whose comparisons
 // are all false) with class -1 and a NaN logit; ev_classwise treats a class outside [0, C) as "no prediction".
 #include "umlh_common.h"
@@ -50,49 +50,26 @@ __global__ __launch_bounds__(256) void ev_tiles(const float* __restrict__ x, int
 // topk_merge -> candidates int32 [n, kc], sentinels as they are.
 __global__ __launch_bounds__(64) void ev_merge(const float* __restrict__ part_s, const int* __restrict__ part_i, int n, int kc,
                                                int splits, int* __restrict__ cand) {
-    topk_merge(part_s, part_i, n, kc, splits, [=](long long o, float, int j) { cand[o] = j; });
+    topk_merge(part_s, part_i, n, kc, splits, TopkCandidates{cand});
 }
 
-// One wave per row (4 per workgroup).  Candidate c's logit: lane l sums x_k w_jk over k = l, l + 64, ... in double, then the
-// xor tree 32, 16, .., 1 (every lane ends with the same bits), + b_j, * scale; lane c keeps it.  Lane c < kc then ranks its
-// candidate among the VALID candidates (0 <= j < C) by (z desc, index asc) with NaN ordered as -inf; rank r < k writes position
-// r.  Positions [valid, k) -- there are none unless scores were NaN -- get class -1 and a NaN logit.  No LDS, no barrier.
+// A candidate's logit z = scale * (sum_k x_k w_jk + b_j), the larger first; z rounded once to fp32 -> logit.  A position without
+// a candidate gets class -1.
+struct EvLogit : TopkOperands {
+    const float* __restrict__ bias;      // [nt] or NULL
+    double sc;
+    static constexpr bool DESCENDING = true;
+    __device__ static double acc(float x, float w, double s) { return fma((double)x, (double)w, s); }
+    __device__ double finish(double s, int j) const { return sc * (s + (bias ? (double)bias[j] : 0.0)); }
+    __device__ static float publish(double z) { return (float)z; }
+    __device__ static int open_slot(int) { return -1; }
+};
+
+// Stage 2 (topk_refine, umlh_topk.h): one wave per row (4 per workgroup) re-ranks its kc candidates -> cls, logit [n, k].
 __global__ __launch_bounds__(256) void ev_refine(const float* __restrict__ x, int n, int ldx, const float* __restrict__ w, int C, int ldw,
                                                  const float* __restrict__ bias, const float* __restrict__ scale, int d, int k, int kc,
                                                  const int* __restrict__ cand, int* __restrict__ cls, float* __restrict__ logit) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long row = (long long)blockIdx.x * 4 + wave;
-    if (row >= n) return;                            // whole waves leave
-    const float* xr = x + row * (long long)ldx;
-    const double sc = scale ? (double)*scale : 1.0;
-    double myz = 0.0;
-    int myj = -1, valid = 0;
-    for (int c = 0; c < kc; ++c) {
-        const int j = cand[row * kc + c];            // wave-uniform
-        if (j < 0 || j >= C) continue;               // a sentinel is never an address
-        const float* wr = w + (long long)j * ldw;
-        double s = 0.0;
-        for (int kk = lane; kk < d; kk += 64) s = fma((double)xr[kk], (double)wr[kk], s);
-        s = wave_sum_f64(s);
-        const double z = sc * (s + (bias ? (double)bias[j] : 0.0));
-        if (lane == valid) { myz = z; myj = j; }     // valid candidates sit in lanes 0 .. valid - 1
-        ++valid;
-    }
-    const double ninf = -(double)INFINITY, key = myz > ninf ? myz : ninf;       // NaN -> -inf
-    int rank = 0;
-    for (int c = 0; c < kc; ++c) {                   // every lane takes part in the shuffles
-        const double z2 = __shfl(myz, c), key2 = z2 > ninf ? z2 : ninf;
-        const int j2 = __shfl(myj, c);
-        rank += j2 >= 0 && (key2 > key || (key2 == key && j2 < myj));
-    }
-    if (myj >= 0 && rank < k) {
-        cls[row * k + rank] = myj;
-        if (logit) logit[row * k + rank] = (float)myz;
-    }
-    if (lane >= valid && lane < k) {
-        cls[row * k + lane] = -1;
-        if (logit) logit[row * k + lane] = __builtin_nanf("");
-    }
+    topk_refine(EvLogit{{x, w, n, ldx, C, ldw, d, kc}, bias, scale ? (double)*scale : 1.0}, k, cand, cls, logit);
 }
 
 __device__ __forceinline__ void add_i64(long long* p, int v) { atomicAdd((unsigned long long*)p, (unsigned long long)v); }
@@ -144,47 +121,22 @@ __global__ __launch_bounds__(256) void ev_classwise(const int* __restrict__ cls,
     }
 }
 
-struct EvPlan { int kc, splits, ntiles; long long part_s, part_i, cand, total; };
-
-EvPlan ev_plan(long long n, long long C, int k, int splits) {
-    EvPlan p;
-    p.kc = (int)(k + EV_MARGIN < C ? k + EV_MARGIN : C);
-    p.splits = topk_splits(n, C, splits);
-    p.ntiles = (int)((C + TK_COLS - 1) / TK_COLS);
-    const long long list = align_up((long long)p.splits * n * p.kc * 4);
-    p.part_s = 0;
-    p.part_i = list;
-    p.cand = 2 * list;
-    p.total = p.cand + align_up(n * p.kc * 4);
-    return p;
-}
-
 }  // namespace
 
 // ---- plan and launchers (validation is the caller's: umlh_api.cpp) ----
 extern "C" {
 
 unsigned long long umlh_evalreport_bytes(long long n, long long C, int k, int splits) {
-    return (unsigned long long)ev_plan(n, C, k, splits).total;
+    return (unsigned long long)topk_plan(n, C, k, EV_MARGIN, splits, 0).total;
 }
 
 int umlh_evalreport_launch_topk(const float* x, long long n, int ldx, const float* w, long long C, int ldw, int d, const float* bias,
                                 const float* scale, int k, int splits, int* cls, float* logit, void* scratch, hipStream_t st) {
-    const EvPlan p = ev_plan(n, C, k, splits);
-    float* ps = at<float>(scratch, p.part_s);
-    int* pi = at<int>(scratch, p.part_i);
-    int* cand = at<int>(scratch, p.cand);
-    const dim3 grid((unsigned)((n + TK_ROWS - 1) / TK_ROWS), (unsigned)p.splits);
-    const bool vec = (d % 4 == 0) && (ldx % 4 == 0) && (ldw % 4 == 0) && ((((uintptr_t)x | (uintptr_t)w) & 15) == 0);
-    if (vec)
-        hipLaunchKernelGGL(ev_tiles<true>, grid, dim3(256), 0, st, x, (int)n, ldx, w, (int)C, ldw, bias, scale, d, p.kc, p.ntiles,
-                           p.splits, ps, pi);
-    else
-        hipLaunchKernelGGL(ev_tiles<false>, grid, dim3(256), 0, st, x, (int)n, ldx, w, (int)C, ldw, bias, scale, d, p.kc, p.ntiles,
-                           p.splits, ps, pi);
-    hipLaunchKernelGGL(ev_merge, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, ps, pi, (int)n, p.kc, p.splits, cand);
-    hipLaunchKernelGGL(ev_refine, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, x, (int)n, ldx, w, (int)C, ldw, bias, scale, d, k,
-                       p.kc, cand, cls, logit);
+    const TopkPlan p = topk_plan(n, C, k, EV_MARGIN, splits, 0);
+    topk_launch_tiles(ev_tiles<true>, ev_tiles<false>, topk_vec_ok(d, ldx, ldw, x, w), n, p.splits, st, x, (int)n, ldx, w, (int)C, ldw,
+                      bias, scale, d, p.kc, p.ntiles, p.splits, at<float>(scratch, p.part_s), at<int>(scratch, p.part_i));
+    topk_launch_rerank(ev_merge, ev_refine, p, n, scratch, st, x, (int)n, ldx, w, (int)C, ldw, bias, scale, d, k, p.kc,
+                       at<int>(scratch, p.cand), cls, logit);
     return (int)hipGetLastError();
 }
 

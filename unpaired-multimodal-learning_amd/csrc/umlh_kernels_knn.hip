@@ -7,9 +7,9 @@
 //                umlh_topk.h, which knn_tiles (umlh_kernels_align.hip) runs as well: here on two matrices, with the score
 //                epilogue above and without the self exclusion.
 //   kp_merge     merges the chunks' lists of a query (topk_merge) -> candidates int32 [n_query, kc]
-//   kp_refine    stage 2: sum_k (q_k - t_k)^2 in double from the fp32 inputs for the kc candidates of a query (one wave per
-//                query: lane l adds k = l, l + 64, ... ascending, then a fixed xor tree), re-ranked by (value asc, index asc);
-//                the first k -> idx, sqrt -> dist
+//   kp_refine    stage 2: sum_k (q_k - t_k)^2 in double from the fp32 inputs for the kc candidates of a query, re-ranked by
+//                (value asc, index asc); the first k -> idx, sqrt -> dist.  The body is topk_refine of umlh_topk.h, which
+//                ev_refine (umlh_kernels_evalreport.hip) runs as well.
 //   kp_vote      the most frequent label among labels[idx[i, :k]], count ties to the smallest label value; integer count of
 //                pred == y
 //
@@ -17,10 +17,10 @@
 // `splits`: column chunks start on 256-column tile boundaries, every score is the same fma chain wherever it is computed, and
 // the kept lists are exact top-kc under a strict total order.
 //
-// List entries that no train row has filled are SENTINELS: negative indices -1 - e, compared as unsigned so that they sort
-// behind every real index at an equal score.  A sentinel is never used as an address: kp_refine and kp_vote test
-// 0 <= j < n_train before every gather, and kp_refine fills the positions that have no valid candidate (a query row of NaNs,
-// whose comparisons are all false) with the in-range index of the position itself and a NaN distance.
+// List entries that no train row has filled are SENTINELS (umlh_topk.h): negative indices.  A sentinel is never used as an
+// address: kp_refine and kp_vote test 0 <= j < n_train before every gather, and kp_refine fills the positions that have no
+// valid candidate (a query row of NaNs, whose comparisons are all false; NaN train rows when n_train < k + their count) with
+// the in-range index of the position itself and a NaN distance.
 #include "umlh_common.h"
 #include "umlh_launch.h"
 #include "umlh_topk.h"
@@ -57,51 +57,24 @@ __global__ __launch_bounds__(256) void kp_tiles(const float* __restrict__ qx, in
 // topk_merge -> candidates int32 [n_query, kc], sentinels as they are.
 __global__ __launch_bounds__(64) void kp_merge(const float* __restrict__ part_s, const int* __restrict__ part_i, int nq, int kc,
                                                int splits, int* __restrict__ cand) {
-    topk_merge(part_s, part_i, nq, kc, splits, [=](long long o, float, int j) { cand[o] = j; });
+    topk_merge(part_s, part_i, nq, kc, splits, TopkCandidates{cand});
 }
 
-// One wave per query (4 per workgroup).  Candidate c's squared distance: lane l sums (q_k - t_k)^2 over k = l, l + 64, ... in
-// double, then the xor tree 32, 16, .., 1 (every lane ends with the same bits); lane c keeps it.  Lane c < kc then ranks its
-// candidate among the VALID candidates (0 <= j < nt) by (value, index) with NaN ordered as +inf; rank r < k writes position r.
-// Positions [valid, k) -- there are none unless the row's scores were NaN -- get the index of the position (k <= nt) and a
-// NaN distance.  No LDS, no barrier.
+// A candidate's squared distance sum_k (q_k - t_k)^2, the smaller first; sqrt -> dist.  A position without a candidate gets its
+// own index (k <= n_train: in range).
+struct KpDistance : TopkOperands {
+    static constexpr bool DESCENDING = false;
+    __device__ static double acc(float q, float t, double s) { const double df = (double)q - (double)t; return fma(df, df, s); }
+    __device__ static double finish(double s, int) { return s; }
+    __device__ static float publish(double v) { return (float)sqrt(v); }
+    __device__ static int open_slot(int lane) { return lane; }
+};
+
+// Stage 2 (topk_refine, umlh_topk.h): one wave per query (4 per workgroup) re-ranks its kc candidates -> idx, dist [n_query, k].
 __global__ __launch_bounds__(256) void kp_refine(const float* __restrict__ qx, int nq, int ldq, const float* __restrict__ tx, int nt,
                                                  int ldt, int d, int k, int kc, const int* __restrict__ cand, int* __restrict__ idx,
                                                  float* __restrict__ dist) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long row = (long long)blockIdx.x * 4 + wave;
-    if (row >= nq) return;                           // whole waves leave
-    const float* q = qx + row * (long long)ldq;
-    double myv = 0.0;
-    int myj = -1, valid = 0;
-    for (int c = 0; c < kc; ++c) {
-        const int j = cand[row * kc + c];            // wave-uniform
-        if (j < 0 || j >= nt) continue;              // a sentinel is never an address
-        const float* t = tx + (long long)j * ldt;
-        double s = 0.0;
-        for (int kk = lane; kk < d; kk += 64) {
-            const double df = (double)q[kk] - (double)t[kk];
-            s = fma(df, df, s);
-        }
-        s = wave_sum_f64(s);
-        if (lane == c) { myv = s; myj = j; }
-        ++valid;
-    }
-    const double inf = (double)INFINITY, key = myv < inf ? myv : inf;
-    int rank = 0;
-    for (int c = 0; c < kc; ++c) {                   // every lane takes part in the shuffles
-        const double v2 = __shfl(myv, c), key2 = v2 < inf ? v2 : inf;
-        const int j2 = __shfl(myj, c);
-        rank += j2 >= 0 && (key2 < key || (key2 == key && j2 < myj));
-    }
-    if (myj >= 0 && rank < k) {
-        idx[row * k + rank] = myj;
-        if (dist) dist[row * k + rank] = (float)sqrt(myv);
-    }
-    if (lane >= valid && lane < k) {
-        idx[row * k + lane] = lane;
-        if (dist) dist[row * k + lane] = __builtin_nanf("");
-    }
+    topk_refine(KpDistance{{qx, tx, nq, ldq, nt, ldt, d, kc}}, k, cand, idx, dist);
 }
 
 // Thread per query.  The winner has the largest count; among equal counts the smallest label value (sklearn: argmax over the
@@ -141,21 +114,8 @@ __global__ __launch_bounds__(256) void kp_vote(const int* __restrict__ idx, int 
     }
 }
 
-struct KpPlan { int kc, splits, ntiles; long long norms, part_s, part_i, cand, total; };
-
-KpPlan kp_plan(long long nt, long long nq, int k, int splits) {
-    KpPlan p;
-    p.kc = (int)(k + KP_MARGIN < nt ? k + KP_MARGIN : nt);
-    p.splits = topk_splits(nq, nt, splits);
-    p.ntiles = (int)((nt + TK_COLS - 1) / TK_COLS);
-    const long long list = align_up((long long)p.splits * nq * p.kc * 4);
-    p.norms = 0;
-    p.part_s = align_up(nt * 4);
-    p.part_i = p.part_s + list;
-    p.cand = p.part_i + list;
-    p.total = p.cand + align_up(nq * p.kc * 4);
-    return p;
-}
+// |t|^2 [n_train] in front of the lists and candidates
+TopkPlan kp_plan(long long nt, long long nq, int k, int splits) { return topk_plan(nq, nt, k, KP_MARGIN, splits, nt * 4); }
 
 }  // namespace
 
@@ -168,23 +128,13 @@ unsigned long long umlh_knn_bytes(long long nt, long long nq, int k, int splits)
 
 int umlh_knn_launch_search(const float* train, long long nt, int ldt, const float* query, long long nq, int ldq, int d, int k,
                            int splits, int* idx, float* dist, void* scratch, hipStream_t st) {
-    const KpPlan p = kp_plan(nt, nq, k, splits);
-    float* tn = at<float>(scratch, p.norms);
-    float* ps = at<float>(scratch, p.part_s);
-    int* pi = at<int>(scratch, p.part_i);
-    int* cand = at<int>(scratch, p.cand);
+    const TopkPlan p = kp_plan(nt, nq, k, splits);
+    float* tn = at<float>(scratch, 0);
     hipLaunchKernelGGL(kp_norms, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, train, nt, d, ldt, tn);
-    const dim3 grid((unsigned)((nq + TK_ROWS - 1) / TK_ROWS), (unsigned)p.splits);
-    const bool vec = (d % 4 == 0) && (ldt % 4 == 0) && (ldq % 4 == 0) && ((((uintptr_t)train | (uintptr_t)query) & 15) == 0);
-    if (vec)
-        hipLaunchKernelGGL(kp_tiles<true>, grid, dim3(256), 0, st, query, (int)nq, ldq, train, (int)nt, ldt, tn, d, p.kc, p.ntiles,
-                           p.splits, ps, pi);
-    else
-        hipLaunchKernelGGL(kp_tiles<false>, grid, dim3(256), 0, st, query, (int)nq, ldq, train, (int)nt, ldt, tn, d, p.kc, p.ntiles,
-                           p.splits, ps, pi);
-    hipLaunchKernelGGL(kp_merge, dim3((unsigned)((nq + 63) / 64)), dim3(64), 0, st, ps, pi, (int)nq, p.kc, p.splits, cand);
-    hipLaunchKernelGGL(kp_refine, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st, query, (int)nq, ldq, train, (int)nt, ldt, d, k,
-                       p.kc, cand, idx, dist);
+    topk_launch_tiles(kp_tiles<true>, kp_tiles<false>, topk_vec_ok(d, ldq, ldt, query, train), nq, p.splits, st, query, (int)nq, ldq,
+                      train, (int)nt, ldt, tn, d, p.kc, p.ntiles, p.splits, at<float>(scratch, p.part_s), at<int>(scratch, p.part_i));
+    topk_launch_rerank(kp_merge, kp_refine, p, nq, scratch, st, query, (int)nq, ldq, train, (int)nt, ldt, d, k, p.kc,
+                       at<int>(scratch, p.cand), idx, dist);
     return (int)hipGetLastError();
 }
 

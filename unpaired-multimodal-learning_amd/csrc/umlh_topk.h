@@ -1,7 +1,7 @@
 // The streaming top-k neighbour core shared by the alignment k-NN (knn_tiles / knn_merge, umlh_kernels_align.hip), the
-// k-NN probe (kp_tiles / kp_merge, umlh_kernels_knn.hip) and the class report (ev_tiles / ev_merge,
-// umlh_kernels_evalreport.hip), and the 32 x 64 Gram k loop that rbf_tiles
-// (umlh_kernels_align_ext.hip) runs as well.  Device code for the .hip files only; the kernels stay where they are launched.
+// k-NN probe (kp_tiles / kp_merge / kp_refine, umlh_kernels_knn.hip) and the class report (ev_tiles / ev_merge / ev_refine,
+// umlh_kernels_evalreport.hip), the 32 x 64 Gram k loop that rbf_tiles (umlh_kernels_align_ext.hip) runs as well, and the
+// scratch plan and launch sequence of the three users.  For the .hip files only; the kernels stay where they are launched.
 //
 // A workgroup takes a strip of 32 query rows and a chunk of 256-column tiles of the train rows, scores every (row, column)
 // pair on v_mfma_f32_32x32x2_f32 (a k-ordered fp32 fma chain) and keeps, per row, the `width` best columns under the strict
@@ -14,6 +14,7 @@
 // address; a caller that publishes indices says what a negative one becomes.
 #pragma once
 #include "umlh_common.h"
+#include "umlh_launch.h"
 
 constexpr int TK_ROWS = 32;              // query rows of a workgroup's strip
 constexpr int TK_COLS = 256;             // train rows (columns) of a tile: 4 waves x 64
@@ -29,6 +30,45 @@ inline int topk_splits(long long n_query, long long n_train, int splits) {
     long long s = splits > 0 ? splits : (TK_TARGET_WG + strips - 1) / strips;
     if (s > TK_MAX_SPLITS) s = TK_MAX_SPLITS;
     return (int)(s < 1 ? 1 : (s > ntiles ? ntiles : s));
+}
+
+// Scratch of a launch: `front_bytes` of the caller's own, the chunks' partial lists (scores, then indices: [splits][nq][kc]
+// each) and, for a two-stage user, the merged candidates [nq][kc], kc = min(k + margin, nt).  A user without stage 2 passes
+// margin 0 (its k < nt: kc = k) and needs `cand` bytes: its scratch ends where the candidates would start.
+struct TopkPlan { int kc, splits, ntiles; long long part_s, part_i, cand, total; };
+
+inline TopkPlan topk_plan(long long nq, long long nt, int k, int margin, int splits, long long front_bytes) {
+    TopkPlan p;
+    p.kc = (int)(k + margin < nt ? k + margin : nt);
+    p.splits = topk_splits(nq, nt, splits);
+    p.ntiles = (int)((nt + TK_COLS - 1) / TK_COLS);
+    const long long list = align_up((long long)p.splits * nq * p.kc * 4);
+    p.part_s = align_up(front_bytes);
+    p.part_i = p.part_s + list;
+    p.cand = p.part_i + list;
+    p.total = p.cand + align_up(nq * p.kc * 4);
+    return p;
+}
+
+// load4<true> may be used: whole float4s in every row, every row on a 16-byte boundary.
+inline bool topk_vec_ok(int d, int ldq, int ldt, const float* q, const float* t) {
+    return (d % 4 == 0) && (ldq % 4 == 0) && (ldt % 4 == 0) && ((((uintptr_t)q | (uintptr_t)t) & 15) == 0);
+}
+
+// Stage 1: the tiles kernel, in its vector or its scalar form, on the strip x splits grid.
+template <class... A, class... B>
+inline void topk_launch_tiles(void (*vec)(A...), void (*scalar)(A...), bool vec_ok, long long nq, int splits, hipStream_t st, B... args) {
+    const dim3 grid((unsigned)((nq + TK_ROWS - 1) / TK_ROWS), (unsigned)splits);
+    hipLaunchKernelGGL(vec_ok ? vec : scalar, grid, dim3(256), 0, st, args...);
+}
+
+// The merge of a plan's lists into its candidates (thread per row), then stage 2 on them (wave per row) with its own arguments.
+template <class... A, class... B>
+inline void topk_launch_rerank(void (*merge)(const float*, const int*, int, int, int, int*), void (*refine)(A...), const TopkPlan& p,
+                               long long nq, void* scratch, hipStream_t st, B... refine_args) {
+    hipLaunchKernelGGL(merge, dim3((unsigned)((nq + 63) / 64)), dim3(64), 0, st, at<float>(scratch, p.part_s), at<int>(scratch, p.part_i),
+                       (int)nq, p.kc, p.splits, at<int>(scratch, p.cand));
+    hipLaunchKernelGGL(refine, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st, refine_args...);
 }
 
 __device__ __forceinline__ bool topk_better(float s, int j, float ts, int tj) {
@@ -243,4 +283,57 @@ __device__ __forceinline__ void topk_merge(const float* __restrict__ part_s, con
         int* ti = ci; ci = ni; ni = ti;
     }
     for (int q = 0; q < width; ++q) write(row * width + q, cs[q], ci[q]);
+}
+
+// The write of a two-stage user's merge kernel: candidates int32 [nq, kc], sentinels as they are.
+struct TopkCandidates { int* __restrict__ cand; __device__ void operator()(long long o, float, int j) const { cand[o] = j; } };
+
+// Stage 2 of a two-stage user: a row's merged candidates scored again in double from the fp32 operands and re-ranked; the first
+// k -> out_idx / out_val [nq, k] (out_val may be NULL).  A policy R starts from TopkOperands (width = kc) and adds
+//   static constexpr bool DESCENDING                 the larger value ranks first (else the smaller); equal values by index asc
+//   static double acc(float q, float t, double s)    one element of the row sum
+//   double finish(double s, int j) const             the ranked value, from the row sum and the column
+//   static float publish(double v)                   what out_val gets
+//   static int open_slot(int lane)                   what out_idx gets at a position that no candidate fills (out_val: NaN)
+// One wave per row (4 per workgroup).  Lane l adds k = l, l + 64, ... ascending, then the xor tree of wave_sum_f64 (every lane ends
+// with the same bits).  Only a VALID candidate, 0 <= j < nt, is scored: a sentinel is never an address.  The v-th valid candidate
+// parks in lane v, which is also its place c in the list: a merged list carries its sentinels last (they sit at -inf behind every
+// real index, topk_better).  A lane ranks its candidate among the valid ones with NaN last (NaN and the worst infinity share one
+// key; the index settles equal keys); rank r < k writes position r.  Positions [valid, k) -- none unless scores were NaN -- are
+// open slots.  No LDS, no barrier.
+template <class R>
+__device__ __forceinline__ void topk_refine(const R& r, int k, const int* __restrict__ cand, int* __restrict__ out_idx,
+                                            float* __restrict__ out_val) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, kc = r.width;
+    const long long row = (long long)blockIdx.x * 4 + wave;
+    if (row >= r.nq) return;                         // whole waves leave
+    const float* q = r.qx + row * (long long)r.ldq;
+    double myv = 0.0;
+    int myj = -1, valid = 0;
+    for (int c = 0; c < kc; ++c) {
+        const int j = cand[row * kc + c];            // wave-uniform
+        if (j < 0 || j >= r.nt) continue;
+        const float* t = r.tx + (long long)j * r.ldt;
+        double s = 0.0;
+        for (int kk = lane; kk < r.d; kk += 64) s = R::acc(q[kk], t[kk], s);
+        const double v = r.finish(wave_sum_f64(s), j);
+        if (lane == valid) { myv = v; myj = j; }
+        ++valid;
+    }
+    const auto first = [](double a, double b) { return R::DESCENDING ? a > b : a < b; };
+    const double worst = R::DESCENDING ? -(double)INFINITY : (double)INFINITY, key = first(myv, worst) ? myv : worst;
+    int rank = 0;
+    for (int c = 0; c < kc; ++c) {                   // every lane takes part in the shuffles
+        const double v2 = __shfl(myv, c), key2 = first(v2, worst) ? v2 : worst;
+        const int j2 = __shfl(myj, c);
+        rank += j2 >= 0 && (first(key2, key) || (key2 == key && j2 < myj));
+    }
+    if (myj >= 0 && rank < k) {
+        out_idx[row * k + rank] = myj;
+        if (out_val) out_val[row * k + rank] = R::publish(myv);
+    }
+    if (lane >= valid && lane < k) {
+        out_idx[row * k + lane] = R::open_slot(lane);
+        if (out_val) out_val[row * k + lane] = __builtin_nanf("");
+    }
 }
