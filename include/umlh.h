@@ -880,6 +880,59 @@ int  umlh_eval_topk(const float* x, int64_t n, int32_t ldx, const float* w, int6
 int  umlh_eval_classwise(const int32_t* cls, int64_t n, int32_t k, const int64_t* labels, int64_t n_class,
                          int64_t* support, int64_t* hit1, int64_t* hitk, int64_t* confusion_or_null, int64_t* misc2, void* stream);
 
+/* ---- outlier clamp and feature preparation of the alignment metrics: the module-level remove_outliers and
+ * compute_knn_accuracy of vision_language/metrics.py (the same in MultiBench/ and Gaussian_experiment/).
+ * Additive to ABI v11: umlh_version() is unchanged, callers detect the feature by these symbols.  Features are row-major fp32
+ * [n, d] with row stride ld >= d.  |x| is ordered by key = bits(x) & 0x7fffffff as an unsigned integer: the order of the
+ * absolute values, -0.0 equal to +0.0, every NaN pattern above Inf (where torch.sort puts NaN).  Order statistics are found by
+ * an MSB-first radix select (four 8-bit digits), never by a sort: they are exact, so every result below is bitwise
+ * reproducible across calls and streams; counters are integers and no sum uses a float atomic.  Every argument check happens
+ * before any HIP call; `scratch` is caller device memory of at least umlh_outlier_scratch_bytes(kind, n, d) bytes; everything
+ * runs on `stream` and nothing is read back to the host.
+ * Envelope: n >= 1, 1 <= d < 2^31, ld >= d, n * d < 2^40; anything else is UMLH_E_INVALID. */
+#define UMLH_OUTLIER_ROW_QUANTILE 0
+#define UMLH_OUTLIER_ABS_KTH      1
+#define UMLH_OUTLIER_KNN_ACCURACY 2
+/* Row widths at which umlh_row_abs_quantile and umlh_clamp_rows(normalize = 1) change kernels: up to WAVE_COLS columns a wave
+ * works on a row (four rows per workgroup); up to LDS_COLS a workgroup reads its row from memory once and keeps it in LDS
+ * (60 KiB: two workgroups per CU); a longer row is streamed once per pass. */
+#define UMLH_ROW_QUANTILE_WAVE_COLS 1024
+#define UMLH_ROW_QUANTILE_LDS_COLS  15360
+
+/* Scratch bytes of the entry point `kind` (above); for UMLH_OUTLIER_KNN_ACCURACY d is the list width m.  0 on invalid
+ * arguments (unknown kind, n < 1, d < 1, d >= 2^31, n * d >= 2^40; n >= 2^31 for the accuracy). */
+uint64_t umlh_outlier_scratch_bytes(int32_t kind, int64_t n, int64_t d);
+/* torch.quantile(feats.abs().flatten(start_dim=1), q, dim=1).mean() (metrics.py:336).  With s the ascending |x| of a row,
+ * pos = q * (d - 1) in double, lo = floor(pos), hi = min(lo + 1, d - 1):
+ *   lo_val[i] = s[lo], hi_val[i] = s[hi]                              (fp32 [n]; either may be NULL)
+ *   quant[i]  = s[lo] + (s[hi] - s[lo]) * (pos - lo)                  formed in double, rounded once (fp32 [n], required)
+ *   mean64[0] = sum_i quant[i] / n in double, in a fixed order        (may be NULL);   q_val[0] = (float)mean64 (required)
+ * A row that holds a NaN gets quant = NaN (as torch.quantile) while its lo_val and hi_val follow the key order; mean64 and q_val
+ * are then NaN.  0 <= q < 1 (q = 1 is the caller's identity case, metrics.py:328-329). */
+int  umlh_row_abs_quantile(const float* x, int64_t n, int64_t d, int64_t ld, double q, float* lo_val, float* hi_val,
+                           float* quant, double* mean64, float* q_val, void* scratch, uint64_t scratch_bytes, void* stream);
+/* feats.view(-1).abs().sort().values[k] (metrics.py:333): the element of rank k (0-based, ascending) among all n * d values
+ * of |x| -> out[0], one fp32 in device memory, bit-exact.  Four launches (one per digit); every workgroup adds its LDS counters
+ * into 64-bit global counters and the one that takes the last ticket picks the digit: no workgroup waits for another.
+ * 0 <= k < n * d. */
+int  umlh_abs_kth(const float* x, int64_t n, int64_t d, int64_t ld, int64_t k, float* out, void* scratch,
+                  uint64_t scratch_bytes, void* stream);
+/* feats.clamp(-q_val, q_val) (metrics.py:341) with q_val ONE fp32 in device memory (never read on the host), torch.clamp's
+ * tensor-bound semantics: a NaN element stays NaN, a NaN bound makes every element NaN, otherwise min(max(x, -q), q), so
+ * +-Inf become +-q and -0.0 stays -0.0.  normalize != 0: the clamped row is then divided by max(|row|_2, 1e-12)
+ * (F.normalize(dim=-1)) in the same launch; |row|^2 is summed in double in a fixed order, the division is one fp32 division.
+ * out is row-major [n, d] with its own row stride ldo >= d; out == x (with ldo == ldx) works in place.  No scratch. */
+int  umlh_clamp_rows(const float* x, int64_t n, int64_t d, int64_t ldx, const float* q_val, int32_t normalize, float* out,
+                     int64_t ldo, void* stream);
+/* compute_knn_accuracy(knn) (metrics.py:258-269): the share of rows i of the int32 list knn [n, m] that contain the value
+ * i (m = topk, or topk^2 for the reference's knn_A[knn_B] of shape [n, k, k]).  Hits are summed as integers and the mean is
+ * formed once in double -> out[0].  Row i starts at knn + i * ld, ld >= m; ld = 0 makes every row read the same m entries: the
+ * share of the indices 0 .. n-1 found anywhere in ONE table of m entries, which is what the reference's expression evaluates to
+ * for a 2-D list [n, k] (its comparison against arange(n).view(-1, 1, 1) broadcasts to [n, n, k]; m = n * k there).
+ * 1 <= n < 2^31, 1 <= m < 2^31. */
+int  umlh_knn_accuracy(const int32_t* knn, int64_t n, int64_t m, int64_t ld, double* out, void* scratch, uint64_t scratch_bytes,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

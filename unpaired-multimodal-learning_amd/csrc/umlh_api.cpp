@@ -2503,3 +2503,84 @@ int umlh_eval_classwise(const int32_t* cls, int64_t n, int32_t k, const int64_t*
            "umlh_eval_classwise");
     return UMLH_OK;
 }
+
+// ---- outlier clamp and feature preparation (kernels: umlh_kernels_outlier.hip); every check precedes the first HIP call ----
+static bool outlier_shape_ok(int64_t n, int64_t d) {
+    return n >= 1 && d >= 1 && d < (1LL << 31) && n < (1LL << 40) && n * d < (1LL << 40);      // n, d < 2^40, 2^31: no overflow
+}
+
+uint64_t umlh_outlier_scratch_bytes(int32_t kind, int64_t n, int64_t d) {
+    if (!outlier_shape_ok(n, d)) return 0;
+    if (kind == UMLH_OUTLIER_ROW_QUANTILE) return umlh_outlier_quantile_bytes(n);
+    if (kind == UMLH_OUTLIER_ABS_KTH) return umlh_outlier_kth_bytes();
+    if (kind == UMLH_OUTLIER_KNN_ACCURACY) return n < (1LL << 31) ? umlh_outlier_accuracy_bytes(n) : 0;
+    return 0;
+}
+
+static int outlier_check(const char* who, int64_t n, int64_t d, int64_t ld) {
+    if (!outlier_shape_ok(n, d))
+        return fail(UMLH_E_INVALID, "%s: n=%lld d=%lld (need n >= 1, 1 <= d < 2^31, n * d < 2^40)", who, (long long)n, (long long)d);
+    if (ld < d) return fail(UMLH_E_INVALID, "%s: row stride %lld < d=%lld", who, (long long)ld, (long long)d);
+    return UMLH_OK;
+}
+
+int umlh_row_abs_quantile(const float* x, int64_t n, int64_t d, int64_t ld, double q, float* lo_val, float* hi_val, float* quant,
+                          double* mean64, float* q_val, void* scratch, uint64_t scratch_bytes, void* stream) {
+    if (!x || !quant || !q_val || !scratch)
+        return fail(UMLH_E_INVALID, "umlh_row_abs_quantile: null pointer (x, quant, q_val and scratch are required)");
+    if (int e = outlier_check("umlh_row_abs_quantile", n, d, ld)) return e;
+    if (!(q >= 0.0 && q < 1.0)) return fail(UMLH_E_INVALID, "umlh_row_abs_quantile: q=%g outside [0, 1)", q);
+    const uint64_t need = umlh_outlier_quantile_bytes(n);
+    if (scratch_bytes < need)
+        return fail(UMLH_E_INVALID, "umlh_row_abs_quantile: scratch_bytes=%llu, %llu needed", (unsigned long long)scratch_bytes,
+                    (unsigned long long)need);
+    if ((reinterpret_cast<uintptr_t>(scratch) & 7) != 0) return fail(UMLH_E_INVALID, "umlh_row_abs_quantile: scratch must be 8-byte aligned");
+    const double pos = q * (double)(d - 1);
+    int64_t lo = (int64_t)std::floor(pos);
+    if (lo > d - 1) lo = d - 1;
+    const int64_t hi = lo + 1 < d ? lo + 1 : d - 1;
+    HIPCHK(umlh_outlier_launch_quantile(x, n, (int)d, ld, (int)lo, (int)hi, pos - (double)lo, lo_val, hi_val, quant, mean64, q_val,
+                                        scratch, (hipStream_t)stream), "umlh_row_abs_quantile");
+    return UMLH_OK;
+}
+
+int umlh_abs_kth(const float* x, int64_t n, int64_t d, int64_t ld, int64_t k, float* out, void* scratch, uint64_t scratch_bytes,
+                 void* stream) {
+    if (!x || !out || !scratch) return fail(UMLH_E_INVALID, "umlh_abs_kth: null pointer (x, out and scratch are required)");
+    if (int e = outlier_check("umlh_abs_kth", n, d, ld)) return e;
+    if (k < 0 || k >= n * d) return fail(UMLH_E_INVALID, "umlh_abs_kth: k=%lld outside 0..n*d-1 = %lld", (long long)k, (long long)(n * d - 1));
+    const uint64_t need = umlh_outlier_kth_bytes();
+    if (scratch_bytes < need)
+        return fail(UMLH_E_INVALID, "umlh_abs_kth: scratch_bytes=%llu, %llu needed", (unsigned long long)scratch_bytes,
+                    (unsigned long long)need);
+    if ((reinterpret_cast<uintptr_t>(scratch) & 7) != 0) return fail(UMLH_E_INVALID, "umlh_abs_kth: scratch must be 8-byte aligned");
+    HIPCHK(umlh_outlier_launch_kth(x, n, d, ld, k, out, scratch, (hipStream_t)stream), "umlh_abs_kth");
+    return UMLH_OK;
+}
+
+int umlh_clamp_rows(const float* x, int64_t n, int64_t d, int64_t ldx, const float* q_val, int32_t normalize, float* out,
+                    int64_t ldo, void* stream) {
+    if (!x || !q_val || !out) return fail(UMLH_E_INVALID, "umlh_clamp_rows: null pointer (x, q_val and out are required)");
+    if (int e = outlier_check("umlh_clamp_rows", n, d, ldx)) return e;
+    if (ldo < d) return fail(UMLH_E_INVALID, "umlh_clamp_rows: output row stride %lld < d=%lld", (long long)ldo, (long long)d);
+    if (out == x && ldo != ldx)
+        return fail(UMLH_E_INVALID, "umlh_clamp_rows: in place needs ldo == ldx (ldo=%lld ldx=%lld)", (long long)ldo, (long long)ldx);
+    HIPCHK(umlh_outlier_launch_clamp(x, n, (int)d, ldx, q_val, normalize != 0, out, ldo, (hipStream_t)stream), "umlh_clamp_rows");
+    return UMLH_OK;
+}
+
+int umlh_knn_accuracy(const int32_t* knn, int64_t n, int64_t m, int64_t ld, double* out, void* scratch, uint64_t scratch_bytes,
+                      void* stream) {
+    if (!knn || !out || !scratch) return fail(UMLH_E_INVALID, "umlh_knn_accuracy: null pointer (knn, out and scratch are required)");
+    if (!outlier_shape_ok(n, m) || n >= (1LL << 31))
+        return fail(UMLH_E_INVALID, "umlh_knn_accuracy: n=%lld m=%lld (need 1 <= n < 2^31, 1 <= m < 2^31, n * m < 2^40)", (long long)n,
+                    (long long)m);
+    if (ld != 0 && ld < m) return fail(UMLH_E_INVALID, "umlh_knn_accuracy: row stride %lld (need 0 or >= m=%lld)", (long long)ld, (long long)m);
+    const uint64_t need = umlh_outlier_accuracy_bytes(n);
+    if (scratch_bytes < need)
+        return fail(UMLH_E_INVALID, "umlh_knn_accuracy: scratch_bytes=%llu, %llu needed", (unsigned long long)scratch_bytes,
+                    (unsigned long long)need);
+    if ((reinterpret_cast<uintptr_t>(scratch) & 7) != 0) return fail(UMLH_E_INVALID, "umlh_knn_accuracy: scratch must be 8-byte aligned");
+    HIPCHK(umlh_outlier_launch_accuracy(knn, n, m, ld, out, scratch, (hipStream_t)stream), "umlh_knn_accuracy");
+    return UMLH_OK;
+}

@@ -188,6 +188,17 @@ int umlh_rollout_launch(const umlh_rollout_cfg_t* cfg, const float* const* P, co
 long long umlh_spectrum_partials(int B, int T, int d);        // partial vectors of one call; -1: more than the final kernel takes
 unsigned long long umlh_spectrum_bytes(int B, int T, int d);
 int umlh_spectrum_launch(const float* x, long long ldb, long long ldt, int B, int T, int d, double* out, void* scratch, hipStream_t st);
+// ---- umlh_kernels_outlier.hip: row quantile and global k-th of |x|, clamp (+ row normalisation), k-NN accuracy ----
+unsigned long long umlh_outlier_quantile_bytes(long long n);
+unsigned long long umlh_outlier_kth_bytes(void);
+unsigned long long umlh_outlier_accuracy_bytes(long long n);
+int umlh_outlier_launch_quantile(const float* x, long long n, int d, long long ld, int lo, int hi, double frac, float* lo_val,
+                                 float* hi_val, float* quant, double* mean64, float* q_val, void* scratch, hipStream_t st);
+int umlh_outlier_launch_kth(const float* x, long long n, long long d, long long ld, long long k, float* out, void* scratch,
+                            hipStream_t st);
+int umlh_outlier_launch_clamp(const float* x, long long n, int d, long long ldx, const float* q_val, int normalize, float* out,
+                              long long ldo, hipStream_t st);
+int umlh_outlier_launch_accuracy(const int* knn, long long n, long long m, long long ld, double* out, void* scratch, hipStream_t st);
 
 // ---- umlh_api.cpp, for umlh_encoder.cpp ----
 // out[M,N] (ldo == N) = epilogue(A B^T) with the operand layouts of umlh_gemm_f32.  `splits` K-slabs go to `slabs`

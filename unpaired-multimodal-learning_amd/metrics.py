@@ -6,6 +6,9 @@ Built: ``cka`` with ``kernel_metric='ip'`` and ``unbiased=False`` (what every ca
 ``svcca`` run as HIP kernels through ``umlh.align.measure``, which takes the same names and keyword arguments; ``svcca``
 is ``umlh.align.svcca(feats_A, feats_B, cca_dim)``); unknown names raise ``ValueError`` as the reference does.  Like the reference's ``.item()``, ``measure`` returns Python floats.
 
+The module-level ``remove_outliers`` and ``compute_knn_accuracy`` are built too (``umlh.align.remove_outliers``,
+``umlh.align.knn_accuracy``: a radix select instead of the reference's sorts), so every name of the reference's module exists here.
+
 Neighbours are by raw inner product with self excluded; exact ties go to the smaller column index (the reference leaves
 that order to torch's sort).  Importing this module does not touch the GPU.
 """
@@ -90,6 +93,25 @@ def compute_nearest_neighbors(feats, topk=1):
     device, like the reference's argsort."""
     assert feats.ndim == 2, f"Expected feats to be 2D, got {feats.ndim}"
     return umlh.align.knn(feats, topk).long()
+
+
+def compute_knn_accuracy(knn):
+    """The share of rows i of ``knn`` [N, topk, topk] that contain i (metrics.py:258-269; what ``cycle_knn`` passes): a 0-d fp32
+    device tensor, like the reference's ``.float()...mean()``.  For a 2-D ``knn`` [N, topk] the reference's comparison against
+    ``arange(n).view(-1, 1, 1)`` broadcasts to [N, N, topk], so its value is the share of indices found ANYWHERE in the list; that
+    is reproduced (``umlh.align.knn_accuracy(knn)`` is the per-row form for either shape)."""
+    return umlh.align.knn_accuracy(knn, whole_table=knn.ndim == 2).to(torch.float32)
+
+
+def remove_outliers(feats, q, exact=False, max_threshold=None):
+    """``feats.clamp(-q_val, q_val)`` with ``q_val`` the mean over rows of the q-quantile of ``|feats|`` flattened from dim 1, or
+    with ``exact`` the element ``int(q * feats.numel())`` of all sorted ``|feats|`` (metrics.py:327-341); an fp32 device tensor.
+    ``q == 1`` returns ``feats`` itself.  An ``exact`` index outside the tensor raises ``ValueError`` (the reference: ``IndexError``).
+    ``max_threshold`` is accepted and has no effect: the reference computes ``max(max_threshold, q_val)`` into a local and never
+    uses it (:338-339), and this keeps that behaviour."""
+    if q == 1:
+        return feats
+    return umlh.align.remove_outliers(feats, q, exact=exact, max_threshold=max_threshold)
 
 
 # the callers' fixed arguments (vision_language/finetune.py:111-118, Gaussian_experiment/main.py:20-26)

@@ -20,7 +20,7 @@ PREC_IDS = {"fp32": 0, "bf16": 1}
 N_CORE_SCALARS = 8
 N_SCALARS = 12
 
-SOURCES = ["umlh_p2p.hip", "umlh_kernels_f32.hip", "umlh_kernels_bf16.hip", "umlh_kernels_micro.hip", "umlh_kernels_seq.hip", "umlh_kernels_enc.hip", "umlh_kernels_align.hip", "umlh_kernels_align_ext.hip", "umlh_kernels_probe.hip", "umlh_kernels_knn.hip", "umlh_kernels_spectral.hip", "umlh_kernels_capture.hip", "umlh_kernels_stepstats.hip", "umlh_kernels_rollout.hip", "umlh_kernels_classstats.hip", "umlh_kernels_evalreport.hip", "umlh_api.cpp", "umlh_encoder.cpp"]
+SOURCES = ["umlh_p2p.hip", "umlh_kernels_f32.hip", "umlh_kernels_bf16.hip", "umlh_kernels_micro.hip", "umlh_kernels_seq.hip", "umlh_kernels_enc.hip", "umlh_kernels_align.hip", "umlh_kernels_align_ext.hip", "umlh_kernels_probe.hip", "umlh_kernels_knn.hip", "umlh_kernels_spectral.hip", "umlh_kernels_capture.hip", "umlh_kernels_stepstats.hip", "umlh_kernels_rollout.hip", "umlh_kernels_classstats.hip", "umlh_kernels_evalreport.hip", "umlh_kernels_outlier.hip", "umlh_api.cpp", "umlh_encoder.cpp"]
 
 
 class UmlhError(RuntimeError):
@@ -214,6 +214,12 @@ def _prototypes() -> dict:
         "umlh_eval_topk_scratch_bytes": (u64, (i64, i64, i32, i32, i32)),
         "umlh_eval_topk": (rc, (vp, i64, i32, vp, i64, i32, i32, vp, vp, i32, i32, vp, vp, vp, u64, vp)),
         "umlh_eval_classwise": (rc, (vp, i64, i32, vp, i64, vp, vp, vp, vp, vp, vp)),
+        # outlier clamp and feature preparation: row quantile and global k-th of |x|, clamp (+ normalise), k-NN accuracy
+        "umlh_outlier_scratch_bytes": (u64, (i32, i64, i64)),
+        "umlh_row_abs_quantile": (rc, (vp, i64, i64, i64, f64, vp, vp, vp, vp, vp, vp, u64, vp)),
+        "umlh_abs_kth": (rc, (vp, i64, i64, i64, i64, vp, vp, u64, vp)),
+        "umlh_clamp_rows": (rc, (vp, i64, i64, i64, vp, i32, vp, i64, vp)),
+        "umlh_knn_accuracy": (rc, (vp, i64, i64, i64, vp, vp, u64, vp)),
     }
 
 

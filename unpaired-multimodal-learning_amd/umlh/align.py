@@ -11,6 +11,12 @@ with hsic_unbiased :230-249), ``rbf_cka`` (``cka(kernel_metric='rbf')``, biased 
 ``cycle_knn`` (:39-51), ``lcs_knn`` (:88-92) and ``edit_distance_knn`` (:164-176), and ``measure`` dispatches the reference's
 metric names and keyword arguments to all of them.  Not built: the ``distance_agnostic`` / biased CKNNA.
 
+The kernels of umlh_kernels_outlier.hip (C ABI: ``umlh_row_abs_quantile``, ``umlh_abs_kth``, ``umlh_clamp_rows``,
+``umlh_knn_accuracy``) are the module-level preprocessing of that file: ``remove_outliers`` (:327-341) with its
+two thresholds ``row_abs_quantile`` and ``abs_kth`` (a radix select, no sort), ``prepare_features`` (clamp and
+``F.normalize(dim=-1)`` in one launch) and ``knn_accuracy`` (``compute_knn_accuracy``, :258-269).  These take inputs of any
+``ndim >= 2``: the trailing dimensions are flattened from dim 1 as a view when the tensor is contiguous.
+
 ``svcca`` (:129-160) runs on the kernels of umlh_kernels_spectral.hip (C ABI: ``umlh_svcca``) in closed form: see its
 docstring and DESIGN section 13.  ``measure("svcca", ...)`` is not routed to it yet and still raises NotImplementedError.
 """
@@ -304,3 +310,154 @@ def measure(metric: str, feats_A: torch.Tensor, feats_B: torch.Tensor, **kwargs)
           "cka": _cka_any, "unbiased_cka": lambda a, b, **kw: _cka_any(a, b, **{**kw, "unbiased": True}),
           "cknna": _cknna_any, "svcca": _svcca}[metric]
     return float(fn(feats_A, feats_B, **kwargs).item())
+
+
+# ---- outlier clamp and feature preparation (umlh_kernels_outlier.hip) ----
+KIND_ROW_QUANTILE, KIND_ABS_KTH, KIND_KNN_ACCURACY = range(3)
+ROW_QUANTILE_WAVE_COLS = 1024      # UMLH_ROW_QUANTILE_WAVE_COLS: up to here a wave per row, four rows per workgroup
+ROW_QUANTILE_LDS_COLS = 15360      # UMLH_ROW_QUANTILE_LDS_COLS: up to here the row is read once and kept in LDS
+MAX_ELEMENTS = 1 << 40
+
+
+def _check_feats(feats, what: str) -> None:
+    if not isinstance(feats, torch.Tensor) or feats.ndim < 2:
+        raise ValueError(f"{what}: expected a tensor [N, ...] with ndim >= 2, got {getattr(feats, 'shape', type(feats))}")
+    if not feats.is_floating_point():
+        raise ValueError(f"{what}: expected a floating-point tensor, got {feats.dtype}")
+    if feats.numel() == 0:
+        raise ValueError(f"{what}: empty features {tuple(feats.shape)}")
+    if feats.numel() >= MAX_ELEMENTS or feats.numel() // feats.shape[0] >= 1 << 31:
+        raise ValueError(f"{what}: features {tuple(feats.shape)} outside the envelope (row width < 2^31, elements < 2^40)")
+
+
+def _check_q(q, what: str, upper_ok: bool) -> float:
+    q = float(q)
+    if not (0.0 <= q < 1.0 or (upper_ok and q == 1.0)):
+        raise ValueError(f"{what}: q={q} outside [0, 1{']' if upper_ok else ')'}")
+    return q
+
+
+def _rows(feats: torch.Tensor, what: str, dev: torch.device, width: int | None = None) -> torch.Tensor:
+    """``feats`` as an fp32 device matrix [N, prod(rest)] (or [numel / width, width]): a view where the layout allows."""
+    if feats.ndim == 2 and (width is None or width == feats.shape[1]):
+        return glue.features(feats, what, dev)
+    t = feats.detach().to(device=dev, dtype=torch.float32).contiguous()      # no copy when already fp32, on dev and contiguous
+    return t.view(t.shape[0], -1) if width is None else t.view(-1, width)
+
+
+def row_abs_quantile(feats: torch.Tensor, q: float, return_order_stats: bool = False):
+    """``(q_val, mean64, quant)``: per row of ``feats.abs().flatten(start_dim=1)`` the interpolated quantile ``quant`` fp32 [N]
+    (``torch.quantile(..., q, dim=1)``, interpolated in double from the two exact order statistics), its mean over rows in double
+    (0-d float64) and that mean rounded once (0-d fp32, the clamp bound of ``remove_outliers``); with ``return_order_stats`` also
+    ``lo_val, hi_val`` fp32 [N], the order statistics floor(q (d-1)) and the next.  0 <= q < 1."""
+    _check_feats(feats, "row_abs_quantile")
+    q = _check_q(q, "row_abs_quantile", False)
+    dev = _device()
+    x = _rows(feats, "row_abs_quantile", dev)
+    n, d = x.shape
+    lib = load_library()
+    scratch, nbytes = glue.scratch("umlh_outlier_scratch_bytes", dev, kind=KIND_ROW_QUANTILE, n=n, d=d)
+    quant = torch.empty(n, dtype=torch.float32, device=dev)
+    lo = torch.empty(n, dtype=torch.float32, device=dev) if return_order_stats else None
+    hi = torch.empty(n, dtype=torch.float32, device=dev) if return_order_stats else None
+    mean64 = torch.empty((), dtype=torch.float64, device=dev)
+    q_val = torch.empty((), dtype=torch.float32, device=dev)
+    check(lib.umlh_row_abs_quantile(x.data_ptr(), n, d, x.stride(0), q, glue.ptr(lo), glue.ptr(hi), quant.data_ptr(),
+                                    mean64.data_ptr(), q_val.data_ptr(), scratch.data_ptr(), nbytes, glue.stream(dev)),
+          "umlh_row_abs_quantile")
+    return (q_val, mean64, quant, lo, hi) if return_order_stats else (q_val, mean64, quant)
+
+
+def abs_kth(feats: torch.Tensor, k: int) -> torch.Tensor:
+    """``feats.view(-1).abs().sort().values[k]`` without the sort: a 0-d fp32 device tensor, bit-exact; NaNs order last."""
+    _check_feats(feats, "abs_kth")
+    k = int(k)
+    if not 0 <= k < feats.numel():
+        raise ValueError(f"abs_kth: k={k} outside 0..{feats.numel() - 1}")
+    dev = _device()
+    x = _rows(feats, "abs_kth", dev)
+    n, d = x.shape
+    lib = load_library()
+    scratch, nbytes = glue.scratch("umlh_outlier_scratch_bytes", dev, kind=KIND_ABS_KTH, n=n, d=d)
+    out = torch.empty((), dtype=torch.float32, device=dev)
+    check(lib.umlh_abs_kth(x.data_ptr(), n, d, x.stride(0), k, out.data_ptr(), scratch.data_ptr(), nbytes, glue.stream(dev)),
+          "umlh_abs_kth")
+    return out
+
+
+def _threshold(feats: torch.Tensor, q: float, exact: bool, what: str) -> torch.Tensor:
+    """The clamp bound of ``remove_outliers`` as a 0-d fp32 device tensor (metrics.py:331-336); argument errors before any GPU use."""
+    if exact:
+        k = int(q * feats.numel())
+        if not 0 <= k < feats.numel():
+            raise ValueError(f"{what}: exact index int(q * numel) = {k} outside 0..{feats.numel() - 1}")
+        return abs_kth(feats, k)
+    return row_abs_quantile(feats, q)[0]
+
+
+def _clamp(feats: torch.Tensor, q_val: torch.Tensor, normalize: bool, out, what: str) -> torch.Tensor:
+    dev = q_val.device
+    width = feats.shape[-1]
+    x = _rows(feats, what, dev, width)
+    n, d = x.shape
+    if out is None:
+        res = torch.empty(feats.shape, dtype=torch.float32, device=dev)
+    else:
+        if not isinstance(out, torch.Tensor) or out.shape != feats.shape or out.dtype != torch.float32 or out.device != dev:
+            raise ValueError(f"{what}: out must be an fp32 tensor of shape {tuple(feats.shape)} on {dev}")
+        if not (out.is_contiguous() or (out.ndim == 2 and out.stride(1) == 1 and out.stride(0) >= d)):
+            raise ValueError(f"{what}: out must be contiguous or a 2-D tensor with unit column stride")
+        res = out
+    o = res if res.ndim == 2 else res.view(-1, width)
+    if o.data_ptr() == x.data_ptr() and o.stride(0) != x.stride(0):
+        raise ValueError(f"{what}: out aliases the input with another row stride")
+    check(load_library().umlh_clamp_rows(x.data_ptr(), n, d, x.stride(0), q_val.data_ptr(), int(bool(normalize)), o.data_ptr(),
+                                         o.stride(0), glue.stream(dev)), "umlh_clamp_rows")
+    return res
+
+
+def remove_outliers(feats: torch.Tensor, q: float, exact: bool = False, max_threshold=None, out: torch.Tensor | None = None):
+    """``remove_outliers(feats, q, exact, max_threshold)`` (metrics.py:327-341): ``feats.clamp(-q_val, q_val)`` with ``q_val`` the
+    mean over rows of the q-quantile of |feats| (``exact``: the element ``int(q * numel)`` of all sorted |feats|); an fp32 device
+    tensor of ``feats``' shape, nothing is read back.  ``q == 1`` returns ``feats`` itself.  ``max_threshold`` is accepted and has
+    no effect, as in the reference, which computes ``max(max_threshold, q_val)`` into a local it never uses (:338-339).  ``out``:
+    where to write (``out=feats`` for fp32 device features clamps in place)."""
+    _check_feats(feats, "remove_outliers")
+    q = _check_q(q, "remove_outliers", True)
+    if q == 1.0:
+        return feats
+    return _clamp(feats, _threshold(feats, q, bool(exact), "remove_outliers"), False, out, "remove_outliers")
+
+
+def prepare_features(feats: torch.Tensor, q: float = 0.95, exact: bool = False, normalize: bool = True) -> torch.Tensor:
+    """``F.normalize(remove_outliers(feats, q, exact), dim=-1)`` (what the reference's ``__main__`` and its callers do before
+    measuring) with the clamp and the normalisation in one launch after the selection; ``normalize=False``: the clamp alone.
+    ``q == 1`` keeps every value (an infinite bound).  An fp32 device tensor of ``feats``' shape."""
+    _check_feats(feats, "prepare_features")
+    q = _check_q(q, "prepare_features", True)
+    if q == 1.0:
+        q_val = torch.full((), math.inf, dtype=torch.float32, device=_device())
+    else:
+        q_val = _threshold(feats, q, bool(exact), "prepare_features")
+    return _clamp(feats, q_val, bool(normalize), None, "prepare_features")
+
+
+def knn_accuracy(knn_lists: torch.Tensor, whole_table: bool = False) -> torch.Tensor:
+    """The share of rows i of an integer tensor [N, k] or [N, k, k] that contain the value i (``compute_knn_accuracy`` of
+    metrics.py:258-269 on the [N, k, k] its caller passes); a 0-d float64 device tensor (integer hit count / N).
+    ``whole_table``: the share of the indices 0 .. N-1 found anywhere in the tensor instead, which is what the reference's
+    expression evaluates to for a 2-D list (its ``arange(n).view(-1, 1, 1)`` broadcasts [N, k] to [N, N, k])."""
+    if not isinstance(knn_lists, torch.Tensor) or knn_lists.ndim < 2 or knn_lists.is_floating_point() or knn_lists.dtype == torch.bool:
+        raise ValueError(f"knn_accuracy: expected an integer tensor [N, k] or [N, k, k], got {getattr(knn_lists, 'shape', type(knn_lists))} "
+                         f"{getattr(knn_lists, 'dtype', '')}")
+    if knn_lists.numel() == 0:
+        raise ValueError(f"knn_accuracy: empty list {tuple(knn_lists.shape)}")
+    dev = _device()
+    k = knn_lists.to(device=dev, dtype=torch.int32).contiguous()
+    n = k.shape[0]
+    m, ld = (k.numel(), 0) if whole_table else (k.numel() // n, k.numel() // n)
+    lib = load_library()
+    scratch, nbytes = glue.scratch("umlh_outlier_scratch_bytes", dev, kind=KIND_KNN_ACCURACY, n=n, d=m)
+    out = torch.empty((), dtype=torch.float64, device=dev)
+    check(lib.umlh_knn_accuracy(k.data_ptr(), n, m, ld, out.data_ptr(), scratch.data_ptr(), nbytes, glue.stream(dev)), "umlh_knn_accuracy")
+    return out
