@@ -149,7 +149,7 @@ def emulate(form, Am, Bm):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------- #
-# dispatch (csrc/umlh_api.cpp: umlh_gemm_f32; csrc/umlh_kernels_f32.hip: dw_f32_applies, umlh_f32_launch_gemm)
+# dispatch (csrc/umlh_ops.cpp: umlh_gemm_f32; csrc/umlh_kernels_f32.hip: dw_f32_applies, umlh_f32_launch_gemm)
 # ---------------------------------------------------------------------------------------------------------------------------- #
 def _cdiv(a, b):
     return -(-a // b)

@@ -11,7 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
-#include "umlh.h"
+#include "umlh_host.h"
 #include "umlh_launch.h"
 
 namespace {
@@ -76,7 +76,6 @@ bool dims_ok(const umlh_enc_layer_t* c, Dims& d) {
     return true;
 }
 
-#define RC(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
 #define HC(expr) do { if ((expr) != 0) return UMLH_E_HIP; } while (0)
 
 Epilogue epi_none() { Epilogue e; memset(&e, 0, sizeof(e)); return e; }
