@@ -299,6 +299,37 @@ def test_layernorm_forward_backward(lib, with_r):
     assert not bad, "\n".join(bad)
 
 
+@pytest.mark.parametrize("with_r", [False, True])
+def test_layernorm_forward_signed_zeros(lib, with_r):
+    """s = x + r keeps IEEE signed zeros: -0 + -0 is -0, every other pairing of zeros is +0, and without r it is x + (+0), so a
+    -0 of x comes out as +0.  (A sum that starts from +0, as the slab form's does, would lose the first.)  5 rows: a second block
+    of 4; 65 columns: lane 0 takes a second column."""
+    M, N = 5, 65
+    rng = np.random.default_rng(565)
+    x, r = rng.standard_normal((M, N)).astype(F32), rng.standard_normal((M, N)).astype(F32)
+    gamma, beta = rng.standard_normal(N).astype(F32), rng.standard_normal(N).astype(F32)
+    nz, pz = F32(-0.0), F32(0.0)
+    planted = {(0, 0): (nz, nz), (0, 1): (nz, pz), (1, 63): (pz, nz), (1, 64): (pz, pz), (4, 64): (nz, nz), (4, 0): (pz, nz),
+               (2, 5): (nz, None), (3, 7): (None, nz), (4, 33): (nz, pz)}       # (x, r) at (m, n); None: the random value stays
+    for (m, n), (vx, vr) in planted.items():
+        if vx is not None:
+            x[m, n] = vx
+        if vr is not None:
+            r[m, n] = vr
+    ref = (x + r) if with_r else (x + F32(0))
+    assert ref.dtype == F32
+    for (m, n), (vx, vr) in planted.items():                                    # numpy's own bits for the planted pairs
+        if vx is not None and (vr is not None or not with_r):
+            both_neg = with_r and np.signbit(vx) and np.signbit(vr)
+            assert ref[m, n] == 0 and bool(np.signbit(ref[m, n])) == bool(both_neg), (m, n)
+    s, y, mean, rstd = sentinel(M * N, N), sentinel(M * N, N), sentinel(M), sentinel(M)
+    _ok(lib, lib.umlh_add_layernorm_forward(vp(dev(x)), vp(dev(r)) if with_r else None, vp(dev(gamma)), vp(dev(beta)), M, N,
+                                            C.c_float(R.EPS), vp(s), vp(y), vp(mean), vp(rstd), None), "add_layernorm_forward")
+    got = written(s, M * N, "s")
+    assert np.array_equal(got.view(np.uint32), ref.ravel().view(np.uint32)), "s differs from numpy's fp32 sum in some bit"
+    written(y, M * N, "y"), written(mean, M, "mean"), written(rstd, M, "rstd")
+
+
 # ---------------------------------------------------------------------------------------------------------------------------- #
 # attention
 # ---------------------------------------------------------------------------------------------------------------------------- #

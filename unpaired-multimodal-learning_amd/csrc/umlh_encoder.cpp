@@ -18,19 +18,6 @@ namespace {
 
 inline long long ru64(long long x) { return (x + 63) / 64 * 64; }
 
-// Split-K factor: these GEMMs have few 64x64 output tiles and are bound by the latency of the K walk (one staged chunk per
-// iteration), so K is cut until ~768 workgroups (3 per CU, co-resident) with at least 64 reduction rows each.
-int splits_for(int m, int n, int k) {
-    static const int target = env_int("UMLH_ENC_SPLIT_WGS", 768);
-    const long long tiles = (long long)((m + 63) / 64) * ((n + 63) / 64);
-    if (k < 128 || tiles >= target) return 1;
-    long long s = (target + tiles - 1) / tiles;
-    if (s > k / 64) s = k / 64;
-    if (s > 32) s = 32;
-    return (int)(s < 1 ? 1 : s);
-}
-inline int row_chunk(long long M) { long long c = (M + 63) / 64; return (int)(c < 64 ? 64 : c); }   // <= 64 row chunks of >= 64 rows
-
 struct Dims { int T, B, Z, H, F, R, chunk; long long M; };
 
 struct Saved {           // per-layer activations kept for the backward (offsets in floats inside `saved`)

@@ -11,7 +11,6 @@
 #include "umlh_common.h"
 #include "umlh_launch.h"
 #include <type_traits>
-#include <atomic>
 #include <cstring>
 
 // Timing-only ablations (skip the main loop / the epilogue / an operand's traffic) exist for kernel analysis and are
@@ -1389,15 +1388,7 @@ static size_t fwd_smem_bytes_b(int ctw, int wc, int stw) {
 #define FWDB_CASE(CT, W, S)                                                                          \
     if (ctw == CT && wc == W && stw == S) {                                                          \
         size_t sm = fwd_smem_bytes_b(CT, W, S);                                                      \
-        static std::atomic<unsigned long long> attr_done{0};  /* bit d: done on device d (the attribute is per device) */ \
-        int dev_ = 0;                                                                                \
-        (void)hipGetDevice(&dev_);                                                                   \
-        if (!((attr_done.load(std::memory_order_acquire) >> (dev_ & 63)) & 1ULL)) {                  \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fwd_ce_bf16<CT, W, S>),\
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm); \
-            if (e != hipSuccess) return (int)e;                                                      \
-            attr_done.fetch_or(1ULL << (dev_ & 63), std::memory_order_release);                      \
-        }                                                                                            \
+        if (int e = raise_lds_limit<&fwd_ce_bf16<CT, W, S>>((int)sm)) return e;                      \
         FwdArgsB c_ = *a; c_.plain = umlh_plain_stores();                                            \
         hipLaunchKernelGGL((fwd_ce_bf16<CT, W, S>), dim3(grid), dim3(512), sm, stream, c_);          \
         return (int)hipGetLastError();                                                               \
@@ -1406,13 +1397,7 @@ static size_t fwd_smem_bytes_b(int ctw, int wc, int stw) {
 // 2-D forward: grid = row tiles (128 rows; seg[].blk0 in tile units) x nq class groups of 256
 #define FWDQ_CASE(NQ_, NKS_)                                                                                       \
     if (nq == NQ_ && a->K == 16 * NKS_) {                                                                          \
-        static std::atomic<unsigned long long> attr_done{0};                                                       \
-        if (!((attr_done.load(std::memory_order_acquire) >> (dev_ & 63)) & 1ULL)) {                                \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fwd_ce_bf16_q<NQ_, NKS_>),           \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, FQ_SMEM);               \
-            if (e != hipSuccess) return (int)e;                                                                    \
-            attr_done.fetch_or(1ULL << (dev_ & 63), std::memory_order_release);                                    \
-        }                                                                                                          \
+        if (int e = raise_lds_limit<&fwd_ce_bf16_q<NQ_, NKS_>>(FQ_SMEM)) return e;                                 \
         FwdArgsB c_ = *a; c_.plain = umlh_plain_stores();                                                          \
         hipLaunchKernelGGL((fwd_ce_bf16_q<NQ_, NKS_>), dim3((tiles + 7) / 8 * 8 * NQ_), dim3(512), FQ_SMEM, stream, c_);        \
         return (int)hipGetLastError();                                                                             \
@@ -1421,8 +1406,6 @@ static size_t fwd_smem_bytes_b(int ctw, int wc, int stw) {
 int umlh_bf16_launch_fwd_q(const FwdArgsB* a, int nq, int tiles, hipStream_t stream) {
     if (tiles <= 0) return 0;
     if (!a->xch || a->epoch == 0 || a->C > 256 * nq || a->wtiles < 8 * nq || a->ntiles != tiles) return (int)hipErrorInvalidValue;
-    int dev_ = 0;
-    (void)hipGetDevice(&dev_);
     FWDQ_CASE(2, 32) FWDQ_CASE(3, 32) FWDQ_CASE(4, 32) FWDQ_CASE(2, 16) FWDQ_CASE(3, 16) FWDQ_CASE(4, 16)
     return (int)hipErrorInvalidValue;
 }
@@ -1448,13 +1431,7 @@ int umlh_bf16_launch_transpose_shadow(const float* src, int R, int Cc, int ldd, 
     if (ctw == CT && wc == W) {                                                                                    \
         size_t sm = fwd_smem_bytes_b(CT, W, 1);                                                                    \
         if (sm < (size_t)DW_DMA_LDS_BYTES) sm = DW_DMA_LDS_BYTES;                                                  \
-        static std::atomic<unsigned long long> attr_done{0};  /* bit d: done on device d (the attribute is per device) */ \
-        if (!((attr_done.load(std::memory_order_acquire) >> (dev_ & 63)) & 1ULL)) {                                \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&step_bf16<CT, W>),                   \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);               \
-            if (e != hipSuccess) return (int)e;                                                                    \
-            attr_done.fetch_or(1ULL << (dev_ & 63), std::memory_order_release);                                    \
-        }                                                                                                          \
+        if (int e = raise_lds_limit<&step_bf16<CT, W>>((int)sm)) return e;                                         \
         hipLaunchKernelGGL((step_bf16<CT, W>), dim3(grid), dim3(512), sm, stream, sa);           \
         return (int)hipGetLastError();                                                                             \
     }
@@ -1501,21 +1478,13 @@ int umlh_bf16_launch_step(const FwdArgsB* a, int ctw, int wc, int nfwd, const Dw
     if (cus > 0 && grid > cus) grid = cus;
     StepArgs sa;
     sa.a = fa; sa.g = ga; sa.gate = gate; sa.sh = shp; sa.hf = h;
-    int dev_ = 0;
-    (void)hipGetDevice(&dev_);
     STEP_CASE(1, 1) STEP_CASE(1, 2) STEP_CASE(1, 4) STEP_CASE(1, 8) STEP_CASE(2, 8) STEP_CASE(4, 8)
     return (int)hipErrorInvalidValue;
 }
 
 #define DW_DMA_CASE(A_, O_)                                                                                        \
     if (am == A_ && om == O_) {                                                                                    \
-        static std::atomic<unsigned long long> attr_done{0};                                                       \
-        if (!((attr_done.load(std::memory_order_acquire) >> (dev_ & 63)) & 1ULL)) {                                \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dw_bf16_dma<A_, O_>),                \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, DW_DMA_LDS_BYTES);      \
-            if (e != hipSuccess) return (int)e;                                                                    \
-            attr_done.fetch_or(1ULL << (dev_ & 63), std::memory_order_release);                                    \
-        }                                                                                                          \
+        if (int e = raise_lds_limit<&dw_bf16_dma<A_, O_>>(DW_DMA_LDS_BYTES)) return e;                             \
         hipLaunchKernelGGL((dw_bf16_dma<A_, O_>), grid, dim3(512), DW_DMA_LDS_BYTES, stream, c);                   \
         return (int)hipGetLastError();                                                                             \
     }
@@ -1528,8 +1497,6 @@ int umlh_bf16_launch_dw(const DwArgsB* g, int splits, int am, int om, hipStream_
     dim3 grid(((g->N + DBN - 1) / DBN) * ((g->M + DBM - 1) / DBM) * splits);
     DwArgsB c = *g;
     c.plain = umlh_plain_stores();
-    int dev_ = 0;
-    (void)hipGetDevice(&dev_);
     DW_DMA_CASE(0, 0) DW_DMA_CASE(1, 1) DW_DMA_CASE(0, 2)
     return (int)hipErrorInvalidValue;
 }

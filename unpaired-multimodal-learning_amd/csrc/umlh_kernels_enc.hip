@@ -8,7 +8,6 @@
 // nothing here is reshaped to reach MFMA.
 #include "umlh_common.h"
 #include "umlh_launch.h"
-#include <atomic>
 
 namespace {
 
@@ -60,7 +59,9 @@ __global__ __launch_bounds__(256) void add_inplace_kernel(float* __restrict__ y,
     if (i < total) y[i] += x[i];
 }
 
-// out[n] = sum_m x[m][n]      one block per 64 columns, 4 row groups, fixed summation order
+// The four column kernels (colsum, layernorm_bwd_cols: 16 row groups folded in sequence; colsum_partial, ln_cols_partial: 4 groups
+// folded pairwise) stay separate: public results depend on each fold order, and one template with two fold policies is more than two short kernels.
+// out[n] = sum_m x[m][n]      one block per 64 columns, 16 row groups, fixed summation order
 constexpr int CG = 16;     // row groups of the column reductions (1024 threads: these are latency-bound row walks)
 __global__ __launch_bounds__(1024) void colsum_kernel(const float* __restrict__ x, int M, int N, float* __restrict__ out) {
     __shared__ float sh[CG][64];
@@ -77,18 +78,26 @@ __global__ __launch_bounds__(1024) void colsum_kernel(const float* __restrict__ 
     }
 }
 
-// s = x + r (r may be NULL); y = LayerNorm(s) * gamma + beta; one wave per row
-__global__ __launch_bounds__(256) void add_layernorm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ r,
-                                                                const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                                int M, int N, float eps, float* __restrict__ s_out,
-                                                                float* __restrict__ y, float* __restrict__ mean_out,
-                                                                float* __restrict__ rstd_out) {
+// y = LayerNorm(s) * gamma + beta, one wave per row; s[m][n] is formed from x in one of two ways:
+//   SLABS = false   x + r (r may be NULL; ns, stride and e unused).  Not the slab form with ns = 1: slab_sum starts from +0, which
+//                   would turn -0 + -0 into +0
+//   SLABS = true    epilogue(sum of ns slabs of x): bias, dropout, + residual through e.add (r unused)
+template <bool SLABS>
+__global__ __launch_bounds__(256) void add_layernorm_kernel(const float* __restrict__ x, const float* __restrict__ r, int ns,
+                                                            long long stride, Epilogue e, const float* __restrict__ gamma,
+                                                            const float* __restrict__ beta, int M, int N, float eps,
+                                                            float* __restrict__ s_out, float* __restrict__ y,
+                                                            float* __restrict__ mean_out, float* __restrict__ rstd_out) {
     const int m = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (m >= M) return;
     const size_t o = (size_t)m * N;
     float sum = 0.f;
     for (int n = lane; n < N; n += 64) {
-        float v = x[o + n] + (r ? r[o + n] : 0.f);
+        float v;
+        if constexpr (SLABS) {
+            v = slab_sum(x + o + n, stride, ns);
+            v = epilogue_apply(e, v, (long long)(o + n), n);
+        } else v = x[o + n] + (r ? r[o + n] : 0.f);
         s_out[o + n] = v;
         sum += v;
     }
@@ -101,29 +110,6 @@ __global__ __launch_bounds__(256) void add_layernorm_fwd_kernel(const float* __r
     const float rstd = rsqrtf(wave_sum(var) / (float)N + eps);
     for (int n = lane; n < N; n += 64) y[o + n] = (s_out[o + n] - mean) * rstd * gamma[n] + beta[n];
     if (lane == 0) { mean_out[m] = mean; rstd_out[m] = rstd; }
-}
-
-// ds = rstd * (g*dy - mean_n(g*dy) - xhat * mean_n(g*dy*xhat)),  xhat = (s - mean) * rstd; one wave per row
-__global__ __launch_bounds__(256) void layernorm_bwd_rows_kernel(const float* __restrict__ dy, const float* __restrict__ s,
-                                                                 const float* __restrict__ gamma, const float* __restrict__ mean,
-                                                                 const float* __restrict__ rstd, int M, int N,
-                                                                 float* __restrict__ ds) {
-    const int m = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (m >= M) return;
-    const size_t o = (size_t)m * N;
-    const float mu = mean[m], rs = rstd[m];
-    float a = 0.f, b = 0.f;
-    for (int n = lane; n < N; n += 64) {
-        float g = gamma[n] * dy[o + n], xh = (s[o + n] - mu) * rs;
-        a += g;
-        b += g * xh;
-    }
-    a = wave_sum(a) / (float)N;
-    b = wave_sum(b) / (float)N;
-    for (int n = lane; n < N; n += 64) {
-        float g = gamma[n] * dy[o + n], xh = (s[o + n] - mu) * rs;
-        ds[o + n] = rs * (g - a - xh * b);
-    }
 }
 
 // dgamma[n] = sum_m dy*xhat, dbeta[n] = sum_m dy    (column kernel, fixed order)
@@ -386,55 +372,26 @@ __global__ __launch_bounds__(64 * AW) void attention_bwd_kernel(const float* __r
 // GEMM epilogue or in the row kernel that consumes the GEMM's split-K slabs; column reductions (bias / LayerNorm weight
 // gradients) are row-chunk partials that ONE multi_reduce launch per layer sums in a fixed order.
 // --------------------------------------------------------------------------- //
-// out[i] = epilogue(sum_s slabs[s*stride + i])
-__global__ __launch_bounds__(256) void reduce_epilogue_kernel(const float* __restrict__ slabs, int ns, long long stride, long long total,
-                                                              int N, Epilogue e, float* __restrict__ out) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
-    const float v = slab_sum(slabs + i, stride, ns);
-    out[i] = e.on ? epilogue_apply(e, v, i, (int)(i % N)) : v;
-}
-
-// out[m*ldo + n] = sum_s slabs[s*stride + m*ldo + n] over the [M, N] window only: the split-K reduce of umlh_gemm_f32, whose
-// output (and slabs) may be a window of wider rows -- columns [N, ldo) belong to the caller
-__global__ __launch_bounds__(256) void reduce_window_kernel(const float* __restrict__ slabs, int ns, long long stride, int M, int N,
-                                                            int ldo, float* __restrict__ out) {
+// out[m*ldo + n] = epilogue(sum_s slabs[s*stride + m*ldo + n]) over the [M, N] window only: output and slabs may be windows of wider
+// rows (umlh_gemm_f32; columns [N, ldo) belong to the caller).  The epilogue indexes dense [M, N] buffers with i = m*N + n, so the
+// launcher takes one only at ldo == N
+__global__ __launch_bounds__(256) void reduce_slabs_kernel(const float* __restrict__ slabs, int ns, long long stride, int M, int N,
+                                                           int ldo, Epilogue e, float* __restrict__ out) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= (long long)M * N) return;
-    const long long o = (i / N) * ldo + i % N;
-    out[o] = slab_sum(slabs + o, stride, ns);
+    const int n = (int)(i % N);
+    const long long o = (i / N) * ldo + n;
+    const float v = slab_sum(slabs + o, stride, ns);
+    out[o] = e.on ? epilogue_apply(e, v, i, n) : v;
 }
 
-// s = epilogue(sum of ns slabs of x) (bias, dropout, + residual through e.add); y = LayerNorm(s) * gamma + beta; a wave per row
-__global__ __launch_bounds__(256) void add_layernorm_fused_kernel(const float* __restrict__ x, int ns, long long stride, Epilogue e,
-                                                                  const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                                  int M, int N, float eps, float* __restrict__ s_out,
-                                                                  float* __restrict__ y, float* __restrict__ mean_out,
-                                                                  float* __restrict__ rstd_out) {
-    const int m = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (m >= M) return;
-    const size_t o = (size_t)m * N;
-    float sum = 0.f;
-    for (int n = lane; n < N; n += 64) {
-        float v = slab_sum(x + o + n, stride, ns);
-        v = epilogue_apply(e, v, (long long)(o + n), n);
-        s_out[o + n] = v;
-        sum += v;
-    }
-    const float mean = wave_sum(sum) / (float)N;
-    float var = 0.f;
-    for (int n = lane; n < N; n += 64) {
-        float d = s_out[o + n] - mean;          // written by this lane above
-        var += d * d;
-    }
-    const float rstd = rsqrtf(wave_sum(var) / (float)N + eps);
-    for (int n = lane; n < N; n += 64) y[o + n] = (s_out[o + n] - mean) * rstd * gamma[n] + beta[n];
-    if (lane == 0) { mean_out[m] = mean; rstd_out[m] = rstd; }
-}
-
-// dy = sum of ns slabs (+ add: the gradient arriving over the residual path), kept in dy_out when it had to be formed here;
-// ds = LayerNorm backward of the row; dsd = dropout(ds) on stream `seed` (the branch gradient), NULL = not wanted
-__global__ __launch_bounds__(256) void layernorm_bwd_rows_fused_kernel(const float* __restrict__ dy, int ns, long long stride,
+// dy = sum of ns slabs (+ add: the gradient arriving over the residual path), kept in dy_out when it had to be formed here (dy_out
+// NULL: dy is the gradient itself);  ds = rstd * (g*dy - mean_n(g*dy) - xhat * mean_n(g*dy*xhat)), xhat = (s - mean) * rstd, one wave
+// per row;  dsd = dropout(ds) on stream `seed` (the branch gradient), NULL = not wanted.
+// FUSED = false is the dy_out == NULL && dsd == NULL path decided at compile time (umlh_layernorm_backward): with the branches
+// left to run time the compiler contracts g - a - xh * b differently, and that entry point's bits would move
+template <bool FUSED>
+__global__ __launch_bounds__(256) void layernorm_bwd_rows_kernel(const float* __restrict__ dy, int ns, long long stride,
                                                                        const float* __restrict__ add, float* __restrict__ dy_out,
                                                                        const float* __restrict__ s, const float* __restrict__ gamma,
                                                                        const float* __restrict__ mean, const float* __restrict__ rstd,
@@ -446,11 +403,11 @@ __global__ __launch_bounds__(256) void layernorm_bwd_rows_fused_kernel(const flo
     const unsigned long long seed = seed0 + (seed_ptr ? *seed_ptr : 0ull);
     const size_t o = (size_t)m * N;
     const float mu = mean[m], rs = rstd[m];
-    const float* dyr = dy_out ? dy_out : dy;
+    const float* dyr = FUSED && dy_out ? dy_out : dy;
     float a = 0.f, b = 0.f;
     for (int n = lane; n < N; n += 64) {
         float d;
-        if (dy_out) {
+        if (FUSED && dy_out) {
             d = slab_sum(dy + o + n, stride, ns);
             if (add) d += add[o + n];
             dy_out[o + n] = d;
@@ -465,7 +422,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_rows_fused_kernel(const flo
         const float g = gamma[n] * dyr[o + n], xh = (s[o + n] - mu) * rs;
         const float v = rs * (g - a - xh * b);
         ds[o + n] = v;
-        if (dsd) dsd[o + n] = (thresh == 0 || keep_elem(seed, (unsigned long long)(o + n), thresh)) ? v * inv_keep : 0.f;
+        if (FUSED && dsd) dsd[o + n] = (thresh == 0 || keep_elem(seed, (unsigned long long)(o + n), thresh)) ? v * inv_keep : 0.f;
     }
 }
 
@@ -534,9 +491,18 @@ __global__ void set_u64_kernel(unsigned long long* dst, unsigned long long v) { 
 inline unsigned drop_thresh(float p) { return p <= 0.f ? 0u : (unsigned)((double)p * 4294967296.0); }
 inline unsigned blocks_for(long long n) { return (unsigned)((n + 255) / 256); }
 
+// the attention kernels' envelope, and the LDS floats of one workgroup per direction (rs: the odd row stride of a head in LDS)
+inline bool attention_shape_ok(int T, int Z, int H) { return T >= 1 && T <= ATM && H >= 1 && Z % H == 0 && Z / H <= ADH; }
+inline size_t attention_fwd_lds(int T, int Z, int H) { const size_t rs = (Z / H) | 1; return sizeof(float) * (3 * T * rs + AW * T); }
+inline size_t attention_bwd_lds(int T, int Z, int H) { const size_t rs = (Z / H) | 1; return sizeof(float) * (4 * T * rs + 2 * T + AW * 2 * T); }
+constexpr int ATT_MAX_LDS = 150 * 1024;   // the dynamic-LDS limit both kernels are raised to
+
 }  // namespace
 
 extern "C" {
+
+float umlh_enc_drop_inv_keep(float p) { return p > 0.f ? 1.f / (1.f - p) : 1.f; }
+unsigned umlh_enc_drop_thresh(float p) { return drop_thresh(p); }
 
 int umlh_enc_launch_bias_act(float* y, const float* b, long long M, int N, int relu, hipStream_t st) {
     if (M * N <= 0) return 0;
@@ -571,29 +537,8 @@ int umlh_enc_launch_colsum(const float* x, int M, int N, float* out, hipStream_t
 int umlh_enc_launch_add_layernorm(const float* x, const float* r, const float* gamma, const float* beta, int M, int N, float eps,
                                   float* s_out, float* y, float* mean, float* rstd, hipStream_t st) {
     if (M <= 0) return 0;
-    hipLaunchKernelGGL(add_layernorm_fwd_kernel, dim3((M + 3) / 4), dim3(256), 0, st, x, r, gamma, beta, M, N, eps, s_out, y, mean, rstd);
-    return (int)hipGetLastError();
-}
-
-int umlh_enc_launch_layernorm_bwd(const float* dy, const float* s, const float* gamma, const float* mean, const float* rstd,
-                                  int M, int N, float* ds, float* dgamma, float* dbeta, hipStream_t st) {
-    if (M <= 0) return 0;
-    hipLaunchKernelGGL(layernorm_bwd_rows_kernel, dim3((M + 3) / 4), dim3(256), 0, st, dy, s, gamma, mean, rstd, M, N, ds);
-    hipLaunchKernelGGL(layernorm_bwd_cols_kernel, dim3((N + 63) / 64), dim3(64 * CG), 0, st, dy, s, mean, rstd, M, N, dgamma, dbeta);
-    return (int)hipGetLastError();
-}
-
-
-int umlh_enc_launch_reduce_epilogue(const float* slabs, int ns, long long stride, long long total, int N, const Epilogue* e, float* out,
-                                    hipStream_t st) {
-    if (total <= 0) return 0;
-    hipLaunchKernelGGL(reduce_epilogue_kernel, dim3(blocks_for(total)), dim3(256), 0, st, slabs, ns, stride, total, N, *e, out);
-    return (int)hipGetLastError();
-}
-
-int umlh_enc_launch_reduce_window(const float* slabs, int ns, long long stride, int M, int N, int ldo, float* out, hipStream_t st) {
-    if (M <= 0 || N <= 0) return 0;
-    hipLaunchKernelGGL(reduce_window_kernel, dim3(blocks_for((long long)M * N)), dim3(256), 0, st, slabs, ns, stride, M, N, ldo, out);
+    hipLaunchKernelGGL(add_layernorm_kernel<false>, dim3((M + 3) / 4), dim3(256), 0, st, x, r, 1, 0, Epilogue{}, gamma, beta, M, N, eps,
+                       s_out, y, mean, rstd);
     return (int)hipGetLastError();
 }
 
@@ -601,8 +546,8 @@ int umlh_enc_launch_add_layernorm_fused(const float* x, int ns, long long stride
                                         const float* beta, int M, int N, float eps, float* s_out, float* y, float* mean, float* rstd,
                                         hipStream_t st) {
     if (M <= 0) return 0;
-    hipLaunchKernelGGL(add_layernorm_fused_kernel, dim3((M + 3) / 4), dim3(256), 0, st, x, ns, stride, *e, gamma, beta, M, N, eps,
-                       s_out, y, mean, rstd);
+    hipLaunchKernelGGL(add_layernorm_kernel<true>, dim3((M + 3) / 4), dim3(256), 0, st, x, nullptr, ns, stride, *e, gamma, beta, M, N,
+                       eps, s_out, y, mean, rstd);
     return (int)hipGetLastError();
 }
 
@@ -611,8 +556,26 @@ int umlh_enc_launch_layernorm_bwd_rows_fused(const float* dy, int ns, long long 
                                              float* dsd, float p, unsigned long long seed, const unsigned long long* seed_ptr,
                                              hipStream_t st) {
     if (M <= 0) return 0;
-    hipLaunchKernelGGL(layernorm_bwd_rows_fused_kernel, dim3((M + 3) / 4), dim3(256), 0, st, dy, ns, stride, add, dy_out, s, gamma, mean,
-                       rstd, M, N, ds, dsd, drop_thresh(p), p > 0.f ? 1.f / (1.f - p) : 1.f, seed, seed_ptr);
+    hipLaunchKernelGGL(layernorm_bwd_rows_kernel<true>, dim3((M + 3) / 4), dim3(256), 0, st, dy, ns, stride, add, dy_out, s, gamma, mean,
+                       rstd, M, N, ds, dsd, drop_thresh(p), umlh_enc_drop_inv_keep(p), seed, seed_ptr);
+    return (int)hipGetLastError();
+}
+
+int umlh_enc_launch_layernorm_bwd(const float* dy, const float* s, const float* gamma, const float* mean, const float* rstd,
+                                  int M, int N, float* ds, float* dgamma, float* dbeta, hipStream_t st) {
+    if (M <= 0) return 0;
+    hipLaunchKernelGGL(layernorm_bwd_rows_kernel<false>, dim3((M + 3) / 4), dim3(256), 0, st, dy, 1, 0, nullptr, nullptr, s, gamma, mean,
+                       rstd, M, N, ds, nullptr, 0u, 1.f, 0ull, nullptr);
+    hipLaunchKernelGGL(layernorm_bwd_cols_kernel, dim3((N + 63) / 64), dim3(64 * CG), 0, st, dy, s, mean, rstd, M, N, dgamma, dbeta);
+    return (int)hipGetLastError();
+}
+
+int umlh_enc_launch_reduce_slabs(const float* slabs, int ns, long long stride, int M, int N, int ldo, const Epilogue* e, float* out,
+                                 hipStream_t st) {
+    if (M <= 0 || N <= 0) return 0;
+    if (e && e->on && ldo != N) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(reduce_slabs_kernel, dim3(blocks_for((long long)M * N)), dim3(256), 0, st, slabs, ns, stride, M, N, ldo,
+                       e ? *e : Epilogue{}, out);
     return (int)hipGetLastError();
 }
 
@@ -645,9 +608,6 @@ int umlh_enc_launch_set_u64(unsigned long long* dst, unsigned long long v, hipSt
     return (int)hipGetLastError();
 }
 
-float umlh_enc_drop_inv_keep(float p) { return p > 0.f ? 1.f / (1.f - p) : 1.f; }
-unsigned umlh_enc_drop_thresh(float p) { return drop_thresh(p); }
-
 int umlh_enc_launch_add_pos(float* x, const float* pos, int T, int B, int Z, hipStream_t st) {
     hipLaunchKernelGGL(add_pos_kernel, dim3(blocks_for((long long)T * B * Z)), dim3(256), 0, st, x, pos, T, B, Z);
     return (int)hipGetLastError();
@@ -664,43 +624,23 @@ int umlh_enc_launch_gather_rows(const float* x, const int64_t* idx, int n, int Z
     return (int)hipGetLastError();
 }
 
-// returns hipErrorInvalidValue for shapes outside the kernel's envelope (T <= 128, head dim <= 64)
+// both return hipErrorInvalidValue for shapes outside the kernels' envelope (T <= 128, head dim <= 64)
 int umlh_enc_launch_attention_fwd(const float* qkv, const int64_t* lengths, int T, int B, int Z, int H, float p,
                                   unsigned long long seed, const unsigned long long* seed_ptr, float* ctx, float* lse, hipStream_t st) {
-    if (T < 1 || T > ATM || H < 1 || Z % H != 0 || Z / H > ADH) return (int)hipErrorInvalidValue;
-    const int rs = (Z / H) | 1;
-    const size_t smem = sizeof(float) * (3 * (size_t)T * rs + AW * T);
-    static std::atomic<unsigned long long> attr_done{0};      // bit d: done on device d (the attribute is per device)
-    int dev_ = 0;
-    (void)hipGetDevice(&dev_);
-    if (!((attr_done.load(std::memory_order_acquire) >> (dev_ & 63)) & 1ULL)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_fwd_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_done.fetch_or(1ULL << (dev_ & 63), std::memory_order_release);
-    }
-    hipLaunchKernelGGL(attention_fwd_kernel, dim3(B * H), dim3(64 * AW), smem, st, qkv, lengths, T, B, Z, H, drop_thresh(p),
-                       p > 0.f ? 1.f / (1.f - p) : 1.f, seed, seed_ptr, ctx, lse);
+    if (!attention_shape_ok(T, Z, H)) return (int)hipErrorInvalidValue;
+    if (int e = raise_lds_limit<&attention_fwd_kernel>(ATT_MAX_LDS)) return e;
+    hipLaunchKernelGGL(attention_fwd_kernel, dim3(B * H), dim3(64 * AW), attention_fwd_lds(T, Z, H), st, qkv, lengths, T, B, Z, H,
+                       drop_thresh(p), umlh_enc_drop_inv_keep(p), seed, seed_ptr, ctx, lse);
     return (int)hipGetLastError();
 }
 
 int umlh_enc_launch_attention_bwd(const float* qkv, const int64_t* lengths, const float* lse, const float* dctx, int T, int B,
                                   int Z, int H, float p, unsigned long long seed, const unsigned long long* seed_ptr, float* dqkv,
                                   hipStream_t st) {
-    if (T < 1 || T > ATM || H < 1 || Z % H != 0 || Z / H > ADH) return (int)hipErrorInvalidValue;
-    const int rs = (Z / H) | 1;
-    const size_t smem = sizeof(float) * (4 * (size_t)T * rs + 2 * T + AW * 2 * T);
-    static std::atomic<unsigned long long> attr_done{0};      // bit d: done on device d (the attribute is per device)
-    int dev_ = 0;
-    (void)hipGetDevice(&dev_);
-    if (!((attr_done.load(std::memory_order_acquire) >> (dev_ & 63)) & 1ULL)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_bwd_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_done.fetch_or(1ULL << (dev_ & 63), std::memory_order_release);
-    }
-    hipLaunchKernelGGL(attention_bwd_kernel, dim3(B * H), dim3(64 * AW), smem, st, qkv, lengths, lse, dctx, T, B, Z, H, drop_thresh(p),
-                       p > 0.f ? 1.f / (1.f - p) : 1.f, seed, seed_ptr, dqkv);
+    if (!attention_shape_ok(T, Z, H)) return (int)hipErrorInvalidValue;
+    if (int e = raise_lds_limit<&attention_bwd_kernel>(ATT_MAX_LDS)) return e;
+    hipLaunchKernelGGL(attention_bwd_kernel, dim3(B * H), dim3(64 * AW), attention_bwd_lds(T, Z, H), st, qkv, lengths, lse, dctx, T, B,
+                       Z, H, drop_thresh(p), umlh_enc_drop_inv_keep(p), seed, seed_ptr, dqkv);
     return (int)hipGetLastError();
 }
 

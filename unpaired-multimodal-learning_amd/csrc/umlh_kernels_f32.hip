@@ -15,7 +15,6 @@
 #include "umlh_common.h"
 #include "umlh_launch.h"
 #include <cstdlib>
-#include <atomic>
 
 // timing-only ablations exist for kernel analysis and are compiled in only with -DUMLH_ABLATIONS (see umlh_kernels_bf16.hip)
 #ifdef UMLH_ABLATIONS
@@ -1739,15 +1738,7 @@ static size_t fwd_smem_bytes(int ctw, int wc, int mode) {
 #define FWD_CASE_F(CT, W, F)                                                                        \
     if (ctw == CT && wc == W && mode == F) {                                                        \
         size_t sm = fwd_smem_bytes(CT, W, F);                                                       \
-        static std::atomic<unsigned long long> attr_done{0};  /* bit d: done on device d (the attribute is per device) */ \
-        int dev_ = 0;                                                                               \
-        (void)hipGetDevice(&dev_);                                                                  \
-        if (!((attr_done.load(std::memory_order_acquire) >> (dev_ & 63)) & 1ULL)) {                 \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fwd_ce_f32<CT, W, F>),\
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);\
-            if (e != hipSuccess) return (int)e;                                                     \
-            attr_done.fetch_or(1ULL << (dev_ & 63), std::memory_order_release);                     \
-        }                                                                                           \
+        if (int e = raise_lds_limit<&fwd_ce_f32<CT, W, F>>((int)sm)) return e;                      \
         FwdArgs c_ = *a; c_.plain = umlh_plain_stores();                                            \
         hipLaunchKernelGGL((fwd_ce_f32<CT, W, F>), dim3(grid), dim3(512), sm, stream, c_);          \
         return (int)hipGetLastError();                                                              \
@@ -1784,15 +1775,8 @@ static bool dw_f32_applies(const GemmArgs* g, int ta, int tb) {
 int umlh_f32_launch_gemm(const GemmArgs* g, int ta, int tb, int splits, hipStream_t stream) {
     if (g->M <= 0 || g->N <= 0) return 0;
     if (dw_f32_applies(g, ta, tb)) {
-        int dev = 0;
-        static std::atomic<unsigned long long> attr_done{0};   // per-device bit: the kernel's dynamic LDS limit is raised once
-        if (hipGetDevice(&dev) != hipSuccess) return (int)hipErrorInvalidDevice;
-        if (!((attr_done.load(std::memory_order_acquire) >> (dev & 63)) & 1ULL)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dw_f32), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DW_SMEM);
-            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dw_f32x3), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DW_SMEM_X3);
-            if (e != hipSuccess) return (int)e;
-            attr_done.fetch_or(1ULL << (dev & 63), std::memory_order_release);
-        }
+        if (int e = raise_lds_limit<&dw_f32>((int)DW_SMEM)) return e;
+        if (int e = raise_lds_limit<&dw_f32x3>((int)DW_SMEM_X3)) return e;
         GemmArgs a = *g;
         a.slab_count = splits;
         a.plain = umlh_plain_stores();

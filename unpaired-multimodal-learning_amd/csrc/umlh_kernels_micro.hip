@@ -23,7 +23,6 @@
 // chains micro launches of one process on one device; every spin is bounded and reports through a status word.
 #include "umlh_common.h"
 #include "umlh_launch.h"
-#include <atomic>
 #include "umlh_micro.h"
 #include <type_traits>
 
@@ -759,15 +758,7 @@ __global__ __launch_bounds__(256) void micro_steps_kernel(const UmlhMicroHead* _
 template <int NCH, int CW, bool BF>
 int launch_one(const UmlhMicroHead* heads, int n_heads, int n_steps, int grid, hipStream_t st) {
     using K = MicroCfg<NCH, CW, BF && CW == 128 && NCH <= 5>;
-    static std::atomic<unsigned long long> attr_done{0};   // bit d: done on device d
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!((attr_done.load(std::memory_order_acquire) >> (dev & 63)) & 1ULL)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&micro_steps_kernel<NCH, CW, BF>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, K::SMEM);
-        if (e != hipSuccess) return (int)e;
-        attr_done.fetch_or(1ULL << (dev & 63), std::memory_order_release);
-    }
+    if (int e = raise_lds_limit<&micro_steps_kernel<NCH, CW, BF>>(K::SMEM)) return e;
     hipLaunchKernelGGL((micro_steps_kernel<NCH, CW, BF>), dim3(grid), dim3(256), K::SMEM, st, heads, n_heads, n_steps);
     return (int)hipGetLastError();
 }

@@ -26,7 +26,7 @@
 //   narrow N      a product with fewer output tiles than waves (z = 40: 3) splits its reduction across the idle waves in
 //                 contiguous runs of blocks; the partial sums meet in LDS and are added in run order (rr_ksplit, rr_combine).
 //   latency       the weight loads of 12 blocks x tiles are issued before the first MFMA of a batch (rr_accumulate_nt).
-//   LayerNorm     add_layernorm_fwd_kernel's formulas (mean, then the biased variance of the differences, rsqrtf(var + eps));
+//   LayerNorm     add_layernorm_kernel's formulas (mean, then the biased variance of the differences, rsqrtf(var + eps));
 //                 thread (row, part of 32) adds its columns, the 32 parts are added in part order by every thread of the row.
 //   relu          fmaxf(v, 0) as bias_act_kernel (NaN -> 0).
 // A row's trajectory depends on (Z, d_ff, D, the parameters, its seed) alone: not on n, its index, the grid or the CU count.
@@ -42,7 +42,6 @@
 #include "umlh_common.h"
 #include "umlh_launch.h"
 #include <algorithm>
-#include <atomic>
 
 namespace {
 
@@ -479,20 +478,6 @@ inline size_t sp_lds_bytes(int T) {
     return 2 * (size_t)T * sizeof(double) + K * SP_COLS * sizeof(double) + (size_t)T * SP_COLS * sizeof(float);
 }
 
-// hipFuncAttributeMaxDynamicSharedMemorySize once per device and kernel
-template <class F>
-int raise_lds_limit(F kernel, std::atomic<unsigned long long>& done, int bytes) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return (int)e;
-    if (!((done.load(std::memory_order_acquire) >> (dev & 63)) & 1ULL)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return (int)e;
-        done.fetch_or(1ULL << (dev & 63), std::memory_order_release);
-    }
-    return 0;
-}
-
 }  // namespace
 
 // LDS bytes of one rollout workgroup at this shape (the API compares it with UMLH_ROLLOUT_MAX_LDS)
@@ -501,8 +486,7 @@ extern "C" unsigned long long umlh_rollout_lds_bytes(int Z, int dff, int D) { re
 extern "C" int umlh_rollout_launch(const umlh_rollout_cfg_t* cfg, const float* const* P, const float* conv_w, const float* pos0,
                                    const float* w_in, const float* b_in, const float* w_out, const float* b_out, const float* x0,
                                    long long ldx, long long n, float* out, long long ldb, long long ldt, hipStream_t st) {
-    static std::atomic<unsigned long long> done{0};
-    if (int e = raise_lds_limit(&rollout_rows, done, UMLH_ROLLOUT_MAX_LDS)) return e;
+    if (int e = raise_lds_limit<&rollout_rows>(UMLH_ROLLOUT_MAX_LDS)) return e;
     RolloutArgs a;
     for (int l = 0; l < UMLH_ROLLOUT_MAX_LAYERS; ++l)
         for (int j = 0; j < 12; ++j) a.p[l][j] = l < cfg->n_layers ? P[12 * l + j] : nullptr;
@@ -528,8 +512,7 @@ extern "C" unsigned long long umlh_spectrum_bytes(int B, int T, int d) {
 
 extern "C" int umlh_spectrum_launch(const float* x, long long ldb, long long ldt, int B, int T, int d, double* out, void* scratch,
                                     hipStream_t st) {
-    static std::atomic<unsigned long long> done{0};
-    if (int e = raise_lds_limit(&spec_partial, done, (int)sp_lds_bytes(UMLH_SPECTRUM_MAX_T))) return e;
+    if (int e = raise_lds_limit<&spec_partial>((int)sp_lds_bytes(UMLH_SPECTRUM_MAX_T))) return e;
     double* partial = reinterpret_cast<double*>(scratch);
     const long long p = umlh_spectrum_partials(B, T, d);
     const int col_chunks = (d + SP_COLS - 1) / SP_COLS, K = T / 2 + 1;

@@ -3,6 +3,7 @@
 // calls one includes this header, so a prototype that drifts from its definition is a compile error (the names are
 // extern "C": a drifted prototype would still link).  Not part of the C ABI (include/umlh.h).
 #pragma once
+#include <atomic>
 #include "umlh_common.h"
 #include "umlh_micro.h"
 
@@ -10,6 +11,24 @@
 inline long long align_up(long long x) { return (x + 255) / 256 * 256; }
 template <class T>
 inline T* at(void* scratch, long long off) { return reinterpret_cast<T*>(static_cast<char*>(scratch) + off); }
+
+// Raises Kernel's dynamic-LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) to `bytes`, once per device: the attribute is per
+// device, and bit d of the mask (one mask per kernel instantiation) says it is set on device d.  Returns 0 or the HIP error of
+// hipGetDevice / hipFuncSetAttribute.  Called right before the launch it serves: a stream capture cannot set attributes, so a
+// launcher's first call on a device must come outside one.
+template <auto Kernel>
+__attribute__((visibility("hidden"))) int raise_lds_limit(int bytes) {
+    static std::atomic<unsigned long long> done{0};
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return (int)e;
+    if (!((done.load(std::memory_order_acquire) >> (dev & 63)) & 1ULL)) {
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (e != hipSuccess) return (int)e;
+        done.fetch_or(1ULL << (dev & 63), std::memory_order_release);
+    }
+    return 0;
+}
 
 extern "C" {
 // ---- umlh_kernels_f32.hip: fp32 head step, generic fp32 GEMMs, optimizer / finalize kernels ----
@@ -68,11 +87,10 @@ int umlh_enc_launch_add_layernorm(const float* x, const float* r, const float* g
                                   float eps, float* s_out, float* y, float* mean, float* rstd, hipStream_t st);
 int umlh_enc_launch_layernorm_bwd(const float* dy, const float* s, const float* gamma, const float* mean, const float* rstd,
                                   int M, int N, float* ds, float* dgamma, float* dbeta, hipStream_t st);
-int umlh_enc_launch_reduce_epilogue(const float* slabs, int ns, long long stride, long long total, int N, const Epilogue* e,
-                                    float* out, hipStream_t st);
-// out[m*ldo + n] (m < M, n < N) = sum of ns slabs (slab s at slabs + s*stride, same row stride ldo); columns [N, ldo) untouched
-int umlh_enc_launch_reduce_window(const float* slabs, int ns, long long stride, int M, int N, int ldo, float* out,
-                                  hipStream_t st);
+// out[m*ldo + n] (m < M, n < N) = epilogue(sum of ns slabs) (slab s at slabs + s*stride, same row stride ldo); columns [N, ldo)
+// untouched.  e may be NULL (none); an epilogue indexes dense [M, N] buffers: hipErrorInvalidValue for one at ldo != N
+int umlh_enc_launch_reduce_slabs(const float* slabs, int ns, long long stride, int M, int N, int ldo, const Epilogue* e, float* out,
+                                 hipStream_t st);
 int umlh_enc_launch_add_layernorm_fused(const float* x, int ns, long long stride, const Epilogue* e, const float* gamma,
                                         const float* beta, int M, int N, float eps, float* s_out, float* y, float* mean,
                                         float* rstd, hipStream_t st);

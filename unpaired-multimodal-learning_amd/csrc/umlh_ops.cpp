@@ -92,20 +92,11 @@ int umlh_seq_mse_forward(const float* z, const float* w, const float* bias, cons
     return UMLH_OK;
 }
 
-// split-K factor / row chunking of the decoder gradient: dW [D,Z] over B*T rows (same rule as the encoder layers)
-static int seq_splits(int D, int Z, int R) {
-    const long long tiles = (long long)((D + 63) / 64) * ((Z + 63) / 64);
-    long long s = (768 + tiles - 1) / tiles;
-    if (s > R / 64) s = R / 64;
-    if (s > 32) s = 32;
-    return (int)(s < 1 ? 1 : s);
-}
-static int seq_row_chunk(int R) { int c = (R + 63) / 64; return c < 64 ? 64 : c; }
-
+// the decoder gradient dW [D,Z] over R = B*T rows: splits_for(D, Z, R) slabs and row_chunk(R) rows per db partial, the encoder layers' rule
 uint64_t umlh_seq_mse_backward_scratch_floats(int32_t B, int32_t T, int32_t Z, int32_t D) {
     if (B < 1 || T < 1 || Z < 1 || D < 1) return 0;
-    const int R = B * T, chunk = seq_row_chunk(R);
-    return (uint64_t)seq_splits(D, Z, R) * D * Z + (uint64_t)((R + chunk - 1) / chunk) * D + 64;
+    const int R = B * T, chunk = row_chunk(R);
+    return (uint64_t)splits_for(D, Z, R) * D * Z + (uint64_t)((R + chunk - 1) / chunk) * D + 64;
 }
 
 int umlh_seq_mse_backward(const float* z, const float* w, const float* dres, const float* loss_cnt, const float* grad_out,
@@ -113,7 +104,7 @@ int umlh_seq_mse_backward(const float* z, const float* w, const float* dres, con
     if (!z || !w || !dres || !loss_cnt || !grad_out || !dz || !dw || !db) return fail(UMLH_E_INVALID, "umlh_seq_mse_backward: null buffer");
     if (B < 1 || T < 1 || Z < 1 || D < 1 || D > 8192) return fail(UMLH_E_INVALID, "umlh_seq_mse_backward: bad shape");
     hipStream_t st = (hipStream_t)stream;
-    const int R = B * T, sp = seq_splits(D, Z, R);
+    const int R = B * T, sp = splits_for(D, Z, R);
     if (!scratch || sp == 1) {
         HIPCHK(umlh_seq_launch_bwd(z, w, dres, loss_cnt, grad_out, B, T, Z, D, dz, dw, db, 1, st), "seq bwd");
         return UMLH_OK;
@@ -121,7 +112,7 @@ int umlh_seq_mse_backward(const float* z, const float* w, const float* dres, con
     // dz as before; dW[d][k] = s * sum_r dres[r][d] z[r][k] as split-K slabs, db[d] = s * sum_r dres[r][d] as row-chunk partials,
     // both summed and scaled (s = 2 * grad_out / denominator, device-side) by one multi-reduce
     HIPCHK(umlh_seq_launch_bwd(z, w, dres, loss_cnt, grad_out, B, T, Z, D, dz, dw, db, 0, st), "seq bwd (dz)");
-    const int chunk = seq_row_chunk(R), nr = (R + chunk - 1) / chunk;
+    const int chunk = row_chunk(R), nr = (R + chunk - 1) / chunk;
     float* slabs = scratch;
     float* part = scratch + (size_t)sp * D * Z;
     int ns = 1;
@@ -192,7 +183,7 @@ int umlh_gemm_f32(const float* A, const float* B, float* out, int32_t M, int32_t
     const int ns = (K + chunk - 1) / chunk;
     g.out = slabs; g.k_chunk = chunk; g.slab_stride = (long long)M * ldo;
     HIPCHK(launch(&g, ta, tb, ns, (hipStream_t)stream), "gemm_f32 (split-K)");
-    HIPCHK(umlh_enc_launch_reduce_window(slabs, ns, g.slab_stride, M, N, ldo, out, (hipStream_t)stream), "split-K reduce");
+    HIPCHK(umlh_enc_launch_reduce_slabs(slabs, ns, g.slab_stride, M, N, ldo, nullptr, out, (hipStream_t)stream), "split-K reduce");
     return UMLH_OK;
 }
 
@@ -218,9 +209,7 @@ int umlh_gemm_f32_epi(const float* A, const float* B, float* out, int M, int N, 
     g.out = slabs;
     HIPCHK(umlh_f32_launch_gemm_enc(&g, ta, tb, ns, stream), "gemm_enc (slabs)");
     if (defer) return UMLH_OK;
-    Epilogue none;
-    memset(&none, 0, sizeof(none));
-    HIPCHK(umlh_enc_launch_reduce_epilogue(slabs, ns, g.slab_stride, g.slab_stride, N, epi ? epi : &none, out, stream), "split-K reduce (epilogue)");
+    HIPCHK(umlh_enc_launch_reduce_slabs(slabs, ns, g.slab_stride, M, N, N, epi, out, stream), "split-K reduce (epilogue)");
     return UMLH_OK;
 }
 

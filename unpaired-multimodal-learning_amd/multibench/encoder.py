@@ -31,7 +31,7 @@ def _f32(t):
 
 
 def _splits(m, n, k):
-    """Split-K factor (same rule as csrc/umlh_encoder.cpp: splits_for): these GEMMs have few 64x64 output tiles
+    """Split-K factor (same rule as csrc/umlh_host.h: splits_for): these GEMMs have few 64x64 output tiles
     (z <= 300) and a long reduction (1600 token rows or the 2048-wide FFN) whose walk is latency-bound, so K is cut
     until ~768 workgroups with at least 64 reduction rows each."""
     tiles = ((m + 63) // 64) * ((n + 63) // 64)
