@@ -471,6 +471,31 @@ void umlh_encoder_plan_destroy(umlh_enc_plan_t plan);
  * sampler order (that is reproduced host-side by the loader, finetune.py:370-371). */
 int  umlh_random_permutation(int64_t n, uint64_t seed, int64_t* out, void* stream);
 
+/* The row ids of a block of training steps, both modalities in one launch (index_block_kernel): each modality's ids are the
+ * ids of its spans written back to back into its destination, which then serves as umlh_stream_t.index.  A span is `count`
+ * consecutive positions start .. start+count-1 of one epoch order of n rows:
+ *   UMLH_SPAN_FEISTEL  the order of umlh_random_permutation(n, seed): ids bit-identical to out[start .. start+count) of that
+ *                      call, computed per element, the permutation is never written out;
+ *   UMLH_SPAN_TABLE    order[start .. start+count) of a materialised device order of n int64 ids (a copy);
+ *   UMLH_SPAN_IOTA     start .. start+count-1 (an unshuffled loader).
+ * A modality without rows passes n_spans = 0.  Any number of spans: one launch carries 32 of them, more spans take more launches.
+ * A span with count < 0, start < 0 or start + count > n, a FEISTEL span with n > 2^62, a TABLE span without order and a
+ * destination missing for a positive total are UMLH_E_INVALID, checked for every span before the first launch.  Additive to
+ * ABI v11: umlh_version() is unchanged, callers detect the feature by this symbol. */
+#define UMLH_SPAN_FEISTEL 0
+#define UMLH_SPAN_TABLE   1
+#define UMLH_SPAN_IOTA    2
+typedef struct {
+    int32_t kind;            /* UMLH_SPAN_* */
+    int32_t reserved;        /* 0 */
+    int64_t n;               /* rows of the epoch order */
+    uint64_t seed;           /* FEISTEL: the permutation's key */
+    const int64_t* order;    /* TABLE: device, n ids; otherwise unused */
+    int64_t start, count;
+} umlh_index_span_t;
+int  umlh_index_block(const umlh_index_span_t* img_spans, int32_t n_img_spans, int64_t* img_out,
+                      const umlh_index_span_t* txt_spans, int32_t n_txt_spans, int64_t* txt_out, void* stream);
+
 /* Standalone optimizer.step() for one parameter tensor from a caller-computed
  * gradient (engine/optimizer/optim.py:34-71; torch.optim single-tensor recurrences):
  * the same update kernel the fused step applies.  v may be NULL for SGD. */

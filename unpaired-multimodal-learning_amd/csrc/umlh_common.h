@@ -228,6 +228,13 @@ struct MultiReduceArgs {
     const float* s_num; const float* s_den; float s_mul;   // s_num != NULL: every sum is scaled by s_mul * s_num[0] / s_den[0]
 };
 
+// one launch writes the row ids of a block of steps for both modalities: dst[j] = id j of a span, the spans of a modality back to
+// back (descriptor table travels as a kernel argument).  kind: UMLH_SPAN_* of include/umlh.h; blk0 = first 256-id block of the span.
+constexpr int UMLH_INDEX_SPANS_MAX = 32;
+struct IndexSpanDesc { const long long* order; long long* dst; long long n; unsigned long long seed; long long start; long long count;
+                       int kind; int half; int blk0; int pad; };
+struct IndexBlockArgs { IndexSpanDesc s[UMLH_INDEX_SPANS_MAX]; int count; };
+
 struct OptArgs {
     int   kind;                  // UMLH_OPT_*
     float lr, decay;             // decay = 1 - lr*wd (AdamW)

@@ -14,6 +14,7 @@
 //   zero_shot      head.py:22-37
 #include "umlh_common.h"
 #include "umlh_launch.h"
+#include "umlh_feistel.h"
 #include <cstdlib>
 
 // timing-only ablations exist for kernel analysis and are compiled in only with -DUMLH_ABLATIONS (see umlh_kernels_bf16.hip)
@@ -1625,36 +1626,33 @@ __global__ __launch_bounds__(256) void zero_shot_kernel(const float* __restrict_
 }
 
 // --------------------------------------------------------------------------- //
-// epoch shuffles without a sort: out[i] = pi(i), pi = 4-round Feistel network over 2*half bits
-// keyed by `seed`, restricted to [0, n) by cycle walking (a bijection; O(1) per element).
+// epoch shuffles without a sort: out[i] = pi(i), the Feistel permutation of umlh_feistel.h.
 // Used for throughput-mode loaders (order_rng="device"); reference-identical orders come from
 // the CPU sampler restatement instead.
 // --------------------------------------------------------------------------- //
-__device__ __forceinline__ unsigned mix32(unsigned x) {
-    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
-    return x;
-}
-
 __global__ __launch_bounds__(256) void feistel_perm_kernel(long long n, unsigned long long seed, int half,
                                                            long long* __restrict__ out) {
     long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const unsigned long long mask = (1ULL << half) - 1ULL;
-    const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-    unsigned long long x = (unsigned long long)i;
-    do {
-        unsigned long long L = x >> half, R = x & mask;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            unsigned long long F = (unsigned long long)mix32((unsigned)R * 0x9e3779b1U + (r & 1 ? k1 : k0) + 0x85ebca6bU * (unsigned)r +
-                                                               (unsigned)(R >> 32)) & mask;
-            unsigned long long nl = R;
-            R = L ^ F;
-            L = nl;
-        }
-        x = (L << half) | R;
-    } while (x >= (unsigned long long)n);
-    out[i] = (long long)x;
+    out[i] = feistel_index(i, n, seed, half);
+}
+
+// --------------------------------------------------------------------------- //
+// the row ids of a block of steps: every span of both modalities in one launch, one thread per id.  A span owns the 256-id
+// blocks blk0 .. blk0 + ceil(count / 256) - 1; a block finds its span by walking the (at most 32) descriptors, which is
+// uniform over the block.  FEISTEL ids are computed in place (no permutation of n rows is written), TABLE ids are copied.
+// --------------------------------------------------------------------------- //
+__global__ __launch_bounds__(256) void index_block_kernel(IndexBlockArgs a) {
+    int s = 0;
+    while (s + 1 < a.count && (int)blockIdx.x >= a.s[s + 1].blk0) ++s;
+    const IndexSpanDesc& d = a.s[s];
+    const long long j = (long long)((int)blockIdx.x - d.blk0) * 256 + threadIdx.x;
+    if (j >= d.count) return;
+    const long long i = d.start + j;
+    long long id = i;
+    if (d.kind == UMLH_SPAN_FEISTEL) id = feistel_index(i, d.n, d.seed, d.half);
+    else if (d.kind == UMLH_SPAN_TABLE) id = d.order[i];
+    d.dst[j] = id;
 }
 
 // --------------------------------------------------------------------------- //
@@ -1867,10 +1865,22 @@ int umlh_launch_head_step(const HeadFuse* hf, const DiagArgs* dg, float* shadow3
 
 int umlh_launch_feistel_perm(long long n, unsigned long long seed, long long* out, hipStream_t stream) {
     if (n <= 0) return 0;
-    int bits = 1;
-    while ((1LL << bits) < n) ++bits;
-    int half = (bits + 1) / 2;
-    hipLaunchKernelGGL(feistel_perm_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, seed, half, out);
+    hipLaunchKernelGGL(feistel_perm_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, seed, feistel_half(n), out);
+    return (int)hipGetLastError();
+}
+
+// a->s[i].half and .blk0 are filled here; spans with count == 0 are legal (they own no block)
+int umlh_launch_index_block(IndexBlockArgs* a, hipStream_t stream) {
+    long long blocks = 0;
+    for (int i = 0; i < a->count; ++i) {
+        IndexSpanDesc& d = a->s[i];
+        d.half = d.kind == UMLH_SPAN_FEISTEL ? feistel_half(d.n) : 0;
+        d.blk0 = (int)blocks;
+        blocks += (d.count + 255) / 256;
+        if (blocks > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+    }
+    if (blocks == 0) return 0;
+    hipLaunchKernelGGL(index_block_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, *a);
     return (int)hipGetLastError();
 }
 

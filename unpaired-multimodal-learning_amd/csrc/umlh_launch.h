@@ -44,6 +44,7 @@ int umlh_launch_multi_opt(int n, float* const* p, const float* const* g, float* 
                           const OptArgs* o, hipStream_t stream);
 int umlh_launch_head_step(const HeadFuse* hf, const DiagArgs* dg, float* shadow32, hipStream_t stream);
 int umlh_launch_feistel_perm(long long n, unsigned long long seed, long long* out, hipStream_t stream);
+int umlh_launch_index_block(IndexBlockArgs* a, hipStream_t stream);
 int umlh_launch_finalize(const FinalizeArgs* f, hipStream_t stream);
 int umlh_launch_zero_shot(const float* feats, const int64_t* labels, long long n, int d, int C, float* w, hipStream_t stream);
 // ---- umlh_kernels_bf16.hip: bf16 head step ----

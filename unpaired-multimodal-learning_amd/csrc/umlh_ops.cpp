@@ -303,6 +303,56 @@ int umlh_random_permutation(int64_t n, uint64_t seed, int64_t* out, void* stream
     return UMLH_OK;
 }
 
+// the spans of one modality of umlh_index_block; 0 = fine, *total = ids they write
+static int check_index_spans(const char* who, const char* side, const umlh_index_span_t* spans, int32_t n_spans, const int64_t* out,
+                             int64_t* total) {
+    *total = 0;
+    if (n_spans < 0 || (n_spans > 0 && !spans)) return fail(UMLH_E_INVALID, "%s: %s: %d spans without a span array", who, side, n_spans);
+    for (int i = 0; i < n_spans; ++i) {
+        const umlh_index_span_t& s = spans[i];
+        if (s.kind < UMLH_SPAN_FEISTEL || s.kind > UMLH_SPAN_IOTA) return fail(UMLH_E_INVALID, "%s: %s span %d: unknown kind %d", who, side, i, s.kind);
+        if (s.n < 0 || s.start < 0 || s.count < 0 || s.start > s.n || s.count > s.n - s.start)
+            return fail(UMLH_E_INVALID, "%s: %s span %d: start=%lld count=%lld outside an order of n=%lld rows", who, side, i,
+                        (long long)s.start, (long long)s.count, (long long)s.n);
+        if (s.kind == UMLH_SPAN_FEISTEL && s.n > ((int64_t)1 << 62))
+            return fail(UMLH_E_INVALID, "%s: %s span %d: n=%lld rows (a Feistel order holds at most 2^62)", who, side, i, (long long)s.n);
+        if (s.kind == UMLH_SPAN_TABLE && s.count > 0 && !s.order) return fail(UMLH_E_INVALID, "%s: %s span %d: a TABLE span needs its order", who, side, i);
+        *total += s.count;
+        if (*total >= ROWS_END) return fail(UMLH_E_INVALID, "%s: %s: more than 2^31 - 1 ids in one block", who, side);
+    }
+    if (*total > 0 && !out) return fail(UMLH_E_INVALID, "%s: %s: %lld ids and no destination", who, side, (long long)*total);
+    return UMLH_OK;
+}
+
+int umlh_index_block(const umlh_index_span_t* img_spans, int32_t n_img_spans, int64_t* img_out, const umlh_index_span_t* txt_spans,
+                     int32_t n_txt_spans, int64_t* txt_out, void* stream) {
+    const char* who = "umlh_index_block";
+    int64_t total_img = 0, total_txt = 0;
+    RC(check_index_spans(who, "image", img_spans, n_img_spans, img_out, &total_img));
+    RC(check_index_spans(who, "text", txt_spans, n_txt_spans, txt_out, &total_txt));
+    // descriptors travel by value, UMLH_INDEX_SPANS_MAX per launch: image spans first, then text, each modality back to back
+    IndexBlockArgs a;
+    memset(&a, 0, sizeof(a));
+    const umlh_index_span_t* side[2] = {img_spans, txt_spans};
+    const int32_t n_side[2] = {n_img_spans, n_txt_spans};
+    int64_t* dst_side[2] = {img_out, txt_out};
+    for (int m = 0; m < 2; ++m) {
+        long long* dst = ll(dst_side[m]);
+        for (int i = 0; i < n_side[m]; ++i) {
+            const umlh_index_span_t& s = side[m][i];
+            if (s.count == 0) continue;
+            a.s[a.count++] = IndexSpanDesc{ll(s.order), dst, s.n, s.seed, s.start, s.count, s.kind, 0, 0, 0};
+            dst += s.count;
+            if (a.count == UMLH_INDEX_SPANS_MAX) {
+                HIPCHK(umlh_launch_index_block(&a, (hipStream_t)stream), who);
+                a.count = 0;
+            }
+        }
+    }
+    if (a.count > 0) HIPCHK(umlh_launch_index_block(&a, (hipStream_t)stream), who);
+    return UMLH_OK;
+}
+
 // the step's optimizer constants from loose hyper-parameters
 static OptArgs standalone_opt(int32_t optimizer, double lr, int64_t step, double beta1, double beta2, double eps, double momentum,
                               double weight_decay) {

@@ -145,38 +145,63 @@ class _IndexIter:
     def __init__(self, loader: FeatureLoader):
         self.loader = loader
         torch.empty((), dtype=torch.int64).random_(generator=loader.generator)   # DataLoader iterator base seed
-        self.order = None
+        self.epoch = None       # umlh.EpochOrder of this iterator's epoch, made at its first batch
         self.pos = 0
 
     def __iter__(self):
         return self
 
-    def __next__(self):
+    @property
+    def order(self):
+        """The epoch's order as a device tensor (None before the first batch).  A device-drawn epoch is known by (n, seed):
+        its permutation is written out here, when somebody asks for it, and not by the blockwise loop."""
+        return None if self.epoch is None else self.epoch.tensor()
+
+    @order.setter
+    def order(self, value):
+        if value is None:
+            self.epoch = None
+        elif self.epoch is None or self.epoch._order is not value:
+            import umlh
+            self.epoch = umlh.EpochOrder.table(value)
+
+    def _begin_epoch(self):
+        import umlh
+        ld = self.loader
+        n, dev = len(ld.table), ld.table.device
+        if ld.shuffle:
+            seed = int(torch.empty((), dtype=torch.int64).random_(generator=ld.generator).item())   # RandomSampler seed
+            if ld.order_rng == "device":
+                self.epoch = umlh.EpochOrder.permutation(n, seed, dev)      # no kernel: ids are computed where they are consumed
+            else:
+                g = torch.Generator()
+                g.manual_seed(seed)
+                self.epoch = umlh.EpochOrder.table(torch.randperm(n, generator=g).to(dev, non_blocking=True))
+        else:
+            self.epoch = umlh.EpochOrder.identity(n, dev)
+
+    def next_span(self):
+        """``__next__`` as a ``umlh.IndexSpan`` (positions of the epoch's order) instead of an index tensor: same RNG draws,
+        same StopIteration."""
+        import umlh
         ld = self.loader
         n, bs = len(ld.table), ld.batch_size
-        if self.order is None:
-            if ld.shuffle:
-                seed = int(torch.empty((), dtype=torch.int64).random_(generator=ld.generator).item())   # RandomSampler seed
-                if ld.order_rng == "device":
-                    import umlh
-                    self.order = umlh.random_permutation(n, seed, ld.table.device)   # one tiny kernel, no sort
-                else:
-                    g = torch.Generator()
-                    g.manual_seed(seed)
-                    self.order = torch.randperm(n, generator=g).to(ld.table.device, non_blocking=True)
-            else:
-                self.order = torch.arange(n, dtype=torch.int64, device=ld.table.device)
+        if self.epoch is None:
+            self._begin_epoch()
         if self.pos >= n or (ld.drop_last and self.pos + bs > n):
             raise StopIteration
-        idx = self.order[self.pos:self.pos + bs]
+        span = umlh.IndexSpan(self.epoch, self.pos, min(bs, n - self.pos))
         self.pos += bs
-        return idx
+        return span
 
-    # -- bulk access for the blockwise training loop: many consecutive batches of the CURRENT epoch as one slice --
+    def __next__(self):
+        return self.next_span().tensor()
+
+    # -- bulk access for the blockwise training loop: many consecutive batches of the CURRENT epoch as one span --
     def remaining(self):
         """Batches left in the current epoch that ``__next__`` would deliver without raising (0 before the first
-        batch of an epoch has been drawn: that call draws the sampler seed and must go through ``__next__``)."""
-        if self.order is None:
+        batch of an epoch has been drawn: that call draws the sampler seed and must go through ``__next__`` / ``next_span``)."""
+        if self.epoch is None:
             return 0
         ld = self.loader
         n, bs = len(ld.table), ld.batch_size
@@ -184,14 +209,15 @@ class _IndexIter:
         return max(0, left // bs if ld.drop_last else (left + bs - 1) // bs)
 
     def take_span(self, k):
-        """The next ``k <= remaining()`` batches as (one index slice, [batch sizes])."""
+        """The next ``k <= remaining()`` batches as (one ``umlh.IndexSpan``, [batch sizes])."""
+        import umlh
         ld = self.loader
         n, bs = len(ld.table), ld.batch_size
         end = min(n, self.pos + k * bs)
-        idx = self.order[self.pos:end]
+        span = umlh.IndexSpan(self.epoch, self.pos, end - self.pos)
         sizes = [bs] * ((end - self.pos) // bs)
         if (end - self.pos) % bs:
             sizes.append((end - self.pos) % bs)
         assert len(sizes) == k
         self.pos = end
-        return idx, sizes
+        return span, sizes

@@ -101,6 +101,17 @@ class _RowSource:
         idx, self.it = fetch_next(_Reiter(self._make_iter), self.it)
         return idx
 
+    def next_span(self):
+        """``next_index()`` for the blockwise loop: the same batch (same RNG draws, same restart at the end of an epoch) as a
+        ``umlh.IndexSpan`` where the iterator can say it that way, so that no index tensor is made for it."""
+        if not hasattr(self.it, "next_span"):
+            return self.next_index()
+        try:
+            return self.it.next_span()
+        except StopIteration:
+            self.it = self._make_iter()
+            return self.it.next_span()
+
     def remaining(self):
         return self.it.remaining() if self.indexed and hasattr(self.it, "remaining") else 0
 
@@ -114,12 +125,12 @@ class _RowSource:
     def save(self):
         """Position of the batch stream (iterator, epoch order, offset): ``restore`` rewinds to it."""
         it = self.it
-        return it, getattr(it, "order", None), getattr(it, "pos", None)
+        return it, getattr(it, "epoch", None), getattr(it, "pos", None)      # (the epoch's description: nothing is materialised)
 
     def restore(self, st):
         self.it = st[0]
         if st[2] is not None:
-            self.it.order, self.it.pos = st[1], st[2]
+            self.it.epoch, self.it.pos = st[1], st[2]
 
     def next(self) -> umlh.RowBatch:
         batch, self.it = fetch_next(_Reiter(self._make_iter), self.it)
@@ -188,8 +199,10 @@ def _block_end(i, max_iters, eval_freq):
 
 def _draw_block(img_src, txt_src, n):
     """Index batches of the next ``n`` steps of both loaders.  Consecutive batches inside both loaders' current epochs are
-    taken as ONE index slice each; a step at which a loader starts an epoch goes through next_index() -- image then
-    text, the reference's draw order (finetune.py:164-174) -- so the RNG protocol is untouched."""
+    taken as ONE span each; a step at which a loader starts an epoch goes through next_span() -- image then
+    text, the reference's draw order (finetune.py:164-174) -- so the RNG protocol is untouched.  The entries are
+    ``umlh.IndexSpan`` s (positions of an epoch order, not ids): ``HeadEngine.prepare_steps`` writes the ids of both
+    modalities with one launch, and no epoch permutation is materialised for the block."""
     bi = [] if img_src is not None else None
     bt = [] if txt_src is not None else None
     k = 0
@@ -197,9 +210,9 @@ def _draw_block(img_src, txt_src, n):
         span = min([n - k] + [src.remaining() for src in (img_src, txt_src) if src is not None])
         if span == 0:
             if img_src is not None:
-                bi.append(img_src.next_index())
+                bi.append(img_src.next_span())
             if txt_src is not None:
-                bt.append(txt_src.next_index())
+                bt.append(txt_src.next_span())
             k += 1
         else:
             if img_src is not None:

@@ -51,6 +51,14 @@ class Stream(C.Structure):
                 ("offsets", C.POINTER(C.c_int32))]
 
 
+SPAN_FEISTEL, SPAN_TABLE, SPAN_IOTA = range(3)      # UMLH_SPAN_*
+
+
+class IndexSpanDesc(C.Structure):                  # umlh_index_span_t
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("n", C.c_int64), ("seed", C.c_uint64), ("order", C.c_void_p),
+                ("start", C.c_int64), ("count", C.c_int64)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p)   # umlh_allreduce_fn
 COMM_ID_BYTES = 128
 
@@ -163,6 +171,7 @@ def _prototypes() -> dict:
         "umlh_encoder_plan_destroy": (None, (vp,)),
         # permutation, standalone optimizer
         "umlh_random_permutation": (rc, (i64, u64, vp, vp)),
+        "umlh_index_block": (rc, (P(IndexSpanDesc), i32, vp, P(IndexSpanDesc), i32, vp, vp)),
         "umlh_optimizer_step": (rc, (i32, vp, vp, vp, vp, i64, f64, i64, f64, f64, f64, f64, f64, vp)),
         "umlh_optimizer_step_multi": (rc, (i32, i32, pv, pv, pv, pv, P(i64), f64, i64, f64, f64, f64, f64, f64, vp)),
         # alignment metrics

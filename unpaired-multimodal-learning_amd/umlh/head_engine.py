@@ -264,7 +264,7 @@ class HeadEngine:
             raise UmlhError("train_steps: table must be contiguous fp32 [N,dim] + int64 labels")
         if self.precision == "bf16" and (f16 is None or f16.dtype != torch.bfloat16 or f16.shape != f.shape):
             raise UmlhError("train_steps: bf16 engine needs the table's bf16 shadow")
-        # an entry is one step's index vector, or (index slice, [sizes]) covering several consecutive steps
+        # an entry is one step's index vector or IndexSpan, or (index slice or IndexSpan, [sizes]) covering several consecutive steps
         import numpy as np
         parts, sizes = [], []
         for b in batches:
@@ -281,19 +281,41 @@ class HeadEngine:
         largest = int(np.diff(offs_np).max()) if n else 0
         if largest > cap:
             raise UmlhError(f"train_steps: batch of {largest} rows exceeds capacity {cap}")
-        idx = torch.cat(parts) if len(parts) > 1 else parts[0].contiguous()
-        if idx.numel() != int(offs_np[n]):
+        if sum(int(p.numel()) for p in parts) != int(offs_np[n]):
             raise UmlhError("train_steps: index slices do not match their batch sizes")
+        # one tensor is the block's vector as it stands; anything else (spans of epoch orders, several slices) is written
+        # back to back into one vector by the index-block launch of _fill_index, which serves both modalities
+        # (keep[3], the vector itself, and Stream.index are then set by the fill)
+        idx = fill = None
+        if len(parts) == 1 and isinstance(parts[0], torch.Tensor):
+            idx = parts[0].contiguous()
+        else:
+            fill = (_span_descs(parts, self.device), int(offs_np[n]))
         offs = offs_np.ctypes.data_as(C.POINTER(C.c_int32))
-        keep = (f, y, f16, idx, offs_np)
+        keep = [f, y, f16, idx, offs_np, fill]
         return Stream(ptr(f), ptr(f16), ptr(y), ptr(idx), offs), keep
+
+    def _fill_index(self, si, keep_i, st, keep_t) -> None:
+        """The index-block launch behind ``_make_stream``: the pending vectors of both modalities into fresh tensors, ONE launch
+        on the current stream (none when both are tensors the caller passed whole)."""
+        fills = []
+        for s, k in ((si, keep_i), (st, keep_t)):
+            if k is None or k[5] is None:
+                fills.append(None)
+                continue
+            k[3] = torch.empty(k[5][1], dtype=torch.int64, device=self.device)
+            s.index = k[3].data_ptr()
+            fills.append((k[5][0], k[3]))
+        if fills[0] is not None or fills[1] is not None:
+            _index_block_launch(self.lib, fills[0], fills[1], self.device)
 
     def train_steps(self, img_table, img_index_batches, txt_table, txt_index_batches, lrs, first_step: int,
                     alpha: float = 1.0, img_alpha: float = 1.0, scalars_out: Optional[torch.Tensor] = None) -> None:
         """``len(lrs)`` consecutive fused steps with no Python in between (umlh_train_steps).
         ``*_table`` = (feats, labels[, feats_bf16]) device tensors or None; ``*_index_batches``
-        = one int64 device index vector per step, or (index slice, [batch sizes]) entries that each cover
-        several consecutive steps."""
+        = one int64 device index vector or ``IndexSpan`` per step, or (index slice or ``IndexSpan``, [batch sizes]) entries
+        that each cover several consecutive steps.  Unless a modality is one tensor, the ids of both modalities are written
+        into their block vectors by one ``umlh_index_block`` launch: no concatenation, no epoch permutation."""
         self.train_steps_prepared(self.prepare_steps(img_table, img_index_batches, txt_table, txt_index_batches, lrs),
                                   first_step, alpha=alpha, img_alpha=img_alpha, scalars_out=scalars_out)
 
@@ -304,8 +326,15 @@ class HeadEngine:
         n = len(lrs)
         si, keep_i = self._make_stream(img_table, img_index_batches, self.d_img, self.cfg.max_rows_img, n)
         st, keep_t = self._make_stream(txt_table, txt_index_batches, self.d_shared, self.cfg.max_rows_txt, n)
+        self._fill_index(si, keep_i, st, keep_t)
         lr_arr = (C.c_double * n)(*[float(x) for x in lrs])
         return (n, si, st, lr_arr, keep_i, keep_t)
+
+    @staticmethod
+    def prepared_index(prep):
+        """(image ids, text ids) of a prepared block: the concatenated int64 vectors its steps will read, with their per-step
+        offsets as numpy int32 arrays -- ((ids, offsets) or None per modality)."""
+        return tuple(None if k is None else (k[3], k[4]) for k in (prep[4], prep[5]))
 
     def train_steps_prepared(self, prep, first_step: int, alpha: float = 1.0, img_alpha: float = 1.0,
                              scalars_out: Optional[torch.Tensor] = None) -> None:
@@ -542,6 +571,7 @@ def train_steps_grouped(jobs, n_steps: int) -> None:
             raise UmlhError("train_steps_grouped: every head needs n_steps learning rates")
         si, ki = e._make_stream(job.get("img_table"), job.get("img_index_batches"), e.d_img, e.cfg.max_rows_img, n_steps)
         st, kt = e._make_stream(job.get("txt_table"), job.get("txt_index_batches"), e.d_shared, e.cfg.max_rows_txt, n_steps)
+        e._fill_index(si, ki, st, kt)
         lr_arr = (C.c_double * n_steps)(*[float(x) for x in lrs])
         so = job.get("scalars_out")
         items[j] = GroupItem(e.handle, C.pointer(si) if si is not None else None, C.pointer(st) if st is not None else None,
@@ -647,3 +677,103 @@ def random_permutation(n: int, seed: int, device) -> torch.Tensor:
     st = stream(out.device)
     check(lib.umlh_random_permutation(int(n), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(out), st), "umlh_random_permutation")
     return out
+
+
+class EpochOrder:
+    """The row order of one epoch of a loader over ``n`` rows, held by what defines it: the seed of a device permutation
+    (``random_permutation(n, seed)``, written out only when ``tensor()`` is asked for), a materialised device order, or the
+    identity of an unshuffled loader."""
+    __slots__ = ("kind", "n", "seed", "device", "_order")
+
+    def __init__(self, kind: int, n: int, device, seed: int = 0, order: Optional[torch.Tensor] = None):
+        if kind == _lib.SPAN_TABLE and order is None:
+            raise UmlhError("EpochOrder: a TABLE order needs its tensor")
+        self.kind, self.n, self.seed, self.device, self._order = kind, int(n), int(seed) & 0xFFFFFFFFFFFFFFFF, device, order
+
+    @classmethod
+    def permutation(cls, n, seed, device):
+        return cls(_lib.SPAN_FEISTEL, n, device, seed=seed)
+
+    @classmethod
+    def table(cls, order: torch.Tensor):
+        return cls(_lib.SPAN_TABLE, order.numel(), order.device, order=order)
+
+    @classmethod
+    def identity(cls, n, device):
+        return cls(_lib.SPAN_IOTA, n, device)
+
+    def tensor(self) -> torch.Tensor:
+        """The whole order as an int64 device tensor (materialised on first use, then kept)."""
+        if self._order is None:
+            self._order = (random_permutation(self.n, self.seed, self.device) if self.kind == _lib.SPAN_FEISTEL
+                           else torch.arange(self.n, dtype=torch.int64, device=self.device))
+        return self._order
+
+
+class IndexSpan:
+    """Positions ``start .. start+count-1`` of an ``EpochOrder``: what a loader hands to ``train_steps`` / ``prepare_steps``
+    in place of an index tensor.  ``numel()`` as a tensor's; ``tensor()`` materialises the ids for consumers that need them."""
+    __slots__ = ("epoch", "start", "count")
+
+    def __init__(self, epoch: EpochOrder, start: int, count: int):
+        if start < 0 or count < 0 or start + count > epoch.n:
+            raise UmlhError(f"IndexSpan: start={start} count={count} outside an order of {epoch.n} rows")
+        self.epoch, self.start, self.count = epoch, int(start), int(count)
+
+    def numel(self) -> int:
+        return self.count
+
+    def tensor(self) -> torch.Tensor:
+        return self.epoch.tensor()[self.start:self.start + self.count]
+
+
+def _span_descs(parts, device):
+    """(ctypes umlh_index_span_t array, keep-alive list) of IndexSpans and int64 index tensors (a tensor is a TABLE span over itself)."""
+    arr = (_lib.IndexSpanDesc * len(parts))()
+    keep = []
+    for k, p in enumerate(parts):
+        if isinstance(p, IndexSpan):
+            e = p.epoch
+            order = e.tensor() if e.kind == _lib.SPAN_TABLE else None
+            arr[k] = _lib.IndexSpanDesc(e.kind, 0, e.n, e.seed, order.data_ptr() if order is not None else None, p.start, p.count)
+        else:
+            order = p if p.is_contiguous() else p.contiguous()
+            arr[k] = _lib.IndexSpanDesc(_lib.SPAN_TABLE, 0, order.numel(), 0, order.data_ptr(), 0, order.numel())
+        if order is not None:
+            if order.dtype != torch.int64 or order.device.type != torch.device(device).type or not order.is_contiguous():
+                raise UmlhError("index vectors must be contiguous int64 tensors on the engine's device")
+            keep.append(order)
+    return arr, keep
+
+
+def _index_block_launch(lib, fill_img, fill_txt, device) -> None:
+    """One ``umlh_index_block`` call on the current stream; a fill is ((descriptor array, keep-alive), destination) or None."""
+    def side(fill):
+        if fill is None:
+            return None, 0, None
+        (arr, _), out = fill
+        return arr, len(arr), ptr(out)
+    ai, ni, oi = side(fill_img)
+    at, nt, ot = side(fill_txt)
+    check(lib.umlh_index_block(ai, ni, oi, at, nt, ot, stream(device)), "umlh_index_block")
+
+
+def index_block(img_parts, txt_parts, device, out=(None, None)):
+    """The concatenated int64 row ids of two lists of ``IndexSpan`` / index tensors (either may be None), written by ONE
+    ``umlh_index_block`` launch on the current stream: (image ids or None, text ids or None).  ``out``: contiguous int64
+    device tensors of exactly the total lengths to write into."""
+    lib = _lib.load_library()
+    device = torch.device(device)
+    fills = []
+    for parts, dst in zip((img_parts, txt_parts), out):
+        if parts is None:
+            fills.append(None)
+            continue
+        total = sum(int(p.numel()) for p in parts)
+        if dst is None:
+            dst = torch.empty(total, dtype=torch.int64, device=device)
+        elif dst.dtype != torch.int64 or not dst.is_contiguous() or dst.numel() != total or dst.device.type != device.type:
+            raise UmlhError(f"index_block: out must be a contiguous int64 device tensor of {total} ids")
+        fills.append((_span_descs(parts, device), dst))
+    _index_block_launch(lib, fills[0], fills[1], device)
+    return tuple(None if f is None else f[1] for f in fills)
