@@ -628,6 +628,56 @@ int  umlh_probe_fit(const float* x, int64_t n, int32_t d, int32_t ldx, const int
 int  umlh_probe_score(const float* x, int64_t n, int32_t d, int32_t ldx, const double* stats, const double* coef,
                       const int32_t* y, int64_t* correct, float* decision, void* stream);
 
+/* ---- multinomial (softmax) logistic probe: what LogisticRegression(max_iter=200) of the MultiBench probe factory
+ * (MultiBench/train.py:96-99) fits on labels with more than two classes, and the L-BFGS linear probe of cached features (DESIGN
+ * section 21).  Additive to ABI v11: umlh_version() is unchanged, callers detect the feature by these symbols.  Features are
+ * row-major fp32 [n, d] with row stride ldx >= d, labels int32 in [0, n_class), coefficients fp32 coef[n_class, ldc] with
+ * ldc >= d + 1 and the intercept in column d (columns past d are never touched).  The objective is sklearn's, as a sum:
+ *   f(W) = sum_i (logsumexp_c z_ic - z_{i,y_i}) + (1 / (2 c)) sum_{class, j < d} W_cj^2,   z_ic = W_c . [x_i, 1]
+ * (over-parameterised softmax, intercepts not penalised).  A row whose label lies outside [0, n_class) is never used as an
+ * address and contributes nothing.  stats (NULL or the 2d doubles of umlh_probe_column_stats) standardises x on load,
+ * (float)(((double)x - mean) * (1.0 / scale)); the coefficients then live in the standardised space.  Logits and the gradient
+ * R^T x come off the project's fp32 GEMM (logits computed from the coefficients as partial products over chunks of at most 128
+ * columns, added in double); the residuals R = softmax - onehot are fp32; the intercepts' gradient is the column sum of R in
+ * double with its mean over the classes (0 up to the rounding of R) taken out; the objective, the slab sums of the gradient,
+ * max|g| and every dot product of the solver are summed in double in a fixed order.  No float atomics: results are
+ * bitwise reproducible across calls and streams, and do not depend on the alignment of x (16-byte or 4-byte loads).  Every
+ * argument check happens before any HIP call and names the function and the argument; everything runs on `stream`; outputs are
+ * device memory; the host reads nothing back.
+ * Envelope: 2 <= n_class <= 4096, 1 <= d <= 2048, 2 <= n, n * n_class < 2^31, 0 <= max_iter <= 1000 (0: evaluation only, in
+ * the scratch size), 1 <= history <= 32, finite c > 0; anything else is UMLH_E_INVALID.  scratch must be 8-byte aligned. */
+
+/* Scratch bytes of umlh_softmax_probe_fit (max_iter >= 1) or umlh_softmax_probe_eval (max_iter = 0; history is ignored):
+ * O(n * n_class + n * d + history * n_class * d).  0 on invalid arguments. */
+uint64_t umlh_softmax_probe_scratch_bytes(int64_t n, int32_t d, int32_t n_class, int32_t max_iter, int32_t history);
+/* f, its gradient and max|gradient| at the given coefficients.  objective, max_grad: one double each (either may be NULL);
+ * grad: NULL or fp32 [n_class, ldg] with ldg >= d + 1 (columns 0 .. d of every row are written, nothing else). */
+int  umlh_softmax_probe_eval(const float* x, int64_t n, int32_t d, int32_t ldx, const int32_t* y, const double* stats,
+                             int32_t n_class, double c, const float* coef, int32_t ldc, double* objective, float* grad,
+                             int32_t ldg, double* max_grad, void* scratch, uint64_t scratch_bytes, void* stream);
+/* L-BFGS with `history` pairs from W = 0 (init = 0) or from what coef holds (init = 1), as a fixed train of launches for
+ * max_iter iterations; once the device-side stop test fires every later launch (the GEMMs included) returns at once.  The
+ * direction comes from the Gram matrix of [s_1.., y_1.., g] kept in double (two-loop recursion in coefficient space, H0 =
+ * s.y / y.y, a pair with s.y <= 1e-12 |s||y| skipped, the first direction scaled by 1 / sum|g|); the line search evaluates the
+ * objective at the step lengths 1, 1/2, .., 2^-11 (4 and 2 in front while there is no history) in one pass over Z and
+ * Z_p = [x, 1] p^T and takes the largest with f(t) <= f + 1e-4 t g.p.  The logits are carried in double and advanced by
+ * t Z_p; every decision that ends the fit is taken on logits recomputed from the coefficients, and record->objective and
+ * record->max_grad are those of that fresh evaluation: bit for bit what umlh_softmax_probe_eval returns at the returned
+ * coefficients.  record->converged: 1 = max|g| <= gtol; 2 = no step length gave sufficient decrease on fresh logits (the
+ * precision floor); 0 = budget spent, or the objective or the gradient is NaN.  objectives: NULL or max_iter + 1 doubles,
+ * [0] the objective at the start, [k] that value minus the decreases the line search accepted up to the k-th step
+ * (non-increasing; what re-basing on fresh logits adds is kept out, so [iterations] and record->objective differ by the fp32
+ * rounding of the logits), NaN beyond record->iterations.  Each fit in flight needs its own scratch, coef and record. */
+int  umlh_softmax_probe_fit(const float* x, int64_t n, int32_t d, int32_t ldx, const int32_t* y, const double* stats,
+                            int32_t n_class, double c, int32_t max_iter, int32_t history, double gtol, int32_t init, float* coef,
+                            int32_t ldc, umlh_probe_record_t* record, double* objectives, void* scratch, uint64_t scratch_bytes,
+                            void* stream);
+/* The scaler folded into raw-feature weights: w[c, j] = W_cj / sigma_j (fp32 [n_class, ldw], ldw >= d), bias[c] = W_cd -
+ * sum_j W_cj mu_j / sigma_j (fp32 [n_class]), formed in double and rounded once; stats = NULL: a plain copy.  umlh_eval_topk and
+ * umlh_eval_classwise then score raw features. */
+int  umlh_softmax_probe_fold(const float* coef, int32_t ldc, int32_t n_class, int32_t d, const double* stats, float* w, int32_t ldw,
+                             float* bias, void* stream);
+
 /* ---- k-nearest-neighbour probe: the 'knn' branch of the MultiBench make_classifier (MultiBench/train.py:99-100,
  * KNeighborsClassifier() = Euclidean metric, uniform weights).  Additive to ABI v11: umlh_version() is
  * unchanged, callers detect the feature by these symbols.  train is row-major fp32 [n_train, d] with row stride ld_train >= d,

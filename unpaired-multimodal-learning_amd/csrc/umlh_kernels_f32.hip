@@ -615,6 +615,7 @@ constexpr int GKIDS = 4096;   // reduction rows per split whose row ids fit the 
 
 template <int TA, int TB, int TM>
 __global__ __launch_bounds__(256) void gemm_f32(GemmArgs g) {
+    if (g.skip && *g.skip) return;
     constexpr int GBM = 64 * TM, GBN = 64 * TM, GLD = GBM + 4;
     // double-buffered K-chunks: one barrier per chunk, LDS writes of chunk c+1 overlap the MFMAs of chunk c
     __shared__ __attribute__((aligned(16))) float As2[2][KT * GLD];
@@ -1760,7 +1761,7 @@ int umlh_f32_launch_fwd(const FwdArgs* a, int ctw, int wc, int grid, hipStream_t
 
 static bool dw_f32_applies(const GemmArgs* g, int ta, int tb) {
     static const bool off = env_int("UMLH_F32_DW", 1) == 0;   // timing comparisons
-    if (off || ta != 0 || tb != 1 || g->a_rows || g->epi.on) return false;
+    if (off || ta != 0 || tb != 1 || g->a_rows || g->epi.on || g->skip) return false;
     if ((long long)g->M * g->N < 8LL * 128 * 128 || g->N < 4 || g->N % 4 || g->lda < 4) return false;
     if (g->k_chunk > DWKIDS) return false;
     if (g->lda % 4 || g->ldb % 4 || (reinterpret_cast<uintptr_t>(g->A) & 15) || (reinterpret_cast<uintptr_t>(g->B) & 15)) return false;

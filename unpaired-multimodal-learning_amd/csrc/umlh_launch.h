@@ -157,6 +157,16 @@ int umlh_probe_launch_fit(const float* x, long long n, int d, int ldx, const int
                           hipStream_t st);
 int umlh_probe_launch_score(const float* x, long long n, int d, int ldx, const double* stats, const double* coef, const int* y,
                             long long* correct, float* decision, hipStream_t st);
+// ---- umlh_kernels_softmax_probe.hip: multinomial logistic probe ----
+unsigned long long umlh_softmax_probe_bytes(long long n, int d, int n_class, int fit, int history);     // fit = 0: the evaluation
+int umlh_softmax_probe_launch_eval(const float* x, long long n, int d, int ldx, const int* y, const double* stats, int n_class, double c,
+                                   float* coef, int ldc, double* objective, float* grad, int ldg, double* max_grad, void* scratch,
+                                   hipStream_t st);
+int umlh_softmax_probe_launch_fit(const float* x, long long n, int d, int ldx, const int* y, const double* stats, int n_class, double c,
+                                  int max_iter, int history, double gtol, int init, float* coef, int ldc, umlh_probe_record_t* rec,
+                                  double* objectives, void* scratch, hipStream_t st);
+int umlh_softmax_probe_launch_fold(const float* coef, int ldc, int n_class, int d, const double* stats, float* w, int ldw, float* bias,
+                                   hipStream_t st);
 // ---- umlh_kernels_knn.hip: k-nearest-neighbour probe ----
 unsigned long long umlh_knn_bytes(long long nt, long long nq, int k, int splits);
 int umlh_knn_launch_search(const float* train, long long nt, int ldt, const float* query, long long nq, int ldq, int d, int k,

@@ -577,6 +577,73 @@ int umlh_probe_score(const float* x, int64_t n, int32_t d, int32_t ldx, const do
     return UMLH_OK;
 }
 
+// ---- multinomial logistic probe (kernels: umlh_kernels_softmax_probe.hip) ----
+static const int SOFTMAX_MAX_D = 2048, SOFTMAX_MAX_CLASSES = 4096, SOFTMAX_MAX_HISTORY = 32;
+static bool softmax_shape_ok(int64_t n, int32_t d, int32_t n_class) {
+    return n >= 2 && d >= 1 && d <= SOFTMAX_MAX_D && n_class >= 2 && n_class <= SOFTMAX_MAX_CLASSES && n < ROWS_END && n * n_class < ROWS_END;
+}
+
+// the checks the evaluation and the fit share; 0 = fine
+static int check_softmax(const char* who, const float* x, int64_t n, int32_t d, int32_t ldx, const int32_t* y, int32_t n_class, double c,
+                         const float* coef, int32_t ldc, const void* scratch) {
+    if (!x || !y || !coef || !scratch) return fail(UMLH_E_INVALID, "%s: null pointer (x, y, coef and scratch are required)", who);
+    if (!softmax_shape_ok(n, d, n_class))
+        return fail(UMLH_E_INVALID, "%s: n=%lld d=%d n_class=%d (need 2 <= n, 1 <= d <= 2048, 2 <= n_class <= 4096, n * n_class < 2^31)", who,
+                    (long long)n, d, n_class);
+    if (ldx < d) return fail(UMLH_E_INVALID, "%s: ldx=%d < d=%d", who, ldx, d);
+    if (ldc < d + 1) return fail(UMLH_E_INVALID, "%s: ldc=%d < d + 1 = %d", who, ldc, d + 1);
+    if (!(c > 0.0) || !(c < 1e300)) return fail(UMLH_E_INVALID, "%s: c=%g (need a finite c > 0)", who, c);
+    return UMLH_OK;
+}
+
+uint64_t umlh_softmax_probe_scratch_bytes(int64_t n, int32_t d, int32_t n_class, int32_t max_iter, int32_t history) {
+    if (!softmax_shape_ok(n, d, n_class) || max_iter < 0 || max_iter > PROBE_MAX_ITER) return 0;
+    if (max_iter == 0) return umlh_softmax_probe_bytes(n, d, n_class, 0, 1);
+    if (history < 1 || history > SOFTMAX_MAX_HISTORY) return 0;
+    return umlh_softmax_probe_bytes(n, d, n_class, 1, history);
+}
+
+int umlh_softmax_probe_eval(const float* x, int64_t n, int32_t d, int32_t ldx, const int32_t* y, const double* stats, int32_t n_class,
+                            double c, const float* coef, int32_t ldc, double* objective, float* grad, int32_t ldg, double* max_grad,
+                            void* scratch, uint64_t scratch_bytes, void* stream) {
+    const char* who = "umlh_softmax_probe_eval";
+    RC(check_softmax(who, x, n, d, ldx, y, n_class, c, coef, ldc, scratch));
+    if (!objective && !grad && !max_grad) return fail(UMLH_E_INVALID, "%s: nothing to compute (objective, grad and max_grad are all NULL)", who);
+    if (grad && ldg < d + 1) return fail(UMLH_E_INVALID, "%s: ldg=%d < d + 1 = %d", who, ldg, d + 1);
+    RC(check_scratch(who, scratch, scratch_bytes, umlh_softmax_probe_bytes(n, d, n_class, 0, 1), 8));
+    HIPCHK(umlh_softmax_probe_launch_eval(x, n, d, ldx, y, stats, n_class, c, const_cast<float*>(coef), ldc, objective, grad, ldg, max_grad,
+                                          scratch, (hipStream_t)stream), who);
+    return UMLH_OK;
+}
+
+int umlh_softmax_probe_fit(const float* x, int64_t n, int32_t d, int32_t ldx, const int32_t* y, const double* stats, int32_t n_class,
+                           double c, int32_t max_iter, int32_t history, double gtol, int32_t init, float* coef, int32_t ldc,
+                           umlh_probe_record_t* record, double* objectives, void* scratch, uint64_t scratch_bytes, void* stream) {
+    const char* who = "umlh_softmax_probe_fit";
+    RC(check_softmax(who, x, n, d, ldx, y, n_class, c, coef, ldc, scratch));
+    if (!record) return fail(UMLH_E_INVALID, "%s: null pointer (record is required)", who);
+    if (max_iter < 1 || max_iter > PROBE_MAX_ITER) return fail(UMLH_E_INVALID, "%s: max_iter=%d outside 1..%d", who, max_iter, PROBE_MAX_ITER);
+    if (history < 1 || history > SOFTMAX_MAX_HISTORY) return fail(UMLH_E_INVALID, "%s: history=%d outside 1..%d", who, history, SOFTMAX_MAX_HISTORY);
+    if (!(gtol >= 0.0)) return fail(UMLH_E_INVALID, "%s: gtol=%g (need gtol >= 0)", who, gtol);
+    if (init != 0 && init != 1) return fail(UMLH_E_INVALID, "%s: init=%d (0 = start from zero, 1 = start from coef)", who, init);
+    RC(check_scratch(who, scratch, scratch_bytes, umlh_softmax_probe_bytes(n, d, n_class, 1, history), 8));
+    HIPCHK(umlh_softmax_probe_launch_fit(x, n, d, ldx, y, stats, n_class, c, max_iter, history, gtol, init, coef, ldc, record, objectives,
+                                         scratch, (hipStream_t)stream), who);
+    return UMLH_OK;
+}
+
+int umlh_softmax_probe_fold(const float* coef, int32_t ldc, int32_t n_class, int32_t d, const double* stats, float* w, int32_t ldw,
+                            float* bias, void* stream) {
+    const char* who = "umlh_softmax_probe_fold";
+    if (!coef || !w || !bias) return fail(UMLH_E_INVALID, "%s: null pointer (coef, w and bias are required)", who);
+    if (n_class < 1 || n_class > SOFTMAX_MAX_CLASSES || d < 1 || d > SOFTMAX_MAX_D)
+        return fail(UMLH_E_INVALID, "%s: n_class=%d d=%d (need 1 <= n_class <= 4096, 1 <= d <= 2048)", who, n_class, d);
+    if (ldc < d + 1) return fail(UMLH_E_INVALID, "%s: ldc=%d < d + 1 = %d", who, ldc, d + 1);
+    if (ldw < d) return fail(UMLH_E_INVALID, "%s: ldw=%d < d=%d", who, ldw, d);
+    HIPCHK(umlh_softmax_probe_launch_fold(coef, ldc, n_class, d, stats, w, ldw, bias, (hipStream_t)stream), who);
+    return UMLH_OK;
+}
+
 // ---- k-nearest-neighbour probe (kernels: umlh_kernels_knn.hip) ----
 static bool knn_shape_ok(int64_t n_train, int64_t n_query, int32_t k) {
     return k >= 1 && k <= LIST_MAX_K && n_train >= k && n_train < ROWS_END && n_query >= 1 && n_query < ROWS_END;

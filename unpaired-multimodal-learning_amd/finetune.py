@@ -823,6 +823,53 @@ def setup_feature_run(img_train, img_val, img_test, text_ds, hparams, *, num_cla
             "iter": result["iter"], "train_scalars": result["train_scalars"]}
 
 
+def linear_probe(img_train, img_val, img_test, *, num_classes, C_grid=(0.01, 0.1, 1.0, 10.0, 100.0), max_iter=200, standardize=False,
+                 classwise=False, device="cuda:0", tables=None, warm_start=True):
+    """The linear-probe baseline of few-shot papers on pre-extracted features: an L2-regularised multinomial logistic
+    regression fitted to its optimum by L-BFGS (``umlh.SoftmaxProbe``), C chosen on the validation split.
+
+    img_* are the (features [N, d], labels [N]) pairs of ``setup_feature_run`` (labels 0 .. num_classes - 1, every class present
+    in the train split); ``tables`` (from ``feature_tables``) are used instead where given.  The grid is walked in ascending C,
+    each fit started from the previous one's coefficients (``warm_start=False``: every fit from zero); val and test are scored
+    for every C and nothing is read back until all fits are enqueued.  The best C has the highest val accuracy, ties to the
+    smaller C.  Returns {'best_C', 'val_acc', 'test_acc', 'per_C': [{'C', 'val_acc', 'test_acc'}], 'records': [probe.record()],
+    'probe'} and, with ``classwise=True``, 'classwise': ``validate_classwise``'s kind of report (``umlh.report.class_report``)
+    of the best probe on the test split."""
+    if num_classes < 2:
+        raise ValueError(f"linear_probe: num_classes={num_classes} < 2")
+    grid = sorted(float(c) for c in C_grid)
+    if not grid or grid[0] <= 0:
+        raise ValueError(f"linear_probe: C_grid={C_grid} must hold positive values")
+    dev = torch.device(device)
+    if tables is not None:
+        split = {t: (tables[t].features, tables[t].labels) for t in ("train", "val", "test")}
+    else:
+        split = {"train": img_train, "val": img_val, "test": img_test}
+    with torch.cuda.device(dev):
+        split = {t: (f.to(device=dev, dtype=torch.float32), torch.as_tensor(l).to(device=dev, dtype=torch.int64)) for t, (f, l) in split.items()}
+        probes, counts = [], []
+        for c in grid:
+            pr = umlh.SoftmaxProbe(C=c, max_iter=max_iter, standardize=standardize)
+            pr.fit(*split["train"], coef_init=probes[-1] if (warm_start and probes) else None, check_classes=False, n_classes=num_classes)
+            probes.append(pr)
+            counts += [pr.correct(*split["val"]), pr.correct(*split["test"])]
+        got = torch.stack(counts).cpu().tolist()
+        nv, nt = split["val"][0].shape[0], split["test"][0].shape[0]
+        per_c = [{"C": c, "val_acc": got[2 * i] / nv, "test_acc": got[2 * i + 1] / nt} for i, c in enumerate(grid)]
+        best = max(range(len(grid)), key=lambda i: (per_c[i]["val_acc"], -i))
+        out = {"best_C": grid[best], "val_acc": per_c[best]["val_acc"], "test_acc": per_c[best]["test_acc"], "per_C": per_c,
+               "records": [p.record() for p in probes], "probe": probes[best]}
+        if classwise:
+            from umlh.report import class_report, topk_classes
+            pr = probes[best]
+            cls, _ = topk_classes(split["test"][0], pr.raw_weight_, pr.raw_bias_, k=min(5, num_classes))
+            rep = {k: v.cpu() for k, v in class_report(cls, split["test"][1], num_classes).items()}
+            rep["top1_acc"] = float(rep["hit1"].sum()) / nt
+            rep["topk_acc"] = float(rep["hitk"].sum()) / nt
+            out["classwise"] = rep
+    return out
+
+
 # --------------------------------------------------------------------------------------------- #
 # sweep / main over feature files  (reference: finetune.py:58-77 naming, :323-448 setup/sweep,
 # :451-510 main).  Same flag names on `args`; wandb / Tee logging and raw-image loading are out

@@ -50,9 +50,9 @@ def _label_fn(ds_name):
     return _LABELS[ds_name]
 
 
-def _labels01(batches, ds_name):
-    """0/1 int64 labels of one split on the host (train.py:41-47)."""
-    fn = _label_fn(ds_name)
+def _labels01(batches, ds_name, label_fn=None):
+    """Integer labels of one split on the host: 0/1 by the dataset's rule (train.py:41-47), or what ``label_fn`` makes of them."""
+    fn = label_fn if label_fn is not None else _label_fn(ds_name)
     lab = np.concatenate([np.asarray(b[3].detach().cpu().numpy() if isinstance(b[3], torch.Tensor) else b[3]) for b in batches])
     return np.asarray(fn(lab)).reshape(-1).astype(int)
 
@@ -65,6 +65,25 @@ def _two_classes(y, what):
         raise ValueError(f"{what}: the probes are binary, got labels {np.unique(y)[:5]}")
 
 
+def _class_labels(lab, label_fn):
+    """The label arrays of the three splits as the probes take them, and the number of classes.  Without ``label_fn`` the
+    reference's binary labels, checked as before.  With one: two classes 0/1 stay as they are; anything else is remapped to
+    the index in unique(train labels), as sklearn does (-1 for a value the train split does not hold: it counts as wrong)."""
+    if label_fn is None:
+        _two_classes(lab["train"], "train labels")
+        return lab, 2
+    classes = np.unique(lab["train"])
+    if len(classes) < 2:
+        raise ValueError(f"This solver needs samples of at least 2 classes in the data, but the data contains only one class: {lab['train'][0]!r} (train labels)")
+    if len(classes) == 2 and classes[0] == 0 and classes[1] == 1:
+        return lab, 2
+    out = {}
+    for t, y in lab.items():
+        idx = np.minimum(np.searchsorted(classes, y), len(classes) - 1)
+        out[t] = np.where(classes[idx] == y, idx, -1).astype(int)
+    return out, len(classes)
+
+
 def _kind(ds_name):
     return "liblinear" if ds_name == "mosi" else "lbfgs"         # train.py:97-99
 
@@ -72,14 +91,18 @@ def _kind(ds_name):
 class _Probes:
     """The fits and scores of one evaluate call: everything is enqueued first, ``read`` brings all counts back at once."""
 
-    def __init__(self, ds_name, dev):
-        self.kind, self.dev = _kind(ds_name), dev
+    def __init__(self, ds_name, dev, n_classes=2):
+        self.kind, self.dev, self.n_classes = _kind(ds_name), dev, n_classes
         self.counts, self.names, self.rows, self.clfs = [], [], [], []
 
-    def fit(self, X, y, classifier_type="logistic"):
-        """make_classifier(classifier_type, ds_name) of the reference (train.py:96-102), fitted."""
-        from umlh.probe import KNeighborsProbe, LogisticProbe
-        if classifier_type == "logistic":
+    def fit(self, X, y, classifier_type="logistic", binary=False):
+        """make_classifier(classifier_type, ds_name) of the reference (train.py:96-102), fitted.  More than two label classes
+        make the logistic probe a ``SoftmaxProbe`` (what sklearn's LogisticRegression is then), unless ``binary`` says that
+        this fit's own labels are 0/1 (the modality-separation probe)."""
+        from umlh.probe import KNeighborsProbe, LogisticProbe, logistic_probe
+        if classifier_type == "logistic" and self.n_classes > 2 and not binary:
+            self.clfs.append(logistic_probe(self.kind, self.n_classes).fit(X, y, check_classes=False, n_classes=self.n_classes))
+        elif classifier_type == "logistic":
             self.clfs.append(LogisticProbe(self.kind).fit(X, y, check_classes=False))
         elif classifier_type == "knn":
             self.clfs.append(KNeighborsProbe().fit(X, y))
@@ -108,12 +131,12 @@ def _fit_three(pr, emb, lab, z, tag="", classifier_type="logistic"):
             pr.score(f"{t}/score_{name}{tag}", clf, emb[t][:, cols], yev[t])
 
 
-def evaluate_raw_data(config, ds_name="mosi", device=None, return_probes=False):
+def evaluate_raw_data(config, ds_name="mosi", device=None, return_probes=False, label_fn=None):
     """The raw-feature baselines (train.py:31-91): each modality's plain mean over time, probes on x, y and [x, y].
-    ``return_probes`` adds the pooled [N, dx + dy] device matrices per split and the three fitted probes."""
+    ``return_probes`` adds the pooled [N, dx + dy] device matrices per split and the three fitted probes.  ``label_fn``: see
+    ``evaluate``."""
     import umlh
-    lab = {t: _labels01(config[t], ds_name) for t in _TYPES}
-    _two_classes(lab["train"], "train labels")
+    lab, n_classes = _class_labels({t: _labels01(config[t], ds_name, label_fn) for t in _TYPES}, label_fn)
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     with torch.cuda.device(dev):
         emb, dims = {}, None
@@ -128,7 +151,7 @@ def evaluate_raw_data(config, ds_name="mosi", device=None, return_probes=False):
                 umlh.masked_mean(x.float(), None, out=emb[t][off:off + bs, :dims[0]])
                 umlh.masked_mean(y.float(), None, out=emb[t][off:off + bs, dims[0]:])
                 off += bs
-        pr = _Probes(ds_name, dev)
+        pr = _Probes(ds_name, dev, n_classes)
         _fit_three(pr, emb, lab, dims, tag="_raw")
         got = pr.read()
     results = {k: got[k] for k in ("val/score_x_raw", "val/score_y_raw", "test/score_x_raw", "test/score_y_raw", "test/score_xy_raw",
@@ -137,7 +160,7 @@ def evaluate_raw_data(config, ds_name="mosi", device=None, return_probes=False):
 
 
 @torch.no_grad()
-def evaluate(model, config, ds_name="mosi", device="cuda:0", return_embeddings=False, classifier_types=("logistic",)):
+def evaluate(model, config, ds_name="mosi", device="cuda:0", return_embeddings=False, classifier_types=("logistic",), label_fn=None):
     """The reference's evaluate (train.py:93-240) with its batch layout and result keys.  The model forward is this
     project's eval-mode mirror; pooling, scaler statistics, fits and scores are HIP kernels, the embeddings never leave
     the device, and all six fits (three modality-separation probes, x, y, xy) are enqueued before anything is read back.
@@ -148,17 +171,21 @@ def evaluate(model, config, ds_name="mosi", device="cuda:0", return_embeddings=F
     ``classifier_types`` is the list the reference's loop iterates (train.py:165): 'logistic' or 'knn'
     (``umlh.KNeighborsProbe()``, train.py:99-100); a later type overwrites the score keys of an earlier one, as
     ``results.update`` inside that loop does, and any other name raises the reference's ValueError.  The modality-separation
-    probe is always logistic (train.py:151)."""
+    probe is always logistic (train.py:151).
+    ``label_fn`` (default None: the dataset's binary rule, nothing changes): a callable that maps a batch's label array to
+    integer labels, for a dataset name the reference raises on ('mimic' and its 6 classes) or a caller's own task.  With more
+    than two classes in the train labels the x / y / xy logistic probes are ``umlh.SoftmaxProbe``s; the modality-separation
+    probe stays binary."""
     import umlh
-    _label_fn(ds_name)
+    if label_fn is None:
+        _label_fn(ds_name)
     classifier_types = tuple(classifier_types)
     for ct in classifier_types:
         if ct not in ("logistic", "knn"):
             raise ValueError(f"Unsupported classifier type: {ct}")
     dev = torch.device(device)
     model.eval()
-    lab = {t: _labels01(config[t], ds_name) for t in _TYPES}
-    _two_classes(lab["train"], "train labels")
+    lab, n_classes = _class_labels({t: _labels01(config[t], ds_name, label_fn) for t in _TYPES}, label_fn)
     emb, loss, z = {}, {}, None
     with torch.cuda.device(dev):
         for t in _TYPES:
@@ -180,12 +207,12 @@ def evaluate(model, config, ds_name="mosi", device="cuda:0", return_embeddings=F
                 off += bs
             loss[t] = (torch.stack([o["loss_x"].reshape(()) for o in outs]).double().mean(),
                        torch.stack([o["loss_y"].reshape(()) for o in outs]).double().mean())
-        pr = _Probes(ds_name, dev)
+        pr = _Probes(ds_name, dev, n_classes)
         for t in _TYPES:                                            # which modality a pooled embedding came from (train.py:146-151)
             n = emb[t].shape[0]
             both = torch.cat([emb[t][:, :z[0]], emb[t][:, z[0]:]], dim=0)
             which = torch.cat([torch.zeros(n, dtype=torch.int32, device=dev), torch.ones(n, dtype=torch.int32, device=dev)])
-            pr.score(f"sep/{t}", pr.fit(both, which), both, which)
+            pr.score(f"sep/{t}", pr.fit(both, which, binary=True), both, which)
         for ct in classifier_types:
             _fit_three(pr, emb, lab, z, classifier_type=ct)
         got = pr.read()
@@ -362,7 +389,7 @@ def train(model, train_mode, train_loader_1, train_loader_2, optimizer, modaliti
           debug=False, args=None, device="cuda:0", step_diagnostics=False, rollout_spectra=False, on_step=None, effective_rank=False):
     """Returns {'loss_x': [...], 'loss_y': [...], 'loss': [...]} with one entry per batch pair
     (device tensors are read back once at the end).  With a non-empty ``eval_config`` ({'train', 'val', 'test': batch
-    lists, 'freq': int, optionally 'classifier_types': the probes of ``evaluate``, default ('logistic',)}) it evaluates as the reference does (train.py:350,440-451,519-523): ``evaluate_raw_data`` once,
+    lists, 'freq': int, optionally 'classifier_types': the probes of ``evaluate``, default ('logistic',), and 'label_fn': ``evaluate``'s label rule, default None}) it evaluates as the reference does (train.py:350,440-451,519-523): ``evaluate_raw_data`` once,
     ``evaluate`` whenever i_batch % freq == 0 and once more after the last epoch, the model back in train mode after
     each; the dict then also holds 'raw' and 'eval' = [(epoch, i_batch, results), ...], where results are what the
     reference logs (evaluate's keys without the *_private / *_complete ones, plus the raw baselines) and the closing
@@ -415,7 +442,7 @@ def train(model, train_mode, train_loader_1, train_loader_2, optimizer, modaliti
     raw_results, evals = None, []
     classifier_types = tuple(eval_config.get("classifier_types", ("logistic",)))
     if eval_config:
-        raw_results = evaluate_raw_data(eval_config, ds_name=ds_name, device=device)
+        raw_results = evaluate_raw_data(eval_config, ds_name=ds_name, device=device, label_fn=eval_config.get("label_fn"))
 
     def logged(score):
         out = {k: v for k, v in score.items() if not ("private" in k or "complete" in k)}
@@ -449,7 +476,7 @@ def train(model, train_mode, train_loader_1, train_loader_2, optimizer, modaliti
             if on_step is not None:
                 on_step(epoch, i_batch, out, loss)
             if eval_config and i_batch % eval_config["freq"] == 0:
-                evals.append((epoch, i_batch, logged(evaluate(model, eval_config, ds_name, device=device, classifier_types=classifier_types))))
+                evals.append((epoch, i_batch, logged(evaluate(model, eval_config, ds_name, device=device, classifier_types=classifier_types, label_fn=eval_config.get("label_fn")))))
                 if capture is not None:
                     values, zx, zy = capture.measure(model)
                     evals[-1][2].update(values)
@@ -459,7 +486,7 @@ def train(model, train_mode, train_loader_1, train_loader_2, optimizer, modaliti
                         spectra.append((epoch, i_batch, _capture_spectra(model, capture)))
                 model.train()
         if eval_config and epoch == num_epoch - 1:
-            evals.append((epoch, None, logged(evaluate(model, eval_config, ds_name, device=device, classifier_types=classifier_types))))
+            evals.append((epoch, None, logged(evaluate(model, eval_config, ds_name, device=device, classifier_types=classifier_types, label_fn=eval_config.get("label_fn")))))
             model.train()
     stack = lambda v: torch.stack([t.reshape(()) for t in v]).cpu().tolist() if v else []
     res = {"loss_x": stack(rec_x), "loss_y": stack(rec_y), "loss": stack(rec_l)}

@@ -14,7 +14,7 @@ from .head_engine import (EpochOrder, HeadEngine, IndexSpan, RowBatch, column_su
 from .dp import DataParallelStepper  # noqa: F401,E402
 from . import align  # noqa: F401,E402
 from . import probe  # noqa: F401,E402
-from .probe import KNeighborsProbe, LogisticProbe, masked_mean  # noqa: F401,E402
+from .probe import KNeighborsProbe, LogisticProbe, SoftmaxProbe, logistic_probe, masked_mean  # noqa: F401,E402
 from . import spectral  # noqa: F401,E402
 from .spectral import effective_rank, effective_rank_seq, principal_subspace, svdvals  # noqa: F401,E402
 from .align import svcca, svcca_terms  # noqa: F401,E402

@@ -20,7 +20,7 @@ PREC_IDS = {"fp32": 0, "bf16": 1}
 N_CORE_SCALARS = 8
 N_SCALARS = 12
 
-SOURCES = ["umlh_p2p.hip", "umlh_kernels_f32.hip", "umlh_kernels_bf16.hip", "umlh_kernels_micro.hip", "umlh_kernels_seq.hip", "umlh_kernels_enc.hip", "umlh_kernels_align.hip", "umlh_kernels_align_ext.hip", "umlh_kernels_probe.hip", "umlh_kernels_knn.hip", "umlh_kernels_spectral.hip", "umlh_kernels_capture.hip", "umlh_kernels_stepstats.hip", "umlh_kernels_rollout.hip", "umlh_kernels_classstats.hip", "umlh_kernels_evalreport.hip", "umlh_kernels_outlier.hip", "umlh_api.cpp", "umlh_ops.cpp", "umlh_encoder.cpp"]
+SOURCES = ["umlh_p2p.hip", "umlh_kernels_f32.hip", "umlh_kernels_bf16.hip", "umlh_kernels_micro.hip", "umlh_kernels_seq.hip", "umlh_kernels_enc.hip", "umlh_kernels_align.hip", "umlh_kernels_align_ext.hip", "umlh_kernels_probe.hip", "umlh_kernels_softmax_probe.hip", "umlh_kernels_knn.hip", "umlh_kernels_spectral.hip", "umlh_kernels_capture.hip", "umlh_kernels_stepstats.hip", "umlh_kernels_rollout.hip", "umlh_kernels_classstats.hip", "umlh_kernels_evalreport.hip", "umlh_kernels_outlier.hip", "umlh_api.cpp", "umlh_ops.cpp", "umlh_encoder.cpp"]
 
 
 class UmlhError(RuntimeError):
@@ -190,6 +190,11 @@ def _prototypes() -> dict:
         "umlh_probe_column_stats": (rc, (vp, i64, i32, i32, vp, vp, u64, vp)),
         "umlh_probe_fit": (rc, (vp, i64, i32, i32, vp, vp, i32, f64, i32, f64, vp, vp, vp, vp, u64, vp)),
         "umlh_probe_score": (rc, (vp, i64, i32, i32, vp, vp, vp, vp, vp, vp)),
+        # multinomial logistic probe
+        "umlh_softmax_probe_scratch_bytes": (u64, (i64, i32, i32, i32, i32)),
+        "umlh_softmax_probe_eval": (rc, (vp, i64, i32, i32, vp, vp, i32, f64, vp, i32, vp, vp, i32, vp, vp, u64, vp)),
+        "umlh_softmax_probe_fit": (rc, (vp, i64, i32, i32, vp, vp, i32, f64, i32, i32, f64, i32, vp, i32, vp, vp, vp, u64, vp)),
+        "umlh_softmax_probe_fold": (rc, (vp, i32, i32, i32, vp, vp, i32, vp, vp)),
         # k-nearest-neighbour probe
         "umlh_knn_scratch_bytes": (u64, (i64, i64, i32, i32, i32)),
         "umlh_knn_search": (rc, (vp, i64, i32, vp, i64, i32, i32, i32, i32, vp, vp, vp, u64, vp)),
