@@ -172,7 +172,7 @@ __global__ __launch_bounds__(256) void cka_final(const double* __restrict__ tile
 
 }  // namespace
 
-// ---- plans and launchers (validation is the caller's: umlh_api.cpp) ----
+// ---- plans and launchers (validation is the caller's: umlh_ops.cpp) ----
 extern "C" {
 
 int umlh_align_knn_splits(long long n, int splits) { return topk_splits(n, n, splits); }
@@ -197,10 +197,10 @@ static CkaPlan cka_plan(long long n, int da, int db, int splits) {
     if (r > CK_MAX_RCHUNKS) r = CK_MAX_RCHUNKS;
     p.rchunks = (int)(r < 1 ? 1 : (r > nb ? nb : r));
     p.sum_chunks = umlh_align_cka_sum_chunks(n);
-    p.colsum = 0;
-    p.cross = align_up((long long)p.sum_chunks * (da + db) * 8);
-    p.tile_sq = p.cross + align_up((long long)p.tiles * p.rchunks * 1024 * 8);
-    p.total = p.tile_sq + align_up((long long)p.tiles * 8);
+    ScratchLayout lay;
+    p.colsum = lay.take((long long)p.sum_chunks * (da + db) * 8);
+    p.cross = lay.take((long long)p.tiles * p.rchunks * 1024 * 8);
+    p.tile_sq = lay.take((long long)p.tiles * 8), p.total = lay.end;
     return p;
 }
 
@@ -221,7 +221,7 @@ int umlh_align_launch_knn(const float* x, long long n, int d, int ldx, int topk,
 
 int umlh_align_launch_mutual(const int* ka, const int* kb, long long n, int topk, double* out, void* scratch, hipStream_t st) {
     const int nblocks = (int)((n + 255) / 256);
-    long long* partial = (long long*)scratch;
+    long long* partial = at<long long>(scratch, 0);
     hipLaunchKernelGGL(mutual_count, dim3((unsigned)nblocks), dim3(256), 0, st, ka, kb, (int)n, topk, partial);
     hipLaunchKernelGGL(mutual_final, dim3(1), dim3(256), 0, st, partial, nblocks, (int)n, topk, out);
     return (int)hipGetLastError();
@@ -247,9 +247,9 @@ int umlh_align_launch_cka_products(const float* a, int lda, int da, const float*
     CkaArgs g;
     g.a = a; g.b = b; g.lda = lda; g.ldb = ldb; g.da = da; g.db = db; g.ta = p.ta; g.tb = p.tb;
     g.n = (int)n; g.sum_chunks = p.sum_chunks; g.rchunks = p.rchunks;
-    g.colsum = (const double*)((char*)scratch + p.colsum);
-    g.cross = (double*)((char*)scratch + p.cross);
-    g.tile_sq = (double*)((char*)scratch + p.tile_sq);
+    g.colsum = at<double>(scratch, p.colsum);
+    g.cross = at<double>(scratch, p.cross);
+    g.tile_sq = at<double>(scratch, p.tile_sq);
     hipLaunchKernelGGL(cka_colsum, dim3((unsigned)((da + db + 63) / 64), (unsigned)p.sum_chunks), dim3(256), 0, st, a, lda, da, b, ldb,
                        db, (int)n, p.sum_chunks, (double*)g.colsum);
     hipLaunchKernelGGL(cka_cross, dim3((unsigned)p.tiles, (unsigned)p.rchunks), dim3(256), 0, st, g);
@@ -262,7 +262,7 @@ int umlh_align_launch_cka(const float* a, int lda, int da, const float* b, int l
     const CkaPlan p = cka_plan(n, da, db, splits);
     const int e = umlh_align_launch_cka_products(a, lda, da, b, ldb, db, n, splits, scratch, st);
     if (e) return e;
-    hipLaunchKernelGGL(cka_final, dim3(1), dim3(256), 0, st, (const double*)((char*)scratch + p.tile_sq), p.ta, p.tb, out4);
+    hipLaunchKernelGGL(cka_final, dim3(1), dim3(256), 0, st, (const double*)at<double>(scratch, p.tile_sq), p.ta, p.tb, out4);
     return (int)hipGetLastError();
 }
 

@@ -456,15 +456,14 @@ UnbiasedPlan unbiased_plan(long long n, int da, int db, int splits) {
     p.chunks = umlh_align_cka_sum_chunks(n);
     p.base = (long long)umlh_align_cka_bytes(n, da, db, splits);
     p.nblocks = (n + 63) / 64;
-    p.mean = p.base;
-    p.part2 = p.mean + align_up((long long)(up4(da) + up4(db)) * 4);
-    p.csum = p.part2 + align_up(p.chunks * dt * 8);
-    p.part = p.csum + align_up(dt * 8);
-    p.total = p.part + align_up(p.nblocks * NSUM * 8);
+    ScratchLayout lay(p.base);                       // behind the CKA layout, whose products the launcher runs first
+    p.mean = lay.take((long long)(up4(da) + up4(db)) * 4);
+    p.part2 = lay.take(p.chunks * dt * 8);
+    p.csum = lay.take(dt * 8), p.part = lay.take(p.nblocks * NSUM * 8), p.total = lay.end;
     return p;
 }
 
-struct RbfPlan { int chunks, splits, ntiles; long long strips, mean, norms, pair, rowpart, part, nblocks, total; };
+struct RbfPlan { int chunks, splits, ntiles; long long strips, colsum, mean, norms, pair, rowpart, part, nblocks, total; };
 
 RbfPlan rbf_plan(long long n, int da, int db, int splits) {
     RbfPlan p;
@@ -474,18 +473,27 @@ RbfPlan rbf_plan(long long n, int da, int db, int splits) {
     p.ntiles = (int)((n + TK_COLS - 1) / TK_COLS);
     p.strips = (n + TK_ROWS - 1) / TK_ROWS;
     p.nblocks = (n + 255) / 256;
-    p.mean = align_up(p.chunks * dt * 8);
-    p.norms = p.mean + align_up((long long)(up4(da) + up4(db)) * 4);
-    p.pair = p.norms + align_up(2 * n * 4);
-    p.rowpart = p.pair + align_up(3 * p.splits * p.strips * 8);
-    p.part = p.rowpart + align_up(p.splits * p.strips * TK_ROWS * 2 * 8);
-    p.total = p.part + align_up(p.nblocks * NSUM * 8);
+    ScratchLayout lay;
+    p.colsum = lay.take(p.chunks * dt * 8), p.mean = lay.take((long long)(up4(da) + up4(db)) * 4), p.norms = lay.take(2 * n * 4);
+    p.pair = lay.take(3 * p.splits * p.strips * 8);
+    p.rowpart = lay.take(p.splits * p.strips * TK_ROWS * 2 * 8);
+    p.part = lay.take(p.nblocks * NSUM * 8), p.total = lay.end;
+    return p;
+}
+
+struct CknnaPlan { long long nblocks, rsum, part, total; };
+
+CknnaPlan cknna_plan(long long n) {
+    CknnaPlan p;
+    ScratchLayout lay;
+    p.nblocks = (n + 255) / 256;
+    p.rsum = lay.take(n * 4 * 8), p.part = lay.take(p.nblocks * NSUM * 8), p.total = lay.end;
     return p;
 }
 
 }  // namespace
 
-// ---- plans and launchers (validation is the caller's: umlh_api.cpp) ----
+// ---- plans and launchers (validation is the caller's: umlh_ops.cpp) ----
 extern "C" {
 
 unsigned long long umlh_align_ext_cka_unbiased_bytes(long long n, int da, int db, int splits) {
@@ -496,9 +504,7 @@ unsigned long long umlh_align_ext_rbf_bytes(long long n, int da, int db, int spl
     return (unsigned long long)rbf_plan(n, da, db, splits).total;
 }
 
-unsigned long long umlh_align_ext_cknna_bytes(long long n) {
-    return (unsigned long long)(align_up(n * 4 * 8) + align_up((n + 255) / 256 * NSUM * 8));
-}
+unsigned long long umlh_align_ext_cknna_bytes(long long n) { return (unsigned long long)cknna_plan(n).total; }
 
 unsigned long long umlh_align_ext_list_bytes(long long n) { return (unsigned long long)align_up((n + 63) / 64 * 3 * 8); }
 
@@ -529,11 +535,11 @@ int umlh_align_ext_launch_cka_unbiased(const float* a, int lda, int da, const fl
 int umlh_align_ext_launch_rbf(const float* a, int lda, int da, const float* b, int ldb, int db, long long n, double sigma,
                               int unbiased, int splits, double* out4, void* scratch, hipStream_t st) {
     const RbfPlan p = rbf_plan(n, da, db, splits);
-    int e = umlh_align_launch_colsum(a, lda, da, b, ldb, db, n, at<double>(scratch, 0), st);
+    int e = umlh_align_launch_colsum(a, lda, da, b, ldb, db, n, at<double>(scratch, p.colsum), st);
     if (e) return e;
     float* mean = at<float>(scratch, p.mean);
-    hipLaunchKernelGGL(ext_means, dim3((unsigned)((up4(da) + up4(db) + 255) / 256)), dim3(256), 0, st, at<double>(scratch, 0), p.chunks,
-                       da, db, (int)n, mean);
+    hipLaunchKernelGGL(ext_means, dim3((unsigned)((up4(da) + up4(db) + 255) / 256)), dim3(256), 0, st, at<double>(scratch, p.colsum),
+                       p.chunks, da, db, (int)n, mean);
     RowArgs r;
     r.a = a; r.b = b; r.lda = lda; r.ldb = ldb; r.da = da; r.db = db; r.n = n; r.mean = mean;
     r.csum = nullptr; r.norms = at<float>(scratch, p.norms); r.part = nullptr;
@@ -556,12 +562,11 @@ int umlh_align_ext_launch_rbf(const float* a, int lda, int da, const float* b, i
 
 int umlh_align_ext_launch_cknna(const int* ka, const float* sa, const int* kb, const float* sb, long long n, int topk, double* out4,
                                 void* scratch, hipStream_t st) {
-    const long long nblocks = (n + 255) / 256;
-    double* rsum = at<double>(scratch, 0);
-    double* part = at<double>(scratch, align_up(n * 4 * 8));
-    hipLaunchKernelGGL(cknna_rowsum, dim3((unsigned)nblocks), dim3(256), 0, st, ka, sa, kb, sb, (int)n, topk, rsum);
-    hipLaunchKernelGGL(cknna_rows, dim3((unsigned)nblocks), dim3(256), 0, st, ka, sa, kb, sb, (int)n, topk, rsum, part);
-    hipLaunchKernelGGL(ext_final, dim3(1), dim3(256), 0, st, part, 0LL, 0LL, 0LL, part, nblocks, (double)n, 1, out4);
+    const CknnaPlan p = cknna_plan(n);
+    double *rsum = at<double>(scratch, p.rsum), *part = at<double>(scratch, p.part);
+    hipLaunchKernelGGL(cknna_rowsum, dim3((unsigned)p.nblocks), dim3(256), 0, st, ka, sa, kb, sb, (int)n, topk, rsum);
+    hipLaunchKernelGGL(cknna_rows, dim3((unsigned)p.nblocks), dim3(256), 0, st, ka, sa, kb, sb, (int)n, topk, rsum, part);
+    hipLaunchKernelGGL(ext_final, dim3(1), dim3(256), 0, st, part, 0LL, 0LL, 0LL, part, p.nblocks, (double)n, 1, out4);
     return (int)hipGetLastError();
 }
 

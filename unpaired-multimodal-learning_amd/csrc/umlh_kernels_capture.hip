@@ -122,7 +122,7 @@ inline bool cap_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p
 }  // namespace
 
 extern "C" unsigned long long umlh_capture_cosine_bytes(long long n) {
-    return ((unsigned long long)cap_cos_groups(n) * sizeof(double) + 255) / 256 * 256;
+    return (unsigned long long)align_up((long long)cap_cos_groups(n) * 8);
 }
 
 extern "C" int umlh_capture_launch_compact(const float* z, int B, int T, int d, long long ldb, long long ldt, const long long* lengths,
@@ -143,7 +143,7 @@ extern "C" int umlh_capture_launch_compact(const float* z, int B, int T, int d, 
 extern "C" int umlh_capture_launch_cosine(const float* a, long long lda, const float* b, long long ldb, long long n, int d, double eps,
                                           double* out2, float* rows, void* scratch, hipStream_t st) {
     const int groups = cap_cos_groups(n);
-    double* partial = reinterpret_cast<double*>(scratch);
+    double* partial = at<double>(scratch, 0);
     hipLaunchKernelGGL(cap_cos_rows, dim3((unsigned)groups), dim3(64 * CAP_COS_WAVES), 0, st, a, lda, b, ldb, n, d, eps, rows, partial);
     hipLaunchKernelGGL(cap_cos_final, dim3(1), dim3(64), 0, st, (const double*)partial, groups, n, out2);
     return (int)hipGetLastError();

@@ -39,8 +39,6 @@ constexpr int CS_WAVES = 4;
 constexpr int CS_COLS = 1024;             // columns per pass of the column sums: 16 fp64 accumulators per lane
 constexpr int CS_SCAN = 1024;             // threads of the single-workgroup kernels
 
-inline unsigned long long cs_align(unsigned long long b) { return (b + 255) / 256 * 256; }
-
 // inclusive scan over the workgroup (CS_SCAN threads) in LDS; MAX: running maximum, else running sum
 template <bool MAX>
 __device__ __forceinline__ long long cs_block_scan(long long v, long long* sh) {
@@ -439,60 +437,70 @@ inline long long ci_blocks(long long n) { return (n + CS_CHUNK - 1) / CS_CHUNK; 
 inline long long cs_slots(long long n) { return 2 * n / CS_CHUNK; }     // sum over classes of more than one chunk of their chunks
 inline bool cs_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+struct ClassIndexPlan { int blocks; long long cells, counts, totals, total; };     // the block-by-class count table, the class totals
+ClassIndexPlan classindex_plan(long long n, int n_class) {
+    ClassIndexPlan p;
+    ScratchLayout lay;
+    p.blocks = (int)ci_blocks(n), p.cells = (long long)p.blocks * n_class;
+    p.counts = lay.take(p.cells * 4), p.totals = lay.take((long long)n_class * 4), p.total = lay.end;
+    return p;
+}
+
+struct ClassStatsPlan { long long slots, mono, slot0, ccount, pcnt, pdist, psum, total; };
+ClassStatsPlan classstats_plan(long long n, int d, int n_class) {
+    ClassStatsPlan p;
+    ScratchLayout lay;
+    p.slots = cs_slots(n);
+    p.mono = lay.take(((long long)n_class + 1) * 4), p.slot0 = lay.take(((long long)n_class + 1) * 4);
+    p.ccount = lay.take((long long)n_class * 4), p.pcnt = lay.take((p.slots + 1) * 4);
+    p.pdist = lay.take((p.slots + 1) * 8), p.psum = lay.take((p.slots * d + 1) * 8), p.total = lay.end;
+    return p;
+}
+
 }  // namespace
 
 extern "C" unsigned long long umlh_classindex_bytes(long long n, int n_class) {
-    const unsigned long long cells = (unsigned long long)ci_blocks(n) * (unsigned long long)n_class;
-    if (cells > (1ull << 28)) return 0;                    // the block-by-class count table: at most 1 GiB
-    return cs_align(cells * sizeof(int)) + cs_align((unsigned long long)n_class * sizeof(int));
+    const ClassIndexPlan p = classindex_plan(n, n_class);
+    if (p.cells > (1LL << 28)) return 0;                   // the block-by-class count table: at most 1 GiB
+    return (unsigned long long)p.total;
 }
 
 extern "C" int umlh_classindex_launch(const long long* labels, long long n, int n_class, int* order, long long* offsets, void* scratch,
                                       hipStream_t st) {
-    const int blocks = (int)ci_blocks(n);
-    const unsigned long long cells = (unsigned long long)blocks * (unsigned long long)n_class;
-    int* counts = reinterpret_cast<int*>(scratch);
-    int* total = reinterpret_cast<int*>(reinterpret_cast<char*>(scratch) + cs_align(cells * sizeof(int)));
-    if (hipError_t e = hipMemsetAsync(counts, 0, cells * sizeof(int), st)) return (int)e;
-    hipLaunchKernelGGL(ci_count, dim3((unsigned)blocks), dim3(CS_CHUNK), 0, st, labels, n, n_class, counts);
-    hipLaunchKernelGGL(ci_scan, dim3((unsigned)((n_class + 255) / 256)), dim3(256), 0, st, counts, blocks, n_class, total);
+    const ClassIndexPlan p = classindex_plan(n, n_class);
+    int *counts = at<int>(scratch, p.counts), *total = at<int>(scratch, p.totals);
+    if (hipError_t e = hipMemsetAsync(counts, 0, (size_t)p.cells * sizeof(int), st)) return (int)e;
+    hipLaunchKernelGGL(ci_count, dim3((unsigned)p.blocks), dim3(CS_CHUNK), 0, st, labels, n, n_class, counts);
+    hipLaunchKernelGGL(ci_scan, dim3((unsigned)((n_class + 255) / 256)), dim3(256), 0, st, counts, p.blocks, n_class, total);
     hipLaunchKernelGGL(ci_offsets, dim3(1), dim3(CS_SCAN), 0, st, (const int*)total, n_class, offsets);
-    hipLaunchKernelGGL(ci_scatter, dim3((unsigned)blocks), dim3(CS_CHUNK), 0, st, labels, n, n_class, (const int*)counts,
+    hipLaunchKernelGGL(ci_scatter, dim3((unsigned)p.blocks), dim3(CS_CHUNK), 0, st, labels, n, n_class, (const int*)counts,
                        (const long long*)offsets, order);
     return (int)hipGetLastError();
 }
 
 extern "C" unsigned long long umlh_classstats_bytes(long long n, int d, int n_class) {
-    const unsigned long long slots = (unsigned long long)cs_slots(n);
-    return 2 * cs_align(((unsigned long long)n_class + 1) * sizeof(int)) + cs_align((unsigned long long)n_class * sizeof(int)) +
-           cs_align((slots + 1) * sizeof(int)) + cs_align((slots + 1) * sizeof(double)) +
-           cs_align((slots * (unsigned long long)d + 1) * sizeof(double));
+    return (unsigned long long)classstats_plan(n, d, n_class).total;
 }
 
 extern "C" int umlh_classstats_launch(const float* feats, long long ld, long long n, int d, const int* order, const long long* offsets,
                                       int n_class, float* means, long long ld_means, double* dist, double* out2, void* scratch,
                                       hipStream_t st) {
-    const unsigned long long slots = (unsigned long long)cs_slots(n);
-    char* p = reinterpret_cast<char*>(scratch);
+    const ClassStatsPlan p = classstats_plan(n, d, n_class);
     CsArgs a;
     a.feats = feats, a.ld = ld, a.n = n, a.d = d, a.n_class = n_class, a.order = order, a.offsets = offsets;
-    a.means = means, a.ld_means = ld_means, a.dist = dist, a.out2 = out2, a.slots = (int)slots;
-    a.mono = reinterpret_cast<int*>(p), p += cs_align(((unsigned long long)n_class + 1) * sizeof(int));
-    a.slot0 = reinterpret_cast<int*>(p), p += cs_align(((unsigned long long)n_class + 1) * sizeof(int));
-    a.ccount = reinterpret_cast<int*>(p), p += cs_align((unsigned long long)n_class * sizeof(int));
-    a.pcnt = reinterpret_cast<int*>(p), p += cs_align((slots + 1) * sizeof(int));
-    a.pdist = reinterpret_cast<double*>(p), p += cs_align((slots + 1) * sizeof(double));
-    a.psum = reinterpret_cast<double*>(p);
+    a.means = means, a.ld_means = ld_means, a.dist = dist, a.out2 = out2, a.slots = (int)p.slots;
+    a.mono = at<int>(scratch, p.mono), a.slot0 = at<int>(scratch, p.slot0), a.ccount = at<int>(scratch, p.ccount);
+    a.pcnt = at<int>(scratch, p.pcnt), a.pdist = at<double>(scratch, p.pdist), a.psum = at<double>(scratch, p.psum);
     const bool vec = d % 4 == 0 && ld % 4 == 0 && ld_means % 4 == 0 && cs_aligned16(feats) && cs_aligned16(means);
     const dim3 wg(64 * CS_WAVES);
     hipLaunchKernelGGL(cs_plan, dim3(1), dim3(CS_SCAN), 0, st, offsets, n, n_class, a.mono, a.slot0);
-    const dim3 pass1((unsigned)((unsigned long long)n_class + slots));
+    const dim3 pass1((unsigned)(n_class + p.slots));
     if (vec) hipLaunchKernelGGL(cs_pass1<true>, pass1, wg, 0, st, a);
     else hipLaunchKernelGGL(cs_pass1<false>, pass1, wg, 0, st, a);
-    if (slots > 0) {
-        hipLaunchKernelGGL(cs_big_mean, dim3((unsigned)slots), dim3(256), 0, st, a);
-        if (vec) hipLaunchKernelGGL(cs_big_dist<true>, dim3((unsigned)slots), wg, 0, st, a);
-        else hipLaunchKernelGGL(cs_big_dist<false>, dim3((unsigned)slots), wg, 0, st, a);
+    if (p.slots > 0) {
+        hipLaunchKernelGGL(cs_big_mean, dim3((unsigned)p.slots), dim3(256), 0, st, a);
+        if (vec) hipLaunchKernelGGL(cs_big_dist<true>, dim3((unsigned)p.slots), wg, 0, st, a);
+        else hipLaunchKernelGGL(cs_big_dist<false>, dim3((unsigned)p.slots), wg, 0, st, a);
     }
     hipLaunchKernelGGL(cs_final, dim3(1), dim3(CS_SCAN), 0, st, a);
     return (int)hipGetLastError();

@@ -123,7 +123,7 @@ __global__ __launch_bounds__(256) void ev_classwise(const int* __restrict__ cls,
 
 }  // namespace
 
-// ---- plan and launchers (validation is the caller's: umlh_api.cpp) ----
+// ---- plan and launchers (validation is the caller's: umlh_ops.cpp) ----
 extern "C" {
 
 unsigned long long umlh_evalreport_bytes(long long n, long long C, int k, int splits) {

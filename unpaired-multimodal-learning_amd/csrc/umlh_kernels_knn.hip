@@ -119,7 +119,7 @@ TopkPlan kp_plan(long long nt, long long nq, int k, int splits) { return topk_pl
 
 }  // namespace
 
-// ---- plan and launchers (validation is the caller's: umlh_api.cpp) ----
+// ---- plan and launchers (validation is the caller's: umlh_ops.cpp) ----
 extern "C" {
 
 unsigned long long umlh_knn_bytes(long long nt, long long nq, int k, int splits) {

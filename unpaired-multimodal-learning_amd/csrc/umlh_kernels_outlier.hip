@@ -350,15 +350,21 @@ constexpr int ACC_MAX_BLOCKS = 4096, SELECT_MAX_BLOCKS = 65536, KTH_MAX_BLOCKS =
 inline unsigned capped(long long want, int cap) { return (unsigned)(want < 1 ? 1 : want > cap ? cap : want); }
 inline long long quant_parts(long long n) { return (n + QUANT_CHUNK - 1) / QUANT_CHUNK; }
 inline int acc_blocks(long long n) { return (int)capped((n + 3) / 4, ACC_MAX_BLOCKS); }
-constexpr long long KTH_HIST_BYTES = 4 * 256 * 8;
+struct KthPlan { long long hist, state, total; };          // the four passes' 256-bin histograms, then the state they hand on
+KthPlan kth_plan() {
+    KthPlan p;
+    ScratchLayout lay;
+    p.hist = lay.take(4 * 256 * 8), p.state = lay.take(sizeof(KthState)), p.total = lay.end;
+    return p;
+}
 
 }  // namespace
 
-// ---- plan and launchers (validation is the caller's: umlh_api.cpp) ----
+// ---- plan and launchers (validation is the caller's: umlh_ops.cpp) ----
 extern "C" {
 
 unsigned long long umlh_outlier_quantile_bytes(long long n) { return (unsigned long long)align_up(quant_parts(n) * 8); }
-unsigned long long umlh_outlier_kth_bytes(void) { return (unsigned long long)align_up(KTH_HIST_BYTES + (long long)sizeof(KthState)); }
+unsigned long long umlh_outlier_kth_bytes(void) { return (unsigned long long)kth_plan().total; }
 unsigned long long umlh_outlier_accuracy_bytes(long long n) { return (unsigned long long)align_up((long long)acc_blocks(n) * 8); }
 
 int umlh_outlier_launch_quantile(const float* x, long long n, int d, long long ld, int lo, int hi, double frac, float* lo_val,
@@ -381,11 +387,12 @@ int umlh_outlier_launch_quantile(const float* x, long long n, int d, long long l
 
 int umlh_outlier_launch_kth(const float* x, long long n, long long d, long long ld, long long k, float* out, void* scratch,
                             hipStream_t st) {
-    hipError_t e = hipMemsetAsync(scratch, 0, (size_t)umlh_outlier_kth_bytes(), st);
+    const KthPlan p = kth_plan();
+    hipError_t e = hipMemsetAsync(scratch, 0, (size_t)p.total, st);
     if (e != hipSuccess) return (int)e;
     const long long total = n * d;
-    unsigned long long* gh = at<unsigned long long>(scratch, 0);
-    KthState* ks = at<KthState>(scratch, KTH_HIST_BYTES);
+    unsigned long long* gh = at<unsigned long long>(scratch, p.hist);
+    KthState* ks = at<KthState>(scratch, p.state);
     const long long nvec = ld == d && (reinterpret_cast<uintptr_t>(x) & 15) == 0 ? total / 4 : 0;
     const dim3 grid(capped((total + 4 * KTH_THREADS - 1) / (4 * KTH_THREADS), KTH_MAX_BLOCKS)), block(KTH_THREADS);
     hipLaunchKernelGGL(kth_pass<0>, grid, block, 0, st, x, total, d, ld, nvec, (unsigned long long)k, gh, ks, out);

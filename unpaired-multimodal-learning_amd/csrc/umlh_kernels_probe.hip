@@ -488,12 +488,11 @@ __global__ __launch_bounds__(256) void pb_update(ProbeArgs g, int k) {
     for (int c = tid; c < g.D; c += 256) g.w[c] += t * g.delta[c];
 }
 
-inline unsigned long long up256(unsigned long long x) { return (x + 255) / 256 * 256; }
-
 struct ProbePlan {
     int eblocks, gchunks, nt, tiles, rchunks;
-    unsigned long long st, delta, tstep, z, u, r, s, gpart, lspart, cross, H, total;
+    long long st, delta, tstep, z, u, r, s, gpart, lspart, cross, H, total;
 };
+static_assert(sizeof(ProbeState) <= 256, "the state region is one 256-byte unit");
 
 ProbePlan probe_plan(long long n, int d, int max_iter) {
     ProbePlan p;
@@ -504,29 +503,25 @@ ProbePlan probe_plan(long long n, int d, int max_iter) {
     p.tiles = tri_tiles(p.nt);
     const long long nb = (n + 31) / 32;
     p.rchunks = (int)std::max<long long>(1, std::min<long long>(PB_TARGET_WG / p.tiles, (nb + 3) / 4));
-    unsigned long long o = 0;
-    p.st = o; o += 256;
-    p.delta = o; o += up256(8ull * D);
-    p.tstep = o; o += up256(8ull * (max_iter + 1));
-    p.z = o; o += up256(8ull * n);
-    p.u = o; o += up256(4ull * n);
-    p.r = o; o += up256(4ull * n);
-    p.s = o; o += up256(4ull * n);
-    p.gpart = o; o += up256(8ull * p.gchunks * D);
-    p.lspart = o; o += up256(8ull * p.eblocks * PB_LS);
-    p.cross = o; o += up256(8ull * 1024 * p.tiles * p.rchunks);
-    p.H = o; o += up256(8ull * D * D);
-    p.total = o;
+    ScratchLayout lay;
+    p.st = lay.take(sizeof(ProbeState));
+    p.delta = lay.take(8LL * D), p.tstep = lay.take(8LL * (max_iter + 1));
+    p.z = lay.take(8LL * n);
+    p.u = lay.take(4LL * n), p.r = lay.take(4LL * n), p.s = lay.take(4LL * n);
+    p.gpart = lay.take(8LL * p.gchunks * D), p.lspart = lay.take(8LL * p.eblocks * PB_LS);
+    p.cross = lay.take(8LL * 1024 * p.tiles * p.rchunks);
+    p.H = lay.take(8LL * D * D);
+    p.total = lay.end;
     return p;
 }
 
 }  // namespace
 
-// ---- plans and launchers (validation is the caller's: umlh_api.cpp) ----
+// ---- plans and launchers (validation is the caller's: umlh_ops.cpp) ----
 extern "C" {
 
-unsigned long long umlh_probe_fit_bytes(long long n, int d, int max_iter) { return probe_plan(n, d, max_iter).total; }
-unsigned long long umlh_probe_stats_bytes(int d) { return up256(8ull * PB_STAT_CHUNKS * d); }
+unsigned long long umlh_probe_fit_bytes(long long n, int d, int max_iter) { return (unsigned long long)probe_plan(n, d, max_iter).total; }
+unsigned long long umlh_probe_stats_bytes(int d) { return (unsigned long long)align_up(8LL * PB_STAT_CHUNKS * d); }
 
 int umlh_probe_launch_masked_mean(const float* z, int B, int T, int Z, long long ldb, long long ldt, const long long* lengths,
                                   float* out, int ldo, hipStream_t st) {
@@ -537,7 +532,7 @@ int umlh_probe_launch_masked_mean(const float* z, int B, int T, int Z, long long
 
 // pass 0: stats[0, d) = column means; pass 1: stats[d, 2d) = column scales about those means
 static void launch_stats_pass(int pass, const float* x, long long n, int d, int ldx, double* stats, void* scratch, hipStream_t st) {
-    double* partial = (double*)scratch;
+    double* partial = at<double>(scratch, 0);
     const int chunks = (int)std::min<long long>(PB_STAT_CHUNKS, n);
     const dim3 grid((unsigned)((d + 63) / 64), (unsigned)chunks);
     hipLaunchKernelGGL(pb_colsum, grid, dim3(256), 0, st, x, n, d, ldx, chunks, pass ? (const double*)stats : nullptr, partial);
@@ -559,23 +554,16 @@ int umlh_probe_launch_fit(const float* x, long long n, int d, int ldx, const int
                           int max_iter, double gtol, double* coef, umlh_probe_record_t* rec, double* objectives, void* scratch,
                           hipStream_t st) {
     const ProbePlan p = probe_plan(n, d, max_iter);
-    char* base = (char*)scratch;
     ProbeArgs g;
     g.x = x; g.y = y; g.stats = stats; g.n = n; g.d = d; g.ldx = ldx; g.D = d + 1;
     g.kind = kind; g.max_iter = max_iter; g.inv_c = 1.0 / c; g.gtol = gtol;
     g.eblocks = p.eblocks; g.gchunks = p.gchunks; g.nt = p.nt; g.tiles = p.tiles; g.rchunks = p.rchunks;
-    g.st = (ProbeState*)(base + p.st);
+    g.st = at<ProbeState>(scratch, p.st);
     g.w = coef;
-    g.delta = (double*)(base + p.delta);
-    g.tstep = (double*)(base + p.tstep);
-    g.z = (double*)(base + p.z);
-    g.u = (float*)(base + p.u);
-    g.r = (float*)(base + p.r);
-    g.s = (float*)(base + p.s);
-    g.gpart = (double*)(base + p.gpart);
-    g.lspart = (double*)(base + p.lspart);
-    g.cross = (double*)(base + p.cross);
-    g.H = (double*)(base + p.H);
+    g.delta = at<double>(scratch, p.delta); g.tstep = at<double>(scratch, p.tstep); g.z = at<double>(scratch, p.z);
+    g.u = at<float>(scratch, p.u); g.r = at<float>(scratch, p.r); g.s = at<float>(scratch, p.s);
+    g.gpart = at<double>(scratch, p.gpart); g.lspart = at<double>(scratch, p.lspart);
+    g.cross = at<double>(scratch, p.cross); g.H = at<double>(scratch, p.H);
     g.rec = rec;
     g.objectives = objectives;
     const dim3 eb((unsigned)p.eblocks), b256(256);

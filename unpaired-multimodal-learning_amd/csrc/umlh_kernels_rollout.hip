@@ -507,13 +507,13 @@ extern "C" long long umlh_spectrum_partials(int B, int T, int d) {
 
 extern "C" unsigned long long umlh_spectrum_bytes(int B, int T, int d) {
     const long long p = umlh_spectrum_partials(B, T, d);
-    return ((unsigned long long)(p > 0 ? p : 1) * (unsigned long long)(T / 2 + 1) * sizeof(double) + 255) / 256 * 256;
+    return (unsigned long long)align_up((p > 0 ? p : 1) * (T / 2 + 1) * 8);
 }
 
 extern "C" int umlh_spectrum_launch(const float* x, long long ldb, long long ldt, int B, int T, int d, double* out, void* scratch,
                                     hipStream_t st) {
     if (int e = raise_lds_limit<&spec_partial>((int)sp_lds_bytes(UMLH_SPECTRUM_MAX_T))) return e;
-    double* partial = reinterpret_cast<double*>(scratch);
+    double* partial = at<double>(scratch, 0);
     const long long p = umlh_spectrum_partials(B, T, d);
     const int col_chunks = (d + SP_COLS - 1) / SP_COLS, K = T / 2 + 1;
     hipLaunchKernelGGL(spec_partial, dim3((unsigned)p), dim3(SP_THREADS), sp_lds_bytes(T), st, x, ldb, ldt, B, T, d, col_chunks, partial);

@@ -586,7 +586,7 @@ __global__ __launch_bounds__(256) void sp_fold(const float* __restrict__ coef, i
 struct SpPlan {
     int Dp, Kp, eblocks, rblocks, ns, chunk, cchunks, zchunk;
     long long L, slab_stride;
-    unsigned long long st, xt, z32, r, zd, g, slabs, losspart, gpart, rpart, rtot, gold, p, S, Y, dotpart, combpart, lspart, total;
+    long long st, xt, z32, r, zd, g, slabs, losspart, gpart, rpart, rtot, gold, p, S, Y, dotpart, combpart, lspart, total;
 };
 
 SpPlan sp_plan(long long n, int d, int K, int fit, int history) {
@@ -608,30 +608,24 @@ SpPlan sp_plan(long long n, int d, int K, int fit, int history) {
     const int zparts = (D + 127) / 128;
     p.zchunk = ((D + zparts - 1) / zparts + 3) / 4 * 4;
     const int nb = 2 * history + 1;
-    unsigned long long o = 0;
-    auto take = [&](unsigned long long bytes) { const unsigned long long at = o; o += (unsigned long long)align_up((long long)bytes); return at; };
-    p.st = take(sizeof(SpState));
-    p.xt = take(4ull * n * p.Dp);
-    p.z32 = take(4ull * n * p.Kp);
-    p.r = take(4ull * n * p.Kp);
-    p.zd = take(8ull * n * K);
-    p.g = take(4ull * p.L);
-    p.slabs = take(4ull * p.ns * p.L);
-    p.losspart = take(8ull * p.rblocks);
-    p.gpart = take(8ull * 3 * p.eblocks);
-    p.rpart = take(8ull * p.cchunks * K);
-    p.rtot = take(8ull * K);
+    ScratchLayout lay;
+    p.st = lay.take(sizeof(SpState));
+    p.xt = lay.take(4LL * n * p.Dp);
+    p.z32 = lay.take(4LL * n * p.Kp), p.r = lay.take(4LL * n * p.Kp);
+    p.zd = lay.take(8LL * n * K);
+    p.g = lay.take(4LL * p.L);
+    p.slabs = lay.take(4LL * p.ns * p.L);
+    p.losspart = lay.take(8LL * p.rblocks), p.gpart = lay.take(8LL * 3 * p.eblocks);
+    p.rpart = lay.take(8LL * p.cchunks * K), p.rtot = lay.take(8LL * K);
     p.gold = p.p = p.S = p.Y = p.dotpart = p.combpart = p.lspart = 0;
     if (fit) {
-        p.gold = take(4ull * p.L);
-        p.p = take(4ull * p.L);
-        p.S = take(4ull * history * p.L);
-        p.Y = take(4ull * history * p.L);
-        p.dotpart = take(8ull * 3 * nb * p.eblocks);
-        p.combpart = take(8ull * 2 * p.eblocks);
-        p.lspart = take(8ull * SP_LS * p.rblocks);
+        p.gold = lay.take(4LL * p.L), p.p = lay.take(4LL * p.L);
+        p.S = lay.take(4LL * history * p.L), p.Y = lay.take(4LL * history * p.L);
+        p.dotpart = lay.take(8LL * 3 * nb * p.eblocks);
+        p.combpart = lay.take(8LL * 2 * p.eblocks);
+        p.lspart = lay.take(8LL * SP_LS * p.rblocks);
     }
-    p.total = o;
+    p.total = lay.end;
     return p;
 }
 
@@ -692,7 +686,7 @@ int sp_launch_eval(const SpArgs& a, const SpPlan& p, const int* skip_z, const in
 extern "C" {
 
 unsigned long long umlh_softmax_probe_bytes(long long n, int d, int n_class, int fit, int history) {
-    return sp_plan(n, d, n_class, fit, history).total;
+    return (unsigned long long)sp_plan(n, d, n_class, fit, history).total;
 }
 
 int umlh_softmax_probe_launch_eval(const float* x, long long n, int d, int ldx, const int* y, const double* stats, int n_class, double c,

@@ -633,22 +633,28 @@ int umlh_spectral_chunks(int batch, long long n) {
     return (int)(c < 1 ? 1 : c);
 }
 
-unsigned long long umlh_spectral_bytes(int batch, long long n, int d) {
+struct SpectralPlan { int chunks; long long slabs, g, total; };
+
+static SpectralPlan spectral_plan(int batch, long long n, int d) {
     const long long dd = (long long)d * d * 8;
-    return (unsigned long long)(align_up(dd * batch * umlh_spectral_chunks(batch, n)) + align_up(dd * batch));
+    SpectralPlan p;
+    ScratchLayout lay;
+    p.chunks = umlh_spectral_chunks(batch, n);
+    p.slabs = lay.take(dd * batch * p.chunks), p.g = lay.take(dd * batch), p.total = lay.end;
+    return p;
 }
+
+unsigned long long umlh_spectral_bytes(int batch, long long n, int d) { return (unsigned long long)spectral_plan(batch, n, d).total; }
 
 // Dense: period = rows = n, batch matrices `sm` apart.  Sequence block: batch = 1, rows = n_outer * period.
 int umlh_spectral_launch(const float* a, int batch, long long rows, int period, long long sm, long long so, long long si,
                          const long long* lengths, int drop_last, int d, double eps, double* erank, double* rows_out, double* sv,
                          int sv_ld, void* scratch, hipStream_t st) {
-    const int chunks = umlh_spectral_chunks(batch, rows);
-    const long long dd = (long long)d * d * 8;
-    double* slabs = at<double>(scratch, 0);
-    double* g = at<double>(scratch, align_up(dd * batch * chunks));
+    const SpectralPlan p = spectral_plan(batch, rows, d);
+    double *slabs = at<double>(scratch, p.slabs), *g = at<double>(scratch, p.g);
     RowMap map{a, sm, so, si, lengths, (unsigned)rows, (unsigned)period, drop_last};
-    hipLaunchKernelGGL(spectral_gram, dim3(tri_tiles((d + G64_TILE - 1) / G64_TILE), chunks, batch), dim3(256), 0, st, map, d, chunks, slabs);
-    hipLaunchKernelGGL(spectral_reduce, dim3((d * d + 255) / 256, batch), dim3(256), 0, st, slabs, d, chunks, g);
+    hipLaunchKernelGGL(spectral_gram, dim3(tri_tiles((d + G64_TILE - 1) / G64_TILE), p.chunks, batch), dim3(256), 0, st, map, d, p.chunks, slabs);
+    hipLaunchKernelGGL(spectral_reduce, dim3((d * d + 255) / 256, batch), dim3(256), 0, st, slabs, d, p.chunks, g);
     EigOut out{erank, 1, rows_out, sv, sv_ld, eps};
     hipLaunchKernelGGL(spectral_eig, dim3(batch), dim3(SP_EIG_THREADS), 0, st, g, d, map, (int)(rows / period), out);
     return (int)hipGetLastError();
@@ -668,26 +674,18 @@ SubspacePlan subspace_plan(long long n, int da, int db, int q) {
     SubspacePlan p;
     const long long dm = da > db ? da : db;
     p.chunks = umlh_spectral_chunks(1, n);
-    long long off = 0;
-    auto take = [&off](long long bytes) { const long long at = off; off += align_up(bytes); return at; };
-    p.stats_a = take(8LL * da);
-    p.stats_b = take(8LL * db);
-    p.stat_scr = take((long long)umlh_probe_stats_bytes((int)dm));
-    p.slabs = take(8LL * p.chunks * dm * dm);
-    p.gc_a = take(8LL * da * da);
-    p.gc_b = take(8LL * db * db);
-    p.g_a = take(8LL * da * da);
-    p.g_b = take(8LL * db * db);
-    p.c = take(8LL * da * db);
-    p.work_a = take(8LL * 4 * da * SS_MAX_Q);
-    p.work_b = take(8LL * 4 * db * SS_MAX_Q);
-    p.ev = take(db ? 16LL * q : 0);
-    p.vec_a = take(db ? 8LL * da * q : 0);
-    p.vec_b = take(8LL * db * q);
-    p.w = take(db ? 8LL * da * q : 0);
-    p.m = take(db ? 8LL * q * q : 0);
-    p.s = take(db ? 8LL * q * q : 0);
-    p.total = off;
+    ScratchLayout lay;
+    p.stats_a = lay.take(8LL * da), p.stats_b = lay.take(8LL * db);
+    p.stat_scr = lay.take((long long)umlh_probe_stats_bytes((int)dm)), p.slabs = lay.take(8LL * p.chunks * dm * dm);
+    p.gc_a = lay.take(8LL * da * da), p.gc_b = lay.take(8LL * db * db);
+    p.g_a = lay.take(8LL * da * da), p.g_b = lay.take(8LL * db * db);
+    p.c = lay.take(8LL * da * db);
+    p.work_a = lay.take(8LL * 4 * da * SS_MAX_Q), p.work_b = lay.take(8LL * 4 * db * SS_MAX_Q);
+    p.ev = lay.take(db ? 16LL * q : 0);
+    p.vec_a = lay.take(db ? 8LL * da * q : 0), p.vec_b = lay.take(8LL * db * q);
+    p.w = lay.take(db ? 8LL * da * q : 0);
+    p.m = lay.take(db ? 8LL * q * q : 0), p.s = lay.take(db ? 8LL * q * q : 0);
+    p.total = lay.end;
     return p;
 }
 

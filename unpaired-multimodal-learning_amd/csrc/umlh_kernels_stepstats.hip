@@ -183,12 +183,12 @@ extern "C" long long umlh_stepstats_partials(int B, int T, int d) {
 
 extern "C" unsigned long long umlh_stepstats_bytes(int B, int T, int d) {
     const long long p = umlh_stepstats_partials(B, T, d);
-    return ((unsigned long long)(p > 0 ? p : 1) * 2 * sizeof(double) + 255) / 256 * 256;
+    return (unsigned long long)align_up((p > 0 ? p : 1) * 2 * 8);
 }
 
 extern "C" int umlh_stepstats_launch(const float* x, long long ldb, long long ldt, const float* recon, long long ldb_r, long long ldt_r,
                                      int B, int T, int d, const long long* lengths, double* out4, void* scratch, hipStream_t st) {
-    double* partial = reinterpret_cast<double*>(scratch);
+    double* partial = at<double>(scratch, 0);
     const long long p = umlh_stepstats_partials(B, T, d);
     if (p > 0) {                                                          // t_len == 1 has no pair: the final alone writes zeros
         const int quads = (d + 3) / 4;

@@ -11,6 +11,11 @@
 inline long long align_up(long long x) { return (x + 255) / 256 * 256; }
 template <class T>
 inline T* at(void* scratch, long long off) { return reinterpret_cast<T*>(static_cast<char*>(scratch) + off); }
+struct ScratchLayout {                 // regions of one scratch block, each on a 256-byte boundary
+    long long end;
+    explicit ScratchLayout(long long start = 0) : end(start) {}      // start: a multiple of 256
+    long long take(long long bytes) { const long long at = end; end += align_up(bytes); return at; }
+};
 
 // Raises Kernel's dynamic-LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) to `bytes`, once per device: the attribute is per
 // device, and bit d of the mask (one mask per kernel instantiation) says it is set on device d.  Returns 0 or the HIP error of

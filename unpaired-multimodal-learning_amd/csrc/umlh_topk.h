@@ -42,11 +42,11 @@ inline TopkPlan topk_plan(long long nq, long long nt, int k, int margin, int spl
     p.kc = (int)(k + margin < nt ? k + margin : nt);
     p.splits = topk_splits(nq, nt, splits);
     p.ntiles = (int)((nt + TK_COLS - 1) / TK_COLS);
-    const long long list = align_up((long long)p.splits * nq * p.kc * 4);
-    p.part_s = align_up(front_bytes);
-    p.part_i = p.part_s + list;
-    p.cand = p.part_i + list;
-    p.total = p.cand + align_up(nq * p.kc * 4);
+    const long long list = (long long)p.splits * nq * p.kc * 4;
+    ScratchLayout lay;
+    lay.take(front_bytes);
+    p.part_s = lay.take(list), p.part_i = lay.take(list);
+    p.cand = lay.take(nq * p.kc * 4), p.total = lay.end;
     return p;
 }
 
