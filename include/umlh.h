@@ -1008,6 +1008,55 @@ int  umlh_clamp_rows(const float* x, int64_t n, int64_t d, int64_t ldx, const fl
 int  umlh_knn_accuracy(const int32_t* knn, int64_t n, int64_t m, int64_t ld, double* out, void* scratch, uint64_t scratch_bytes,
                        void* stream);
 
+/* ---- device loader of the affect datasets (mosi, mosei, humor, sarcasm): what Affectdataset.__getitem__ and the _process_1
+ * collate of MultiBench/datasets/affect/get_data.py:159-261,418-444 do per sample and per batch on the host, as three table-build
+ * passes and one step-path kernel.  Additive to ABI v11: umlh_version() is unchanged, callers detect the
+ * feature by these symbols.  A table is dense row-major fp32 [n, t_len, d] (sample, time, feature).  Every argument check
+ * happens before any HIP call and names the function and the argument; everything runs on `stream`; outputs are device memory;
+ * no atomics on global memory: results are bitwise reproducible across calls and streams.
+ * Envelope of a table: 1 <= n < 2^31, t_len >= 1, 1 <= d <= 2^20, t_len * d < 2^31; anything else is UMLH_E_INVALID. */
+#define UMLH_SEQ_GATHER_MAX_SOURCES 3
+
+/* start[i] (int32 [n]) = the row of the first element of x[i] that compares != 0 -- a NaN counts, -0.0 does not, as
+ * text.nonzero()[0][0] (get_data.py:209) -- and t_len when sample i has none (the reference drops or crashes on such a sample;
+ * the caller drops it).  One launch. */
+int  umlh_seq_first_nonzero(const float* x, int64_t n, int32_t t_len, int32_t d, int32_t* start, void* stream);
+
+/* The reference's vision_norm (get_data.py:185-191) over the rows of a [rows, d] matrix (row r at x + r*ldx, rows = n * t_len
+ * of a table, padding rows included):
+ *   stats[c] = mean_r x[r, c],  stats[d + c] = sqrt(mean_r (x[r, c] - stats[c])^2)     (population std; 2 d device doubles)
+ *   out[r*ldo + c] = (float)(((double)x[r, c] - stats[c]) / stats[d + c])
+ * Sums in fp64 from the fp32 values, per row chunk and then in chunk order (the column-sum core of the probe's scaler
+ * statistics); the second pass sums squared deviations from the mean the first one wrote.  A column with a zero std is NOT
+ * special-cased: 0 / 0 = NaN and v / 0 = +-Inf, as numpy's expression gives.  out == x (with ldo == ldx) works in place.
+ * Five launches, no host sync.  Envelope: 1 <= rows < 2^40, 1 <= d <= 2^20, ldx >= d, ldo >= d; scratch 8-byte aligned.
+ * The size query does not end in _scratch_bytes: that family is closed (it is pinned value for value by a recorded file). */
+uint64_t umlh_seq_column_standardize_scratch(int64_t rows, int32_t d);          /* bytes; 0 on invalid arguments */
+int  umlh_seq_column_standardize(const float* x, int64_t rows, int32_t d, int64_t ldx, float* out, int64_t ldo, double* stats,
+                                 void* scratch, uint64_t scratch_bytes, void* stream);
+
+/* The reference's z_norm (get_data.py:223-226), in place: per sample i and column c over the rows t = s_i .. t_len - 1,
+ * s_i = clamp(start[i], 0, t_len), L = t_len - s_i:
+ *   mean = sum_t x / L and sd = sqrt(sum_t (x - mean)^2 / (L - 1)) in fp64 (t ascending, one chain each; the unbiased form),
+ *   x[i, t, c] = nan_to_num((x[i, t, c] - (float)mean) / (float)sd) in fp32:  NaN -> 0, +Inf -> FLT_MAX, -Inf -> -FLT_MAX.
+ * A constant column gives 0 / 0 and L = 1 gives sd = NaN: both become all 0.  Rows t < s_i are not touched.  One thread per
+ * (sample, column): the result for a sample does not depend on n, on the grid or on the sample's position.  One launch. */
+int  umlh_seq_standardize(float* x, int64_t n, int32_t t_len, int32_t d, const int32_t* start, void* stream);
+
+/* One launch builds a batch in the _process_1 layout (get_data.py:418-444).  srcs, dims, outs are HOST arrays of n_src <= 3
+ * entries: source m is a table [n, t_len, dims[m]], outs[m] a dense block [b, t_out, dims[m]]; a NULL source is skipped (its
+ * dims and outs entries are not read), at least one must be given.  start (int32 [n]) and ids (int64 [b]) are device memory.
+ * With s = clamp(start[ids[j]], 0, t_len) and len_j = min(t_len - s, t_out):
+ *   outs[m][j, t, :] = srcs[m][ids[j], s + t, :] for t < len_j,   +0.0 for len_j <= t < t_out;      lengths[j] = len_j  (int64 [b])
+ * t_out is the caller's (the host knows every length): the longest trimmed sequence of the batch reproduces pad_sequence; a
+ * smaller one clips rows and lengths; a larger one pads further.  An id outside [0, n) gives a zero block and length 0 and is
+ * never used as an address.  Repeated ids are fine.  Nothing is written outside the b * t_out * dims[m] words of a block and
+ * lengths[0 .. b).  Envelope: every given source inside the table envelope above, 1 <= b <= 65535, t_out >= 1,
+ * t_out * dims[m] < 2^31. */
+int  umlh_seq_gather_pad(const float* const* srcs, const int32_t* dims, int32_t n_src, int64_t n, int32_t t_len,
+                         const int32_t* start, const int64_t* ids, int32_t b, int32_t t_out, float* const* outs, int64_t* lengths,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

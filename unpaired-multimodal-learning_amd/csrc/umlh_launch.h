@@ -233,6 +233,15 @@ int umlh_outlier_launch_kth(const float* x, long long n, long long d, long long 
 int umlh_outlier_launch_clamp(const float* x, long long n, int d, long long ldx, const float* q_val, int normalize, float* out,
                               long long ldo, hipStream_t st);
 int umlh_outlier_launch_accuracy(const int* knn, long long n, long long m, long long ld, double* out, void* scratch, hipStream_t st);
+// ---- umlh_kernels_seqload.hip: device loader of the affect datasets (first nonzero row, two standardisations, batch gather-pad) ----
+unsigned long long umlh_seqload_colnorm_bytes(long long rows, int d);
+int umlh_seqload_launch_first_row(const float* x, long long n, int T, int D, int* start, hipStream_t st);
+int umlh_seqload_launch_colnorm(const float* x, long long rows, int d, long long ldx, float* out, long long ldo, double* stats,
+                                void* scratch, hipStream_t st);
+int umlh_seqload_launch_znorm(float* x, long long n, int T, int d, const int* start, hipStream_t st);
+// srcs, dims, outs: host arrays of n_src entries; a NULL source is skipped
+int umlh_seqload_launch_gather_pad(const float* const* srcs, const int* dims, int n_src, long long n, int T, const int* start,
+                                   const long long* ids, int B, int t_out, float* const* outs, long long* lengths, hipStream_t st);
 
 // ---- umlh_api.cpp, for umlh_encoder.cpp ----
 // out[M,N] (ldo == N) = epilogue(A B^T) with the operand layouts of umlh_gemm_f32.  `splits` K-slabs go to `slabs`

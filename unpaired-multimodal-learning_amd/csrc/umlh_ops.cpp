@@ -26,7 +26,7 @@ static inline long long* ll(int64_t* p) { return reinterpret_cast<long long*>(p)
 // on a 256-byte boundary from the base (align_up, umlh_launch.h), so the base decides the alignment of every slab.
 // The policy records what each entry point has always checked; it is not derived from the layouts, and the entry points keep it:
 //   8 bytes  umlh_probe_fit (fp64 solver state), umlh_row_abs_quantile (fp64 partials), umlh_abs_kth (u64 histogram),
-//            umlh_knn_accuracy (int64 partials);
+//            umlh_knn_accuracy (int64 partials), umlh_seq_column_standardize (fp64 partials);
 //   4 bytes  umlh_knn_search, umlh_eval_topk (float scores and int indices of the top-k core, nothing wider);
 //   none     everything else.  Of these umlh_align_knn (float / int) and umlh_class_index (int counts) need 4 bytes and
 //            umlh_seq_mse_backward takes a float*; the others carve fp64 or int64 slabs (Gram and column sums, partial sums,
@@ -1079,5 +1079,79 @@ int umlh_knn_accuracy(const int32_t* knn, int64_t n, int64_t m, int64_t ld, doub
     if (ld != 0 && ld < m) return fail(UMLH_E_INVALID, "%s: row stride %lld (need 0 or >= m=%lld)", who, (long long)ld, (long long)m);
     RC(check_scratch(who, scratch, scratch_bytes, umlh_outlier_accuracy_bytes(n), 8, SCRATCH_BYTES_EQ));
     HIPCHK(umlh_outlier_launch_accuracy(knn, n, m, ld, out, scratch, (hipStream_t)stream), who);
+    return UMLH_OK;
+}
+
+// ---- device loader of the affect datasets (kernels: umlh_kernels_seqload.hip) ----
+static const int64_t SEQ_BLOCK_END = (int64_t)1 << 31;    // exclusive: t_len * d words of one sample are indexed with an int
+static const int SEQ_MAX_BATCH = 65535, SEQ_MAX_COLS = 1 << 20;
+
+// the shape of one [n, t_len, d] table; 0 = fine
+static int check_seq_table(const char* who, int64_t n, int32_t t_len, int32_t d) {
+    if (n < 1 || n >= ROWS_END) return fail(UMLH_E_INVALID, "%s: n=%lld samples (need 1 <= n < 2^31)", who, (long long)n);
+    if (t_len < 1) return fail(UMLH_E_INVALID, "%s: t_len=%d < 1", who, t_len);
+    if (d < 1 || d > SEQ_MAX_COLS) return fail(UMLH_E_INVALID, "%s: d=%d outside 1..%d", who, d, SEQ_MAX_COLS);
+    if ((int64_t)t_len * d >= SEQ_BLOCK_END)
+        return fail(UMLH_E_INVALID, "%s: t_len=%d d=%d (need t_len * d < 2^31 words per sample)", who, t_len, d);
+    return UMLH_OK;
+}
+
+int umlh_seq_first_nonzero(const float* x, int64_t n, int32_t t_len, int32_t d, int32_t* start, void* stream) {
+    const char* who = "umlh_seq_first_nonzero";
+    if (!x || !start) return fail(UMLH_E_INVALID, "%s: null pointer (x and start are required)", who);
+    RC(check_seq_table(who, n, t_len, d));
+    HIPCHK(umlh_seqload_launch_first_row(x, n, t_len, d, start, (hipStream_t)stream), who);
+    return UMLH_OK;
+}
+
+static bool colnorm_shape_ok(int64_t rows, int32_t d) { return rows >= 1 && rows < ((int64_t)1 << 40) && d >= 1 && d <= SEQ_MAX_COLS; }
+
+uint64_t umlh_seq_column_standardize_scratch(int64_t rows, int32_t d) {
+    return colnorm_shape_ok(rows, d) ? umlh_seqload_colnorm_bytes(rows, d) : 0;
+}
+
+int umlh_seq_column_standardize(const float* x, int64_t rows, int32_t d, int64_t ldx, float* out, int64_t ldo, double* stats,
+                                void* scratch, uint64_t scratch_bytes, void* stream) {
+    const char* who = "umlh_seq_column_standardize";
+    if (!x || !out || !stats || !scratch) return fail(UMLH_E_INVALID, "%s: null pointer (x, out, stats and scratch are required)", who);
+    if (!colnorm_shape_ok(rows, d))
+        return fail(UMLH_E_INVALID, "%s: rows=%lld d=%d (need 1 <= rows < 2^40, 1 <= d <= %d)", who, (long long)rows, d, SEQ_MAX_COLS);
+    if (ldx < d) return fail(UMLH_E_INVALID, "%s: ldx=%lld < d=%d", who, (long long)ldx, d);
+    if (ldo < d) return fail(UMLH_E_INVALID, "%s: ldo=%lld < d=%d", who, (long long)ldo, d);
+    if (out == x && ldo != ldx)
+        return fail(UMLH_E_INVALID, "%s: in place needs ldo == ldx (ldo=%lld ldx=%lld)", who, (long long)ldo, (long long)ldx);
+    RC(check_scratch(who, scratch, scratch_bytes, umlh_seqload_colnorm_bytes(rows, d), 8));
+    HIPCHK(umlh_seqload_launch_colnorm(x, rows, d, ldx, out, ldo, stats, scratch, (hipStream_t)stream), who);
+    return UMLH_OK;
+}
+
+int umlh_seq_standardize(float* x, int64_t n, int32_t t_len, int32_t d, const int32_t* start, void* stream) {
+    const char* who = "umlh_seq_standardize";
+    if (!x || !start) return fail(UMLH_E_INVALID, "%s: null pointer (x and start are required)", who);
+    RC(check_seq_table(who, n, t_len, d));
+    HIPCHK(umlh_seqload_launch_znorm(x, n, t_len, d, start, (hipStream_t)stream), who);
+    return UMLH_OK;
+}
+
+int umlh_seq_gather_pad(const float* const* srcs, const int32_t* dims, int32_t n_src, int64_t n, int32_t t_len, const int32_t* start,
+                        const int64_t* ids, int32_t b, int32_t t_out, float* const* outs, int64_t* lengths, void* stream) {
+    const char* who = "umlh_seq_gather_pad";
+    if (!srcs || !dims || !outs || !start || !ids || !lengths)
+        return fail(UMLH_E_INVALID, "%s: null pointer (srcs, dims, outs, start, ids and lengths are required)", who);
+    if (n_src < 1 || n_src > UMLH_SEQ_GATHER_MAX_SOURCES)
+        return fail(UMLH_E_INVALID, "%s: n_src=%d outside 1..%d", who, n_src, UMLH_SEQ_GATHER_MAX_SOURCES);
+    if (b < 1 || b > SEQ_MAX_BATCH) return fail(UMLH_E_INVALID, "%s: b=%d outside 1..%d", who, b, SEQ_MAX_BATCH);
+    if (t_out < 1) return fail(UMLH_E_INVALID, "%s: t_out=%d < 1", who, t_out);
+    int used = 0;
+    for (int m = 0; m < n_src; ++m) {
+        if (!srcs[m]) continue;
+        ++used;
+        if (!outs[m]) return fail(UMLH_E_INVALID, "%s: source %d has no destination", who, m);
+        RC(check_seq_table(who, n, t_len, dims[m]));
+        if ((int64_t)t_out * dims[m] >= SEQ_BLOCK_END)
+            return fail(UMLH_E_INVALID, "%s: t_out=%d d=%d of source %d (need t_out * d < 2^31 words per block)", who, t_out, dims[m], m);
+    }
+    if (!used) return fail(UMLH_E_INVALID, "%s: every source is NULL", who);
+    HIPCHK(umlh_seqload_launch_gather_pad(srcs, dims, n_src, n, t_len, start, ll(ids), b, t_out, outs, ll(lengths), (hipStream_t)stream), who);
     return UMLH_OK;
 }

@@ -26,6 +26,7 @@ from . import rollout  # noqa: F401,E402
 from .rollout import rollout_rows, seq_spectrum  # noqa: F401,E402
 from . import report  # noqa: F401,E402
 from .report import class_report, topk_classes  # noqa: F401,E402
+from . import seqload  # noqa: F401,E402
 
 
 def host_cpu_budget() -> int:

@@ -1,0 +1,117 @@
+"""The kernels of the affect datasets' device loader (umlh_kernels_seqload.hip; C ABI: ``umlh_seq_first_nonzero``,
+``umlh_seq_column_standardize``, ``umlh_seq_standardize``, ``umlh_seq_gather_pad``) as thin torch wrappers: what
+MultiBench/datasets/affect/get_data.py does per sample (front trim, vision_norm, z_norm) and per batch (_process_1's
+pad_sequence) on the host.  Every call enqueues on ``torch.cuda.current_stream`` and returns device tensors; nothing is read
+back.  There is no CPU compute path.  The loader built on them is ``multibench.data``."""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from . import _glue as glue
+from ._lib import check, load_library
+
+MAX_SOURCES = 3          # UMLH_SEQ_GATHER_MAX_SOURCES
+MAX_BATCH = 65535
+
+
+def _table(x: torch.Tensor, what: str) -> torch.Tensor:
+    if not isinstance(x, torch.Tensor) or x.ndim != 3 or x.dtype != torch.float32 or not x.is_cuda or not x.is_contiguous():
+        raise ValueError(f"{what}: expected a contiguous fp32 device tensor [n, T, d], got "
+                         f"{getattr(x, 'dtype', type(x))} {tuple(getattr(x, 'shape', ()))}")
+    if min(x.shape) < 1:
+        raise ValueError(f"{what}: empty table {tuple(x.shape)}")
+    return x
+
+
+def _start(start: torch.Tensor, n: int, dev: torch.device, what: str) -> torch.Tensor:
+    if not isinstance(start, torch.Tensor) or start.dtype != torch.int32 or start.device != dev or tuple(start.shape) != (n,) \
+            or not start.is_contiguous():
+        raise ValueError(f"{what}: start must be a contiguous int32 tensor [{n}] on {dev}")
+    return start
+
+
+def first_nonzero(x: torch.Tensor) -> torch.Tensor:
+    """int32 [n]: per sample of the [n, T, d] table the row of its first element != 0 (NaN counts, -0.0 does not), T when it
+    has none -- ``text.nonzero()[0][0]`` of the reference."""
+    x = _table(x, "first_nonzero")
+    n, T, d = x.shape
+    start = torch.empty(n, dtype=torch.int32, device=x.device)
+    with torch.cuda.device(x.device):
+        check(load_library().umlh_seq_first_nonzero(x.data_ptr(), n, T, d, start.data_ptr(), glue.stream(x.device)),
+              "umlh_seq_first_nonzero")
+    return start
+
+
+def column_standardize(x: torch.Tensor, out: torch.Tensor | None = None):
+    """``(x - mu) / sigma`` per column over all n * T rows of the [n, T, d] table (population std, fp64 statistics): the
+    reference's vision_norm.  ``out=x`` works in place; default: a new table.  Returns (out, stats) with stats the float64
+    device tensor [2, d] = mean | std.  A zero std is not special-cased."""
+    x = _table(x, "column_standardize")
+    n, T, d = x.shape
+    out = torch.empty_like(x) if out is None else _table(out, "column_standardize (out)")
+    if out.shape != x.shape or out.device != x.device:
+        raise ValueError(f"column_standardize: out {tuple(out.shape)} on {out.device} for x {tuple(x.shape)} on {x.device}")
+    stats = torch.empty((2, d), dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        scratch, nbytes = glue.scratch("umlh_seq_column_standardize_scratch", x.device, rows=n * T, d=d)
+        check(load_library().umlh_seq_column_standardize(x.data_ptr(), n * T, d, d, out.data_ptr(), d, stats.data_ptr(),
+                                                         scratch.data_ptr(), nbytes, glue.stream(x.device)),
+              "umlh_seq_column_standardize")
+    return out, stats
+
+
+def standardize_(x: torch.Tensor, start: torch.Tensor) -> torch.Tensor:
+    """In place: per sample and column over the rows ``start[i]..T-1`` of the [n, T, d] table,
+    ``nan_to_num((x - mean) / std)`` with the unbiased std (fp64 statistics, fp32 arithmetic): the reference's z_norm.  A
+    constant column and a length-1 sequence become all 0.  Returns ``x``."""
+    x = _table(x, "standardize_")
+    n, T, d = x.shape
+    start = _start(start, n, x.device, "standardize_")
+    with torch.cuda.device(x.device):
+        check(load_library().umlh_seq_standardize(x.data_ptr(), n, T, d, start.data_ptr(), glue.stream(x.device)),
+              "umlh_seq_standardize")
+    return x
+
+
+def gather_pad(sources, start: torch.Tensor, ids: torch.Tensor, t_out: int, outs=None, lengths: torch.Tensor | None = None):
+    """One launch: the batch of the samples ``ids`` (int64 device tensor [b]) of up to three [n, T, d_m] tables, an entry of
+    ``sources`` may be None (skipped).  Returns (blocks, lengths): blocks[m] is the fp32 [b, t_out, d_m] block with
+    ``blocks[m][j, t] = sources[m][ids[j], start[ids[j]] + t]`` for t < len_j = min(T - start[ids[j]], t_out) and +0.0 behind
+    (None for a skipped source), lengths the int64 [b] tensor of len_j.  An id outside [0, n) gives a zero block and length
+    0.  ``outs`` / ``lengths``: destinations to write into instead of new tensors."""
+    sources = list(sources)
+    given = [s for s in sources if s is not None]
+    if not 1 <= len(sources) <= MAX_SOURCES or not given:
+        raise ValueError(f"gather_pad: {len(sources)} sources, {len(given)} given (need 1..{MAX_SOURCES} with at least one given)")
+    for s in given:
+        _table(s, "gather_pad")
+    dev, (n, T) = given[0].device, given[0].shape[:2]
+    if any(s.device != dev or tuple(s.shape[:2]) != (n, T) for s in given):
+        raise ValueError("gather_pad: the sources must share the device, n and T")
+    start = _start(start, n, dev, "gather_pad")
+    if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int64 or ids.device != dev or ids.ndim != 1 or not ids.is_contiguous():
+        raise ValueError(f"gather_pad: ids must be a contiguous int64 tensor [b] on {dev}")
+    b, t_out = ids.shape[0], int(t_out)
+    if not 1 <= b <= MAX_BATCH or t_out < 1:
+        raise ValueError(f"gather_pad: b={b} t_out={t_out} (need 1 <= b <= {MAX_BATCH}, t_out >= 1)")
+    if outs is None:
+        outs = [None if s is None else torch.empty((b, t_out, s.shape[2]), dtype=torch.float32, device=dev) for s in sources]
+    else:
+        outs = list(outs)
+        for s, o in zip(sources, outs):
+            if s is not None and (_table(o, "gather_pad (out)").shape != (b, t_out, s.shape[2]) or o.device != dev):
+                raise ValueError(f"gather_pad: out {tuple(o.shape)} for a block {(b, t_out, s.shape[2])}")
+    if lengths is None:
+        lengths = torch.empty(b, dtype=torch.int64, device=dev)
+    elif lengths.dtype != torch.int64 or lengths.device != dev or tuple(lengths.shape) != (b,) or not lengths.is_contiguous():
+        raise ValueError(f"gather_pad: lengths must be a contiguous int64 tensor [{b}] on {dev}")
+    k = len(sources)
+    srcs = (C.c_void_p * k)(*[None if s is None else s.data_ptr() for s in sources])
+    dsts = (C.c_void_p * k)(*[None if s is None else o.data_ptr() for s, o in zip(sources, outs)])
+    dims = (C.c_int32 * k)(*[0 if s is None else s.shape[2] for s in sources])
+    with torch.cuda.device(dev):
+        check(load_library().umlh_seq_gather_pad(srcs, dims, k, n, T, start.data_ptr(), ids.data_ptr(), b, t_out, dsts,
+                                                 lengths.data_ptr(), glue.stream(dev)), "umlh_seq_gather_pad")
+    return [o if s is not None else None for s, o in zip(sources, outs)], lengths
