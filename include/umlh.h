@@ -333,7 +333,9 @@ int  umlh_to_bf16(const float* src, void* dst_bf16, int64_t n, void* stream);
  * recon [B,T,D] optional; dres [B*T*D] and row_partial [B*T] scratch that the backward reads;
  * loss_cnt device float[2] = {loss, denominator}.  Backward: grad_out device scalar (d/d loss);
  * dz [B,T,Z], dw [D,Z], db [D]; scratch: umlh_seq_mse_backward_scratch_floats(B,T,Z,D) device floats for the split-K
- * slabs of dW and the row-chunk partials of db (NULL: one workgroup walks all B*T rows per output tile). */
+ * slabs of dW and the row-chunk partials of db (NULL: db is one walk over all B*T rows per 64 columns, and dW, where the plan
+ * splits the rows, a chain of launches over the same row chunks, each adding the sum so far).  lengths may hold any value:
+ * below 2 no position of the sequence is live, above T it counts as T. */
 int  umlh_seq_mse_forward(const float* z, const float* w, const float* bias, const float* x, const int64_t* lengths,
                           int32_t B, int32_t T, int32_t Z, int32_t D, float* recon, float* dres, float* row_partial,
                           float* loss_cnt, void* stream);
@@ -347,7 +349,10 @@ uint64_t umlh_seq_mse_backward_scratch_floats(int32_t B, int32_t T, int32_t Z, i
  * pred / target [n, D] dense fp32 rows (the caller selects the valid rows, as the reference's boolean indexing does).
  * Forward leaves: pred_hat, target_hat [n, D] (unit rows), pred_norm [n], probs [n, n] = softmax(logits) - I, row_loss [n],
  * loss (device scalar).  Backward: grad_out device scalar; dhat [n, D] scratch; dpred [n, D] = d loss / d pred * grad_out.
- * (No gradient flows to the targets: they are the model's inputs.) */
+ * (No gradient flows to the targets: they are the model's inputs.)
+ * Rows of norm below 1e-12: a row is divided by max(|x|, 1e-12) and its gradient is (dy - y (y . dy)) / max(|x|, 1e-12) for
+ * every row.  torch's F.normalize clamps with clamp_min, whose backward drops the projection term y (y . dy) of a clamped row; the
+ * two agree for |x| = 0 (y = 0) and differ by |y|^2 = (|x| / 1e-12)^2 of the row's gradient for 0 < |x| < 1e-12. */
 int  umlh_infonce_forward(const float* pred, const float* target, int32_t n, int32_t D, float temperature, float* pred_hat,
                           float* target_hat, float* pred_norm, float* probs, float* row_loss, float* loss, void* stream);
 int  umlh_infonce_backward(const float* pred_hat, const float* target_hat, const float* pred_norm, const float* probs,
@@ -498,7 +503,9 @@ int  umlh_index_block(const umlh_index_span_t* img_spans, int32_t n_img_spans, i
 
 /* Standalone optimizer.step() for one parameter tensor from a caller-computed
  * gradient (engine/optimizer/optim.py:34-71; torch.optim single-tensor recurrences):
- * the same update kernel the fused step applies.  v may be NULL for SGD. */
+ * the same update kernel the fused step applies.  v may be NULL for SGD and is not touched by it; step < 1 counts as
+ * step 1.  That kernel moves 16 bytes per access: when param, grad, m or (Adam / AdamW) v is not 16-byte aligned the call
+ * runs the element-wise kernel of umlh_optimizer_step_multi instead, which needs 4-byte alignment only. */
 int  umlh_optimizer_step(int32_t optimizer, float* param, const float* grad, float* m, float* v, int64_t n,
                          double lr, int64_t step, double beta1, double beta2, double eps, double momentum,
                          double weight_decay, void* stream);

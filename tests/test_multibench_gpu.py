@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from _critic_ref import seq_mse_ref
 from conftest import load_golden
 from oracle import multibench_oracle as MO
 
@@ -61,11 +62,14 @@ def test_fused_decoder_kernel_against_oracle_incl_edge_shapes():
         loss, recon = _DecoderNextStepMSE.apply(tz, tw, tb, torch.as_tensor(x).to(DEV),
                                                 None if lens is None else torch.as_tensor(lens).to(DEV))
         (3.0 * loss).backward()
-        if Tn == 1:      # models.py:209-210: plain reconstruction error of the single position
+        if Tn == 1:      # models.py:209-210: plain reconstruction error of the single position (the form the Gaussian toy trains with)
             ref = float(((z @ w.T + b - x) ** 2).mean())
             assert abs(float(loss) - ref) < 1e-5
-            continue
-        ol, orecon, odz, odw, odb = MO.decoder_next_step_loss(z, w, b, x, lens)
+            r = seq_mse_ref(z, w, b, x, lens, 1.0)             # the float64 reference: every position live, target t, no epsilon
+            ol, orecon, odz, odw, odb = float(r["loss"]), r["recon"], r["dz"], r["dw"], r["db"]
+            assert abs(ol - ref) < 1e-6
+        else:
+            ol, orecon, odz, odw, odb = MO.decoder_next_step_loss(z, w, b, x, lens)
         assert abs(float(loss) - ol) < 1e-5 * max(1.0, ol)
         np.testing.assert_allclose(recon.cpu().numpy(), orecon, atol=1e-4)
         np.testing.assert_allclose(tz.grad.cpu().numpy(), 3 * odz, atol=1e-5, rtol=1e-3)

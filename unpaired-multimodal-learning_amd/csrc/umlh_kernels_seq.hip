@@ -127,7 +127,7 @@ int umlh_seq_launch_fwd(const float* z, const float* w, const float* b, const fl
     return (int)hipGetLastError();
 }
 int umlh_seq_launch_bwd(const float* z, const float* w, const float* dres, const float* loss_cnt, const float* grad_out, int B,
-                        int T, int Z, int D, float* dz, float* dw, float* db, int with_params, hipStream_t st) {
+                        int T, int Z, int D, float* dz, float* dw, float* db, int with_params, int dw_chunk, hipStream_t st) {
     hipLaunchKernelGGL(seq_mse_bwd_dz_kernel, dim3(B * T), dim3(128), sizeof(float) * D, st, dres, w, loss_cnt, grad_out, Z, D, dz);
     if (!with_params) return (int)hipGetLastError();     // dW / db by the caller (split-K slabs + row-chunk partials)
     hipLaunchKernelGGL(seq_mse_bwd_db_kernel, dim3((D + 63) / 64), dim3(1024), 0, st, dres, loss_cnt, grad_out, B * T, D, db);
@@ -136,7 +136,23 @@ int umlh_seq_launch_bwd(const float* z, const float* w, const float* dres, const
     memset(&g, 0, sizeof(g));
     g.A = dres; g.lda = D; g.B = z; g.ldb = Z; g.out = dw; g.ldo = Z;
     g.M = D; g.N = Z; g.K = B * T; g.k_chunk = g.K; g.k_switch = g.K; g.k_valid1 = g.K; g.alpha = 1.f;
-    int rc = umlh_f32_launch_gemm(&g, 1, 1, 1, st);
+    int rc = 0;
+    if (dw_chunk <= 0 || dw_chunk >= B * T) {
+        rc = umlh_f32_launch_gemm(&g, 1, 1, 1, st);
+    } else {
+        // A caller without slab memory whose plan splits K: one launch per dw_chunk rows, each adding the sum so far (the
+        // epilogue's in-place add).  One k-ordered fp32 chain over thousands of rows loses bits that the split-K form keeps:
+        // dres = recon - x correlates with z, so the partial sums drift and every add rounds at the running sum's magnitude
+        // (2^-21.6 rms of the term-magnitude sum at 4160 rows, against 2^-24.4 in chunks of 144).
+        const int R = B * T;
+        for (int r0 = 0; r0 < R && rc == 0; r0 += dw_chunk) {
+            g.A = dres + (size_t)r0 * D; g.B = z + (size_t)r0 * Z;
+            g.K = R - r0 < dw_chunk ? R - r0 : dw_chunk;
+            g.k_chunk = g.K; g.k_switch = g.K; g.k_valid1 = g.K;
+            if (r0 > 0) { g.epi.add = dw; g.epi.on = 1; }
+            rc = umlh_f32_launch_gemm_enc(&g, 1, 1, 1, st);
+        }
+    }
     if (rc) return rc;
     hipLaunchKernelGGL(seq_mse_scale_kernel, dim3((unsigned)(((long long)D * Z + 255) / 256)), dim3(256), 0, st, dw, (long long)D * Z,
                        loss_cnt, grad_out);
@@ -172,6 +188,15 @@ __global__ __launch_bounds__(256) void l2norm_rows_kernel(const float* __restric
     if (lane == 0) norm[r] = den;
 }
 
+// A logit is the ROUNDED product dot * inv_temp everywhere.  The multiply carries no contract flag, so the compiler cannot fuse
+// it into the subtractions that follow: fused, l - mx and lse - diag subtract a rounded logit from an unrounded one and leave
+// the product's rounding error (up to half an ulp of the logit) where the result is exactly 0 -- a single row (n = 1) had a
+// loss of 3e-8, a sharp row's diagonal probability and loss the rounding of a logit of 100 instead of 0.
+__device__ __forceinline__ float nce_logit(float dot, float inv_temp) {
+#pragma clang fp contract(off)
+    return dot * inv_temp;
+}
+
 // row r of the raw dot products: l = dots / temperature; row_loss[r] = logsumexp(l) - l[r]; the row is overwritten with
 // softmax(l) - onehot(r)  (d loss_r / d l)
 __global__ __launch_bounds__(256) void nce_rows_kernel(float* __restrict__ dots, int n, float inv_temp, float* __restrict__ row_loss) {
@@ -179,13 +204,13 @@ __global__ __launch_bounds__(256) void nce_rows_kernel(float* __restrict__ dots,
     if (r >= n) return;
     float* row = dots + (size_t)r * n;
     float mx = -__builtin_huge_valf();
-    for (int j = lane; j < n; j += 64) mx = fmaxf(mx, row[j] * inv_temp);
+    for (int j = lane; j < n; j += 64) mx = fmaxf(mx, nce_logit(row[j], inv_temp));
     mx = nce_wave_max(mx);
     float s = 0.f;
-    for (int j = lane; j < n; j += 64) s += __expf(row[j] * inv_temp - mx);
+    for (int j = lane; j < n; j += 64) s += __expf(nce_logit(row[j], inv_temp) - mx);
     s = nce_wave_sum(s);
-    const float lse = mx + __logf(s), diag = row[r] * inv_temp;
-    for (int j = lane; j < n; j += 64) row[j] = __expf(row[j] * inv_temp - lse) - (j == r ? 1.f : 0.f);
+    const float lse = mx + __logf(s), diag = nce_logit(row[r], inv_temp);
+    for (int j = lane; j < n; j += 64) row[j] = __expf(nce_logit(row[j], inv_temp) - lse) - (j == r ? 1.f : 0.f);
     if (lane == 0) row_loss[r] = lse - diag;
 }
 

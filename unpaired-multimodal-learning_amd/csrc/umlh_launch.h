@@ -78,7 +78,7 @@ int umlh_p2p_status_offset(long long n_max, int n_ranks, unsigned long long* off
 int umlh_seq_launch_fwd(const float* z, const float* w, const float* b, const float* x, const int64_t* lengths, int B, int T,
                         int Z, int D, float* recon, float* dres, float* row_partial, float* loss_cnt, hipStream_t st);
 int umlh_seq_launch_bwd(const float* z, const float* w, const float* dres, const float* loss_cnt, const float* grad_out, int B,
-                        int T, int Z, int D, float* dz, float* dw, float* db, int with_params, hipStream_t st);
+                        int T, int Z, int D, float* dz, float* dw, float* db, int with_params, int dw_chunk, hipStream_t st);
 int umlh_seq_launch_l2norm(const float* x, int n, int D, float* y, float* norm, hipStream_t st);
 int umlh_seq_launch_nce_rows(float* dots, int n, float inv_temp, float* row_loss, float* loss, hipStream_t st);
 int umlh_seq_launch_l2norm_bwd(const float* dy, const float* y, const float* norm, const float* grad_out, float scale, int n,

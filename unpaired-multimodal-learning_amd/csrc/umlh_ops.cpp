@@ -106,12 +106,14 @@ int umlh_seq_mse_backward(const float* z, const float* w, const float* dres, con
     hipStream_t st = (hipStream_t)stream;
     const int R = B * T, sp = splits_for(D, Z, R);
     if (!scratch || sp == 1) {
-        HIPCHK(umlh_seq_launch_bwd(z, w, dres, loss_cnt, grad_out, B, T, Z, D, dz, dw, db, 1, st), "seq bwd");
+        // without slab memory a planned split becomes a chain of launches over the same row chunks (umlh_seq_launch_bwd)
+        const int dw_chunk = sp > 1 ? (int)round_up((R + sp - 1) / sp, KT) : 0;
+        HIPCHK(umlh_seq_launch_bwd(z, w, dres, loss_cnt, grad_out, B, T, Z, D, dz, dw, db, 1, dw_chunk, st), "seq bwd");
         return UMLH_OK;
     }
     // dz as before; dW[d][k] = s * sum_r dres[r][d] z[r][k] as split-K slabs, db[d] = s * sum_r dres[r][d] as row-chunk partials,
     // both summed and scaled (s = 2 * grad_out / denominator, device-side) by one multi-reduce
-    HIPCHK(umlh_seq_launch_bwd(z, w, dres, loss_cnt, grad_out, B, T, Z, D, dz, dw, db, 0, st), "seq bwd (dz)");
+    HIPCHK(umlh_seq_launch_bwd(z, w, dres, loss_cnt, grad_out, B, T, Z, D, dz, dw, db, 0, 0, st), "seq bwd (dz)");
     const int chunk = row_chunk(R), nr = (R + chunk - 1) / chunk;
     float* slabs = scratch;
     float* part = scratch + (size_t)sp * D * Z;
@@ -373,6 +375,19 @@ int umlh_optimizer_step(int32_t optimizer, float* param, const float* grad, floa
     if (!param || !grad || !m || (optimizer != UMLH_OPT_SGD && !v) || n < 0)
         return fail(UMLH_E_INVALID, "umlh_optimizer_step: null buffer");
     const OptArgs o = standalone_opt(optimizer, lr, step, beta1, beta2, eps, momentum, weight_decay);
+    // reduce_update picks its float4 path from n alone and moves 16 bytes per access.  A base that is not 16-byte aligned (a view
+    // at an odd element offset; a block of torch's allocator never is) takes the element-wise kernel of the multi-tensor entry.
+    const uintptr_t bases = reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(m) |
+                            (optimizer != UMLH_OPT_SGD ? reinterpret_cast<uintptr_t>(v) : 0);
+    if (bases & 15) {
+        float* const pp[1] = {param};
+        const float* const gg[1] = {grad};
+        float* const mm[1] = {m};
+        float* const vv[1] = {v};
+        const long long cnt = n;
+        HIPCHK(umlh_launch_multi_opt(1, pp, gg, mm, vv, &cnt, &o, (hipStream_t)stream), "optimizer step (unaligned base)");
+        return UMLH_OK;
+    }
     HIPCHK(umlh_launch_reduce_update(1, grad, 1, n, n, nullptr, param, m, v, &o, 0, 0, (hipStream_t)stream),
            "optimizer step");
     return UMLH_OK;
