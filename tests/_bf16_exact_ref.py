@@ -23,6 +23,10 @@ Scalar definitions (oracle/uml_oracle.py step_grads, include/umlh.h umlh_batch_t
 denominator is ``global_rows``, i.e. sum of the row losses / G, unweighted in the scalars; accuracy = first-arg-max hits / G;
 dZ = weight * scale * (softmax - onehot) / G; dW_head = dZ_i^T F_i + dZ_t^T X_t; dH = dZ_i W_head; dW_proj = dH^T X_i;
 plain SGD: W - lr * g.
+
+``own_rows`` (the single-launch micro step, tests/test_micro_kernels_gpu.py): the denominator of each modality is its OWN row
+count of the step in place of G -- the micro kernel's ``w / rows`` -- and must be a power of two (1 .. 64), so that
+weight * scale / rows stays one; C' = 16 joins the live counts there (1/16 and 15/16 are bf16 numbers).
 """
 from __future__ import annotations
 
@@ -55,11 +59,16 @@ class Shape:
     tab_t: int = 350
     live_from: int = 0            # classes below are all dead
     dense: bool = False           # index=None: rows 0..rows-1 of the tables
+    own_rows: bool = False        # denominators: each modality's own row count (a power of two), not G
 
     @property
     def id(self) -> str:
         s = f"{self.d_img}-{self.d}" if self.two_layer else f"{self.d}"
-        return f"{s}-{self.C}-{self.live}-{self.ri}-{self.rt}" + ("-neg" if self.scale < 0 else "") + ("-dense" if self.dense else "")
+        return f"{s}-{self.C}-{self.live}-{self.ri}-{self.rt}" + ("-neg" if self.scale < 0 else "") + ("-dense" if self.dense else "") + (f"-own{self.live_from}" if self.own_rows else "")
+
+    def den(self, mod: str) -> int:
+        """The denominator of a modality's mean ('img' / 'txt')."""
+        return (self.ri if mod == "img" else self.rt) if self.own_rows else G
 
 
 def single(d, C, live, ri, rt, **kw) -> Shape:
@@ -151,7 +160,7 @@ def _live_set(rng, s: Shape) -> np.ndarray:
     if s.live == s.C:
         return np.arange(s.C)
     chosen = []
-    if s.C > 256:                 # every 32-class slice (one wave's classes of the widest forward) holds a live class
+    if s.C > 256 and not s.own_rows:   # every 32-class slice (one wave's classes of the widest forward) holds a live class
         chosen = [int(rng.integers(lo, min(lo + 32, s.C))) for lo in range(0, s.C, 32)]
     rest = np.setdiff1d(cand, chosen)
     chosen = np.concatenate([np.asarray(chosen, dtype=np.int64), rng.choice(rest, s.live - len(chosen), replace=False)])
@@ -171,7 +180,9 @@ def _labels(rng, s: Shape, live: np.ndarray, n: int) -> np.ndarray:
 
 
 def make_case(s: Shape, seed: Optional[int] = None) -> Case:
-    if s.live not in LIVE_COUNTS:
+    if s.own_rows and any(r & (r - 1) or r > 64 for r in (s.ri, s.rt)):
+        raise ValueError("own_rows: row counts must be powers of two up to 64 (or 0)")
+    if s.live not in LIVE_COUNTS + ((16,) if s.own_rows else ()):
         raise ValueError(f"C' = {s.live}: the dZ values coef/C' and coef(1/C' - 1) are bf16 numbers only for C' in {LIVE_COUNTS} "
                          "(at 512, 511/512 is a rounding tie)")
     if s.live > s.C - s.live_from or abs(s.scale) != 64.0:
@@ -224,7 +235,7 @@ def make_case(s: Shape, seed: Optional[int] = None) -> Case:
 MUTATIONS = ("drop_last_row", "padded_row_dz", "swap_across_seam", "shift_k_chunk", "dh_rounded_twice", "argmax_second_live")
 
 
-def _segment(case: Case, F: np.ndarray, y: np.ndarray, weight: float, mutation):
+def _segment(case: Case, F: np.ndarray, y: np.ndarray, weight: float, mutation, den: int = G):
     """Forward + CE of one modality's rows F [r, d] (float64): (dZ [r, C], sum of row losses, first-arg-max hits)."""
     s = case.shape
     W = case.w_head.astype(np.float64)
@@ -246,7 +257,7 @@ def _segment(case: Case, F: np.ndarray, y: np.ndarray, weight: float, mutation):
     assert np.allclose(ce, np.log(s.live) + np.where(is_live[y], 0.0, 128.0), rtol=0, atol=1e-12)
     p = np.where(is_live, 1.0 / s.live, 0.0)[None, :].repeat(r, axis=0)       # the softmax, exactly ...
     assert np.abs(e / se - p).max(initial=0.0) < 1e-15                            # ... as float64 confirms
-    coef = weight * s.scale / G
+    coef = weight * s.scale / den
     onehot = np.zeros_like(p)
     onehot[np.arange(r), y] = 1.0
     dz = coef * (p - onehot)
@@ -276,7 +287,8 @@ def reference(case: Case, mutation: Optional[str] = None) -> Ref:
     W = case.w_head.astype(f64)
     assert_bf16_exact("W_head", W)
     assert np.abs(W).max() < 4
-    q = ALPHA * abs(s.scale) / G / s.live                     # the quantum of every gradient term (image terms: 2q)
+    q = ALPHA * abs(s.scale) / max(s.den("img"), s.den("txt")) / s.live   # the quantum of every gradient term (image terms: 2q;
+                                                              # own_rows: both coefficients are power-of-two multiples of it)
     g_head = np.zeros((s.C, s.d), dtype=f64)
     terms_head = np.zeros((s.C, s.d), dtype=f64)
     g_proj = None
@@ -299,7 +311,7 @@ def reference(case: Case, mutation: Optional[str] = None) -> Ref:
             F = X @ Wp.T
             assert_bf16_exact("H", F)
             assert np.abs(F).max() <= 48 and np.all(F == np.round(F))
-        dz, ce_sum, hits = _segment(case, F, y, weight, mutation)
+        dz, ce_sum, hits = _segment(case, F, y, weight, mutation, s.den(mod))
         out[mod] = (ce_sum, hits)
         Fdw = F
         if mutation == "shift_k_chunk" and mod == "img":         # the second 64-row chunk of the dW operand one row late
@@ -309,7 +321,7 @@ def reference(case: Case, mutation: Optional[str] = None) -> Ref:
         terms_head += np.abs(dz.T) @ np.abs(Fdw)
         g_head += dz.T @ Fdw
         if mutation == "padded_row_dz" and mod == "img":         # the row behind the last one, as if it were no padding
-            pad = np.where(np.isin(np.arange(s.C), case.live), weight * s.scale / G / s.live, 0.0)
+            pad = np.where(np.isin(np.arange(s.C), case.live), weight * s.scale / s.den(mod) / s.live, 0.0)
             nxt = tab[(int(ids[-1]) + 1) % tab.shape[0]].astype(f64)
             g_head += np.outer(pad, nxt @ case.w_proj.astype(f64).T if s.two_layer else nxt)
         if mod == "img" and s.two_layer:
@@ -330,8 +342,9 @@ def reference(case: Case, mutation: Optional[str] = None) -> Ref:
             g_proj = np.zeros((s.d, s.d_img), dtype=f64)
         g_proj32 = assert_f32_exact("dW_proj", g_proj)
         wp_new = assert_f32_exact("W_proj - lr g", case.w_proj.astype(f64) - LR * g_proj)
-    acc = [assert_f32_exact("accuracy", np.asarray(out[m][1] / G, dtype=f64)) for m in ("img", "txt")]
-    return Ref(g_head32, g_proj32, out["img"][0] / G, out["txt"][0] / G, np.float32(acc[0]), np.float32(acc[1]), w_new, wp_new)
+    acc = [assert_f32_exact("accuracy", np.asarray(out[m][1] / max(s.den(m), 1), dtype=f64)) for m in ("img", "txt")]
+    return Ref(g_head32, g_proj32, out["img"][0] / max(s.den("img"), 1), out["txt"][0] / max(s.den("txt"), 1), np.float32(acc[0]),
+               np.float32(acc[1]), w_new, wp_new)
 
 
 @functools.lru_cache(maxsize=None)

@@ -1,6 +1,10 @@
 """GPU: the single-launch micro step (umlh_kernels_micro.hip) -- the reference's own operating point (batch 8 / 32 / 64,
 engine/optimizer/default.py:3-45) -- against the CPU oracle, against the general three-kernel path, and the grouped
-multi-head launch (finetune.py:406-448 sweep) against isolated runs, bit for bit."""
+multi-head launch (finetune.py:406-448 sweep) against isolated runs, bit for bit.
+
+The sharp single-step checks live in tests/test_micro_kernels_gpu.py (every instantiation against float64 under CPU-calibrated
+bounds, multi-step launches as chains of single steps, bit for bit); the looser multi-step comparisons below stay as the
+end-to-end view over 10 - 30 steps and are marked where a sharper check now covers them."""
 import numpy as np
 import pytest
 import torch
@@ -85,7 +89,10 @@ def test_micro_steps_match_oracle_and_general_path(d, C, ri, rt, optim, learn, s
     cols = list(range(8)) if learn else [0, 1, 2, 3, 6, 7]          # d loss / d scale is only formed for learnable scales
     np.testing.assert_allclose(scm[:, cols], scg[:, cols], atol=2e-5, rtol=1e-4)       # == the general path
     wm, wg = em.w_head.cpu().numpy(), eg.w_head.cpu().numpy()
-    # Adam's early steps move each weight by ~lr*sign(g): elements whose gradient is at fp32-noise level may take the other sign
+    # Adam's early steps move each weight by ~lr*sign(g): elements whose gradient is at fp32-noise level may take the other sign.
+    # (Redundant as a test of the kernel's arithmetic since test_micro_kernels_gpu.py: the gradient probe and the optimizer step
+    # from a live state bound W', m' and v' of one step element by element, and the chain test carries that to 9 and 515 steps;
+    # the moments' rtol 2e-3 against the general path below likewise.  Kept as the 12-step end-to-end comparison.)
     lim = 2 * sum(lrs) + 1e-6
     for ref in (st.w_head, wg):
         diff = np.abs(wm - ref)
@@ -245,6 +252,8 @@ def test_micro_steps_bf16_operand_mode(d, C, ri, rt, monkeypatch):
     wg, sg = run(False, "bf16")
     wf, sf = run(True, "fp32")
     cols = [c for c, live in ((umlh.S_LOSS_IMG, ri), (umlh.S_LOSS_TXT, rt)) if live]
+    # (test_micro_kernels_gpu.py holds bf16 mode to its float64 statement per step and bit for bit on exact operands; the 5 %
+    # allowance and the 3e-3 below remain the comparison of two implementations over 10 chaotic steps)
     np.testing.assert_allclose(sm[:, cols], sg[:, cols], atol=3e-3, rtol=2e-3)          # two bf16 implementations
     np.testing.assert_allclose(sm[:, cols], sf[:, cols], atol=2e-2, rtol=1e-2)          # bf16 operands vs fp32
     acc = [c for c, live in ((umlh.S_ACC_IMG, ri), (umlh.S_ACC_TXT, rt)) if live]

@@ -548,7 +548,7 @@ __global__ __launch_bounds__(256) void micro_steps_kernel(const UmlhMicroHead* _
         // per-sample scalars (identical in every slice; slice 0 writes the step's row): loss, top-1, d loss / d scale
         float vl = 0.f, vc = 0.f, vg = 0.f;
         if (valid && g == 0) {
-            vl = logf(S) + M - RY * sc;
+            vl = logf(S) + (M - RY * sc);          // the two large terms first: (logf(S) + M) rounds at the ulp of the largest logit
             vc = AM == lab ? 1.f : 0.f;
             vg = SR / S - RY;
         }
