@@ -1015,6 +1015,26 @@ int  umlh_clamp_rows(const float* x, int64_t n, int64_t d, int64_t ldx, const fl
 int  umlh_knn_accuracy(const int32_t* knn, int64_t n, int64_t m, int64_t ld, double* out, void* scratch, uint64_t scratch_bytes,
                        void* stream);
 
+/* ---- robustness test sets of the affect datasets: time-series noise on a table of the device loader below (the table layout
+ * and its envelope are that section's; this one stands in front of it because the loader section is pinned as the last). ---- */
+/* The time-series noise of the robustness test sets (MultiBench/robustness/timeseries_robust.py: white_noise, structured_drop,
+ * random_drop) on one table, src -> dst, both [n, t_len, d].  Additive to ABI v11.
+ * A unit shares one draw: unit_rows = t_len makes the unit a sample (what get_data.py:349-404 gets by handing whole tables to
+ * the noise function), unit_rows = 1 a time step; anything else is UMLH_E_INVALID.  Unit u covers the rows u * unit_rows ... of
+ * the flattened [n * t_len, d] table.  eps (double) and keep (uint8) are DEVICE arrays of n * t_len / unit_rows entries, drawn
+ * on the host in the reference's order; either may be NULL (no noise / nothing dropped).  Per element x of unit u:
+ *   keep[u] == 0          -> +0.0f, WRITTEN (an assignment as in the reference: NaN, Inf and negative values become +0.0)
+ *   otherwise, with eps   -> (float)((double)x + eps[u]): one fp64 add, one rounding (eps[u] = 0.0 turns -0.0 into +0.0)
+ *   otherwise, eps NULL   -> x, bit for bit
+ * elem_p > 0 additionally writes +0.0f to element i (flat index in the table) when keep_elem(seed, i, thresh) of the project's
+ * counter stream is false, thresh formed from elem_p as umlh_dropout forms it from p (elem_p = 1 drops every element); no
+ * rescaling.  This is random_drop; it is NOT draw-compatible with numpy, where one host uniform is drawn per element.
+ * elem_p = 0: off.  elem_p outside [0, 1] (NaN included) is UMLH_E_INVALID.
+ * dst may be src (in place); a partial overlap is UMLH_E_INVALID.  start_out (optional, int32 [n]) receives
+ * umlh_seq_first_nonzero of the RESULT, bit-equal to that function run on dst, from the same pass.  One launch, no scratch. */
+int  umlh_seq_perturb(const float* src, int64_t n, int32_t t_len, int32_t d, int32_t unit_rows, const double* eps,
+                      const uint8_t* keep, float elem_p, uint64_t seed, float* dst, int32_t* start_out, void* stream);
+
 /* ---- device loader of the affect datasets (mosi, mosei, humor, sarcasm): what Affectdataset.__getitem__ and the _process_1
  * collate of MultiBench/datasets/affect/get_data.py:159-261,418-444 do per sample and per batch on the host, as three table-build
  * passes and one step-path kernel.  Additive to ABI v11: umlh_version() is unchanged, callers detect the

@@ -154,6 +154,68 @@ __global__ __launch_bounds__(256) void sl_gather_pad(GatherArgs a, long long n, 
     }
 }
 
+// The time-series noise of the robustness test sets (reference: MultiBench/robustness/timeseries_robust.py) on one table:
+// unit u (a sample, or with PER_STEP a row) shares one host draw eps[u] and one host draw keep[u].  A workgroup takes whole
+// samples, block-strided, and streams each like sl_gather_pad: dword accesses, 2048 words per step, eight loads in flight per
+// thread before the first store.  src and dst may be the same table: a word is read and written by the same thread.  The first
+// nonzero row of the RESULT falls out of the same pass: a thread remembers its first flat index with a result != 0 (its indices
+// ascend), the workgroup takes the LDS minimum, and min(flat index) / D is the minimum row.
+// SL_PERTURB_LOADS, the dword loads in flight per thread, was measured at 4, 8, 16: 4 643 x 50 x 300 takes
+// 165 / 150 / 139 us and 4 643 x 50 x 35, whose 1 750-word samples are shorter than a 16-load step, 22.4 / 22.4 / 24.7 us.
+constexpr int SL_PERTURB_LOADS = 8;
+
+template <bool PER_STEP>
+__global__ __launch_bounds__(256) void sl_perturb(const float* src, long long n, int T, int D, const double* __restrict__ eps,
+                                                  const unsigned char* __restrict__ keep, unsigned thresh, int drop_all,
+                                                  unsigned long long seed, float* dst, int* __restrict__ start_out) {
+    __shared__ unsigned first;
+    const unsigned tid = threadIdx.x, total = (unsigned)T * (unsigned)D;
+    for (long long s = blockIdx.x; s < n; s += gridDim.x) {
+        if (tid == 0) first = total;
+        __syncthreads();
+        const long long base = s * (long long)total;
+        const float* p = src + base;
+        float* q = dst + base;
+        double e = 0.0;
+        bool kept = true;
+        if (!PER_STEP) {
+            if (eps) e = eps[s];
+            if (keep) kept = keep[s] != 0;
+        }
+        unsigned mine = total;
+        for (unsigned i0 = 0; i0 < total; i0 += 256 * SL_PERTURB_LOADS) {
+            float v[SL_PERTURB_LOADS];
+#pragma unroll
+            for (int j = 0; j < SL_PERTURB_LOADS; ++j) {
+                const unsigned i = i0 + j * 256 + tid;
+                v[j] = i < total ? p[i] : 0.0f;
+            }
+#pragma unroll
+            for (int j = 0; j < SL_PERTURB_LOADS; ++j) {
+                const unsigned i = i0 + j * 256 + tid;
+                if (i >= total) continue;
+                if (PER_STEP) {
+                    const long long u = s * T + (long long)(i / (unsigned)D);
+                    if (eps) e = eps[u];
+                    if (keep) kept = keep[u] != 0;
+                }
+                float r = v[j];
+                if (eps) r = (float)((double)r + e);              // one fp64 add, one rounding
+                if (!kept) r = 0.0f;                              // an assignment: NaN, Inf and -x become +0.0
+                if (drop_all || (thresh && !keep_elem(seed, (unsigned long long)(base + i), thresh))) r = 0.0f;
+                q[i] = r;
+                if (r != 0.0f && i < mine) mine = i;              // true for NaN, false for -0.0
+            }
+        }
+        if (start_out) {
+            if (mine < total) atomicMin(&first, mine);            // LDS
+            __syncthreads();
+            if (tid == 0) start_out[s] = first < total ? (int)(first / (unsigned)D) : T;
+        }
+        __syncthreads();                                          // `first` is reset by the next sample
+    }
+}
+
 struct ColnormPlan { int chunks; long long partial, total; };
 
 ColnormPlan colnorm_plan(long long rows, int d) {
@@ -211,6 +273,16 @@ int umlh_seqload_launch_gather_pad(const float* const* srcs, const int* dims, in
     const long long chunks = ((long long)t_out * d_max + SL_WG_WORDS - 1) / SL_WG_WORDS;
     const dim3 grid((unsigned)std::min<long long>(chunks, SL_MAX_CHUNKS), (unsigned)B, UMLH_SEQ_GATHER_MAX_SOURCES);
     hipLaunchKernelGGL(sl_gather_pad, grid, dim3(256), 0, st, a, n, T, start, ids, t_out, lengths);
+    return (int)hipGetLastError();
+}
+
+int umlh_seqload_launch_perturb(const float* src, long long n, int T, int D, int per_step, const double* eps, const unsigned char* keep,
+                                float elem_p, unsigned long long seed, float* dst, int* start_out, hipStream_t st) {
+    const unsigned thresh = elem_p < 1.f ? umlh_enc_drop_thresh(elem_p) : 0u;       // as umlh_dropout forms it; p = 1 drops all
+    const int drop_all = elem_p >= 1.f;
+    const dim3 grid((unsigned)std::min<long long>(n, 1 << 16));
+    if (per_step) hipLaunchKernelGGL(sl_perturb<true>, grid, dim3(256), 0, st, src, n, T, D, eps, keep, thresh, drop_all, seed, dst, start_out);
+    else hipLaunchKernelGGL(sl_perturb<false>, grid, dim3(256), 0, st, src, n, T, D, eps, keep, thresh, drop_all, seed, dst, start_out);
     return (int)hipGetLastError();
 }
 

@@ -242,6 +242,9 @@ int umlh_seqload_launch_znorm(float* x, long long n, int T, int d, const int* st
 // srcs, dims, outs: host arrays of n_src entries; a NULL source is skipped
 int umlh_seqload_launch_gather_pad(const float* const* srcs, const int* dims, int n_src, long long n, int T, const int* start,
                                    const long long* ids, int B, int t_out, float* const* outs, long long* lengths, hipStream_t st);
+// per_step: the unit of one eps / keep draw is a row (else a sample); eps, keep and start_out may be NULL; dst may be src
+int umlh_seqload_launch_perturb(const float* src, long long n, int T, int D, int per_step, const double* eps, const unsigned char* keep,
+                                float elem_p, unsigned long long seed, float* dst, int* start_out, hipStream_t st);
 
 // ---- umlh_api.cpp, for umlh_encoder.cpp ----
 // out[M,N] (ldo == N) = epilogue(A B^T) with the operand layouts of umlh_gemm_f32.  `splits` K-slabs go to `slabs`

@@ -1170,3 +1170,21 @@ int umlh_seq_gather_pad(const float* const* srcs, const int32_t* dims, int32_t n
     HIPCHK(umlh_seqload_launch_gather_pad(srcs, dims, n_src, n, t_len, start, ll(ids), b, t_out, outs, ll(lengths), (hipStream_t)stream), who);
     return UMLH_OK;
 }
+
+// ---- robustness test sets: time-series noise on a table of the loader (after the loader's section here: it shares its checks) ----
+int umlh_seq_perturb(const float* src, int64_t n, int32_t t_len, int32_t d, int32_t unit_rows, const double* eps, const uint8_t* keep,
+                     float elem_p, uint64_t seed, float* dst, int32_t* start_out, void* stream) {
+    const char* who = "umlh_seq_perturb";
+    if (!src || !dst) return fail(UMLH_E_INVALID, "%s: null pointer (src and dst are required)", who);
+    RC(check_seq_table(who, n, t_len, d));
+    if (unit_rows != t_len && unit_rows != 1)
+        return fail(UMLH_E_INVALID, "%s: unit_rows=%d (need t_len=%d, one draw per sample, or 1, one per time step)", who, unit_rows, t_len);
+    if (!(elem_p >= 0.f && elem_p <= 1.f)) return fail(UMLH_E_INVALID, "%s: elem_p=%g outside [0, 1]", who, (double)elem_p);
+    const uintptr_t a = reinterpret_cast<uintptr_t>(src), b = reinterpret_cast<uintptr_t>(dst);
+    const uintptr_t bytes = (uintptr_t)n * (uintptr_t)t_len * (uintptr_t)d * sizeof(float);
+    if (a != b && a < b + bytes && b < a + bytes)
+        return fail(UMLH_E_INVALID, "%s: dst overlaps src partially (in place needs dst == src)", who);
+    HIPCHK(umlh_seqload_launch_perturb(src, n, t_len, d, unit_rows == 1 && t_len != 1, eps, keep, elem_p, seed, dst, start_out,
+                                       (hipStream_t)stream), who);
+    return UMLH_OK;
+}

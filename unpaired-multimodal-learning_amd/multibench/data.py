@@ -21,6 +21,12 @@ Declared differences from the reference:
     column is exactly 0.
   * ``aligned=False``, ``flatten_time_series``, ``max_pad`` (``_process_2``), ``task='classification'`` and ``robust_test`` raise
     NotImplementedError; the mimic loader is not part of this.
+
+``robust_loaders`` is the time-series part of the reference's ``robust_test=True`` (get_data.py:349-404): per
+noise level the test split after the drop, Gaussian noise and structured drop on vision, on audio, or on all three tables (host
+draws in the reference's order, one ``umlh_seq_perturb`` launch per table), then the build above on the noisy tables -- the
+second drop, ``vision_norm`` and the front trim see the noise.  The flag itself stays refused: the reference's return under it
+begins with the text family, which needs raw words and GloVe vectors.
 """
 from __future__ import annotations
 
@@ -51,6 +57,10 @@ def _refuse_unsupported(who, options):
             raise TypeError(f"{who}: unexpected argument {name!r}")
         if name == "task" and value == "regression":          # the reference treats 'regression' as None (get_data.py:239)
             continue
+        if name == "robust_test" and value:
+            raise NotImplementedError(f"{who}: robust_test={value!r} is not implemented: the reference's return under that flag "
+                                      "begins with the text family (raw words and GloVe).  The time-series families are "
+                                      "multibench.data.robust_loaders")
         if value != _DEFAULTS[name]:
             raise NotImplementedError(f"{who}: {name}={value!r} is not implemented (only {name}={_DEFAULTS[name]!r}: the "
                                       "aligned, unflattened _process_1 path of get_data.py)")
@@ -73,7 +83,6 @@ class AffectTable:
     kept samples, as in the reference.  The build reads ``start`` back once; that is its only synchronisation."""
 
     def __init__(self, split, data_type="mosi", z_norm=False, vision_norm=False, device=None, **options):
-        from umlh import seqload
         _refuse_unsupported("AffectTable", options)
         arrays = [np.asarray(split[m]) for m in MODALITIES]
         for m, a in zip(MODALITIES, arrays):
@@ -87,8 +96,25 @@ class AffectTable:
         self.device, self.data_type, self.t_len = _device(device), data_type, t_len
         with torch.cuda.device(self.device):
             tables = [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(self.device) for a in arrays]
+        self._build(tables, labels.reshape(n_all), np.asarray(split["id"]) if "id" in split else None, z_norm, vision_norm)
+
+    @classmethod
+    def _from_device(cls, tables, labels, ids, data_type="mosi", z_norm=False, vision_norm=False, start=None, positions=None):
+        """The build from three fp32 device tables [n, T, D_m], which it may modify in place (``robust_loaders``: the noisy
+        tables of one level).  ``labels`` [n] and ``ids`` are host arrays; ``start`` is the text's first-nonzero rows when the
+        caller has them already; ``positions`` maps a row of the tables to its position in the split (``kept``)."""
+        self = cls.__new__(cls)
+        self.device, self.data_type, self.t_len = tables[0].device, data_type, tables[0].shape[1]
+        self._build(list(tables), labels, ids, z_norm, vision_norm, start, positions)
+        return self
+
+    def _build(self, tables, labels, ids, z_norm, vision_norm, start=None, positions=None):
+        from umlh import seqload
+        n_all, t_len = tables[0].shape[0], self.t_len
+        with torch.cuda.device(self.device):
             tables[1].masked_fill_(tables[1] == float("-inf"), 0.0)                   # get_data.py:182
-            start = seqload.first_nonzero(tables[2])
+            if start is None:
+                start = seqload.first_nonzero(tables[2])
             start_host = start.cpu().numpy()                                          # the build's one synchronisation
             keep = np.flatnonzero(start_host < t_len)
             if keep.size == 0:
@@ -102,14 +128,15 @@ class AffectTable:
             if z_norm:                                                                # get_data.py:223-226
                 for t in tables:
                     seqload.standardize_(t, start)
-        self.tables, self.start, self.kept = tables, start, keep
+        self.tables, self.start = tables, start
+        self.kept = keep if positions is None else np.asarray(positions)[keep]
         self.dims = tuple(t.shape[2] for t in tables)
         self.lengths = (t_len - start_host[keep]).astype(np.int64)
-        lab = labels.reshape(n_all)[keep]
-        if data_type in ("humor", "sarcasm"):                                         # get_data.py:238-243, task=None
+        lab = labels[keep]
+        if self.data_type in ("humor", "sarcasm"):                                    # get_data.py:238-243, task=None
             lab = np.where(lab < 1, -1.0, 1.0)
         self.labels = torch.from_numpy(np.ascontiguousarray(lab, dtype=np.float32)).view(-1, 1)
-        self.ids = np.asarray(split["id"])[keep] if "id" in split else None
+        self.ids = ids[keep] if ids is not None else None
 
     def __len__(self):
         return int(self.kept.size)
@@ -263,6 +290,105 @@ def get_dataloader(data, batch_size=32, train_shuffle=True, data_type="mosi", z_
     g = torch.Generator().manual_seed(42) if train_shuffle else None
     return (SequenceLoader(tables["train"], batch_size, shuffle=train_shuffle, generator=g),
             SequenceLoader(tables["valid"], batch_size), SequenceLoader(tables["test"], batch_size))
+
+
+ROBUST_FAMILIES = {"robust_vision": ((0,), 10.0), "robust_audio": ((1,), 10.0), "robust_timeseries": ((0, 1, 2), 30.0)}
+
+
+class _RobustLevels:
+    """The loaders of one family, level by level.  The clean test tables after the first drop stay on the device; a level's
+    noisy table is built when its loader is first asked for and only the latest one is kept."""
+
+    def __init__(self, base, labels, ids, positions, start, draws, noisy, per_step, batch_size, build):
+        self.base, self.labels, self.ids, self.positions, self.start = base, labels, ids, positions, start
+        self.draws, self.noisy, self.per_step, self.batch_size, self.build = draws, noisy, per_step, batch_size, build
+        self._last = (None, None)
+
+    def __len__(self):
+        return len(self.draws)
+
+    def table(self, level):
+        """The AffectTable of one level (get_data.py:349-404 for that level, then Affectdataset)."""
+        from umlh import seqload
+        if self._last[0] == level:
+            return self._last[1]
+        self._last = (None, None)                               # release the previous level before this one is built
+        dev = self.base[0].device
+        tables, start = [], self.start
+        with torch.cuda.device(dev):
+            for m, x in enumerate(self.base):
+                if m not in self.noisy:
+                    tables.append(x.clone())                    # the build works in place
+                    continue
+                eps, keep = self.draws[level][self.noisy.index(m)]
+                if m == 2:                                      # the trim and the second drop come from the noisy text
+                    start = torch.empty(x.shape[0], dtype=torch.int32, device=dev)
+                tables.append(seqload.perturb(x, None if eps is None else torch.from_numpy(eps).to(dev),
+                                              None if keep is None else torch.from_numpy(keep).to(dev), per_step=self.per_step,
+                                              start_out=start if m == 2 else None))
+        table = AffectTable._from_device(tables, self.labels, self.ids, start=start, positions=self.positions, **self.build)
+        self._last = (level, table)
+        return table
+
+    def __getitem__(self, level):
+        if isinstance(level, slice):
+            return [self[i] for i in range(len(self))[level]]
+        level = int(level)
+        if level < 0:
+            level += len(self)
+        if not 0 <= level < len(self):
+            raise IndexError(level)
+        return SequenceLoader(self.table(level), self.batch_size)
+
+
+def robust_loaders(data, family, batch_size=32, data_type="mosi", z_norm=False, vision_norm=False, device=None, levels=10,
+                   rng=None, per_step=False):
+    """The noisy test sets of one family of the reference's ``get_dataloader(robust_test=True)`` (get_data.py:349-404):
+    a sequence of ``levels`` unshuffled SequenceLoaders over the test split of ``data`` (the dict of splits or its pickle's
+    path).  ``family``: 'robust_vision' / 'robust_audio' (that modality at noise level i / 10, the others clean) or
+    'robust_timeseries' (all three in one call at i / 30: the draws are eps for vision, audio, text, then the drops for
+    vision, audio, text); 'robust_text' needs raw words and GloVe vectors and raises NotImplementedError.
+    Per level: the test split after the drop of text-less samples, Gaussian noise and structured drop with one draw per
+    sample (``per_step``: per time step, see ``multibench.robustness``), then the normal build -- the second drop, ``-inf``,
+    ``vision_norm`` and the front trim all see the noisy tables.  ``rng``: a numpy RandomState, an int seed, or None for numpy's
+    global state (the reference).  All host draws happen here, in level order; a level's table is built when its loader is
+    first asked for."""
+    from umlh import seqload
+    from .robustness import draw_timeseries_noise
+    if family == "robust_text":
+        raise NotImplementedError("robust_loaders: 'robust_text' needs the raw words and GloVe vectors of the test split "
+                                  "(text_robust.py, get_rawtext, _glove_embeddings); only the time-series families are implemented")
+    if family not in ROBUST_FAMILIES:
+        raise ValueError(f"robust_loaders: unknown family {family!r} (known: {sorted(ROBUST_FAMILIES)})")
+    if not isinstance(data, dict):
+        with open(data, "rb") as f:
+            data = pickle.load(f)
+    split = data["test"]
+    noisy, scale = ROBUST_FAMILIES[family]
+    arrays = [np.asarray(split[m]) for m in MODALITIES]
+    if any(a.ndim != 3 or a.shape[:2] != arrays[0].shape[:2] or min(a.shape) < 1 for a in arrays):
+        raise ValueError(f"robust_loaders: the test split's tables have shapes {[a.shape for a in arrays]}; expected [N, T, D_m]")
+    n_all, t_len = arrays[0].shape[:2]
+    dev = _device(device)
+    with torch.cuda.device(dev):                                # the first drop; audio keeps its -inf: noise comes before that
+        base = [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev) for a in arrays]
+        start = seqload.first_nonzero(base[2])
+        kept = np.flatnonzero(start.cpu().numpy() < t_len)
+        if kept.size == 0:
+            raise ValueError("robust_loaders: every test sample's text is all zero")
+        if kept.size < n_all:
+            idx = torch.from_numpy(kept).to(dev)
+            base = [t.index_select(0, idx) for t in base]
+            start = start.index_select(0, idx).contiguous()
+    if isinstance(rng, (int, np.integer)):
+        rng = np.random.RandomState(int(rng))                   # one stream for all levels
+    counts = [(int(kept.size), t_len) if per_step else int(kept.size) for _ in noisy]
+    dtypes = [arrays[m].dtype for m in noisy]
+    draws = [draw_timeseries_noise(counts, i / scale, True, True, rng, dtypes) for i in range(int(levels))]
+    labels = np.asarray(split["labels"]).reshape(-1)[kept]
+    ids = np.asarray(split["id"])[kept] if "id" in split else None
+    return _RobustLevels(base, labels, ids, kept, start, draws, list(noisy), per_step, batch_size,
+                         {"data_type": data_type, "z_norm": z_norm, "vision_norm": vision_norm})
 
 
 def build_run(ds_name, data, zdim, modality="xy", lr=1e-4, infoNCE_loss=False, pos_embd=False, pos_learnable=False, device=None):

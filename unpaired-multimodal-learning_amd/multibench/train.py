@@ -13,7 +13,8 @@ and compared by ``umlh.align`` and ``umlh.paired_cosine`` (``multibench.capture`
 norms, ``loss_private`` and ``diff_next_*`` the forward already returns.
 ``rollout`` (train.py:268-292) generates every step of every row in one launch of ``umlh.rollout_rows``; ``spectral_bias`` /
 ``analyze_spectral_bias`` (train.py:245-266) take their spectra from ``umlh.seq_spectrum``; ``train(rollout_spectra=True)`` is
-the reference's block train.py:474-482.  The covariance matrices the reference forms and drops (train.py:386,388) and wandb
+the reference's block train.py:474-482.  ``evaluate_robustness`` scores the probes ``evaluate`` fits on the noisy test sets of
+``multibench.data.robust_loaders``, level by level.  The covariance matrices the reference forms and drops (train.py:386,388) and wandb
 itself are outside this port."""
 from __future__ import annotations
 
@@ -159,6 +160,32 @@ def evaluate_raw_data(config, ds_name="mosi", device=None, return_probes=False, 
     return (results, emb, pr.clfs) if return_probes else results
 
 
+def _embed_split(model, batches, dev, who="evaluate"):
+    """One split through the eval-mode model and the masked mean (train.py:104-141): the pooled [N, zx + zy] device matrix,
+    the (loss_x, loss_y) means over its batches as device doubles, and (zx, zy).  Everything is enqueued, nothing read back;
+    the caller holds ``torch.no_grad`` and the device."""
+    import umlh
+    outs, lens = [], []
+    for b in batches:
+        x, y, lx, ly = b[0][0], b[0][2], b[1][0].to(dev), b[1][2].to(dev)
+        outs.append(model(x.to(dev), y.to(dev), x_lengths=lx, y_lengths=ly))
+        lens.append((lx, ly))
+    z = (outs[0]["zx"].shape[-1], outs[0]["zy"].shape[-1])
+    if z[0] != z[1]:
+        raise ValueError(f"{who}: zx and zy have different widths {z}; the modality-separation probe stacks them")
+    n = sum(o["zx"].shape[0] for o in outs)
+    emb = torch.empty((n, z[0] + z[1]), dtype=torch.float32, device=dev)
+    off = 0
+    for o, (lx, ly) in zip(outs, lens):
+        bs = o["zx"].shape[0]
+        umlh.masked_mean(o["zx"], lx, out=emb[off:off + bs, :z[0]])
+        umlh.masked_mean(o["zy"], ly, out=emb[off:off + bs, z[0]:])
+        off += bs
+    loss = (torch.stack([o["loss_x"].reshape(()) for o in outs]).double().mean(),
+            torch.stack([o["loss_y"].reshape(()) for o in outs]).double().mean())
+    return emb, loss, z
+
+
 @torch.no_grad()
 def evaluate(model, config, ds_name="mosi", device="cuda:0", return_embeddings=False, classifier_types=("logistic",), label_fn=None):
     """The reference's evaluate (train.py:93-240) with its batch layout and result keys.  The model forward is this
@@ -176,7 +203,6 @@ def evaluate(model, config, ds_name="mosi", device="cuda:0", return_embeddings=F
     integer labels, for a dataset name the reference raises on ('mimic' and its 6 classes) or a caller's own task.  With more
     than two classes in the train labels the x / y / xy logistic probes are ``umlh.SoftmaxProbe``s; the modality-separation
     probe stays binary."""
-    import umlh
     if label_fn is None:
         _label_fn(ds_name)
     classifier_types = tuple(classifier_types)
@@ -189,24 +215,7 @@ def evaluate(model, config, ds_name="mosi", device="cuda:0", return_embeddings=F
     emb, loss, z = {}, {}, None
     with torch.cuda.device(dev):
         for t in _TYPES:
-            outs, lens = [], []
-            for b in config[t]:
-                x, y, lx, ly = b[0][0], b[0][2], b[1][0].to(dev), b[1][2].to(dev)
-                outs.append(model(x.to(dev), y.to(dev), x_lengths=lx, y_lengths=ly))
-                lens.append((lx, ly))
-            z = (outs[0]["zx"].shape[-1], outs[0]["zy"].shape[-1])
-            if z[0] != z[1]:
-                raise ValueError(f"evaluate: zx and zy have different widths {z}; the modality-separation probe stacks them")
-            n = sum(o["zx"].shape[0] for o in outs)
-            emb[t] = torch.empty((n, z[0] + z[1]), dtype=torch.float32, device=dev)
-            off = 0
-            for o, (lx, ly) in zip(outs, lens):
-                bs = o["zx"].shape[0]
-                umlh.masked_mean(o["zx"], lx, out=emb[t][off:off + bs, :z[0]])
-                umlh.masked_mean(o["zy"], ly, out=emb[t][off:off + bs, z[0]:])
-                off += bs
-            loss[t] = (torch.stack([o["loss_x"].reshape(()) for o in outs]).double().mean(),
-                       torch.stack([o["loss_y"].reshape(()) for o in outs]).double().mean())
+            emb[t], loss[t], z = _embed_split(model, config[t], dev)
         pr = _Probes(ds_name, dev, n_classes)
         for t in _TYPES:                                            # which modality a pooled embedding came from (train.py:146-151)
             n = emb[t].shape[0]
@@ -223,6 +232,63 @@ def evaluate(model, config, ds_name="mosi", device="cuda:0", return_embeddings=F
     results.update({"val/loss_x": losses[0], "test/loss_x": losses[1], "val/loss_y": losses[2], "test/loss_y": losses[3]})
     if return_embeddings:
         return results, emb, pr.clfs
+    return results
+
+
+@torch.no_grad()
+def evaluate_robustness(model, config, robust, ds_name="mosi", device="cuda:0", classifier_types=("logistic",), label_fn=None):
+    """Score curves over noise levels: what the reference's robustness protocol asks of a trained model (test sets corrupted
+    at increasing levels, get_data.py:349-404), with ``evaluate``'s embeddings and probes.  ``config`` is ``evaluate``'s config
+    (only 'train' is read); ``robust`` maps a family name to a sequence over levels of batch lists or loaders
+    (``multibench.data.robust_loaders``).  The x / y / xy probes are fitted once on the clean train embeddings, exactly as
+    ``evaluate`` fits them; every level's batches then go through the eval-mode forward and the masked mean and are scored with
+    those fitted probes.  Levels are consumed one at a time (a lazily built loader's table is released with the next one);
+    all scores are read back at once, the losses in a second read.
+    Returns ``robust/{family}/score_x``, ``score_y``, ``score_xy``, ``loss_x``, ``loss_y`` as lists over the levels, ``n`` the
+    rows per level (drops shrink it), and ``mean_score_x`` / ``_y`` / ``_xy``, the plain mean over the levels.  With several
+    ``classifier_types`` a later one overwrites an earlier one's scores, as in ``evaluate``."""
+    if label_fn is None:
+        _label_fn(ds_name)
+    classifier_types = tuple(classifier_types)
+    for ct in classifier_types:
+        if ct not in ("logistic", "knn"):
+            raise ValueError(f"Unsupported classifier type: {ct}")
+    dev = torch.device(device)
+    model.eval()
+    lab = {"train": _labels01(config["train"], ds_name, label_fn)}
+    emb, loss, keys = {}, [], []
+    with torch.cuda.device(dev):
+        emb["train"], _loss, z = _embed_split(model, config["train"], dev, "evaluate_robustness")
+        for family, levels in robust.items():
+            for i in range(len(levels)):
+                batches = levels[i]
+                batches = batches if isinstance(batches, list) else list(batches)
+                key = (family, i)
+                lab[key] = _labels01(batches, ds_name, label_fn)
+                emb[key], l_xy, _z = _embed_split(model, batches, dev, "evaluate_robustness")
+                loss.extend(l_xy)
+                keys.append(key)
+                del batches
+        lab, n_classes = _class_labels(lab, label_fn)
+        pr = _Probes(ds_name, dev, n_classes)
+        ytr = torch.from_numpy(lab["train"]).to(dev)
+        for ct in classifier_types:
+            for name, cols in (("x", slice(0, z[0])), ("y", slice(z[0], z[0] + z[1])), ("xy", slice(0, z[0] + z[1]))):
+                clf = pr.fit(emb["train"][:, cols], ytr, ct)
+                for family, i in keys:
+                    pr.score(f"{family}/{i}/{name}", clf, emb[(family, i)][:, cols], torch.from_numpy(lab[(family, i)]).to(dev))
+        got = pr.read()
+        losses = torch.stack(loss).cpu().tolist() if loss else []
+    results = {}
+    for family, levels in robust.items():
+        idx = [j for j, k in enumerate(keys) if k[0] == family]
+        for name in ("x", "y", "xy"):
+            scores = [got[f"{family}/{keys[j][1]}/{name}"] for j in idx]
+            results[f"robust/{family}/score_{name}"] = scores
+            results[f"robust/{family}/mean_score_{name}"] = float(np.mean(scores)) if scores else float("nan")
+        results[f"robust/{family}/loss_x"] = [losses[2 * j] for j in idx]
+        results[f"robust/{family}/loss_y"] = [losses[2 * j + 1] for j in idx]
+        results[f"robust/{family}/n"] = [int(emb[keys[j]].shape[0]) for j in idx]
     return results
 
 

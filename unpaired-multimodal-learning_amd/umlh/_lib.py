@@ -234,6 +234,8 @@ def _prototypes() -> dict:
         "umlh_abs_kth": (rc, (vp, i64, i64, i64, i64, vp, vp, u64, vp)),
         "umlh_clamp_rows": (rc, (vp, i64, i64, i64, vp, i32, vp, i64, vp)),
         "umlh_knn_accuracy": (rc, (vp, i64, i64, i64, vp, vp, u64, vp)),
+        # robustness test sets: time-series noise on a table of the device loader
+        "umlh_seq_perturb": (rc, (vp, i64, i32, i32, i32, vp, vp, f32, u64, vp, vp, vp)),
         # device loader of the affect datasets: first nonzero row, column and per-sequence standardisation, batch gather-pad
         "umlh_seq_first_nonzero": (rc, (vp, i64, i32, i32, vp, vp)),
         "umlh_seq_column_standardize_scratch": (u64, (i64, i32)),

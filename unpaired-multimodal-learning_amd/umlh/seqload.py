@@ -1,7 +1,7 @@
 """The kernels of the affect datasets' device loader (umlh_kernels_seqload.hip; C ABI: ``umlh_seq_first_nonzero``,
-``umlh_seq_column_standardize``, ``umlh_seq_standardize``, ``umlh_seq_gather_pad``) as thin torch wrappers: what
-MultiBench/datasets/affect/get_data.py does per sample (front trim, vision_norm, z_norm) and per batch (_process_1's
-pad_sequence) on the host.  Every call enqueues on ``torch.cuda.current_stream`` and returns device tensors; nothing is read
+``umlh_seq_column_standardize``, ``umlh_seq_standardize``, ``umlh_seq_gather_pad``, ``umlh_seq_perturb``) as thin torch
+wrappers: what MultiBench/datasets/affect/get_data.py does per sample (front trim, vision_norm, z_norm) and per batch
+(_process_1's pad_sequence) on the host, and the time-series noise of its robustness test sets.  Every call enqueues on ``torch.cuda.current_stream`` and returns device tensors; nothing is read
 back.  There is no CPU compute path.  The loader built on them is ``multibench.data``."""
 from __future__ import annotations
 
@@ -73,6 +73,39 @@ def standardize_(x: torch.Tensor, start: torch.Tensor) -> torch.Tensor:
         check(load_library().umlh_seq_standardize(x.data_ptr(), n, T, d, start.data_ptr(), glue.stream(x.device)),
               "umlh_seq_standardize")
     return x
+
+
+def _draws(a, dtype, units: int, dev: torch.device, name: str):
+    if a is None:
+        return 0
+    if not isinstance(a, torch.Tensor) or a.dtype != dtype or a.device != dev or a.numel() != units or not a.is_contiguous():
+        raise ValueError(f"perturb: {name} must be a contiguous {dtype} tensor of {units} entries on {dev}")
+    return a.data_ptr()
+
+
+def perturb(x: torch.Tensor, eps: torch.Tensor | None = None, keep: torch.Tensor | None = None, per_step: bool = False,
+            elem_p: float = 0.0, seed: int = 0, out: torch.Tensor | None = None, start_out: torch.Tensor | None = None):
+    """The reference's time-series noise (robustness/timeseries_robust.py) on the [n, T, d] table ``x``, one launch.  A unit is
+    a sample, or a time step with ``per_step``; ``eps`` (float64) and ``keep`` (uint8) are device tensors with one entry per
+    unit (n, or n * T), either may be None.  A unit with ``keep == 0`` is written as +0.0; otherwise an element becomes
+    ``float32(float64(x) + eps[u])`` (``x`` itself, bit for bit, without ``eps``).  ``elem_p > 0`` also zeroes element i of the
+    counter stream ``seed`` with that probability (the reference's random_drop; not numpy's draws).  ``out=x`` works in place;
+    default: a new table.  ``start_out`` (int32 [n]) receives ``first_nonzero`` of the result from the same pass.
+    Returns ``out``."""
+    x = _table(x, "perturb")
+    n, T, d = x.shape
+    out = torch.empty_like(x) if out is None else _table(out, "perturb (out)")
+    if out.shape != x.shape or out.device != x.device:
+        raise ValueError(f"perturb: out {tuple(out.shape)} on {out.device} for x {tuple(x.shape)} on {x.device}")
+    units = n * T if per_step else n
+    eps_p = _draws(eps, torch.float64, units, x.device, "eps")
+    keep_p = _draws(keep, torch.uint8, units, x.device, "keep")
+    start_p = 0 if start_out is None else _start(start_out, n, x.device, "perturb").data_ptr()
+    with torch.cuda.device(x.device):
+        check(load_library().umlh_seq_perturb(x.data_ptr(), n, T, d, 1 if per_step else T, eps_p, keep_p, float(elem_p),
+                                              int(seed) & 0xFFFFFFFFFFFFFFFF, out.data_ptr(), start_p, glue.stream(x.device)),
+              "umlh_seq_perturb")
+    return out
 
 
 def gather_pad(sources, start: torch.Tensor, ids: torch.Tensor, t_out: int, outs=None, lengths: torch.Tensor | None = None):
