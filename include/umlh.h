@@ -1035,6 +1035,55 @@ int  umlh_knn_accuracy(const int32_t* knn, int64_t n, int64_t m, int64_t ld, dou
 int  umlh_seq_perturb(const float* src, int64_t n, int32_t t_len, int32_t d, int32_t unit_rows, const double* eps,
                       const uint8_t* keep, float elem_p, uint64_t seed, float* dst, int32_t* start_out, void* stream);
 
+/* ---- MIMIC loader: table build, tabular noise and batches of MultiBench/datasets/mimic/get_data.py and
+ * MultiBench/robustness/tabular_robust.py (kernels: umlh_kernels_tabular.hip).  Additive to ABI v11.  In
+ * front of the affect loader's section for the same reason as the one above.  Every argument check happens before any HIP call
+ * and names the function and the argument; everything runs on `stream`; no atomics on global memory: results are bitwise
+ * reproducible across calls and streams. ---- */
+/* get_data.py:38-51 in one call, on a [rows, d] matrix x (row r at x + r*ldx; float, or double with x_is_f64 = 1):
+ *   v = x[r, c], or +0.0 where x[r, c] is NaN or +-Inf                   (X[isinf] = 0; X[isnan] = 0)
+ *   stats[c] = mean_r v,  stats[d + c] = sqrt(mean_r (v - stats[c])^2)   (population std, as np.std; 2 d device doubles)
+ *   out[r*ldo + c] = (float)((v - stats[c]) / stats[d + c])              (v in the source's precision: one fp64 subtraction,
+ *                                                                         one fp64 division, one rounding)
+ * The sums are those of umlh_seq_column_standardize: fp64, per row chunk and then in chunk order, on the same column-sum core
+ * and the same plan -- on a float source without non-finite values stats and out equal that function's bit for bit.  A zero
+ * std is NOT special-cased: 0 / 0 = NaN and v / 0 = +-Inf, as numpy gives.  out == x (with ldo == ldx) works in place for a
+ * float source; any other overlap of out with a float x, and any overlap with a double x, is UMLH_E_INVALID.  x itself is
+ * never written otherwise (the reference cleans its arrays in place).  Five launches, no host sync.  Envelope as umlh_seq_column_standardize: 1 <= rows < 2^40,
+ * 1 <= d <= 2^20, ldx >= d, ldo >= d; scratch 8-byte aligned.  The size query does not end in _scratch_bytes (a closed family). */
+uint64_t umlh_tab_standardize_scratch(int64_t rows, int32_t d);                  /* bytes; 0 on invalid arguments */
+int  umlh_tab_standardize(const void* x, int32_t x_is_f64, int64_t rows, int32_t d, int64_t ldx, float* out, int64_t ldo,
+                          double* stats, void* scratch, uint64_t scratch_bytes, void* stream);
+
+/* add_tabular_noise (tabular_robust.py:7-52) on src [n, d] -> dst [n, d], fp32, row strides lds and ldd.  Per row i:
+ *   1. drop:   v[j] = drop[i*d + j] ? +0.0f : src[i, j]      (an assignment: NaN, Inf and negative values become +0.0)
+ *   2. carry:  out[0] = v[0];  out[j] = carry[i*(d-1) + j-1] ? out[j-1] : v[j]   for j >= 1
+ * Step 2 is what the reference's swap_entry DOES.  Despite its name it swaps nothing: `data[i][j] = data[i][j-1]` copies the
+ * already updated left neighbour to the right, and its second assignment `data[i][j-1] = data[i][j]` writes back the value it
+ * has just read.  out[j] is therefore the dropped value of the last column <= j that does not carry: a prefix maximum over
+ * column indices, not a serial chain.  Rows of at most 64 columns take a thread each; wider rows take a wave each with a scan
+ * per 64-column chunk, the last result carried into the next chunk.  Everything else moves bit for bit (NaN payloads, -0.0).
+ * drop ([n, d]) and carry ([n, d-1]) are DEVICE uint8 arrays drawn on the host in the reference's order (all of drop_entry's
+ * uniforms, then all of swap_entry's); either may be NULL; with d = 1 carry is not read.  Counter-stream mode: with drop NULL
+ * and p_drop > 0 element (i, j) drops when keep_elem(seed, i*d + j, thresh(p_drop)) of the project's counter stream is false,
+ * thresh as umlh_dropout forms it (p = 1 takes every element); with carry NULL and p_carry > 0 column j >= 1 carries by the
+ * same rule on seed + 1.  This mode is NOT draw-compatible with numpy.  A given mask wins over its p.  p outside [0, 1] (NaN
+ * included) is UMLH_E_INVALID.  dst may be src with ldd == lds (in place); any other overlap is UMLH_E_INVALID.
+ * Envelope: 1 <= n < 2^31, 1 <= d <= 2^20, lds >= d, ldd >= d.  One launch, no scratch. */
+int  umlh_tab_perturb(const float* src, int64_t n, int32_t d, int64_t lds, const uint8_t* drop, const uint8_t* carry, float p_drop,
+                      float p_carry, uint64_t seed, float* dst, int64_t ldd, void* stream);
+
+/* One launch forms a batch from tables of different row widths (MIMIC: the static table, 5 words per sample, and the flattened
+ * series, 24 * 12 = 288).  srcs, widths, outs are HOST arrays of n_src <= UMLH_SEQ_GATHER_MAX_SOURCES entries: source m is a
+ * dense fp32 table [n, widths[m]], outs[m] a dense block [b, widths[m]]; a NULL source is skipped (its widths and outs
+ * entries are not read), at least one must be given.  ids is int64 device memory [b]:
+ *   outs[m][j, :] = srcs[m][ids[j], :], bit for bit;   a zero row for an id outside [0, n), which is never used as an address.
+ * Repeated ids are fine.  Nothing is written outside the b * widths[m] words of a block.  Envelope: 1 <= b <= 65535,
+ * 1 <= widths[m] < 2^31, 1 <= n < 2^31.  The step-path kernel of the MIMIC loader, as umlh_seq_gather_pad is the affect
+ * loader's (that one needs one t_len for all its sources). */
+int  umlh_rows_gather(const float* const* srcs, const int32_t* widths, int32_t n_src, int64_t n, const int64_t* ids, int32_t b,
+                      float* const* outs, void* stream);
+
 /* ---- device loader of the affect datasets (mosi, mosei, humor, sarcasm): what Affectdataset.__getitem__ and the _process_1
  * collate of MultiBench/datasets/affect/get_data.py:159-261,418-444 do per sample and per batch on the host, as three table-build
  * passes and one step-path kernel.  Additive to ABI v11: umlh_version() is unchanged, callers detect the

@@ -31,7 +31,7 @@
 
 namespace {
 
-constexpr int SL_STAT_CHUNKS = 256;       // row chunks of the column statistics
+constexpr int SL_STAT_CHUNKS = UMLH_COLSTAT_CHUNKS;   // row chunks of the column statistics (shared with umlh_kernels_tabular.hip)
 constexpr int SL_WG_WORDS = 1024;         // words one workgroup of the gather moves per step (4 per thread)
 constexpr int SL_MAX_CHUNKS = 64;         // most workgroups along one (sample, source) block of the gather
 
@@ -238,6 +238,11 @@ int umlh_seqload_launch_first_row(const float* x, long long n, int T, int D, int
     return (int)hipGetLastError();
 }
 
+int umlh_seqload_launch_stats_final(const double* partial, long long rows, int d, int chunks, int pass, double* stats, hipStream_t st) {
+    hipLaunchKernelGGL(sl_stats_final, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, st, partial, rows, d, chunks, pass, stats);
+    return (int)hipGetLastError();
+}
+
 int umlh_seqload_launch_colnorm(const float* x, long long rows, int d, long long ldx, float* out, long long ldo, double* stats,
                                 void* scratch, hipStream_t st) {
     const ColnormPlan p = colnorm_plan(rows, d);
@@ -245,8 +250,7 @@ int umlh_seqload_launch_colnorm(const float* x, long long rows, int d, long long
     const dim3 grid((unsigned)((d + 63) / 64), (unsigned)p.chunks);
     for (int pass = 0; pass < 2; ++pass) {                    // pass 1 reads the means pass 0 wrote
         hipLaunchKernelGGL(sl_colsum, grid, dim3(256), 0, st, x, rows, d, ldx, p.chunks, pass ? (const double*)stats : nullptr, partial);
-        hipLaunchKernelGGL(sl_stats_final, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, st, (const double*)partial, rows, d, p.chunks,
-                           pass, stats);
+        umlh_seqload_launch_stats_final(partial, rows, d, p.chunks, pass, stats, st);
     }
     const long long blocks = (rows * d + 255) / 256;
     hipLaunchKernelGGL(sl_col_apply, dim3((unsigned)std::min<long long>(blocks, 1 << 16)), dim3(256), 0, st, x, rows, d, ldx,

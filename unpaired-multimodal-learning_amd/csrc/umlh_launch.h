@@ -11,6 +11,7 @@
 inline long long align_up(long long x) { return (x + 255) / 256 * 256; }
 template <class T>
 inline T* at(void* scratch, long long off) { return reinterpret_cast<T*>(static_cast<char*>(scratch) + off); }
+constexpr int UMLH_COLSTAT_CHUNKS = 256;       // most row chunks of the fp64 column statistics of the device loaders
 struct ScratchLayout {                 // regions of one scratch block, each on a 256-byte boundary
     long long end;
     explicit ScratchLayout(long long start = 0) : end(start) {}      // start: a multiple of 256
@@ -235,6 +236,10 @@ int umlh_outlier_launch_clamp(const float* x, long long n, int d, long long ldx,
 int umlh_outlier_launch_accuracy(const int* knn, long long n, long long m, long long ld, double* out, void* scratch, hipStream_t st);
 // ---- umlh_kernels_seqload.hip: device loader of the affect datasets (first nonzero row, two standardisations, batch gather-pad) ----
 unsigned long long umlh_seqload_colnorm_bytes(long long rows, int d);
+// the final kernel of the column statistics: the `chunks` partials of every column in chunk order -> stats[c] = mean (pass 0),
+// stats[d + c] = population std (pass 1).  Shared with umlh_kernels_tabular.hip, whose plan is the same min(rows,
+// UMLH_COLSTAT_CHUNKS) row chunks in one region of doubles
+int umlh_seqload_launch_stats_final(const double* partial, long long rows, int d, int chunks, int pass, double* stats, hipStream_t st);
 int umlh_seqload_launch_first_row(const float* x, long long n, int T, int D, int* start, hipStream_t st);
 int umlh_seqload_launch_colnorm(const float* x, long long rows, int d, long long ldx, float* out, long long ldo, double* stats,
                                 void* scratch, hipStream_t st);
@@ -245,6 +250,16 @@ int umlh_seqload_launch_gather_pad(const float* const* srcs, const int* dims, in
 // per_step: the unit of one eps / keep draw is a row (else a sample); eps, keep and start_out may be NULL; dst may be src
 int umlh_seqload_launch_perturb(const float* src, long long n, int T, int D, int per_step, const double* eps, const unsigned char* keep,
                                 float elem_p, unsigned long long seed, float* dst, int* start_out, hipStream_t st);
+// ---- umlh_kernels_tabular.hip: MIMIC loader (standardisation of a cleaned float / double table, tabular noise, row gather) ----
+// scratch: umlh_seqload_colnorm_bytes(rows, d)
+int umlh_tab_launch_standardize(const void* x, int x_is_f64, long long rows, int d, long long ldx, float* out, long long ldo,
+                                double* stats, void* scratch, hipStream_t st);
+// drop [n, d] and carry [n, d - 1] may be NULL: then p_drop / p_carry of the counter streams seed / seed + 1; dst may be src
+int umlh_tab_launch_perturb(const float* src, long long n, int d, long long lds, const unsigned char* drop, const unsigned char* carry,
+                            float p_drop, float p_carry, unsigned long long seed, float* dst, long long ldd, hipStream_t st);
+// srcs, widths, outs: host arrays of n_src entries; a NULL source is skipped
+int umlh_tab_launch_gather(const float* const* srcs, const int* widths, int n_src, long long n, const long long* ids, int B,
+                           float* const* outs, hipStream_t st);
 
 // ---- umlh_api.cpp, for umlh_encoder.cpp ----
 // out[M,N] (ldo == N) = epilogue(A B^T) with the operand layouts of umlh_gemm_f32.  `splits` K-slabs go to `slabs`

@@ -26,7 +26,7 @@ static inline long long* ll(int64_t* p) { return reinterpret_cast<long long*>(p)
 // on a 256-byte boundary from the base (align_up, umlh_launch.h), so the base decides the alignment of every slab.
 // The policy records what each entry point has always checked; it is not derived from the layouts, and the entry points keep it:
 //   8 bytes  umlh_probe_fit (fp64 solver state), umlh_row_abs_quantile (fp64 partials), umlh_abs_kth (u64 histogram),
-//            umlh_knn_accuracy (int64 partials), umlh_seq_column_standardize (fp64 partials);
+//            umlh_knn_accuracy (int64 partials), umlh_seq_column_standardize and umlh_tab_standardize (fp64 partials);
 //   4 bytes  umlh_knn_search, umlh_eval_topk (float scores and int indices of the top-k core, nothing wider);
 //   none     everything else.  Of these umlh_align_knn (float / int) and umlh_class_index (int counts) need 4 bytes and
 //            umlh_seq_mse_backward takes a float*; the others carve fp64 or int64 slabs (Gram and column sums, partial sums,
@@ -1186,5 +1186,76 @@ int umlh_seq_perturb(const float* src, int64_t n, int32_t t_len, int32_t d, int3
         return fail(UMLH_E_INVALID, "%s: dst overlaps src partially (in place needs dst == src)", who);
     HIPCHK(umlh_seqload_launch_perturb(src, n, t_len, d, unit_rows == 1 && t_len != 1, eps, keep, elem_p, seed, dst, start_out,
                                        (hipStream_t)stream), who);
+    return UMLH_OK;
+}
+
+// ---- MIMIC loader: standardisation of a cleaned table, tabular noise, row gather (kernels: umlh_kernels_tabular.hip; after the
+// loader's section here, as the robustness section above: it shares its checks) ----
+// bytes [a, a + na) and [b, b + nb) share at least one byte
+static bool ranges_overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + nb && y < x + na;
+}
+
+uint64_t umlh_tab_standardize_scratch(int64_t rows, int32_t d) {
+    return colnorm_shape_ok(rows, d) ? umlh_seqload_colnorm_bytes(rows, d) : 0;
+}
+
+int umlh_tab_standardize(const void* x, int32_t x_is_f64, int64_t rows, int32_t d, int64_t ldx, float* out, int64_t ldo, double* stats,
+                         void* scratch, uint64_t scratch_bytes, void* stream) {
+    const char* who = "umlh_tab_standardize";
+    if (!x || !out || !stats || !scratch) return fail(UMLH_E_INVALID, "%s: null pointer (x, out, stats and scratch are required)", who);
+    if (x_is_f64 != 0 && x_is_f64 != 1) return fail(UMLH_E_INVALID, "%s: x_is_f64=%d (0: a float source, 1: a double source)", who, x_is_f64);
+    if (!colnorm_shape_ok(rows, d))
+        return fail(UMLH_E_INVALID, "%s: rows=%lld d=%d (need 1 <= rows < 2^40, 1 <= d <= %d)", who, (long long)rows, d, SEQ_MAX_COLS);
+    if (ldx < d) return fail(UMLH_E_INVALID, "%s: ldx=%lld < d=%d", who, (long long)ldx, d);
+    if (ldo < d) return fail(UMLH_E_INVALID, "%s: ldo=%lld < d=%d", who, (long long)ldo, d);
+    if (x_is_f64) {
+        if (ranges_overlap(x, ((uint64_t)(rows - 1) * ldx + d) * sizeof(double), out, ((uint64_t)(rows - 1) * ldo + d) * sizeof(float)))
+            return fail(UMLH_E_INVALID, "%s: out aliases the double source x (in place needs a float source)", who);
+    } else if (out == x) {
+        if (ldo != ldx) return fail(UMLH_E_INVALID, "%s: in place needs ldo == ldx (ldo=%lld ldx=%lld)", who, (long long)ldo, (long long)ldx);
+    } else if (ranges_overlap(x, ((uint64_t)(rows - 1) * ldx + d) * sizeof(float), out, ((uint64_t)(rows - 1) * ldo + d) * sizeof(float))) {
+        return fail(UMLH_E_INVALID, "%s: out overlaps x partially (in place needs out == x and ldo == ldx)", who);
+    }
+    RC(check_scratch(who, scratch, scratch_bytes, umlh_seqload_colnorm_bytes(rows, d), 8));
+    HIPCHK(umlh_tab_launch_standardize(x, x_is_f64, rows, d, ldx, out, ldo, stats, scratch, (hipStream_t)stream), who);
+    return UMLH_OK;
+}
+
+int umlh_tab_perturb(const float* src, int64_t n, int32_t d, int64_t lds, const uint8_t* drop, const uint8_t* carry, float p_drop,
+                     float p_carry, uint64_t seed, float* dst, int64_t ldd, void* stream) {
+    const char* who = "umlh_tab_perturb";
+    if (!src || !dst) return fail(UMLH_E_INVALID, "%s: null pointer (src and dst are required)", who);
+    if (n < 1 || n >= ROWS_END) return fail(UMLH_E_INVALID, "%s: n=%lld rows (need 1 <= n < 2^31)", who, (long long)n);
+    if (d < 1 || d > SEQ_MAX_COLS) return fail(UMLH_E_INVALID, "%s: d=%d outside 1..%d", who, d, SEQ_MAX_COLS);
+    if (lds < d) return fail(UMLH_E_INVALID, "%s: lds=%lld < d=%d", who, (long long)lds, d);
+    if (ldd < d) return fail(UMLH_E_INVALID, "%s: ldd=%lld < d=%d", who, (long long)ldd, d);
+    if (!(p_drop >= 0.f && p_drop <= 1.f)) return fail(UMLH_E_INVALID, "%s: p_drop=%g outside [0, 1]", who, (double)p_drop);
+    if (!(p_carry >= 0.f && p_carry <= 1.f)) return fail(UMLH_E_INVALID, "%s: p_carry=%g outside [0, 1]", who, (double)p_carry);
+    if (src == dst ? lds != ldd
+                   : ranges_overlap(src, ((uint64_t)(n - 1) * lds + d) * sizeof(float), dst, ((uint64_t)(n - 1) * ldd + d) * sizeof(float)))
+        return fail(UMLH_E_INVALID, "%s: dst overlaps src partially (in place needs dst == src and ldd == lds)", who);
+    HIPCHK(umlh_tab_launch_perturb(src, n, d, lds, drop, carry, p_drop, p_carry, seed, dst, ldd, (hipStream_t)stream), who);
+    return UMLH_OK;
+}
+
+int umlh_rows_gather(const float* const* srcs, const int32_t* widths, int32_t n_src, int64_t n, const int64_t* ids, int32_t b,
+                     float* const* outs, void* stream) {
+    const char* who = "umlh_rows_gather";
+    if (!srcs || !widths || !outs || !ids) return fail(UMLH_E_INVALID, "%s: null pointer (srcs, widths, outs and ids are required)", who);
+    if (n_src < 1 || n_src > UMLH_SEQ_GATHER_MAX_SOURCES)
+        return fail(UMLH_E_INVALID, "%s: n_src=%d outside 1..%d", who, n_src, UMLH_SEQ_GATHER_MAX_SOURCES);
+    if (n < 1 || n >= ROWS_END) return fail(UMLH_E_INVALID, "%s: n=%lld rows (need 1 <= n < 2^31)", who, (long long)n);
+    if (b < 1 || b > SEQ_MAX_BATCH) return fail(UMLH_E_INVALID, "%s: b=%d outside 1..%d", who, b, SEQ_MAX_BATCH);
+    int used = 0;
+    for (int m = 0; m < n_src; ++m) {
+        if (!srcs[m]) continue;
+        ++used;
+        if (!outs[m]) return fail(UMLH_E_INVALID, "%s: source %d has no destination", who, m);
+        if (widths[m] < 1) return fail(UMLH_E_INVALID, "%s: widths[%d]=%d (need 1 <= width < 2^31)", who, m, widths[m]);
+    }
+    if (!used) return fail(UMLH_E_INVALID, "%s: every source is NULL", who);
+    HIPCHK(umlh_tab_launch_gather(srcs, widths, n_src, n, ll(ids), b, outs, (hipStream_t)stream), who);
     return UMLH_OK;
 }

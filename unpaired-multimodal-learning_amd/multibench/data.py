@@ -20,7 +20,7 @@ Declared differences from the reference:
     constant column is not always that constant (seven rows of 0.1f give -0.926 everywhere instead of 0); here every constant
     column is exactly 0.
   * ``aligned=False``, ``flatten_time_series``, ``max_pad`` (``_process_2``), ``task='classification'`` and ``robust_test`` raise
-    NotImplementedError; the mimic loader is not part of this.
+    NotImplementedError; the mimic loader is ``multibench.mimic`` (its own config and ``build_run``: ``DATASETS`` holds the affect sets only).
 
 ``robust_loaders`` is the time-series part of the reference's ``robust_test=True`` (get_data.py:349-404): per
 noise level the test split after the drop, Gaussian noise and structured drop on vision, on audio, or on all three tables (host

@@ -20,7 +20,7 @@ PREC_IDS = {"fp32": 0, "bf16": 1}
 N_CORE_SCALARS = 8
 N_SCALARS = 12
 
-SOURCES = ["umlh_p2p.hip", "umlh_kernels_f32.hip", "umlh_kernels_bf16.hip", "umlh_kernels_micro.hip", "umlh_kernels_seq.hip", "umlh_kernels_enc.hip", "umlh_kernels_align.hip", "umlh_kernels_align_ext.hip", "umlh_kernels_probe.hip", "umlh_kernels_softmax_probe.hip", "umlh_kernels_knn.hip", "umlh_kernels_spectral.hip", "umlh_kernels_capture.hip", "umlh_kernels_stepstats.hip", "umlh_kernels_rollout.hip", "umlh_kernels_classstats.hip", "umlh_kernels_evalreport.hip", "umlh_kernels_outlier.hip", "umlh_kernels_seqload.hip", "umlh_api.cpp", "umlh_ops.cpp", "umlh_encoder.cpp"]
+SOURCES = ["umlh_p2p.hip", "umlh_kernels_f32.hip", "umlh_kernels_bf16.hip", "umlh_kernels_micro.hip", "umlh_kernels_seq.hip", "umlh_kernels_enc.hip", "umlh_kernels_align.hip", "umlh_kernels_align_ext.hip", "umlh_kernels_probe.hip", "umlh_kernels_softmax_probe.hip", "umlh_kernels_knn.hip", "umlh_kernels_spectral.hip", "umlh_kernels_capture.hip", "umlh_kernels_stepstats.hip", "umlh_kernels_rollout.hip", "umlh_kernels_classstats.hip", "umlh_kernels_evalreport.hip", "umlh_kernels_outlier.hip", "umlh_kernels_seqload.hip", "umlh_kernels_tabular.hip", "umlh_api.cpp", "umlh_ops.cpp", "umlh_encoder.cpp"]
 
 
 class UmlhError(RuntimeError):
@@ -236,6 +236,11 @@ def _prototypes() -> dict:
         "umlh_knn_accuracy": (rc, (vp, i64, i64, i64, vp, vp, u64, vp)),
         # robustness test sets: time-series noise on a table of the device loader
         "umlh_seq_perturb": (rc, (vp, i64, i32, i32, i32, vp, vp, f32, u64, vp, vp, vp)),
+        # MIMIC loader: standardisation of a cleaned float / double table, tabular noise, row gather
+        "umlh_tab_standardize_scratch": (u64, (i64, i32)),
+        "umlh_tab_standardize": (rc, (vp, i32, i64, i32, i64, vp, i64, vp, vp, u64, vp)),
+        "umlh_tab_perturb": (rc, (vp, i64, i32, i64, vp, vp, f32, f32, u64, vp, i64, vp)),
+        "umlh_rows_gather": (rc, (pv, P(i32), i32, i64, vp, i32, pv, vp)),
         # device loader of the affect datasets: first nonzero row, column and per-sequence standardisation, batch gather-pad
         "umlh_seq_first_nonzero": (rc, (vp, i64, i32, i32, vp, vp)),
         "umlh_seq_column_standardize_scratch": (u64, (i64, i32)),

@@ -2,7 +2,10 @@
 ``umlh_seq_column_standardize``, ``umlh_seq_standardize``, ``umlh_seq_gather_pad``, ``umlh_seq_perturb``) as thin torch
 wrappers: what MultiBench/datasets/affect/get_data.py does per sample (front trim, vision_norm, z_norm) and per batch
 (_process_1's pad_sequence) on the host, and the time-series noise of its robustness test sets.  Every call enqueues on ``torch.cuda.current_stream`` and returns device tensors; nothing is read
-back.  There is no CPU compute path.  The loader built on them is ``multibench.data``."""
+back.  There is no CPU compute path.  The loader built on them is ``multibench.data``.
+The second part holds the kernels of the MIMIC loader (umlh_kernels_tabular.hip; ``umlh_tab_standardize``, ``umlh_tab_perturb``,
+``umlh_rows_gather``): MultiBench/datasets/mimic/get_data.py and robustness/tabular_robust.py on [n, d] device matrices; the loader
+built on them is ``multibench.mimic``."""
 from __future__ import annotations
 
 import ctypes as C
@@ -148,3 +151,107 @@ def gather_pad(sources, start: torch.Tensor, ids: torch.Tensor, t_out: int, outs
         check(load_library().umlh_seq_gather_pad(srcs, dims, k, n, T, start.data_ptr(), ids.data_ptr(), b, t_out, dsts,
                                                  lengths.data_ptr(), glue.stream(dev)), "umlh_seq_gather_pad")
     return [o if s is not None else None for s, o in zip(sources, outs)], lengths
+
+
+# ---- MIMIC loader (umlh_kernels_tabular.hip; C ABI: umlh_tab_standardize, umlh_tab_perturb, umlh_rows_gather) ----
+def _matrix(x, what: str, dtypes=(torch.float32,)) -> torch.Tensor:
+    if not isinstance(x, torch.Tensor) or x.ndim != 2 or x.dtype not in dtypes or not x.is_cuda or x.stride(1) != 1 \
+            or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        raise ValueError(f"{what}: expected a {' / '.join(str(t) for t in dtypes)} device matrix [n, d] with unit column stride, "
+                         f"got {getattr(x, 'dtype', type(x))} {tuple(getattr(x, 'shape', ()))}")
+    if min(x.shape) < 1:
+        raise ValueError(f"{what}: empty matrix {tuple(x.shape)}")
+    return x
+
+
+def _ld(x: torch.Tensor) -> int:
+    return x.stride(0) if x.shape[0] > 1 else x.shape[1]
+
+
+def tab_standardize(x: torch.Tensor, out: torch.Tensor | None = None):
+    """get_data.py:38-51 of the MIMIC loader on the [rows, d] device matrix ``x`` (float32 or float64, row stride >= d):
+    NaN and +-Inf count as 0, then ``(x - mu) / sigma`` per column with the population std, statistics and arithmetic in fp64,
+    one rounding to fp32.  ``out=x`` works in place for a float32 ``x``; default: a new fp32 matrix.  ``x`` is not modified
+    otherwise.  Returns (out, stats) with stats the float64 device tensor [2, d] = mean | std.  A zero std is not
+    special-cased."""
+    x = _matrix(x, "tab_standardize", (torch.float32, torch.float64))
+    rows, d = x.shape
+    out = torch.empty((rows, d), dtype=torch.float32, device=x.device) if out is None else _matrix(out, "tab_standardize (out)")
+    if out.shape != x.shape or out.device != x.device:
+        raise ValueError(f"tab_standardize: out {tuple(out.shape)} on {out.device} for x {tuple(x.shape)} on {x.device}")
+    stats = torch.empty((2, d), dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        scratch, nbytes = glue.scratch("umlh_tab_standardize_scratch", x.device, rows=rows, d=d)
+        check(load_library().umlh_tab_standardize(x.data_ptr(), int(x.dtype == torch.float64), rows, d, _ld(x), out.data_ptr(),
+                                                  _ld(out), stats.data_ptr(), scratch.data_ptr(), nbytes, glue.stream(x.device)),
+              "umlh_tab_standardize")
+    return out, stats
+
+
+def _mask(a, shape, dev: torch.device, name: str):
+    if a is None:
+        return 0
+    if not isinstance(a, torch.Tensor) or a.dtype != torch.uint8 or a.device != dev or tuple(a.shape) != shape or not a.is_contiguous():
+        raise ValueError(f"tab_perturb: {name} must be a contiguous uint8 tensor {list(shape)} on {dev}")
+    return a.data_ptr()
+
+
+def tab_perturb(x: torch.Tensor, drop: torch.Tensor | None = None, carry: torch.Tensor | None = None, p_drop: float = 0.0,
+                p_carry: float = 0.0, seed: int = 0, out: torch.Tensor | None = None) -> torch.Tensor:
+    """The reference's tabular noise (robustness/tabular_robust.py) on the fp32 [n, d] device matrix ``x``, one launch:
+    ``drop`` (uint8 [n, d]) writes +0.0 where it is set, then ``carry`` (uint8 [n, d - 1], entry j - 1 for column j) copies
+    the already updated left neighbour into column j -- what the reference's swap_entry does.  Both are device tensors of host
+    draws in the reference's order; either may be None.  With a mask None, ``p_drop`` / ``p_carry`` > 0 take the decisions
+    from the project's counter streams ``seed`` / ``seed + 1`` (not numpy's draws).  ``out=x`` works in place; default: a new
+    matrix.  Returns ``out``."""
+    x = _matrix(x, "tab_perturb")
+    n, d = x.shape
+    out = torch.empty((n, d), dtype=torch.float32, device=x.device) if out is None else _matrix(out, "tab_perturb (out)")
+    if out.shape != x.shape or out.device != x.device:
+        raise ValueError(f"tab_perturb: out {tuple(out.shape)} on {out.device} for x {tuple(x.shape)} on {x.device}")
+    drop_p = _mask(drop, (n, d), x.device, "drop")
+    carry_p = _mask(carry, (n, d - 1), x.device, "carry")
+    with torch.cuda.device(x.device):
+        check(load_library().umlh_tab_perturb(x.data_ptr(), n, d, _ld(x), drop_p, carry_p, float(p_drop), float(p_carry),
+                                              int(seed) & 0xFFFFFFFFFFFFFFFF, out.data_ptr(), _ld(out), glue.stream(x.device)),
+              "umlh_tab_perturb")
+    return out
+
+
+def rows_gather(sources, ids: torch.Tensor, outs=None):
+    """One launch: the rows ``ids`` (int64 device tensor [b]) of up to three dense fp32 device tables that share n; a table
+    may have any number of trailing dimensions (its row is their flattened words) and an entry of ``sources`` may be None
+    (skipped).  Returns the blocks [b, *sources[m].shape[1:]] (None for a skipped source), ``blocks[m][j] = sources[m][ids[j]]``
+    bit for bit; an id outside [0, n) gives a zero row.  ``outs``: destinations to write into instead of new tensors."""
+    sources = list(sources)
+    given = [s for s in sources if s is not None]
+    if not 1 <= len(sources) <= MAX_SOURCES or not given:
+        raise ValueError(f"rows_gather: {len(sources)} sources, {len(given)} given (need 1..{MAX_SOURCES} with at least one given)")
+    for s in given:
+        if not isinstance(s, torch.Tensor) or s.ndim < 2 or s.dtype != torch.float32 or not s.is_cuda or not s.is_contiguous() \
+                or min(s.shape) < 1:
+            raise ValueError(f"rows_gather: expected contiguous non-empty fp32 device tables [n, ...], got "
+                             f"{getattr(s, 'dtype', type(s))} {tuple(getattr(s, 'shape', ()))}")
+    dev, n = given[0].device, given[0].shape[0]
+    if any(s.device != dev or s.shape[0] != n for s in given):
+        raise ValueError("rows_gather: the sources must share the device and n")
+    if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int64 or ids.device != dev or ids.ndim != 1 or not ids.is_contiguous():
+        raise ValueError(f"rows_gather: ids must be a contiguous int64 tensor [b] on {dev}")
+    b = ids.shape[0]
+    if not 1 <= b <= MAX_BATCH:
+        raise ValueError(f"rows_gather: b={b} (need 1 <= b <= {MAX_BATCH})")
+    if outs is None:
+        outs = [None if s is None else torch.empty((b, *s.shape[1:]), dtype=torch.float32, device=dev) for s in sources]
+    else:
+        outs = list(outs)
+        for s, o in zip(sources, outs):
+            if s is not None and (not isinstance(o, torch.Tensor) or o.dtype != torch.float32 or o.device != dev
+                                  or tuple(o.shape) != (b, *s.shape[1:]) or not o.is_contiguous()):
+                raise ValueError(f"rows_gather: out {tuple(getattr(o, 'shape', ()))} for a block {(b, *s.shape[1:])}")
+    k = len(sources)
+    srcs = (C.c_void_p * k)(*[None if s is None else s.data_ptr() for s in sources])
+    dsts = (C.c_void_p * k)(*[None if s is None else o.data_ptr() for s, o in zip(sources, outs)])
+    widths = (C.c_int32 * k)(*[0 if s is None else s[0].numel() for s in sources])
+    with torch.cuda.device(dev):
+        check(load_library().umlh_rows_gather(srcs, widths, k, n, ids.data_ptr(), b, dsts, glue.stream(dev)), "umlh_rows_gather")
+    return [o if s is not None else None for s, o in zip(sources, outs)]
