@@ -466,6 +466,20 @@ __device__ __forceinline__ bool fwd_ce_bf16_body(const FwdArgsB& a, const int bi
             const bool odd = lane & 1;
             const unsigned psel = odd ? 0x03020706u : 0x05040100u;          // bytes 0-3 = own (S1), 4-7 = neighbour (S0)
             unsigned* dzl = dzs + (4 * h + (odd ? 1 : 0)) * ZRS + (l31 >> 1);
+            // one-hot term: the label element of this sample lives in exactly one wave; its h = 0 lane
+            // recomputes e from the label logit (same fma + exp2 as pass 2) and overwrites the staged value
+            u16 hot;
+            {
+                const float ey = __builtin_amdgcn_exp2f(__builtin_fmaf(rawy_wave, asl2, -mwl));
+                const f32x2v v = {__builtin_fmaf(ey, ic, -coef), 0.f};
+                hot = (u16)(__builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2v)) & 0xffffu);
+            }
+            const int colbase = sg.col0 + row0 + ws * 32 * STW + st * 32;      // first column of this 32-sample tile
+            u16* gbase = a.dzt + ((size_t)(colbase >> 6) * a.crows) * 64 + (colbase & 63);
+            // Class tile by class tile: stage its 32 rows, patch the one-hot element if the label lies in it, store it.  The
+            // write-through stores of tile ct are in flight while tile ct+1 is scaled and packed; with all CTW tiles staged
+            // first and the 2*CTW stores issued behind them, the second-dispatched half of the workgroup (which loses the VALU
+            // arbitration) ended its stores 2.2k cycles after the first half and the tile waited for it.
 #pragma unroll
             for (int ct = 0; ct < CTW; ++ct) {
 #pragma unroll
@@ -475,31 +489,22 @@ __device__ __forceinline__ bool fwd_ce_bf16_body(const FwdArgsB& a, const int bi
                     const unsigned nbr = (unsigned)__builtin_amdgcn_update_dpp(0, (int)own, 0xB1, 0xf, 0xf, true);
                     dzl[(ct * 32 + (i & 3) + 8 * (i >> 2)) * ZRS] = __builtin_amdgcn_perm(nbr, own, psel);
                 }
-            }
-            // one-hot term: the label element of this sample lives in exactly one wave; its h = 0 lane
-            // recomputes e from the label logit (same fma + exp2 as pass 2) and overwrites the staged value
-            if (h == 0 && rel >= 0 && rel < CTW * 32) {
-                const float ey = __builtin_amdgcn_exp2f(__builtin_fmaf(rawy_wave, asl2, -mwl));
-                const f32x2v v = {__builtin_fmaf(ey, ic, -coef), 0.f};
-                const unsigned pk = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2v));
-                dzs16[rel * (2 * ZRS) + l31] = (u16)(pk & 0xffffu);
-            }
-            // wave-local transpose done (same wave wrote and reads: program order + lgkmcnt suffice).
-            // Each lane now stores 16 B = 8 columns of one class row: 16 rows x 64 B per instruction
-            // instead of 4-B scattered stores (the store tail was issue-bound, not bandwidth-bound).
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            const int colbase = sg.col0 + row0 + ws * 32 * STW + st * 32;      // first column of this 32-sample tile
-            u16* gbase = a.dzt + ((size_t)(colbase >> 6) * a.crows) * 64 + (colbase & 63);
+                if (h == 0 && rel >= ct * 32 && rel < ct * 32 + 32) dzs16[rel * (2 * ZRS) + l31] = hot;
+                // wave-local transpose done (same wave wrote and reads: program order + lgkmcnt suffice).
+                // Each lane now stores 16 B = 8 columns of one class row: 16 rows x 64 B per instruction
+                // instead of 4-B scattered stores (the store tail was issue-bound, not bandwidth-bound).
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll
-            for (int it = 0; it < CTW * 2; ++it) {
-                const int lr = it * 16 + (lane >> 2);                           // row within the wave's class range
-                const int cls = wave_c0 + lr;
-                const u32x4 v = *reinterpret_cast<const u32x4*>(dzs + lr * ZRS + (lane & 3) * 4);
-                if (cls < C) {
-                    if (!a.plain) store_wt_b128(gbase + (size_t)cls * 64 + (lane & 3) * 8, v);
-                    else *reinterpret_cast<u32x4*>(gbase + (size_t)cls * 64 + (lane & 3) * 8) = v;
+                for (int it = 2 * ct; it < 2 * ct + 2; ++it) {
+                    const int lr = it * 16 + (lane >> 2);                       // row within the wave's class range
+                    const int cls = wave_c0 + lr;
+                    const u32x4 v = *reinterpret_cast<const u32x4*>(dzs + lr * ZRS + (lane & 3) * 4);
+                    if (cls < C) {
+                        if (!a.plain) store_wt_b128(gbase + (size_t)cls * 64 + (lane & 3) * 8, v);
+                        else *reinterpret_cast<u32x4*>(gbase + (size_t)cls * 64 + (lane & 3) * 8) = v;
+                    }
                 }
             }
             if (STW > 1) __builtin_amdgcn_wave_barrier();                      // next tile reuses the staging slice
