@@ -134,6 +134,52 @@ def test_rng_none_consumes_the_global_state():
         np.random.set_state(state)
 
 
+@pytest.mark.parametrize("counts", [[5, 5, 5], [(5, 4)] * 3], ids=["per_sample", "per_step"])
+@pytest.mark.parametrize("as_state", [False, True], ids=["int_seed", "RandomState"])
+def test_inner_draws_on_a_resolved_stream_equal_the_public_function(counts, as_state):
+    """``robust_loaders`` and ``draw_mimic_noise`` resolve their stream once and call the inner function level after level:
+    it must draw what ``draw_timeseries_noise`` draws, and leave the stream where that leaves it."""
+    from multibench.robustness import _draw, _rng, draw_timeseries_noise
+    seed, dtypes = 77, [np.float32, np.float64, np.float32]
+    pub = np.random.RandomState(seed) if as_state else seed
+    inner = _rng(np.random.RandomState(seed) if as_state else seed)
+    assert isinstance(inner, np.random.RandomState) and _rng(inner) is inner and _rng(None) is np.random
+    for p, gauss, drop in ((0.3, True, True), (0.5, True, False), (0.5, False, True)):
+        want = draw_timeseries_noise(counts, p, gauss, drop, pub, dtypes)
+        got = _draw(inner, counts, p, gauss, drop, dtypes)
+        if not as_state:                                         # an int seed starts the public function afresh at every call
+            inner = _rng(seed)
+        for (e1, k1), (e2, k2) in zip(got, want):
+            assert (e1 is None) == (e2 is None) == (not gauss) and (k1 is None) == (k2 is None) == (not drop)
+            assert e1 is None or (e1.dtype == e2.dtype and e1.shape == e2.shape and e1.tobytes() == e2.tobytes())
+            assert k1 is None or (k1.dtype == k2.dtype and k1.shape == k2.shape and k1.tobytes() == k2.tobytes())
+    if as_state:                                                 # three calls on one stream: the same state afterwards
+        assert np.array_equal(inner.get_state()[1], pub.get_state()[1]) and inner.get_state()[2] == pub.get_state()[2]
+    ref = np.random.RandomState(seed)                            # and after one call, the state of a stream that drew as much
+    draw_timeseries_noise(counts, 0.3, rng=ref, table_dtype=dtypes)
+    one = _rng(seed)
+    _draw(one, counts, 0.3, True, True, dtypes)
+    assert np.array_equal(one.get_state()[1], ref.get_state()[1]) and one.get_state()[2] == ref.get_state()[2]
+
+
+def test_draw_mimic_noise_equals_the_recorded_draws(golden_dir):
+    """tests/golden/mimic_draws.npz was drawn by the code before the draw function was split (scripts/make_golden_mimic_draws.py):
+    one stream through all levels, per level drop, carry, eps, elem, keep."""
+    import os
+    from multibench.mimic import draw_mimic_noise
+    with np.load(os.path.join(golden_dir, "mimic_draws.npz"), allow_pickle=False) as z:
+        want = {k: z[k] for k in z.files}
+    assert len(want) == 15
+    for rng in (11, np.random.RandomState(11)):
+        drawn = draw_mimic_noise(7, levels=3, rng=rng)
+        assert len(drawn) == 3
+        for k, lv in enumerate(drawn):
+            for key in ("drop", "carry", "eps", "elem", "keep"):
+                w = want[f"{k}/{key}"]
+                assert lv[key].dtype == w.dtype and lv[key].shape == w.shape and lv[key].tobytes() == w.tobytes(), (k, key)
+    assert any(want[f"{k}/drop"].any() for k in (1, 2)) and want["2/eps"].any()        # the recording is not a trivial one
+
+
 # ---- wrong statements ----
 def _caught(fx, variant, cases):
     return any(not _equal(_restated(fx, case, li, variant), RR.noise_outputs(fx, case, li)) for case in cases for li in (0, 1, 2))

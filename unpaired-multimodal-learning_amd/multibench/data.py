@@ -8,7 +8,9 @@ text-less samples, ``audio[audio == -inf] = 0``, ``vision_norm``, the front trim
 so ``multibench.train.train`` / ``evaluate`` / ``evaluate_raw_data`` and ``multibench.capture.take_fixed_samples`` take them
 unchanged: blocks and lengths are device tensors, ``inds`` and ``labels`` host tensors (the consumers move them where they
 need them; nothing is read back).  ``SequenceSampler`` is the batch order, pure host code that follows torch's DataLoader
-protocol draw for draw, so a run here visits the samples in the reference's order.
+protocol draw for draw, so a run here visits the samples in the reference's order.  ``DeviceLoader`` (sampler, epoch driver,
+deep copy) and ``LevelSequence`` (the lazy sequence of loaders over noise levels) are what this loader shares with
+``multibench.mimic``, as are the pickle opener and the model builder of ``build_run``.
 
 Declared differences from the reference:
   * drop: a sample is dropped when its text has no nonzero element; the reference drops on ``text.sum() == 0``.  A text whose
@@ -72,6 +74,45 @@ def _device(device):
     return torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
 
 
+def _open_pickle(data):
+    """``data`` itself when it is the unpickled dict, else the dict in the pickle at that path."""
+    if isinstance(data, dict):
+        return data
+    with open(data, "rb") as f:
+        return pickle.load(f)
+
+
+def _affect_arrays(split):
+    """The three arrays of a split, and the index of the first that is not [N, T, D] with vision's N and T (None: all are)."""
+    arrays = [np.asarray(split[m]) for m in MODALITIES]
+    bad = [m for m, a in enumerate(arrays) if a.ndim != 3 or a.shape[:2] != arrays[0].shape[:2] or min(a.shape) < 1]
+    return arrays, bad[0] if bad else None
+
+
+def _upload(arrays, dev):
+    return [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev) for a in arrays]
+
+
+def _drop_textless(tables, start, none_left):
+    """drop_entry (get_data.py:27-44) on three device tables [n, T, D_m]: the samples whose text has a nonzero element.
+    ``start``: the text's first-nonzero rows when the caller has them already.  Returns the kept tables, their ``start``, the
+    kept positions and the kept lengths T - start (host arrays); ``none_left`` is the error text when nothing is kept.  The
+    read-back of ``start`` is the one synchronisation; the caller holds the device."""
+    from umlh import seqload
+    n_all, t_len = tables[0].shape[:2]
+    if start is None:
+        start = seqload.first_nonzero(tables[2])
+    start_host = start.cpu().numpy()
+    keep = np.flatnonzero(start_host < t_len)
+    if keep.size == 0:
+        raise ValueError(none_left)
+    if keep.size < n_all:
+        idx = torch.from_numpy(keep).to(tables[0].device)
+        tables = [t.index_select(0, idx) for t in tables]
+        start = start.index_select(0, idx).contiguous()
+    return tables, start, keep, (t_len - start_host[keep]).astype(np.int64)
+
+
 class AffectTable:
     """One split of an affect pickle on the device.  ``split``: the unpickled dict with 'vision', 'audio', 'text' as
     [N, T, D_m] numpy arrays and 'labels' (and 'id'); it is not modified.
@@ -84,18 +125,17 @@ class AffectTable:
 
     def __init__(self, split, data_type="mosi", z_norm=False, vision_norm=False, device=None, **options):
         _refuse_unsupported("AffectTable", options)
-        arrays = [np.asarray(split[m]) for m in MODALITIES]
-        for m, a in zip(MODALITIES, arrays):
-            if a.ndim != 3 or a.shape[:2] != arrays[0].shape[:2] or min(a.shape) < 1:
-                raise ValueError(f"AffectTable: {m} has shape {a.shape}; expected [N, T, D] with the N and T of vision "
-                                 f"{arrays[0].shape[:2]}")
+        arrays, bad = _affect_arrays(split)
+        if bad is not None:
+            raise ValueError(f"AffectTable: {MODALITIES[bad]} has shape {arrays[bad].shape}; expected [N, T, D] with the N and T "
+                             f"of vision {arrays[0].shape[:2]}")
         labels = np.asarray(split["labels"])
         n_all, t_len = arrays[0].shape[:2]
         if labels.shape[0] != n_all or labels.size != n_all:
             raise NotImplementedError(f"AffectTable: labels of shape {labels.shape} for {n_all} samples (one value per sample)")
         self.device, self.data_type, self.t_len = _device(device), data_type, t_len
         with torch.cuda.device(self.device):
-            tables = [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(self.device) for a in arrays]
+            tables = _upload(arrays, self.device)
         self._build(tables, labels.reshape(n_all), np.asarray(split["id"]) if "id" in split else None, z_norm, vision_norm)
 
     @classmethod
@@ -110,20 +150,10 @@ class AffectTable:
 
     def _build(self, tables, labels, ids, z_norm, vision_norm, start=None, positions=None):
         from umlh import seqload
-        n_all, t_len = tables[0].shape[0], self.t_len
         with torch.cuda.device(self.device):
             tables[1].masked_fill_(tables[1] == float("-inf"), 0.0)                   # get_data.py:182
-            if start is None:
-                start = seqload.first_nonzero(tables[2])
-            start_host = start.cpu().numpy()                                          # the build's one synchronisation
-            keep = np.flatnonzero(start_host < t_len)
-            if keep.size == 0:
-                raise ValueError("AffectTable: every sample's text is all zero")
-            if keep.size < n_all:                                                     # drop_entry, get_data.py:27-44
-                idx = torch.from_numpy(keep).to(self.device)
-                tables = [t.index_select(0, idx) for t in tables]
-                start = start.index_select(0, idx).contiguous()
-            if vision_norm:                                                           # get_data.py:185-191
+            tables, start, keep, self.lengths = _drop_textless(tables, start, "AffectTable: every sample's text is all zero")
+            if vision_norm:                                                          # get_data.py:185-191
                 seqload.column_standardize(tables[0], out=tables[0])
             if z_norm:                                                                # get_data.py:223-226
                 for t in tables:
@@ -131,7 +161,6 @@ class AffectTable:
         self.tables, self.start = tables, start
         self.kept = keep if positions is None else np.asarray(positions)[keep]
         self.dims = tuple(t.shape[2] for t in tables)
-        self.lengths = (t_len - start_host[keep]).astype(np.int64)
         lab = labels[keep]
         if self.data_type in ("humor", "sarcasm"):                                    # get_data.py:238-243, task=None
             lab = np.where(lab < 1, -1.0, 1.0)
@@ -221,24 +250,17 @@ class SequenceSampler:
         return SequenceSampler(self.n, self.batch_size, self.shuffle, _copy_generator(self.generator))
 
 
-class SequenceLoader:
-    """Batches of an ``AffectTable`` in the ``_process_1`` layout: ``([v, a, t], [lv, la, lt], inds, labels)`` with fp32 device
-    blocks [b, Lmax, D_m] (Lmax = the longest trimmed sequence of that batch, zero padding behind every sequence), int64 device
-    lengths [b], ``inds`` int64 [b, 1] and ``labels`` float32 [b, 1] on the host.  Entries of ``modalities`` (indices into
-    vision, audio, text) that are not requested are None in both lists; the requested ones share one lengths tensor (the trim
-    is common to the three modalities).
+class DeviceLoader:
+    """What the device loaders share: a ``SequenceSampler`` for the order and the epoch driver.  An epoch uploads nothing
+    before its first batch is asked for; then the order is known, ``_prepare(order)`` (int64 host tensor, the epoch's whole
+    index stream) makes the epoch's device ids and host slices once, and ``_batch(epoch, i, lo, hi)`` yields batch ``i``, the
+    entries ``lo:hi`` of the order, from what ``_prepare`` returned.  ``iter_index()`` runs the same epoch as host id lists.
+    ``copy.deepcopy`` shares everything but the sampler, whose generator state it copies (``take_fixed_samples`` and
+    ``train``'s effective-rank sample iterate deep copies of their loaders)."""
 
-    An epoch uploads its order once, at the first batch, and then enqueues one ``umlh_seq_gather_pad`` launch per batch on the
-    current stream; the host side of a batch is three slices.  ``iter_index()`` runs the same epoch as host id lists.
-    ``copy.deepcopy`` shares the table and copies the generator's state (``take_fixed_samples`` and ``train``'s effective-rank
-    sample iterate deep copies of their loaders)."""
-
-    def __init__(self, table, batch_size, shuffle=False, generator=None, modalities=(0, 1, 2)):
-        self.table, self.batch_size = table, int(batch_size)
-        self.modalities = tuple(sorted(set(int(m) for m in modalities)))
-        if not self.modalities or self.modalities[0] < 0 or self.modalities[-1] > 2:
-            raise ValueError(f"SequenceLoader: modalities={modalities!r} (indices into vision, audio, text)")
-        self.sampler = SequenceSampler(len(table), batch_size, shuffle, generator)
+    def __init__(self, n, batch_size, shuffle, generator):
+        self.batch_size = int(batch_size)
+        self.sampler = SequenceSampler(n, batch_size, shuffle, generator)
 
     @property
     def generator(self):
@@ -254,81 +276,69 @@ class SequenceLoader:
         return self._epoch(iter(self.sampler))                # the base-seed draw happens here, not at the first batch
 
     def _epoch(self, batches):
-        from umlh import seqload
-        tb, bs = self.table, self.batch_size
-        sources = [tb.tables[m] if m in self.modalities else None for m in range(3)]
-        order = order_dev = labels = t_out = None
+        bs, epoch = self.batch_size, None
         for i, ids in enumerate(batches):
-            if order is None:                                 # the epoch's order is known now: one upload, host slices prepared
-                order = torch.tensor(batches.order, dtype=torch.int64)
-                order_dev = order.to(tb.device)
-                labels = tb.labels[order]
-                t_out = np.maximum.reduceat(tb.lengths[batches.order], np.arange(0, len(order), bs))
-            lo, hi = i * bs, i * bs + len(ids)
-            blocks, lengths = seqload.gather_pad(sources, tb.start, order_dev[lo:hi], int(t_out[i]))
-            yield blocks, [None if b is None else lengths for b in blocks], order[lo:hi].view(-1, 1), labels[lo:hi]
+            if epoch is None:                                 # the epoch's order is known now: one upload, host slices prepared
+                epoch = self._prepare(torch.tensor(batches.order, dtype=torch.int64))
+            yield self._batch(epoch, i, i * bs, i * bs + len(ids))
 
     def __deepcopy__(self, memo):
-        c = SequenceLoader.__new__(SequenceLoader)
-        c.table, c.batch_size, c.modalities = self.table, self.batch_size, self.modalities
+        c = copy.copy(self)
         c.sampler = copy.deepcopy(self.sampler, memo)
         return c
 
 
-def get_dataloader(data, batch_size=32, train_shuffle=True, data_type="mosi", z_norm=False, vision_norm=False, device=None,
-                   **options):
-    """The reference's ``get_dataloader`` (get_data.py:268-416): ``(train, valid, test)`` SequenceLoaders.  ``data``: the
-    ``{'train', 'valid', 'test'}`` dict of splits, or the path of its pickle.  The train loader shuffles with a generator seeded
-    42 when ``train_shuffle`` (get_data.py:313-319); valid and test run in order.  Every split is normalised with its own
-    statistics, as there."""
-    _refuse_unsupported("get_dataloader", options)
-    if not isinstance(data, dict):
-        with open(data, "rb") as f:
-            data = pickle.load(f)
-    tables = {s: AffectTable(data[s], data_type=data_type, z_norm=z_norm, vision_norm=vision_norm, device=device)
-              for s in ("train", "valid", "test")}
-    g = torch.Generator().manual_seed(42) if train_shuffle else None
-    return (SequenceLoader(tables["train"], batch_size, shuffle=train_shuffle, generator=g),
-            SequenceLoader(tables["valid"], batch_size), SequenceLoader(tables["test"], batch_size))
+class SequenceLoader(DeviceLoader):
+    """Batches of an ``AffectTable`` in the ``_process_1`` layout: ``([v, a, t], [lv, la, lt], inds, labels)`` with fp32 device
+    blocks [b, Lmax, D_m] (Lmax = the longest trimmed sequence of that batch, zero padding behind every sequence), int64 device
+    lengths [b], ``inds`` int64 [b, 1] and ``labels`` float32 [b, 1] on the host.  Entries of ``modalities`` (indices into
+    vision, audio, text) that are not requested are None in both lists; the requested ones share one lengths tensor (the trim
+    is common to the three modalities).
+
+    An epoch uploads its order once, at the first batch, and then enqueues one ``umlh_seq_gather_pad`` launch per batch on the
+    current stream; the host side of a batch is three slices."""
+
+    def __init__(self, table, batch_size, shuffle=False, generator=None, modalities=(0, 1, 2)):
+        self.table = table
+        self.modalities = tuple(sorted(set(int(m) for m in modalities)))
+        if not self.modalities or self.modalities[0] < 0 or self.modalities[-1] > 2:
+            raise ValueError(f"SequenceLoader: modalities={modalities!r} (indices into vision, audio, text)")
+        super().__init__(len(table), batch_size, shuffle, generator)
+
+    def _prepare(self, order):
+        from umlh import seqload
+        tb = self.table
+        sources = [tb.tables[m] if m in self.modalities else None for m in range(3)]
+        t_out = np.maximum.reduceat(tb.lengths[order.numpy()], np.arange(0, len(order), self.batch_size))
+        return seqload.gather_pad, sources, order, order.to(tb.device), tb.labels[order], t_out
+
+    def _batch(self, epoch, i, lo, hi):
+        gather_pad, sources, order, order_dev, labels, t_out = epoch
+        blocks, lengths = gather_pad(sources, self.table.start, order_dev[lo:hi], int(t_out[i]))
+        return blocks, [None if b is None else lengths for b in blocks], order[lo:hi].view(-1, 1), labels[lo:hi]
 
 
-ROBUST_FAMILIES = {"robust_vision": ((0,), 10.0), "robust_audio": ((1,), 10.0), "robust_timeseries": ((0, 1, 2), 30.0)}
+class LevelSequence:
+    """A lazy sequence of loaders over noise levels.  ``build(level)`` makes one level's tables from ``base``, the clean
+    device tables, which stay; ``loader(built)`` is an unshuffled loader over what it returned.  A level is built when its
+    loader is first asked for, and only the latest one is kept: the previous level is released before the next is built.
+    ``table(level)`` / ``tables(level)`` give what ``build`` made for that level (from the cache when it is the latest)."""
 
-
-class _RobustLevels:
-    """The loaders of one family, level by level.  The clean test tables after the first drop stay on the device; a level's
-    noisy table is built when its loader is first asked for and only the latest one is kept."""
-
-    def __init__(self, base, labels, ids, positions, start, draws, noisy, per_step, batch_size, build):
-        self.base, self.labels, self.ids, self.positions, self.start = base, labels, ids, positions, start
-        self.draws, self.noisy, self.per_step, self.batch_size, self.build = draws, noisy, per_step, batch_size, build
+    def __init__(self, n, build, loader, base=None):
+        self._n, self._build, self._loader, self.base = int(n), build, loader, base
         self._last = (None, None)
 
     def __len__(self):
-        return len(self.draws)
+        return self._n
 
     def table(self, level):
-        """The AffectTable of one level (get_data.py:349-404 for that level, then Affectdataset)."""
-        from umlh import seqload
         if self._last[0] == level:
             return self._last[1]
         self._last = (None, None)                               # release the previous level before this one is built
-        dev = self.base[0].device
-        tables, start = [], self.start
-        with torch.cuda.device(dev):
-            for m, x in enumerate(self.base):
-                if m not in self.noisy:
-                    tables.append(x.clone())                    # the build works in place
-                    continue
-                eps, keep = self.draws[level][self.noisy.index(m)]
-                if m == 2:                                      # the trim and the second drop come from the noisy text
-                    start = torch.empty(x.shape[0], dtype=torch.int32, device=dev)
-                tables.append(seqload.perturb(x, None if eps is None else torch.from_numpy(eps).to(dev),
-                                              None if keep is None else torch.from_numpy(keep).to(dev), per_step=self.per_step,
-                                              start_out=start if m == 2 else None))
-        table = AffectTable._from_device(tables, self.labels, self.ids, start=start, positions=self.positions, **self.build)
-        self._last = (level, table)
-        return table
+        self._last = (level, self._build(level))
+        return self._last[1]
+
+    tables = table
 
     def __getitem__(self, level):
         if isinstance(level, slice):
@@ -338,7 +348,25 @@ class _RobustLevels:
             level += len(self)
         if not 0 <= level < len(self):
             raise IndexError(level)
-        return SequenceLoader(self.table(level), self.batch_size)
+        return self._loader(self.table(level))
+
+
+def get_dataloader(data, batch_size=32, train_shuffle=True, data_type="mosi", z_norm=False, vision_norm=False, device=None,
+                   **options):
+    """The reference's ``get_dataloader`` (get_data.py:268-416): ``(train, valid, test)`` SequenceLoaders.  ``data``: the
+    ``{'train', 'valid', 'test'}`` dict of splits, or the path of its pickle.  The train loader shuffles with a generator seeded
+    42 when ``train_shuffle`` (get_data.py:313-319); valid and test run in order.  Every split is normalised with its own
+    statistics, as there."""
+    _refuse_unsupported("get_dataloader", options)
+    data = _open_pickle(data)
+    tables = {s: AffectTable(data[s], data_type=data_type, z_norm=z_norm, vision_norm=vision_norm, device=device)
+              for s in ("train", "valid", "test")}
+    g = torch.Generator().manual_seed(42) if train_shuffle else None
+    return (SequenceLoader(tables["train"], batch_size, shuffle=train_shuffle, generator=g),
+            SequenceLoader(tables["valid"], batch_size), SequenceLoader(tables["test"], batch_size))
+
+
+ROBUST_FAMILIES = {"robust_vision": ((0,), 10.0), "robust_audio": ((1,), 10.0), "robust_timeseries": ((0, 1, 2), 30.0)}
 
 
 def robust_loaders(data, family, batch_size=32, data_type="mosi", z_norm=False, vision_norm=False, device=None, levels=10,
@@ -353,42 +381,54 @@ def robust_loaders(data, family, batch_size=32, data_type="mosi", z_norm=False, 
     ``vision_norm`` and the front trim all see the noisy tables.  ``rng``: a numpy RandomState, an int seed, or None for numpy's
     global state (the reference).  All host draws happen here, in level order; a level's table is built when its loader is
     first asked for."""
-    from umlh import seqload
-    from .robustness import draw_timeseries_noise
+    from .robustness import _draw, _perturb, _rng
     if family == "robust_text":
         raise NotImplementedError("robust_loaders: 'robust_text' needs the raw words and GloVe vectors of the test split "
                                   "(text_robust.py, get_rawtext, _glove_embeddings); only the time-series families are implemented")
     if family not in ROBUST_FAMILIES:
         raise ValueError(f"robust_loaders: unknown family {family!r} (known: {sorted(ROBUST_FAMILIES)})")
-    if not isinstance(data, dict):
-        with open(data, "rb") as f:
-            data = pickle.load(f)
-    split = data["test"]
+    split = _open_pickle(data)["test"]
     noisy, scale = ROBUST_FAMILIES[family]
-    arrays = [np.asarray(split[m]) for m in MODALITIES]
-    if any(a.ndim != 3 or a.shape[:2] != arrays[0].shape[:2] or min(a.shape) < 1 for a in arrays):
+    arrays, bad = _affect_arrays(split)
+    if bad is not None:
         raise ValueError(f"robust_loaders: the test split's tables have shapes {[a.shape for a in arrays]}; expected [N, T, D_m]")
-    n_all, t_len = arrays[0].shape[:2]
+    t_len = arrays[0].shape[1]
     dev = _device(device)
     with torch.cuda.device(dev):                                # the first drop; audio keeps its -inf: noise comes before that
-        base = [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev) for a in arrays]
-        start = seqload.first_nonzero(base[2])
-        kept = np.flatnonzero(start.cpu().numpy() < t_len)
-        if kept.size == 0:
-            raise ValueError("robust_loaders: every test sample's text is all zero")
-        if kept.size < n_all:
-            idx = torch.from_numpy(kept).to(dev)
-            base = [t.index_select(0, idx) for t in base]
-            start = start.index_select(0, idx).contiguous()
-    if isinstance(rng, (int, np.integer)):
-        rng = np.random.RandomState(int(rng))                   # one stream for all levels
+        base, clean_start, kept, _ = _drop_textless(_upload(arrays, dev), None, "robust_loaders: every test sample's text is all zero")
+    g = _rng(rng)                                               # one stream for all levels
     counts = [(int(kept.size), t_len) if per_step else int(kept.size) for _ in noisy]
     dtypes = [arrays[m].dtype for m in noisy]
-    draws = [draw_timeseries_noise(counts, i / scale, True, True, rng, dtypes) for i in range(int(levels))]
+    draws = [_draw(g, counts, i / scale, True, True, dtypes) for i in range(int(levels))]
     labels = np.asarray(split["labels"]).reshape(-1)[kept]
     ids = np.asarray(split["id"])[kept] if "id" in split else None
-    return _RobustLevels(base, labels, ids, kept, start, draws, list(noisy), per_step, batch_size,
-                         {"data_type": data_type, "z_norm": z_norm, "vision_norm": vision_norm})
+
+    def build(level):
+        """The AffectTable of one level (get_data.py:349-404 for that level, then Affectdataset)."""
+        tables, start = [], clean_start
+        with torch.cuda.device(dev):
+            for m, x in enumerate(base):
+                if m not in noisy:
+                    tables.append(x.clone())                    # the build works in place
+                    continue
+                eps, keep = draws[level][noisy.index(m)]
+                if m == 2:                                      # the trim and the second drop come from the noisy text
+                    start = torch.empty(x.shape[0], dtype=torch.int32, device=dev)
+                tables.append(_perturb(x, eps, keep, per_step=per_step, start_out=start if m == 2 else None))
+        return AffectTable._from_device(tables, labels, ids, data_type, z_norm, vision_norm, start, kept)
+
+    return LevelSequence(len(draws), build, lambda table: SequenceLoader(table, batch_size), base)
+
+
+def _build_model(indims, zdim, modality, lr, infoNCE_loss, pos_embd, pos_learnable, dev):
+    """The UML model of main.py:104-122 on ``dev`` and its Adam: the shared encoder is constructed first, then the two
+    in-projections and the two decoders (the order in which the initialisation draws from torch's global generator)."""
+    from .models import UML, Linear, Transformer
+    encoder = Transformer(zdim, zdim, nhead=5, num_layers=5, conv1d=True, out_last=False, pos_embd=pos_embd,
+                          pos_learnable=pos_learnable, max_len=128)
+    model = UML(Linear(indims[0], zdim), Linear(indims[1], zdim), encoder, [Linear(zdim, indims[0]), Linear(zdim, indims[1])],
+                modality=modality, infoNCE_loss=infoNCE_loss).to(dev)
+    return model, torch.optim.Adam(model.parameters(), lr=lr)
 
 
 def build_run(ds_name, data, zdim, modality="xy", lr=1e-4, infoNCE_loss=False, pos_embd=False, pos_learnable=False, device=None):
@@ -396,24 +436,17 @@ def build_run(ds_name, data, zdim, modality="xy", lr=1e-4, infoNCE_loss=False, p
     shuffled train loaders (both seeded 42; they share one table), the three unshuffled evaluation loaders, the UML model on
     the device and Adam.  ``data``: the pickle's dict or its path.  Returns a dict with 'train_loader', 'train_loader_2',
     'eval_config' (the batch lists ``train`` expects, freq 100), 'model', 'optimizer', 'indims' and 'batch_size'."""
-    from .models import UML, Linear, Transformer
     if ds_name not in DATASETS:
         raise NotImplementedError(f"build_run: dataset {ds_name!r} (known: {sorted(DATASETS)})")
     cfg = DATASETS[ds_name]
     dev = _device(device)
-    if not isinstance(data, dict):
-        with open(data, "rb") as f:
-            data = pickle.load(f)
+    data = _open_pickle(data)
     kw = {"batch_size": cfg["batch_size"], "data_type": cfg["data_type"], "vision_norm": cfg["vision_norm"], "device": dev}
     train_loader, valid, test = get_dataloader(data, train_shuffle=True, **kw)
     train_loader_2 = SequenceLoader(train_loader.table, cfg["batch_size"], shuffle=True, generator=torch.Generator().manual_seed(42))
     eval_train = SequenceLoader(train_loader.table, cfg["batch_size"])
     indims = cfg["indims"]
-    encoder = Transformer(zdim, zdim, nhead=5, num_layers=5, conv1d=True, out_last=False, pos_embd=pos_embd,
-                          pos_learnable=pos_learnable, max_len=128)
-    model = UML(Linear(indims[0], zdim), Linear(indims[1], zdim), encoder, [Linear(zdim, indims[0]), Linear(zdim, indims[1])],
-                modality=modality, infoNCE_loss=infoNCE_loss).to(dev)
-    optimizer = torch.optim.Adam(model.parameters(), lr=lr)
+    model, optimizer = _build_model(indims, zdim, modality, lr, infoNCE_loss, pos_embd, pos_learnable, dev)
     return {"train_loader": train_loader, "train_loader_2": train_loader_2, "model": model, "optimizer": optimizer,
             "eval_config": {"train": list(eval_train), "val": list(valid), "test": list(test), "freq": 100},
             "indims": indims, "batch_size": cfg["batch_size"]}

@@ -27,26 +27,17 @@ Declared differences and limitations:
 """
 from __future__ import annotations
 
-import copy
-import pickle
 import random
 
 import numpy as np
 import torch
 
-from .data import SequenceSampler, _device
+from .data import DeviceLoader, LevelSequence, _build_model, _device, _open_pickle
 
 # main.py:89-96: batch size, [x, y] input widths (static, series), the pickle's name and the icd9 task; 40 is the default
 # batch size of the reference's get_dataloader, which its evaluation loaders run with
 MIMIC = {"batch_size": 128, "eval_batch_size": 40, "indims": [5, 12], "file": "im.pk", "task": 7}
 LEVELS = 11
-
-
-def _load(datafile):
-    if isinstance(datafile, dict):
-        return datafile
-    with open(datafile, "rb") as f:
-        return pickle.load(f)
 
 
 def labels_for_task(datafile, task):
@@ -83,7 +74,7 @@ class MimicTable:
 
     def __init__(self, datafile, task, device=None):
         from umlh import seqload
-        datafile = _load(datafile)
+        datafile = _open_pickle(datafile)
         xs, xt = np.asarray(datafile["adm_features_all"]), np.asarray(datafile["ep_tdata"])
         if xs.ndim != 2 or xt.ndim != 3 or xt.shape[0] != xs.shape[0] or min(xs.shape) < 1 or min(xt.shape) < 1:
             raise ValueError(f"MimicTable: adm_features_all {xs.shape} and ep_tdata {xt.shape}; expected [N, ds] and [N, T, dt]")
@@ -103,14 +94,13 @@ class MimicTable:
         return int(self.static.shape[0])
 
 
-class MimicLoader:
+class MimicLoader(DeviceLoader):
     """Batches of the rows ``rows`` (host positions into the two device tables ``static`` [n, ds] and ``series`` [n, T, dt])
     with ``labels`` (host array, one per entry of ``rows``): ``SequenceSampler`` for the order, one ``umlh_rows_gather`` launch
     per batch.  Default layout, the ``_process_1`` one: ``([static [b, 1, ds], None, series [b, T, dt]], [ones [b], None,
     full(T) [b]], inds [b, 1], labels [b, 1])`` with blocks and lengths on the device, ``inds`` (positions in this loader's
     dataset) and ``labels`` on the host.  ``reference_layout``: the reference's own ``(static [b, ds], series [b, T, dt],
-    labels [b])``.  ``flatten_time_series``: the series block as [b, T * dt], a view of the same block.
-    ``copy.deepcopy`` shares the tables and copies the generator's state, as ``SequenceLoader``."""
+    labels [b])``.  ``flatten_time_series``: the series block as [b, T * dt], a view of the same block."""
 
     def __init__(self, static, series, rows, labels, batch_size, shuffle=False, generator=None, reference_layout=False,
                  flatten_time_series=False):
@@ -119,47 +109,24 @@ class MimicLoader:
         self.labels = torch.as_tensor(np.ascontiguousarray(labels))
         if self.rows.ndim != 1 or self.labels.shape != self.rows.shape:
             raise ValueError(f"MimicLoader: rows {tuple(self.rows.shape)} and labels {tuple(self.labels.shape)} (one label per row)")
-        self.batch_size, self.reference_layout, self.flatten = int(batch_size), bool(reference_layout), bool(flatten_time_series)
-        self.sampler = SequenceSampler(len(self.rows), batch_size, shuffle, generator)
+        self.reference_layout, self.flatten = bool(reference_layout), bool(flatten_time_series)
+        super().__init__(len(self.rows), batch_size, shuffle, generator)
 
-    @property
-    def generator(self):
-        return self.sampler.generator
-
-    def __len__(self):
-        return len(self.sampler)
-
-    def iter_index(self):
-        return iter(self.sampler)
-
-    def __iter__(self):
-        return self._epoch(iter(self.sampler))                # the base-seed draw happens here, not at the first batch
-
-    def _epoch(self, batches):
+    def _prepare(self, order):
         from umlh import seqload
-        dev, bs, t_len = self.static.device, self.batch_size, self.series.shape[1]
-        order = ids = labels = ones = full = None
-        for i, batch in enumerate(batches):
-            if order is None:                                 # the epoch's order is known now: one upload, host slices prepared
-                order = torch.tensor(batches.order, dtype=torch.int64)
-                ids = self.rows[order].to(dev)
-                labels = self.labels[order]
-                ones = torch.ones(min(bs, len(order)), dtype=torch.int64, device=dev)
-                full = torch.full_like(ones, t_len)
-            lo, hi = i * bs, i * bs + len(batch)
-            st, se = seqload.rows_gather([self.static, self.series], ids[lo:hi])
-            if self.flatten:
-                se = se.view(se.shape[0], -1)
-            if self.reference_layout:
-                yield st, se, labels[lo:hi]
-            else:
-                yield [st.unsqueeze(1), None, se], [ones[:hi - lo], None, full[:hi - lo]], order[lo:hi].view(-1, 1), labels[lo:hi].view(-1, 1)
+        dev = self.static.device
+        ids = self.rows[order].to(dev)
+        ones = torch.ones(min(self.batch_size, len(order)), dtype=torch.int64, device=dev)
+        return seqload.rows_gather, order, ids, self.labels[order], ones, torch.full_like(ones, self.series.shape[1])
 
-    def __deepcopy__(self, memo):
-        c = MimicLoader.__new__(MimicLoader)
-        c.__dict__.update(self.__dict__)
-        c.sampler = copy.deepcopy(self.sampler, memo)
-        return c
+    def _batch(self, epoch, i, lo, hi):
+        rows_gather, order, ids, labels, ones, full = epoch
+        st, se = rows_gather([self.static, self.series], ids[lo:hi])
+        if self.flatten:
+            se = se.view(se.shape[0], -1)
+        if self.reference_layout:
+            return st, se, labels[lo:hi]
+        return [st.unsqueeze(1), None, se], [ones[:hi - lo], None, full[:hi - lo]], order[lo:hi].view(-1, 1), labels[lo:hi].view(-1, 1)
 
 
 def draw_mimic_noise(n_test, levels=LEVELS, tabular_robust=True, timeseries_robust=True, rng=None, static_dim=5, series_shape=(24, 12)):
@@ -171,9 +138,8 @@ def draw_mimic_noise(n_test, levels=LEVELS, tabular_robust=True, timeseries_robu
     Returns per level a dict: 'drop' uint8 [n, static_dim] and 'carry' uint8 [n, static_dim - 1] (1 where
     ``random_sample() < p``), 'eps' float64 [n], 'elem' uint8 [n, T * dt] (1 where dropped) and 'keep' uint8 [n] (0 where
     dropped); None for a disabled family.  Level 0 still draws."""
-    from .robustness import _rng, draw_timeseries_noise
+    from .robustness import _draw, _rng
     g = _rng(rng)                                             # one stream for all levels, also when ``rng`` is an int seed
-    own = None if g is np.random else g                       # what draw_timeseries_noise takes for the same stream
     n, words = int(n_test), int(series_shape[0]) * int(series_shape[1])
     out = []
     for k in range(int(levels)):
@@ -183,56 +149,29 @@ def draw_mimic_noise(n_test, levels=LEVELS, tabular_robust=True, timeseries_robu
             lv["drop"] = (g.random_sample((n, static_dim)) < p).astype(np.uint8)
             lv["carry"] = (g.random_sample((n, static_dim - 1)) < p).astype(np.uint8)
         if timeseries_robust:                                 # the series are float64 in the reference: eps is not rounded
-            lv["eps"] = draw_timeseries_noise([n], p, True, False, own, np.float64)[0][0]
+            lv["eps"] = _draw(g, [n], p, True, False, [np.float64])[0][0]
             lv["elem"] = (g.random_sample((n, words)) < p).astype(np.uint8)
-            lv["keep"] = draw_timeseries_noise([n], p, False, True, own)[0][1]
+            lv["keep"] = _draw(g, [n], p, False, True, [np.float32])[0][1]
         out.append(lv)
     return out
 
 
-class _MimicLevels:
-    """The test loaders level by level.  The clean test rows stay on the device; a level's tables are built when its loader is
-    first asked for and only the latest level is kept (as ``multibench.data._RobustLevels``)."""
-
-    def __init__(self, static, series, labels, draws, batch_size, loader_options):
-        self.static, self.series, self.labels, self.draws = static, series, labels, draws
-        self.batch_size, self.loader_options = batch_size, loader_options
-        self._last = (None, None)
-
-    def __len__(self):
-        return len(self.draws)
-
-    def tables(self, level):
-        """(static [n, ds], series [n, T, dt]) of one level: one ``tab_perturb`` on the static rows; on the series one
-        ``umlh_seq_perturb`` with a draw per sample (Gaussian noise and the per-sample drop) and one ``tab_perturb`` on its
-        [n, T * dt] view with the element mask as ``drop`` and no carry -- zeroing commutes with the rest."""
-        from umlh import seqload
-        if self._last[0] == level:
-            return self._last[1]
-        self._last = (None, None)                               # release the previous level before this one is built
-        lv, dev = self.draws[level], self.static.device
-        up = lambda a: torch.from_numpy(a).to(dev)
-        static, series = self.static, self.series
-        with torch.cuda.device(dev):
-            if lv["drop"] is not None:
-                static = seqload.tab_perturb(static, up(lv["drop"]), up(lv["carry"]) if static.shape[1] > 1 else None)
-            if lv["eps"] is not None:
-                series = seqload.perturb(series, up(lv["eps"]), up(lv["keep"]))
-                flat = series.view(series.shape[0], -1)
-                seqload.tab_perturb(flat, up(lv["elem"]), None, out=flat)
-        self._last = (level, (static, series))
-        return static, series
-
-    def __getitem__(self, level):
-        if isinstance(level, slice):
-            return [self[i] for i in range(len(self))[level]]
-        level = int(level)
-        if level < 0:
-            level += len(self)
-        if not 0 <= level < len(self):
-            raise IndexError(level)
-        static, series = self.tables(level)
-        return MimicLoader(static, series, np.arange(static.shape[0]), self.labels, self.batch_size, **self.loader_options)
+def _level_tables(static, series, lv):
+    """(static [n, ds], series [n, T, dt]) of one level from its draws ``lv``: one ``tab_perturb`` on the static rows; on the
+    series one ``umlh_seq_perturb`` with a draw per sample (Gaussian noise and the per-sample drop) and one ``tab_perturb`` on
+    its [n, T * dt] view with the element mask as ``drop`` and no carry -- zeroing commutes with the rest."""
+    from umlh import seqload
+    from .robustness import _perturb
+    dev = static.device
+    up = lambda a: torch.from_numpy(a).to(dev)
+    with torch.cuda.device(dev):
+        if lv["drop"] is not None:
+            static = seqload.tab_perturb(static, up(lv["drop"]), up(lv["carry"]) if static.shape[1] > 1 else None)
+        if lv["eps"] is not None:
+            series = _perturb(series, lv["eps"], lv["keep"])
+            flat = series.view(series.shape[0], -1)
+            seqload.tab_perturb(flat, up(lv["elem"]), None, out=flat)
+    return static, series
 
 
 def get_dataloader(task, batch_size=40, num_workers=1, train_shuffle=True, imputed_path="im.pk", flatten_time_series=False,
@@ -257,7 +196,10 @@ def get_dataloader(task, batch_size=40, num_workers=1, train_shuffle=True, imput
         draws = draw_mimic_noise(n_test, LEVELS, tabular_robust, timeseries_robust, rng, tb.static.shape[1], tuple(tb.series.shape[1:]))
         with torch.cuda.device(tb.device):
             static, series = seqload.rows_gather([tb.static, tb.series], torch.tensor(tb.test, dtype=torch.int64).to(tb.device))
-        levels = _MimicLevels(static, series, lab(tb.test), draws, batch_size, opts)
+        test_labels = lab(tb.test)
+        levels = LevelSequence(len(draws), lambda k: _level_tables(static, series, draws[k]),
+                               lambda t: MimicLoader(t[0], t[1], np.arange(t[0].shape[0]), test_labels, batch_size, **opts),
+                               (static, series))
     return trains, valids, {"timeseries": levels}
 
 
@@ -277,7 +219,6 @@ def build_run(data, zdim, task=MIMIC["task"], modality="xy", lr=1e-4, infoNCE_lo
     levels of the test split, for ``evaluate_robustness``), 'table', 'model', 'optimizer', 'indims', 'batch_size' and
     'ds_name': 'mimic_icd9' or 'mimic_mortality', the name to pass to ``train`` / ``evaluate`` (NOT 'mimic', see the module's
     docstring)."""
-    from .models import UML, Linear, Transformer
     dev = _device(device)
     ds_name = "mimic_mortality" if task < 0 else "mimic_icd9"
     table = MimicTable(data, task, dev)
@@ -286,11 +227,7 @@ def build_run(data, zdim, task=MIMIC["task"], modality="xy", lr=1e-4, infoNCE_lo
                                  generator=generator_2)
     eval_train, valid, robust = get_dataloader(task, eval_batch_size, train_shuffle=False, table=table, rng=rng)
     indims = [int(table.static.shape[1]), int(table.series.shape[2])]
-    encoder = Transformer(zdim, zdim, nhead=5, num_layers=5, conv1d=True, out_last=False, pos_embd=pos_embd,
-                          pos_learnable=pos_learnable, max_len=128)
-    model = UML(Linear(indims[0], zdim), Linear(indims[1], zdim), encoder, [Linear(zdim, indims[0]), Linear(zdim, indims[1])],
-                modality=modality, infoNCE_loss=infoNCE_loss).to(dev)
-    optimizer = torch.optim.Adam(model.parameters(), lr=lr)
+    model, optimizer = _build_model(indims, zdim, modality, lr, infoNCE_loss, pos_embd, pos_learnable, dev)
     valid_batches = list(valid)
     return {"train_loader": train_loader, "train_loader_2": train_loader_2, "model": model, "optimizer": optimizer,
             "eval_config": {"train": list(eval_train), "val": valid_batches, "test": valid_batches, "freq": 100,

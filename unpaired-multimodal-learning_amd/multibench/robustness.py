@@ -40,21 +40,26 @@ def draw_timeseries_noise(counts, noise_level, gaussian_noise=True, struct_drop=
     for each sample in order, the reference's call on that sample's list of [T, d] arrays).  Returns per array
     ``(eps, keep)``: float64 and uint8 arrays of shape [n] or [n, T], None for a step that is off.  ``keep`` is 0 where the
     reference's ``random_sample() < noise_level`` holds.  ``table_dtype``: one dtype, or one per array, of the arrays the
-    reference would add into (see the module's docstring)."""
-    g, p, counts = _rng(rng), float(noise_level), list(counts)
+    reference would add into (see the module's docstring).  ``rng`` is resolved here; ``_draw`` is the same on a resolved
+    stream, for callers that run one stream through several calls."""
+    g, counts = _rng(rng), list(counts)
     dtypes = list(table_dtype) if isinstance(table_dtype, (list, tuple)) else [table_dtype] * len(counts)
     if len(dtypes) != len(counts):
         raise ValueError(f"draw_timeseries_noise: {len(dtypes)} dtypes for {len(counts)} arrays")
-    per_step = any(isinstance(c, (tuple, list)) for c in counts)
-    if not per_step:
-        eps = [g.normal(0, p, size=int(c)) if gaussian_noise else None for c in counts]
-        keep = [(~(g.random_sample(int(c)) < p)).astype(np.uint8) if struct_drop else None for c in counts]
-    else:
+    if any(isinstance(c, (tuple, list)) for c in counts):
         shapes = {tuple(int(v) for v in c) for c in counts}
         if len(shapes) != 1 or len(next(iter(shapes))) != 2:
             raise ValueError(f"draw_timeseries_noise: per-step counts must be one (n, T) for every array, got {counts}")
-        n, T = next(iter(shapes))
-        k = len(counts)
+    return _draw(g, counts, float(noise_level), gaussian_noise, struct_drop, dtypes)
+
+
+def _draw(g, counts, p, gaussian_noise, struct_drop, dtypes):
+    """``draw_timeseries_noise`` on the resolved stream ``g`` (``_rng``), with checked ``counts`` and one dtype per array."""
+    if not (counts and isinstance(counts[0], (tuple, list))):
+        eps = [g.normal(0, p, size=int(c)) if gaussian_noise else None for c in counts]
+        keep = [(~(g.random_sample(int(c)) < p)).astype(np.uint8) if struct_drop else None for c in counts]
+    else:
+        (n, T), k = (int(v) for v in counts[0]), len(counts)
         e = np.empty((n, k, T)) if gaussian_noise else None
         u = np.empty((n, k, T)) if struct_drop else None
         for s in range(n):                                     # one reference call per sample: its normals, then its uniforms
@@ -67,15 +72,11 @@ def draw_timeseries_noise(counts, noise_level, gaussian_noise=True, struct_drop=
     return [(None if e_ is None else _round_eps(e_, dt), k_) for e_, k_, dt in zip(eps, keep, dtypes)]
 
 
-def _apply(tests, draws, per_step, elem_p, seed):
+def _perturb(x, eps, keep, **options):
+    """One table's host draws uploaded to its device and its one ``umlh_seq_perturb`` launch (``umlh.seqload.perturb``)."""
     from umlh import seqload
-    out = []
-    for i, (x, (eps, keep)) in enumerate(zip(tests, draws)):
-        dev = x.device
-        out.append(seqload.perturb(x, None if eps is None else torch.from_numpy(eps).to(dev),
-                                   None if keep is None else torch.from_numpy(keep).to(dev), per_step=per_step,
-                                   elem_p=elem_p, seed=int(seed) + i))
-    return out
+    up = lambda a: None if a is None else torch.from_numpy(a).to(x.device)
+    return seqload.perturb(x, up(eps), up(keep), **options)
 
 
 def _counts(tests, per_step):
@@ -96,7 +97,8 @@ def add_timeseries_noise(tests, noise_level=0.3, gaussian_noise=True, rand_drop=
     tests, counts = _counts(tests, per_step)
     draws = draw_timeseries_noise(counts, noise_level, gaussian_noise, struct_drop, rng, table_dtype)
     elem_p = min(max(float(noise_level), 0.0), 1.0) if rand_drop else 0.0     # a probability: `uniform < p` beyond [0, 1] is 0 or 1
-    return _apply(tests, draws, per_step, elem_p, seed)
+    return [_perturb(x, eps, keep, per_step=per_step, elem_p=elem_p, seed=int(seed) + i)
+            for i, (x, (eps, keep)) in enumerate(zip(tests, draws))]
 
 
 def white_noise(data, p, rng=None, per_step=False, table_dtype=np.float32):

@@ -121,39 +121,45 @@ class _Probes:
         return {k: c / n for k, c, n in zip(self.names, got, self.rows)}
 
 
-def _fit_three(pr, emb, lab, z, tag="", classifier_type="logistic"):
-    """The x, y and xy probes (train.py:163-183): fitted on train, scored on val and test.  emb[t] is [N_t, zx + zy] with
-    the x block in the first zx columns: the three feature sets are views of it (the row stride travels to the kernels)."""
+def _fit_three(pr, emb, lab, z, splits, name_of, classifier_type="logistic"):
+    """The x, y and xy probes (train.py:163-183): each fitted on 'train' and scored on every key of ``splits``, under the name
+    ``name_of(split, 'x' | 'y' | 'xy')``.  emb[k] is [N_k, zx + zy] with the x block in the first zx columns: the three
+    feature sets are views of it (the row stride travels to the kernels)."""
     ytr = torch.from_numpy(lab["train"]).to(pr.dev)
-    yev = {t: torch.from_numpy(lab[t]).to(pr.dev) for t in ("val", "test")}
+    yev = {t: torch.from_numpy(lab[t]).to(pr.dev) for t in splits}
     for name, cols in (("x", slice(0, z[0])), ("y", slice(z[0], z[0] + z[1])), ("xy", slice(0, z[0] + z[1]))):
         clf = pr.fit(emb["train"][:, cols], ytr, classifier_type)
-        for t in ("val", "test"):
-            pr.score(f"{t}/score_{name}{tag}", clf, emb[t][:, cols], yev[t])
+        for t in splits:
+            pr.score(name_of(t, name), clf, emb[t][:, cols], yev[t])
+
+
+def _pooled(parts, dims, dev):
+    """The [N, dims[0] + dims[1]] fp32 device matrix of the masked means of ``parts``, a list of per-batch
+    ``(x, x_lengths, y, y_lengths)`` (lengths None: the plain mean over time), batch under batch in their order."""
+    import umlh
+    emb = torch.empty((sum(p[0].shape[0] for p in parts), dims[0] + dims[1]), dtype=torch.float32, device=dev)
+    off = 0
+    for x, lx, y, ly in parts:
+        bs = x.shape[0]
+        umlh.masked_mean(x.float(), lx, out=emb[off:off + bs, :dims[0]])
+        umlh.masked_mean(y.float(), ly, out=emb[off:off + bs, dims[0]:])
+        off += bs
+    return emb
 
 
 def evaluate_raw_data(config, ds_name="mosi", device=None, return_probes=False, label_fn=None):
     """The raw-feature baselines (train.py:31-91): each modality's plain mean over time, probes on x, y and [x, y].
     ``return_probes`` adds the pooled [N, dx + dy] device matrices per split and the three fitted probes.  ``label_fn``: see
     ``evaluate``."""
-    import umlh
     lab, n_classes = _class_labels({t: _labels01(config[t], ds_name, label_fn) for t in _TYPES}, label_fn)
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     with torch.cuda.device(dev):
         emb, dims = {}, None
         for t in _TYPES:
-            n = sum(b[0][0].shape[0] for b in config[t])
             dims = (config[t][0][0][0].shape[-1], config[t][0][0][2].shape[-1])
-            emb[t] = torch.empty((n, dims[0] + dims[1]), dtype=torch.float32, device=dev)
-            off = 0
-            for b in config[t]:
-                x, y = b[0][0], b[0][2]
-                bs = x.shape[0]
-                umlh.masked_mean(x.float(), None, out=emb[t][off:off + bs, :dims[0]])
-                umlh.masked_mean(y.float(), None, out=emb[t][off:off + bs, dims[0]:])
-                off += bs
+            emb[t] = _pooled([(b[0][0], None, b[0][2], None) for b in config[t]], dims, dev)
         pr = _Probes(ds_name, dev, n_classes)
-        _fit_three(pr, emb, lab, dims, tag="_raw")
+        _fit_three(pr, emb, lab, dims, ("val", "test"), lambda t, name: f"{t}/score_{name}_raw")
         got = pr.read()
     results = {k: got[k] for k in ("val/score_x_raw", "val/score_y_raw", "test/score_x_raw", "test/score_y_raw", "test/score_xy_raw",
                                    "val/score_xy_raw")}
@@ -164,7 +170,6 @@ def _embed_split(model, batches, dev, who="evaluate"):
     """One split through the eval-mode model and the masked mean (train.py:104-141): the pooled [N, zx + zy] device matrix,
     the (loss_x, loss_y) means over its batches as device doubles, and (zx, zy).  Everything is enqueued, nothing read back;
     the caller holds ``torch.no_grad`` and the device."""
-    import umlh
     outs, lens = [], []
     for b in batches:
         x, y, lx, ly = b[0][0], b[0][2], b[1][0].to(dev), b[1][2].to(dev)
@@ -173,17 +178,25 @@ def _embed_split(model, batches, dev, who="evaluate"):
     z = (outs[0]["zx"].shape[-1], outs[0]["zy"].shape[-1])
     if z[0] != z[1]:
         raise ValueError(f"{who}: zx and zy have different widths {z}; the modality-separation probe stacks them")
-    n = sum(o["zx"].shape[0] for o in outs)
-    emb = torch.empty((n, z[0] + z[1]), dtype=torch.float32, device=dev)
-    off = 0
-    for o, (lx, ly) in zip(outs, lens):
-        bs = o["zx"].shape[0]
-        umlh.masked_mean(o["zx"], lx, out=emb[off:off + bs, :z[0]])
-        umlh.masked_mean(o["zy"], ly, out=emb[off:off + bs, z[0]:])
-        off += bs
+    emb = _pooled([(o["zx"], lx, o["zy"], ly) for o, (lx, ly) in zip(outs, lens)], z, dev)
     loss = (torch.stack([o["loss_x"].reshape(()) for o in outs]).double().mean(),
             torch.stack([o["loss_y"].reshape(()) for o in outs]).double().mean())
     return emb, loss, z
+
+
+def _begin_evaluation(model, ds_name, device, classifier_types, label_fn):
+    """What ``evaluate`` and ``evaluate_robustness`` do before they touch a batch: the dataset's label rule must exist (unless
+    ``label_fn`` replaces it), every classifier type must be known, and the model goes into eval mode.  Returns the types as a
+    tuple and the device."""
+    if label_fn is None:
+        _label_fn(ds_name)
+    classifier_types = tuple(classifier_types)
+    for ct in classifier_types:
+        if ct not in ("logistic", "knn"):
+            raise ValueError(f"Unsupported classifier type: {ct}")
+    dev = torch.device(device)
+    model.eval()
+    return classifier_types, dev
 
 
 @torch.no_grad()
@@ -203,14 +216,7 @@ def evaluate(model, config, ds_name="mosi", device="cuda:0", return_embeddings=F
     integer labels, for a dataset name the reference raises on ('mimic' and its 6 classes) or a caller's own task.  With more
     than two classes in the train labels the x / y / xy logistic probes are ``umlh.SoftmaxProbe``s; the modality-separation
     probe stays binary."""
-    if label_fn is None:
-        _label_fn(ds_name)
-    classifier_types = tuple(classifier_types)
-    for ct in classifier_types:
-        if ct not in ("logistic", "knn"):
-            raise ValueError(f"Unsupported classifier type: {ct}")
-    dev = torch.device(device)
-    model.eval()
+    classifier_types, dev = _begin_evaluation(model, ds_name, device, classifier_types, label_fn)
     lab, n_classes = _class_labels({t: _labels01(config[t], ds_name, label_fn) for t in _TYPES}, label_fn)
     emb, loss, z = {}, {}, None
     with torch.cuda.device(dev):
@@ -223,7 +229,7 @@ def evaluate(model, config, ds_name="mosi", device="cuda:0", return_embeddings=F
             which = torch.cat([torch.zeros(n, dtype=torch.int32, device=dev), torch.ones(n, dtype=torch.int32, device=dev)])
             pr.score(f"sep/{t}", pr.fit(both, which, binary=True), both, which)
         for ct in classifier_types:
-            _fit_three(pr, emb, lab, z, classifier_type=ct)
+            _fit_three(pr, emb, lab, z, ("val", "test"), lambda t, name: f"{t}/score_{name}", ct)
         got = pr.read()
         losses = torch.stack([loss["val"][0], loss["test"][0], loss["val"][1], loss["test"][1]]).cpu().tolist()
     results = {"val/modality_separate": float(np.mean([got[f"sep/{t}"] for t in _TYPES]))}
@@ -247,14 +253,7 @@ def evaluate_robustness(model, config, robust, ds_name="mosi", device="cuda:0", 
     Returns ``robust/{family}/score_x``, ``score_y``, ``score_xy``, ``loss_x``, ``loss_y`` as lists over the levels, ``n`` the
     rows per level (drops shrink it), and ``mean_score_x`` / ``_y`` / ``_xy``, the plain mean over the levels.  With several
     ``classifier_types`` a later one overwrites an earlier one's scores, as in ``evaluate``."""
-    if label_fn is None:
-        _label_fn(ds_name)
-    classifier_types = tuple(classifier_types)
-    for ct in classifier_types:
-        if ct not in ("logistic", "knn"):
-            raise ValueError(f"Unsupported classifier type: {ct}")
-    dev = torch.device(device)
-    model.eval()
+    classifier_types, dev = _begin_evaluation(model, ds_name, device, classifier_types, label_fn)
     lab = {"train": _labels01(config["train"], ds_name, label_fn)}
     emb, loss, keys = {}, [], []
     with torch.cuda.device(dev):
@@ -271,12 +270,8 @@ def evaluate_robustness(model, config, robust, ds_name="mosi", device="cuda:0", 
                 del batches
         lab, n_classes = _class_labels(lab, label_fn)
         pr = _Probes(ds_name, dev, n_classes)
-        ytr = torch.from_numpy(lab["train"]).to(dev)
         for ct in classifier_types:
-            for name, cols in (("x", slice(0, z[0])), ("y", slice(z[0], z[0] + z[1])), ("xy", slice(0, z[0] + z[1]))):
-                clf = pr.fit(emb["train"][:, cols], ytr, ct)
-                for family, i in keys:
-                    pr.score(f"{family}/{i}/{name}", clf, emb[(family, i)][:, cols], torch.from_numpy(lab[(family, i)]).to(dev))
+            _fit_three(pr, emb, lab, z, keys, lambda key, name: f"{key[0]}/{key[1]}/{name}", ct)
         got = pr.read()
         losses = torch.stack(loss).cpu().tolist() if loss else []
     results = {}
@@ -510,7 +505,8 @@ def train(model, train_mode, train_loader_1, train_loader_2, optimizer, modaliti
     if eval_config:
         raw_results = evaluate_raw_data(eval_config, ds_name=ds_name, device=device, label_fn=eval_config.get("label_fn"))
 
-    def logged(score):
+    def logged_evaluation():
+        score = evaluate(model, eval_config, ds_name, device=device, classifier_types=classifier_types, label_fn=eval_config.get("label_fn"))
         out = {k: v for k, v in score.items() if not ("private" in k or "complete" in k)}
         out.update(raw_results)
         return out
@@ -542,7 +538,7 @@ def train(model, train_mode, train_loader_1, train_loader_2, optimizer, modaliti
             if on_step is not None:
                 on_step(epoch, i_batch, out, loss)
             if eval_config and i_batch % eval_config["freq"] == 0:
-                evals.append((epoch, i_batch, logged(evaluate(model, eval_config, ds_name, device=device, classifier_types=classifier_types, label_fn=eval_config.get("label_fn")))))
+                evals.append((epoch, i_batch, logged_evaluation()))
                 if capture is not None:
                     values, zx, zy = capture.measure(model)
                     evals[-1][2].update(values)
@@ -552,7 +548,7 @@ def train(model, train_mode, train_loader_1, train_loader_2, optimizer, modaliti
                         spectra.append((epoch, i_batch, _capture_spectra(model, capture)))
                 model.train()
         if eval_config and epoch == num_epoch - 1:
-            evals.append((epoch, None, logged(evaluate(model, eval_config, ds_name, device=device, classifier_types=classifier_types, label_fn=eval_config.get("label_fn")))))
+            evals.append((epoch, None, logged_evaluation()))
             model.train()
     stack = lambda v: torch.stack([t.reshape(()) for t in v]).cpu().tolist() if v else []
     res = {"loss_x": stack(rec_x), "loss_y": stack(rec_y), "loss": stack(rec_l)}
