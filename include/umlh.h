@@ -1084,6 +1084,75 @@ int  umlh_tab_perturb(const float* src, int64_t n, int32_t d, int64_t lds, const
 int  umlh_rows_gather(const float* const* srcs, const int32_t* widths, int32_t n_src, int64_t n, const int64_t* ids, int32_t b,
                       float* const* outs, void* stream);
 
+/* ---- the Gaussian toy's SharedAutoencoder (Gaussian_experiment/model.py:5-59, main.py:33-91): the forward of either or both
+ * views as one call, and whole training steps (both views, forward, MSE, backward, optimizer update) as two launches each
+ * (kernels: umlh_kernels_gauss.hip).  Additive to ABI v11: umlh_version() is unchanged, callers detect the
+ * feature by these symbols.  The section sits in front of the affect loader's for the same reason as the one above.
+ * Dimensions: dim_obs = D, dim_common = C, dim_latent = L.  P is a HOST array of 16 device pointers to dense row-major fp32
+ * tensors in the model's state_dict order: in_head_x.{weight [C, D], bias [C]}, in_head_y, shared_encoder.0 [L, C],
+ * shared_encoder.2 [L, L], shared_decoder.0 [L, L], shared_decoder.2 [C, L], out_head_x [D, C], out_head_y.  Per view v in
+ * {x, y}, row r of that view:
+ *   a0 = table_v[idx_v[r]]                       (row gather by int32 index; idx NULL = rows 0 .. n - 1; row i at table + i*ld)
+ *   a1 = W_in_v a0 + b      a2 = relu(W_e0 a1 + b)     a3 = W_e2 a2 + b        (a3: the embedding, get_embeddings)
+ *   a4 = relu(W_d0 a3 + b)  a5 = W_d2 a4 + b           rec = W_out_v a5 + b
+ *   loss_v = mean over rows_v * D of (rec - a0)^2      (0 for an absent view)
+ * Products: fp32 MFMA with fp32 accumulation, one fma chain per output in an order that depends on the reduction length alone
+ * (blocks of 16 k ascending, MFMA i of a block takes k0 + i, k0 + 4 + i, k0 + 8 + i, k0 + 12 + i); the bias is one fp32 add behind
+ * it; relu is fmaxf(v, 0), its backward keeps the gradient where the saved activation is > 0 (as umlh_relu_backward).  The loss
+ * squares and sums are fp64 from the fp32 residuals, in a fixed order, rounded once to fp32.  A row's reconstruction and embedding
+ * depend on the parameters and the row alone, not on its position or on the other rows.
+ * Every argument check happens before any HIP call and names the function and the argument; everything runs on `stream`, no host
+ * sync; no float atomics, no workgroup waits on another; grids and summation orders are functions of the shapes alone: results are
+ * bitwise reproducible across calls, streams and CU counts.
+ * Envelope: 1 <= D <= 1024, 1 <= C <= 512, 1 <= L <= 512, ld >= D; there is no fallback: anything else is UMLH_E_INVALID. */
+#define UMLH_AE_MAX_OBS        1024
+#define UMLH_AE_MAX_COMMON     512
+#define UMLH_AE_MAX_LATENT     512
+#define UMLH_AE_MAX_EVAL_ROWS  1048576   /* rows per view of one umlh_ae_forward                    */
+#define UMLH_AE_MAX_BATCH      65536     /* rows per view and step, steps per umlh_ae_train_steps   */
+typedef struct {
+    int32_t dim_obs;        /* D */
+    int32_t dim_common;     /* C */
+    int32_t dim_latent;     /* L */
+} umlh_ae_cfg_t;
+
+/* Scratch bytes of umlh_ae_forward (train = 0: the tiles' loss partials; rows up to UMLH_AE_MAX_EVAL_ROWS) or of
+ * umlh_ae_train_steps (train = 1: also a0 .. a5 and the six dZ blocks of every row, 2 D + 4 C + 6 L floats per row; rows up to
+ * UMLH_AE_MAX_BATCH), computed from the one layout plan the launchers use; 0 on invalid arguments (both views absent included).
+ * The fourth argument and the name are this header's: one plan serves both entry points, and the name does not end in
+ * _scratch_bytes (a closed family, pinned value for value by a recorded file). */
+uint64_t umlh_ae_scratch(const umlh_ae_cfg_t* cfg, int32_t rows_x, int32_t rows_y, int32_t train);
+
+/* The evaluation forward over n_x rows of x and n_y rows of y (0 = view absent, its table is not read; at least one present).
+ * Outputs, each optional (NULL): losses [2] = {loss_x, loss_y}; rec_x [n_x, D], rec_y [n_y, D]; emb_x [n_x, L], emb_y [n_y, L],
+ * dense fp32 device memory.  A view whose loss and reconstruction are both unwanted stops behind its embedding.  One launch, one
+ * more for the losses.  scratch: umlh_ae_scratch(cfg, n_x, n_y, 0), 8-byte aligned. */
+int  umlh_ae_forward(const umlh_ae_cfg_t* cfg, const float* const* P, const float* x, int64_t ldx, const int32_t* idx_x, int32_t n_x,
+                     const float* y, int64_t ldy, const int32_t* idx_y, int32_t n_y, float* losses, float* rec_x, float* rec_y,
+                     float* emb_x, float* emb_y, void* scratch, uint64_t scratch_bytes, void* stream);
+
+/* n_steps consecutive training steps, enqueued by a C loop: two launches per step whatever the dimensions, no host sync.  Step s
+ * (0-based) takes the rows idx_x[s*batch_x .. (s+1)*batch_x) of x and idx_y[s*batch_y ..) of y: DEVICE int32 arrays of
+ * n_steps * batch entries.  THE CALLER GUARANTEES that every index is a row of its table: an index is used as an address
+ * unchecked.  A NULL index array means rows 0 .. batch - 1 in every step.  batch 0 = the view is absent (at least one present).
+ * M and V are HOST arrays of 16 device pointers like P: the moments of the tensors (momentum_buffer / exp_avg, and exp_avg_sq).
+ * P, M and V are updated IN PLACE, element by element, by the update of umlh_optimizer_step (sgd, adam, adamw) with the step
+ * number first_step + s; under sgd V is neither read nor written and may be NULL.
+ *   backward_y = 1 (the reference's mode 'xy'): dRec_v = alpha_v * 2 / (rows_v * D) * (rec - a0) with the factor formed in double
+ *     and rounded once; loss = alpha_x * loss_x + alpha_y * loss_y as two fp32 products and one add, no contraction.
+ *   backward_y = 0 (mode 'x', main.py:54-56): the y view runs forward only; loss_y is reported, loss = loss_x; in_head_y.*,
+ *     out_head_y.* and their moments are not touched at all; the shared layers receive the x rows' gradient alone.
+ * The gradient of a tensor is summed over the x rows, then the y rows: wave w of its tile's workgroup takes the 4-row blocks
+ * w, w + 4, ... of a view in ascending order (one MFMA each) and the four wave sums are added in wave order; a bias gradient adds
+ * the same blocks per lane and the 16 lane sums in a fixed order.  Every weight element is owned by one thread of one workgroup.
+ * losses: [n_steps, 3] fp32 = loss_x, loss_y, loss of each step.  scratch: umlh_ae_scratch(cfg, batch_x, batch_y, 1), 8-byte
+ * aligned, reused by every step.  Envelope: 0 <= batch <= 65536 per view, 1 <= n_steps <= 65536. */
+int  umlh_ae_train_steps(const umlh_ae_cfg_t* cfg, float* const* P, float* const* M, float* const* V, const float* x, int64_t ldx,
+                         const int32_t* idx_x, int32_t batch_x, const float* y, int64_t ldy, const int32_t* idx_y, int32_t batch_y,
+                         int32_t n_steps, int32_t backward_y, float alpha_x, float alpha_y, int32_t optimizer, double lr,
+                         int64_t first_step, double beta1, double beta2, double eps, double momentum, double weight_decay,
+                         float* losses, void* scratch, uint64_t scratch_bytes, void* stream);
+
 /* ---- device loader of the affect datasets (mosi, mosei, humor, sarcasm): what Affectdataset.__getitem__ and the _process_1
  * collate of MultiBench/datasets/affect/get_data.py:159-261,418-444 do per sample and per batch on the host, as three table-build
  * passes and one step-path kernel.  Additive to ABI v11: umlh_version() is unchanged, callers detect the

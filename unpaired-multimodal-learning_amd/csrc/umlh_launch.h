@@ -260,6 +260,24 @@ int umlh_tab_launch_perturb(const float* src, long long n, int d, long long lds,
 // srcs, widths, outs: host arrays of n_src entries; a NULL source is skipped
 int umlh_tab_launch_gather(const float* const* srcs, const int* widths, int n_src, long long n, const long long* ids, int B,
                            float* const* outs, hipStream_t st);
+// ---- umlh_kernels_gauss.hip: the Gaussian toy's autoencoder (forward; one training step = launch A + launch B) ----
+unsigned long long umlh_ae_plan_bytes(const umlh_ae_cfg_t* cfg, int rows_x, int rows_y, int train);
+int umlh_ae_launch_forward(const umlh_ae_cfg_t* cfg, const float* const* P, const float* x, long long ldx, const int* idx_x, int n_x,
+                           const float* y, long long ldy, const int* idx_y, int n_y, float* losses, float* rec_x, float* rec_y,
+                           float* emb_x, float* emb_y, void* scratch, hipStream_t st);
+int umlh_ae_launch_step(const umlh_ae_cfg_t* cfg, float* const* P, float* const* M, float* const* V, const float* x, long long ldx,
+                        const int* idx_x, int batch_x, const float* y, long long ldy, const int* idx_y, int batch_y, int backward_y,
+                        float alpha_x, float alpha_y, const OptArgs* o, float* losses, void* scratch, int part, hipStream_t st);
+// ---- umlh_ops.cpp, for scripts/bench_gaussian.py alone ----
+// umlh_ae_train_steps with its checks, launching only a part of every step: part 1 = launch A alone, 2 = launch B alone on the
+// scratch an earlier whole step left, 0 = whole steps.  NOT a training call (with part 1 the weights never change, with part 2
+// they move along a stale gradient) and not part of the C ABI: it exists so that the two launches can be timed apart, and nothing
+// in the environment can make umlh_ae_train_steps do this.
+int umlh_ae_bench_steps(const umlh_ae_cfg_t* cfg, float* const* P, float* const* M, float* const* V, const float* x, long long ldx,
+                        const int* idx_x, int batch_x, const float* y, long long ldy, const int* idx_y, int batch_y, int n_steps,
+                        int backward_y, float alpha_x, float alpha_y, int optimizer, double lr, long long first_step, double beta1,
+                        double beta2, double eps, double momentum, double weight_decay, float* losses, void* scratch,
+                        unsigned long long scratch_bytes, int part, void* stream);
 
 // ---- umlh_api.cpp, for umlh_encoder.cpp ----
 // out[M,N] (ldo == N) = epilogue(A B^T) with the operand layouts of umlh_gemm_f32.  `splits` K-slabs go to `slabs`

@@ -1259,3 +1259,103 @@ int umlh_rows_gather(const float* const* srcs, const int32_t* widths, int32_t n_
     HIPCHK(umlh_tab_launch_gather(srcs, widths, n_src, n, ll(ids), b, outs, (hipStream_t)stream), who);
     return UMLH_OK;
 }
+
+// ---- the Gaussian toy's autoencoder (kernels: umlh_kernels_gauss.hip) ----
+// the dimensions and the rows of both views against the envelope; 0 = fine.  who == NULL: silent (the size query)
+static int check_ae_shape(const char* who, const umlh_ae_cfg_t* cfg, int32_t rows_x, int32_t rows_y, int32_t max_rows, const char* rx,
+                          const char* ry) {
+#define AE_FAIL(...) return who ? fail(UMLH_E_INVALID, __VA_ARGS__) : UMLH_E_INVALID
+    if (!cfg) AE_FAIL("%s: cfg is NULL", who);
+    if (cfg->dim_obs < 1 || cfg->dim_obs > UMLH_AE_MAX_OBS) AE_FAIL("%s: dim_obs=%d outside 1..%d", who, cfg->dim_obs, UMLH_AE_MAX_OBS);
+    if (cfg->dim_common < 1 || cfg->dim_common > UMLH_AE_MAX_COMMON)
+        AE_FAIL("%s: dim_common=%d outside 1..%d", who, cfg->dim_common, UMLH_AE_MAX_COMMON);
+    if (cfg->dim_latent < 1 || cfg->dim_latent > UMLH_AE_MAX_LATENT)
+        AE_FAIL("%s: dim_latent=%d outside 1..%d", who, cfg->dim_latent, UMLH_AE_MAX_LATENT);
+    if (rows_x < 0 || rows_x > max_rows) AE_FAIL("%s: %s=%d outside 0..%d", who, rx, rows_x, max_rows);
+    if (rows_y < 0 || rows_y > max_rows) AE_FAIL("%s: %s=%d outside 0..%d", who, ry, rows_y, max_rows);
+    if (rows_x == 0 && rows_y == 0) AE_FAIL("%s: %s=0 and %s=0 (both views absent)", who, rx, ry);
+#undef AE_FAIL
+    return UMLH_OK;
+}
+
+static int check_ae_tensors(const char* who, const char* name, const float* const* t) {
+    if (!t) return fail(UMLH_E_INVALID, "%s: %s is NULL (an array of 16 device pointers)", who, name);
+    for (int i = 0; i < 16; ++i)
+        if (!t[i]) return fail(UMLH_E_INVALID, "%s: %s[%d] is NULL", who, name, i);
+    return UMLH_OK;
+}
+
+static int check_ae_table(const char* who, const char* name, const char* ldname, const float* table, int64_t ld, int32_t rows, int32_t d) {
+    if (rows == 0) return UMLH_OK;
+    if (!table) return fail(UMLH_E_INVALID, "%s: %s is NULL with %d rows asked for", who, name, rows);
+    if (ld < d) return fail(UMLH_E_INVALID, "%s: %s=%lld < dim_obs=%d", who, ldname, (long long)ld, d);
+    return UMLH_OK;
+}
+
+uint64_t umlh_ae_scratch(const umlh_ae_cfg_t* cfg, int32_t rows_x, int32_t rows_y, int32_t train) {
+    if (train != 0 && train != 1) return 0;
+    if (check_ae_shape(nullptr, cfg, rows_x, rows_y, train ? UMLH_AE_MAX_BATCH : UMLH_AE_MAX_EVAL_ROWS, "", "")) return 0;
+    return umlh_ae_plan_bytes(cfg, rows_x, rows_y, train);
+}
+
+int umlh_ae_forward(const umlh_ae_cfg_t* cfg, const float* const* P, const float* x, int64_t ldx, const int32_t* idx_x, int32_t n_x,
+                    const float* y, int64_t ldy, const int32_t* idx_y, int32_t n_y, float* losses, float* rec_x, float* rec_y,
+                    float* emb_x, float* emb_y, void* scratch, uint64_t scratch_bytes, void* stream) {
+    const char* who = "umlh_ae_forward";
+    RC(check_ae_shape(who, cfg, n_x, n_y, UMLH_AE_MAX_EVAL_ROWS, "n_x", "n_y"));
+    RC(check_ae_tensors(who, "P", P));
+    RC(check_ae_table(who, "x", "ldx", x, ldx, n_x, cfg->dim_obs));
+    RC(check_ae_table(who, "y", "ldy", y, ldy, n_y, cfg->dim_obs));
+    if (!scratch) return fail(UMLH_E_INVALID, "%s: scratch is NULL", who);
+    RC(check_scratch(who, scratch, scratch_bytes, umlh_ae_plan_bytes(cfg, n_x, n_y, 0), 8));
+    HIPCHK(umlh_ae_launch_forward(cfg, P, x, ldx, idx_x, n_x, y, ldy, idx_y, n_y, losses, n_x ? rec_x : nullptr, n_y ? rec_y : nullptr,
+                                  n_x ? emb_x : nullptr, n_y ? emb_y : nullptr, scratch, (hipStream_t)stream), who);
+    return UMLH_OK;
+}
+
+// part: 0 = whole steps (umlh_ae_train_steps); 1 / 2 = one launch of every step (umlh_ae_bench_steps)
+static int ae_steps(const char* who, int part, const umlh_ae_cfg_t* cfg, float* const* P, float* const* M, float* const* V, const float* x,
+                    int64_t ldx, const int32_t* idx_x, int32_t batch_x, const float* y, int64_t ldy, const int32_t* idx_y, int32_t batch_y,
+                    int32_t n_steps, int32_t backward_y, float alpha_x, float alpha_y, int32_t optimizer, double lr, int64_t first_step,
+                    double beta1, double beta2, double eps, double momentum, double weight_decay, float* losses, void* scratch,
+                    uint64_t scratch_bytes, void* stream) {
+    if (part < 0 || part > 2) return fail(UMLH_E_INVALID, "%s: part=%d outside 0..2", who, part);
+    RC(check_ae_shape(who, cfg, batch_x, batch_y, UMLH_AE_MAX_BATCH, "batch_x", "batch_y"));
+    if (n_steps < 1 || n_steps > UMLH_AE_MAX_BATCH) return fail(UMLH_E_INVALID, "%s: n_steps=%d outside 1..%d", who, n_steps, UMLH_AE_MAX_BATCH);
+    if (backward_y != 0 && backward_y != 1) return fail(UMLH_E_INVALID, "%s: backward_y=%d (0: mode 'x', 1: mode 'xy')", who, backward_y);
+    if (optimizer < UMLH_OPT_SGD || optimizer > UMLH_OPT_ADAMW) return fail(UMLH_E_INVALID, "%s: unknown optimizer %d", who, optimizer);
+    RC(check_ae_tensors(who, "P", P));
+    RC(check_ae_tensors(who, "M", M));
+    if (optimizer != UMLH_OPT_SGD) RC(check_ae_tensors(who, "V", V));
+    RC(check_ae_table(who, "x", "ldx", x, ldx, batch_x, cfg->dim_obs));
+    RC(check_ae_table(who, "y", "ldy", y, ldy, batch_y, cfg->dim_obs));
+    if (!losses) return fail(UMLH_E_INVALID, "%s: losses is NULL", who);
+    if (!scratch) return fail(UMLH_E_INVALID, "%s: scratch is NULL", who);
+    RC(check_scratch(who, scratch, scratch_bytes, umlh_ae_plan_bytes(cfg, batch_x, batch_y, 1), 8));
+    for (int s = 0; s < n_steps; ++s) {
+        const OptArgs o = standalone_opt(optimizer, lr, first_step + s, beta1, beta2, eps, momentum, weight_decay);
+        HIPCHK(umlh_ae_launch_step(cfg, P, M, optimizer != UMLH_OPT_SGD ? V : nullptr, x, ldx, idx_x ? idx_x + (size_t)s * batch_x : nullptr,
+                                   batch_x, y, ldy, idx_y ? idx_y + (size_t)s * batch_y : nullptr, batch_y, backward_y, alpha_x, alpha_y,
+                                   &o, losses + (size_t)3 * s, scratch, part, (hipStream_t)stream), who);
+    }
+    return UMLH_OK;
+}
+
+int umlh_ae_train_steps(const umlh_ae_cfg_t* cfg, float* const* P, float* const* M, float* const* V, const float* x, int64_t ldx,
+                        const int32_t* idx_x, int32_t batch_x, const float* y, int64_t ldy, const int32_t* idx_y, int32_t batch_y,
+                        int32_t n_steps, int32_t backward_y, float alpha_x, float alpha_y, int32_t optimizer, double lr,
+                        int64_t first_step, double beta1, double beta2, double eps, double momentum, double weight_decay,
+                        float* losses, void* scratch, uint64_t scratch_bytes, void* stream) {
+    return ae_steps("umlh_ae_train_steps", 0, cfg, P, M, V, x, ldx, idx_x, batch_x, y, ldy, idx_y, batch_y, n_steps, backward_y, alpha_x,
+                    alpha_y, optimizer, lr, first_step, beta1, beta2, eps, momentum, weight_decay, losses, scratch, scratch_bytes, stream);
+}
+
+// benchmark only (umlh_launch.h): one launch of every step
+extern "C" int umlh_ae_bench_steps(const umlh_ae_cfg_t* cfg, float* const* P, float* const* M, float* const* V, const float* x, long long ldx,
+                                   const int* idx_x, int batch_x, const float* y, long long ldy, const int* idx_y, int batch_y, int n_steps,
+                                   int backward_y, float alpha_x, float alpha_y, int optimizer, double lr, long long first_step,
+                                   double beta1, double beta2, double eps, double momentum, double weight_decay, float* losses,
+                                   void* scratch, unsigned long long scratch_bytes, int part, void* stream) {
+    return ae_steps("umlh_ae_bench_steps", part, cfg, P, M, V, x, ldx, idx_x, batch_x, y, ldy, idx_y, batch_y, n_steps, backward_y, alpha_x,
+                    alpha_y, optimizer, lr, first_step, beta1, beta2, eps, momentum, weight_decay, losses, scratch, scratch_bytes, stream);
+}

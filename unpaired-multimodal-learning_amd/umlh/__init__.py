@@ -27,6 +27,8 @@ from .rollout import rollout_rows, seq_spectrum  # noqa: F401,E402
 from . import report  # noqa: F401,E402
 from .report import class_report, topk_classes  # noqa: F401,E402
 from . import seqload  # noqa: F401,E402
+from . import gauss  # noqa: F401,E402
+from .gauss import ae_forward, ae_train_steps  # noqa: F401,E402
 
 
 def host_cpu_budget() -> int:

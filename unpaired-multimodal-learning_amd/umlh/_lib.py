@@ -20,7 +20,7 @@ PREC_IDS = {"fp32": 0, "bf16": 1}
 N_CORE_SCALARS = 8
 N_SCALARS = 12
 
-SOURCES = ["umlh_p2p.hip", "umlh_kernels_f32.hip", "umlh_kernels_bf16.hip", "umlh_kernels_micro.hip", "umlh_kernels_seq.hip", "umlh_kernels_enc.hip", "umlh_kernels_align.hip", "umlh_kernels_align_ext.hip", "umlh_kernels_probe.hip", "umlh_kernels_softmax_probe.hip", "umlh_kernels_knn.hip", "umlh_kernels_spectral.hip", "umlh_kernels_capture.hip", "umlh_kernels_stepstats.hip", "umlh_kernels_rollout.hip", "umlh_kernels_classstats.hip", "umlh_kernels_evalreport.hip", "umlh_kernels_outlier.hip", "umlh_kernels_seqload.hip", "umlh_kernels_tabular.hip", "umlh_api.cpp", "umlh_ops.cpp", "umlh_encoder.cpp"]
+SOURCES = ["umlh_p2p.hip", "umlh_kernels_f32.hip", "umlh_kernels_bf16.hip", "umlh_kernels_micro.hip", "umlh_kernels_seq.hip", "umlh_kernels_enc.hip", "umlh_kernels_align.hip", "umlh_kernels_align_ext.hip", "umlh_kernels_probe.hip", "umlh_kernels_softmax_probe.hip", "umlh_kernels_knn.hip", "umlh_kernels_spectral.hip", "umlh_kernels_capture.hip", "umlh_kernels_stepstats.hip", "umlh_kernels_rollout.hip", "umlh_kernels_classstats.hip", "umlh_kernels_evalreport.hip", "umlh_kernels_outlier.hip", "umlh_kernels_seqload.hip", "umlh_kernels_tabular.hip", "umlh_kernels_gauss.hip", "umlh_api.cpp", "umlh_ops.cpp", "umlh_encoder.cpp"]
 
 
 class UmlhError(RuntimeError):
@@ -77,6 +77,10 @@ class EncLayer(C.Structure):
 class Hyper(C.Structure):
     _fields_ = [("lr", C.c_double), ("step", C.c_int64), ("alpha", C.c_float), ("img_alpha", C.c_float),
                 ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class AeCfg(C.Structure):                          # umlh_ae_cfg_t
+    _fields_ = [("dim_obs", C.c_int32), ("dim_common", C.c_int32), ("dim_latent", C.c_int32)]
 
 
 class RolloutCfg(C.Structure):
@@ -241,6 +245,11 @@ def _prototypes() -> dict:
         "umlh_tab_standardize": (rc, (vp, i32, i64, i32, i64, vp, i64, vp, vp, u64, vp)),
         "umlh_tab_perturb": (rc, (vp, i64, i32, i64, vp, vp, f32, f32, u64, vp, i64, vp)),
         "umlh_rows_gather": (rc, (pv, P(i32), i32, i64, vp, i32, pv, vp)),
+        # the Gaussian toy's autoencoder: forward, fused training steps
+        "umlh_ae_scratch": (u64, (P(AeCfg), i32, i32, i32)),
+        "umlh_ae_forward": (rc, (P(AeCfg), pv, vp, i64, vp, i32, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp, u64, vp)),
+        "umlh_ae_train_steps": (rc, (P(AeCfg), pv, pv, pv, vp, i64, vp, i32, vp, i64, vp, i32, i32, i32, f32, f32, i32, f64, i64,
+                                     f64, f64, f64, f64, f64, vp, vp, u64, vp)),
         # device loader of the affect datasets: first nonzero row, column and per-sequence standardisation, batch gather-pad
         "umlh_seq_first_nonzero": (rc, (vp, i64, i32, i32, vp, vp)),
         "umlh_seq_column_standardize_scratch": (u64, (i64, i32)),
