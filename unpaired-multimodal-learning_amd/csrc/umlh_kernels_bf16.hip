@@ -173,25 +173,76 @@ __device__ __forceinline__ bool fwd_ce_bf16_body(const FwdArgsB& a, const int bi
     const int row0 = (bid - sg.blk0) * TS;
     const int C = a.C, K = a.K;
 
+    // ---- prologue: every request below is UNCONDITIONAL and issued in an order that lets counted waits (vmcnt retires in
+    // order) leave the W stream in flight -- no load waits for a load it does not depend on:
+    //   1. the row ids of this thread's X pieces and of this lane's labels           (NPX + STW loads)
+    //   2. ring slots 0 .. PD/2-1: W starts flowing before any index value is used   (CTW * PD/2 loads)
+    //   3. the X pieces of the first K block, behind a wait that covers group 1 only (NPX loads)
+    //   4. ring slots PD/2 .. PD-1, then the labels                                  (CTW * PD/2 + STW loads)
+    // and the first barrier's ds_writes wait for the X pieces with group 4 still outstanding (half a ring is what
+    // the stream moves during the row-id round trip).  The waits are the compiler's own counts; they stay counted because no
+    // group sits under a branch -- a conditional load that meets an unconditional one at a join is merged to vmcnt(0) (the
+    // ring used to sit under `if (live)`: a full drain in front of the X loads; DESIGN 7.6 has the same trap in dw_f32x3).
+    // Without an index vector the row-id load reads a dummy word of the W shadow and a select discards it; a wave that is not
+    // live reads its fragments (in bounds: the shadow is padded to CPAD classes) like any other and never uses them.
     // X pieces of this thread: piece p -> row p / (XK/8), 16-B column p % (XK/8).  Rows past the
     // segment are clamped to its last row (finite garbage the epilogue discards).
-    const u16* xsrc[NPX];
+    const int64_t* const no_index = reinterpret_cast<const int64_t*>(a.W);
+    int xrow_id[NPX], lrow_id[STW];
+    int64_t xrid[NPX], lrid[STW];
 #pragma unroll
     for (int q = 0; q < NPX; ++q) {
-        int p = tid + 512 * q;
-        int r = min(row0 + p / (XK / 8), sg.rows - 1);
-        int64_t rid = sg.feat_index ? sg.feat_index[r] : (int64_t)r;
-        xsrc[q] = sg.feats + (size_t)rid * sg.ld + 8 * (p % (XK / 8));
+        xrow_id[q] = min(row0 + (tid + 512 * q) / (XK / 8), sg.rows - 1);
+        xrid[q] = *(sg.feat_index ? sg.feat_index + xrow_id[q] : no_index);
     }
-
-    // labels of this lane's samples: two dependent global loads (row id, then label) issued NOW so
-    // their latency hides behind the whole main loop instead of stalling the epilogue
-    int labs[STW];
 #pragma unroll
     for (int st = 0; st < STW; ++st) {
-        int r = min(row0 + ws * 32 * STW + st * 32 + l31, sg.rows - 1);
-        labs[st] = (int)sg.labels[sg.label_index ? sg.label_index[r] : (int64_t)r];
+        lrow_id[st] = min(row0 + ws * 32 * STW + st * 32 + l31, sg.rows - 1);
+        lrid[st] = *(sg.label_index ? sg.label_index + lrow_id[st] : no_index);
     }
+    __builtin_amdgcn_sched_barrier(0);
+
+    const int nks = K / 16;                                      // total k-steps (multiple of PD)
+    // fragment (k-step ks, class tile t) = 1 KiB at W + ((ks * CPAD/32 + t) * 64 + lane) * 8
+    const u16* wlane = a.W + ((size_t)(wc * CTW) * 64 + lane) * 8;
+    auto wfrag = [&](int ks, int ct) -> bf16x8 {
+        return *reinterpret_cast<const bf16x8*>(wlane + ((size_t)ks * (CPAD / 32) + ct) * 512);
+    };
+    // a wave whose sample rows all lie past the segment (batch 32 in a 64-row block) or whose classes are all
+    // padding issues no MFMAs and no refills (wave-uniform); its accumulators stay 0 and are masked below
+    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+    const bool live = row0 + (wave_u / WC) * 32 * STW < sg.rows && (wave_u % WC) * CTW * 32 < C;
+    bf16x8 ring[PD][CTW];
+#pragma unroll
+    for (int d = 0; d < PD / 2; ++d)
+#pragma unroll
+        for (int ct = 0; ct < CTW; ++ct) ring[d][ct] = wfrag(min(d, nks - 1), ct);
+    __builtin_amdgcn_sched_barrier(0);
+
+    const u16* xsrc[NPX];
+    u32x4 xr0[NPX];                                              // the X pieces of the first K block
+    const int kbw0 = min(XK, K);
+#pragma unroll
+    for (int q = 0; q < NPX; ++q) {
+        const int64_t rid = sg.feat_index ? xrid[q] : (int64_t)xrow_id[q];
+        const int col = 8 * ((tid + 512 * q) % (XK / 8));
+        xsrc[q] = sg.feats + (size_t)rid * sg.ld + col;
+        xr0[q] = *reinterpret_cast<const u32x4*>(xsrc[q] + min(col, kbw0 - 8) - col);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int d = PD / 2; d < PD; ++d)
+#pragma unroll
+        for (int ct = 0; ct < CTW; ++ct) ring[d][ct] = wfrag(min(d, nks - 1), ct);
+    __builtin_amdgcn_sched_barrier(0);
+    // labels of this lane's samples: the second of two dependent global loads (row id, then label), issued NOW so that its
+    // latency hides behind the whole main loop instead of stalling the epilogue -- and last, so that the X wait in front of
+    // the first barrier leaves it in flight.  The low dword only: with the whole int64 requested, its dead high register is
+    // reused while the load is in flight, and that write waits for it with vmcnt(0).
+    int labs[STW];
+#pragma unroll
+    for (int st = 0; st < STW; ++st)
+        labs[st] = *reinterpret_cast<const int*>(sg.labels + (sg.label_index ? lrid[st] : (int64_t)lrow_id[st]));
 
     f32x16 acc[CTW][STW];
 #pragma unroll
@@ -201,43 +252,24 @@ __device__ __forceinline__ bool fwd_ce_bf16_body(const FwdArgsB& a, const int bi
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[ct][st][i] = 0.f;
 
-    const int nks = K / 16;                                      // total k-steps (multiple of PD)
-    // fragment (k-step ks, class tile t) = 1 KiB at W + ((ks * CPAD/32 + t) * 64 + lane) * 8
-    const u16* wlane = a.W + ((size_t)(wc * CTW) * 64 + lane) * 8;
-    auto wfrag = [&](int ks, int ct) -> bf16x8 {
-        return *reinterpret_cast<const bf16x8*>(wlane + ((size_t)ks * (CPAD / 32) + ct) * 512);
-    };
-    // a wave whose sample rows all lie past the segment (batch 32 in a 64-row block) or whose classes are all
-    // padding neither streams W nor issues MFMAs (wave-uniform); its accumulators stay 0 and are masked below
-    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-    const bool live = row0 + (wave_u / WC) * 32 * STW < sg.rows && (wave_u % WC) * CTW * 32 < C;
-    bf16x8 ring[PD][CTW];
-    if (live) {
-#pragma unroll
-        for (int d = 0; d < PD; ++d)
-#pragma unroll
-            for (int ct = 0; ct < CTW; ++ct) ring[d][ct] = wfrag(min(d, nks - 1), ct);
-    }
-
     STAMP(1);
-    for (int kb0 = 0; kb0 < (UMLH_ABL(a.dbg == 2 || a.dbg == 5) ? 0 : K); kb0 += XK) {
-        const int kbw = min(XK, K - kb0);                        // multiple of 128
-        // ---- stage the X block: global -> registers -> LDS ----
-        u32x4 xr[NPX];
-#pragma unroll
-        for (int q = 0; q < NPX; ++q) {
-            int col = 8 * ((tid + 512 * q) % (XK / 8));
-            xr[q] = *reinterpret_cast<const u32x4*>(xsrc[q] + kb0 + min(col, kbw - 8) - col);
-        }
-        if (hook != nullptr && kb0 == 0 && tid < 4) hook->verdict[tid] = tag_older(hook->old, hook->epoch) ? 1 : 0;
-        __syncthreads();                                         // previous block fully consumed
-        if (hook != nullptr && kb0 == 0 && !hook->verdict[0]) return false;   // (uniform: the forward tile's verdict)
+    // ---- stage an X block: registers -> LDS, between the barrier that ends the previous block's reads and the one that
+    // publishes this block ----
+    auto stage_x = [&](const u32x4 (&xr)[NPX]) {
 #pragma unroll
         for (int q = 0; q < NPX; ++q) {
             int p = tid + 512 * q;
             *reinterpret_cast<u32x4*>(Xt + (p / (XK / 8)) * XRS + 8 * (p % (XK / 8))) = xr[q];
         }
         __syncthreads();
+    };
+    // the first block: its pieces were requested above; the take verdict (TakeHook) is settled in front of the first barrier
+    if (hook != nullptr && tid < 4) hook->verdict[tid] = tag_older(hook->old, hook->epoch) ? 1 : 0;
+    __syncthreads();
+    if (hook != nullptr && !hook->verdict[0]) return false;      // (uniform: the forward tile's verdict; nothing was stored)
+    stage_x(xr0);
+    for (int kb0 = 0; !UMLH_ABL(a.dbg == 2 || a.dbg == 5);) {
+        const int kbw = min(XK, K - kb0);                        // multiple of 128
         // ---- k-steps of this block ----
         const int ks0 = kb0 / 16, nst = kbw / 16;                // nst is a multiple of PD
         const u16* xrow = Xt + (ws * 32 * STW + l31) * XRS + h * 8;
@@ -277,6 +309,18 @@ __device__ __forceinline__ bool fwd_ce_bf16_body(const FwdArgsB& a, const int bi
             for (int s = 0; s < nfull; s += PD) kgroup(s, std::true_type{});
             if (last_block) kgroup(nst - PD, std::false_type{});
         }
+        kb0 += XK;
+        if (kb0 >= K) break;
+        // ---- K > XK: the next X block, requested and staged as before (global -> registers -> LDS) ----
+        const int kbn = min(XK, K - kb0);
+        u32x4 xr[NPX];
+#pragma unroll
+        for (int q = 0; q < NPX; ++q) {
+            int col = 8 * ((tid + 512 * q) % (XK / 8));
+            xr[q] = *reinterpret_cast<const u32x4*>(xsrc[q] + kb0 + min(col, kbn - 8) - col);
+        }
+        __syncthreads();                                         // previous block fully consumed
+        stage_x(xr);
     }
 
     STAMP(2);
@@ -1041,27 +1085,41 @@ __device__ __forceinline__ int dw_bf16_body_dma(const DwArgsB& g, const int vbid
     }
     __syncthreads();                                    // (also drains the id loads: no ordinary vector load is pending from here on)
     DSTAMP(1);
+    // GATED: BOTH stages are filled before the loop -- the feature halves of chunks 0 and 1 in front of the gate, their dZ^T
+    // halves behind it -- and iteration 0 issues nothing.  (With chunk 1 issued by iteration 0 and awaited at its end, stage 1
+    // stood empty through the whole gate wait and that iteration waited for its DMA: DESIGN 7.1.)  Steady
+    // state is what it was: two stages allow no more than one chunk in flight behind the one being read.
     issueF(0, 0);
+    if (GATED) issueF(1, 1);
     if (GATED) {
         if (wave == 0) {
             const int b0 = kb / gate.ts, nb = (min(ke, gate.total_cols) - kb + gate.ts - 1) / gate.ts;
             const int rc = nb > 0 ? tasks_wait(gate.ctl, gate.fwd_base + b0, nb, lane, 1u) : TW_OK;
             if (lane == 0) *sh_rc = rc;
         }
-        __syncthreads();                                // (emits vmcnt(0): the feature pieces above have landed -- harmless, they are needed next)
+        __syncthreads();                                // (emits vmcnt(0): the feature pieces above have landed -- harmless, they are needed next,
+                                                        // and on the way out below no LDS-DMA may be in flight: a forward tile taken during
+                                                        // the wait reuses this LDS)
         const int rc = *sh_rc;
         __syncthreads();                                // (the word is rewritten by the next wait)
         if (rc != TW_OK) return rc;
         if (gate.timeline && tid == 0) gate.timeline[(size_t)(gate.self_base + vbid) * 4 + 1] = __builtin_amdgcn_s_memrealtime();
     }
     issueA(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (GATED) {
+        issueA(1, 1);
+        // chunk 0 has landed; in flight stay only the four dZ^T pieces of chunk 1 just issued (the feature pieces of both
+        // chunks were drained by the gate's barrier, the dZ^T pieces of chunk 0 are older than those four)
+        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    } else {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
     __builtin_amdgcn_s_barrier();
     DSTAMP(2);
     for (int c = 0; c < nchunks; ++c) {
         const int st = c & 1;
         // the other stage was last read in iteration c-1, which every wave has left (the barrier below)
-        if (c + 1 < nchunks) { issueA(c + 1, st ^ 1); issueF(c + 1, st ^ 1); }
+        if (c + 1 < nchunks && !(GATED && c == 0)) { issueA(c + 1, st ^ 1); issueF(c + 1, st ^ 1); }   // (GATED: chunk 1 is on its way)
         // fragment reads run four k-steps ahead of their MFMAs (inline asm: behind the ds_read_tr16 builtin hipcc drains the
         // LDS-DMA queue with s_waitcnt vmcnt(0) in front of every chunk's first read, and its own waits do not count asm loads
         // anyway); every k-step waits for ITS four reads with a counted lgkmcnt (LDS operations complete in order; at most 16
