@@ -1153,6 +1153,46 @@ int  umlh_ae_train_steps(const umlh_ae_cfg_t* cfg, float* const* P, float* const
                          int64_t first_step, double beta1, double beta2, double eps, double momentum, double weight_decay,
                          float* losses, void* scratch, uint64_t scratch_bytes, void* stream);
 
+/* Grouped forms: up to UMLH_AE_MAX_GROUP independent runs (members) in one launch pair per step, for sweeps whose single runs
+ * leave most of the device idle.  Additive to ABI v11.  A member is described by the arguments of the single-run entry point and
+ * keeps their meaning field for field: the envelope, NULL index arrays, an absent view, V == NULL under sgd, backward_y = 0.
+ * Members may differ in every field, cfg included; all take the same n_steps.
+ *   BIT IDENTITY: after umlh_ae_train_steps_grouped every member's P, M, V and losses hold, bit for bit, what
+ *   umlh_ae_train_steps with that member's arguments leaves; every output of umlh_ae_forward_grouped is bit for bit that of
+ *   umlh_ae_forward.  A workgroup of a grouped launch finds its member and then runs the single-run kernel's own body.
+ * Members may share feature tables and index arrays.  They may NOT share parameter or moment tensors: a device pointer that
+ * occurs twice among all members' P / M / V (V of an sgd member is not looked at) is UMLH_E_INVALID.
+ * Every check happens before the first HIP call; the message names the function, the member (`member i`) and the argument.
+ * The members' descriptors and the optimizer constants of every step (formed on the host as by umlh_ae_train_steps) reach the
+ * device in ONE asynchronous upload per call from pinned staging that is reused behind events: no upload per step and no host
+ * synchronisation (a call waits only for the upload of the call before the previous one on the same device).  The device side
+ * of these tables lives in the caller's scratch, in front of one private region per member: the size queries count both, which is
+ * why the training query takes n_steps.  Launches per step: two, whatever n_items is.  scratch: 8-byte aligned. */
+#define UMLH_AE_MAX_GROUP 64
+typedef struct {                 /* one run of a training group: the arguments of umlh_ae_train_steps */
+    umlh_ae_cfg_t cfg;
+    float* const* P; float* const* M; float* const* V;     /* HOST arrays of 16 device pointers */
+    const float* x; int64_t ldx; const int32_t* idx_x; int32_t batch_x;
+    const float* y; int64_t ldy; const int32_t* idx_y; int32_t batch_y;
+    int32_t backward_y; float alpha_x, alpha_y;
+    int32_t optimizer; double lr; int64_t first_step; double beta1, beta2, eps, momentum, weight_decay;
+    float* losses;               /* [n_steps, 3] */
+} umlh_ae_group_item_t;
+typedef struct {                 /* one run of an evaluation group: the arguments of umlh_ae_forward */
+    umlh_ae_cfg_t cfg; const float* const* P;
+    const float* x; int64_t ldx; const int32_t* idx_x; int32_t n_x;
+    const float* y; int64_t ldy; const int32_t* idx_y; int32_t n_y;
+    float* losses; float* rec_x; float* rec_y; float* emb_x; float* emb_y;
+} umlh_ae_eval_item_t;
+/* Scratch bytes of the grouped calls, from the one plan their launchers use: a multiple of 256; 0 on invalid arguments (items
+ * NULL, n_items outside 1..UMLH_AE_MAX_GROUP, n_steps outside 1..UMLH_AE_MAX_BATCH, a member outside the single-run envelope). */
+uint64_t umlh_ae_group_scratch(const umlh_ae_group_item_t* items, int32_t n_items, int32_t n_steps);
+uint64_t umlh_ae_eval_group_scratch(const umlh_ae_eval_item_t* items, int32_t n_items);
+int  umlh_ae_train_steps_grouped(const umlh_ae_group_item_t* items, int32_t n_items, int32_t n_steps,
+                                 void* scratch, uint64_t scratch_bytes, void* stream);
+int  umlh_ae_forward_grouped(const umlh_ae_eval_item_t* items, int32_t n_items,
+                             void* scratch, uint64_t scratch_bytes, void* stream);
+
 /* ---- device loader of the affect datasets (mosi, mosei, humor, sarcasm): what Affectdataset.__getitem__ and the _process_1
  * collate of MultiBench/datasets/affect/get_data.py:159-261,418-444 do per sample and per batch on the host, as three table-build
  * passes and one step-path kernel.  Additive to ABI v11: umlh_version() is unchanged, callers detect the

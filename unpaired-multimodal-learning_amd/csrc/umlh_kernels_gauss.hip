@@ -30,9 +30,19 @@
 //   rounds once, and forms loss = alpha_x loss_x + alpha_y loss_y as two fp32 products and one add (no contraction).
 // No float atomics, no workgroup waits on another; grids and summation orders are functions of the shapes alone: results are bitwise
 // reproducible across calls, streams and CU counts.  A row's activations depend on the parameters and the row alone.
+//
+// ae_rows and ae_update are the instantiations ae_rows_k<false> and ae_update_k<false> of the kernel templates below.
+// Grouped forms: ae_rows_grouped = ae_rows_k<true>, ae_update_grouped = ae_update_k<true> and ae_loss_grouped
+//   run several independent runs (members) in one launch each.  A workgroup finds its member from blockIdx.x and a prefix array of
+//   first workgroups, copies the member's descriptor from a device table that stays constant for the whole call, and then runs the
+//   very statements the single-run instantiation runs: per member the results are bit for bit those of the single-run launches.
+//   Members share nothing that is written: each has its own scratch region (ae_group_plan).  No atomics, no waits.
 #include "umlh_common.h"
 #include "umlh_launch.h"
 #include <algorithm>
+#include <climits>
+#include <cstring>
+#include <mutex>
 
 namespace {
 
@@ -165,12 +175,49 @@ __device__ __forceinline__ void ae_linear(const float* __restrict__ W, int N, in
     __syncthreads();
 }
 
-__global__ __launch_bounds__(AE_THREADS) void ae_rows(const AeRowArgs a) {
+// The member of workgroup wg of a grouped launch: the largest m with first[m] <= wg.  first[i] = the first workgroup of member i
+// (strictly ascending: every member has a workgroup; first[0] = 0), first[n] = the grid, INT_MAX from there to entry
+// UMLH_AE_MAX_GROUP.  A uniform binary search: six dependent scalar loads within one 256-byte block.
+__device__ __forceinline__ int ae_member(const int* __restrict__ first, int wg) {
+    static_assert(UMLH_AE_MAX_GROUP == 64, "the search below walks 64 entries");
+    int m = 0;
+#pragma unroll
+    for (int step = UMLH_AE_MAX_GROUP / 2; step >= 1; step >>= 1)
+        if (wg >= first[m + step]) m += step;
+    return m;
+}
+
+// Launch A, the one statement of every product of the rows path, in two instantiations.
+//   GROUPED = false (ae_rows): a is the run's descriptor, workgroup blockIdx.x is one of its (view, 16-row tile) pairs; tab, first,
+//     n_members and step are not read.
+//   GROUPED = true (ae_rows_grouped): a arrives unset.  The workgroup finds its member m in first, copies from tab[m] (a device
+//     table that stays as it is for the whole call) the fields the body reads into a, its own view as view 0 of a one-view run,
+//     and forms what depends on the step from step.  From there on it is the same code on the same values.  The copy into locals
+//     matters: a descriptor read through a pointer would be loaded again behind every memory clobber of ae_linear.
+// The body is kept in the kernel and not in a __device__ function taking the descriptor by reference: across such a boundary the
+// compiler reads both views' fields up front (69 -> 106 SGPRs and 72 spilled in ae_rows; profiles/gaussian_group_resources.txt).
+template <bool GROUPED>
+__global__ __launch_bounds__(AE_THREADS) void ae_rows_k(AeRowArgs a, const AeRowArgs* __restrict__ tab, const int* __restrict__ first,
+                                                        int n_members, int step) {
     extern __shared__ __attribute__((aligned(16))) float ae_lds[];
+    int wg = (int)blockIdx.x;
+    if constexpr (GROUPED) {
+        const int m = ae_member(first, wg);
+        const AeRowArgs& g = tab[m];
+        const int local = wg - first[m], tx = g.tiles_x, gv = local >= tx ? 1 : 0;
+        a.v[0] = g.v[gv];
+        if (a.v[0].idx) a.v[0].idx += (size_t)step * (size_t)a.v[0].rows;   // the step takes idx[step * batch ..)
+        a.tiles_x = INT_MAX;                                            // every workgroup is view 0's
+        a.we0 = g.we0; a.be0 = g.be0; a.we2 = g.we2; a.be2 = g.be2;
+        a.wd0 = g.wd0; a.bd0 = g.bd0; a.wd2 = g.wd2; a.bd2 = g.bd2;
+        a.D = g.D; a.C = g.C; a.L = g.L;
+        wg = local - (gv ? tx : 0);
+        __builtin_assume(wg < INT_MAX);                                 // so that the view index below is the constant 0
+    }
     const int D = a.D, C = a.C, L = a.L;
-    const int vi = (int)blockIdx.x >= a.tiles_x ? 1 : 0;
+    const int vi = wg >= a.tiles_x ? 1 : 0;
     const AeView& V = a.v[vi];
-    const int tile = (int)blockIdx.x - (vi ? a.tiles_x : 0);
+    const int tile = wg - (vi ? a.tiles_x : 0);
     const int row0 = tile * AE_ROWS, n = V.rows, tid = threadIdx.x;
     const int maxw = ae_pad16(D > C ? (D > L ? D : L) : (C > L ? C : L));
     float* X = ae_lds;
@@ -305,11 +352,33 @@ __global__ __launch_bounds__(AE_UPD_THREADS) void ae_loss(const AeLoss l) {
     ae_loss_body(l, red);
 }
 
-__global__ __launch_bounds__(AE_UPD_THREADS) void ae_update(const AeUpdArgs a) {
+// Launch B, the one statement of the update path, in two instantiations (as ae_rows_k).
+//   GROUPED = false (ae_update): a is the run's descriptor; workgroup blockIdx.x is one of its weight tiles or its loss workgroup.
+//   GROUPED = true (ae_update_grouped): a arrives unset.  Member m's workgroups are its weight tiles and then its loss workgroup;
+//     the workgroup copies its own tensor from tab[m] into a as the only tensor, the member's optimizer constants of the step from
+//     opt ([n_steps][n_members], formed on the host), and the loss descriptor with out moved to the step's three floats.
+template <bool GROUPED>
+__global__ __launch_bounds__(AE_UPD_THREADS) void ae_update_k(AeUpdArgs a, const AeUpdArgs* __restrict__ tab, const int* __restrict__ first,
+                                                              const OptArgs* __restrict__ opt, int n_members, int step) {
     __shared__ double red[AE_UPD_THREADS];
     __shared__ float part[AE_UPD_WAVES][256];
     __shared__ float bpart[16][16];
-    const int b = blockIdx.x, tid = threadIdx.x;
+    int b = blockIdx.x;
+    if constexpr (GROUPED) {
+        const int m = ae_member(first, b);
+        const AeUpdArgs& g = tab[m];
+        b -= first[m];
+        int gi = 0;
+        for (int i = 1; i < g.count; ++i)
+            if (b >= g.t[i].blk0) gi = i;
+        a.t[0] = g.t[gi];                                               // unused by the loss workgroup
+        a.count = 1;
+        a.tiles = g.tiles;
+        a.o = opt[(size_t)step * (size_t)n_members + m];
+        a.loss = g.loss;
+        a.loss.out += (size_t)3 * (size_t)step;
+    }
+    const int tid = threadIdx.x;
     if (b >= a.tiles) {
         ae_loss_body(a.loss, red);
         return;
@@ -381,6 +450,14 @@ __global__ __launch_bounds__(AE_UPD_THREADS) void ae_update(const AeUpdArgs a) {
     }
 }
 
+// the losses of a grouped evaluation forward: one workgroup per member (none asked for: nothing to do)
+__global__ __launch_bounds__(AE_UPD_THREADS) void ae_loss_grouped(const AeLoss* __restrict__ tab) {
+    __shared__ double red[AE_UPD_THREADS];
+    const AeLoss l = tab[blockIdx.x];
+    if (l.out == nullptr) return;                                        // uniform
+    ae_loss_body(l, red);
+}
+
 inline size_t ae_lds_bytes(int D, int C, int L) {
     const size_t maxw = (size_t)ae_pad16(std::max(D, std::max(C, L)));
     return 2 * maxw * AE_ROWS * sizeof(float) + AE_THREADS * sizeof(double);
@@ -411,6 +488,33 @@ inline AePlan ae_plan(int D, int C, int L, int rows_x, int rows_y, int train) {
     return p;
 }
 
+// The scratch plan of a grouped call, built on ae_plan.  In front the tables that one upload per call fills: the members' launch-A
+// descriptors, their launch-B descriptors (training) or loss descriptors (evaluation), the two prefix arrays of first workgroups
+// and (training) the [n_steps][n] optimizer constants.  Behind them one private ae_plan region per member: no member's workgroups
+// read or write another's.  n_steps > 0: a training group; n_steps == 0: an evaluation group.
+struct AeGroupPlan {
+    long long rows, upd, first_a, first_b, opt;
+    long long head;                                   // bytes of the uploaded tables, from offset 0
+    long long member[UMLH_AE_MAX_GROUP];
+    long long bytes;
+};
+
+AeGroupPlan ae_group_plan(int n, int n_steps, const umlh_ae_cfg_t* const* cfg, const int* rows_x, const int* rows_y) {
+    AeGroupPlan p = {};
+    ScratchLayout lay;
+    const int train = n_steps > 0;
+    p.rows = lay.take((long long)n * (long long)sizeof(AeRowArgs));
+    p.upd = lay.take((long long)n * (long long)(train ? sizeof(AeUpdArgs) : sizeof(AeLoss)));
+    p.first_a = lay.take((long long)(UMLH_AE_MAX_GROUP + 1) * (long long)sizeof(int));
+    p.first_b = lay.take((long long)(UMLH_AE_MAX_GROUP + 1) * (long long)sizeof(int));
+    p.opt = lay.take((long long)n_steps * n * (long long)sizeof(OptArgs));
+    p.head = lay.end;
+    for (int i = 0; i < n; ++i)
+        p.member[i] = lay.take(ae_plan(cfg[i]->dim_obs, cfg[i]->dim_common, cfg[i]->dim_latent, rows_x[i], rows_y[i], train).bytes);
+    p.bytes = lay.end;
+    return p;
+}
+
 void ae_fill_rows(AeRowArgs& r, const umlh_ae_cfg_t* cfg, const float* const* P) {
     r.D = cfg->dim_obs; r.C = cfg->dim_common; r.L = cfg->dim_latent;
     r.v[0].w_in = P[0]; r.v[0].b_in = P[1]; r.v[1].w_in = P[2]; r.v[1].b_in = P[3];
@@ -418,24 +522,11 @@ void ae_fill_rows(AeRowArgs& r, const umlh_ae_cfg_t* cfg, const float* const* P)
     r.v[0].w_out = P[12]; r.v[0].b_out = P[13]; r.v[1].w_out = P[14]; r.v[1].b_out = P[15];
 }
 
-int ae_launch_rows(const AeRowArgs& r, hipStream_t st) {
-    if (int e = raise_lds_limit<&ae_rows>((int)ae_lds_bytes(UMLH_AE_MAX_OBS, UMLH_AE_MAX_COMMON, UMLH_AE_MAX_LATENT))) return e;
-    const int tiles_y = (r.v[1].rows + AE_ROWS - 1) / AE_ROWS;
-    hipLaunchKernelGGL(ae_rows, dim3((unsigned)(r.tiles_x + tiles_y)), dim3(AE_THREADS), ae_lds_bytes(r.D, r.C, r.L), st, r);
-    return (int)hipGetLastError();
-}
-
-}  // namespace
-
-extern "C" unsigned long long umlh_ae_plan_bytes(const umlh_ae_cfg_t* cfg, int rows_x, int rows_y, int train) {
-    return (unsigned long long)ae_plan(cfg->dim_obs, cfg->dim_common, cfg->dim_latent, rows_x, rows_y, train).bytes;
-}
-
-extern "C" int umlh_ae_launch_forward(const umlh_ae_cfg_t* cfg, const float* const* P, const float* x, long long ldx, const int* idx_x,
-                                      int n_x, const float* y, long long ldy, const int* idx_y, int n_y, float* losses, float* rec_x,
-                                      float* rec_y, float* emb_x, float* emb_y, void* scratch, hipStream_t st) {
+// The descriptors of one evaluation forward on its scratch region: launch A's (r) and the loss launch's (l; l.out NULL: no losses).
+void ae_build_forward(AeRowArgs& r, AeLoss& l, const umlh_ae_cfg_t* cfg, const float* const* P, const float* x, long long ldx,
+                      const int* idx_x, int n_x, const float* y, long long ldy, const int* idx_y, int n_y, float* losses, float* rec_x,
+                      float* rec_y, float* emb_x, float* emb_y, void* scratch) {
     const AePlan p = ae_plan(cfg->dim_obs, cfg->dim_common, cfg->dim_latent, n_x, n_y, 0);
-    AeRowArgs r = {};
     ae_fill_rows(r, cfg, P);
     const float* tab[2] = {x, y};
     const long long ld[2] = {ldx, ldy};
@@ -443,7 +534,6 @@ extern "C" int umlh_ae_launch_forward(const umlh_ae_cfg_t* cfg, const float* con
     const int rows[2] = {n_x, n_y};
     float* rec[2] = {rec_x, rec_y};
     float* emb[2] = {emb_x, emb_y};
-    AeLoss l = {};
     for (int v = 0; v < 2; ++v) {
         AeView& V = r.v[v];
         V.table = tab[v]; V.idx = idx[v]; V.ld = ld[v]; V.rows = rows[v]; V.rec = rec[v]; V.emb = emb[v];
@@ -452,23 +542,16 @@ extern "C" int umlh_ae_launch_forward(const umlh_ae_cfg_t* cfg, const float* con
         l.partial[v] = V.partial; l.tiles[v] = (rows[v] + AE_ROWS - 1) / AE_ROWS; l.rows[v] = rows[v];
     }
     r.tiles_x = l.tiles[0];
-    if (int e = ae_launch_rows(r, st)) return e;
-    if (losses) {
-        l.D = cfg->dim_obs; l.out = losses; l.n_out = 2;
-        hipLaunchKernelGGL(ae_loss, dim3(1), dim3(AE_UPD_THREADS), 0, st, l);
-    }
-    return (int)hipGetLastError();
+    l.D = cfg->dim_obs; l.out = losses; l.n_out = 2;
 }
 
-// one training step: launch A, launch B.  idx_x / idx_y and losses are the step's own.  part: 0 = the step; 1 = launch A alone,
-// 2 = launch B alone on the scratch an earlier whole step left (umlh_ae_bench_steps only: not a training step).
-extern "C" int umlh_ae_launch_step(const umlh_ae_cfg_t* cfg, float* const* P, float* const* M, float* const* V, const float* x,
-                                   long long ldx, const int* idx_x, int batch_x, const float* y, long long ldy, const int* idx_y,
-                                   int batch_y, int backward_y, float alpha_x, float alpha_y, const OptArgs* o, float* losses,
-                                   void* scratch, int part, hipStream_t st) {
+// The descriptors of one training step of one run on its scratch region: launch A's (r) and launch B's (u, all but the optimizer
+// constants u.o).  idx_x / idx_y and losses are the step's own.
+void ae_build_step(AeRowArgs& r, AeUpdArgs& u, const umlh_ae_cfg_t* cfg, float* const* P, float* const* M, float* const* V, const float* x,
+                   long long ldx, const int* idx_x, int batch_x, const float* y, long long ldy, const int* idx_y, int batch_y,
+                   int backward_y, float alpha_x, float alpha_y, float* losses, void* scratch) {
     const int D = cfg->dim_obs, C = cfg->dim_common, L = cfg->dim_latent;
     const AePlan p = ae_plan(D, C, L, batch_x, batch_y, 1);
-    AeRowArgs r = {};
     ae_fill_rows(r, cfg, P);
     const float* tab[2] = {x, y};
     const long long ld[2] = {ldx, ldy};
@@ -476,7 +559,6 @@ extern "C" int umlh_ae_launch_step(const umlh_ae_cfg_t* cfg, float* const* P, fl
     const int rows[2] = {batch_x, batch_y};
     const float alpha[2] = {alpha_x, alpha_y};
     const int back[2] = {batch_x > 0, batch_y > 0 && backward_y};
-    AeUpdArgs u = {};
     for (int v = 0; v < 2; ++v) {
         AeView& W = r.v[v];
         W.table = tab[v]; W.idx = idx[v]; W.ld = ld[v]; W.rows = rows[v]; W.rec = nullptr; W.emb = nullptr;
@@ -513,9 +595,193 @@ extern "C" int umlh_ae_launch_step(const umlh_ae_cfg_t* cfg, float* const* P, fl
         blk += ((f.N + 15) / 16) * T.kt;
     }
     u.tiles = blk;
+}
+
+inline int ae_tiles(const AeRowArgs& r) { return r.tiles_x + (r.v[1].rows + AE_ROWS - 1) / AE_ROWS; }
+
+int ae_launch_rows(const AeRowArgs& r, hipStream_t st) {
+    if (int e = raise_lds_limit<&ae_rows_k<false>>((int)ae_lds_bytes(UMLH_AE_MAX_OBS, UMLH_AE_MAX_COMMON, UMLH_AE_MAX_LATENT))) return e;
+    hipLaunchKernelGGL(ae_rows_k<false>, dim3((unsigned)ae_tiles(r)), dim3(AE_THREADS), ae_lds_bytes(r.D, r.C, r.L), st, r, nullptr, nullptr, 0, 0);
+    return (int)hipGetLastError();
+}
+
+// Pinned staging of the grouped calls' tables: two buffers per device, each reused once the copy of its last use has finished (an
+// event behind that copy), grown when a call needs more.  The source of the asynchronous upload therefore outlives it, and a call
+// waits on the host only for a copy that is two calls old.
+struct AeStage {
+    unsigned char* buf[2];
+    size_t cap[2];
+    hipEvent_t ev[2];
+    bool used[2];
+    int next;
+    bool ready;
+};
+AeStage g_ae_stage[64];
+std::mutex g_ae_stage_mu;
+
+// dst[0, bytes) = what fill writes into a staging buffer, as one copy on st
+template <class Fill>
+int ae_upload(void* dst, size_t bytes, hipStream_t st, Fill fill) {
+    int dev = 0;
+    if (hipError_t e = hipGetDevice(&dev)) return (int)e;
+    std::lock_guard<std::mutex> lk(g_ae_stage_mu);
+    AeStage& S = g_ae_stage[dev & 63];
+    if (!S.ready) {
+        for (int i = 0; i < 2; ++i)
+            if (hipError_t e = hipEventCreateWithFlags(&S.ev[i], hipEventDisableTiming)) return (int)e;
+        S.ready = true;
+    }
+    const int i = S.next;
+    S.next ^= 1;
+    if (S.used[i])
+        if (hipError_t e = hipEventSynchronize(S.ev[i])) return (int)e;
+    if (S.cap[i] < bytes) {
+        if (S.buf[i]) (void)hipHostFree(S.buf[i]);
+        S.buf[i] = nullptr;
+        S.cap[i] = 0;
+        const size_t cap = (bytes + 65535) / 65536 * 65536;
+        if (hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&S.buf[i]), cap, hipHostMallocDefault)) return (int)e;
+        S.cap[i] = cap;
+    }
+    fill(S.buf[i]);
+    if (hipError_t e = hipMemcpyAsync(dst, S.buf[i], bytes, hipMemcpyHostToDevice, st)) return (int)e;
+    S.used[i] = true;
+    return (int)hipEventRecord(S.ev[i], st);
+}
+
+// first[i] = first workgroup of member i; first[n] = the grid; INT_MAX from there on
+void ae_fill_first(int* first, const int* counts, int n) {
+    int at = 0;
+    for (int i = 0; i <= UMLH_AE_MAX_GROUP; ++i) {
+        first[i] = i <= n ? at : INT_MAX;
+        if (i < n) at += counts[i];
+    }
+}
+
+int ae_launch_rows_grouped(const AeRowArgs* tab, const int* first, int n, int grid, size_t lds, int s, hipStream_t st) {
+    if (int e = raise_lds_limit<&ae_rows_k<true>>((int)ae_lds_bytes(UMLH_AE_MAX_OBS, UMLH_AE_MAX_COMMON, UMLH_AE_MAX_LATENT))) return e;
+    hipLaunchKernelGGL(ae_rows_k<true>, dim3((unsigned)grid), dim3(AE_THREADS), lds, st, AeRowArgs{}, tab, first, n, s);
+    return (int)hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" unsigned long long umlh_ae_plan_bytes(const umlh_ae_cfg_t* cfg, int rows_x, int rows_y, int train) {
+    return (unsigned long long)ae_plan(cfg->dim_obs, cfg->dim_common, cfg->dim_latent, rows_x, rows_y, train).bytes;
+}
+
+extern "C" int umlh_ae_launch_forward(const umlh_ae_cfg_t* cfg, const float* const* P, const float* x, long long ldx, const int* idx_x,
+                                      int n_x, const float* y, long long ldy, const int* idx_y, int n_y, float* losses, float* rec_x,
+                                      float* rec_y, float* emb_x, float* emb_y, void* scratch, hipStream_t st) {
+    AeRowArgs r = {};
+    AeLoss l = {};
+    ae_build_forward(r, l, cfg, P, x, ldx, idx_x, n_x, y, ldy, idx_y, n_y, losses, rec_x, rec_y, emb_x, emb_y, scratch);
+    if (int e = ae_launch_rows(r, st)) return e;
+    if (losses) hipLaunchKernelGGL(ae_loss, dim3(1), dim3(AE_UPD_THREADS), 0, st, l);
+    return (int)hipGetLastError();
+}
+
+// one training step: launch A, launch B.  idx_x / idx_y and losses are the step's own.  part: 0 = the step; 1 = launch A alone,
+// 2 = launch B alone on the scratch an earlier whole step left (umlh_ae_bench_steps only: not a training step).
+extern "C" int umlh_ae_launch_step(const umlh_ae_cfg_t* cfg, float* const* P, float* const* M, float* const* V, const float* x,
+                                   long long ldx, const int* idx_x, int batch_x, const float* y, long long ldy, const int* idx_y,
+                                   int batch_y, int backward_y, float alpha_x, float alpha_y, const OptArgs* o, float* losses,
+                                   void* scratch, int part, hipStream_t st) {
+    AeRowArgs r = {};
+    AeUpdArgs u = {};
+    ae_build_step(r, u, cfg, P, M, V, x, ldx, idx_x, batch_x, y, ldy, idx_y, batch_y, backward_y, alpha_x, alpha_y, losses, scratch);
     u.o = *o;
     if (part != 2)
         if (int e = ae_launch_rows(r, st)) return e;
-    if (part != 1) hipLaunchKernelGGL(ae_update, dim3((unsigned)(blk + 1)), dim3(AE_UPD_THREADS), 0, st, u);
+    if (part != 1) hipLaunchKernelGGL(ae_update_k<false>, dim3((unsigned)(u.tiles + 1)), dim3(AE_UPD_THREADS), 0, st, u, nullptr, nullptr, nullptr, 0, 0);
     return (int)hipGetLastError();
 }
+
+extern "C" unsigned long long umlh_ae_group_plan_bytes(const umlh_ae_group_item_t* items, int n, int n_steps) {
+    const umlh_ae_cfg_t* cfg[UMLH_AE_MAX_GROUP];
+    int rx[UMLH_AE_MAX_GROUP], ry[UMLH_AE_MAX_GROUP];
+    for (int i = 0; i < n; ++i) { cfg[i] = &items[i].cfg; rx[i] = items[i].batch_x; ry[i] = items[i].batch_y; }
+    return (unsigned long long)ae_group_plan(n, n_steps, cfg, rx, ry).bytes;
+}
+
+extern "C" unsigned long long umlh_ae_eval_group_plan_bytes(const umlh_ae_eval_item_t* items, int n) {
+    const umlh_ae_cfg_t* cfg[UMLH_AE_MAX_GROUP];
+    int rx[UMLH_AE_MAX_GROUP], ry[UMLH_AE_MAX_GROUP];
+    for (int i = 0; i < n; ++i) { cfg[i] = &items[i].cfg; rx[i] = items[i].n_x; ry[i] = items[i].n_y; }
+    return (unsigned long long)ae_group_plan(n, 0, cfg, rx, ry).bytes;
+}
+
+// n_steps training steps of n runs: one upload of the tables, then launch A and launch B of the whole group per step.  opt: HOST
+// [n_steps][n] optimizer constants.  V of a member under sgd has been replaced by NULL by the caller.
+extern "C" int umlh_ae_launch_group(const umlh_ae_group_item_t* items, int n, int n_steps, const OptArgs* opt, void* scratch,
+                                    hipStream_t st) {
+    const umlh_ae_cfg_t* cfg[UMLH_AE_MAX_GROUP];
+    int rx[UMLH_AE_MAX_GROUP], ry[UMLH_AE_MAX_GROUP];
+    for (int i = 0; i < n; ++i) { cfg[i] = &items[i].cfg; rx[i] = items[i].batch_x; ry[i] = items[i].batch_y; }
+    const AeGroupPlan p = ae_group_plan(n, n_steps, cfg, rx, ry);
+    int grid_a = 0, grid_b = 0;
+    size_t lds = 0;
+    const int e = ae_upload(scratch, (size_t)p.head, st, [&](unsigned char* h) {
+        AeRowArgs* R = at<AeRowArgs>(h, p.rows);
+        AeUpdArgs* U = at<AeUpdArgs>(h, p.upd);
+        int ca[UMLH_AE_MAX_GROUP], cb[UMLH_AE_MAX_GROUP];
+        for (int i = 0; i < n; ++i) {
+            const umlh_ae_group_item_t& it = items[i];
+            R[i] = AeRowArgs{};
+            U[i] = AeUpdArgs{};
+            ae_build_step(R[i], U[i], &it.cfg, it.P, it.M, it.optimizer != UMLH_OPT_SGD ? it.V : nullptr, it.x, it.ldx, it.idx_x, it.batch_x,
+                          it.y, it.ldy, it.idx_y, it.batch_y, it.backward_y, it.alpha_x, it.alpha_y, it.losses, at<char>(scratch, p.member[i]));
+            ca[i] = ae_tiles(R[i]);
+            cb[i] = U[i].tiles + 1;
+            grid_a += ca[i];
+            grid_b += cb[i];
+            lds = std::max(lds, ae_lds_bytes(R[i].D, R[i].C, R[i].L));
+        }
+        ae_fill_first(at<int>(h, p.first_a), ca, n);
+        ae_fill_first(at<int>(h, p.first_b), cb, n);
+        memcpy(h + p.opt, opt, (size_t)n_steps * n * sizeof(OptArgs));
+    });
+    if (e) return e;
+    for (int s = 0; s < n_steps; ++s) {
+        if (int e2 = ae_launch_rows_grouped(at<AeRowArgs>(scratch, p.rows), at<int>(scratch, p.first_a), n, grid_a, lds, s, st)) return e2;
+        hipLaunchKernelGGL(ae_update_k<true>, dim3((unsigned)grid_b), dim3(AE_UPD_THREADS), 0, st, AeUpdArgs{}, at<AeUpdArgs>(scratch, p.upd),
+                           at<int>(scratch, p.first_b), at<OptArgs>(scratch, p.opt), n, s);
+        if (int e2 = (int)hipGetLastError()) return e2;
+    }
+    return 0;
+}
+
+// the evaluation forward of n runs: one upload, launch A of the whole group, one loss workgroup per member
+extern "C" int umlh_ae_launch_forward_group(const umlh_ae_eval_item_t* items, int n, void* scratch, hipStream_t st) {
+    const umlh_ae_cfg_t* cfg[UMLH_AE_MAX_GROUP];
+    int rx[UMLH_AE_MAX_GROUP], ry[UMLH_AE_MAX_GROUP];
+    for (int i = 0; i < n; ++i) { cfg[i] = &items[i].cfg; rx[i] = items[i].n_x; ry[i] = items[i].n_y; }
+    const AeGroupPlan p = ae_group_plan(n, 0, cfg, rx, ry);
+    int grid_a = 0;
+    size_t lds = 0;
+    bool any_loss = false;
+    const int e = ae_upload(scratch, (size_t)p.head, st, [&](unsigned char* h) {
+        AeRowArgs* R = at<AeRowArgs>(h, p.rows);
+        AeLoss* Ls = at<AeLoss>(h, p.upd);
+        int ca[UMLH_AE_MAX_GROUP];
+        for (int i = 0; i < n; ++i) {
+            const umlh_ae_eval_item_t& it = items[i];
+            R[i] = AeRowArgs{};
+            Ls[i] = AeLoss{};
+            ae_build_forward(R[i], Ls[i], &it.cfg, it.P, it.x, it.ldx, it.idx_x, it.n_x, it.y, it.ldy, it.idx_y, it.n_y, it.losses,
+                             it.n_x ? it.rec_x : nullptr, it.n_y ? it.rec_y : nullptr, it.n_x ? it.emb_x : nullptr,
+                             it.n_y ? it.emb_y : nullptr, at<char>(scratch, p.member[i]));
+            ca[i] = ae_tiles(R[i]);
+            grid_a += ca[i];
+            lds = std::max(lds, ae_lds_bytes(R[i].D, R[i].C, R[i].L));
+            any_loss = any_loss || it.losses != nullptr;
+        }
+        ae_fill_first(at<int>(h, p.first_a), ca, n);
+        ae_fill_first(at<int>(h, p.first_b), ca, 0);
+    });
+    if (e) return e;
+    if (int e2 = ae_launch_rows_grouped(at<AeRowArgs>(scratch, p.rows), at<int>(scratch, p.first_a), n, grid_a, lds, 0, st)) return e2;
+    if (any_loss) hipLaunchKernelGGL(ae_loss_grouped, dim3((unsigned)n), dim3(AE_UPD_THREADS), 0, st, at<AeLoss>(scratch, p.upd));
+    return (int)hipGetLastError();
+}
+

@@ -268,6 +268,11 @@ int umlh_ae_launch_forward(const umlh_ae_cfg_t* cfg, const float* const* P, cons
 int umlh_ae_launch_step(const umlh_ae_cfg_t* cfg, float* const* P, float* const* M, float* const* V, const float* x, long long ldx,
                         const int* idx_x, int batch_x, const float* y, long long ldy, const int* idx_y, int batch_y, int backward_y,
                         float alpha_x, float alpha_y, const OptArgs* o, float* losses, void* scratch, int part, hipStream_t st);
+// grouped forms: n members in one launch pair per step.  opt: HOST [n_steps][n] optimizer constants, member i of step s at s * n + i
+unsigned long long umlh_ae_group_plan_bytes(const umlh_ae_group_item_t* items, int n, int n_steps);
+unsigned long long umlh_ae_eval_group_plan_bytes(const umlh_ae_eval_item_t* items, int n);
+int umlh_ae_launch_group(const umlh_ae_group_item_t* items, int n, int n_steps, const OptArgs* opt, void* scratch, hipStream_t st);
+int umlh_ae_launch_forward_group(const umlh_ae_eval_item_t* items, int n, void* scratch, hipStream_t st);
 // ---- umlh_ops.cpp, for scripts/bench_gaussian.py alone ----
 // umlh_ae_train_steps with its checks, launching only a part of every step: part 1 = launch A alone, 2 = launch B alone on the
 // scratch an earlier whole step left, 0 = whole steps.  NOT a training call (with part 1 the weights never change, with part 2

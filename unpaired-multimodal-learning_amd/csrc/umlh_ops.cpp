@@ -1,10 +1,14 @@
 // The stateless entry points of include/umlh.h, in the header's section order: each one checks its arguments and calls one
 // launcher (a few chain two or three).  None takes a umlh_handle_t (those are in umlh_api.cpp).  Every check precedes the
-// first HIP call, so a refused call has touched neither the device nor the stream.  No allocation, no synchronisation.
+// first HIP call, so a refused call has touched neither the device nor the stream.  No allocation, no synchronisation (one
+// exception, said where it is: the host-side tables of umlh_ae_train_steps_grouped).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
+#include <functional>
+#include <vector>
 
 #include "umlh_host.h"
 #include "umlh_launch.h"
@@ -1292,6 +1296,33 @@ static int check_ae_table(const char* who, const char* name, const char* ldname,
     return UMLH_OK;
 }
 
+// the argument checks one run shares between the single-run entry points and the members of the grouped ones (who: the function,
+// or the function and the member)
+static int check_ae_forward_args(const char* who, const umlh_ae_cfg_t* cfg, const float* const* P, const float* x, int64_t ldx, int32_t n_x,
+                                 const float* y, int64_t ldy, int32_t n_y) {
+    RC(check_ae_shape(who, cfg, n_x, n_y, UMLH_AE_MAX_EVAL_ROWS, "n_x", "n_y"));
+    RC(check_ae_tensors(who, "P", P));
+    RC(check_ae_table(who, "x", "ldx", x, ldx, n_x, cfg->dim_obs));
+    RC(check_ae_table(who, "y", "ldy", y, ldy, n_y, cfg->dim_obs));
+    return UMLH_OK;
+}
+
+static int check_ae_train_args(const char* who, const umlh_ae_cfg_t* cfg, float* const* P, float* const* M, float* const* V, const float* x,
+                               int64_t ldx, int32_t batch_x, const float* y, int64_t ldy, int32_t batch_y, int32_t n_steps,
+                               int32_t backward_y, int32_t optimizer, const float* losses) {
+    RC(check_ae_shape(who, cfg, batch_x, batch_y, UMLH_AE_MAX_BATCH, "batch_x", "batch_y"));
+    if (n_steps < 1 || n_steps > UMLH_AE_MAX_BATCH) return fail(UMLH_E_INVALID, "%s: n_steps=%d outside 1..%d", who, n_steps, UMLH_AE_MAX_BATCH);
+    if (backward_y != 0 && backward_y != 1) return fail(UMLH_E_INVALID, "%s: backward_y=%d (0: mode 'x', 1: mode 'xy')", who, backward_y);
+    if (optimizer < UMLH_OPT_SGD || optimizer > UMLH_OPT_ADAMW) return fail(UMLH_E_INVALID, "%s: unknown optimizer %d", who, optimizer);
+    RC(check_ae_tensors(who, "P", P));
+    RC(check_ae_tensors(who, "M", M));
+    if (optimizer != UMLH_OPT_SGD) RC(check_ae_tensors(who, "V", V));
+    RC(check_ae_table(who, "x", "ldx", x, ldx, batch_x, cfg->dim_obs));
+    RC(check_ae_table(who, "y", "ldy", y, ldy, batch_y, cfg->dim_obs));
+    if (!losses) return fail(UMLH_E_INVALID, "%s: losses is NULL", who);
+    return UMLH_OK;
+}
+
 uint64_t umlh_ae_scratch(const umlh_ae_cfg_t* cfg, int32_t rows_x, int32_t rows_y, int32_t train) {
     if (train != 0 && train != 1) return 0;
     if (check_ae_shape(nullptr, cfg, rows_x, rows_y, train ? UMLH_AE_MAX_BATCH : UMLH_AE_MAX_EVAL_ROWS, "", "")) return 0;
@@ -1302,10 +1333,7 @@ int umlh_ae_forward(const umlh_ae_cfg_t* cfg, const float* const* P, const float
                     const float* y, int64_t ldy, const int32_t* idx_y, int32_t n_y, float* losses, float* rec_x, float* rec_y,
                     float* emb_x, float* emb_y, void* scratch, uint64_t scratch_bytes, void* stream) {
     const char* who = "umlh_ae_forward";
-    RC(check_ae_shape(who, cfg, n_x, n_y, UMLH_AE_MAX_EVAL_ROWS, "n_x", "n_y"));
-    RC(check_ae_tensors(who, "P", P));
-    RC(check_ae_table(who, "x", "ldx", x, ldx, n_x, cfg->dim_obs));
-    RC(check_ae_table(who, "y", "ldy", y, ldy, n_y, cfg->dim_obs));
+    RC(check_ae_forward_args(who, cfg, P, x, ldx, n_x, y, ldy, n_y));
     if (!scratch) return fail(UMLH_E_INVALID, "%s: scratch is NULL", who);
     RC(check_scratch(who, scratch, scratch_bytes, umlh_ae_plan_bytes(cfg, n_x, n_y, 0), 8));
     HIPCHK(umlh_ae_launch_forward(cfg, P, x, ldx, idx_x, n_x, y, ldy, idx_y, n_y, losses, n_x ? rec_x : nullptr, n_y ? rec_y : nullptr,
@@ -1320,16 +1348,7 @@ static int ae_steps(const char* who, int part, const umlh_ae_cfg_t* cfg, float* 
                     double beta1, double beta2, double eps, double momentum, double weight_decay, float* losses, void* scratch,
                     uint64_t scratch_bytes, void* stream) {
     if (part < 0 || part > 2) return fail(UMLH_E_INVALID, "%s: part=%d outside 0..2", who, part);
-    RC(check_ae_shape(who, cfg, batch_x, batch_y, UMLH_AE_MAX_BATCH, "batch_x", "batch_y"));
-    if (n_steps < 1 || n_steps > UMLH_AE_MAX_BATCH) return fail(UMLH_E_INVALID, "%s: n_steps=%d outside 1..%d", who, n_steps, UMLH_AE_MAX_BATCH);
-    if (backward_y != 0 && backward_y != 1) return fail(UMLH_E_INVALID, "%s: backward_y=%d (0: mode 'x', 1: mode 'xy')", who, backward_y);
-    if (optimizer < UMLH_OPT_SGD || optimizer > UMLH_OPT_ADAMW) return fail(UMLH_E_INVALID, "%s: unknown optimizer %d", who, optimizer);
-    RC(check_ae_tensors(who, "P", P));
-    RC(check_ae_tensors(who, "M", M));
-    if (optimizer != UMLH_OPT_SGD) RC(check_ae_tensors(who, "V", V));
-    RC(check_ae_table(who, "x", "ldx", x, ldx, batch_x, cfg->dim_obs));
-    RC(check_ae_table(who, "y", "ldy", y, ldy, batch_y, cfg->dim_obs));
-    if (!losses) return fail(UMLH_E_INVALID, "%s: losses is NULL", who);
+    RC(check_ae_train_args(who, cfg, P, M, V, x, ldx, batch_x, y, ldy, batch_y, n_steps, backward_y, optimizer, losses));
     if (!scratch) return fail(UMLH_E_INVALID, "%s: scratch is NULL", who);
     RC(check_scratch(who, scratch, scratch_bytes, umlh_ae_plan_bytes(cfg, batch_x, batch_y, 1), 8));
     for (int s = 0; s < n_steps; ++s) {
@@ -1348,6 +1367,93 @@ int umlh_ae_train_steps(const umlh_ae_cfg_t* cfg, float* const* P, float* const*
                         float* losses, void* scratch, uint64_t scratch_bytes, void* stream) {
     return ae_steps("umlh_ae_train_steps", 0, cfg, P, M, V, x, ldx, idx_x, batch_x, y, ldy, idx_y, batch_y, n_steps, backward_y, alpha_x,
                     alpha_y, optimizer, lr, first_step, beta1, beta2, eps, momentum, weight_decay, losses, scratch, scratch_bytes, stream);
+}
+
+// ---- grouped forms: several runs in one launch pair per step ----
+static int check_ae_group_count(const char* who, const void* items, int32_t n_items) {
+    if (!items) return who ? fail(UMLH_E_INVALID, "%s: items is NULL", who) : UMLH_E_INVALID;
+    if (n_items < 1 || n_items > UMLH_AE_MAX_GROUP)
+        return who ? fail(UMLH_E_INVALID, "%s: n_items=%d outside 1..%d", who, n_items, UMLH_AE_MAX_GROUP) : UMLH_E_INVALID;
+    return UMLH_OK;
+}
+
+// no device pointer occurs twice among the members' P / M / V (V of an sgd member is not looked at): every member's workgroups
+// update its tensors in place while the others' run
+static int check_ae_group_unique(const char* who, const umlh_ae_group_item_t* items, int32_t n_items) {
+    struct Ref { const float* p; int member, set, index; };
+    std::vector<Ref> refs;
+    refs.reserve((size_t)n_items * 48);
+    for (int i = 0; i < n_items; ++i) {
+        float* const* sets[3] = {items[i].P, items[i].M, items[i].optimizer != UMLH_OPT_SGD ? items[i].V : nullptr};
+        for (int k = 0; k < 3; ++k)
+            for (int j = 0; sets[k] && j < 16; ++j) refs.push_back({sets[k][j], i, k, j});
+    }
+    std::sort(refs.begin(), refs.end(), [](const Ref& a, const Ref& b) {
+        return a.p != b.p ? std::less<const float*>()(a.p, b.p) : a.member != b.member ? a.member < b.member
+               : a.set != b.set ? a.set < b.set : a.index < b.index;
+    });
+    for (size_t i = 1; i < refs.size(); ++i)
+        if (refs[i].p == refs[i - 1].p)
+            return fail(UMLH_E_INVALID, "%s: member %d: %c[%d] is also member %d's %c[%d] (members may not share parameter or moment tensors)",
+                        who, refs[i].member, "PMV"[refs[i].set], refs[i].index, refs[i - 1].member, "PMV"[refs[i - 1].set], refs[i - 1].index);
+    return UMLH_OK;
+}
+
+uint64_t umlh_ae_group_scratch(const umlh_ae_group_item_t* items, int32_t n_items, int32_t n_steps) {
+    if (check_ae_group_count(nullptr, items, n_items)) return 0;
+    if (n_steps < 1 || n_steps > UMLH_AE_MAX_BATCH) return 0;
+    for (int i = 0; i < n_items; ++i)
+        if (check_ae_shape(nullptr, &items[i].cfg, items[i].batch_x, items[i].batch_y, UMLH_AE_MAX_BATCH, "", "")) return 0;
+    return umlh_ae_group_plan_bytes(items, n_items, n_steps);
+}
+
+uint64_t umlh_ae_eval_group_scratch(const umlh_ae_eval_item_t* items, int32_t n_items) {
+    if (check_ae_group_count(nullptr, items, n_items)) return 0;
+    for (int i = 0; i < n_items; ++i)
+        if (check_ae_shape(nullptr, &items[i].cfg, items[i].n_x, items[i].n_y, UMLH_AE_MAX_EVAL_ROWS, "", "")) return 0;
+    return umlh_ae_eval_group_plan_bytes(items, n_items);
+}
+
+// The one entry point of this file that allocates on the host: the [n_steps][n_items] optimizer constants are formed here, step by
+// step as ae_steps forms them, and handed to the launcher, which stages them with the descriptors for one upload.
+int umlh_ae_train_steps_grouped(const umlh_ae_group_item_t* items, int32_t n_items, int32_t n_steps, void* scratch, uint64_t scratch_bytes,
+                                void* stream) {
+    const char* who = "umlh_ae_train_steps_grouped";
+    RC(check_ae_group_count(who, items, n_items));
+    char member[64];
+    for (int i = 0; i < n_items; ++i) {
+        const umlh_ae_group_item_t& it = items[i];
+        snprintf(member, sizeof(member), "%s: member %d", who, i);
+        RC(check_ae_train_args(member, &it.cfg, it.P, it.M, it.V, it.x, it.ldx, it.batch_x, it.y, it.ldy, it.batch_y, n_steps, it.backward_y,
+                               it.optimizer, it.losses));
+    }
+    RC(check_ae_group_unique(who, items, n_items));
+    if (!scratch) return fail(UMLH_E_INVALID, "%s: scratch is NULL", who);
+    RC(check_scratch(who, scratch, scratch_bytes, umlh_ae_group_plan_bytes(items, n_items, n_steps), 8));
+    std::vector<OptArgs> opt((size_t)n_steps * n_items);
+    for (int s = 0; s < n_steps; ++s)
+        for (int i = 0; i < n_items; ++i) {
+            const umlh_ae_group_item_t& it = items[i];
+            opt[(size_t)s * n_items + i] = standalone_opt(it.optimizer, it.lr, it.first_step + s, it.beta1, it.beta2, it.eps, it.momentum,
+                                                          it.weight_decay);
+        }
+    HIPCHK(umlh_ae_launch_group(items, n_items, n_steps, opt.data(), scratch, (hipStream_t)stream), who);
+    return UMLH_OK;
+}
+
+int umlh_ae_forward_grouped(const umlh_ae_eval_item_t* items, int32_t n_items, void* scratch, uint64_t scratch_bytes, void* stream) {
+    const char* who = "umlh_ae_forward_grouped";
+    RC(check_ae_group_count(who, items, n_items));
+    char member[64];
+    for (int i = 0; i < n_items; ++i) {
+        const umlh_ae_eval_item_t& it = items[i];
+        snprintf(member, sizeof(member), "%s: member %d", who, i);
+        RC(check_ae_forward_args(member, &it.cfg, it.P, it.x, it.ldx, it.n_x, it.y, it.ldy, it.n_y));
+    }
+    if (!scratch) return fail(UMLH_E_INVALID, "%s: scratch is NULL", who);
+    RC(check_scratch(who, scratch, scratch_bytes, umlh_ae_eval_group_plan_bytes(items, n_items), 8));
+    HIPCHK(umlh_ae_launch_forward_group(items, n_items, scratch, (hipStream_t)stream), who);
+    return UMLH_OK;
 }
 
 // benchmark only (umlh_launch.h): one launch of every step

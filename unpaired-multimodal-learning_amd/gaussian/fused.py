@@ -1,6 +1,7 @@
 """The fused training path of the Gaussian experiment: the batch order of the reference's shuffled loader restated on the
 host, and a trainer that runs whole steps of the SharedAutoencoder through ``umlh.gauss.ae_train_steps`` (two launches per
-step) with the batches gathered by index from device-resident tables.
+step) with the batches gathered by index from device-resident tables; ``GroupedTrainer`` steps several such trainers in one
+launch pair per step (``umlh.gauss.ae_train_steps_grouped``).
 
 ``BatchOrder`` reproduces, draw for draw, the index stream of
 ``DataLoader(UnpairedDataset, batch_size, shuffle=True, drop_last=True, generator=g)`` cycled by ``train_model_steps``'
@@ -64,13 +65,20 @@ class FusedTrainer:
     update the model's parameters and the optimizer's ``state_for(p)`` tensors through their own storages, so ``state_dict``,
     checkpoints and a later ``optimizer.step()`` keep working."""
 
-    def __init__(self, model, optimizer, dataset, batch_size, generator, device, span_steps=1024, total_steps=None):
+    def __init__(self, model, optimizer, dataset, batch_size, generator, device, span_steps=1024, total_steps=None, tables=None):
         self.model, self.optimizer, self.device = model, optimizer, torch.device(device)
         self.batch_size = int(batch_size)
         self.order = BatchOrder(len(dataset), batch_size, generator)
         self.len_x, self.len_y = dataset.len_x, dataset.len_y
-        self.x = torch.as_tensor(dataset.data_x).to(self.device, torch.float32).contiguous()
-        self.y = torch.as_tensor(dataset.data_y).to(self.device, torch.float32).contiguous()
+        # tables: (x, y) fp32 device tensors that already hold the dataset's rows (row i of the view at row i): used as they
+        # are, so that trainers over the same data share one upload
+        if tables is None:
+            tables = (torch.as_tensor(dataset.data_x).to(self.device, torch.float32).contiguous(),
+                      torch.as_tensor(dataset.data_y).to(self.device, torch.float32).contiguous())
+        self.x, self.y = tables
+        for t, rows, name in ((self.x, self.len_x, "x"), (self.y, self.len_y, "y")):
+            if t.device != self.device or t.dtype != torch.float32 or t.ndim != 2 or t.shape[0] < rows:
+                raise ValueError(f"FusedTrainer: tables[{name}] must be an fp32 device tensor of at least {rows} rows on {self.device}")
         self.span_steps = max(int(span_steps), 1)
         # the row ids of a span are drawn ahead of the steps that use them.  total_steps (the steps the caller will run in all)
         # caps what is drawn, so that the generator ends where the reference's loader leaves it after that many steps; without
@@ -98,23 +106,27 @@ class FusedTrainer:
         self._idx_y = (order % self.len_y).to(torch.int32).to(self.device)
         self._have, self._used = steps, 0
 
+    def _step_args(self, k, mode, alpha_x, alpha_y, losses):
+        """The arguments of ``ae_train_steps`` (``n_steps`` excepted) for the next ``k`` steps of the current id span."""
+        g = self.optimizer.param_groups[0]
+        b = self.batch_size
+        lo, hi = self._used * b, (self._used + k) * b
+        return dict(params=[p.data for p in self.params], m=self.m, v=self.v, x=self.x, y=self.y, idx_x=self._idx_x[lo:hi],
+                    idx_y=self._idx_y[lo:hi], batch_x=b, batch_y=b, mode=mode, alpha_x=alpha_x, alpha_y=alpha_y,
+                    optimizer=self.optimizer.name, lr=g["lr"], first_step=self.optimizer.step_count + 1, betas=g["betas"], eps=g["eps"],
+                    momentum=g["momentum"], weight_decay=g["weight_decay"], losses=losses)
+
     def steps(self, n, mode="xy", alpha_x=1.0, alpha_y=1.0):
         """Runs ``n`` steps; returns their [n, 3] device losses (loss_x, loss_y, loss) and advances ``optimizer.step_count``."""
         from umlh import gauss
         n = int(n)
         out = torch.empty((n, 3), dtype=torch.float32, device=self.device)
-        g = self.optimizer.param_groups[0]
         done = 0
         while done < n:
             if self._used == self._have:
                 self._refill(min(n - done, 65536))
             k = min(n - done, self._have - self._used, 65536)
-            b = self.batch_size
-            lo, hi = self._used * b, (self._used + k) * b
-            gauss.ae_train_steps([p.data for p in self.params], self.m, self.v, self.x, self.y, self._idx_x[lo:hi], self._idx_y[lo:hi],
-                                 b, b, k, mode=mode, alpha_x=alpha_x, alpha_y=alpha_y, optimizer=self.optimizer.name, lr=g["lr"],
-                                 first_step=self.optimizer.step_count + 1, betas=g["betas"], eps=g["eps"], momentum=g["momentum"],
-                                 weight_decay=g["weight_decay"], losses=out[done:done + k])
+            gauss.ae_train_steps(n_steps=k, **self._step_args(k, mode, alpha_x, alpha_y, out[done:done + k]))
             self.optimizer.step_count += k
             self._used += k
             done += k
@@ -125,3 +137,46 @@ class FusedTrainer:
         from umlh import gauss
         losses, _, _, ex, ey = gauss.ae_forward([p.data for p in self.params], val_x, val_y, recon=False, embeddings=embeddings)
         return losses, ex, ey
+
+
+class GroupedTrainer:
+    """Several ``FusedTrainer``s stepped together through ``umlh.gauss.ae_train_steps_grouped``: two launches per step for the
+    whole group.  The members' tables, id spans, bound parameters and moments are used as they are, and every member is left --
+    parameters, moments, ``optimizer.step_count``, generator -- exactly where its own ``FusedTrainer.steps`` would leave it.
+    ``settings``: one ``(mode, alpha_x, alpha_y)`` per member."""
+
+    def __init__(self, trainers, settings):
+        self.trainers, self.settings = list(trainers), [tuple(s) for s in settings]
+        if not self.trainers or len(self.trainers) != len(self.settings):
+            raise ValueError("GroupedTrainer: one (mode, alpha_x, alpha_y) per trainer, at least one trainer")
+        self.device = self.trainers[0].device
+        if any(t.device != self.device for t in self.trainers):
+            raise ValueError("GroupedTrainer: the members live on different devices")
+
+    def steps(self, n):
+        """Runs ``n`` steps of every member; returns the members' [n, 3] device losses.  The call is split where any member's id
+        span runs out; that member refills as it would alone."""
+        from umlh import gauss
+        n = int(n)
+        outs = [torch.empty((n, 3), dtype=torch.float32, device=self.device) for _ in self.trainers]
+        done = 0
+        while done < n:
+            for t in self.trainers:
+                if t._used == t._have:
+                    t._refill(min(n - done, 65536))
+            k = min([n - done, 65536] + [t._have - t._used for t in self.trainers])
+            gauss.ae_train_steps_grouped([t._step_args(k, mode, ax, ay, out[done:done + k])
+                                          for t, (mode, ax, ay), out in zip(self.trainers, self.settings, outs)], k)
+            for t in self.trainers:
+                t.optimizer.step_count += k
+                t._used += k
+            done += k
+        return outs
+
+    def evaluate(self, val, embeddings=False):
+        """One grouped forward over all members.  ``val``: one ``(val_x, val_y)`` pair of device tensors per member (members may
+        name the same tensors).  Returns one ``(losses [2], emb_x, emb_y)`` per member."""
+        from umlh import gauss
+        out = gauss.ae_forward_grouped([dict(params=[p.data for p in t.params], x=vx, y=vy, recon=False, embeddings=embeddings)
+                                        for t, (vx, vy) in zip(self.trainers, val)])
+        return [(losses, ex, ey) for losses, _, _, ex, ey in out]

@@ -28,7 +28,7 @@ from . import report  # noqa: F401,E402
 from .report import class_report, topk_classes  # noqa: F401,E402
 from . import seqload  # noqa: F401,E402
 from . import gauss  # noqa: F401,E402
-from .gauss import ae_forward, ae_train_steps  # noqa: F401,E402
+from .gauss import ae_forward, ae_forward_grouped, ae_train_steps, ae_train_steps_grouped  # noqa: F401,E402
 
 
 def host_cpu_budget() -> int:

@@ -83,6 +83,25 @@ class AeCfg(C.Structure):                          # umlh_ae_cfg_t
     _fields_ = [("dim_obs", C.c_int32), ("dim_common", C.c_int32), ("dim_latent", C.c_int32)]
 
 
+class AeGroupItem(C.Structure):                    # umlh_ae_group_item_t: one run of umlh_ae_train_steps_grouped
+    _fields_ = [("cfg", AeCfg), ("P", C.POINTER(C.c_void_p)), ("M", C.POINTER(C.c_void_p)), ("V", C.POINTER(C.c_void_p)),
+                ("x", C.c_void_p), ("ldx", C.c_int64), ("idx_x", C.c_void_p), ("batch_x", C.c_int32),
+                ("y", C.c_void_p), ("ldy", C.c_int64), ("idx_y", C.c_void_p), ("batch_y", C.c_int32),
+                ("backward_y", C.c_int32), ("alpha_x", C.c_float), ("alpha_y", C.c_float),
+                ("optimizer", C.c_int32), ("lr", C.c_double), ("first_step", C.c_int64), ("beta1", C.c_double), ("beta2", C.c_double),
+                ("eps", C.c_double), ("momentum", C.c_double), ("weight_decay", C.c_double), ("losses", C.c_void_p)]
+
+
+class AeEvalItem(C.Structure):                     # umlh_ae_eval_item_t: one run of umlh_ae_forward_grouped
+    _fields_ = [("cfg", AeCfg), ("P", C.POINTER(C.c_void_p)),
+                ("x", C.c_void_p), ("ldx", C.c_int64), ("idx_x", C.c_void_p), ("n_x", C.c_int32),
+                ("y", C.c_void_p), ("ldy", C.c_int64), ("idx_y", C.c_void_p), ("n_y", C.c_int32),
+                ("losses", C.c_void_p), ("rec_x", C.c_void_p), ("rec_y", C.c_void_p), ("emb_x", C.c_void_p), ("emb_y", C.c_void_p)]
+
+
+AE_MAX_GROUP = 64                                  # UMLH_AE_MAX_GROUP
+
+
 class RolloutCfg(C.Structure):
     _fields_ = [("Z", C.c_int32), ("d_ff", C.c_int32), ("D", C.c_int32), ("n_layers", C.c_int32), ("steps", C.c_int32),
                 ("eps", C.c_float)]
@@ -250,6 +269,10 @@ def _prototypes() -> dict:
         "umlh_ae_forward": (rc, (P(AeCfg), pv, vp, i64, vp, i32, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp, u64, vp)),
         "umlh_ae_train_steps": (rc, (P(AeCfg), pv, pv, pv, vp, i64, vp, i32, vp, i64, vp, i32, i32, i32, f32, f32, i32, f64, i64,
                                      f64, f64, f64, f64, f64, vp, vp, u64, vp)),
+        "umlh_ae_group_scratch": (u64, (P(AeGroupItem), i32, i32)),
+        "umlh_ae_eval_group_scratch": (u64, (P(AeEvalItem), i32)),
+        "umlh_ae_train_steps_grouped": (rc, (P(AeGroupItem), i32, i32, vp, u64, vp)),
+        "umlh_ae_forward_grouped": (rc, (P(AeEvalItem), i32, vp, u64, vp)),
         # device loader of the affect datasets: first nonzero row, column and per-sequence standardisation, batch gather-pad
         "umlh_seq_first_nonzero": (rc, (vp, i64, i32, i32, vp, vp)),
         "umlh_seq_column_standardize_scratch": (u64, (i64, i32)),
