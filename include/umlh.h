@@ -585,6 +585,55 @@ int  umlh_align_cknna(const int32_t* knn_a, const float* scores_a, const int32_t
 int  umlh_align_list_stats(const int32_t* knn_a, const int32_t* knn_b, int64_t n, int32_t topk, int32_t* rows, double* out3,
                            void* scratch, uint64_t scratch_bytes, void* stream);
 
+/* Grouped form: the CKA and / or the mutual k-NN of up to UMLH_ALIGN_MAX_PAIRS feature pairs (members) in one fixed train of
+ * launches, for callers that measure many small pairs at once (every evaluation of a sweep, the pairs of an embedding capture).
+ *   bit identity    with the same `splits`, every word a member's outputs receive is the word the single-pair entry points
+ *                   write: out5[0..3] is the out4 of umlh_align_cka, out5[4] the output of umlh_align_mutual_knn on the lists of
+ *                   umlh_align_knn on a and on b, and the lists and scores, where asked for, are umlh_align_knn's.
+ *   independence    members may differ in every field, and a member's results do not depend on which other members are in the
+ *                   group or on their order.
+ *   chunk counts    a CKA's bits depend on its row-chunk count, so every member uses the row chunks umlh_align_cka picks for
+ *                   (n, d_a, d_b, splits).  k-NN bits do not depend on the column-chunk count: with splits = 0 it follows from the
+ *                   32-row strips of ALL views of the group (the rule of the single call on their sum, at most one chunk per
+ *                   256-column tile of the member), so a group of many small members runs one chunk per view.  splits > 0 is
+ *                   taken as given for both metrics.  One exception, which the single calls share among themselves: a list that
+ *                   no column fills (a row of NaN scores) holds one run of sentinels per merged chunk, so ITS words are those of
+ *                   the single call made with the same chunk count; they are >= n at a score of -inf for every count.
+ *   launches        at most ten, whatever n_items is: column sums, cross products, tile squares and the final of the CKAs; the
+ *                   k-NN tiles (one launch per load form: rows of whole aligned float4s, and the rest), one merge; the mutual
+ *                   count and its final.  Both views of every member share the tiles and merge launches.  A stage that no
+ *                   member asks for is not launched.
+ *   pointers        members may share inputs.  An output pointer (out5, knn_*, scores_*) that occurs twice among the members
+ *                   is UMLH_E_INVALID.
+ *   checks          every check precedes the first HIP call; the message names the function, `member i` and the argument.
+ *                   n_items outside 1..UMLH_ALIGN_MAX_PAIRS, a member with cka == 0 and topk == 0, and a NULL or short scratch
+ *                   are UMLH_E_INVALID; otherwise a member is held to the checks of umlh_align_cka / umlh_align_knn.
+ *   descriptors     the members' descriptors reach the device in one asynchronous upload per call into the head of `scratch`,
+ *                   from pinned staging that is reused behind events.  The call does not synchronise the host; `items` may be
+ *                   freed when it returns.
+ * Additive to ABI v11: umlh_version() is unchanged, callers detect the feature by this symbol. */
+#define UMLH_ALIGN_MAX_PAIRS 64
+typedef struct {                      /* one pair: the arguments of umlh_align_cka / _knn / _mutual_knn */
+    const float* a; int32_t lda, d_a;
+    const float* b; int32_t ldb, d_b;
+    int64_t n;
+    int32_t cka;                      /* 0: out5[0..3] are left untouched */
+    int32_t topk;                     /* 0: no lists, out5[4] is left untouched; else 1..32, < n */
+    double* out5;                     /* {cka, hsic_kl, hsic_kk, hsic_ll, mutual_knn} */
+    int32_t* knn_a; int32_t* knn_b;   /* [n, topk], or NULL: the lists live in scratch */
+    float* scores_a; float* scores_b; /* [n, topk] or NULL */
+} umlh_align_pair_t;
+/* Scratch bytes of umlh_align_pairs with these arguments (a multiple of 256: the descriptor tables, then per member its CKA
+ * region, its two views' list slabs, the lists where knn_* is NULL, the mutual partials).  With splits > 0, and for one member
+ * at splits = 0, this is at least the sum of the members' umlh_align_scratch_bytes, and it grows with every member added.  With
+ * splits = 0 a larger group may need LESS than its members' single calls together, and adding a member may shrink it: the k-NN
+ * slabs follow the group's chunk count, which falls as the group grows (six pairs of n = 2000, topk 10, d 10 + 10: about 0.85 MB,
+ * against 1.28 MB for one single call).  0 on invalid arguments (items NULL,
+ * n_items outside 1..64, splits < 0, a member outside the single-pair envelope or one that asks for nothing). */
+uint64_t umlh_align_pairs_scratch(const umlh_align_pair_t* items, int32_t n_items, int32_t splits);
+int  umlh_align_pairs(const umlh_align_pair_t* items, int32_t n_items, int32_t splits, void* scratch, uint64_t scratch_bytes,
+                      void* stream);
+
 /* ---- linear probes of the MultiBench evaluate() (MultiBench/train.py:31-91,93-240): masked mean pooling, StandardScaler
  * statistics, an L2-regularised BINARY logistic regression fitted on the device, and its score.  Features are row-major fp32
  * [n, d] with row stride ld >= d, labels int32 0/1.  Every argument check happens before any HIP call; everything runs on

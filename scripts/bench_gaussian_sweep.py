@@ -3,7 +3,7 @@
 a whole group of runs) against the same runs stepped one after another through FusedTrainer.steps, on the same GPU in the same
 process.  The sequential fused path is the yardstick everywhere; the grouped code is never its own yardstick.
 
-    python scripts/bench_gaussian_sweep.py [--reps R] [--steps N] [--out profiles/gaussian_sweep_bench.txt]
+    python scripts/bench_gaussian_sweep.py [--reps R] [--steps N] [--only-sweeps] [--out profiles/gaussian_sweep_bench.txt]
 
 A window is a pair of device events around N >= 2 000 steps of every member (grouped: one GroupedTrainer.steps(N); sequential:
 FusedTrainer.steps(N) member after member).  Every trainer holds one id span of N steps that each window walks again (its
@@ -113,28 +113,9 @@ def paper_points(g):
     return [dict(base[i % 2], seed=i // 2) for i in range(g)]
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--steps", type=int, default=2000)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "gaussian_sweep_bench.txt"))
-    ap.add_argument("--skip-sweeps", action="store_true", help="leave out part 3")
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_gaussian_sweep.py measures on the GPU; none is visible")
-    if args.steps < 2000:
-        raise SystemExit("a window is at least 2000 steps")
+def train_step_parts(args, emit):
+    """Parts 1 and 2: windows of train steps alone."""
     from gaussian import sweep
-    from gaussian.train import train_model_steps_fused
-    prop = torch.cuda.get_device_properties(0)
-    lines = [f"# scripts/bench_gaussian_sweep.py on {prop.name} ({getattr(prop, 'gcnArchName', '?')}, {prop.multi_processor_count} CUs), "
-             f"reps={args.reps}, steps per window={args.steps}",
-             "# grouped: GroupedTrainer.steps (two launches per step for the group); sequential: FusedTrainer.steps member after member"]
-
-    def emit(obj):
-        lines.append(obj if isinstance(obj, str) else json.dumps(obj))
-        print(lines[-1], flush=True)
-
     emit("# 1. train steps alone, (D, C, L, batch) = (50, 128, 10, 512), members alternating 'xy' / 'x'")
     best = None
     for g in GROUP_SIZES:
@@ -156,6 +137,33 @@ def main():
         emit(row(f"{name} one group of {n}", n, *windows(trainers, settings, [n], args.steps, args.reps)))
         emit(row(f"{name} {n // 6} groups of 6", n, *windows(trainers, settings, [6] * (n // 6), args.steps, args.reps)))
         del trainers
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=2000)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "gaussian_sweep_bench.txt"))
+    ap.add_argument("--skip-sweeps", action="store_true", help="leave out part 3")
+    ap.add_argument("--only-sweeps", action="store_true", help="part 3 alone")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_gaussian_sweep.py measures on the GPU; none is visible")
+    if args.steps < 2000:
+        raise SystemExit("a window is at least 2000 steps")
+    from gaussian import sweep
+    from gaussian.train import train_model_steps_fused
+    prop = torch.cuda.get_device_properties(0)
+    lines = [f"# scripts/bench_gaussian_sweep.py on {prop.name} ({getattr(prop, 'gcnArchName', '?')}, {prop.multi_processor_count} CUs), "
+             f"reps={args.reps}, steps per window={args.steps}",
+             "# grouped: GroupedTrainer.steps (two launches per step for the group); sequential: FusedTrainer.steps member after member"]
+
+    def emit(obj):
+        lines.append(obj if isinstance(obj, str) else json.dumps(obj))
+        print(lines[-1], flush=True)
+
+    if not args.only_sweeps:
+        train_step_parts(args, emit)
 
     if not args.skip_sweeps:
         emit("# 3. original.yaml: six runs x 1000 steps, wall seconds from building the models to a final synchronise")

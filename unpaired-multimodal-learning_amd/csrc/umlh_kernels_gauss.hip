@@ -39,6 +39,7 @@
 //   Members share nothing that is written: each has its own scratch region (ae_group_plan).  No atomics, no waits.
 #include "umlh_common.h"
 #include "umlh_launch.h"
+#include "umlh_stage.h"
 #include <algorithm>
 #include <climits>
 #include <cstring>
@@ -605,49 +606,9 @@ int ae_launch_rows(const AeRowArgs& r, hipStream_t st) {
     return (int)hipGetLastError();
 }
 
-// Pinned staging of the grouped calls' tables: two buffers per device, each reused once the copy of its last use has finished (an
-// event behind that copy), grown when a call needs more.  The source of the asynchronous upload therefore outlives it, and a call
-// waits on the host only for a copy that is two calls old.
-struct AeStage {
-    unsigned char* buf[2];
-    size_t cap[2];
-    hipEvent_t ev[2];
-    bool used[2];
-    int next;
-    bool ready;
-};
-AeStage g_ae_stage[64];
-std::mutex g_ae_stage_mu;
-
-// dst[0, bytes) = what fill writes into a staging buffer, as one copy on st
-template <class Fill>
-int ae_upload(void* dst, size_t bytes, hipStream_t st, Fill fill) {
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev)) return (int)e;
-    std::lock_guard<std::mutex> lk(g_ae_stage_mu);
-    AeStage& S = g_ae_stage[dev & 63];
-    if (!S.ready) {
-        for (int i = 0; i < 2; ++i)
-            if (hipError_t e = hipEventCreateWithFlags(&S.ev[i], hipEventDisableTiming)) return (int)e;
-        S.ready = true;
-    }
-    const int i = S.next;
-    S.next ^= 1;
-    if (S.used[i])
-        if (hipError_t e = hipEventSynchronize(S.ev[i])) return (int)e;
-    if (S.cap[i] < bytes) {
-        if (S.buf[i]) (void)hipHostFree(S.buf[i]);
-        S.buf[i] = nullptr;
-        S.cap[i] = 0;
-        const size_t cap = (bytes + 65535) / 65536 * 65536;
-        if (hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&S.buf[i]), cap, hipHostMallocDefault)) return (int)e;
-        S.cap[i] = cap;
-    }
-    fill(S.buf[i]);
-    if (hipError_t e = hipMemcpyAsync(dst, S.buf[i], bytes, hipMemcpyHostToDevice, st)) return (int)e;
-    S.used[i] = true;
-    return (int)hipEventRecord(S.ev[i], st);
-}
+// Pinned staging of the grouped calls' tables (umlh_stage.h): the source of the asynchronous upload outlives it, and a call waits
+// on the host only for a copy that is two calls old.
+StageRings g_ae_stage;
 
 // first[i] = first workgroup of member i; first[n] = the grid; INT_MAX from there on
 void ae_fill_first(int* first, const int* counts, int n) {
@@ -721,7 +682,7 @@ extern "C" int umlh_ae_launch_group(const umlh_ae_group_item_t* items, int n, in
     const AeGroupPlan p = ae_group_plan(n, n_steps, cfg, rx, ry);
     int grid_a = 0, grid_b = 0;
     size_t lds = 0;
-    const int e = ae_upload(scratch, (size_t)p.head, st, [&](unsigned char* h) {
+    const int e = g_ae_stage.upload(scratch, (size_t)p.head, st, [&](unsigned char* h) {
         AeRowArgs* R = at<AeRowArgs>(h, p.rows);
         AeUpdArgs* U = at<AeUpdArgs>(h, p.upd);
         int ca[UMLH_AE_MAX_GROUP], cb[UMLH_AE_MAX_GROUP];
@@ -760,7 +721,7 @@ extern "C" int umlh_ae_launch_forward_group(const umlh_ae_eval_item_t* items, in
     int grid_a = 0;
     size_t lds = 0;
     bool any_loss = false;
-    const int e = ae_upload(scratch, (size_t)p.head, st, [&](unsigned char* h) {
+    const int e = g_ae_stage.upload(scratch, (size_t)p.head, st, [&](unsigned char* h) {
         AeRowArgs* R = at<AeRowArgs>(h, p.rows);
         AeLoss* Ls = at<AeLoss>(h, p.upd);
         int ca[UMLH_AE_MAX_GROUP];

@@ -137,6 +137,9 @@ int umlh_align_launch_colsum(const float* a, int lda, int da, const float* b, in
                              hipStream_t st);
 int umlh_align_launch_cka_products(const float* a, int lda, int da, const float* b, int ldb, int db, long long n, int splits,
                                    void* scratch, hipStream_t st);
+// grouped form: n pairs in one fixed train of launches (the plan is that of the size query)
+unsigned long long umlh_align_pairs_bytes(const umlh_align_pair_t* items, int n, int splits);
+int umlh_align_launch_pairs(const umlh_align_pair_t* items, int n, int splits, void* scratch, hipStream_t st);
 // ---- umlh_kernels_align_ext.hip: unbiased / RBF CKA, CKNNA, k-NN list statistics ----
 unsigned long long umlh_align_ext_cka_unbiased_bytes(long long n, int da, int db, int splits);
 unsigned long long umlh_align_ext_rbf_bytes(long long n, int da, int db, int splits);

@@ -65,11 +65,12 @@ static int check_strides(const char* who, const char* ldb_name, const char* ldt_
     return UMLH_OK;
 }
 
-// the list length and the row count of the alignment entry points that take topk >= 1; 0 = fine
+// the list length and the row count of the alignment entry points that take topk >= 1; 0 = fine.  who = NULL: no message (a
+// size query)
 static int check_align_lists(const char* who, int32_t topk, int64_t n) {
-    if (topk < 1 || topk > 32) return fail(UMLH_E_INVALID, "%s: topk=%d outside 1..32", who, topk);
+    if (topk < 1 || topk > 32) return who ? fail(UMLH_E_INVALID, "%s: topk=%d outside 1..32", who, topk) : UMLH_E_INVALID;
     if (n <= topk || n > ALIGN_MAX_ROWS)
-        return fail(UMLH_E_INVALID, "%s: n=%lld rows for topk=%d (need topk < n <= 2^30)", who, (long long)n, topk);
+        return who ? fail(UMLH_E_INVALID, "%s: n=%lld rows for topk=%d (need topk < n <= 2^30)", who, (long long)n, topk) : UMLH_E_INVALID;
     return UMLH_OK;
 }
 
@@ -453,16 +454,25 @@ int umlh_align_mutual_knn(const int32_t* knn_a, const int32_t* knn_b, int64_t n,
     return UMLH_OK;
 }
 
+// the shape checks of one feature pair, shared by the CKA forms and the members of umlh_align_pairs (who: the function, or the
+// function and the member; NULL: no message, a size query); 0 = fine
+static int check_pair_shape(const char* who, int32_t lda, int32_t d_a, int32_t ldb, int32_t d_b, int64_t n, int32_t unbiased, int32_t splits) {
+    if (d_a < 1 || d_b < 1 || lda < d_a || ldb < d_b)
+        return who ? fail(UMLH_E_INVALID, "%s: d_a=%d lda=%d d_b=%d ldb=%d (need 1 <= d <= ld)", who, d_a, lda, d_b, ldb) : UMLH_E_INVALID;
+    if (n < 1 || n > ALIGN_MAX_ROWS)
+        return who ? fail(UMLH_E_INVALID, "%s: n=%lld rows (need 1 <= n <= 2^30)", who, (long long)n) : UMLH_E_INVALID;
+    if (unbiased && n < 4)
+        return who ? fail(UMLH_E_INVALID, "%s: n=%lld rows, the unbiased HSIC divides by n - 3 (need n >= 4)", who, (long long)n)
+                   : UMLH_E_INVALID;
+    if (splits < 0) return who ? fail(UMLH_E_INVALID, "%s: splits=%d < 0", who, splits) : UMLH_E_INVALID;
+    return UMLH_OK;
+}
+
 // the shared checks of the feature-space CKA forms; 0 = fine
 static int check_cka(const char* who, const float* a, int32_t lda, int32_t d_a, const float* b, int32_t ldb, int32_t d_b, int64_t n,
                      int32_t unbiased, int32_t splits, const double* out4, const void* scratch) {
     if (!a || !b || !out4 || !scratch) return fail(UMLH_E_INVALID, "%s: null pointer (a, b, out4 and scratch are required)", who);
-    if (d_a < 1 || d_b < 1 || lda < d_a || ldb < d_b)
-        return fail(UMLH_E_INVALID, "%s: d_a=%d lda=%d d_b=%d ldb=%d (need 1 <= d <= ld)", who, d_a, lda, d_b, ldb);
-    if (n < 1 || n > ALIGN_MAX_ROWS) return fail(UMLH_E_INVALID, "%s: n=%lld rows (need 1 <= n <= 2^30)", who, (long long)n);
-    if (unbiased && n < 4) return fail(UMLH_E_INVALID, "%s: n=%lld rows, the unbiased HSIC divides by n - 3 (need n >= 4)", who, (long long)n);
-    if (splits < 0) return fail(UMLH_E_INVALID, "%s: splits=%d < 0", who, splits);
-    return UMLH_OK;
+    return check_pair_shape(who, lda, d_a, ldb, d_b, n, unbiased, splits);
 }
 
 int umlh_align_cka(const float* a, int32_t lda, int32_t d_a, const float* b, int32_t ldb, int32_t d_b, int64_t n,
@@ -471,6 +481,70 @@ int umlh_align_cka(const float* a, int32_t lda, int32_t d_a, const float* b, int
     RC(check_cka(who, a, lda, d_a, b, ldb, d_b, n, 0, splits, out4, scratch));
     RC(check_scratch(who, scratch, scratch_bytes, umlh_align_cka_bytes(n, d_a, d_b, splits), 0));
     HIPCHK(umlh_align_launch_cka(a, lda, d_a, b, ldb, d_b, n, splits, out4, scratch, (hipStream_t)stream), who);
+    return UMLH_OK;
+}
+
+// ---- grouped form: many pairs in one fixed train of launches ----
+// what one member is held to: the pair's shape as umlh_align_cka holds it, the list length as umlh_align_knn does.  who = NULL:
+// the size query, which runs the same shape checks without a message and does not look at the pointers
+static int check_align_member(const char* who, const umlh_align_pair_t& it, int32_t splits) {
+    if (who && (!it.a || !it.b || !it.out5))
+        return fail(UMLH_E_INVALID, "%s: null pointer (%s is required)", who, !it.a ? "a" : !it.b ? "b" : "out5");
+    if (!it.cka && !it.topk) return who ? fail(UMLH_E_INVALID, "%s: cka=0 and topk=0 ask for nothing", who) : UMLH_E_INVALID;
+    RC(check_pair_shape(who, it.lda, it.d_a, it.ldb, it.d_b, it.n, 0, splits));
+    if (it.topk != 0) RC(check_align_lists(who, it.topk, it.n));
+    return UMLH_OK;
+}
+
+static int check_align_group_count(const char* who, const void* items, int32_t n_items, int32_t splits) {
+    if (!items) return who ? fail(UMLH_E_INVALID, "%s: items is NULL", who) : UMLH_E_INVALID;
+    if (n_items < 1 || n_items > UMLH_ALIGN_MAX_PAIRS)
+        return who ? fail(UMLH_E_INVALID, "%s: n_items=%d outside 1..%d", who, n_items, UMLH_ALIGN_MAX_PAIRS) : UMLH_E_INVALID;
+    if (splits < 0) return who ? fail(UMLH_E_INVALID, "%s: splits=%d < 0", who, splits) : UMLH_E_INVALID;
+    return UMLH_OK;
+}
+
+// no output pointer occurs twice among the members: every member's workgroups write while the others' run
+static int check_align_group_unique(const char* who, const umlh_align_pair_t* items, int32_t n_items) {
+    static const char* const NAMES[5] = {"out5", "knn_a", "knn_b", "scores_a", "scores_b"};
+    struct Ref { const void* p; int member, field; };
+    std::vector<Ref> refs;
+    refs.reserve((size_t)n_items * 5);
+    for (int i = 0; i < n_items; ++i) {
+        const void* out[5] = {items[i].out5, items[i].knn_a, items[i].knn_b, items[i].scores_a, items[i].scores_b};
+        for (int k = 0; k < 5; ++k)
+            if (out[k] && (k == 0 || items[i].topk != 0)) refs.push_back({out[k], i, k});
+    }
+    std::sort(refs.begin(), refs.end(), [](const Ref& a, const Ref& b) {
+        return a.p != b.p ? std::less<const void*>()(a.p, b.p) : a.member != b.member ? a.member < b.member : a.field < b.field;
+    });
+    for (size_t i = 1; i < refs.size(); ++i)
+        if (refs[i].p == refs[i - 1].p)
+            return fail(UMLH_E_INVALID, "%s: member %d: %s is also member %d's %s (members may not share output buffers)", who,
+                        refs[i].member, NAMES[refs[i].field], refs[i - 1].member, NAMES[refs[i - 1].field]);
+    return UMLH_OK;
+}
+
+uint64_t umlh_align_pairs_scratch(const umlh_align_pair_t* items, int32_t n_items, int32_t splits) {
+    if (check_align_group_count(nullptr, items, n_items, splits)) return 0;
+    for (int i = 0; i < n_items; ++i)
+        if (check_align_member(nullptr, items[i], splits)) return 0;
+    return umlh_align_pairs_bytes(items, n_items, splits);
+}
+
+int umlh_align_pairs(const umlh_align_pair_t* items, int32_t n_items, int32_t splits, void* scratch, uint64_t scratch_bytes,
+                     void* stream) {
+    const char* who = "umlh_align_pairs";
+    RC(check_align_group_count(who, items, n_items, splits));
+    char member[64];
+    for (int i = 0; i < n_items; ++i) {
+        snprintf(member, sizeof(member), "%s: member %d", who, i);
+        RC(check_align_member(member, items[i], splits));
+    }
+    RC(check_align_group_unique(who, items, n_items));
+    if (!scratch) return fail(UMLH_E_INVALID, "%s: scratch is NULL", who);
+    RC(check_scratch(who, scratch, scratch_bytes, umlh_align_pairs_bytes(items, n_items, splits), 8));
+    HIPCHK(umlh_align_launch_pairs(items, n_items, splits, scratch, (hipStream_t)stream), who);
     return UMLH_OK;
 }
 

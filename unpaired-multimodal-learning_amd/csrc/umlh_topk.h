@@ -24,12 +24,18 @@ constexpr int TK_KLD = TK_KMAX + 1;      // list row stride
 constexpr int TK_TARGET_WG = 512;        // auto splits: about two workgroups per CU of the 256
 constexpr int TK_MAX_SPLITS = 1024;      // (grid y)
 
+// Column chunks asked of a launch (or of several that share one grid) of `strips` 32-row strips in all: `splits` as asked for,
+// or (0 = auto) as many as bring the grid to TK_TARGET_WG workgroups.
+inline int topk_splits_for_strips(long long strips, int splits) {
+    long long s = splits > 0 ? splits : (strips > 0 ? (TK_TARGET_WG + strips - 1) / strips : 1);
+    return (int)(s > TK_MAX_SPLITS ? TK_MAX_SPLITS : (s < 1 ? 1 : s));
+}
+
 // Column chunks of a launch over n_query x n_train: `splits` as asked for (0 = auto), at most one per tile.
 inline int topk_splits(long long n_query, long long n_train, int splits) {
     const long long ntiles = (n_train + TK_COLS - 1) / TK_COLS, strips = (n_query + TK_ROWS - 1) / TK_ROWS;
-    long long s = splits > 0 ? splits : (TK_TARGET_WG + strips - 1) / strips;
-    if (s > TK_MAX_SPLITS) s = TK_MAX_SPLITS;
-    return (int)(s < 1 ? 1 : (s > ntiles ? ntiles : s));
+    const long long s = topk_splits_for_strips(strips, splits);
+    return (int)(s > ntiles ? ntiles : s);
 }
 
 // Scratch of a launch: `front_bytes` of the caller's own, the chunks' partial lists (scores, then indices: [splits][nq][kc]

@@ -3,7 +3,8 @@ expands them) run in groups through the grouped fused step (``gaussian.fused.Gro
 and one evaluation forward for a whole group of runs, whatever their widths, batch sizes, modes and seeds.
 
 Every run's log, parameters and optimizer state are bit for bit those of the same point run alone through ``build_run(fused=True)``
-and ``train_model_steps_fused``.  The alignment metrics of an evaluation stay one call per member."""
+and ``train_model_steps_fused``.  The alignment metrics of an evaluation are one ``umlh.align.measure_pairs`` call for the whole group
+(DESIGN section 27)."""
 from __future__ import annotations
 
 from itertools import product
@@ -128,10 +129,13 @@ def sweep_grouped(points, *, num_steps=None, eval_every=1, alignment=False, grou
                 log["loss"].append(losses)
             step += k
             if eval_every and step % eval_every == 0:
-                for log, (v, ex, ey) in zip(logs, grouped.evaluate(val, embeddings=alignment)):
+                evals = grouped.evaluate(val, embeddings=alignment)
+                for log, (v, _, _) in zip(logs, evals):
                     log["val_loss_x"].append(v[0]); log["val_loss_y"].append(v[1])
-                    if alignment:                                             # main.py:78-84, per member
-                        log["val_cka"].append(align.cka(ex, ey)); log["val_mknn"].append(align.mutual_knn(ex, ey, 10))
+                if alignment:                                                 # main.py:78-84, all members in one call
+                    res = align.measure_pairs([(ex, ey) for _, ex, ey in evals], topk=10)
+                    for i, log in enumerate(logs):
+                        log["val_cka"].append(res[i, 0]); log["val_mknn"].append(res[i, 4])
         pending.extend(zip(points[g0:g0 + group_size], models, logs))
     out = []
     for _, _, dlog in pending:                                                # the one read-back

@@ -69,7 +69,8 @@ def train_model_steps_fused(model, dataset, optimizer, num_steps, val_data_x, va
             val, ex, ey = trainer.evaluate(vx, vy, embeddings=alignment)
             log["val_loss_x"].append(val[0]); log["val_loss_y"].append(val[1])
             if alignment:                                                 # main.py:78-84
-                log["val_cka"].append(align.cka(ex, ey)); log["val_mknn"].append(align.mutual_knn(ex, ey, 10))
+                res = align.measure_pairs([(ex, ey)], topk=10)
+                log["val_cka"].append(res[0, 0]); log["val_mknn"].append(res[0, 4])
     if losses:
         host = torch.cat(losses).cpu()
         log["loss_x"], log["loss_y"], log["loss"] = ([float(t) for t in host[:, j]] for j in range(3))

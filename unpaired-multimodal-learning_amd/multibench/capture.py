@@ -128,11 +128,11 @@ class EmbeddingCapture:
                 lens, off = (self.l1, self.off1) if side == 1 else (self.l2, self.off2)
                 m[name] = self._pack([o[name] for o in outs], lens, off,
                                      out=self._matrix(name, outs[0][name].shape[-1], fresh=name in ("zx", "zy")))
-            cka, mknn = umlh.align.cka, lambda a, b: umlh.align.mutual_knn(a, b, topk=MKNN_TOPK)
-            got = torch.stack([cka(m["x_proj"], m["y_proj"]), mknn(m["x_proj"], m["y_proj"]), umlh.paired_cosine(m["x_proj"], m["y_proj"]),
-                               cka(m["zx"], m["zy"]), mknn(m["zx"], m["zy"]), umlh.paired_cosine(m["zx"], m["zy"]),
-                               cka(m["x_recon"], m["y_recon"]), mknn(m["x_recon"], m["y_recon"]),
-                               cka(m["zy"], self.raw_y)]).cpu().tolist()
+            al = umlh.align.measure_pairs([(m["x_proj"], m["y_proj"]), (m["zx"], m["zy"]), (m["x_recon"], m["y_recon"]),
+                                           (m["zy"], self.raw_y, {"topk": 0})], topk=MKNN_TOPK)      # the seven metrics in one call
+            got = torch.stack([al[0, 0], al[0, 4], umlh.paired_cosine(m["x_proj"], m["y_proj"]),
+                               al[1, 0], al[1, 4], umlh.paired_cosine(m["zx"], m["zy"]),
+                               al[2, 0], al[2, 4], al[3, 0]]).cpu().tolist()
         model.train()
         res = dict(zip(KEYS[:9], got))
         for k in ("val/cka_proj", "val/cka_embed", "val/cka_out", "val/cka_text_embeddings_features"):

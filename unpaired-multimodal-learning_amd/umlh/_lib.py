@@ -102,6 +102,15 @@ class AeEvalItem(C.Structure):                     # umlh_ae_eval_item_t: one ru
 AE_MAX_GROUP = 64                                  # UMLH_AE_MAX_GROUP
 
 
+class AlignPair(C.Structure):                      # umlh_align_pair_t: one member of umlh_align_pairs
+    _fields_ = [("a", C.c_void_p), ("lda", C.c_int32), ("d_a", C.c_int32), ("b", C.c_void_p), ("ldb", C.c_int32), ("d_b", C.c_int32),
+                ("n", C.c_int64), ("cka", C.c_int32), ("topk", C.c_int32), ("out5", C.c_void_p), ("knn_a", C.c_void_p),
+                ("knn_b", C.c_void_p), ("scores_a", C.c_void_p), ("scores_b", C.c_void_p)]
+
+
+ALIGN_MAX_PAIRS = 64                               # UMLH_ALIGN_MAX_PAIRS
+
+
 class RolloutCfg(C.Structure):
     _fields_ = [("Z", C.c_int32), ("d_ff", C.c_int32), ("D", C.c_int32), ("n_layers", C.c_int32), ("steps", C.c_int32),
                 ("eps", C.c_float)]
@@ -207,6 +216,8 @@ def _prototypes() -> dict:
         "umlh_align_cka_rbf": (rc, (vp, i32, i32, vp, i32, i32, i64, f64, i32, i32, vp, vp, u64, vp)),
         "umlh_align_cknna": (rc, (vp, vp, vp, vp, i64, i32, vp, vp, u64, vp)),
         "umlh_align_list_stats": (rc, (vp, vp, i64, i32, vp, vp, vp, u64, vp)),
+        "umlh_align_pairs_scratch": (u64, (P(AlignPair), i32, i32)),
+        "umlh_align_pairs": (rc, (P(AlignPair), i32, i32, vp, u64, vp)),
         # linear probes
         "umlh_masked_mean": (rc, (vp, i32, i32, i32, i64, i64, vp, vp, i32, vp)),
         "umlh_probe_scratch_bytes": (u64, (i64, i32, i32)),

@@ -5,6 +5,8 @@
 (:96-119, :252-255).  Every call enqueues on ``torch.cuda.current_stream`` and returns device tensors without
 synchronising.  Inputs: fp32 CUDA tensors with unit column stride are used in place (the row stride is passed on);
 other float dtypes are upcast and CPU tensors copied to the current device.  There is no CPU compute path.
+``measure_pairs`` (C ABI: ``umlh_align_pairs``) gives ``cka_terms`` and ``mutual_knn`` of many pairs in at most ten launches,
+bit for bit the values of the single calls.
 
 The kernels of umlh_kernels_align_ext.hip add the rest of the reference's ``AlignmentMetrics``: ``unbiased_cka`` (:122-125
 with hsic_unbiased :230-249), ``rbf_cka`` (``cka(kernel_metric='rbf')``, biased and unbiased, :103-119), ``cknna`` (:180-227),
@@ -28,7 +30,7 @@ import torch
 
 from . import _glue as glue
 from . import spectral
-from ._lib import check, load_library
+from ._lib import ALIGN_MAX_PAIRS, AlignPair, UmlhError, check, load_library
 
 MAX_TOPK = 32
 
@@ -116,6 +118,86 @@ def cka_terms(a: torch.Tensor, b: torch.Tensor, splits: int = 0) -> torch.Tensor
 def cka(a: torch.Tensor, b: torch.Tensor, splits: int = 0) -> torch.Tensor:
     """AlignmentMetrics.cka(a, b, kernel_metric='ip'): a 0-d float64 device tensor."""
     return cka_terms(a, b, splits)[0]
+
+
+# ---- many pairs in one fixed train of launches (umlh_align_pairs, DESIGN section 27) ----
+_PAIR_SCRATCH = {}      # (device, stream, splits, member signature) -> (uint8 device tensor, its size)
+
+
+def _pair_scratch(dev, items, n, splits, signature):
+    """Scratch of one umlh_align_pairs call, leased per (device, stream, group signature): calls on one stream run in order."""
+    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream, splits) + signature
+    hit = _PAIR_SCRATCH.get(key)
+    if hit is None:
+        nbytes = load_library().umlh_align_pairs_scratch(items, n, splits)
+        if nbytes == 0:
+            raise UmlhError(f"umlh_align_pairs_scratch: invalid arguments n_items={n} splits={splits} members={signature}")
+        if len(_PAIR_SCRATCH) >= 16:
+            _PAIR_SCRATCH.clear()
+        hit = _PAIR_SCRATCH[key] = (torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes)
+    return hit
+
+
+def measure_pairs(pairs, topk: int = 10, cka: bool = True, splits: int = 0, return_lists: bool = False):
+    """``cka_terms(a, b)`` and ``mutual_knn(a, b, topk)`` of many feature pairs at once: a float64 device tensor [G, 5] =
+    {cka, hsic_kl, hsic_kk, hsic_ll, mutual_knn} per pair, every word bit for bit what the single calls give with the same
+    ``splits``.  The whole group takes at most ten launches, whatever G is (more than 64 pairs: consecutive groups of 64).
+
+    ``pairs``: a list of ``(a, b)`` or ``(a, b, {"topk": ..., "cka": ...})``; the dict overrides the call's ``topk`` / ``cka`` for
+    that pair.  ``topk=0`` skips the mutual k-NN and ``cka=False`` the CKA of a pair: its columns are NaN.  Pairs may differ in
+    every shape and may share tensors.  ``return_lists``: also a list with, per pair, ``(knn_a, scores_a, knn_b, scores_b)`` as
+    ``knn(..., return_scores=True)`` returns them (None for a pair without lists)."""
+    what = "measure_pairs"
+    pairs = list(pairs)
+    if not pairs:
+        raise ValueError(f"{what}: no pairs")
+    if splits < 0:
+        raise ValueError(f"{what}: splits={splits} < 0")
+    members = []
+    for i, pr in enumerate(pairs):
+        who = f"{what}: member {i}"
+        if not isinstance(pr, (tuple, list)) or len(pr) not in (2, 3) or (len(pr) == 3 and not isinstance(pr[2], dict)):
+            raise ValueError(f"{who}: expected (a, b) or (a, b, {{'topk': ..., 'cka': ...}})")
+        opts = dict(pr[2]) if len(pr) == 3 else {}
+        unknown = set(opts) - {"topk", "cka"}
+        if unknown:
+            raise ValueError(f"{who}: unknown options {sorted(unknown)}")
+        k, c = int(opts.get("topk", topk)), bool(opts.get("cka", cka))
+        _check_pair(pr[0], pr[1], who, splits)
+        if k != 0:
+            _check_topk(k, pr[0].shape[0], who)
+        if k == 0 and not c:
+            raise ValueError(f"{who}: cka=False and topk=0 ask for nothing")
+        members.append((pr[0], pr[1], k, c))
+    dev = _device()
+    lib = load_library()
+    if all(k != 0 and c for _, _, k, c in members):                  # every word is written: no fill
+        out = torch.empty((len(members), 5), dtype=torch.float64, device=dev)
+    else:
+        out = torch.full((len(members), 5), math.nan, dtype=torch.float64, device=dev)
+    lists = []
+    for g0 in range(0, len(members), ALIGN_MAX_PAIRS):
+        group = members[g0:g0 + ALIGN_MAX_PAIRS]
+        items = (AlignPair * len(group))()
+        keep, sig = [], []
+        for i, (it, (a, b, k, c)) in enumerate(zip(items, group)):
+            xa, xb = glue.features(a, f"{what}: member {g0 + i}", dev), glue.features(b, f"{what}: member {g0 + i}", dev)
+            n = xa.shape[0]
+            it.a, it.lda, it.d_a = xa.data_ptr(), xa.stride(0), xa.shape[1]
+            it.b, it.ldb, it.d_b = xb.data_ptr(), xb.stride(0), xb.shape[1]
+            it.n, it.cka, it.topk = n, int(c), k
+            it.out5 = out[g0 + i].data_ptr()
+            got = None
+            if return_lists and k:
+                got = (torch.empty((n, k), dtype=torch.int32, device=dev), torch.empty((n, k), dtype=torch.float32, device=dev),
+                       torch.empty((n, k), dtype=torch.int32, device=dev), torch.empty((n, k), dtype=torch.float32, device=dev))
+                it.knn_a, it.scores_a, it.knn_b, it.scores_b = (t.data_ptr() for t in got)
+            lists.append(got)
+            keep.append((xa, xb))
+            sig.append((n, it.d_a, it.d_b, k, int(c), got is not None))
+        scratch, nbytes = _pair_scratch(dev, items, len(group), splits, tuple(sig))
+        check(lib.umlh_align_pairs(items, len(group), splits, scratch.data_ptr(), nbytes, glue.stream(dev)), "umlh_align_pairs")
+    return (out, lists) if return_lists else out
 
 
 # ---- unbiased / RBF CKA, CKNNA and the list statistics (umlh_kernels_align_ext.hip) ----
