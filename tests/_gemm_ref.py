@@ -24,7 +24,7 @@ CRIT_MAX = 2.0 ** -20
 CRIT_RMS = 2.0 ** -23
 
 KT = 16              # K chunk of the tile kernels (csrc/umlh_common.h)
-DWKIDS = 4096        # reduction rows per split whose row ids fit dw_f32's LDS table (csrc/umlh_kernels_f32.hip)
+DWKIDS = 4096        # reduction rows per split whose row ids fit dw_f32's LDS table (csrc/umlh_kernels_f32.hip: KIDS)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------- #

@@ -5,7 +5,11 @@ sides of the 768-workgroup switch, against float64 (tests/_gemm_ref.py: the crit
 The case table (_gemm_ref.CASES) runs in fresh child processes, one per setting of the switches UMLH_F32_X3 / UMLH_F32_TM /
 UMLH_F32_DW (they are read once per process), one after another.  Every output buffer is (M+1) x ldo floats filled with a
 sentinel and every slab buffer is one slab longer than the launch needs and filled with NaN: a write outside the [M, N] window
-lands on a sentinel inside the allocation, and the parent checks that every element outside the window is bit-unchanged."""
+lands on a sentinel inside the allocation, and the parent checks that every element outside the window is bit-unchanged.
+
+The SHA-256 digest of every (case, setting) window is also compared with the one that scripts/make_f32_digests.py recorded in
+tests/golden/f32_path_digests.json from an earlier build (the table's "recorded_from"): the kernel paths keep their bits across
+commits, not only their accuracy."""
 import hashlib
 import json
 import os
@@ -80,6 +84,18 @@ def _window(c, buf):
     return full[:M, :N], full.view(np.uint32)[mask]
 
 
+def window_digests(dirs):
+    """{case id: {environment: SHA-256 of the [M, N] window}} of the children's outputs (cases that launch something)."""
+    return {c["id"]: {name: hashlib.sha256(np.ascontiguousarray(_window(c, np.load(dirs[name] / (c["id"] + "_out.npy")))[0]).tobytes()).hexdigest()
+                      for name in ENVS} for c in CASES if c["M"] and c["N"]}
+
+
+def _recorded_digests():
+    """The same digests of the build that tests/golden/f32_path_digests.json was recorded from (scripts/make_f32_digests.py)."""
+    with open(os.path.join(ROOT, "tests", "golden", "f32_path_digests.json")) as f:
+        return json.load(f)["gemm"]
+
+
 def _check_nonfinite(kernel, got, ref, S):
     """Exact IEEE pattern on the fp32-MFMA and gemm_enc paths; on the x3 paths an infinite operand may give NaN instead of +-inf
     (its mid piece is inf - inf), so there: non-finite where float64 is, NaN where float64 is, the rest within the criterion."""
@@ -99,6 +115,8 @@ def _check_nonfinite(kernel, got, ref, S):
 def test_gemm_f32_every_kernel_path_against_float64(tmp_path):
     dirs = _run_children(tmp_path)
     digests, kernels, levels, failures = {}, {}, {}, []
+    by_case, recorded = window_digests(dirs), _recorded_digests()
+    assert sorted(by_case) == sorted(recorded)
     for c in CASES:
         ref, S = case_ref(c) if c["M"] and c["N"] else (None, None)
         for name, env in ENVS.items():
@@ -116,7 +134,9 @@ def test_gemm_f32_every_kernel_path_against_float64(tmp_path):
                     failures.append(f"{c['id']} [{name}, {kernel}]: a split-K slab was written outside its [M, N] window")
             if ref is None:
                 continue
-            digests[c["id"], name] = hashlib.sha256(np.ascontiguousarray(got).tobytes()).hexdigest()
+            digests[c["id"], name] = by_case[c["id"]][name]
+            if digests[c["id"], name] != recorded[c["id"]][name]:
+                failures.append(f"{c['id']} [{name}, {kernel}]: the bits differ from the recorded build's")
             try:
                 err = _check_nonfinite(kernel, got, ref, S) if c["nonfinite"] else gemm_err(got, ref, S)
             except AssertionError as e:

@@ -43,6 +43,22 @@ __device__ __forceinline__ f32x4v load4_guard(const float* p, int lim, bool vec_
 }
 
 // --------------------------------------------------------------------------- //
+// x3 products (umlh_f32_x3, umlh_common.h): both fp32 operands split into three bf16 piece planes (0 = hi, 1 = mid, 2 = lo),
+// six piece products per product on v_mfma_f32_32x32x16_bf16.  X3_ORDER is the order they are issued in, {plane of A, plane
+// of B}: small terms first, the hi*hi product last.  gemm_f32, dw_f32x3 and the forward's MODE 3 all read it (and
+// tests/_gemm_ref.py restates it as X3_PAIRS).
+// --------------------------------------------------------------------------- //
+constexpr int X3_ORDER[6][2] = {{2, 0}, {0, 2}, {1, 1}, {1, 0}, {0, 1}, {0, 0}};   // lo*hi, hi*lo, mid*mid, mid*hi, hi*mid, hi*hi
+typedef unsigned int u32x4s __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+// element i of the three planes p[0..2] <- the pieces of the pair (x, y)
+__device__ __forceinline__ void split3_into(u32x4s (&p)[3], int i, float x, float y) {
+    const Split3 s3 = split3_pair(x, y);
+    p[0][i] = s3.hi; p[1][i] = s3.mid; p[2][i] = s3.lo;
+}
+
+// --------------------------------------------------------------------------- //
 // fused forward + cross entropy
 // --------------------------------------------------------------------------- //
 // Workgroup = 8 waves = WC (class direction) x WS (sample direction).  The MFMA is
@@ -59,27 +75,36 @@ __device__ __forceinline__ f32x4v load4_guard(const float* p, int lim, bool vec_
 // while their rings refill (the stream is 16 B/clk/CU, a quarter of what the bf16 forward pulls).  MODE 1 spent 28 % of its
 // main loop between chunks (64 KB of W through registers into LDS and a barrier per 16 k: 5.67k cycles per chunk for 4.1k of
 // MFMA; scripts/fwd32_stamps.py).  Same products in the same order as MODE 1: bit-identical results.
+// LDS layout of fwd_ce_f32<CTW, WC, MODE> in floats: the kernel takes its offsets from it, the launcher its byte count.
+template <int CTW, int WC, int MODE>
+struct FwdLds {
+    static constexpr int WS = 8 / WC, CPAD = 32 * CTW * WC, TS = 32 * WS;
+    static constexpr int LDW = CPAD + 4, LDX = TS + 4;   // k-major rows of MODE 0's tiles
+    // two LDS buffers of the (W, X) K-chunk ([KT][LDW] then [KT][LDX] each): chunk c+1 is written while chunk c feeds the MFMAs,
+    // one barrier per chunk (the 64-cycle fp32 MFMAs of the partner wave cover the ds_write_b32 stream)
+    static constexpr int BUF = KT * (LDW + LDX);
+    static constexpr int STG = 8 * CTW * 32 * 32;        // epilogue: dZ staging, 8 waves x [CTW*32][32] floats (aliases the tile buffers)
+    static constexpr int XK = 16384 / TS;                // MODE 2 / 3: K-block of the X rows resident in LDS: TS x XK floats = 64 KB
+    static constexpr int XLD = XK + 4;                   // its row stride (floats): an odd multiple of 16 B -> the b128 reads of 16 rows hit 16 slots
+    static constexpr int XT2 = MODE >= 2 ? TS * XLD : 0;
+    static constexpr int TILE0 = 2 * BUF > STG ? 2 * BUF : STG;
+    static constexpr int TILE = TILE0 > XT2 ? TILE0 : XT2;
+    static constexpr int RED = TILE;                     // [WC][TS][4]
+    static constexpr int RED2 = RED + WC * TS * 4;       // [WS][4]
+    static constexpr size_t BYTES = sizeof(float) * (RED2 + WS * 4 + 16);
+};
+
 template <int CTW, int WC, int MODE>
 __global__ __launch_bounds__(512) void fwd_ce_f32(FwdArgs a) {
+    typedef FwdLds<CTW, WC, MODE> L;
     constexpr bool FAST = MODE >= 1;
-    constexpr int WS = 8 / WC;
-    constexpr int CPAD = 32 * CTW * WC;
-    constexpr int TS = 32 * WS;
-    constexpr int LDW = CPAD + 4;
-    constexpr int LDX = TS + 4;
+    constexpr int WS = L::WS, CPAD = L::CPAD, TS = L::TS, LDW = L::LDW, LDX = L::LDX, BUF = L::BUF;
     constexpr int NPW = (CPAD * 4 + 511) / 512;     // float4 pieces of W per thread
     constexpr int NPX = (TS * 4 + 511) / 512;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    // two LDS buffers of the (W, X) K-chunk: chunk c+1 is written while chunk c feeds the MFMAs, one
-    // barrier per chunk (the 64-cycle fp32 MFMAs of the partner wave cover the ds_write_b32 stream)
-    constexpr int BUF = KT * (LDW + LDX);
     float* Ws0 = smem;                    // [2][KT][LDW] then [KT][LDX]
-    constexpr int STG = 8 * CTW * 32 * 32;                                  // epilogue: dZ staging, 8 waves x [CTW*32][32] floats (aliases the tile buffers)
-    constexpr int XT2 = MODE >= 2 ? TS * (16384 / TS + 4) : 0;              // MODE 2 / 3: the resident X block
-    constexpr int TILE0 = 2 * BUF > STG ? 2 * BUF : STG;
-    constexpr int TILE = TILE0 > XT2 ? TILE0 : XT2;
-    float* red = smem + TILE;             // [WC][TS][4]
-    float* red2 = red + WC * TS * 4;      // [WS][4]
+    float* red = smem + L::RED;
+    float* red2 = smem + L::RED2;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wc = wave % WC, ws = wave / WC;
@@ -112,102 +137,9 @@ __global__ __launch_bounds__(512) void fwd_ce_f32(FwdArgs a) {
     // runs alone.  Wave-uniform; the accumulators stay 0 and the epilogue masks them as before.
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     const bool wave_live = row0 + (wave_u / WC) * 32 < sg.rows && (wave_u % WC) * CTW * 32 < C;
-    if constexpr (MODE == 3) {
-        // MODE 2's structure on the bf16 matrix pipe (umlh_f32_x3 in umlh_common.h): W arrives pre-split -- three bf16 piece planes
-        // per fragment, [K/16 chunk][CPAD/32 tile][3 planes][64 lanes][8 bf16], 3 KB per (chunk, tile) instead of 2 KB --, the
-        // wave splits its B fragment (8 floats of its sample row per chunk, read from the fp32 X block in LDS) in registers (44
-        // VALU operations per chunk, issued under the MFMAs), and a chunk of a class tile is six v_mfma_f32_32x32x16_bf16
-        // (192 cycles) instead of eight v_mfma_f32_32x32x2_f32 (512 cycles).  Same accumulator layout: the epilogue is shared.
-        typedef unsigned int u32x4s __attribute__((ext_vector_type(4)));
-        typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-        constexpr int XK = 16384 / TS;
-        constexpr int XLD = XK + 4;
-        constexpr int NPX2 = (TS * (XK / 4)) / 512;
-        constexpr int PD = 2;
-        float* Xt = smem;
-        const float* xs2[NPX2];
-#pragma unroll
-        for (int q = 0; q < NPX2; ++q) {
-            const int pp = tid + 512 * q;
-            const int rc = min(row0 + pp / (XK / 4), sg.rows - 1);
-            const int64_t rid = sg.feat_index ? sg.feat_index[rc] : (int64_t)rc;
-            xs2[q] = sg.feats + (size_t)rid * sg.ld + 4 * (pp % (XK / 4));
-        }
-        const u32x4s* wl = reinterpret_cast<const u32x4s*>(a.Ws) + (size_t)(wc * CTW) * 192 + lane;
-        const int nch = K / KT;
-        auto wfrag = [&](int c, int ct, int plane) -> u32x4s { return wl[((size_t)c * (CPAD / 32) + ct) * 192 + plane * 64]; };
-        u32x4s ring[PD][CTW][3];
-        if (wave_live) {
-#pragma unroll
-            for (int d = 0; d < PD; ++d)
-#pragma unroll
-                for (int ct = 0; ct < CTW; ++ct)
-#pragma unroll
-                    for (int pl = 0; pl < 3; ++pl) ring[d][ct][pl] = wfrag(min(d, nch - 1), ct, pl);
-        }
-        STAMP(1);
-        for (int kb0 = 0; kb0 < K; kb0 += XK) {
-            const int kbw = min(XK, K - kb0);
-            f32x4v xr[NPX2];
-#pragma unroll
-            for (int q = 0; q < NPX2; ++q) {
-                const int col = 4 * ((tid + 512 * q) % (XK / 4));
-                xr[q] = *reinterpret_cast<const f32x4v*>(xs2[q] + kb0 + min(col, kbw - 4) - col);
-            }
-            __syncthreads();
-#pragma unroll
-            for (int q = 0; q < NPX2; ++q) {
-                const int pp = tid + 512 * q;
-                *reinterpret_cast<f32x4v*>(Xt + (pp / (XK / 4)) * XLD + 4 * (pp % (XK / 4))) = xr[q];
-            }
-            __syncthreads();
-            if (wave_live) {
-                const int c0 = kb0 / KT, ncb = kbw / KT;
-                const float* xrow = Xt + (ws * 32 + l31) * XLD + 8 * h;
-                for (int c = 0; c < ncb; c += PD) {
-#pragma unroll
-                    for (int d = 0; d < PD; ++d) {
-                        const f32x4v b0 = *reinterpret_cast<const f32x4v*>(xrow + (c + d) * KT);
-                        const f32x4v b1 = *reinterpret_cast<const f32x4v*>(xrow + (c + d) * KT + 4);
-                        u32x4s bh, bm, bl;
-                        { const Split3 s3 = split3_pair(b0[0], b0[1]); bh[0] = s3.hi; bm[0] = s3.mid; bl[0] = s3.lo; }
-                        { const Split3 s3 = split3_pair(b0[2], b0[3]); bh[1] = s3.hi; bm[1] = s3.mid; bl[1] = s3.lo; }
-                        { const Split3 s3 = split3_pair(b1[0], b1[1]); bh[2] = s3.hi; bm[2] = s3.mid; bl[2] = s3.lo; }
-                        { const Split3 s3 = split3_pair(b1[2], b1[3]); bh[3] = s3.hi; bm[3] = s3.mid; bl[3] = s3.lo; }
-                        const bf16x8 vbh = __builtin_bit_cast(bf16x8, bh), vbm = __builtin_bit_cast(bf16x8, bm), vbl = __builtin_bit_cast(bf16x8, bl);
-#pragma unroll
-                        for (int ct = 0; ct < CTW; ++ct) {
-                            const bf16x8 ah = __builtin_bit_cast(bf16x8, ring[d][ct][0]), am = __builtin_bit_cast(bf16x8, ring[d][ct][1]);
-                            const bf16x8 al = __builtin_bit_cast(bf16x8, ring[d][ct][2]);
-                            // small terms first, the hi*hi product last
-                            acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, vbh, acc[ct], 0, 0, 0);
-                            acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, vbl, acc[ct], 0, 0, 0);
-                            acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, vbm, acc[ct], 0, 0, 0);
-                            acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, vbh, acc[ct], 0, 0, 0);
-                            acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, vbm, acc[ct], 0, 0, 0);
-                            acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, vbh, acc[ct], 0, 0, 0);
-                        }
-                        const int nxt = min(c0 + c + d + PD, nch - 1);
-#pragma unroll
-                        for (int ct = 0; ct < CTW; ++ct)
-#pragma unroll
-                            for (int pl = 0; pl < 3; ++pl) ring[d][ct][pl] = wfrag(nxt, ct, pl);
-                        // a tile's three planes are requested again as soon as its six MFMAs are out (not after the chunk's 24): more of
-                        // the stream in flight per wave at the same register count
-                        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);            // B reads
-#pragma unroll
-                        for (int ct = 0; ct < CTW; ++ct) {
-                            __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);        // this tile's MFMAs (the split's VALU operations float between them)
-                            __builtin_amdgcn_sched_group_barrier(0x020, 3, 0);        // its refill
-                        }
-                    }
-                }
-            }
-        }
-        __syncthreads();
-    } else if constexpr (MODE == 2) {
-        constexpr int XK = 16384 / TS;                      // K-block of the X rows resident in LDS: TS x XK floats = 64 KB
-        constexpr int XLD = XK + 4;                         // row stride (floats): an odd multiple of 16 B -> the b128 reads of 16 rows hit 16 slots
+    if constexpr (MODE >= 2) {
+        // the streamed loops: the block's X rows are resident in LDS one K-block at a time, W streams into a register ring
+        constexpr int XK = L::XK, XLD = L::XLD;
         constexpr int NPX2 = (TS * (XK / 4)) / 512;         // 16-B pieces of an X block per thread
         constexpr int PD = 2;                               // chunks (16 k) of W fragments in flight per wave
         float* Xt = smem;                                   // [TS][XLD]
@@ -219,24 +151,7 @@ __global__ __launch_bounds__(512) void fwd_ce_f32(FwdArgs a) {
             const int64_t rid = sg.feat_index ? sg.feat_index[rc] : (int64_t)rc;
             xs2[q] = sg.feats + (size_t)rid * sg.ld + 4 * (pp % (XK / 4));
         }
-        // fragment (chunk c, class tile t): 64 lanes x 8 floats at Ws + ((c * CPAD/32 + t) * 64 + lane) * 8; lane (r, h) holds
-        // W[32 t + r][16 c + 8 h .. + 8): the A operands of its eight 32x32x2 steps of the chunk (k order inside a chunk is
-        // free as long as W and X agree; it is MODE 1's)
-        const float* wl = a.Ws + ((size_t)(wc * CTW) * 64 + lane) * 8;
-        const int nch = K / KT;                             // even (host-checked)
-        auto wfrag = [&](int c, int ct, int half) -> f32x4v {
-            return *reinterpret_cast<const f32x4v*>(wl + ((size_t)c * (CPAD / 32) + ct) * 512 + 4 * half);
-        };
-        f32x4v ring[PD][CTW][2];
-        if (wave_live) {
-#pragma unroll
-            for (int d = 0; d < PD; ++d)
-#pragma unroll
-                for (int ct = 0; ct < CTW; ++ct) { ring[d][ct][0] = wfrag(min(d, nch - 1), ct, 0); ring[d][ct][1] = wfrag(min(d, nch - 1), ct, 1); }
-        }
-        STAMP(1);
-        for (int kb0 = 0; kb0 < K; kb0 += XK) {
-            const int kbw = min(XK, K - kb0);               // multiple of 32
+        auto x_stage = [&](int kb0, int kbw) {              // columns kb0 .. kb0 + kbw of the block's rows -> Xt, both barriers included
             f32x4v xr[NPX2];
 #pragma unroll
             for (int q = 0; q < NPX2; ++q) {
@@ -250,28 +165,107 @@ __global__ __launch_bounds__(512) void fwd_ce_f32(FwdArgs a) {
                 *reinterpret_cast<f32x4v*>(Xt + (pp / (XK / 4)) * XLD + 4 * (pp % (XK / 4))) = xr[q];
             }
             __syncthreads();
+        };
+        const int nch = K / KT;                             // even (host-checked)
+        if constexpr (MODE == 3) {
+            // MODE 2's structure on the bf16 matrix pipe (umlh_f32_x3 in umlh_common.h): W arrives pre-split -- three bf16 piece planes
+            // per fragment, [K/16 chunk][CPAD/32 tile][3 planes][64 lanes][8 bf16], 3 KB per (chunk, tile) instead of 2 KB --, the
+            // wave splits its B fragment (8 floats of its sample row per chunk, read from the fp32 X block in LDS) in registers (44
+            // VALU operations per chunk, issued under the MFMAs), and a chunk of a class tile is six v_mfma_f32_32x32x16_bf16
+            // (192 cycles) instead of eight v_mfma_f32_32x32x2_f32 (512 cycles).  Same accumulator layout: the epilogue is shared.
+            const u32x4s* wl = reinterpret_cast<const u32x4s*>(a.Ws) + (size_t)(wc * CTW) * 192 + lane;
+            auto wfrag = [&](int c, int ct, int plane) -> u32x4s { return wl[((size_t)c * (CPAD / 32) + ct) * 192 + plane * 64]; };
+            u32x4s ring[PD][CTW][3];
             if (wave_live) {
-                const int c0 = kb0 / KT, ncb = kbw / KT;
-                const float* xrow = Xt + (ws * 32 + l31) * XLD + 8 * h;
-                for (int c = 0; c < ncb; c += PD) {
 #pragma unroll
-                    for (int d = 0; d < PD; ++d) {
-                        const int cb = UMLH_ABL(a.dbg == 22 || a.dbg == 23) ? 0 : c + d;
-                        const f32x4v b0 = *reinterpret_cast<const f32x4v*>(xrow + cb * KT);
-                        const f32x4v b1 = *reinterpret_cast<const f32x4v*>(xrow + cb * KT + 4);
+                for (int d = 0; d < PD; ++d)
 #pragma unroll
-                        for (int s2 = 0; s2 < 8; ++s2)
+                    for (int ct = 0; ct < CTW; ++ct)
+#pragma unroll
+                        for (int pl = 0; pl < 3; ++pl) ring[d][ct][pl] = wfrag(min(d, nch - 1), ct, pl);
+            }
+            STAMP(1);
+            for (int kb0 = 0; kb0 < K; kb0 += XK) {
+                const int kbw = min(XK, K - kb0);
+                x_stage(kb0, kbw);
+                if (wave_live) {
+                    const int c0 = kb0 / KT, ncb = kbw / KT;
+                    const float* xrow = Xt + (ws * 32 + l31) * XLD + 8 * h;
+                    for (int c = 0; c < ncb; c += PD) {
+#pragma unroll
+                        for (int d = 0; d < PD; ++d) {
+                            const f32x4v b0 = *reinterpret_cast<const f32x4v*>(xrow + (c + d) * KT);
+                            const f32x4v b1 = *reinterpret_cast<const f32x4v*>(xrow + (c + d) * KT + 4);
+                            u32x4s bp[3];
+                            split3_into(bp, 0, b0[0], b0[1]);
+                            split3_into(bp, 1, b0[2], b0[3]);
+                            split3_into(bp, 2, b1[0], b1[1]);
+                            split3_into(bp, 3, b1[2], b1[3]);
 #pragma unroll
                             for (int ct = 0; ct < CTW; ++ct)
-                                acc[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(ring[d][ct][s2 >> 2][s2 & 3], (s2 < 4 ? b0 : b1)[s2 & 3], acc[ct], 0, 0, 0);
-                        const int nxt = UMLH_ABL(a.dbg == 21 || a.dbg == 23) ? 0 : min(c0 + c + d + PD, nch - 1);      // (past the end: a harmless re-load of the last chunk)
 #pragma unroll
-                        for (int ct = 0; ct < CTW; ++ct) { ring[d][ct][0] = wfrag(nxt, ct, 0); ring[d][ct][1] = wfrag(nxt, ct, 1); }
-                        // pin the emitted order per chunk: B reads, its MFMAs, then the slot's refill loads (left alone, hipcc sinks
-                        // every refill to the end of the loop body and the next iteration's first MFMA waits a full L2 round trip)
-                        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);            // B reads
-                        __builtin_amdgcn_sched_group_barrier(0x008, 8 * CTW, 0);      // MFMAs
-                        __builtin_amdgcn_sched_group_barrier(0x020, 2 * CTW, 0);      // VMEM reads
+                                for (int pd = 0; pd < 6; ++pd)
+                                    acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ring[d][ct][X3_ORDER[pd][0]]),
+                                                                                      __builtin_bit_cast(bf16x8, bp[X3_ORDER[pd][1]]), acc[ct], 0, 0, 0);
+                            const int nxt = min(c0 + c + d + PD, nch - 1);
+#pragma unroll
+                            for (int ct = 0; ct < CTW; ++ct)
+#pragma unroll
+                                for (int pl = 0; pl < 3; ++pl) ring[d][ct][pl] = wfrag(nxt, ct, pl);
+                            // a tile's three planes are requested again as soon as its six MFMAs are out (not after the chunk's 24): more of
+                            // the stream in flight per wave at the same register count
+                            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);            // B reads
+#pragma unroll
+                            for (int ct = 0; ct < CTW; ++ct) {
+                                __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);        // this tile's MFMAs (the split's VALU operations float between them)
+                                __builtin_amdgcn_sched_group_barrier(0x020, 3, 0);        // its refill
+                            }
+                        }
+                    }
+                }
+            }
+        } else {
+            // fragment (chunk c, class tile t): 64 lanes x 8 floats at Ws + ((c * CPAD/32 + t) * 64 + lane) * 8; lane (r, h) holds
+            // W[32 t + r][16 c + 8 h .. + 8): the A operands of its eight 32x32x2 steps of the chunk (k order inside a chunk is
+            // free as long as W and X agree; it is MODE 1's)
+            const float* wl = a.Ws + ((size_t)(wc * CTW) * 64 + lane) * 8;
+            auto wfrag = [&](int c, int ct, int half) -> f32x4v {
+                return *reinterpret_cast<const f32x4v*>(wl + ((size_t)c * (CPAD / 32) + ct) * 512 + 4 * half);
+            };
+            f32x4v ring[PD][CTW][2];
+            if (wave_live) {
+#pragma unroll
+                for (int d = 0; d < PD; ++d)
+#pragma unroll
+                    for (int ct = 0; ct < CTW; ++ct) { ring[d][ct][0] = wfrag(min(d, nch - 1), ct, 0); ring[d][ct][1] = wfrag(min(d, nch - 1), ct, 1); }
+            }
+            STAMP(1);
+            for (int kb0 = 0; kb0 < K; kb0 += XK) {
+                const int kbw = min(XK, K - kb0);               // multiple of 32
+                x_stage(kb0, kbw);
+                if (wave_live) {
+                    const int c0 = kb0 / KT, ncb = kbw / KT;
+                    const float* xrow = Xt + (ws * 32 + l31) * XLD + 8 * h;
+                    for (int c = 0; c < ncb; c += PD) {
+#pragma unroll
+                        for (int d = 0; d < PD; ++d) {
+                            const int cb = UMLH_ABL(a.dbg == 22 || a.dbg == 23) ? 0 : c + d;
+                            const f32x4v b0 = *reinterpret_cast<const f32x4v*>(xrow + cb * KT);
+                            const f32x4v b1 = *reinterpret_cast<const f32x4v*>(xrow + cb * KT + 4);
+#pragma unroll
+                            for (int s2 = 0; s2 < 8; ++s2)
+#pragma unroll
+                                for (int ct = 0; ct < CTW; ++ct)
+                                    acc[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(ring[d][ct][s2 >> 2][s2 & 3], (s2 < 4 ? b0 : b1)[s2 & 3], acc[ct], 0, 0, 0);
+                            const int nxt = UMLH_ABL(a.dbg == 21 || a.dbg == 23) ? 0 : min(c0 + c + d + PD, nch - 1);      // (past the end: a harmless re-load of the last chunk)
+#pragma unroll
+                            for (int ct = 0; ct < CTW; ++ct) { ring[d][ct][0] = wfrag(nxt, ct, 0); ring[d][ct][1] = wfrag(nxt, ct, 1); }
+                            // pin the emitted order per chunk: B reads, its MFMAs, then the slot's refill loads (left alone, hipcc sinks
+                            // every refill to the end of the loop body and the next iteration's first MFMA waits a full L2 round trip)
+                            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);            // B reads
+                            __builtin_amdgcn_sched_group_barrier(0x008, 8 * CTW, 0);      // MFMAs
+                            __builtin_amdgcn_sched_group_barrier(0x020, 2 * CTW, 0);      // VMEM reads
+                        }
                     }
                 }
             }
@@ -548,8 +542,9 @@ __global__ __launch_bounds__(512) void fwd_ce_f32(FwdArgs a) {
         const float inv = 1.f / se;
         const float ic = inv * coef;                                  // one multiply per element (p * coef with p = e * inv differs in the last bit only)
         // every wave has passed the last barrier of the main loop (and the exchanges above): the tile buffers are free.
-        // Wave-private staging tile [CTW*32 class rows][32 samples] fp32, no padding: the ds_write_b32 of a register is 32
-        // consecutive floats per lane half, the ds_read_b128 of 8 rows x 8 quads is conflict-free in the 16-lane groups
+        // Wave-private staging tile [CTW*32 class rows][32 samples] fp32
+        // (the slab tile idiom of slab_tile_stage / slab_tile_store, spelled out: through the helpers fwd_ce_f32<1,2,1> takes 66
+        // VGPRs instead of 64 and loses a wave of occupancy)
         float* stg = smem + wave * (CTW * 32 * 32);
 #pragma unroll
         for (int ct = 0; ct < CTW; ++ct)
@@ -611,7 +606,76 @@ __global__ __launch_bounds__(512) void fwd_ce_f32(FwdArgs a) {
 // --------------------------------------------------------------------------- //
 // tile = 64*TM x 64*TM, 4 waves (2x2) of TM x TM MFMA tiles each.  TM = 2 (128x128) maximises reuse; TM = 1
 // (64x64) quadruples the workgroup count for GEMMs whose 128x128 grid cannot fill the chip.
-constexpr int GKIDS = 4096;   // reduction rows per split whose row ids fit the LDS table
+
+// ---- split-K prologue shared by gemm_f32, dw_f32 and dw_f32x3 ----
+// reduction rows per split whose row ids fit the LDS table (16 KB; 2048 sent cfg3's dW_head -- 2 splits of 4096 rows -- to the
+// 64x64 gemm_f32 tile: 812 us instead of ~300)
+constexpr int KIDS = 4096;
+
+struct KRange { int kb, ke; };
+// reduction range of split z: uniform chunks, or modality-aligned ones (GemmArgs::nsplit1)
+__device__ __forceinline__ KRange splitk_range(const GemmArgs& g, int z) {
+    int kb = z * g.k_chunk, ke = min(g.K, kb + g.k_chunk);
+    if (g.nsplit1 > 0) {
+        if (z < g.nsplit1) ke = min(g.k_switch, kb + g.k_chunk);
+        else { kb = g.k_switch + (z - g.nsplit1) * g.k_chunk; ke = min(g.K, kb + g.k_chunk); }
+    }
+    return {kb, ke};
+}
+
+// reduction index k is a valid row of its modality (TB == 1: rows outside [0, k_valid) of either part are zeros)
+__device__ __forceinline__ bool kvalid(const GemmArgs& g, int k) {
+    return k < g.k_switch ? (k < g.k_valid1) : (k - g.k_switch < g.k_valid2);
+}
+// ... and lies inside the split; written with selects (the dW tiles evaluate it between MFMAs, without branches)
+__device__ __forceinline__ bool kvalid_before(const GemmArgs& g, int k, int ke) {
+    const bool first = k < g.k_switch;
+    return (k < ke) & ((first ? k : k - g.k_switch) < (first ? g.k_valid1 : g.k_valid2));
+}
+
+// kid[i] = gathered row id of reduction row kb + i of this split, -1 = masked row; NT threads, ends with the barrier
+template <int NT>
+__device__ __forceinline__ void fill_row_ids(const GemmArgs& g, int* kid, int kb, int ke, int tid) {
+    for (int i = tid; i < ke - kb; i += NT) {
+        const int k = kb + i;
+        int rid = -1;
+        if (kvalid(g, k)) {
+            if (k < g.k_switch) rid = g.k_rows ? (int)g.k_rows[k] : k;
+            else { const int kl = k - g.k_switch; rid = g.k_rows2 ? (int)g.k_rows2[kl] : kl; }
+        }
+        kid[i] = rid;
+    }
+    __syncthreads();
+}
+
+// ---- slab tile store: a wave's NI x NJ accumulator tiles (32 x 32 each) -> its private LDS tile [32 NI rows][32 NJ columns] ->
+// 16-byte row stores (a lane stores 16 B of one row instead of 64 scattered 4-byte write-through stores).  No padding: the
+// ds_write_b32 of a register is 32 consecutive floats per lane half, and the ds_read_b128 of the rows of one store instruction
+// is conflict-free in its 16-lane groups.  The LDS must be free (every wave past the main loop's last barrier). ----
+template <int NI, int NJ>
+__device__ __forceinline__ void slab_tile_stage(float* stg, const f32x16* acc, float mul, int lane) {
+    const int h = lane >> 5, l31 = lane & 31;
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) stg[(i * 32 + acc_row(e, h)) * (32 * NJ) + j * 32 + l31] = acc[i * NJ + j][e] * mul;
+}
+// out: the tile's row 0 at this lane's column (4 * (lane % (8 NJ)) of the tile); tile row r is global row r0 + r, stored if < rlim
+template <int NI, int NJ>
+__device__ __forceinline__ void slab_tile_store(const float* stg, float* out, int ld, int r0, int rlim, bool col_ok, int plain, int lane) {
+    constexpr int W = 32 * NJ, LPR = W / 4, RPI = 64 / LPR;      // floats per row, lanes per row, rows per store instruction
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+    for (int it = 0; it < 32 * NI / RPI; ++it) {
+        const int row = it * RPI + lane / LPR;
+        const f32x4v v = *reinterpret_cast<const f32x4v*>(stg + row * W + 4 * (lane % LPR));
+        if (r0 + row < rlim && col_ok) store_out_f32x4(out + (size_t)(r0 + row) * ld, v, plain);
+    }
+}
 
 template <int TA, int TB, int TM>
 __global__ __launch_bounds__(256) void gemm_f32(GemmArgs g) {
@@ -624,16 +688,8 @@ __global__ __launch_bounds__(256) void gemm_f32(GemmArgs g) {
     const int wm = wave >> 1, wn = wave & 1;
     const int h = lane >> 5, l31 = lane & 31;
     const int m0 = blockIdx.y * GBM, n0 = blockIdx.x * GBN;
-    int kb = blockIdx.z * g.k_chunk, ke = min(g.K, kb + g.k_chunk);
-    if (g.nsplit1 > 0) {                                  // modality-aligned split-K
-        const int z = blockIdx.z;
-        if (z < g.nsplit1) ke = min(g.k_switch, kb + g.k_chunk);
-        else { kb = g.k_switch + (z - g.nsplit1) * g.k_chunk; ke = min(g.K, kb + g.k_chunk); }
-    }
-
-    auto kvalid = [&](int k) -> bool {
-        return k < g.k_switch ? (k < g.k_valid1) : (k - g.k_switch < g.k_valid2);
-    };
+    const KRange kr = splitk_range(g, blockIdx.z);
+    const int kb = kr.kb, ke = kr.ke;
 
     f32x16 acc[TM][TM];
 #pragma unroll
@@ -672,19 +728,9 @@ __global__ __launch_bounds__(256) void gemm_f32(GemmArgs g) {
     // TB == 1: the gathered row id of every reduction row of this split is staged in LDS once.
     // Loading it per chunk made each chunk pay a dependent index->row round trip (~2 us x 64 chunks
     // on the cfg2 dW GEMM).  -1 = masked row.
-    __shared__ int kid[GKIDS];
-    const bool use_kid = TB == 1 && (ke - kb) <= GKIDS;
-    if (use_kid) {
-        for (int i = tid; i < ke - kb; i += 256) {
-            int k = kb + i, rid = -1;
-            if (kvalid(k)) {
-                if (k < g.k_switch) rid = g.k_rows ? (int)g.k_rows[k] : k;
-                else { int kl = k - g.k_switch; rid = g.k_rows2 ? (int)g.k_rows2[kl] : kl; }
-            }
-            kid[i] = rid;
-        }
-        __syncthreads();
-    }
+    __shared__ int kid[KIDS];
+    const bool use_kid = TB == 1 && (ke - kb) <= KIDS;
+    if (use_kid) fill_row_ids<256>(g, kid, kb, ke, tid);
 
     auto gload = [&](int k0) {
 #pragma unroll
@@ -695,7 +741,7 @@ __global__ __launch_bounds__(256) void gemm_f32(GemmArgs g) {
                 f32x4v v = a_src[q] ? load4_guard(a_src[q] + k, ke - k, vecA) : f32x4v{0.f, 0.f, 0.f, 0.f};
                 if (TB == 1) {                   // reduction index is a dZ^T column: mask padding
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) if (!kvalid(k + j)) v[j] = 0.f;
+                    for (int j = 0; j < 4; ++j) if (!kvalid(g, k + j)) v[j] = 0.f;
                 }
                 areg[q] = v;
             } else {                             // piece = (k row, 4 consecutive m)
@@ -715,7 +761,7 @@ __global__ __launch_bounds__(256) void gemm_f32(GemmArgs g) {
                         const bool s2 = k >= g.k_switch;
                         v = load4_guard((s2 ? g.B2 : g.B) + (size_t)rid * (s2 ? g.ldb2 : g.ldb) + nn, g.N - nn, s2 ? vecB2 : vecB);
                     }
-                } else if (k < ke && kvalid(k)) {
+                } else if (k < ke && kvalid(g, k)) {
                     if (k < g.k_switch) {
                         int64_t rid = g.k_rows ? g.k_rows[k] : (int64_t)k;
                         v = load4_guard(g.B + (size_t)rid * g.ldb + nn, g.N - nn, vecB);
@@ -761,27 +807,22 @@ __global__ __launch_bounds__(256) void gemm_f32(GemmArgs g) {
             // products on the bf16 matrix pipe (umlh_f32_x3): lane half h takes k = 8h .. 8h+7 of the chunk in both operands (8 scalar
             // LDS reads per tile, as many as the fp32 form's), splits them three ways in registers and issues six
             // v_mfma_f32_32x32x16_bf16 per output tile (192 cycles) where the fp32 form issues eight 64-cycle MFMAs
-            typedef unsigned int u32x4s __attribute__((ext_vector_type(4)));
-            typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
             u32x4s fa[TM][3], fb[TM][3];
 #pragma unroll
             for (int t = 0; t < TM; ++t) {
 #pragma unroll
                 for (int pr = 0; pr < 4; ++pr) {
-                    const Split3 sa = split3_pair(As[(8 * h + 2 * pr) * GLD + wm * 32 * TM + t * 32 + l31], As[(8 * h + 2 * pr + 1) * GLD + wm * 32 * TM + t * 32 + l31]);
-                    fa[t][0][pr] = sa.hi; fa[t][1][pr] = sa.mid; fa[t][2][pr] = sa.lo;
-                    const Split3 sb = split3_pair(Bs[(8 * h + 2 * pr) * GLD + wn * 32 * TM + t * 32 + l31], Bs[(8 * h + 2 * pr + 1) * GLD + wn * 32 * TM + t * 32 + l31]);
-                    fb[t][0][pr] = sb.hi; fb[t][1][pr] = sb.mid; fb[t][2][pr] = sb.lo;
+                    split3_into(fa[t], pr, As[(8 * h + 2 * pr) * GLD + wm * 32 * TM + t * 32 + l31], As[(8 * h + 2 * pr + 1) * GLD + wm * 32 * TM + t * 32 + l31]);
+                    split3_into(fb[t], pr, Bs[(8 * h + 2 * pr) * GLD + wn * 32 * TM + t * 32 + l31], Bs[(8 * h + 2 * pr + 1) * GLD + wn * 32 * TM + t * 32 + l31]);
                 }
             }
-            constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};         // lo*hi, hi*lo, mid*mid, mid*hi, hi*mid, hi*hi
 #pragma unroll
             for (int pd = 0; pd < 6; ++pd)
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
                     for (int j = 0; j < TM; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[i][PA[pd]]), __builtin_bit_cast(bf16x8, fb[j][PB[pd]]), acc[i][j], 0, 0, 0);
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[i][X3_ORDER[pd][0]]), __builtin_bit_cast(bf16x8, fb[j][X3_ORDER[pd][1]]), acc[i][j], 0, 0, 0);
             return;
         }
 #pragma unroll
@@ -846,8 +887,7 @@ __global__ __launch_bounds__(256) void gemm_f32(GemmArgs g) {
 // --------------------------------------------------------------------------- //
 constexpr int DWKC = 32;                                  // reduction rows per staged chunk (one 128-B line of a dZ^T row)
 constexpr int DWLD = DWKC + 4;                            // floats per LDS row (b128 reads of 16 lanes cover all 64 banks)
-constexpr int DWKIDS = 4096;                              // reduction rows per split whose row ids fit the LDS table (16 KB; round 3: was 2048, which sent cfg3's dW_head -- 2 splits of 4096 rows -- to the 64x64 gemm_f32 tile: 812 us instead of ~300)
-constexpr size_t DW_SMEM = sizeof(float) * 4 * 128 * DWLD + sizeof(int) * DWKIDS;
+constexpr size_t DW_SMEM = sizeof(float) * 4 * 128 * DWLD + sizeof(int) * KIDS;
 __global__ __launch_bounds__(256) void dw_f32(GemmArgs g) {
     extern __shared__ __attribute__((aligned(16))) float dw_smem[];
     float* const As2 = dw_smem;                           // [2][128 * DWLD]
@@ -860,22 +900,9 @@ __global__ __launch_bounds__(256) void dw_f32(GemmArgs g) {
     // index fastest, the 4 column tiles sharing a dZ^T row block sat on 4 different XCDs)
     const int nsplit = (int)g.slab_count, z = blockIdx.x % nsplit, tile = blockIdx.x / nsplit, ntx = (g.N + 127) / 128;
     const int m0 = (tile / ntx) * 128, n0 = (tile % ntx) * 128;
-    int kb = z * g.k_chunk, ke = min(g.K, kb + g.k_chunk);
-    if (g.nsplit1 > 0) {                                  // modality-aligned split-K
-        if (z < g.nsplit1) ke = min(g.k_switch, kb + g.k_chunk);
-        else { kb = g.k_switch + (z - g.nsplit1) * g.k_chunk; ke = min(g.K, kb + g.k_chunk); }
-    }
-    auto kvalid = [&](int k) -> bool { return k < g.k_switch ? (k < g.k_valid1) : (k - g.k_switch < g.k_valid2); };
-    for (int i = tid; i < ke - kb; i += 256) {            // gathered row id of every reduction row of this split; -1 = masked
-        const int k = kb + i;
-        int rid = -1;
-        if (kvalid(k)) {
-            if (k < g.k_switch) rid = g.k_rows ? (int)g.k_rows[k] : k;
-            else { const int kl = k - g.k_switch; rid = g.k_rows2 ? (int)g.k_rows2[kl] : kl; }
-        }
-        kid[i] = rid;
-    }
-    __syncthreads();
+    const KRange kr = splitk_range(g, z);
+    const int kb = kr.kb, ke = kr.ke;
+    fill_row_ids<256>(g, kid, kb, ke, tid);
 
     f32x16 acc[2][2];
 #pragma unroll
@@ -920,11 +947,7 @@ __global__ __launch_bounds__(256) void dw_f32(GemmArgs g) {
     bool av[4];
     auto lstore_masks = [&]() {                           // validity of the 4 reduction indices of the staged A pieces (no branches)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int k = a_k + j;
-            const bool first = k < g.k_switch;
-            av[j] = (k < ke) & ((first ? k : k - g.k_switch) < (first ? g.k_valid1 : g.k_valid2));
-        }
+        for (int j = 0; j < 4; ++j) av[j] = kvalid_before(g, a_k + j, ke);
     };
     auto lstore_piece = [&](int buf, int q) {
         float* As = As2 + buf * 128 * DWLD;
@@ -1001,28 +1024,12 @@ __global__ __launch_bounds__(256) void dw_f32(GemmArgs g) {
     }
     float* out = g.out + (size_t)z * g.slab_stride;
     const float alpha = g.alpha * (g.alpha_ptr ? *g.alpha_ptr : 1.f);
-    // slab tile through the (free: every wave has passed the loop's last barrier) LDS tiles, wave-private [64 rows][64 columns]:
-    // a lane then stores 16 B of one row (4 rows x 256 B per instruction) instead of 64 scattered 4-byte write-through stores
-    // (round 3; the same change took 3 us off fwd_ce_f32).  256-B rows: the ds_write_b32 of a register is 32 consecutive floats
-    // per lane half, the b128 read of 4 rows x 16 quads is conflict-free in its 16-lane groups.
+    // slab tile through the LDS tiles (free: every wave has passed the loop's last barrier), wave-private [64 rows][64 columns]:
+    // 4 rows x 256 B per store instruction (the same change took 3 us off fwd_ce_f32)
     float* stg = dw_smem + wave * (64 * 64);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) stg[(i * 32 + acc_row(e, h)) * 64 + j * 32 + l31] = acc[i][j][e] * alpha;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    slab_tile_stage<2, 2>(stg, &acc[0][0], alpha, lane);
     const int nq = n0 + wn * 64 + 4 * (lane & 15);
-#pragma unroll
-    for (int it = 0; it < 16; ++it) {
-        const int row = it * 4 + (lane >> 4);
-        const int m = m0 + wm * 64 + row;
-        const f32x4v v = *reinterpret_cast<const f32x4v*>(stg + row * 64 + 4 * (lane & 15));
-        if (m < g.M && nq < g.N) store_out_f32x4(out + (size_t)m * g.ldo + nq, v, g.plain);
-    }
+    slab_tile_store<2, 2>(stg, out + nq, g.ldo, m0 + wm * 64, g.M, nq < g.N, g.plain, lane);
 }
 
 // --------------------------------------------------------------------------- //
@@ -1048,10 +1055,9 @@ __global__ __launch_bounds__(256) void dw_f32(GemmArgs g) {
 //     chunk c multiplies, chunk c+2 is requested right after -- a barrier per chunk.
 // --------------------------------------------------------------------------- //
 constexpr int X3_ARS = 64, X3_APL = 128 * X3_ARS, X3_BPL = 32 * 256, X3_BUF = 3 * X3_APL + 3 * X3_BPL;   // bytes per A row / A plane / B plane / buffer
-constexpr size_t DW_SMEM_X3 = 2 * (size_t)X3_BUF + sizeof(int) * DWKIDS;
+constexpr size_t DW_SMEM_X3 = 2 * (size_t)X3_BUF + sizeof(int) * KIDS;
 __global__ __launch_bounds__(512) void dw_f32x3(GemmArgs g) {
     typedef unsigned int u32x2s __attribute__((ext_vector_type(2)));
-    typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
     typedef short s16x4 __attribute__((ext_vector_type(4)));
     typedef short s16x8 __attribute__((ext_vector_type(8)));
     extern __shared__ __attribute__((aligned(16))) float dw_smem[];
@@ -1062,22 +1068,9 @@ __global__ __launch_bounds__(512) void dw_f32x3(GemmArgs g) {
     const int g16 = lane >> 4, q4 = (lane & 15) >> 2, p4 = lane & 3;
     const int nsplit = (int)g.slab_count, z = blockIdx.x % nsplit, tile = blockIdx.x / nsplit, ntx = (g.N + 127) / 128;
     const int m0 = (tile / ntx) * 128, n0 = (tile % ntx) * 128;
-    int kb = z * g.k_chunk, ke = min(g.K, kb + g.k_chunk);
-    if (g.nsplit1 > 0) {                                  // modality-aligned split-K
-        if (z < g.nsplit1) ke = min(g.k_switch, kb + g.k_chunk);
-        else { kb = g.k_switch + (z - g.nsplit1) * g.k_chunk; ke = min(g.K, kb + g.k_chunk); }
-    }
-    auto kvalid = [&](int k) -> bool { return k < g.k_switch ? (k < g.k_valid1) : (k - g.k_switch < g.k_valid2); };
-    for (int i = tid; i < ke - kb; i += 512) {            // gathered row id of every reduction row of this split; -1 = masked
-        const int k = kb + i;
-        int rid = -1;
-        if (kvalid(k)) {
-            if (k < g.k_switch) rid = g.k_rows ? (int)g.k_rows[k] : k;
-            else { const int kl = k - g.k_switch; rid = g.k_rows2 ? (int)g.k_rows2[kl] : kl; }
-        }
-        kid[i] = rid;
-    }
-    __syncthreads();
+    const KRange kr = splitk_range(g, z);
+    const int kb = kr.kb, ke = kr.ke;
+    fill_row_ids<512>(g, kid, kb, ke, tid);
 
     f32x16 acc[2];
 #pragma unroll
@@ -1129,12 +1122,7 @@ __global__ __launch_bounds__(512) void dw_f32x3(GemmArgs g) {
             f32x4v v = areg[q];
             if (!chunk_full) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int k = a_k + j;
-                    const bool first = k < g.k_switch;
-                    const bool ok = (k < ke) & ((first ? k : k - g.k_switch) < (first ? g.k_valid1 : g.k_valid2));
-                    v[j] = ok ? v[j] : 0.f;
-                }
+                for (int j = 0; j < 4; ++j) v[j] = kvalid_before(g, a_k + j, ke) ? v[j] : 0.f;
             }
             const Split3 s0 = split3_pair(v[0], v[1]), s1 = split3_pair(v[2], v[3]);
             unsigned char* d = base + a_wr + 64 * q * X3_ARS;
@@ -1143,7 +1131,6 @@ __global__ __launch_bounds__(512) void dw_f32x3(GemmArgs g) {
             *reinterpret_cast<u32x2s*>(d + 2 * X3_APL) = u32x2s{s0.lo, s1.lo};
         }
         {
-            typedef unsigned int u32x4s __attribute__((ext_vector_type(4)));
             f32x4v v0 = breg[0], v1 = breg[1];
             if (!chunk_full) {
 #pragma unroll
@@ -1185,11 +1172,10 @@ __global__ __launch_bounds__(512) void dw_f32x3(GemmArgs g) {
                 const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
                 B[pl] = __builtin_bit_cast(bf16x8, v);
             }
-            constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};     // lo*hi, hi*lo, mid*mid, mid*hi, hi*mid, hi*hi
 #pragma unroll
             for (int pd = 0; pd < 6; ++pd)
 #pragma unroll
-                for (int i = 0; i < 2; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[i][PA[pd]], B[PB[pd]], acc[i], 0, 0, 0);
+                for (int i = 0; i < 2; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[i][X3_ORDER[pd][0]], B[X3_ORDER[pd][1]], acc[i], 0, 0, 0);
             if (g2 == 0) {
                 if (st1) stage(buf ^ 1);                  // chunk c+1 (in registers) -> the other buffer, under the MFMAs above and the partner wave's
                 if (ld2) gload(k0 + 2 * DWKC);            // ... and the registers are free for chunk c+2: a whole chunk of time to land
@@ -1204,21 +1190,9 @@ __global__ __launch_bounds__(512) void dw_f32x3(GemmArgs g) {
     const float alpha = g.alpha * (g.alpha_ptr ? *g.alpha_ptr : 1.f);
     // slab tile through the (free) LDS, wave-private [64 rows][32 columns]: a lane stores 16 B of one row
     float* stg = dw_smem + wave * (64 * 32);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) stg[(i * 32 + acc_row(e, h)) * 32 + l31] = acc[i][e] * alpha;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    slab_tile_stage<2, 1>(stg, acc, alpha, lane);
     const int nq = n0 + wn * 32 + 4 * (lane & 7);
-#pragma unroll
-    for (int it = 0; it < 8; ++it) {
-        const int row = it * 8 + (lane >> 3);
-        const int m = m0 + wm * 64 + row;
-        const f32x4v v = *reinterpret_cast<const f32x4v*>(stg + row * 32 + 4 * (lane & 7));
-        if (m < g.M && nq < g.N) store_out_f32x4(out + (size_t)m * g.ldo + nq, v, g.plain);
-    }
+    slab_tile_store<2, 1>(stg, out + nq, g.ldo, m0 + wm * 64, g.M, nq < g.N, g.plain, lane);
 }
 
 // --------------------------------------------------------------------------- //
@@ -1457,8 +1431,6 @@ __global__ __launch_bounds__(256) void finalize_kernel(FinalizeArgs f) {
 // shadow of W that the next forward streams (bf16 mode), and (last block) reduce the forward
 // partials to the step's scalars + update the learnable logit scales.
 // --------------------------------------------------------------------------- //
-typedef unsigned int u32x4s __attribute__((ext_vector_type(4)));
-
 // 4 consecutive elements per thread (twice the workgroups of an 8-element split: at C*d = 512 000 that is 500 workgroups
 // = 2 per CU instead of one 4-wave workgroup per CU, and the kernel is bound by bytes in flight, not by arithmetic).
 __global__ __launch_bounds__(256) void head_step_kernel(const float* __restrict__ slabs, int n_slabs, long long slab_stride,
@@ -1725,18 +1697,9 @@ int umlh_f32_fwd_config(int C, int* ctw, int* wc) {
     return 32 * (8 / w);
 }
 
-static size_t fwd_smem_bytes(int ctw, int wc, int mode) {
-    int ws = 8 / wc, cpad = 32 * ctw * wc, ts = 32 * ws;
-    size_t tile = (size_t)2 * KT * (cpad + 4 + ts + 4), stg = (size_t)8 * ctw * 32 * 32;   // (the epilogue's dZ staging aliases the tile buffers)
-    size_t xt2 = mode >= 2 ? (size_t)ts * (16384 / ts + 4) : 0;
-    if (stg > tile) tile = stg;
-    if (xt2 > tile) tile = xt2;
-    return sizeof(float) * (tile + (size_t)(wc * ts * 4 + ws * 4 + 16));
-}
-
 #define FWD_CASE_F(CT, W, F)                                                                        \
     if (ctw == CT && wc == W && mode == F) {                                                        \
-        size_t sm = fwd_smem_bytes(CT, W, F);                                                       \
+        size_t sm = FwdLds<CT, W, F>::BYTES;                                                        \
         if (int e = raise_lds_limit<&fwd_ce_f32<CT, W, F>>((int)sm)) return e;                      \
         FwdArgs c_ = *a; c_.plain = umlh_plain_stores();                                            \
         hipLaunchKernelGGL((fwd_ce_f32<CT, W, F>), dim3(grid), dim3(512), sm, stream, c_);          \
@@ -1763,7 +1726,7 @@ static bool dw_f32_applies(const GemmArgs* g, int ta, int tb) {
     static const bool off = env_int("UMLH_F32_DW", 1) == 0;   // timing comparisons
     if (off || ta != 0 || tb != 1 || g->a_rows || g->epi.on || g->skip) return false;
     if ((long long)g->M * g->N < 8LL * 128 * 128 || g->N < 4 || g->N % 4 || g->lda < 4) return false;
-    if (g->k_chunk > DWKIDS) return false;
+    if (g->k_chunk > KIDS) return false;
     if (g->lda % 4 || g->ldb % 4 || (reinterpret_cast<uintptr_t>(g->A) & 15) || (reinterpret_cast<uintptr_t>(g->B) & 15)) return false;
     if (g->ldo % 4 || g->slab_stride % 4 || (reinterpret_cast<uintptr_t>(g->out) & 15)) return false;      // 16-byte slab stores
     if (g->B2 && (g->ldb2 % 4 || (reinterpret_cast<uintptr_t>(g->B2) & 15))) return false;
