@@ -23,18 +23,30 @@
  *     optional `index` (int64) gathers rows from a device-resident table, which
  *     replaces the DataLoader collate of finetune.py:33-39,165-172.
  *
- * Environment switches read by the library (tuning / analysis; defaults are the measured-fastest settings):
- *   UMLH_WT=0            plain instead of write-through (sc1) stores for what a kernel hands to the next launch
+ * Environment switches read by the library (tuning / analysis; defaults are the measured-fastest settings; the table
+ * tests/_switches.py names the line that reads each one, and a test holds it and this list to the source).
+ * Read when a handle is created or its workspace is sized (umlh_create, umlh_workspace_bytes): a process may create
+ * handles under different settings.
  *   UMLH_BF16_FUSE=2|1|0 bf16 mode, linear head: the whole step as one launch (step_bf16, default) | forward + dW as one
  *                        launch (fwd_dw_bf16) + the update kernel | three launches
  *   UMLH_BF16_FWD2D=1    bf16 mode: the 2-D forward (128-row tiles x 256-class groups, in-launch softmax merge); slower at cfg2
  *   UMLH_BF16_STW=2      bf16 mode: two sample tiles per wave of the 1-D forward
  *   UMLH_MICRO=0         never take the single-launch micro step
- *   UMLH_F32_DW=0        fp32 dW through the generic GEMM instead of dw_f32
- *   UMLH_ENC_GRAPH=0 / UMLH_ENC_FORK=1   encoder plans: no HIP-graph replay / weight-gradient work on a forked branch
+ *   UMLH_STEP_GRID=n     bf16 mode: the one-launch step on n workgroups instead of one per compute unit
+ *   UMLH_STEP_LAZY=1     bf16 mode: every fourth workgroup of the one-launch step leaves its home tiles to whoever needs them
  *   UMLH_FORCE_DP=1      take the data-parallel split step (grad -> all-reduce -> update) with one rank
- *   UMLH_DBG_FWD / UMLH_DBG_DW / UMLH_DBG_MICRO / UMLH_DBG_STEP   in-kernel stamps (scripts/fwd_stamps.py, dw_stamps.py,
- *                        micro_stamps.py, step_timeline.py)
+ *   UMLH_DBG_FWD / UMLH_DBG_DW / UMLH_DBG_STEP   in-kernel stamps (scripts/fwd_stamps.py, dw_stamps.py, step_timeline.py)
+ * Those below are read once per process, at the first call that needs them: another value takes a fresh process.
+ *   UMLH_WT=0            plain instead of write-through (sc1) stores for what a kernel hands to the next launch
+ *   UMLH_F32_X3=0        fp32 mode: products on the fp32 MFMA instead of three-way bf16 splits on the bf16 MFMA
+ *   UMLH_F32_FWD=1       fp32 forward stages W through LDS chunk by chunk instead of streaming its fragment-major shadow
+ *   UMLH_F32_DW=0        fp32 dW through the generic GEMM instead of dw_f32
+ *   UMLH_F32_TM=1|2      fp32 GEMM: force the 64 x 64 | 128 x 128 tile (tuning runs)
+ *   UMLH_ENC_GRAPH=0     encoder plans: no HIP-graph replay
+ *   UMLH_ENC_SPLIT_WGS=n encoder GEMMs: split K until about n workgroups are in flight (default 768)
+ *   UMLH_DBG_MICRO       in-kernel stamps of the micro step (scripts/micro_stamps.py)
+ *   UMLH_DBG_GEMM_STAMPS / UMLH_DBG_GEMM_CALL   analysis builds only, read at every gemm_enc launch: address of a stamp
+ *                        buffer and the index of the launch to stamp
  */
 #ifndef UMLH_H
 #define UMLH_H

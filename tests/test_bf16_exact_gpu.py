@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import _bf16_exact_ref as R
+from _switches import monkeypatch_engine_env
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -28,7 +29,6 @@ VARIANTS = {
     "fuse2": {"UMLH_BF16_FUSE": "2"},                                  # the one-launch step
     "fuse2_grid7": {"UMLH_BF16_FUSE": "2", "UMLH_STEP_GRID": "7"},     # ... on 7 workgroups
 }
-SWITCHES = ("UMLH_BF16_FUSE", "UMLH_BF16_STW", "UMLH_BF16_FWD2D", "UMLH_STEP_GRID", "UMLH_STEP_LAZY", "UMLH_FORCE_DP")
 _ALWAYS = ["fuse0", "fuse1", "fuse2", "fuse2_grid7"]
 
 
@@ -74,10 +74,7 @@ def _batches(s):
 
 def _engine(s, env, monkeypatch):
     import umlh
-    for k in SWITCHES:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
+    monkeypatch_engine_env(monkeypatch, env)
     case, _ = R.case_and_reference(s)
     e = umlh.HeadEngine(s.d_img, s.d, s.C, has_proj=s.two_layer, optimizer="sgd", momentum=0.0, weight_decay=0.0,
                         max_rows_img=s.cap, max_rows_txt=512, precision="bf16", device=DEV)

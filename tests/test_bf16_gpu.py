@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+from _switches import child_env, monkeypatch_engine_env
 from oracle import uml_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -53,9 +54,10 @@ def _rb(x, y, idx=None):
                                                  (384, 397, 40, 0, 50.0, "f"), (1024, 1000, 70, 300, -100.0, "f")])
 def test_bf16_grad_step_vs_oracle_on_rounded_operands(d, C, bi, bt, scale, stw, monkeypatch):
     import umlh
-    monkeypatch.setenv("UMLH_BF16_STW", "1" if stw in ("q", "f") else str(stw))
-    monkeypatch.setenv("UMLH_BF16_FWD2D", "1" if stw == "q" else "0")
-    monkeypatch.setenv("UMLH_BF16_FUSE", "1" if stw == "f" else "0")      # "f": forward and dW as ONE launch (granule-gated dW blocks)
+    monkeypatch_engine_env(monkeypatch, {
+        "UMLH_BF16_STW": "1" if stw in ("q", "f") else str(stw),
+        "UMLH_BF16_FWD2D": "1" if stw == "q" else "0",
+        "UMLH_BF16_FUSE": "1" if stw == "f" else "0"})                    # "f": forward and dW as ONE launch (granule-gated dW blocks)
     rng = np.random.default_rng(d + C)
     xi, yi, xt, yt, w = _case(rng, d, C, 400, 350, scale)
     ii = rng.permutation(400)[:bi] if bi else None
@@ -261,7 +263,7 @@ def test_bf16_single_launch_forward_dw_equals_two_launches_bit_for_bit(monkeypat
     xi, yi, xt, yt, w = _case(rng, d, C, n, 3000, 100.0)
     out = {}
     for mode in ("0", "1", "2"):       # separate launches / forward + dW as one / the whole step (update + scalars too) as one
-        monkeypatch.setenv("UMLH_BF16_FUSE", mode)
+        monkeypatch_engine_env(monkeypatch, {"UMLH_BF16_FUSE": mode})
         e = _engine(w.copy(), 100.0, 1024, 1024, "bf16")
         bi_t, bt_t = _rb(xi, yi), _rb(xt, yt)
         bi_t.feats_bf16, bt_t.feats_bf16 = umlh.to_bf16(bi_t.feats), umlh.to_bf16(bt_t.feats)
@@ -292,7 +294,7 @@ def test_bf16_single_launch_step_optimizers_and_learnable_temperature(opt, learn
     xi, yi, xt, yt, w = _case(rng, d, C, n, 2000, 20.0)
     out = {}
     for mode in ("0", "2"):
-        monkeypatch.setenv("UMLH_BF16_FUSE", mode)
+        monkeypatch_engine_env(monkeypatch, {"UMLH_BF16_FUSE": mode})
         e = umlh.HeadEngine(d, d, C, optimizer=opt, weight_decay=0.01, learnable_temp=learn, max_rows_img=512, max_rows_txt=512,
                             precision="bf16", device=DEV)
         e.w_head.copy_(torch.from_numpy(w)); e.scales.fill_(20.0)
@@ -379,7 +381,7 @@ def test_plain_stores_switch_gives_identical_results(tmp_path):
     script.write_text(_WT_SCRIPT)
     digests = {}
     for wt in ("1", "0"):
-        env = dict(os.environ, UMLH_WT=wt)
+        env = child_env({"UMLH_WT": wt})
         r = subprocess.run([sys.executable, str(script), root], env=env, capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stderr[-2000:]
         digests[wt] = [l for l in r.stdout.splitlines() if l.startswith("DIGEST")][-1]
@@ -440,14 +442,12 @@ def test_bf16_one_launch_step_is_independent_of_grid_width_and_of_who_runs_a_tas
     xi, yi, xt, yt, w = _case(rng, d, C, n, 3000, 100.0)
     out = {}
     for mode in ("0", "2"):
-        monkeypatch.setenv("UMLH_BF16_FUSE", mode)
-        monkeypatch.delenv("UMLH_STEP_GRID", raising=False)
-        monkeypatch.delenv("UMLH_STEP_LAZY", raising=False)
-        monkeypatch.delenv("UMLH_FORCE_DP", raising=False)
+        env = {"UMLH_BF16_FUSE": mode}
         if mode == "2":
-            if "grid24" in variant: monkeypatch.setenv("UMLH_STEP_GRID", "24")
-            if "grid7" in variant: monkeypatch.setenv("UMLH_STEP_GRID", "7")
-            if "lazy" in variant: monkeypatch.setenv("UMLH_STEP_LAZY", "1")
+            if "grid24" in variant: env["UMLH_STEP_GRID"] = "24"
+            if "grid7" in variant: env["UMLH_STEP_GRID"] = "7"
+            if "lazy" in variant: env["UMLH_STEP_LAZY"] = "1"
+        monkeypatch_engine_env(monkeypatch, env)
         e = _engine(w.copy(), 100.0, 1024, 1024, "bf16")
         bi_t, bt_t = _rb(xi, yi), _rb(xt, yt)
         bi_t.feats_bf16, bt_t.feats_bf16 = umlh.to_bf16(bi_t.feats), umlh.to_bf16(bt_t.feats)

@@ -7,7 +7,7 @@ UMLH_F32_DW (they are read once per process), one after another.  Every output b
 sentinel and every slab buffer is one slab longer than the launch needs and filled with NaN: a write outside the [M, N] window
 lands on a sentinel inside the allocation, and the parent checks that every element outside the window is bit-unchanged.
 
-The SHA-256 digest of every (case, setting) window is also compared with the one that scripts/make_f32_digests.py recorded in
+The SHA-256 digest of every (case, setting) window is also compared with the one that scripts/make_step_digests.py recorded in
 tests/golden/f32_path_digests.json from an earlier build (the table's "recorded_from"): the kernel paths keep their bits across
 commits, not only their accuracy."""
 import hashlib
@@ -21,6 +21,7 @@ import pytest
 
 from _gemm_ref import (CASES, ENVS, SENTINEL_BITS, X3_KERNELS, case_ref, gemm_err, meets_criterion, predict_kernel,
                        slab_count)
+from _switches import child_env
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "unpaired-multimodal-learning_amd")
@@ -66,10 +67,8 @@ def _run_children(tmp_path):
     for name, env_over in ENVS.items():             # one after another; the first failure ends the test
         d = tmp_path / name
         d.mkdir()
-        env = {k: v for k, v in os.environ.items() if k not in ("UMLH_F32_X3", "UMLH_F32_TM", "UMLH_F32_DW")}
-        env.update(env_over)
-        r = subprocess.run([sys.executable, str(script), os.path.dirname(os.path.abspath(__file__)), PKG, str(d)], env=env,
-                           capture_output=True, text=True, timeout=300)
+        r = subprocess.run([sys.executable, str(script), os.path.dirname(os.path.abspath(__file__)), PKG, str(d)],
+                           env=child_env(env_over), capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, (name, r.returncode, r.stdout[-1000:], r.stderr[-3000:])
         dirs[name] = d
     return dirs
@@ -91,7 +90,7 @@ def window_digests(dirs):
 
 
 def _recorded_digests():
-    """The same digests of the build that tests/golden/f32_path_digests.json was recorded from (scripts/make_f32_digests.py)."""
+    """The same digests of the build that tests/golden/f32_path_digests.json was recorded from (scripts/make_step_digests.py)."""
     with open(os.path.join(ROOT, "tests", "golden", "f32_path_digests.json")) as f:
         return json.load(f)["gemm"]
 

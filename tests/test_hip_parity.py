@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from _switches import child_env
 from conftest import load_golden
 from oracle import uml_oracle as O
 
@@ -525,7 +526,7 @@ def test_fp32_forward_streamed_weights_equals_lds_staged_forward_bit_for_bit(tmp
     script.write_text(_F32_FWD_SCRIPT)
     digests = {}
     for mode in ("1", "2"):
-        env = dict(os.environ, UMLH_F32_FWD=mode, UMLH_F32_X3="0")      # (both on the fp32 MFMA: the x3 products are a different rounding)
+        env = child_env({"UMLH_F32_FWD": mode, "UMLH_F32_X3": "0"})     # (both on the fp32 MFMA: the x3 products are a different rounding)
         r = subprocess.run([sys.executable, str(script), root], env=env, capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stderr[-2000:]
         digests[mode] = [l for l in r.stdout.splitlines() if l.startswith("DIGEST")][-1]
@@ -545,7 +546,7 @@ def test_fp32_mode_on_the_bf16_matrix_pipe_matches_the_fp32_mfma_path(tmp_path):
     script.write_text(_F32_FWD_SCRIPT)
     vals = {}
     for x3 in ("0", "1"):
-        env = dict(os.environ, UMLH_F32_X3=x3)
+        env = child_env({"UMLH_F32_X3": x3})
         out = tmp_path / f"vals_{x3}.npy"
         r = subprocess.run([sys.executable, str(script), root, str(out)], env=env, capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stderr[-2000:]

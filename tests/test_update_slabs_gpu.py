@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+from _switches import monkeypatch_engine_env
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
@@ -108,9 +110,7 @@ def test_slab_sum_order_bit_for_bit_on_exact_partials(n_img, n_txt, path, monkey
     """Slab counts on both sides of the group of 8 loads (1+1 ... 63+1, image only, text only).  The fp32 engine plans its
     own split of the same row counts (16-row quantum, 64-row minimum: 4+4, 8+4, 28+4, 32+4, 32+32, 46+8 with a short last
     image slab, 63+1, 20+0, 0+12), restated here as well."""
-    monkeypatch.setenv("UMLH_BF16_FUSE", "0" if path == "launch_per_kernel" else "2")
-    for k in ("UMLH_STEP_GRID", "UMLH_STEP_LAZY", "UMLH_FORCE_DP"):
-        monkeypatch.delenv(k, raising=False)
+    monkeypatch_engine_env(monkeypatch, {"UMLH_BF16_FUSE": "0" if path == "launch_per_kernel" else "2"})
     r0, r1 = 256 * n_img, 256 * n_txt
     plan = _plan_splits(r0, r1, 64, 16, 64) if path == "fp32" else _plan_splits(r0, r1, 64, 256, 256)
     if path != "fp32":
@@ -145,12 +145,11 @@ def test_update_slices_under_stealing_equal_launch_per_kernel_step(variant, monk
     sizes = [(4096, 4096), (4096, 1000), (3000, 4096), (4096, 0), (0, 4096), (4096, 4096)]
     out = {}
     for mode in ("0", "2"):
-        monkeypatch.setenv("UMLH_BF16_FUSE", mode)
-        for k in ("UMLH_STEP_GRID", "UMLH_STEP_LAZY", "UMLH_FORCE_DP"):
-            monkeypatch.delenv(k, raising=False)
+        env = {"UMLH_BF16_FUSE": mode}
         if mode == "2":
-            if "grid3" in variant: monkeypatch.setenv("UMLH_STEP_GRID", "3")
-            if "lazy" in variant: monkeypatch.setenv("UMLH_STEP_LAZY", "1")
+            if "grid3" in variant: env["UMLH_STEP_GRID"] = "3"
+            if "lazy" in variant: env["UMLH_STEP_LAZY"] = "1"
+        monkeypatch_engine_env(monkeypatch, env)
         e = umlh.HeadEngine(d, d, Cn, optimizer="adamw", weight_decay=0.01, max_rows_img=4096, max_rows_txt=4096,
                             precision="bf16", device=DEV)
         e.w_head.copy_(torch.from_numpy(w))
